@@ -9,7 +9,7 @@
   N > 1    : `value` is WEAK scaling of independent frames -- every rank optimises its own 4096x4096 frame (frame
              index = rank) with no data-path collective; RCCL only carries the barrier and the gather of the per-image
              result records.  value = N * pixels * steps / max-over-ranks(time).
-  batch    : for every N, additionally BASELINE.json configs[3] -- 256 synthetic 1920x1080 frames split over the N ranks
+  batch    : (--full) for every N, additionally BASELINE.json configs[3] -- 256 synthetic 1920x1080 frames split over the N ranks
              with pngloss_amd.shard.contiguous_partition, one device-resident batch per rank; reported under the `batch`
              key (whole-job Mpixels/s, per-rank engine ms, reference digests of ALL 256 frames checked) and, as `batch_value`, at the
              top level of the line for every N.  This is the image-batch (strong) scaling north_star asks about; it is not part of `value`.  One GPU runs one image per CU, so
@@ -17,6 +17,11 @@
              4096 frames in all at N = 8) is the leg whose rate can scale with N.
   engines  : the library picks the row engine per batch (pngloss_hip_last_engine_info): few large images -> segment-parallel
              (the whole GPU on one image), batches -> one workgroup per image.
+
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs when --dump-outputs DIR is given and prints the
+line: the headline and the roofline of the timed steps.  Everything else -- the PCIe transfers, the reference digest check of the last
+step (`bit_exact_vs_reference_digest`), the write side, cpu_baseline, the batch legs, configs[2], configs[4] and the read side -- runs
+with --full only.
 
 Prints ONE JSON line on rank 0.  `roofline` prices the dominant kernel (the row engine) against HBM with the
 ALGORITHMIC traffic of SURVEY.md section 8(d): 8 bytes per RGBA8 pixel (read 4 + write 4; the H filter bytes are
@@ -68,6 +73,21 @@ def profile_stamp(name):
     except OSError:
         pass
     return out
+
+
+DUMP_ROWS, DUMP_SEED = 512, 20250   # --dump-outputs: 512 of the 4096 output rows (32 MiB as float32), the same rows in every run
+
+
+def dump_outputs(dirname, out, filt):
+    """--dump-outputs: what the last timed step handed back, as float32 / float64 .npy files under `dirname` (32 MiB in all).  The whole
+    output frame (4096x4096x4 bytes) would be 256 MiB as float32: `pixels_sample` holds a fixed, seeded choice of DUMP_ROWS of its rows
+    in full, `pixels_row_sums` every row's per-channel sums, `filters` every row's PNG filter ID."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(out.shape[0], DUMP_ROWS, replace=False))
+    np.save(os.path.join(dirname, "pixels_sample.npy"), out[rows].astype(np.float32))
+    np.save(os.path.join(dirname, "pixels_row_sums.npy"), out.sum(axis=1, dtype=np.float64))
+    np.save(os.path.join(dirname, "filters.npy"), filt.astype(np.float32))
 
 
 def _ref_worker(frame_index):
@@ -156,7 +176,7 @@ def cpu_all_cores():
                 model = ln.split(":", 1)[1].strip(); break
     except OSError:
         pass
-    ctxm = mp.get_context("fork")
+    ctxm = mp.get_context("spawn")       # (not fork: this process holds a HIP context, which forked workers would inherit)
     curve = []
     for n in sorted({1, min(8, nmax), min(64, nmax), nmax}):
         with ctxm.Pool(n) as pool:
@@ -235,7 +255,7 @@ def engine_kernels():
         pass
     if out:
         out["static"] = True
-        out["source"] = "profiles/%s (a committed rocprofv3 --kernel-trace --stats run of `bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-batch --no-sweep` on the builder's GPU box: NOT measured by this invocation)" % KERNEL_STATS
+        out["source"] = "profiles/%s (a committed rocprofv3 --kernel-trace --stats run of `bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-batch --no-sweep` on an MI355X: NOT measured by this invocation)" % KERNEL_STATS
     return out
 
 
@@ -529,11 +549,17 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="besides the headline, run every other leg: PCIe transfers, the reference digest check of the last step, "
+                                                        "the write side, cpu_baseline, the batch legs, the configs[2] suite batch, the configs[4] sweep and the read side "
+                                                        "(the --no-* switches below leave legs of a --full run out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last step computed to DIR/*.npy: a fixed, seeded sample of "
+                                                          "rank 0's output rows, per-row channel sums of the whole output, and the per-row filter IDs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-batch", action="store_true", help="skip the configs[3] batch leg and the saturating batch leg")
     ap.add_argument("--no-cpu-full-frame", action="store_true", help="cpu_baseline: only the 4096x1024 strip, not the full 4096x4096 frame (the full frame is ~18 s of ONE host core on an otherwise idle host)")
     ap.add_argument("--no-sweep", action="store_true", help="skip the configs[4] sweep (8192x8192, 12 points) and the configs[2] suite batch (rank 0, N = 1 only)")
     args = ap.parse_args()
+    full = args.full
 
     import numpy as np
     import torch
@@ -578,14 +604,15 @@ def main():
         engine_info.update(ctx.engine_info(0))
         return ctx.engine_ms, ctx.total_ms
 
-    # PCIe legs, reported separately and never part of `value` (inputs are resident before the timed region)
-    pinned = torch.from_numpy(frame).pin_memory()
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-    scratch = torch.empty_like(src)
-    ev[0].record(); scratch.copy_(pinned, non_blocking=True); ev[1].record(); pinned.copy_(scratch, non_blocking=True); ev[2].record()
-    torch.cuda.synchronize()
-    h2d_ms, d2h_ms = ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
-    del scratch
+    # PCIe legs (--full), reported separately and never part of `value` (inputs are resident before the timed region)
+    if full:
+        pinned = torch.from_numpy(frame).pin_memory()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        scratch = torch.empty_like(src)
+        ev[0].record(); scratch.copy_(pinned, non_blocking=True); ev[1].record(); pinned.copy_(scratch, non_blocking=True); ev[2].record()
+        torch.cuda.synchronize()
+        h2d_ms, d2h_ms = ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
+        del scratch
 
     for i in range(args.warmup):
         step(i)
@@ -606,11 +633,16 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed_max = float(t.item())
 
-    # ---- correctness of what was just timed: digests of the last step, gathered over ranks ----
-    out_last = work[nrun - 1].cpu().numpy()
-    filt_last = filt[nrun - 1].cpu().numpy()
-    rec = [dict(index=rank, out="%016x" % P.fnv1a64(out_last, P.SURVEY_FNV_BASIS),
-                filters="%016x" % P.fnv1a64(filt_last, P.SURVEY_FNV_BASIS), engine_ms=sum(engine_ms) / len(engine_ms))]
+    # ---- what the last step computed: its outputs for --dump-outputs (rank 0); with --full also the digests of that step, gathered over ranks
+    #      and checked against the reference's ----
+    rec = [dict(index=rank, engine_ms=sum(engine_ms) / len(engine_ms))]
+    if full or (args.dump_outputs and rank == 0):
+        out_last = work[nrun - 1].cpu().numpy()
+        filt_last = filt[nrun - 1].cpu().numpy()
+        if full:
+            rec[0].update(out="%016x" % P.fnv1a64(out_last, P.SURVEY_FNV_BASIS), filters="%016x" % P.fnv1a64(filt_last, P.SURVEY_FNV_BASIS))
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, out_last, filt_last)
     try:
         records = S.gather_records(rec)
     except Exception as exc:          # never lose the measurement to a failed record gather
@@ -621,7 +653,7 @@ def main():
     #      the timed headline steps and the GPU batch legs, and this process waits for it (round 5 ran it beside the batch legs, whose launch thread, clones and uploads
     #      kept the host busy: the ratio then depended on what else bench.py happened to be doing -- the advisor's finding) ----
     full_ff = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_cpu_full_frame:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_cpu_full_frame:
         import multiprocessing as mp
         mpc = mp.get_context("spawn")       # (not fork: this process holds a HIP context)
         full_q = mpc.Queue()
@@ -638,7 +670,7 @@ def main():
     batch = None
     batch_sat = None
     shares = None
-    if not args.no_batch:
+    if full and not args.no_batch:
         del work, filt
         torch.cuda.empty_cache()
         bdt, beng, brecs = run_batch(P, S, torch, lambda: batch_ctx(P, local_rank), rank, world, local_rank, barrier)
@@ -670,9 +702,6 @@ def main():
                 shares = {"error": repr(exc)}
 
     if rank == 0:
-        golden = json.load(open(os.path.join(ROOT, "tests", "golden", "digests.json")))
-        g = [e for e in golden["synthetic"] if e["width"] == W and e["height"] == H and e["strength"] == STRENGTH][0]
-        bit_exact = records[0]["out"] == g["out"] and records[0]["filters"] == g["filters"]
         px = W * H
         value = world * px * args.steps / elapsed_max / 1e6
         eng_ms = sum(r["engine_ms"] for r in records) / len(records)
@@ -691,7 +720,6 @@ def main():
                                    "(Appendix B generator mode 0, frame=rank), strength 19, bleed 2, "
                                    "row_filters requested; device-resident in, device-resident out",
                        "images_per_gpu": 1, "parallelism": f"image-parallel x{world}, no data-path collective"},
-            "bit_exact_vs_reference_digest": bool(bit_exact),
             "roofline": {"bound": "hbm", "kernel": "row engine: " + str(engine_info.get("engine")) + (" (four launches per row attempt: seg_k_ctl [control of this attempt + validation of the attempt before, side by side], seg_k_enum, seg_k_chain, seg_k_replay)" if engine_info.get("engine") == "segment-parallel" else " (pl_engine)"),
                          "achieved": round(achieved, 6), "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
@@ -719,10 +747,14 @@ def main():
         line["static_profile_head"] = stamps[0]["head"]
         if line["static_profiles"]["stale"]:
             print("bench.py: WARNING: static profile blocks come from other sources than this tree: %s" % ", ".join(line["static_profiles"]["stale"]), file=sys.stderr)
-        line["transfers"] = {"h2d_ms": round(h2d_ms, 3), "d2h_ms": round(d2h_ms, 3), "bytes_each_way": W * H * 4,
-                             "note": "pinned 64 MiB frame over PCIe, outside the timed region; with both legs one step "
-                                     "would take %.1f ms" % (elapsed_max / args.steps * 1e3 + h2d_ms + d2h_ms)}
-        if world == 1 and not args.no_cpu_baseline:
+        if full:
+            golden = json.load(open(os.path.join(ROOT, "tests", "golden", "digests.json")))
+            g = [e for e in golden["synthetic"] if e["width"] == W and e["height"] == H and e["strength"] == STRENGTH][0]
+            line["bit_exact_vs_reference_digest"] = records[0]["out"] == g["out"] and records[0]["filters"] == g["filters"]
+            line["transfers"] = {"h2d_ms": round(h2d_ms, 3), "d2h_ms": round(d2h_ms, 3), "bytes_each_way": W * H * 4,
+                                 "note": "pinned 64 MiB frame over PCIe, outside the timed region; with both legs one step "
+                                         "would take %.1f ms" % (elapsed_max / args.steps * 1e3 + h2d_ms + d2h_ms)}
+        if full and world == 1 and not args.no_cpu_baseline:
             # the write side of the same frame, outside the timed region: scanline filtering + deflate on
             # the device; reported next to the headline, never part of `value`
             try:
@@ -751,7 +783,7 @@ def main():
                 except Exception as exc:          # informational only
                     line["cpu_baseline"]["full_frame"] = {"error": repr(exc)}
             line["speedup_vs_build_container_reference"] = round(value / BUILD_CONTAINER_REFERENCE_MPX, 2)
-        if world == 1 and not args.no_sweep:
+        if full and world == 1 and not args.no_sweep:
             for key, fn in (("suite_batch", run_suite_batch), ("sweep_8192", run_sweep_8192)):
                 try:
                     line[key] = fn(P, torch, lambda: batch_ctx(P, local_rank), golden)

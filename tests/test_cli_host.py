@@ -1,8 +1,13 @@
 """CPU tests of the C host side of the command line tool (no GPU compute):
   * our rwpng.c (PNG <-> RGBA8, explicit row filters) against the reference's rwpng.c on PNGs of every colour type --
-    both compiled into the same tiny driver (tests/c/rwpng_copy.c), outputs must be byte-identical;
-  * the option handling / exit codes of pngloss_amd/cli/pngloss against the reference CLI for argument errors."""
+    both compiled into the same tiny driver (tests/c/rwpng_copy.c; the reference's build is oracle/_ref/rwpng_copy_ref),
+    outputs must be byte-identical;
+  * the option handling / exit codes of pngloss_amd/cli/pngloss against the reference CLI for argument errors.
+Where oracle/_ref is not built, both compare against what the reference's builds gave on the same inputs, committed as
+tests/golden/rwpng_ref.npz and tests/golden/cli_errors_ref.json (tests/golden/make_ref_vectors.py)."""
+import hashlib
 import io
+import json
 import os
 import subprocess
 
@@ -14,8 +19,13 @@ from tests import util as U
 CLI = os.path.join(U.ROOT, "pngloss_amd", "cli")
 PNG_INC = "/opt/conda/include"
 PNG_LIB = "/lib/x86_64-linux-gnu/libpng16.so.16"
-REF_SRC = "/root/reference/src"
+REF_RWPNG = os.path.join(U.ROOT, "oracle", "_ref", "rwpng_copy_ref")
 REF_CLI = os.path.join(U.ROOT, "oracle", "_ref", "pngloss_ref_cli")
+#: argument errors whose exit codes and first stderr line must match the reference CLI's
+CLI_ERROR_ARGS = [[], ["-s", "300", "x.png"], ["-b", "0", "x.png"], ["-b", "40000", "x.png"], ["-s", "abc", "x.png"],
+                  ["-o", "a.png", "-o", "b.png", "x.png"], ["--ext", "e.png", "-o", "a.png", "x.png"],
+                  ["-o", "a.png", "x.png", "y.png"], ["-o", "-", "x.png", "y.png"], ["--bogus"],
+                  ["-f", "/nonexistent/dir/file.png"], ["-V"]]
 have_png = os.path.exists(os.path.join(PNG_INC, "png.h")) and os.path.exists(PNG_LIB)
 pytestmark = pytest.mark.skipif(not have_png, reason="libpng headers/runtime not found on this box")
 
@@ -26,12 +36,7 @@ def drivers(tmp_path_factory):
     ours = str(d / "copy_ours")
     subprocess.run(["gcc", "-O1", "-std=gnu11", "-w", "-I" + PNG_INC, "-I" + CLI, "-o", ours,
                     os.path.join(U.ROOT, "tests", "c", "rwpng_copy.c"), os.path.join(CLI, "png_bridge.c"), PNG_LIB, "-lz", "-lm"], check=True)
-    ref = None
-    if os.path.exists(os.path.join(REF_SRC, "rwpng.c")):
-        ref = str(d / "copy_ref")
-        subprocess.run(["gcc", "-O1", "-std=gnu11", "-w", '-DRWPNG_HEADER="rwpng.h"', "-I" + PNG_INC, "-I" + REF_SRC, "-o", ref,
-                        os.path.join(U.ROOT, "tests", "c", "rwpng_copy.c"), os.path.join(REF_SRC, "rwpng.c"), PNG_LIB, "-lz", "-lm"], check=True)
-    return ours, ref, d
+    return ours, (REF_RWPNG if os.path.exists(REF_RWPNG) else None), d
 
 
 def _samples(d):
@@ -79,18 +84,33 @@ def test_our_rwpng_decodes_like_pil_and_reencodes_losslessly(drivers):
                 assert np.array_equal(got, want), (src, policy)
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_SRC, "rwpng.c")), reason="needs /root/reference (build container)")
 def test_our_rwpng_writes_the_same_bytes_as_the_reference_rwpng(drivers):
+    """Live against oracle/_ref/rwpng_copy_ref where it is built; everywhere against the reference's outputs on the committed inputs."""
     ours, ref, d = drivers
-    for src in _samples(d):
-        for policy in (-1, 0, 1, 2, 3, 4, 5):
-            for strip in (0, 1):
-                a, b = src[:-4] + ".a.png", src[:-4] + ".b.png"
-                ra = subprocess.run([ours, src, a, str(policy), str(strip)], capture_output=True, text=True)
-                rb = subprocess.run([ref, src, b, str(policy), str(strip)], capture_output=True, text=True)
-                assert ra.returncode == rb.returncode == 0, (src, ra.stderr, rb.stderr)
-                assert ra.stdout == rb.stdout, (src, policy, strip, ra.stdout, rb.stdout)
-                assert open(a, "rb").read() == open(b, "rb").read(), (src, policy, strip)
+    if ref is not None:
+        for src in _samples(d):
+            for policy in (-1, 0, 1, 2, 3, 4, 5):
+                for strip in (0, 1):
+                    a, b = src[:-4] + ".a.png", src[:-4] + ".b.png"
+                    ra = subprocess.run([ours, src, a, str(policy), str(strip)], capture_output=True, text=True)
+                    rb = subprocess.run([ref, src, b, str(policy), str(strip)], capture_output=True, text=True)
+                    assert ra.returncode == rb.returncode == 0, (src, ra.stderr, rb.stderr)
+                    assert ra.stdout == rb.stdout, (src, policy, strip, ra.stdout, rb.stdout)
+                    assert open(a, "rb").read() == open(b, "rb").read(), (src, policy, strip)
+    g = U.load_npz("rwpng_ref.npz")
+    want = json.loads(bytes(g["expected.json"]).decode())
+    stored = d / "stored"
+    stored.mkdir()
+    for name, runs in want.items():
+        src = str(stored / name)
+        with open(src, "wb") as fh:
+            fh.write(bytes(g[name]))
+        for r in runs:
+            a = src[:-4] + ".a.png"
+            ra = subprocess.run([ours, src, a, str(r["policy"]), str(r["strip"])], capture_output=True, text=True)
+            assert ra.returncode == 0, (name, ra.stderr)
+            assert ra.stdout == r["stdout"], (name, r, ra.stdout)
+            assert hashlib.sha256(open(a, "rb").read()).hexdigest() == r["sha256"], (name, r)
 
 
 def _build_cli():
@@ -100,18 +120,21 @@ def _build_cli():
     return exe
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CLI), reason="oracle/_ref/pngloss_ref_cli not built")
-@pytest.mark.parametrize("args", [[], ["-s", "300", "x.png"], ["-b", "0", "x.png"], ["-b", "40000", "x.png"], ["-s", "abc", "x.png"],
-                                  ["-o", "a.png", "-o", "b.png", "x.png"], ["--ext", "e.png", "-o", "a.png", "x.png"],
-                                  ["-o", "a.png", "x.png", "y.png"], ["-o", "-", "x.png", "y.png"], ["--bogus"],
-                                  ["-f", "/nonexistent/dir/file.png"], ["-V"]])
+@pytest.mark.parametrize("args", CLI_ERROR_ARGS)
 def test_argument_errors_and_exit_codes_match_the_reference(args, tmp_path):
+    """Live against oracle/_ref/pngloss_ref_cli where it is built, else against what it gave (tests/golden/cli_errors_ref.json)."""
     exe = _build_cli()
     ours = subprocess.run([exe] + args, capture_output=True, text=True, cwd=tmp_path)
-    ref = subprocess.run([REF_CLI] + args, capture_output=True, text=True, cwd=tmp_path)
-    assert ours.returncode == ref.returncode, (args, ours.stderr, ref.stderr)
+    if os.path.exists(REF_CLI):
+        ref = subprocess.run([REF_CLI] + args, capture_output=True, text=True, cwd=tmp_path)
+        ref_rc, ref_first = ref.returncode, ref.stderr.strip().splitlines()[:1]
+    else:
+        with open(os.path.join(U.GOLDEN, "cli_errors_ref.json")) as fh:
+            r = [e for e in json.load(fh) if e["args"] == args][0]
+        ref_rc, ref_first = r["returncode"], r["stderr_first_line"]
+    assert ours.returncode == ref_rc, (args, ours.stderr, ref_rc)
     if args and args != ["-V"] and args != ["--bogus"]:
-        assert ours.stderr.strip().splitlines()[:1] == ref.stderr.strip().splitlines()[:1]
+        assert ours.stderr.strip().splitlines()[:1] == ref_first
 
 
 def test_overwrite_rule_is_checked_before_any_work(tmp_path):

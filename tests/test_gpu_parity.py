@@ -881,7 +881,7 @@ def test_every_visible_device_takes_part_when_there_are_several(tmp_path):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("PNGLOSS_HIP_ENGINE", None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29577",
-                        os.path.join(U.ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"],
+                        os.path.join(U.ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, env=env, timeout=1200)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -1,8 +1,8 @@
 """CPU tests: pin the oracle (oracle/pngloss_port.c) to the reference.
 
 Sources of truth, in order of strength:
-  1. the REAL reference compiled from /root/reference (oracle/_ref) -- only where it was built (the build container)
-  2. tests/golden/*.npz -- outputs of that same reference build, committed as data
+  1. the REAL reference compiled by oracle/Makefile (oracle/_ref) -- only where it was built
+  2. tests/golden/*.npz -- outputs of that same reference build, committed as data (stand in for 1. where it is absent)
   3. tests/golden/digests.json -- digests of the BASELINE.json configurations
 """
 import ctypes as C
@@ -52,24 +52,38 @@ def test_port_matches_reference_digest_1080p_frame():
     assert "%016x" % P.fnv1a64(f, P.SURVEY_FNV_BASIS) == e["filters"]
 
 
-@pytest.mark.skipif(U.ref() is None, reason="oracle/_ref not built (no /root/reference on this box)")
 @pytest.mark.parametrize("variant", [0, 1, 2], ids=["plain", "gpu-shaped", "band-leader"])
 def test_port_matches_real_reference_on_seeded_inputs(variant):
-    for img, s, b, filt in U.seeded_cases(seed=11, n=36):
-        o1, f1 = U.run_ref(img, s, b, filt)
+    """Live against oracle/_ref where it is built, else against its outputs on the same inputs (tests/golden/seeded_ref.npz)."""
+    g = U.load_npz("seeded_ref.npz")
+    for i, (img, s, b, filt) in enumerate(U.seeded_cases(seed=11, n=36)):
+        if U.ref() is not None:
+            o1, f1 = U.run_ref(img, s, b, filt)
+        else:
+            o1, f1 = g["c%02d/out" % i], (g["c%02d/filters" % i] if filt else None)
         o2, f2 = U.run_port(img, s, b, filt, variant=variant)
         assert np.array_equal(o1, o2), (img.shape, s, b, filt)
         if filt:
             assert np.array_equal(f1, f2), (img.shape, s, b, filt)
 
 
-@pytest.mark.skipif(U.ref() is None, reason="oracle/_ref not built (no /root/reference on this box)")
 def test_golden_fixtures_are_what_the_reference_produces():
+    """Live against oracle/_ref where it is built, else against the reference digests digests.json holds for the same cases."""
     g = U.load_npz("synth_cases.npz")
+    digests = {(e["width"], e["height"], e["mode"], e["strength"], e["bleed"], e["frame"]): e for e in U.load_digests()["synthetic"]}
+    checked = 0
     for case in U.SYNTH_CASES[:8]:
         w, h, m, s, b, fr, filt = case
-        out, f = U.run_ref(P.synth_rgba(w, h, m, fr), s, b, filt)
-        assert np.array_equal(out, g[U.case_key(case) + "/out"])
+        if U.ref() is not None:
+            out, f = U.run_ref(P.synth_rgba(w, h, m, fr), s, b, filt)
+            assert np.array_equal(out, g[U.case_key(case) + "/out"])
+            checked += 1
+        elif (w, h, m, s, b, fr) in digests:
+            e = digests[(w, h, m, s, b, fr)]
+            assert "%016x" % P.fnv1a64(g[U.case_key(case) + "/out"], P.SURVEY_FNV_BASIS) == e["out"], case
+            assert "%016x" % P.fnv1a64(g[U.case_key(case) + "/filters"], P.SURVEY_FNV_BASIS) == e["filters"], case
+            checked += 1
+    assert checked >= 6
 
 
 def test_strength_zero_is_identity_for_every_class():

@@ -10,7 +10,7 @@ nproc > $OUT/${TAG}_legs.txt; cat /sys/fs/cgroup/cpu.max >> $OUT/${TAG}_legs.txt
 i=0
 for ENVS in "${@:2}"; do
   i=$((i+1))
-  env $(echo "$ENVS" | tr ',' ' ') python bench.py ${BENCH_FLAGS:-} > $OUT/${TAG}_bench$i.json 2> $OUT/${TAG}_bench$i.err
+  env $(echo "$ENVS" | tr ',' ' ') python bench.py --full ${BENCH_FLAGS:-} > $OUT/${TAG}_bench$i.json 2> $OUT/${TAG}_bench$i.err
   python - $OUT/${TAG}_bench$i.json "$ENVS" >> $OUT/${TAG}_legs.txt <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

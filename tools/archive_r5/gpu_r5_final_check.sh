@@ -12,7 +12,7 @@ DIGEST=$(python -c 'import pngloss_amd as P; print(P.source_digest())' 2>/dev/nu
 STAMP="source_digest=$DIGEST head=${HEAD:-unknown}"
 { echo "# $STAMP"; ( time timeout 1500 python -m pytest tests -m gpu -q ) 2>&1 | tail -12; } > $OUT/${TAG}_pytest_gpu.txt 2>&1
 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/${TAG}_smoke.txt 2>&1; echo "smoke rc=$?" >> $OUT/${TAG}_smoke.txt
-python bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench rc=$?" >> $OUT/${TAG}_bench.err
+python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench rc=$?" >> $OUT/${TAG}_bench.err
 { echo "# $STAMP"
   for seed in 51 52; do
     echo "## FUZZ_ENGINES=seg,,seg,mix  python tests/tools/gpu_fuzz.py 120 $seed"; FUZZ_ENGINES=seg,,seg,mix timeout 400 python tests/tools/gpu_fuzz.py 120 $seed 2>&1 | grep -v amdgpu.ids | tail -2

@@ -10,11 +10,11 @@ cd /tmp && export TMPDIR=/tmp
 cd $R
 python -m pytest tests -m gpu -q > $OUT/${TAG}_pytest_gpu.txt 2>&1; echo "pytest rc=$?" >> $OUT/${TAG}_pytest_gpu.txt
 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/${TAG}_smoke.txt 2>&1; echo "smoke rc=$?" >> $OUT/${TAG}_smoke.txt
-python bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench rc=$?" >> $OUT/${TAG}_bench.err
-BENCH="python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-batch"
+python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench rc=$?" >> $OUT/${TAG}_bench.err
+BENCH="python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-batch"
 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_prof_trace -o trace --output-format csv -- $BENCH > $OUT/${TAG}_prof_trace.log 2>&1
-{ echo "# rocprofv3 --kernel-trace --stats -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-batch   (one MI355X; 3 engine runs of the 4096x4096 frame)"; cat $(find $OUT/${TAG}_prof_trace -name "*kernel_stats.csv" | head -1); } > $OUT/${TAG}_kernel_trace_stats.txt
-BENCH1="python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-batch"
+{ echo "# rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-batch   (one MI355X; 3 engine runs of the 4096x4096 frame)"; cat $(find $OUT/${TAG}_prof_trace -name "*kernel_stats.csv" | head -1); } > $OUT/${TAG}_kernel_trace_stats.txt
+BENCH1="python $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-batch"
 for C in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --kernel-trace --pmc $C -d $OUT/${TAG}_prof_$C -o pmc --output-format csv -- $BENCH1 > $OUT/${TAG}_prof_$C.log 2>&1
 done
@@ -29,7 +29,7 @@ for c in ("FETCH_SIZE", "WRITE_SIZE"):
             if n.startswith("void "): n = n[5:]
             agg[n][r["Counter_Name"]] += float(r["Counter_Value"])
             if r["Counter_Name"] == c: calls[(n, c)] += 1
-print("# rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-batch")
+print("# rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-batch")
 print("# summed over the dispatches of each kernel during ONE engine run of the 4096x4096 frame; raw counter units (KB; FETCH_SIZE counts 64 B per 128 B request on gfx950)")
 print("%-28s %10s %16s %16s" % ("kernel", "dispatches", "FETCH_SIZE", "WRITE_SIZE"))
 for n in sorted(agg, key=lambda k: -agg[k]["FETCH_SIZE"]):

@@ -20,18 +20,18 @@ if has tests; then
   python -c "import __graft_entry__ as g; g.smoke()" > $OUT/${TAG}_smoke.txt 2>&1; echo "smoke rc=$?" >> $OUT/${TAG}_smoke.txt
 fi
 if has bench; then
-  python bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench rc=$?" >> $OUT/${TAG}_bench.err
+  python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench rc=$?" >> $OUT/${TAG}_bench.err
 fi
 BENCHARGS="--no-cpu-baseline --no-batch --no-sweep"
 if has trace; then
-  rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_prof_trace -o trace --output-format csv -- python $R/bench.py --steps 2 --warmup 1 $BENCHARGS > $OUT/${TAG}_prof_trace.log 2>&1
-  { echo "# rocprofv3 --kernel-trace --stats -- python bench.py --steps 2 --warmup 1 $BENCHARGS   ($BOX; 3 engine runs of the 4096x4096 frame, s=19 b=2; no profiling switch of the library set)"; cat $(find $OUT/${TAG}_prof_trace -name "*kernel_stats.csv" | head -1); } > $OUT/${TAG}_kernel_trace_stats.txt
+  rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_prof_trace -o trace --output-format csv -- python $R/bench.py --full --steps 2 --warmup 1 $BENCHARGS > $OUT/${TAG}_prof_trace.log 2>&1
+  { echo "# rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 2 --warmup 1 $BENCHARGS   ($BOX; 3 engine runs of the 4096x4096 frame, s=19 b=2; no profiling switch of the library set)"; cat $(find $OUT/${TAG}_prof_trace -name "*kernel_stats.csv" | head -1); } > $OUT/${TAG}_kernel_trace_stats.txt
   rm -rf $OUT/${TAG}_prof_trace
 fi
 if has pmc; then
   for C in FETCH_SIZE WRITE_SIZE; do
     # (counter collection serialises the dispatches of all queues: the caller's stream must not hold a wait for the engine's "finished" word in front of them -- the blocking variant of the entry)
-    PNGLOSS_HIP_NO_STREAM_WAIT=1 rocprofv3 --kernel-trace --pmc $C -d $OUT/${TAG}_prof_$C -o pmc --output-format csv -- python $R/bench.py --steps 1 --warmup 0 $BENCHARGS > $OUT/${TAG}_prof_$C.log 2>&1
+    PNGLOSS_HIP_NO_STREAM_WAIT=1 rocprofv3 --kernel-trace --pmc $C -d $OUT/${TAG}_prof_$C -o pmc --output-format csv -- python $R/bench.py --full --steps 1 --warmup 0 $BENCHARGS > $OUT/${TAG}_prof_$C.log 2>&1
   done
   python - "$OUT" "$TAG" > $OUT/${TAG}_pmc_fetch_write.txt <<'PY'
 import csv, glob, collections, json, sys
@@ -44,7 +44,7 @@ for c in ("FETCH_SIZE", "WRITE_SIZE"):
             if n.startswith("void "): n = n[5:]
             agg[n][r["Counter_Name"]] += float(r["Counter_Value"])
             if r["Counter_Name"] == c: calls[(n, c)] += 1
-print("# PNGLOSS_HIP_NO_STREAM_WAIT=1 rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-batch --no-sweep")
+print("# PNGLOSS_HIP_NO_STREAM_WAIT=1 rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-batch --no-sweep")
 print("# summed over the dispatches of each kernel during ONE engine run of the 4096x4096 frame (s=19 b=2); raw counter units (KB; FETCH_SIZE counts 64 B per 128 B request on gfx950)")
 print("%-28s %10s %16s %16s" % ("kernel", "dispatches", "FETCH_SIZE", "WRITE_SIZE"))
 for n in sorted(agg, key=lambda k: -agg[k]["FETCH_SIZE"]):
