@@ -224,15 +224,21 @@ int pngloss_hip_last_histogram(pngloss_hip_ctx *ctx, size_t index, uint32_t *his
  * x and y, run as a row wavefront on the device) and the transformations that reader registers -- palette / low bit depths / tRNS
  * expanded, 16-bit samples stripped to their high byte, gray to RGB, alpha 255 filled in (rwpng.c:239-258).  The caller parses the
  * chunks and inflates IDAT (zlib; pngloss_amd/cli/png_stream_reader.c does, on host threads) and passes
- *   scanlines     height * (1 + rowbytes) inflated bytes of a NON-INTERLACED image, filter type byte first in every row
- *   color_type, bit_depth   as in IHDR;  palette / palette_entries   the PLTE payload (RGB triples);  trns / trns_bytes   the tRNS payload
- *   rgba          out: width * height * 4 bytes, exactly what rwpng_read_image24 returns in rgba_data
- * Returns PNGLOSS_SUCCESS, PNGLOSS_INVALID_ARGUMENT (not a PNG format) or 25 (LIBPNG_FATAL_ERROR, rwpng.h:33: a filter type beyond 4).
- * Interlaced files are not taken (Adam7 passes have their own geometry): the tool reads those with libpng. */
+ *   scanlines     the inflated image data: height * (1 + rowbytes) bytes, filter type byte first in every row; for an Adam7-interlaced
+ *                 image its seven passes one after another (each an image of its own, with its own rows and rowbytes; an empty pass has
+ *                 no bytes at all)
+ *   color_type, bit_depth, interlace   as in IHDR (interlace 0 = none, 1 = Adam7);  palette / palette_entries   the PLTE payload (RGB
+ *                 triples);  trns / trns_bytes   the tRNS payload
+ *   rgba          out: width * height * 4 bytes, exactly what rwpng_read_image24 returns in rgba_data (interlaced files are de-interlaced)
+ * Zero-initialise these structs (and pngloss_hip_png_zsource below): members may be added where the layout has padding today, as
+ * `interlace` was, and zero keeps the meaning they had before.
+ * Returns PNGLOSS_SUCCESS, PNGLOSS_INVALID_ARGUMENT (not a PNG format, or an interlace method other than 0 and 1) or 25
+ * (LIBPNG_FATAL_ERROR, rwpng.h:33: a filter type beyond 4, in any pass). */
 typedef struct {
     const unsigned char *scanlines;
     uint32_t width, height;
     uint8_t color_type, bit_depth;
+    uint8_t interlace;              /* 0 = none, 1 = Adam7 */
     const unsigned char *palette;
     uint32_t palette_entries;
     const unsigned char *trns;
@@ -262,7 +268,7 @@ int pngloss_hip_png_decode_batch_device(pngloss_hip_ctx *ctx, const pngloss_hip_
  * fixed and dynamic blocks, the 32 KB window in shared memory, Adler-32 checked), for the files of a window, whose streams are independent.
  * This replaces ALL of the reader behind the chunk walk (/root/reference/src/rwpng.c:179-400: libpng's png_read_image = zlib inflate + inverse
  * filters + transformations); what goes up is the file's compressed bytes, what comes out stays on the device.
- *   zstream   the concatenated payloads of the file's IDAT chunks (one zlib stream), zbytes of them
+ *   zstream   the concatenated payloads of the file's IDAT chunks (one zlib stream), zbytes of them; interlaced files (interlace = 1) too
  * A stream the device inflater does not take (damaged, preset dictionary, size mismatch ...) gets status 25 and the call returns 25: read that
  * file on the host (so does a stream shorter than 6 bytes or beyond 4 GiB -- that file only).  One wave decodes ~3 MB/s (profiles/r04_read_side.txt; zlib: ~250 MB/s per host thread): this pays only when a call brings well over
  * a thousand files; otherwise use the scanline form above, with zlib on host threads. */
@@ -271,6 +277,7 @@ typedef struct {
     size_t zbytes;
     uint32_t width, height;
     uint8_t color_type, bit_depth;
+    uint8_t interlace;              /* 0 = none, 1 = Adam7 */
     const unsigned char *palette;
     uint32_t palette_entries;
     const unsigned char *trns;

@@ -4,11 +4,13 @@
  * What rwpng_read_image24_libpng (/root/reference/src/rwpng.c:179-400) gets from libpng, split in two: here the container format
  * (signature, chunk walk with CRC check, IHDR / PLTE / tRNS / gAMA / sRGB) and the inflate of the concatenated IDAT data with zlib
  * -- a serial bit stream per file, so it stays on the host, one file per decode thread; on the device
- * (pngloss_hip_png_decode_batch_host) the inverse filters and the expansion to RGBA8.  Files this reader does not take -- Adam7
- * interlace, any other chunk (text, ICC profiles, physical size ...: what libpng does with them is libpng's business), anything
+ * (pngloss_hip_png_decode_batch_host) the inverse filters and the expansion to RGBA8, of Adam7-interlaced files too (their seven passes are
+ * inflated as one stream, pl_pngread_core.h gives their sizes).  Files this reader does not take -- any other chunk (text, ICC profiles, physical size ...: what libpng does with them is libpng's business), anything
  * damaged -- go through libpng as before.
  */
 #include "png_stream_reader.h"
+
+#include "../csrc/pl_pngread_core.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -47,7 +49,8 @@ bool png_stream_read(const char *path, png_stream_source *out)
                 seen_ihdr = true;
                 out->width = be32(body); out->height = be32(body + 4);
                 out->bit_depth = body[8]; out->color_type = body[9];
-                if (body[10] != 0 || body[11] != 0 || body[12] != 0) { bad = true; break; }      /* interlace (Adam7): libpng's */
+                if (body[10] != 0 || body[11] != 0 || body[12] > 1) { bad = true; break; }       /* (interlace methods beyond Adam7: libpng's) */
+                out->interlace = body[12];
                 if (!out->width || !out->height || out->width > 0x7fffffffu / 8 || out->height > 0x7fffffffu / 8) { bad = true; break; }
                 /* libpng's own user limits (1,000,000 each way) and the reference's size check (rwpng.c:287: rowbytes > INT_MAX / height) stay
                  * libpng's and the reference's to report */
@@ -83,13 +86,9 @@ bool png_stream_read(const char *path, png_stream_source *out)
         if (bad || !seen_iend || !seen_idat) break;
         /* the formats PNG allows */
         const int ct = out->color_type, d = out->bit_depth;
-        const int channels = ct == 0 ? 1 : ct == 2 ? 3 : ct == 3 ? 1 : ct == 4 ? 2 : ct == 6 ? 4 : 0;
-        const bool fmt = (ct == 0 && (d == 1 || d == 2 || d == 4 || d == 8 || d == 16)) || (ct == 3 && (d == 1 || d == 2 || d == 4 || d == 8)) ||
-                         ((ct == 2 || ct == 4 || ct == 6) && (d == 8 || d == 16));
-        if (!fmt || (ct == 3 && !out->palette_entries)) break;
+        if (!pr_valid(ct, d) || (ct == 3 && !out->palette_entries)) break;
         if (out->has_trns && (ct == 4 || ct == 6)) break;                                       /* not allowed; leave the complaint to libpng */
-        const size_t rowbytes = ((size_t)out->width * (size_t)(channels * d) + 7) / 8;
-        const size_t want = (rowbytes + 1) * (size_t)out->height;
+        const size_t want = (size_t)pr_scanline_bytes(out->width, out->height, ct, d, out->interlace);
         out->scanlines = malloc(want ? want : 1);
         if (!out->scanlines) break;
         z_stream z;

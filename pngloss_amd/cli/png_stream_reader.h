@@ -9,7 +9,8 @@
 typedef struct {
     uint32_t width, height;
     uint8_t color_type, bit_depth;
-    unsigned char *scanlines;      /* malloc'ed: height * (1 + rowbytes) inflated bytes */
+    uint8_t interlace;             /* 0 = none, 1 = Adam7 */
+    unsigned char *scanlines;      /* malloc'ed: the inflated bytes, height * (1 + rowbytes) or the seven Adam7 passes one after another */
     size_t scanline_bytes;
     unsigned char palette[768];
     uint32_t palette_entries;
@@ -21,7 +22,7 @@ typedef struct {
 } png_stream_source;
 
 /* Reads the file and inflates its image data.  true: `out` is filled (free out->scanlines).  false: the file is not one this
- * path takes -- interlaced, chunks beyond IHDR PLTE tRNS gAMA sRGB IDAT IEND (their handling is libpng's), damaged -- and the
+ * path takes -- an interlace method other than none and Adam7, chunks beyond IHDR PLTE tRNS gAMA sRGB IDAT IEND (their handling is libpng's), damaged -- and the
  * caller reads it with libpng instead (which also produces the error messages for damaged files). */
 bool png_stream_read(const char *path, png_stream_source *out);
 

@@ -61,8 +61,8 @@ static const char usage_text[] =
     "  --strip           remove optional metadata (default on Mac)\n"
     "  --gpu-deflate     compress the image data on the GPU too (not zlib's bytes, same pixels,\n"
     "                    files several percent smaller than with zlib level 9, much faster)\n"
-    "  --gpu-read        undo the PNG scanline filters and expand to RGBA on the GPU (plain,\n"
-    "                    non-interlaced files; the others are read with libpng as usual)\n"
+    "  --gpu-read        undo the PNG scanline filters and expand to RGBA on the GPU (plain or\n"
+    "                    Adam7-interlaced files; the others are read with libpng as usual)\n"
     "\n"
     "Lossily compresses PNGs by using more compressible colors that are close enough to the\n"
     "original values; the filter+quantise pass runs on the GPU (all files of a call as one batch).\n"
@@ -419,7 +419,7 @@ static void decode_window_on_device(struct job *jobs, size_t n, const struct opt
         for (size_t i = 0; i < n && rc == PNGLOSS_SUCCESS; i++) {
             struct job *j = &jobs[i];
             if (!j->src.scanlines || j->status != SUCCESS) continue;
-            src[k] = (pngloss_hip_png_source){ j->src.scanlines, j->src.width, j->src.height, j->src.color_type, j->src.bit_depth,
+            src[k] = (pngloss_hip_png_source){ j->src.scanlines, j->src.width, j->src.height, j->src.color_type, j->src.bit_depth, j->src.interlace,
                                                j->src.palette_entries ? j->src.palette : NULL, j->src.palette_entries,
                                                j->src.has_trns ? j->src.trns : NULL, j->src.trns_bytes, j->in.rgba_data };
             who[k++] = i;

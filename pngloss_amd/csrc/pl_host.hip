@@ -1495,6 +1495,13 @@ int pngloss_hip_png_decode_batch_host(pngloss_hip_ctx *ctx, const pngloss_hip_pn
 }
 
 } /* extern "C" */
+/* `interlace` sits where both source structs had padding: their size and every other member's offset are what they were before it */
+static_assert(sizeof(pngloss_hip_png_source) == 64 && offsetof(pngloss_hip_png_source, interlace) == 18 && offsetof(pngloss_hip_png_source, palette) == 24 &&
+              offsetof(pngloss_hip_png_source, palette_entries) == 32 && offsetof(pngloss_hip_png_source, trns) == 40 &&
+              offsetof(pngloss_hip_png_source, trns_bytes) == 48 && offsetof(pngloss_hip_png_source, rgba) == 56, "pngloss_hip_png_source layout");
+static_assert(sizeof(pngloss_hip_png_zsource) == 64 && offsetof(pngloss_hip_png_zsource, interlace) == 26 && offsetof(pngloss_hip_png_zsource, palette) == 32 &&
+              offsetof(pngloss_hip_png_zsource, palette_entries) == 40 && offsetof(pngloss_hip_png_zsource, trns) == 48 &&
+              offsetof(pngloss_hip_png_zsource, trns_bytes) == 56, "pngloss_hip_png_zsource layout");
 namespace {
 /* d_out == nullptr: the decoded images are downloaded to src[i].rgba.  Else they STAY on the device, in the context's frame arena (apart
  * from the workspace the optimiser carves up), and d_out[i] receives their device pointers. */
@@ -1515,37 +1522,73 @@ int png_decode_body(pngloss_hip_ctx *ctx, const pngloss_hip_png_source *src, siz
         return PNGLOSS_INVALID_ARGUMENT;
     }
     PL_CHECK(hipSetDevice(ctx->device));
-    std::vector<PrJob> jobs(n);
-    std::vector<size_t> raw_off(n), out_off(n), last_off(n), prog_off(n), z_off(n);
+    /* one job per non-interlaced file, one per non-empty Adam7 pass of an interlaced one (pl_pngread.h); offsets below are relative to the
+     * data region behind the tables, the device pointers are filled in once the workspace is there */
+    std::vector<PrJob> jobs;
+    jobs.reserve(n);
+    struct JobAt { size_t file; uint64_t raw; size_t last, prog; };
+    std::vector<JobAt> at;
+    at.reserve(n);
+    std::vector<size_t> raw_off(n), out_off(n), z_off(n);
+    std::vector<uint64_t> raw_bytes(n);
     static const unsigned char bad_stream[6] = { 0, 0, 0, 0, 0, 0 };       /* (CMF 0: not deflate) */
     std::vector<ZRef> zsub(zs ? n : 0);
     uint32_t max_bands = 0;
-    size_t total = align_up(sizeof(PrJob) * n, 256) + 2 * align_up(sizeof(int32_t) * n, 256) + align_up(sizeof(PliStream) * n, 256), ftotal = 0;
-    const size_t jobs_bytes = align_up(sizeof(PrJob) * n, 256), st_bytes = align_up(sizeof(int32_t) * n, 256);
+    size_t total = 0, ftotal = 0, nprog = 0;
     for (size_t i = 0; i < n; i++) {
         if ((!zs && !src[i].scanlines) || (zs && !zs[i].z) || (!d_out && !src[i].rgba)) return PNGLOSS_INVALID_ARGUMENT;
+        if (src[i].interlace > 1) {
+            std::fprintf(stderr, "pngloss_hip: image %zu: interlace method %d (0 = none, 1 = Adam7; the struct has to be zero-initialised)\n", i, src[i].interlace);
+            return PNGLOSS_INVALID_ARGUMENT;
+        }
         /* a stream too short to be zlib's (header + one block + Adler-32) or beyond the inflater's 32-bit positions is THAT file's problem: it gets
          * status 25 like any other stream the inflater refuses (it is handed a six-byte stream with an invalid header), the batch goes on */
         if (zs && (zs[i].bytes < 6 || zs[i].bytes > 0xFFFFFFF0u)) zsub[i] = ZRef{ bad_stream, sizeof bad_stream };
         else if (zs) zsub[i] = zs[i];
-        if (!pr_format(jobs[i].F, src[i].width, src[i].height, src[i].color_type, src[i].bit_depth, src[i].palette, src[i].palette_entries, src[i].trns, src[i].trns_bytes)) {
+        PrFormat F;
+        if (!pr_format(F, src[i].width, src[i].height, src[i].color_type, src[i].bit_depth, src[i].palette, src[i].palette_entries, src[i].trns, src[i].trns_bytes)) {
             std::fprintf(stderr, "pngloss_hip: image %zu: colour type %d with bit depth %d (or an empty image / a palette image without PLTE) is not a PNG format\n", i, src[i].color_type, src[i].bit_depth);
             return PNGLOSS_INVALID_ARGUMENT;
         }
-        raw_off[i] = total; total += align_up(((size_t)jobs[i].F.rowbytes + 1) * src[i].height, 256);
+        uint64_t pass_off[PR_ADAM7_PASSES] = {};
+        raw_bytes[i] = src[i].interlace ? pr_adam7_bytes(F.width, F.height, F.color_type, F.bit_depth, pass_off) : pr_scanline_bytes(F.width, F.height, F.color_type, F.bit_depth, 0);
+        raw_off[i] = total; total += align_up(raw_bytes[i], 256);
         if (zs) {
-            if (((size_t)jobs[i].F.rowbytes + 1) * src[i].height > 0xFFFFFFF0u) return PNGLOSS_INVALID_ARGUMENT;     /* (32-bit positions in the inflater) */
+            if (raw_bytes[i] > 0xFFFFFFF0u) return PNGLOSS_INVALID_ARGUMENT;     /* (32-bit positions in the inflater) */
             z_off[i] = total; total += align_up(zsub[i].bytes + 16, 256);
         }
         const size_t out_bytes = align_up((size_t)src[i].width * src[i].height * 4, 256);
         if (d_out) { out_off[i] = ftotal; ftotal += out_bytes; } else { out_off[i] = total; total += out_bytes; }
-        /* per band of PR_ROWS rows: its last row (for the band below) and a progress word */
-        jobs[i].nbands = (src[i].height + PR_ROWS - 1) / PR_ROWS;
-        jobs[i].lastpitch = (uint32_t)align_up(jobs[i].F.rowbytes, 256);
-        max_bands = std::max(max_bands, jobs[i].nbands);
-        last_off[i] = total; total += (size_t)jobs[i].lastpitch * jobs[i].nbands;
-        prog_off[i] = total; total += align_up(sizeof(uint32_t) * jobs[i].nbands, 256);
+        for (int p = 0; p < (src[i].interlace ? PR_ADAM7_PASSES : 1); p++) {
+            PrJob j{};
+            j.F = F;                                                              /* (a pass: the file's format with the pass's geometry) */
+            if (src[i].interlace) {
+                const PrPass ps = pr_adam7_pass(p, F.width, F.height, F.color_type, F.bit_depth);
+                if (!ps.bytes) continue;                                          /* an empty pass has no bytes in the stream */
+                j.F.width = ps.width; j.F.height = ps.height; j.F.rowbytes = ps.rowbytes;
+                j.ox = ps.x0; j.oy = ps.y0; j.sx = ps.dx; j.sy = ps.dy;
+            } else {
+                j.ox = 0; j.oy = 0; j.sx = 1; j.sy = 1;
+            }
+            j.pitch = F.width;
+            /* per band of PR_ROWS rows: its last row (for the band below) and a progress word */
+            j.nbands = (j.F.height + PR_ROWS - 1) / PR_ROWS;
+            j.lastpitch = (uint32_t)align_up(j.F.rowbytes, 256);
+            max_bands = std::max(max_bands, j.nbands);
+            at.push_back(JobAt{ i, src[i].interlace ? pass_off[p] : 0, total, nprog });
+            total += (size_t)j.lastpitch * j.nbands;
+            nprog += j.nbands;
+            jobs.push_back(j);
+        }
     }
+    const size_t m = jobs.size();
+    /* tables in front: jobs, then the status words of the decode and of the inflate and the progress words (zeroed by one memset), then the
+     * inflate's streams.  (Every job carries its format, palette included: 1.1 KB a pass.  A first version whose jobs pointed at one format
+     * per file had a table 4.6 MB smaller at 768 interlaced files, but a kernel 13 % slower on plain files: DESIGN.md section 9.2) */
+    const size_t jobs_bytes = align_up(sizeof(PrJob) * m, 256), st_bytes = align_up(sizeof(int32_t) * n, 256);
+    const size_t prog_bytes = align_up(sizeof(uint32_t) * nprog, 256), zjobs_bytes = align_up(sizeof(PliStream) * n, 256);
+    const size_t head = jobs_bytes + 2 * st_bytes + prog_bytes + zjobs_bytes;
+    total += head;
     const auto tr0 = std::chrono::steady_clock::now();
     auto ms_since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr0).count(); };
     int rc = ensure_ws(ctx, total);
@@ -1558,28 +1601,31 @@ int png_decode_body(pngloss_hip_ctx *ctx, const pngloss_hip_png_source *src, siz
         ctx->frames_bytes = want;
     }
     const double ms_ws = ms_since();
-    char *b = ctx->d_ws, *fb = d_out ? ctx->d_frames : ctx->d_ws;
+    char *b = ctx->d_ws, *d = b + head, *fb = d_out ? ctx->d_frames : d;
     int32_t *d_status = reinterpret_cast<int32_t *>(b + jobs_bytes), *d_zstatus = reinterpret_cast<int32_t *>(b + jobs_bytes + st_bytes);
-    PliStream *d_zjobs = reinterpret_cast<PliStream *>(b + jobs_bytes + 2 * st_bytes);
+    uint32_t *d_prog = reinterpret_cast<uint32_t *>(b + jobs_bytes + 2 * st_bytes);
+    PliStream *d_zjobs = reinterpret_cast<PliStream *>(b + jobs_bytes + 2 * st_bytes + prog_bytes);
     std::vector<PliStream> zjobs(zs ? n : 0);
-    PL_CHECK(hipMemsetAsync(d_status, 0, 2 * st_bytes, stream));
+    PL_CHECK(hipMemsetAsync(d_status, 0, 2 * st_bytes + prog_bytes, stream));
+    for (size_t k = 0; k < m; k++) {
+        const size_t i = at[k].file;
+        jobs[k].raw = reinterpret_cast<const uint8_t *>(d + raw_off[i] + at[k].raw);
+        jobs[k].rgba = reinterpret_cast<uint32_t *>(fb + out_off[i]);
+        jobs[k].lastrow = reinterpret_cast<uint8_t *>(d + at[k].last);
+        jobs[k].progress = d_prog + at[k].prog;
+        jobs[k].status = d_status + i;
+    }
     for (size_t i = 0; i < n; i++) {
-        jobs[i].raw = reinterpret_cast<const uint8_t *>(b + raw_off[i]);
-        jobs[i].rgba = reinterpret_cast<uint32_t *>(fb + out_off[i]);
-        jobs[i].lastrow = reinterpret_cast<uint8_t *>(b + last_off[i]);
-        jobs[i].progress = reinterpret_cast<uint32_t *>(b + prog_off[i]);
-        PL_CHECK(hipMemsetAsync(b + prog_off[i], 0, sizeof(uint32_t) * jobs[i].nbands, stream));
-        jobs[i].status = d_status + i;
         /* (from pinned memory -- pngloss_hip_pinned_alloc -- this is one DMA; from pageable memory the runtime stages it: 33 ms against 1.3 for 64 MiB) */
         if (zs) {
-            PL_CHECK(hipMemcpyAsync(b + z_off[i], zsub[i].z, zsub[i].bytes, hipMemcpyHostToDevice, stream));
-            zjobs[i].z = reinterpret_cast<const uint8_t *>(b + z_off[i]); zjobs[i].zbytes = (uint32_t)zsub[i].bytes;
-            zjobs[i].out = reinterpret_cast<uint8_t *>(b + raw_off[i]); zjobs[i].expect = (uint32_t)(((size_t)jobs[i].F.rowbytes + 1) * src[i].height);
+            PL_CHECK(hipMemcpyAsync(d + z_off[i], zsub[i].z, zsub[i].bytes, hipMemcpyHostToDevice, stream));
+            zjobs[i].z = reinterpret_cast<const uint8_t *>(d + z_off[i]); zjobs[i].zbytes = (uint32_t)zsub[i].bytes;
+            zjobs[i].out = reinterpret_cast<uint8_t *>(d + raw_off[i]); zjobs[i].expect = (uint32_t)raw_bytes[i];
             zjobs[i].status = d_zstatus + i;
         } else
-        PL_CHECK(hipMemcpyAsync(b + raw_off[i], src[i].scanlines, ((size_t)jobs[i].F.rowbytes + 1) * src[i].height, hipMemcpyHostToDevice, stream));
+        PL_CHECK(hipMemcpyAsync(d + raw_off[i], src[i].scanlines, raw_bytes[i], hipMemcpyHostToDevice, stream));
     }
-    PL_CHECK(hipMemcpyAsync(b, jobs.data(), sizeof(PrJob) * n, hipMemcpyHostToDevice, stream));
+    PL_CHECK(hipMemcpyAsync(b, jobs.data(), sizeof(PrJob) * m, hipMemcpyHostToDevice, stream));
     if (zs) {
         PL_CHECK(hipMemcpyAsync(d_zjobs, zjobs.data(), sizeof(PliStream) * n, hipMemcpyHostToDevice, stream));
         PL_CHECK(pl_launch_inflate(d_zjobs, n, stream));
@@ -1587,13 +1633,13 @@ int png_decode_body(pngloss_hip_ctx *ctx, const pngloss_hip_png_source *src, siz
     const bool seam_dbg = ctx->hooks.debug_seam;
     double ms_up = 0, ms_k = 0;
     if (seam_dbg) { PL_CHECK(hipStreamSynchronize(stream)); ms_up = ms_since(); }
-    PL_CHECK(pl_launch_png_decode(reinterpret_cast<const PrJob *>(b), n, max_bands, stream));
+    PL_CHECK(pl_launch_png_decode(reinterpret_cast<const PrJob *>(b), m, max_bands, stream));
     if (seam_dbg) { PL_CHECK(hipStreamSynchronize(stream)); ms_k = ms_since(); }
     std::vector<int32_t> st(n), zst(n, 0);
     if (zs) PL_CHECK(hipMemcpyAsync(zst.data(), d_zstatus, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
     if (!d_out)
         for (size_t i = 0; i < n; i++)
-            PL_CHECK(hipMemcpyAsync(src[i].rgba, b + out_off[i], (size_t)src[i].width * src[i].height * 4, hipMemcpyDeviceToHost, stream));
+            PL_CHECK(hipMemcpyAsync(src[i].rgba, fb + out_off[i], (size_t)src[i].width * src[i].height * 4, hipMemcpyDeviceToHost, stream));
     PL_CHECK(hipMemcpyAsync(st.data(), d_status, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
     PL_CHECK(hipStreamSynchronize(stream));
     if (seam_dbg) std::fprintf(stderr, "pngloss_hip: read side: %zu files, workspace %zu MB ready after %.1f ms, upload %.1f ms, unfilter + expand %.1f ms, %s %.1f ms\n", n, (total + ftotal) >> 20, ms_ws, ms_up - ms_ws, ms_k - ms_up, d_out ? "status (the frames stay on the device)" : "download", ms_since() - ms_k);
@@ -1649,7 +1695,7 @@ int pngloss_hip_png_decode_batch_device_z(pngloss_hip_ctx *ctx, const pngloss_hi
     std::vector<pngloss_hip_png_source> src(n);
     std::vector<ZRef> zs(n);
     for (size_t i = 0; i < n; i++) {
-        src[i] = pngloss_hip_png_source{ nullptr, zsrc[i].width, zsrc[i].height, zsrc[i].color_type, zsrc[i].bit_depth, zsrc[i].palette, zsrc[i].palette_entries, zsrc[i].trns, zsrc[i].trns_bytes, nullptr };
+        src[i] = pngloss_hip_png_source{ nullptr, zsrc[i].width, zsrc[i].height, zsrc[i].color_type, zsrc[i].bit_depth, zsrc[i].interlace, zsrc[i].palette, zsrc[i].palette_entries, zsrc[i].trns, zsrc[i].trns_bytes, nullptr };
         zs[i] = ZRef{ zsrc[i].zstream, zsrc[i].zbytes };
     }
     return png_decode_common(ctx, src.data(), n, status, d_rgba, static_cast<hipStream_t>(stream), zs.data());

@@ -2,7 +2,7 @@
  * pl_pngread.hip -- the PNG READ side on the device: inflated IDAT bytes -> RGBA8, what libpng does for
  * the reference's rwpng_read_image24_libpng (/root/reference/src/rwpng.c:179-400) behind the inflate: the inverse scanline filters and
  * the expansion to RGBA8 (pl_pngread_core.h).  The inflate itself -- a serial bit stream per file -- stays with zlib on host threads
- * (pngloss_amd/cli/png_stream_reader.c); interlaced files stay with libpng.
+ * (pngloss_amd/cli/png_stream_reader.c), or on the device (pl_inflate.hip).
  *
  * Unfiltering is a recurrence: byte (x, y) needs the reconstructed bytes at (x - bpp, y), (x, y - 1), (x - bpp, y - 1).  Rows are NOT
  * independent, but row y can run one pixel behind row y - 1: a wavefront.  One wave per BAND of 64 rows (blockIdx.x = band,
@@ -11,13 +11,17 @@
  * reads from a per-band row buffer once that band's progress word says the block is there (release / acquire at device scope;
  * workgroups are dispatched in blockIdx order, so the band waited for is always running or done; a bounded wait turns a broken
  * assumption into an error status instead of a hang).  A 4096 x 4096 RGBA file: 64 bands in flight instead of one wave walking
- * them in turn (449 ms -> 7.5 ms, profiles/r03_read_side.txt).  The band's data goes through LDS in blocks of 960 bytes per row (a multiple
+ * them in turn (449 ms -> 7.5 ms, profiles/r03_read_side.txt).  An Adam7-interlaced file is seven such images (its passes, blockIdx.y = job): each
+ * pass is unfiltered on its own and its pixels are scattered to their places in the file's RGBA8 (PrJob's placement; passes 4-6, 7/8 of the
+ * pixels, store every first or second pixel, passes 0-3 every fourth or eighth).  The band's data goes through LDS in blocks of 960 bytes per row (a multiple
  * of every pixel size 1, 2, 3, 4, 6, 8 and of every step, so blocks cut between pixels), 65 rows (the row above the band first) x 976 bytes = 62 KB.  Neighbouring lanes
  * exchange the "above" bytes through that tile one step apart (wave-synchronous: same wave, program order).  Behind every block the
  * band's last row is published, then all 64 lanes expand the block's pixels to RGBA8 with coalesced stores.  Images of a batch are independent.
  */
 #include "pl_device.h"
 #include "pl_pngread.h"
+
+#include <algorithm>
 
 namespace {
 
@@ -184,10 +188,14 @@ __global__ __launch_bounds__(64) void pr_k_decode(const PrJob *jobs)
             uint32_t px0, px1;
             if (F.bit_depth >= 8) { px0 = b0 / bppf; px1 = (b0 + (uint32_t)nb) / bppf; }
             else { px0 = b0 * 8u / F.bit_depth; px1 = min(W, (b0 + (uint32_t)nb) * 8u / F.bit_depth); }
+            uint32_t *const base = j.rgba + (size_t)j.oy * j.pitch + j.ox;                    /* (placement, read once per block) */
+            const size_t ystride = (size_t)j.sy * j.pitch;
+            const uint32_t sx = j.sx;
             for (int r = 0; r < nrows; r++) {
                 const uint8_t *rowp = pr_tile + (size_t)(r + 1) * PR_STRIDE + PR_PAD - b0;       /* so that absolute byte offsets index it */
-                uint32_t *out = j.rgba + (size_t)(y0 + r) * W;
-                for (uint32_t x = px0 + (uint32_t)lane; x < px1; x += 64) out[x] = pr_expand(F, rowp, x);
+                uint32_t *out = base + (size_t)(y0 + r) * ystride;
+                if (sx == 1) for (uint32_t x = px0 + (uint32_t)lane; x < px1; x += 64) out[x] = pr_expand(F, rowp, x);
+                else for (uint32_t x = px0 + (uint32_t)lane; x < px1; x += 64) out[(size_t)x * sx] = pr_expand(F, rowp, x);
             }
             /* the last pixel of every row becomes the margin of the next block */
             uint8_t keep[8];
@@ -217,6 +225,11 @@ __global__ __launch_bounds__(64) void pr_k_decode(const PrJob *jobs)
 hipError_t pl_launch_png_decode(const PrJob *d_jobs, size_t n, uint32_t max_bands, hipStream_t stream)
 {
     if (!n || !max_bands) return hipSuccess;
-    hipLaunchKernelGGL(pr_k_decode, dim3(max_bands, (unsigned)n), dim3(64), (PR_ROWS + 1) * PR_STRIDE, stream, d_jobs);
-    return hipGetLastError();
+    /* (at most 65535 jobs a launch in y: the bands of a job always share a launch, and jobs do not wait for each other) */
+    for (size_t j0 = 0; j0 < n; j0 += 65535) {
+        hipLaunchKernelGGL(pr_k_decode, dim3(max_bands, (unsigned)std::min<size_t>(65535, n - j0)), dim3(64), (PR_ROWS + 1) * PR_STRIDE, stream, d_jobs + j0);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }

@@ -6,27 +6,27 @@
  *     1/2/4 bits -> 8 bits, tRNS -> alpha; rwpng.c:239-242), filler alpha 255 (:242), png_set_strip_16 = the HIGH byte of every
  *     16-bit sample (:252-254; tRNS keys are compared on the full 16 bits first, libpng expands before it strips),
  *     png_set_gray_to_rgb (:256-258).  No gamma correction is applied to pixels by that reader (the gamma is only recorded).
- * Shared by the HIP kernel (pl_pngread.hip) and the CPU check of tests/c/pngread_host.cpp (test infrastructure).
+ * Shared by the HIP kernel (pl_pngread.hip), its host set-up (pl_host.hip), the CPU checks of tests/c/pngread_host.cpp and
+ * tests/c/pngread_adam7_host.cpp (test infrastructure) and -- the geometry part, which is plain C -- the command line tool's reader.
  */
 #ifndef PL_PNGREAD_CORE_H
 #define PL_PNGREAD_CORE_H
 
 #include <stddef.h>
 #include <stdint.h>
+#ifndef __cplusplus
+#include <stdbool.h>
+#endif
 
 #if defined(__HIPCC__)
 #define PR_HD __host__ __device__ __forceinline__
-#else
+#elif defined(__cplusplus)
 #define PR_HD inline
+#else
+#define PR_HD static inline
 #endif
 
-/* everything the expansion needs to know about one image */
-struct PrFormat {
-    uint32_t width, height, rowbytes;
-    uint8_t color_type, bit_depth, bppf, has_trns;   /* bppf: bytes per complete pixel, at least 1 (the filters' stride) */
-    uint16_t key[3];                                 /* tRNS of gray (key[0]) / RGB images: the transparent sample values */
-    uint32_t pal[256];                               /* palette images: RGBA8 of every index (alpha from tRNS, 255 beyond it) */
-};
+/* ---- geometry, plain C as well: the command line tool's reader (pngloss_amd/cli/png_stream_reader.c) sizes its inflate with it ---- */
 
 PR_HD int pr_channels(int color_type) { return color_type == 0 ? 1 : color_type == 2 ? 3 : color_type == 3 ? 1 : color_type == 4 ? 2 : 4; }
 PR_HD bool pr_valid(int color_type, int depth)
@@ -38,6 +38,63 @@ PR_HD bool pr_valid(int color_type, int depth)
     default: return false;
     }
 }
+
+/* bytes of one scanline of `width` pixels, without its filter type byte (a row at a depth below 8 ends in padding bits) */
+PR_HD uint32_t pr_rowbytes(uint32_t width, int color_type, int depth)
+{
+    return (uint32_t)(((uint64_t)width * (uint64_t)(pr_channels(color_type) * depth) + 7) / 8);
+}
+
+/* One pass of an Adam7-interlaced image (PNG specification section 8.2): the pixels (x0 + j * dx, y0 + i * dy), an ordinary filtered image
+ * of width x height pixels whose rows (filter type byte first, padding bits of their own) refer only to rows of the same pass.  An empty
+ * pass (no column or no row) has no bytes in the stream, not even filter type bytes. */
+typedef struct PrPass {
+    uint32_t x0, y0, dx, dy, width, height, rowbytes;
+    uint64_t bytes;                 /* height * (1 + rowbytes), 0 for an empty pass */
+} PrPass;
+
+#define PR_ADAM7_PASSES 7
+
+PR_HD PrPass pr_adam7_pass(int p, uint32_t W, uint32_t H, int color_type, int depth)
+{
+    /* the table of the specification, one nibble per pass (pass 6 leftmost): x0 0 4 0 2 0 1 0, y0 0 0 4 0 2 0 1, dx 8 8 4 4 2 2 1, dy 8 8 8 4 4 2 2 */
+    const uint32_t sh = 4u * (uint32_t)p, lx = (0x0112233u >> sh) & 15u, ly = (0x1122333u >> sh) & 15u;       /* log2 dx, log2 dy */
+    PrPass s;
+    s.x0 = (0x0102040u >> sh) & 15u; s.y0 = (0x1020400u >> sh) & 15u; s.dx = 1u << lx; s.dy = 1u << ly;
+    s.width = W > s.x0 ? (W - s.x0 + s.dx - 1) >> lx : 0u;
+    s.height = H > s.y0 ? (H - s.y0 + s.dy - 1) >> ly : 0u;
+    s.rowbytes = pr_rowbytes(s.width, color_type, depth);
+    s.bytes = s.width && s.height ? (uint64_t)s.height * (1u + (uint64_t)s.rowbytes) : 0u;
+    return s;
+}
+
+/* inflated bytes of an Adam7-interlaced file: the seven passes one after another; off (NULL or 7 entries) receives where each pass starts */
+PR_HD uint64_t pr_adam7_bytes(uint32_t W, uint32_t H, int color_type, int depth, uint64_t *off)
+{
+    uint64_t total = 0;
+    for (int p = 0; p < PR_ADAM7_PASSES; p++) {
+        if (off) off[p] = total;
+        total += pr_adam7_pass(p, W, H, color_type, depth).bytes;
+    }
+    return total;
+}
+
+/* inflated bytes of a file: interlace 0 = height * (1 + rowbytes), 1 = Adam7 */
+PR_HD uint64_t pr_scanline_bytes(uint32_t W, uint32_t H, int color_type, int depth, int interlace)
+{
+    return interlace ? pr_adam7_bytes(W, H, color_type, depth, NULL) : (uint64_t)H * (1u + (uint64_t)pr_rowbytes(W, color_type, depth));
+}
+
+#ifdef __cplusplus
+/* ---- pixel arithmetic ---- */
+
+/* everything the expansion needs to know about one image */
+struct PrFormat {
+    uint32_t width, height, rowbytes;
+    uint8_t color_type, bit_depth, bppf, has_trns;   /* bppf: bytes per complete pixel, at least 1 (the filters' stride) */
+    uint16_t key[3];                                 /* tRNS of gray (key[0]) / RGB images: the transparent sample values */
+    uint32_t pal[256];                               /* palette images: RGBA8 of every index (alpha from tRNS, 255 beyond it) */
+};
 
 /* inverse filter of one byte: x = filtered byte, a = left, b = above, c = upper left (reconstructed bytes, 0 outside the image) */
 PR_HD int pr_recon(int ft, int x, int a, int b, int c)
@@ -120,7 +177,7 @@ inline bool pr_format(PrFormat &F, uint32_t width, uint32_t height, int color_ty
     if (!pr_valid(color_type, depth) || !width || !height) return false;
     F.width = width; F.height = height; F.color_type = (uint8_t)color_type; F.bit_depth = (uint8_t)depth;
     const uint32_t bits = (uint32_t)pr_channels(color_type) * (uint32_t)depth;
-    F.rowbytes = (uint32_t)(((uint64_t)width * bits + 7) / 8);
+    F.rowbytes = pr_rowbytes(width, color_type, depth);
     F.bppf = (uint8_t)(bits >= 8 ? bits / 8 : 1);
     F.has_trns = 0; F.key[0] = F.key[1] = F.key[2] = 0;
     for (int i = 0; i < 256; i++) F.pal[i] = 0xff000000u;          /* libpng: indices beyond PLTE read as black */
@@ -136,5 +193,6 @@ inline bool pr_format(PrFormat &F, uint32_t width, uint32_t height, int color_ty
     }
     return true;
 }
+#endif /* __cplusplus */
 
 #endif

@@ -48,8 +48,15 @@ class ZStream(C.Structure):
 
 
 class PngSource(C.Structure):
+    """pngloss_hip_png_source.  `interlace` (0 = none, 1 = Adam7) sits in what was padding behind bit_depth; the positional arguments are the
+    ten of the struct without it, so it is given by keyword."""
     _fields_ = [("scanlines", C.c_char_p), ("width", C.c_uint32), ("height", C.c_uint32), ("color_type", C.c_uint8), ("bit_depth", C.c_uint8),
+                ("interlace", C.c_uint8),
                 ("palette", C.c_char_p), ("palette_entries", C.c_uint32), ("trns", C.c_char_p), ("trns_bytes", C.c_uint32), ("rgba", C.c_void_p)]
+
+    def __init__(self, scanlines=None, width=0, height=0, color_type=0, bit_depth=0, palette=None, palette_entries=0, trns=None, trns_bytes=0,
+                 rgba=None, interlace=0):
+        super().__init__(scanlines, width, height, color_type, bit_depth, interlace, palette, palette_entries, trns, trns_bytes, rgba)
 
 
 def parse_png(data):
@@ -81,8 +88,14 @@ def parse_png(data):
 
 
 class PngZSource(C.Structure):
+    """pngloss_hip_png_zsource; `interlace` by keyword, as in PngSource."""
     _fields_ = [("zstream", C.c_char_p), ("zbytes", C.c_size_t), ("width", C.c_uint32), ("height", C.c_uint32), ("color_type", C.c_uint8), ("bit_depth", C.c_uint8),
+                ("interlace", C.c_uint8),
                 ("palette", C.c_char_p), ("palette_entries", C.c_uint32), ("trns", C.c_char_p), ("trns_bytes", C.c_uint32)]
+
+    def __init__(self, zstream=None, zbytes=0, width=0, height=0, color_type=0, bit_depth=0, palette=None, palette_entries=0, trns=None, trns_bytes=0,
+                 interlace=0):
+        super().__init__(zstream, zbytes, width, height, color_type, bit_depth, interlace, palette, palette_entries, trns, trns_bytes)
 
 
 class Result(C.Structure):
@@ -384,10 +397,8 @@ class HipContext:
         outs = [np.zeros((p["height"], p["width"], 4), np.uint8) for p in parsed]
         src = (PngSource * max(1, len(parsed)))()
         for i, (p, o) in enumerate(zip(parsed, outs)):
-            if p["interlace"]:
-                raise ValueError("interlaced PNG files are read with libpng, not on the device")
             src[i] = PngSource(p["scanlines"], p["width"], p["height"], p["ctype"], p["depth"], p["plte"], len(p["plte"]) // 3 if p["plte"] else 0,
-                               p["trns"], len(p["trns"]) if p["trns"] else 0, o.ctypes.data)
+                               p["trns"], len(p["trns"]) if p["trns"] else 0, o.ctypes.data, interlace=p["interlace"])
         self._lib.pngloss_hip_png_decode_batch_host.argtypes = [C.c_void_p, C.POINTER(PngSource), C.c_size_t]
         self._lib.pngloss_hip_png_decode_batch_host.restype = C.c_int
         _check(self._lib.pngloss_hip_png_decode_batch_host(self._ctx, src, len(parsed)), "png_decode")
@@ -406,8 +417,6 @@ class HipContext:
         self._lib.pngloss_hip_pinned_free.restype = None
         staged = []
         for i, p in enumerate(parsed):
-            if p["interlace"]:
-                raise ValueError("interlaced PNG files are read with libpng, not on the device")
             sl = p["scanlines"]
             if pinned and len(sl):
                 buf = self._lib.pngloss_hip_pinned_alloc(len(sl))
@@ -417,7 +426,7 @@ class HipContext:
                 staged.append(buf)
                 sl = C.cast(buf, C.c_char_p)
             src[i] = PngSource(sl, p["width"], p["height"], p["ctype"], p["depth"], p["plte"], len(p["plte"]) // 3 if p["plte"] else 0,
-                               p["trns"], len(p["trns"]) if p["trns"] else 0, None)
+                               p["trns"], len(p["trns"]) if p["trns"] else 0, None, interlace=p["interlace"])
         ptrs = (C.c_void_p * max(1, n))()
         st = (C.c_int * max(1, n))()
         self._lib.pngloss_hip_png_decode_batch_device.argtypes = [C.c_void_p, C.POINTER(PngSource), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p]
@@ -443,7 +452,7 @@ class HipContext:
             z = zstreams[i] if zstreams is not None else p["zstream"]
             keep.append(z)
             src[i] = PngZSource(z, len(z), p["width"], p["height"], p["ctype"], p["depth"], p["plte"], len(p["plte"]) // 3 if p["plte"] else 0,
-                                p["trns"], len(p["trns"]) if p["trns"] else 0)
+                                p["trns"], len(p["trns"]) if p["trns"] else 0, interlace=p["interlace"])
         ptrs = (C.c_void_p * max(1, n))()
         st = (C.c_int * max(1, n))()
         self._lib.pngloss_hip_png_decode_batch_device_z.argtypes = [C.c_void_p, C.POINTER(PngZSource), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p]
@@ -460,7 +469,7 @@ class HipContext:
         src = (PngSource * max(1, len(parsed)))()
         for i, (p, o) in enumerate(zip(parsed, outs)):
             src[i] = PngSource(p["scanlines"], p["width"], p["height"], p["ctype"], p["depth"], p["plte"], len(p["plte"]) // 3 if p["plte"] else 0,
-                               p["trns"], len(p["trns"]) if p["trns"] else 0, o.ctypes.data)
+                               p["trns"], len(p["trns"]) if p["trns"] else 0, o.ctypes.data, interlace=p["interlace"])
         st = (C.c_int * max(1, len(parsed)))()
         self._lib.pngloss_hip_png_decode_batch_host_status.argtypes = [C.c_void_p, C.POINTER(PngSource), C.c_size_t, C.POINTER(C.c_int)]
         self._lib.pngloss_hip_png_decode_batch_host_status.restype = C.c_int
