@@ -12,6 +12,7 @@
 #include "pl_inflate.h"
 #define SEG_PLAIN_POINTERS   /* host plumbing only: SegJob is filled here, never dereferenced */
 #include "pl_seg.h"
+#include "pl_plan.h"
 
 #include <chrono>
 #include <pthread.h>
@@ -25,7 +26,6 @@
 #include <thread>
 #include <mutex>
 #include <new>
-#include <string>
 #include <vector>
 
 #define PL_CHECK(expr)                                                                                           \
@@ -38,54 +38,31 @@
         }                                                                                                        \
     } while (0)
 
-#define SEG_MAX_GROUPS 8
-/* Timing / test hooks of the environment, read ONCE, when a context is created (pngloss_hip_create) -- not per call.  None of them changes results: they pin choices the library
- * otherwise makes itself (launch groups, units, workgroup sizes), pick the blocking variant of the asynchronous entry, or print.  The one hook that is read per call is
- * PNGLOSS_HIP_ENGINE (the tests' pin of the row engine, read once at the top of enqueue; pngloss_hip_set_option(ctx, "engine", ..) takes precedence).  A hook that DOES change results
- * -- "candidate f wins every row", a debugging aid of rounds 1-3 -- exists in builds made with -DPL_DEBUG_FORCE_FILTER=f only: no environment variable of the shipped library can
- * make the drop-in seam write anything but the reference's bytes. */
-struct PlHooks {
-    int seg_groups = 0;          /* PNGLOSS_HIP_SEG_GROUPS: launch groups of a batch on the segment engine (0: the library's choice) */
-    bool no_stream_wait = false; /* PNGLOSS_HIP_NO_STREAM_WAIT: the blocking variant of the asynchronous entry (rocprofv3 --pmc needs it) */
-    int seg_unit = -1;           /* PNGLOSS_HIP_SEG_UNIT: 0 / 1 pins the enumeration per segment / in units (-1: the library's choice) */
-    int tparts = 0;              /* PNGLOSS_HIP_SEG_TPARTS */
-    int enum_nt = 0;             /* PNGLOSS_HIP_ENUM_NT: 512 / 1024 */
-    int kin = -1;                /* PNGLOSS_HIP_KIN: run-in pixels of the seeded enumeration */
-    int seg_seeds = -1;          /* PNGLOSS_HIP_SEG_SEEDS: 0 = units start from every state, as in round 5 (-1 / 1: from seeds where the pair has a seed set) */
-    int seg_seeds1 = -1;         /* PNGLOSS_HIP_SEG_SEEDS1: 0 / 1 pins the per-segment enumeration from seeds (seg_k_enum_unit<1>; -1: batches of two or more images) */
-    int pin = -1;                /* PNGLOSS_HIP_PIN: 0 = the launch thread is not pinned to a CPU (-1 / 1: pinned when the affinity set has room, run_seg_engine) */
-    int calib = -1;              /* PNGLOSS_HIP_CALIB: 1 = the cost model that picks the row engine of a batch is calibrated on this device by a probe (engine_calib; off by default: see enqueue) */
-    int seed_kin = -1;           /* PNGLOSS_HIP_SEED_KIN: run-in pixels of the units' seeds (1 .. SEG_SEED_KMAX) */
-    bool segprof = false;        /* PNGLOSS_HIP_SEGPROF: phase clocks inside the kernels (slows them down) */
-    bool debug = false;          /* PNGLOSS_HIP_DEBUG */
-    bool debug_seam = false;     /* PNGLOSS_HIP_DEBUG_SEAM */
-    bool force_careful = false;  /* PNGLOSS_HIP_FORCE_CAREFUL: the int16-wrap variant of the round-1 chains for every row (same bytes) */
-    bool no_split = false;       /* PNGLOSS_HIP_NO_SPLIT */
-    int split = 0;               /* PNGLOSS_HIP_SPLIT: chunks of a host window */
-    static PlHooks from_env()
-    {
-        PlHooks h;
-        auto num = [](const char *name, int dflt) { const char *e = std::getenv(name); return e ? std::atoi(e) : dflt; };
-        if (std::getenv("PNGLOSS_HIP_SEG_GROUPS")) h.seg_groups = std::max(1, std::min(SEG_MAX_GROUPS, num("PNGLOSS_HIP_SEG_GROUPS", 0)));
-        h.no_stream_wait = std::getenv("PNGLOSS_HIP_NO_STREAM_WAIT") != nullptr;
-        if (std::getenv("PNGLOSS_HIP_SEG_UNIT")) h.seg_unit = num("PNGLOSS_HIP_SEG_UNIT", 0) != 0 ? 1 : 0;
-        h.tparts = num("PNGLOSS_HIP_SEG_TPARTS", 0);
-        h.enum_nt = num("PNGLOSS_HIP_ENUM_NT", 0);
-        h.kin = num("PNGLOSS_HIP_KIN", -1);
-        h.seg_seeds = num("PNGLOSS_HIP_SEG_SEEDS", -1);
-        h.seg_seeds1 = num("PNGLOSS_HIP_SEG_SEEDS1", -1);
-        h.pin = num("PNGLOSS_HIP_PIN", -1);
-        h.calib = num("PNGLOSS_HIP_CALIB", -1);
-        h.seed_kin = num("PNGLOSS_HIP_SEED_KIN", -1);
-        h.segprof = std::getenv("PNGLOSS_HIP_SEGPROF") != nullptr;
-        h.debug = std::getenv("PNGLOSS_HIP_DEBUG") != nullptr;
-        h.debug_seam = std::getenv("PNGLOSS_HIP_DEBUG_SEAM") != nullptr;
-        h.force_careful = std::getenv("PNGLOSS_HIP_FORCE_CAREFUL") != nullptr;
-        { const char *no = std::getenv("PNGLOSS_HIP_NO_SPLIT"); h.no_split = no && *no == '1'; }
-        { const int v = num("PNGLOSS_HIP_SPLIT", 0); if (v >= 1 && v <= 8) h.split = v; }
-        return h;
-    }
-};
+/* the hooks of the environment (PlHooks, pl_plan.h): read once, when a context is created */
+static PlHooks from_env()
+{
+    PlHooks h;
+    auto num = [](const char *name, int dflt) { const char *e = std::getenv(name); return e ? std::atoi(e) : dflt; };
+    if (std::getenv("PNGLOSS_HIP_SEG_GROUPS")) h.seg_groups = std::max(1, std::min(SEG_MAX_GROUPS, num("PNGLOSS_HIP_SEG_GROUPS", 0)));
+    h.no_stream_wait = std::getenv("PNGLOSS_HIP_NO_STREAM_WAIT") != nullptr;
+    if (std::getenv("PNGLOSS_HIP_SEG_UNIT")) h.seg_unit = num("PNGLOSS_HIP_SEG_UNIT", 0) != 0 ? 1 : 0;
+    h.tparts = num("PNGLOSS_HIP_SEG_TPARTS", 0);
+    h.enum_nt = num("PNGLOSS_HIP_ENUM_NT", 0);
+    h.kin = num("PNGLOSS_HIP_KIN", -1);
+    h.seg_seeds = num("PNGLOSS_HIP_SEG_SEEDS", -1);
+    h.seg_seeds1 = num("PNGLOSS_HIP_SEG_SEEDS1", -1);
+    h.pin = num("PNGLOSS_HIP_PIN", -1);
+    h.calib = num("PNGLOSS_HIP_CALIB", -1);
+    h.seed_kin = num("PNGLOSS_HIP_SEED_KIN", -1);
+    h.segprof = std::getenv("PNGLOSS_HIP_SEGPROF") != nullptr;
+    h.debug = std::getenv("PNGLOSS_HIP_DEBUG") != nullptr;
+    h.debug_seam = std::getenv("PNGLOSS_HIP_DEBUG_SEAM") != nullptr;
+    h.force_careful = std::getenv("PNGLOSS_HIP_FORCE_CAREFUL") != nullptr;
+    { const char *no = std::getenv("PNGLOSS_HIP_NO_SPLIT"); h.no_split = no && *no == '1'; }
+    { const int v = num("PNGLOSS_HIP_SPLIT", 0); if (v >= 1 && v <= 8) h.split = v; }
+    return h;
+}
+
 struct pngloss_hip_ctx {
     int device = 0;
     PlHooks hooks;                   /* (from the environment, at creation) */
@@ -106,7 +83,7 @@ struct pngloss_hip_ctx {
     size_t arena_bytes = 0;
     char *h_pinned = nullptr;
     size_t pinned_bytes = 0;
-    std::string opt_engine;          /* pngloss_hip_set_option("engine", ...): empty = the cost model (or, for tests, $PNGLOSS_HIP_ENGINE) */
+    PlEnginePin opt_engine = PlEnginePin::Auto;   /* pngloss_hip_set_option("engine", ...): Auto = the cost model (or, for tests, $PNGLOSS_HIP_ENGINE) */
     char *d_frames = nullptr;        /* device frames of pngloss_hip_png_decode_batch_device: decoded RGBA8 that stays on the device for the optimiser */
     size_t frames_bytes = 0;
     hipStream_t copy_stream = nullptr;
@@ -321,10 +298,12 @@ void seg_worker_main(pngloss_hip_ctx *ctx, SegGroups gs, long max_attempts)
     ctx->seg_rc.store(rc, std::memory_order_release);
 }
 
-int run_seg_engine(pngloss_hip_ctx *ctx, const PlJob *d_jobs, const std::vector<uint32_t> &list, const SegParams &params, const std::vector<size_t> &seg_offs,
-                   size_t jobs_off, size_t params_off, hipStream_t stream, const uint32_t *d_sel, size_t n_wg, const PlEngineParams &prm)
+int run_seg_engine(pngloss_hip_ctx *ctx, const PlJob *d_jobs, const PlPlan &plan, const std::vector<size_t> &seg_offs,
+                   size_t jobs_off, size_t params_off, hipStream_t stream, const uint32_t *d_sel, const PlEngineParams &prm)
 {
+    const std::vector<uint32_t> &list = plan.seg_list;
     const size_t n = list.size();                              /* the images of the batch this engine takes */
+    const int ngroups = plan.ngroups;                          /* (launch groups: pl_plan_batch) */
     if (!ctx->h_seg_words) PL_CHECK(hipHostMalloc(reinterpret_cast<void **>(&ctx->h_seg_words), 16 * SEG_MAX_GROUPS, hipHostMallocMapped | hipHostMallocCoherent));
     if (!ctx->seg_stream) {
         /* a stream of the HIGHEST priority: streams of one priority share a few hardware queues, and a queue whose head is a caller's
@@ -339,32 +318,7 @@ int run_seg_engine(pngloss_hip_ctx *ctx, const PlJob *d_jobs, const std::vector<
     }
     if (!ctx->ev_prep) PL_CHECK(hipEventCreateWithFlags(&ctx->ev_prep, hipEventDisableTiming));
     if (!ctx->ev_seg_done) { PL_CHECK(hipEventCreateWithFlags(&ctx->ev_seg_done, hipEventDisableTiming)); ctx->ev_seg_gdone[0] = ctx->ev_seg_done; }
-    /* GROUPS: a batch's images in up to SEG_MAX_GROUPS launch sequences on as many streams.  An attempt is four dependent launches with a latency floor
-     * each (the enumeration's dependent steps above all: 75 us with units); images of ONE sequence sit through every floor together, images of different
-     * sequences fill each other's floors.  One launch thread feeds all of them. */
-    int ngroups = 1;
-    {
-        size_t segs = 0;
-        for (size_t i = 0; i < n; i++) segs += (ctx->h_jobs[list[i]].width + SEG_L - 1) / SEG_L;
-        /* (measured, profiles/r05_unit_groups.txt: two sequences 1.2x one from 16 frames of 1080p on, three another 2-6 %, FOUR collapse -- 250 ms for 8 frames
-         *  against 113: with the caller's stream they outnumber the hardware queues a process gets, and the stream that shares a queue with the caller's sits
-         *  behind its wait for the finished word (without that wait four run, six collapse: profiles/r05_validation_in_enum.txt).  THREE looked 6 % faster in a
-         *  process that does nothing else -- and halved every later engine run of bench.py's process, single images included (suite batch 45 -> 14 Mpx/s, 8192 x 8192
-         *  137 -> 71): the hardware queues a third engine stream brings into the process's pool stay there, and from then on an engine stream shares one with a
-         *  waiting stream.  Two it is for the asynchronous entry: a caller with streams of its own must still fit.  The SYNCHRONOUS entry point puts no wait on
-         *  any stream (run_seg_engine below): there three groups are safe -- bench.py's process, every leg after a three-group batch at full speed -- and worth
-         *  6 % at 32 frames, 3 % at 64.) */
-        /* Round 6 (the advisor's finding on round 5): three is OPT-IN -- pngloss_hip_set_option(ctx, "launch_groups", "3"), for a process that uses the synchronous
-         * entry point only (bench.py's batch legs do and say so in their output) --, because nothing stopped a process from running a three-group batch and an asynchronous
-         * one with a stream of its own later: the default is two.  Two guards on top, process-wide: once ANY context of the process has put a wait on a caller's stream no
-         * third engine stream is created any more; and once a third engine stream exists the asynchronous entry takes its blocking variant (no wait on any stream) instead
-         * of running at half speed behind one. */
-        const bool three = ctx->opt_launch_groups == 3 && ctx->sync_call && ctx->three_groups_ok && n >= 12 && !g_stream_wait_used.load(std::memory_order_relaxed);
-        if (segs > SEG_UNIT_MIN_SEGS && n >= 8) ngroups = three ? 3 : 2;
-        else if (n >= 2) ngroups = 2;                              /* (a small batch: see the shares below) */
-        if (ctx->hooks.seg_groups) ngroups = ctx->hooks.seg_groups;   /* (timing / test hook: results do not depend on it) */
-        ngroups = (int)std::min<size_t>((size_t)ngroups, n);
-    }
+    /* one stream per launch group; one launch thread feeds all of them */
     for (int g = 1; g < ngroups; g++) {
         if (!ctx->seg_gstream[g] && g >= 2) g_third_engine_stream.store(true, std::memory_order_relaxed);
         if (!ctx->seg_gstream[g]) PL_CHECK(seg_stream_pool().take(ctx->device, ctx->seg_prio, &ctx->seg_gstream[g]));
@@ -380,42 +334,11 @@ int run_seg_engine(pngloss_hip_ctx *ctx, const PlJob *d_jobs, const std::vector<
     PL_CHECK(hipHostGetDevicePointer(&d_words, ctx->h_seg_words, 0));
     volatile uint32_t *words = ctx->h_seg_words;
     for (int q = 0; q < 4 * SEG_MAX_GROUPS; q++) words[q] = 0;       /* ([2g], [2g + 1]: see seg_worker_main; [2 * SEG_MAX_GROUPS + g]: rows of group g the chain kernel broke off) */
-    /* group g = images [gfirst[g], gfirst[g + 1]) of `list` (tallest first: enqueue): equal shares -- or, in a batch of two groups whose tallest image stands out, that
-     * image alone and the others together.  A group takes as many attempts as its image with the most, and every attempt costs what ALL its images' workgroups
-     * cost: the reference's suite as one batch (configs[2]) spent 71 ms on the 1199 attempts of its tallest image, a screenshot whose candidate none fails in 40 % of
-     * its rows -- at the price of eight images each; the other seven need 625 (profiles/r05_suite_groups.txt). */
-    size_t gfirst[SEG_MAX_GROUPS + 1];
-    for (int g = 0; g <= ngroups; g++) gfirst[g] = n * (size_t)g / (size_t)ngroups;
-    if (ngroups == 2 && n > 2 && !ctx->hooks.seg_groups) {
-        const uint32_t h0 = ctx->h_jobs[list[0]].height, h1 = ctx->h_jobs[list[1]].height;
-        if ((uint64_t)h0 * 100u > (uint64_t)h1 * 105u) gfirst[1] = 1;
-    }
+    const size_t *gfirst = plan.gfirst;
     auto group_of = [&](size_t i) { int g = 0; while (g + 1 < ngroups && i >= gfirst[g + 1]) g++; return g; };
     ctx->h_sj.assign(n, SegJob{});
-    ctx->h_seg_params = params;
-    size_t seg_total = 0;
-    {
-        /* Enumeration in UNITS of SEG_UNIT segments (seg_enum_unit_body): less than half the instructions per row, a dependent path SEG_UNIT times as long.
-         * It pays when the batch is what keeps the GPU busy, not the latency of one row: from a handful of images on.  Results do not depend on it (the
-         * validation is the ground truth either way); PNGLOSS_HIP_SEG_UNIT=0 / 1 pins it for tests and timing. */
-        size_t segs = 0;
-        for (size_t i = 0; i < n; i++) segs += (ctx->h_jobs[list[i]].width + SEG_L - 1) / SEG_L;
-        const bool can = !params.seeded && params.ns <= SEG_NSP;       /* (state sets of one chunk of lanes: with more, the distinct states of a workgroup's pairs outgrow its lanes) */
-        const bool have_seeds = can && params.seed_n > 0 && ctx->hooks.seg_seeds != 0;
-        /* (with seeds the per-segment enumeration stays ahead up to sixteen 1080p frames: pl_seg_core.h -- where it applies: batches of NARROW images, which it does not take, go to units from
-         *  the round-5 size on: 40 photographs of 512 .. 768 pixels, 784 segments, 54.8 ms in units against 62.4 per segment from every state) */
-        const bool seeds1_fit = have_seeds && n >= 2 && segs >= SEG_SEEDS1_MIN_SEGS && segs >= (size_t)SEG_SEEDS1_MIN_SEGS_PER_IMAGE * n;
-        bool units = can && segs > (seeds1_fit ? (size_t)SEG_UNIT_MIN_SEGS_SEEDS : (size_t)SEG_UNIT_MIN_SEGS);
-        seg_total = segs;
-        if (ctx->hooks.seg_unit >= 0) units = can && ctx->hooks.seg_unit != 0;
-        ctx->h_seg_params.unit = units ? SEG_UNIT : 1;
-        ctx->h_seg_params.tparts = units ? SEG_TPARTS_BATCH : SEG_TPARTS;     /* (batches: one control workgroup per candidate) */
-        if (ctx->hooks.tparts == 1 || ctx->hooks.tparts == SEG_TPARTS) ctx->h_seg_params.tparts = ctx->hooks.tparts == 1 ? SEG_TPARTS_BATCH : SEG_TPARTS;   /* (timing / test hook) */
-        if (ctx->hooks.seed_kin >= 1 && ctx->hooks.seed_kin <= SEG_SEED_KMAX) ctx->h_seg_params.seed_kin = ctx->hooks.seed_kin;   /* (timing hook) */
-    }
-    SegGroups gs{};                     /* (value-initialised: the per-group maxima below start from zero) */
-    gs.n = ngroups;
-    uint32_t max_h = 0;
+    ctx->h_seg_params = plan.params;
+    const SegParams &params = plan.params;
     for (size_t i = 0; i < n; i++) {
         const PlJob &pj = ctx->h_jobs[list[i]];
         const PlSegLayout l = pl_seg_layout(pj.width ? pj.width : 1, (uint32_t)params.nsp, params.seeded != 0);
@@ -436,40 +359,24 @@ int run_seg_engine(pngloss_hip_ctx *ctx, const PlJob *d_jobs, const std::vector<
         s.grpcnt = reinterpret_cast<uint32_t *>(base + l.grpcnt); s.grpleft = reinterpret_cast<uint32_t *>(base + l.grpleft);
         s.firstidx = reinterpret_cast<uint32_t *>(base + l.firstidx); s.rowmm = reinterpret_cast<int32_t *>(base + l.rowmm);
         s.nseg = pj.width ? l.nseg : 0; s.ngrp = pj.width ? l.ngrp : 0;
-        PlSegBatch &bg = gs.b[group_of(i)];
-        bg.max_nseg = std::max(bg.max_nseg, l.nseg); bg.max_ngrp = std::max(bg.max_ngrp, l.ngrp);
-        bg.max_ncommit = std::max(bg.max_ncommit, (pj.width + SEG_COMMIT_W - 1) / SEG_COMMIT_W);
-        max_h = std::max(max_h, pj.height);
     }
     SegJob *d_sj = reinterpret_cast<SegJob *>(ctx->d_ws + jobs_off);
     for (size_t i = 0; i < n; i++) ctx->h_sj[i].self = d_sj + i;
     SegParams *d_params = reinterpret_cast<SegParams *>(ctx->d_ws + params_off);
     PL_CHECK(hipMemcpyAsync(d_sj, ctx->h_sj.data(), sizeof(SegJob) * n, hipMemcpyHostToDevice, stream));
     PL_CHECK(hipMemcpyAsync(d_params, &ctx->h_seg_params, sizeof(SegParams), hipMemcpyHostToDevice, stream));
+    SegGroups gs{};
+    gs.n = ngroups;
     for (int g = 0; g < ngroups; g++) {
+        const PlSegGroupPlan &pg = plan.group[g];
         PlSegBatch &b = gs.b[g];
-        if (!b.max_ncommit) b.max_ncommit = 1;
-        b.d_sj = d_sj + gfirst[g]; b.d_params = d_params; b.n = gfirst[g + 1] - gfirst[g];
-        b.small_ok = params.small_ok != 0;
-        b.seeded = params.seeded != 0;
-        b.unit = (uint32_t)ctx->h_seg_params.unit;
-        /* round 6: units start from seeds with a run-in where the (strength, bleed) pair has a seed set (PNGLOSS_HIP_SEG_SEEDS=0 / 1 pins it for tests and timing; same bytes) */
-        b.seeds = b.unit > 1 && ctx->h_seg_params.seed_n > 0 && ctx->hooks.seg_seeds != 0;
-        /* ... and a batch of two or more images below that size goes segment by segment from seeds, through the same bodies (seg_k_enum_unit<1>; PNGLOSS_HIP_SEG_SEEDS1=0 / 1 pins it) */
-        if (b.unit == 1 && !params.seeded && ctx->h_seg_params.seed_n > 0 && ctx->hooks.seg_seeds != 0 && ctx->h_seg_params.ns <= SEG_NSP)
-            b.seeds = ctx->hooks.seg_seeds1 >= 0 ? ctx->hooks.seg_seeds1 != 0 : (n >= 2 && seg_total >= SEG_SEEDS1_MIN_SEGS && seg_total >= (size_t)SEG_SEEDS1_MIN_SEGS_PER_IMAGE * n);
-        b.tparts = (uint32_t)ctx->h_seg_params.tparts;
-        b.enum_nt = (size_t)b.max_nseg * b.n <= SEG_ENUM_NT_SMALL_MAX_NSEG ? 512u : 1024u;     /* (the images of THIS group: gridDim.y of its launches) */
-        if (ctx->hooks.enum_nt == 512 || ctx->hooks.enum_nt == 1024) b.enum_nt = (uint32_t)ctx->hooks.enum_nt;   /* test hook */
+        b.d_sj = d_sj + gfirst[g]; b.d_params = d_params; b.n = pg.n;
+        b.max_nseg = pg.max_nseg; b.max_ngrp = pg.max_ngrp; b.max_ncommit = pg.max_ncommit;
+        b.enum_nt = pg.enum_nt; b.small_ok = pg.small_ok; b.seeded = pg.seeded; b.tparts = pg.tparts; b.unit = pg.unit; b.seeds = pg.seeds;
     }
     PL_CHECK(pl_seg_launch_resolve(d_jobs, d_sj, n, stream));
     PL_CHECK(hipEventRecord(ctx->ev_prep, stream));
-    if (n_wg) PL_CHECK(pl_launch_engine(d_jobs, d_sel, n_wg, prm, stream));      /* (a mixed batch: the other engine's images, side by side with this one's) */
-    /* every row needs one attempt, every epoch one more; a bound far above anything real stops a runaway loop */
-    /* every row needs one attempt per strength it is tried at (pngloss_image.c:266-274: down to 0 in the worst case), every epoch two more (the
-     * attempt under way when its validation fails is void): a bound far above anything real, there to stop a runaway loop -- the stall
-     * detector of the launch thread is the other net.  (Seen: 1813 attempts for a 63 x 2 image at strength 200, all rows adaptive.) */
-    const long max_attempts = (long)std::min<double>(2.0e9, (double)max_h * ((double)params.strength + 1.0) * (2.0 + 2.0 * SEG_MAX_RESTARTS * SEG_NFILT) + 1024.0);
+    if (!plan.wg_list.empty()) PL_CHECK(pl_launch_engine(d_jobs, d_sel, plan.wg_list.size(), prm, stream));      /* (a mixed batch: the other engine's images, side by side with this one's) */
     ctx->seg_rc.store(PNGLOSS_SUCCESS, std::memory_order_relaxed);
     /* (round 5, measured with tools/gpu_r5_benchlegs.sh: the stream memory operation on the caller's stream is not free -- its queue polls the finished word while
      *  the engine runs -- : without it the headline frame is 1.4 % faster, the seeded 8192 x 8192 points up to 7 %.  The synchronous entry point has no use for it.) */
@@ -488,7 +395,7 @@ int run_seg_engine(pngloss_hip_ctx *ctx, const PlJob *d_jobs, const std::vector<
         }
     }
     ctx->seg_async_wait = waiting;
-    try { ctx->seg_worker = std::thread(seg_worker_main, ctx, gs, max_attempts); }
+    try { ctx->seg_worker = std::thread(seg_worker_main, ctx, gs, plan.max_attempts); }
     catch (...) { std::fprintf(stderr, "pngloss_hip: cannot start the launch thread\n"); for (int g = 0; g < ngroups; g++) words[2 * g] = (uint32_t)gs.b[g].n; return PNGLOSS_HIP_ERROR; }
     if (!waiting) {
         /* no stream memory operations on this device: wait for the launch loop here, and order the caller's stream behind the engine's */
@@ -533,7 +440,7 @@ EngineCalib engine_calib(int device, bool debug)
     bool ok = tmp && hipMalloc(&d_img, img.size() * 4) == hipSuccess && hipMalloc(&d_f, h) == hipSuccess;
     double ms[2] = { 0, 0 };
     for (int e = 0; e < 2 && ok; e++) {
-        ok = pngloss_hip_set_option(tmp, "engine", e == 0 ? "seg" : "wg") == PNGLOSS_SUCCESS;
+        tmp->opt_engine = e == 0 ? PlEnginePin::Seg : PlEnginePin::Wg;
         double best = 1e30;
         for (int rep = 0; rep < 3 && ok; rep++) {
             ok = hipMemcpy(d_img, img.data(), img.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
@@ -575,24 +482,17 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
     ctx->h_jobs.clear();
     ctx->n_last = 0;
     ctx->split_last = false;                                         /* (only a split host window sets it again: batch_host) */
-    /* drop empty images (the reference's loops simply do nothing for them) */
-    /* STRENGTH 0 has a row engine of its own (pl_rows.hip: nothing is quantised, the five candidate rows are the original row, what is left is the filter search):
-     * every image of the batch, unless a test pins another engine.  "rows" pins it (a no-op at other strengths). */
-    bool use_rows = false;
-    /* the pin of the row engine: the option of the ABI first; the environment variable is the tests' hook (the one hook read per call, once: here) */
-    const std::string em_s = !ctx->opt_engine.empty() ? ctx->opt_engine : std::string(std::getenv("PNGLOSS_HIP_ENGINE") ? std::getenv("PNGLOSS_HIP_ENGINE") : "");
-    const char *const em = em_s.empty() ? nullptr : em_s.c_str();
     const PlHooks &hk = ctx->hooks;
+    PlPlanInput in;
+    in.strength = strength; in.bleed = bleed; in.hooks = hk;
+    /* the pin of the row engine: the option of the ABI first; the environment variable is the tests' hook (the one hook read per call, once: here) */
+    const char *const env_engine = ctx->opt_engine == PlEnginePin::Auto ? std::getenv("PNGLOSS_HIP_ENGINE") : nullptr;
+    in.pin = ctx->opt_engine != PlEnginePin::Auto ? ctx->opt_engine : pl_engine_pin_of_env(env_engine);
+    const bool engine_named = ctx->opt_engine != PlEnginePin::Auto || (env_engine && *env_engine);
 #ifdef PL_DEBUG_FORCE_FILTER
-    const bool forced_filter = true;      /* (a debugging BUILD: candidate PL_DEBUG_FORCE_FILTER wins every row -- not the reference's bytes; pngloss_hip_version says so) */
-#else
-    const bool forced_filter = false;
+    in.forced_filter = PL_DEBUG_FORCE_FILTER;   /* (a debugging BUILD: candidate PL_DEBUG_FORCE_FILTER wins every row -- not the reference's bytes; pngloss_hip_version says so) */
 #endif
-    {
-        const bool free_choice = !em || std::strcmp(em, "auto") == 0 || std::strcmp(em, "rows") == 0;
-        use_rows = strength == 0 && free_choice && !forced_filter && !hk.force_careful;
-    }
-    if (use_rows) {
+    if (pl_rows_wanted(strength, in.pin, hk, in.forced_filter)) {
         /* the row-statistics engine keeps PL_ROWSTAT_WORDS counters per ROW of every image (5.6 MB per 1080p frame: 2.8 GB for 512 frames) -- the other engines need nothing
          * comparable.  A batch whose counters would not fit beside its images runs strength 0 the long way (the segment / workgroup engines) instead of failing: same bytes. */
         size_t rs = 0, free_b = 0, total_b = 0;
@@ -600,113 +500,44 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
         const size_t have = ctx->ws_bytes;                       /* (what the context's arena already holds counts as available) */
         if (rs > have && hipMemGetInfo(&free_b, &total_b) == hipSuccess && rs - have > free_b / 2) {
             if (hk.debug) std::fprintf(stderr, "pngloss_hip: strength 0: %zu MB of row counters against %zu MB free: using the other row engines for this batch\n", rs >> 20, free_b >> 20);
-            use_rows = false;
+            in.rows_fit = false;
         }
     }
+    for (size_t i = 0; i < n; i++) {
+        if (!images[i].d_rgba && images[i].width && images[i].height) return PNGLOSS_INVALID_ARGUMENT;
+        in.width.push_back(images[i].width);
+        in.height.push_back(images[i].height);
+    }
+    { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) == hipSuccess && cus > 0) in.cus = (double)cus; }
+    in.sync_call = ctx->sync_call; in.three_groups_ok = ctx->three_groups_ok; in.opt_launch_groups = ctx->opt_launch_groups;
+    in.stream_wait_used = g_stream_wait_used.load(std::memory_order_relaxed);
+    PlPlan plan = pl_plan_batch(in);
+    /* OPT-IN (PNGLOSS_HIP_CALIB=1) since it was measured inside bench.py: the probe is 2 - 6 ms of GPU work, and what it finds depends on what the process did before it
+     * (the clock governor follows the load: after the headline's steps the probe read the segment engine 1.3x slower against the other one than in a fresh process, the
+     * model sent 128 frames of 1080p to the wrong engine and the 256-frame batch lost 16 %: profiles/r06_host_side.txt).  A wrong calibration costs more than the constants
+     * of the reference box cost on a box of another kind; the CU count (deterministic) is always taken from the device. */
+    if (plan.seg_costed && !engine_named && n >= 2 && hk.calib > 0 && !t_calibrating) {
+        const EngineCalib cal = engine_calib(ctx->device, hk.debug);
+        in.cus = cal.cus; in.seg_scale = cal.seg; in.wg_scale = cal.wg;
+        plan = pl_plan_batch(in);
+    }
+    if (plan.seg_pin_unmet)
+        std::fprintf(stderr, "pngloss_hip: PNGLOSS_HIP_ENGINE=seg: nothing in this batch for the segment engine (widths beyond %u?); using the one-workgroup-per-image engine\n", SEG_MAX_WIDTH);
+    const bool use_rows = plan.use_rows, use_seg = !plan.seg_list.empty();
+    const std::vector<uint32_t> &wg_list = plan.wg_list;
     std::vector<size_t> offs;
     size_t total = align_up(sizeof(PlJob) * (n ? n : 1), 256);
     for (size_t i = 0; i < n; i++) {
-        if (!images[i].d_rgba && images[i].width && images[i].height) return PNGLOSS_INVALID_ARGUMENT;
         offs.push_back(total);
         total += image_ws(images[i].width ? images[i].width : 1, images[i].height, use_rows).total;
     }
-    /* Which row engine, IMAGE BY IMAGE: one workgroup for the image (pl_engine: batches, narrow images) or the image spread over the
-     * whole GPU (pl_seg: few wide images).  The segment engine takes every strength / bleed pair and rows up to SEG_MAX_WIDTH pixels;
-     * it pays off while the batch leaves it the machine (its work per row is ~250x redundant by design).  In a mixed batch the two
-     * engines run side by side -- the segment engine's images in one launch sequence (blockIdx.y = image) on the engine's own stream,
-     * the others as one workgroup each on the caller's.
-     * Cost model (measured on 1 .. 64 frames of 512x512 and 1920x1080, tests/tools/gpu_seg_batch.py): a row
-     * attempt of the segment engine takes ~38 us plus ~0.032 us per workgroup of its widest kernel (about 3 per segment and 40 more per
-     * image), whatever the width, and there are as many attempts as the tallest of its images has rows; the workgroup engine ~0.18 us
-     * per pixel of its largest image, all images side by side (256 CUs).  State sets beyond the lanes (s = 85 at bleed 1 or 2 ...) are
-     * enumerated from seeds with a run-in of one segment: about twice the enumeration and a wider chain.  Greedy: the images go to the
-     * segment engine in the order of their cost on the other one, as long as that shortens the batch. */
-    SegParams seg_params;
-    std::vector<uint8_t> on_seg(n, 0);
-    size_t n_seg = 0;
-    {
-        const bool forced = em && std::strcmp(em, "seg") == 0;
-        const bool allowed = !em || forced || std::strcmp(em, "auto") == 0 || std::strcmp(em, "rows") == 0;       /* "wg" / "lead" / "legacy": the one-workgroup-per-image engine */
-        bool seg_ok = n && allowed && !use_rows && !hk.force_careful && pl_seg_supported(nullptr, 0, strength, bleed, &seg_params);
-        if (seg_ok) {
-            EngineCalib cal;
-            /* OPT-IN (PNGLOSS_HIP_CALIB=1) since it was measured inside bench.py: the probe is 2 - 6 ms of GPU work, and what it finds depends on what the process did before it
-             * (the clock governor follows the load: after the headline's steps the probe read the segment engine 1.3x slower against the other one than in a fresh process, the
-             * model sent 128 frames of 1080p to the wrong engine and the 256-frame batch lost 16 %: profiles/r06_host_side.txt).  A wrong calibration costs more than the constants
-             * of the reference box cost on a box of another kind; the CU count (deterministic) is always taken from the device. */
-            if (!em && n >= 2 && hk.calib > 0 && !t_calibrating) cal = engine_calib(ctx->device, hk.debug);
-            else { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) == hipSuccess && cus > 0) cal.cus = (double)cus; }
-            const double cu_scale = 256.0 / cal.cus;
-            const double a_us = seg_params.seeded ? 82.0 : 38.0, w_us = seg_params.seeded ? 0.05 : 0.032;   /* (round 4: an attempt is four launches: 49.5 us at 4096 pixels = 424 workgroups in these units, 46 at 1920, 69 at 8192) */
-            /* round 5: a batch whose images have more than SEG_UNIT_MIN_SEGS segments between them is enumerated in UNITS, in two launch groups, with the
-             * small workgroups of batches (run_seg_engine): an attempt then takes ~45 us + 0.015 us per workgroup-unit, but not less than ~95 us (the
-             * dependent steps of a unit): 1080p frames 16 / 32 / 64 = 102 / 150 / 261 us measured (profiles/r05_unit_groups.txt) */
-            const bool can_units = !seg_params.seeded && seg_params.ns <= SEG_NSP;
-            auto attempt_us_ref = [&](double wgs, double segs, size_t k) {
-                const bool have_seeds = can_units && seg_params.seed_n > 0 && hk.seg_seeds != 0;
-                /* round 6, from seeds (per row of the tallest image, epochs included; 1080p frames, profiles/r06_seeds.txt): units 24 / 32 / 64 / 128 frames 105 / 114 / 168 / 301 us,
-                 * segment by segment 6 / 11 / 16 frames 61 / 76 / 90 us -- 128 frames 325 ms against 373 on the other engine, the crossover near 148 */
-                const bool seeds1_fit = have_seeds && k >= 2 && segs >= SEG_SEEDS1_MIN_SEGS && segs >= (double)SEG_SEEDS1_MIN_SEGS_PER_IMAGE * (double)k;
-                if (have_seeds && segs > (seeds1_fit ? SEG_UNIT_MIN_SEGS_SEEDS : SEG_UNIT_MIN_SEGS)) return std::max(100.0, 35.0 + 0.00945 * wgs);
-                if (seeds1_fit) return 43.0 + 0.0134 * wgs;
-                if (can_units && segs > SEG_UNIT_MIN_SEGS) return std::max(100.0, 28.0 + 0.0124 * wgs);   /* (three launch groups, validation in whole replay groups: 16 / 64 / 96 / 112 / 128 frames of 1080p 102 / 205 / 289 / 333 / 377 us: the segment engine up to 116 such frames -- measured: 112 frames 361 against 372 ms, 120 frames 385 against 372) */
-                /* (two or more images run as two launch sequences side by side: 4 / 8 / 12 frames of 1080p 58 / 80 / 102 us per attempt, profiles/r05_suite_groups.txt) */
-                if (k >= 2 && !seg_params.seeded) return 35.0 + 0.026 * wgs;
-                return a_us + w_us * wgs;
-            };
-            auto attempt_us = [&](double wgs, double segs, size_t k) { return cal.seg * attempt_us_ref(wgs * cu_scale, segs, k); };      /* (fewer CUs: every workgroup weighs more) */
-            auto wg_cost = [&](size_t i) { return cal.wg * 0.18 * (double)images[i].width * (double)images[i].height; };
-            std::vector<size_t> order;
-            for (size_t i = 0; i < n; i++)
-                if (images[i].width && images[i].height && images[i].width <= SEG_MAX_WIDTH) order.push_back(i);
-            std::sort(order.begin(), order.end(), [&](size_t x, size_t y) { return wg_cost(x) > wg_cost(y); });
-            if (forced) { for (size_t i : order) on_seg[i] = 1; n_seg = order.size(); }
-            else {
-                /* wg side: the largest image left sets its time (or the sum over 256 CUs when there are more images than CUs) */
-                double wg_sum = 0;
-                for (size_t i = 0; i < n; i++) wg_sum += wg_cost(i);
-                double seg_rows = 0, seg_wgs = 0, seg_segs = 0;
-                auto batch_us = [&](size_t k, double rows, double wgs, double wsum, double segs) {   /* the first k images of `order` on the segment engine */
-                    const double wg_us = k < order.size() ? std::max(wg_cost(order[k]), wsum / cal.cus) : wsum / cal.cus;
-                    const double seg_us = k ? rows * attempt_us(wgs, segs, k) : 0.0;
-                    /* side by side only while the other engine leaves the segment engine CUs to run on: its workgroups are persistent and own a CU each (104 KB of
-                     * LDS, every register) -- next to 200 and more of them the segment engine's launches wait until they are through: one after the other
-                     * (measured: 512 frames of 1080p in one call, 130 of them sent to the segment engine by the model of before: 1034 ms against 2 x 375) */
-                    if ((double)(n - k) > 0.75 * cal.cus) return wg_us + seg_us;
-                    return std::max(wg_us, seg_us);
-                };
-                double best = batch_us(0, 0, 0, wg_sum, 0);
-                size_t best_k = 0;
-                double wsum = wg_sum;
-                for (size_t k = 1; k <= order.size(); k++) {
-                    const size_t i = order[k - 1];
-                    seg_rows = std::max(seg_rows, (double)images[i].height);
-                    seg_wgs += 3.0 * ((images[i].width + SEG_L - 1) / SEG_L) + 40.0;
-                    seg_segs += (images[i].width + SEG_L - 1) / SEG_L;
-                    wsum -= wg_cost(i);
-                    if (seg_segs > 8192) break;
-                    const double t = batch_us(k, seg_rows, seg_wgs, wsum, seg_segs);
-                    if (t < best) { best = t; best_k = k; }
-                }
-                for (size_t k = 0; k < best_k; k++) on_seg[order[k]] = 1;
-                n_seg = best_k;
-            }
-        }
-        if (forced && !n_seg && n)
-            std::fprintf(stderr, "pngloss_hip: PNGLOSS_HIP_ENGINE=seg: nothing in this batch for the segment engine (widths beyond %u?); using the one-workgroup-per-image engine\n", SEG_MAX_WIDTH);
-    }
-    const bool use_seg = n_seg != 0;
-    std::vector<uint32_t> seg_list, wg_list;
-    for (size_t i = 0; i < n; i++) (on_seg[i] ? seg_list : wg_list).push_back((uint32_t)i);
-    /* the segment engine's images, tallest first: its launch groups are runs of this list (run_seg_engine), and the tallest image gets a sequence of its own when it stands out */
-    std::stable_sort(seg_list.begin(), seg_list.end(), [&](uint32_t x, uint32_t y) { return images[x].height > images[y].height; });
     std::vector<size_t> seg_offs;
     size_t seg_jobs_off = 0, seg_params_off = 0, sel_off = 0;
     if (use_seg) {
-        seg_jobs_off = total; total += align_up(sizeof(SegJob) * n_seg, 256);
+        seg_jobs_off = total; total += align_up(sizeof(SegJob) * plan.seg_list.size(), 256);
         seg_params_off = total; total += align_up(sizeof(SegParams), 256);
         sel_off = total; total += align_up(sizeof(uint32_t) * (wg_list.size() ? wg_list.size() : 1), 256);
-        for (uint32_t i : seg_list) { seg_offs.push_back(total); total += pl_seg_layout(images[i].width ? images[i].width : 1, (uint32_t)seg_params.nsp, seg_params.seeded != 0).total; }
+        for (uint32_t i : plan.seg_list) { seg_offs.push_back(total); total += pl_seg_layout(images[i].width ? images[i].width : 1, (uint32_t)plan.params.nsp, plan.params.seeded != 0).total; }
     }
     int rc = ensure_ws(ctx, total);
     if (rc) return rc;
@@ -754,13 +585,7 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
     prm.rbleed = recip_up_host(bleed);
     prm.r29 = 2.0f * recip_up_host(9);
     prm.force_careful = hk.force_careful;   /* test hook, see pl_device.h */
-    {
-        /* "legacy" = round-1 chains only */
-        prm.engine_mode = (em && std::strcmp(em, "legacy") == 0) ? 1 : ((em && std::strcmp(em, "lead") == 0) ? 2 : ((em && std::strcmp(em, "mix") == 0) ? 3 : 0));   /* "lead": never fall back adaptively; "mix": alternate every four rows */
-#ifdef PL_DEBUG_FORCE_FILTER
-        prm.engine_mode |= ((PL_DEBUG_FORCE_FILTER) + 1) << 8;   /* debugging build only */
-#endif
-    }
+    prm.engine_mode = plan.engine_mode;
 
     PL_CHECK(hipEventRecord(ctx->ev[0], stream));
     PL_CHECK(pl_launch_prepare(d_jobs, ctx->h_jobs.data(), n, stream, !use_rows));
@@ -775,12 +600,7 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
         d_sel = reinterpret_cast<const uint32_t *>(ctx->d_ws + sel_off);
     }
     if (use_seg) {
-#ifdef PL_DEBUG_FORCE_FILTER
-        seg_params.engine_flags = ((PL_DEBUG_FORCE_FILTER) + 1) << 8;   /* debugging build only */
-#endif
-        if (hk.segprof) seg_params.engine_flags |= 1;                                                   /* phase clocks of the validation kernel */
-        if (seg_params.seeded && hk.kin >= 0 && hk.kin <= SEG_KIN) seg_params.kin = hk.kin;             /* experiment: run-in pixels of the seeded enumeration */
-        rc = run_seg_engine(ctx, d_jobs, seg_list, seg_params, seg_offs, seg_jobs_off, seg_params_off, stream, d_sel, wg_list.size(), prm);
+        rc = run_seg_engine(ctx, d_jobs, plan, seg_offs, seg_jobs_off, seg_params_off, stream, d_sel, prm);
         if (rc) return rc;
     } else if (use_rows) PL_CHECK(pl_launch_rows(d_jobs, ctx->h_jobs.data(), n, stream));
     else PL_CHECK(pl_launch_engine(d_jobs, nullptr, n, prm, stream));
@@ -1023,7 +843,7 @@ pngloss_hip_ctx *pngloss_hip_create(int device)
     pngloss_hip_ctx *ctx = new (std::nothrow) pngloss_hip_ctx;
     if (!ctx) return nullptr;
     ctx->device = device;
-    ctx->hooks = PlHooks::from_env();
+    ctx->hooks = from_env();
     { static std::atomic<int> serial{ 0 }; ctx->pin_slot = std::max(device, serial.fetch_add(1)); }
     if (hipSetDevice(device) != hipSuccess) { delete ctx; return nullptr; }
     for (auto &e : ctx->ev)
@@ -1278,13 +1098,9 @@ static int batch_host(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images
 {
     if (!ctx || (n && !images)) return PNGLOSS_INVALID_ARGUMENT;
     ctx->split_last = false;
-    /* Chunks, each on its own context and stream, staggered by the staging turns: chunk k+1 is staged and uploaded while chunk k
-     * computes, chunk k is downloaded while chunk k+1 computes.  Measured on 256 x 1280x720 (profiles/r03_host_seam.txt): one chunk
-     * 0.237 s, two 0.221 s, four 0.218 s (the engine alone: 0.176 s) -- two it is; PNGLOSS_HIP_SPLIT=k for experiments. */
-    size_t K = n >= 16 ? 2 : 1;
-    if (ctx->hooks.split) K = (size_t)ctx->hooks.split;
-    if (K > n) K = n ? n : 1;
-    if (K <= 1 || zs || ctx->hooks.no_split) return batch_host_one(ctx, images, n, quantization_strength, bleed_divider, results, lines, zs);
+    /* chunks, each on its own context and stream, staggered by the staging turns (pl_host_window_chunks) */
+    size_t K = pl_host_window_chunks(n, ctx->hooks, zs != nullptr);
+    if (K <= 1) return batch_host_one(ctx, images, n, quantization_strength, bleed_divider, results, lines, zs);
     while (ctx->peers.size() < K - 1) {
         pngloss_hip_ctx *p = pngloss_hip_create(ctx->device);
         if (!p) break;
@@ -1292,19 +1108,9 @@ static int batch_host(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images
     }
     K = std::min(K, ctx->peers.size() + 1);
     if (K <= 1) return batch_host_one(ctx, images, n, quantization_strength, bleed_divider, results, lines, zs);
-    /* cut where the pixels are: equal shares */
-    size_t total = 0;
-    for (size_t i = 0; i < n; i++) total += (size_t)images[i].width * images[i].height;
-    std::vector<size_t> first(K + 1, n);
-    first[0] = 0;
-    {
-        size_t run = 0, c = 1;
-        for (size_t i = 0; i < n && c < K; i++) {
-            run += (size_t)images[i].width * images[i].height;
-            if (run * K >= total * c && i + 1 < n) first[c++] = i + 1;
-        }
-        for (; c < K; c++) first[c] = n;
-    }
+    std::vector<uint64_t> pixels(n);
+    for (size_t i = 0; i < n; i++) pixels[i] = (uint64_t)images[i].width * images[i].height;
+    const std::vector<size_t> first = pl_host_window_cut(pixels, K);
     std::vector<pngloss_hip_result> own;
     if (!results) { own.resize(n); results = own.data(); }
     HostTurns turns;
@@ -1706,10 +1512,7 @@ int pngloss_hip_set_option(pngloss_hip_ctx *ctx, const char *name, const char *v
     if (!ctx || !name || !value) return PNGLOSS_INVALID_ARGUMENT;
     if (ctx->pending) return PNGLOSS_INVALID_ARGUMENT;
     if (std::strcmp(name, "engine") == 0) {
-        static const char *const known[] = { "auto", "seg", "wg", "lead", "legacy", "mix", "rows" };
-        for (const char *k : known)
-            if (std::strcmp(value, k) == 0) { ctx->opt_engine = std::strcmp(value, "auto") == 0 ? "" : value; return PNGLOSS_SUCCESS; }
-        return PNGLOSS_INVALID_ARGUMENT;
+        return pl_engine_pin_parse(value, &ctx->opt_engine) ? PNGLOSS_SUCCESS : PNGLOSS_INVALID_ARGUMENT;
     }
     if (std::strcmp(name, "launch_groups") == 0) {
         /* launch groups of a large batch on the segment engine through the SYNCHRONOUS entry point: "auto" / "2" (default) or "3" -- for a process that never hands the

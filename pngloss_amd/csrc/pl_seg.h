@@ -7,12 +7,7 @@
 #include "pl_device.h"
 #include "pl_seg_core.h"
 
-/* per-image device workspace of the engine, beyond what PlJob already has (offsets into one 256-B aligned carve) */
-struct PlSegLayout { size_t ctl, base, h0, acc, err0, err1, rowcopy, tables, maps, ehash, rout, rst, rck, dnout, dcnt, entry, segcnt, grpcnt, grpleft, firstidx, rowmm, total; uint32_t nseg, ngrp; };
-PlSegLayout pl_seg_layout(uint32_t width, uint32_t nsp, bool seeded);   /* nsp, seeded: SegParams::nsp / ::seeded of the (strength, bleed) pair */
-
-/* can the engine take this batch?  (chain states of (strength, bleed) fit the lanes, every row fits the chain kernel) */
-bool pl_seg_supported(const uint32_t *widths, size_t n, unsigned strength, long bleed, SegParams *params_out);
+/* (the per-image device workspace of the engine, beyond what PlJob already has, and which batches it takes: pl_plan.h) */
 
 struct PlSegBatch {
     const SegJob *d_sj;       /* device: one per image */

@@ -212,8 +212,6 @@ __global__ __launch_bounds__(SEG_GT) void seg_k_gather_seeded(const SegJob *__re
     seg_gather_seeded_body(j, seg_view_of(sj + blockIdx.y, par, (int)(fc >> 2)), (int)(fc >> 2), (int)(fc & 3), (int)blk);
 }
 
-inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
 /* the kernels of the engine whose dynamic LDS can exceed 64 KB: opted in per device (pl_lds_optin) */
 hipError_t chain_attr()
 {
@@ -232,46 +230,6 @@ static_assert(SEG_SM_REPLAY <= 65536 && SEG_SM_ENUM_NT(1024) <= 65536 && SEG_SM_
 static_assert((SEG_TBL_WORDS + 1024 + 512) * 4 + SEG_UNIT * SEG_L * 4 * 8 <= SEG_SM_ENUM_UNIT && (SEG_TBL_WORDS + 1024 + 512) * 4 + SEG_L * 4 * 8 <= SEG_SM_ENUM_NT(512), "seg_first_body's carve fits the enumeration kernels' LDS");
 
 } // namespace
-
-PlSegLayout pl_seg_layout(uint32_t width, uint32_t nsp, bool seeded)
-{
-    PlSegLayout l{};
-    l.nseg = (width + SEG_L - 1) / SEG_L;
-    l.ngrp = (l.nseg + SEG_GRP - 1) / SEG_GRP;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o = align256(o + (bytes ? bytes : 4)); return at; };
-    l.ctl = take(3 * sizeof(SegCtl));
-    l.base = take(3 * SEG_NFILT * 256 * 4);
-    l.h0 = take(3 * 256 * 4);
-    l.acc = take(3 * sizeof(SegAcc));
-    l.err0 = take((size_t)width * 16);
-    l.err1 = take((size_t)width * 16);
-    l.rowcopy = take((size_t)width * 12);
-    l.tables = take((size_t)SEG_NFILT * SEG_TBL_WORDS * 4);
-    l.maps = take(seeded ? 0 : (size_t)SEG_NFILT * l.nseg * 4 * nsp * 2);
-    l.ehash = take(seeded ? (size_t)SEG_NFILT * l.nseg * 4 * SEG_EH_WORDS * 4 : 0);
-    l.rout = take((size_t)SEG_NFILT * l.nseg * 4 * SEG_NSP * 2);
-    l.rst = take((size_t)SEG_NFILT * l.nseg * 4 * SEG_NSP * 4);
-    l.rck = take((size_t)SEG_NFILT * l.nseg * 4 * SEG_NSP * (SEG_PARTS - 1) * 4);
-    l.dnout = take((size_t)SEG_NFILT * l.nseg * 4 * 2);
-    l.dcnt = take((size_t)SEG_NFILT * l.nseg * 4 * 4);
-    l.entry = take((size_t)SEG_NFILT * l.nseg * 4 * 4);
-    l.segcnt = take((size_t)SEG_NFILT * l.nseg * 256 * 2);
-    l.grpcnt = take((size_t)SEG_NFILT * l.ngrp * 256 * 4);
-    l.grpleft = take((size_t)SEG_NFILT * l.ngrp * 4);
-    l.firstidx = take(SEG_NFILT * 4 * 2 * 4);
-    l.rowmm = take(16);
-    l.total = o;
-    return l;
-}
-
-bool pl_seg_supported(const uint32_t *widths, size_t n, unsigned strength, long bleed, SegParams *params_out)
-{
-    if (bleed < 1 || bleed > 32767 || strength > 255) return false;
-    for (size_t i = 0; i < n; i++)
-        if (widths[i] > SEG_MAX_WIDTH) return false;
-    return seg_build_params(*params_out, (int)strength, (int)bleed);
-}
 
 hipError_t pl_seg_launch_resolve(const PlJob *d_jobs, SegJob *d_sj, size_t n, hipStream_t stream)
 {

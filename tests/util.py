@@ -249,6 +249,32 @@ def seg_host_lib():
     return _seg
 
 
+_plan = None
+
+
+def plan_host_lib():
+    """tests/c/plan_host.cpp (the batch plan of the library, pngloss_amd/csrc/pl_plan.h, behind a C ABI) built into a shared object (cached per process)."""
+    global _plan
+    if _plan is None:
+        import subprocess
+        import tempfile
+        so = os.path.join(tempfile.mkdtemp(prefix="plan_host_"), "libplan_host.so")
+        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-w", "-o", so, os.path.join(ROOT, "tests", "c", "plan_host.cpp")], check=True)
+        lib = C.CDLL(so)
+        lib.plan_host_run.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_long, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.plan_host_run.restype = None
+        lib.plan_host_enum_kind.argtypes = [C.c_size_t, C.c_size_t, C.c_uint, C.c_long, C.c_int, C.c_int, C.c_int]
+        lib.plan_host_enum_kind.restype = C.c_int
+        lib.plan_host_seed_n.argtypes = [C.c_uint, C.c_long]
+        lib.plan_host_seed_n.restype = C.c_int
+        lib.plan_host_parse_option.argtypes = [C.c_char_p]
+        lib.plan_host_parse_option.restype = C.c_int
+        lib.plan_host_window.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p]
+        lib.plan_host_window.restype = C.c_size_t
+        _plan = lib
+    return _plan
+
+
 def run_seg_host(img, s=19, b=2, filters=True):
     """The segment-parallel engine's kernel bodies on the CPU: returns rc, out, filters, stats
     (attempts, restarts, retried rows, serial rows, unique symbols, bpp, chain states, status)."""
