@@ -35,9 +35,6 @@
 #include <cstdio>
 #include <type_traits>
 
-#ifndef PL_SEGPROF
-#define PL_SEGPROF 0   /* timing experiments only: s_memtime stamps inside the chain loop (perturbs it) */
-#endif
 #ifndef PL_ABLATE
 #define PL_ABLATE 0   /* timing experiments only (tools/ablate.sh): >0 removes pieces of the chain, results become wrong */
 #endif
@@ -114,7 +111,8 @@ struct RowCtx {
     int s;
     float rq, rbleed, r29;
     uint32_t slow;            /* out: pixels that took the exact-repair slow path        */
-    unsigned long long seg[4];/* out (PL_SEGPROF): cycles in head+gather | reductions | check | tail */
+    unsigned long long seg[4];/* out, always 0 and read by nobody: left from a removed timing experiment.  chain_dispatch is __noinline__
+                                 and writes the RowCtx through a reference, so dropping the field and its stores changes the code object */
 };
 
 __device__ __forceinline__ uint32_t sad_u32(uint32_t a, uint32_t b)
@@ -189,7 +187,6 @@ __device__ __forceinline__ void chain_row(RowCtx &k, const int lane)
     const int upd_and = upd ? 255 : 0, upd_or = upd ? 0 : dummy;
     const bool sel0 = jl == 0, sel1 = jl == 1;          /* which earlier channel this lane checks                  */
     uint32_t slow = 0;
-    unsigned long long seg0 = 0, seg1 = 0, seg2 = 0, seg3 = 0, tprev = PL_SEGPROF ? __builtin_readcyclecounter() : 0;
 
     int left = 0, rem = 0, thr_prev = 0, thr_cur = 0;
 
@@ -242,8 +239,6 @@ __device__ __forceinline__ void chain_row(RowCtx &k, const int lane)
         auto pixel = [&](const int ii) {
             const int i = g + ii;
             const u32x4 rn = R[(((i + 1) & (PL_CHUNK - 1)) * 4 + c) * RS + half];   /* prefetch the next pixel's record */
-            unsigned long long tA = 0, tC = 0, tD = 0, tE = 0;
-            if (PL_SEGPROF) { tA = __builtin_readcyclecounter(); seg3 += tA - tprev; }
 
             /* ---- uniform per group: optimize_state.c:157-210 ---- */
             int osym, lo, predraw, filt;
@@ -299,7 +294,6 @@ __device__ __forceinline__ void chain_row(RowCtx &k, const int lane)
                     kk[t] = e[t].y + ((jj[t] == josym) ? 256u : 0u) + (uint32_t)(256 - jj[t]);
                     hm = max(hm, e[t].x);
                 }
-                if (PL_SEGPROF) { asm volatile("" : "+v"(hm)); tC = __builtin_readcyclecounter(); seg0 += tC - tA; }
                 Hwin = PL_ABLATE >= 4 ? hm : groupmax_u32<GL>(hm);
                 uint32_t km = 0;
 #pragma unroll
@@ -317,7 +311,6 @@ __device__ __forceinline__ void chain_row(RowCtx &k, const int lane)
                 }
                 K = groupmax_u32<GL>(km);
             }
-            if (PL_SEGPROF) { asm volatile("" : "+v"(K)); tD = __builtin_readcyclecounter(); seg1 += tD - tC; }
             int jwin = (int)((0u - K) & 255u);          /* K-1 = rank<<9 | flag<<8 | 255-j */
             int vwin = vmin + jwin;
 
@@ -403,7 +396,6 @@ __device__ __forceinline__ void chain_row(RowCtx &k, const int lane)
                 remv = pl_sext16((int)le);
                 thrv = (int)le >> 16;
             }
-            if (PL_SEGPROF) { asm volatile("" : "+v"(remv), "+v"(thrv)); tE = __builtin_readcyclecounter(); seg2 += tE - tD; tprev = tE; }
             thr_prev = thr_cur;
             thr_cur = thrv;
             rem = remv;
@@ -424,7 +416,7 @@ __device__ __forceinline__ void chain_row(RowCtx &k, const int lane)
         else serial_part(std::false_type{});
     }
     k.slow = slow;
-    k.seg[0] = seg0; k.seg[1] = seg1; k.seg[2] = seg2; k.seg[3] = seg3;
+    k.seg[0] = 0; k.seg[1] = 0; k.seg[2] = 0; k.seg[3] = 0;
 }
 
 template <int MODE, bool TR, bool WRAP>
@@ -1574,7 +1566,7 @@ __global__ __launch_bounds__(PL_ENGINE_THREADS) void pl_engine(const PlJob *jobs
     uint32_t adapt_backoff = 2u, adapt_last_lead = ~0u;
     unsigned long long lead_cyc[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     unsigned long long cyc_post = 0, cyc_commit = 0;      /* diagnostics */   /* diagnostics: vector | fast | exact | rescan | table build */
-    unsigned long long chain_cycles = 0, segs[4] = { 0, 0, 0, 0 };
+    unsigned long long chain_cycles = 0;
     int status = 0;
     for (uint32_t y = 0; y < H && !status; y++) {
         const bool adaptive = !j.row_filters || y == 0;   /* pngloss_image.c:210 */
@@ -1677,7 +1669,6 @@ __global__ __launch_bounds__(PL_ENGINE_THREADS) void pl_engine(const PlJob *jobs
                 chain_cycles += dtc;
                 if (lane == 0) atomicMax(&rowcyc, (uint32_t)min(dtc, 0xffffffffull));
                 slow_px += k.slow;
-                if (PL_SEGPROF) for (int q = 0; q < 4; q++) segs[q] += k.seg[q];
             }
             __syncthreads();   /* candidate rows (global, same CU) and histograms (LDS) complete and visible */
             if (lead_ok && (prm.engine_mode & 15) == 0) {
@@ -1854,40 +1845,39 @@ __global__ __launch_bounds__(PL_ENGINE_THREADS) void pl_engine(const PlJob *jobs
     if (nz) atomicAdd(&uniq, nz);
     __syncthreads();
     /* diagnostics: per chain wave, cycles spent in the serial chain (>>10) and pixels that needed the exact repair */
-    if (lane == 0 && wave < 4) {
-        j.result[8 + wave] = (int32_t)(chain_cycles >> 10);
-        j.result[12 + wave] = (int32_t)slow_px;
-        if (PL_SEGPROF) for (int q = 0; q < 4; q++) j.result[16 + wave * 4 + q] = (int32_t)(segs[q] >> 10);
+    if (lane == 0 && wave < PLR_WG_CHAIN_WAVES) {
+        j.result[PLR_WG_CHAIN_KCYC + wave] = (int32_t)(chain_cycles >> 10);
+        j.result[PLR_WG_SLOW_PX + wave] = (int32_t)slow_px;
     }
     if (lane == 0 && wave < PL_NFILT) {
-        for (int qq = 0; qq < 5; qq++) j.result[32 + wave * 5 + qq] = (int32_t)(lead_cyc[qq] >> 10);
-        j.result[57 + wave] = (int32_t)(lead_cyc[6] ? lead_cyc[5] / lead_cyc[6] : 0);
-        j.result[27 + wave] = (int32_t)(lead_cyc[7] >> 10);   /* flush + relation check */
-        if (!PL_SEGPROF) j.result[16 + wave] = (int32_t)light_px;   /* light pixels */
+        for (int qq = 0; qq < PLR_WG_PHASES; qq++) j.result[PLR_WG_PHASE_KCYC + wave * PLR_WG_PHASES + qq] = (int32_t)(lead_cyc[qq] >> 10);
+        j.result[PLR_WG_CYC_PER_PX + wave] = (int32_t)(lead_cyc[6] ? lead_cyc[5] / lead_cyc[6] : 0);
+        j.result[PLR_WG_FLUSH_KCYC + wave] = (int32_t)(lead_cyc[7] >> 10);   /* flush + relation check */
+        j.result[PLR_WG_LIGHT_PX + wave] = (int32_t)light_px;
     }
-    if (lane == 0 && wave == 0) { j.result[62] = (int32_t)(cyc_post >> 10); j.result[63] = (int32_t)(cyc_commit >> 10); }
+    if (lane == 0 && wave == 0) { j.result[PLR_WG_POST_KCYC] = (int32_t)(cyc_post >> 10); j.result[PLR_WG_COMMIT_KCYC] = (int32_t)(cyc_commit >> 10); }
     {   /* diagnostics: which SIMD each wave of the workgroup sits on (HW_ID bits 5:4), two bits per wave */
         uint32_t hwid;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
         if (lane == 0) atomicOr(&simd_map, ((hwid >> 4) & 3u) << (2 * wave));
     }
     __syncthreads();
-    if (tid == 0) j.result[7] = (int32_t)simd_map;
-    if (tid == 0) { j.result[22] = (int32_t)est_lead; j.result[23] = (int32_t)est_legacy; }
-    if (tid == 0) j.result[21] = (int32_t)adapt_legacy_rows;   /* rows that took the round-1 chains by the adaptive choice */
+    if (tid == 0) j.result[PLR_WG_SIMD_MAP] = (int32_t)simd_map;
+    if (tid == 0) { j.result[PLR_WG_EST_LEAD] = (int32_t)est_lead; j.result[PLR_WG_EST_LEGACY] = (int32_t)est_legacy; }
+    if (tid == 0) j.result[PLR_WG_ADAPT_LEGACY] = (int32_t)adapt_legacy_rows;
     if (lane == 0 && wave == 4) {
-        j.result[24] = (int32_t)(chain_cycles >> 10);
-        j.result[25] = (int32_t)slow_px;
-        j.result[26] = (int32_t)lead_rebuilds;
+        j.result[PLR_WG_W4_KCYC] = (int32_t)(chain_cycles >> 10);
+        j.result[PLR_WG_W4_SLOW_PX] = (int32_t)slow_px;
+        j.result[PLR_WG_W4_RESCANS] = (int32_t)lead_rebuilds;
     }
     if (tid == 0) {
-        j.result[0] = status;
-        j.result[1] = (int32_t)bpp;
-        j.result[2] = (int32_t)uniq;
-        j.result[3] = (int32_t)retried;
-        j.result[4] = (int32_t)slow_px;   /* wave 0's count of pixels that needed the exact channel repair / exact redo */
-        j.result[5] = (int32_t)lead_rows;  /* row attempts that ran the band-leader chains */
-        j.result[6] = (int32_t)lead_rebuilds;
+        j.result[PLR_STATUS] = status;
+        j.result[PLR_BPP] = (int32_t)bpp;
+        j.result[PLR_UNIQUE] = (int32_t)uniq;
+        j.result[PLR_RETRIED] = (int32_t)retried;
+        j.result[PLR_REPAIRED] = (int32_t)slow_px;   /* wave 0's count of pixels that needed the exact channel repair / exact redo */
+        j.result[PLR_WG_LEAD_ROWS] = (int32_t)lead_rows;
+        j.result[PLR_WG_RESCANS] = (int32_t)lead_rebuilds;
     }
 }
 

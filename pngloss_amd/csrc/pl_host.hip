@@ -119,7 +119,7 @@ struct pngloss_hip_ctx {
     int seg_prio = 0;
     bool seg_prio_distinct = false;
 
-    int last_engine = 0;            /* 0 = one workgroup per image (pl_engine), 3 = segment-parallel (pl_seg) */
+    std::vector<uint8_t> engine;    /* per image of the last batch: the row engine its plan gave it (PLR_ENGINE_*, pl_result.h) */
     long seg_attempts = 0;
 };
 
@@ -589,7 +589,8 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
 
     PL_CHECK(hipEventRecord(ctx->ev[0], stream));
     PL_CHECK(pl_launch_prepare(d_jobs, ctx->h_jobs.data(), n, stream, !use_rows));
-    ctx->last_engine = use_seg ? 3 : (use_rows ? 4 : 0);
+    ctx->engine.assign(n, (uint8_t)(use_rows ? PLR_ENGINE_ROWS : PLR_ENGINE_WG));
+    for (uint32_t i : plan.seg_list) ctx->engine[i] = (uint8_t)PLR_ENGINE_SEG;
     PL_CHECK(hipEventRecord(ctx->ev[1], stream));
     /* the images of the one-workgroup-per-image engine: all of them, or -- a mixed batch -- those the segment engine did not get; they
      * run on the caller's stream while the segment engine works on its own */
@@ -623,6 +624,77 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
     return PNGLOSS_SUCCESS;
 }
 
+/* PNGLOSS_HIP_DEBUG / PNGLOSS_HIP_SEGPROF: what the row engine did for image i of the batch just finished, from its record r (pl_result.h) and the
+ * engine the plan gave it.  tools/ab_*.sh grep these lines ("engine [0-9.]* ms"). */
+void print_engine_report(const pngloss_hip_ctx *ctx, size_t i, const int32_t *r, int engine)
+{
+    const PlHooks &hk = ctx->hooks;
+    if (i == 0 && hk.debug) std::fprintf(stderr, "pngloss_hip: row engine occupancy query: %d workgroups per CU\n", pl_engine_occupancy());
+    if (engine == PLR_ENGINE_SEG) {
+        if (hk.debug)
+            std::fprintf(stderr, "pngloss_hip: image %zu: segment-parallel engine: %d attempts for %u rows, %d epochs (validation restarts), %d rows finished serially, candidate none dropped by its cost bound %d times, %d segments walked step by step by the chain kernel, engine %.3f ms\n",
+                         i, r[PLR_SEG_ATTEMPTS], ctx->h_jobs[i].height, r[PLR_REPAIRED], r[PLR_SEG_SERIAL_ROWS], r[PLR_SEG_NONE_DROPPED], r[PLR_SEG_WALKED], ctx->engine_ms);
+        if (!hk.segprof) return;
+        /* the phase clocks (100 MHz ticks), in us: the slowest workgroup, and the average over the `runs` workgroups that added to a sum */
+        auto mx = [&](int slot) { return r[slot] / 100.0; };
+        auto avg = [&](int sum, int runs) { return (uint32_t)r[sum] / 100.0 / (uint32_t)r[runs]; };
+        const int cand = PLR_SEG_CAND_RUNS, commit = PLR_SEG_COMMIT_RUNS, en = PLR_SEG_ENUM_RUNS, ch = PLR_SEG_CHAIN_RUNS, val = PLR_SEG_VAL_RUNS;
+        std::fprintf(stderr, "pngloss_hip:   validation kernel, slowest workgroup per phase (us): load %.1f  pass1 %.1f  watched bins + pass3 %.1f  none bound %.1f  sums %.1f; pending decisions %d\n",
+                     mx(PLR_SEG_VAL_MAX), mx(PLR_SEG_VAL_MAX + 1), mx(PLR_SEG_VAL_MAX + 2), mx(PLR_SEG_VAL_MAX + 3), mx(PLR_SEG_VAL_MAX + 4), r[PLR_SEG_VAL_PENDING]);
+        std::fprintf(stderr, "pngloss_hip:   control kernel, slowest (us): candidate workgroup up to the table build %.1f, table build %.1f, commit workgroup %.1f\n",
+                     mx(PLR_SEG_CTL_MAX), mx(PLR_SEG_CTL_MAX + 1), mx(PLR_SEG_CTL_MAX + 2));
+        if (r[cand] && r[commit])
+            std::fprintf(stderr, "pngloss_hip:   ... average (us): candidate workgroup up to the table build %.2f, table build %.2f, commit workgroup %.2f\n",
+                         avg(PLR_SEG_CAND_SUM, cand), avg(PLR_SEG_CAND_SUM + 1, cand), avg(PLR_SEG_COMMIT_SUM, commit));
+        if (r[cand])
+            std::fprintf(stderr, "pngloss_hip:   ... candidate workgroup, average (us): requests + copy %.2f, decision %.2f, new histogram + fields %.2f\n",
+                         avg(PLR_SEG_CAND_REQ_SUM, cand), avg(PLR_SEG_CAND_DECIDE_SUM, cand), avg(PLR_SEG_CAND_HIST_SUM, cand));
+        if (r[cand])
+            std::fprintf(stderr, "pngloss_hip:   ... commit workgroup, average (us): requests + copy %.2f, decision %.2f, terms %.2f, rows + extremes %.2f\n",
+                         avg(PLR_SEG_COMMIT_REQ_SUM, commit), avg(PLR_SEG_COMMIT_DECIDE_SUM, commit), avg(PLR_SEG_COMMIT_TERMS_SUM, commit), avg(PLR_SEG_COMMIT_ROWS_SUM, commit));
+        if (r[cand])
+            std::fprintf(stderr, "pngloss_hip:   ... table build, average (us): keys %.2f, classes %.2f, entries + write %.2f\n",
+                         avg(PLR_SEG_TABLE_SUM, cand), avg(PLR_SEG_TABLE_SUM + 1, cand), avg(PLR_SEG_TABLE_SUM + 2, cand));
+        if (r[en])
+            std::fprintf(stderr, "pngloss_hip:   enumeration workgroups (us), slowest / average: load %.1f / %.2f  first steps (%d, or %d for a state set of one chunk) + dedupe %.1f / %.2f  remaining steps %.1f / %.2f  map %.1f / %.2f; distinct states per channel after the dedupe %.1f; first-segment walker %.1f / %.2f\n",
+                         mx(PLR_SEG_ENUM_MAX), avg(PLR_SEG_ENUM_SUM, en), SEG_K1, SEG_K1_ONE_CHUNK, mx(PLR_SEG_ENUM_MAX + 1), avg(PLR_SEG_ENUM_SUM + 1, en),
+                         mx(PLR_SEG_ENUM_MAX + 2), avg(PLR_SEG_ENUM_SUM + 2, en), mx(PLR_SEG_ENUM_MAX + 3), avg(PLR_SEG_ENUM_SUM + 3, en),
+                         (uint32_t)r[PLR_SEG_ENUM_STATES] / 4.0 / (uint32_t)r[en], mx(PLR_SEG_FIRST_MAX), r[PLR_SEG_FIRST_RUNS] ? avg(PLR_SEG_FIRST_SUM, PLR_SEG_FIRST_RUNS) : 0.0);
+        if (r[ch])
+            std::fprintf(stderr, "pngloss_hip:   chain workgroups (us), slowest / average: gather %.1f / %.2f  compose %.1f / %.2f  walk %.1f / %.2f  tail %.1f / %.2f; %u runs, %u through the serial walk, %u at the wide stride\n",
+                         mx(PLR_SEG_CHAIN_MAX), avg(PLR_SEG_CHAIN_SUM, ch), mx(PLR_SEG_CHAIN_MAX + 1), avg(PLR_SEG_CHAIN_SUM + 1, ch), mx(PLR_SEG_CHAIN_MAX + 2), avg(PLR_SEG_CHAIN_SUM + 2, ch),
+                         mx(PLR_SEG_CHAIN_MAX + 3), avg(PLR_SEG_CHAIN_SUM + 3, ch), (uint32_t)r[ch], (uint32_t)r[PLR_SEG_WALKED], (uint32_t)r[PLR_SEG_CHAIN_WIDE]);
+        if (r[val])
+            std::fprintf(stderr, "pngloss_hip:   ... average per workgroup (us): load %.2f  pass1 %.2f  watched bins + pass3 %.2f  none bound %.2f  sums %.2f  (%u workgroup runs)\n",
+                         avg(PLR_SEG_VAL_SUM, val), avg(PLR_SEG_VAL_SUM + 1, val), avg(PLR_SEG_VAL_SUM + 2, val), avg(PLR_SEG_VAL_SUM + 3, val), avg(PLR_SEG_VAL_SUM + 4, val), (uint32_t)r[val]);
+        return;
+    }
+    /* the workgroup engine's slots (the row-statistics engine leaves them 0) */
+    if (!hk.debug) return;
+    const int32_t *kc = r + PLR_WG_CHAIN_KCYC, *slow = r + PLR_WG_SLOW_PX, *light = r + PLR_WG_LIGHT_PX, *flush = r + PLR_WG_FLUSH_KCYC, *cpp = r + PLR_WG_CYC_PER_PX;
+    const bool lead = r[PLR_WG_LEAD_ROWS] != 0;
+    std::fprintf(stderr, "pngloss_hip: image %zu: chain kcycles per wave %d %d %d %d, repaired pixels %d %d %d %d, engine %.3f ms\n", i,
+                 kc[0], kc[1], kc[2], kc[3], slow[0], slow[1], slow[2], slow[3], ctx->engine_ms);
+    std::fprintf(stderr, "pngloss_hip: image %zu: band-leader row attempts %d, wave 4 kcycles %d, exact redos %d, band rescans (wave 0 / 4) %d %d\n", i,
+                 r[PLR_WG_LEAD_ROWS], r[PLR_WG_W4_KCYC], r[PLR_WG_W4_SLOW_PX], r[PLR_WG_RESCANS], r[PLR_WG_W4_RESCANS]);
+    if (lead)
+        for (int w = 0; w < PLR_WG_WAVES; w++) {
+            const int32_t *ph = r + PLR_WG_PHASE_KCYC + PLR_WG_PHASES * w;
+            std::fprintf(stderr, "pngloss_hip:   wave %d (%s) kcycles: vector %d  fast groups %d  exact redo %d  rescan %d  table build %d\n", w,
+                         w == 0 ? "up" : (w == 1 ? "sub" : (w == 2 ? "average" : (w == 3 ? "paeth" : "none"))), ph[0], ph[1], ph[2], ph[3], ph[4]);
+        }
+    if (lead)
+        std::fprintf(stderr, "pngloss_hip:   cycles per pixel of undisturbed whole-chunk runs (up sub average paeth none): %d %d %d %d %d\n", cpp[0], cpp[1], cpp[2], cpp[3], cpp[4]);
+    std::fprintf(stderr, "pngloss_hip:   wave 0 kcycles in the post pass %d, in the commit pass %d; flush + relation check per chain wave %d %d %d %d %d\n",
+                 r[PLR_WG_POST_KCYC], r[PLR_WG_COMMIT_KCYC], flush[0], flush[1], flush[2], flush[3], flush[4]);
+    const int32_t m = r[PLR_WG_SIMD_MAP];
+    std::fprintf(stderr, "pngloss_hip:   SIMD of waves 0..7: %d %d %d %d %d %d %d %d\n", m & 3, (m >> 2) & 3, (m >> 4) & 3, (m >> 6) & 3,
+                 (m >> 8) & 3, (m >> 10) & 3, (m >> 12) & 3, (m >> 14) & 3);
+    if (lead)
+        std::fprintf(stderr, "pngloss_hip:   light pixels per chain wave %d %d %d %d %d; rows on the round-1 chains by the adaptive choice %d (last cycles per pixel: band-leader %d, round-1 %d)\n",
+                     light[0], light[1], light[2], light[3], light[4], r[PLR_WG_ADAPT_LEGACY], r[PLR_WG_EST_LEAD], r[PLR_WG_EST_LEGACY]);
+}
+
 int finish(pngloss_hip_ctx *ctx, pngloss_hip_result *results, size_t n)
 {
     if (!ctx) return PNGLOSS_INVALID_ARGUMENT;
@@ -638,7 +710,7 @@ int finish(pngloss_hip_ctx *ctx, pngloss_hip_result *results, size_t n)
         seg_rc = ctx->seg_rc.load(std::memory_order_acquire);
     }
     PL_CHECK(hipEventSynchronize(ctx->ev[3]));
-    if (ctx->last_engine == 3) for (int g = 0; g < SEG_MAX_GROUPS; g++) if (ctx->seg_gstream[g]) PL_CHECK(hipStreamSynchronize(ctx->seg_gstream[g]));   /* (attempts queued behind the last row: they find the images finished) */
+    if (std::find(ctx->engine.begin(), ctx->engine.end(), (uint8_t)PLR_ENGINE_SEG) != ctx->engine.end()) for (int g = 0; g < SEG_MAX_GROUPS; g++) if (ctx->seg_gstream[g]) PL_CHECK(hipStreamSynchronize(ctx->seg_gstream[g]));   /* (attempts queued behind the last row: they find the images finished) */
     ctx->pending = false;
     if (seg_rc) return seg_rc;
     float ms = 0.f;
@@ -646,75 +718,17 @@ int finish(pngloss_hip_ctx *ctx, pngloss_hip_result *results, size_t n)
     ctx->engine_ms = ms;
     PL_CHECK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[3]));
     ctx->total_ms = ms;
-    if (ctx->hooks.debug) std::fprintf(stderr, "pngloss_hip: row engine occupancy query: %d workgroups per CU\n", pl_engine_occupancy());
     int worst = PNGLOSS_SUCCESS;
     for (size_t i = 0; i < ctx->n_last; i++) {
-        int32_t r[64] = { 0 };
+        int32_t r[PLR_WORDS] = { 0 };
         PL_CHECK(hipMemcpy(r, ctx->h_jobs[i].result, sizeof r, hipMemcpyDeviceToHost));
-        if (results && i < n) results[i] = pngloss_hip_result{ r[0], (uint32_t)r[1], (uint32_t)r[2], (uint32_t)r[3], (uint32_t)r[4] };
-        if (r[20] == 3) {
-            if (ctx->hooks.debug)
-                std::fprintf(stderr, "pngloss_hip: image %zu: segment-parallel engine: %d attempts for %u rows, %d epochs (validation restarts), %d rows finished serially, candidate none dropped by its cost bound %d times, %d segments walked step by step by the chain kernel, engine %.3f ms\n",
-                             i, r[5], ctx->h_jobs[i].height, r[4], r[6], r[7], r[17], ctx->engine_ms);
-            if (ctx->hooks.segprof)
-                std::fprintf(stderr, "pngloss_hip:   validation kernel, slowest workgroup per phase (us): load %.1f  pass1 %.1f  watched bins + pass3 %.1f  none bound %.1f  sums %.1f; pending decisions %d, largest reach %d\n",
-                             r[40] / 100.0, r[41] / 100.0, r[42] / 100.0, r[43] / 100.0, r[44] / 100.0, r[46], r[47]);
-            if (ctx->hooks.segprof)
-                std::fprintf(stderr, "pngloss_hip:   control kernel, slowest (us): candidate workgroup up to the table build %.1f, table build %.1f, commit workgroup %.1f\n", r[56] / 100.0, r[57] / 100.0, r[58] / 100.0);
-            if (ctx->hooks.segprof && r[61] && r[63])
-                std::fprintf(stderr, "pngloss_hip:   ... average (us): candidate workgroup up to the table build %.2f, table build %.2f, commit workgroup %.2f\n",
-                             (uint32_t)r[59] / 100.0 / (uint32_t)r[61], (uint32_t)r[60] / 100.0 / (uint32_t)r[61], (uint32_t)r[62] / 100.0 / (uint32_t)r[63]);
-            if (ctx->hooks.segprof && r[61])
-                std::fprintf(stderr, "pngloss_hip:   ... candidate workgroup, average (us): requests + copy %.2f, decision %.2f, new histogram + fields %.2f\n",
-                             (uint32_t)r[19] / 100.0 / (uint32_t)r[61], (uint32_t)r[21] / 100.0 / (uint32_t)r[61], (uint32_t)r[22] / 100.0 / (uint32_t)r[61]);
-            if (ctx->hooks.segprof && r[61])
-                std::fprintf(stderr, "pngloss_hip:   ... commit workgroup, average (us): requests + copy %.2f, decision %.2f, terms %.2f, rows + extremes %.2f\n",
-                             (uint32_t)r[23] / 100.0 / (uint32_t)r[63], (uint32_t)r[45] / 100.0 / (uint32_t)r[63], (uint32_t)r[54] / 100.0 / (uint32_t)r[63], (uint32_t)r[55] / 100.0 / (uint32_t)r[63]);
-            if (ctx->hooks.segprof && r[61])
-                std::fprintf(stderr, "pngloss_hip:   ... table build, average (us): keys %.2f, classes %.2f, entries + write %.2f\n",
-                             (uint32_t)r[37] / 100.0 / (uint32_t)r[61], (uint32_t)r[38] / 100.0 / (uint32_t)r[61], (uint32_t)r[39] / 100.0 / (uint32_t)r[61]);
-            if (ctx->hooks.segprof && r[32])
-                std::fprintf(stderr, "pngloss_hip:   enumeration workgroups (us), slowest / average: load %.1f / %.2f  first steps (%d, or %d for a state set of one chunk) + dedupe %.1f / %.2f  remaining steps %.1f / %.2f  map %.1f / %.2f; distinct states per channel after the dedupe %.1f; first-segment walker %.1f / %.2f\n",
-                             r[24] / 100.0, (uint32_t)r[28] / 100.0 / (uint32_t)r[32], SEG_K1, SEG_K1_ONE_CHUNK, r[25] / 100.0, (uint32_t)r[29] / 100.0 / (uint32_t)r[32], r[26] / 100.0, (uint32_t)r[30] / 100.0 / (uint32_t)r[32],
-                             r[27] / 100.0, (uint32_t)r[31] / 100.0 / (uint32_t)r[32], (uint32_t)r[33] / 4.0 / (uint32_t)r[32], r[34] / 100.0, r[36] ? (uint32_t)r[35] / 100.0 / (uint32_t)r[36] : 0.0);
-            if (ctx->hooks.segprof && r[16])
-                std::fprintf(stderr, "pngloss_hip:   chain workgroups (us), slowest / average: gather %.1f / %.2f  compose %.1f / %.2f  walk %.1f / %.2f  tail %.1f / %.2f; %u runs, %u through the serial walk, %u at the wide stride\n",
-                             r[8] / 100.0, (uint32_t)r[12] / 100.0 / (uint32_t)r[16], r[9] / 100.0, (uint32_t)r[13] / 100.0 / (uint32_t)r[16], r[10] / 100.0, (uint32_t)r[14] / 100.0 / (uint32_t)r[16],
-                             r[11] / 100.0, (uint32_t)r[15] / 100.0 / (uint32_t)r[16], (uint32_t)r[16], (uint32_t)r[17], (uint32_t)r[18]);
-            if (ctx->hooks.segprof && r[53])
-                std::fprintf(stderr, "pngloss_hip:   ... average per workgroup (us): load %.2f  pass1 %.2f  watched bins + pass3 %.2f  none bound %.2f  sums %.2f  (%u workgroup runs)\n",
-                             (uint32_t)r[48] / 100.0 / (uint32_t)r[53], (uint32_t)r[49] / 100.0 / (uint32_t)r[53], (uint32_t)r[50] / 100.0 / (uint32_t)r[53], (uint32_t)r[51] / 100.0 / (uint32_t)r[53],
-                             (uint32_t)r[52] / 100.0 / (uint32_t)r[53], (uint32_t)r[53]);
-            if (r[0]) { std::fprintf(stderr, "pngloss_hip: image %zu: no acceptable filter row (device status %d)\n", i, r[0]); worst = PNGLOSS_INTERNAL_ABORT; }
-            if (results && i < n) results[i].repaired_pixels = (uint32_t)r[4];
-            continue;
-        }
-        if (ctx->hooks.debug)
-            std::fprintf(stderr, "pngloss_hip: image %zu: chain kcycles per wave %d %d %d %d, repaired pixels %d %d %d %d, engine %.3f ms\n", i,
-                         r[8], r[9], r[10], r[11], r[12], r[13], r[14], r[15], ctx->engine_ms);
-        if (ctx->hooks.debug)
-            std::fprintf(stderr, "pngloss_hip: image %zu: band-leader row attempts %d, wave 4 kcycles %d, exact redos %d, band rescans (wave 0 / 4) %d %d\n", i,
-                         r[5], r[24], r[25], r[6], r[26]);
-        if (ctx->hooks.debug && r[5])
-            for (int w = 0; w < 5; w++)
-                std::fprintf(stderr, "pngloss_hip:   wave %d (%s) kcycles: vector %d  fast groups %d  exact redo %d  rescan %d  table build %d\n", w,
-                             w == 0 ? "up" : (w == 1 ? "sub" : (w == 2 ? "average" : (w == 3 ? "paeth" : "none"))),
-                             r[32 + 5 * w], r[33 + 5 * w], r[34 + 5 * w], r[35 + 5 * w], r[36 + 5 * w]);
-        if (ctx->hooks.debug && r[5])
-            std::fprintf(stderr, "pngloss_hip:   cycles per pixel of undisturbed whole-chunk runs (up sub average paeth none): %d %d %d %d %d\n", r[57], r[58], r[59], r[60], r[61]);
-        if (ctx->hooks.debug)
-            std::fprintf(stderr, "pngloss_hip:   wave 0 kcycles in the post pass %d, in the commit pass %d; flush + relation check per chain wave %d %d %d %d %d\n", r[62], r[63], r[27], r[28], r[29], r[30], r[31]);
-        if (ctx->hooks.debug)
-            std::fprintf(stderr, "pngloss_hip:   SIMD of waves 0..7: %d %d %d %d %d %d %d %d\n", r[7] & 3, (r[7] >> 2) & 3, (r[7] >> 4) & 3, (r[7] >> 6) & 3,
-                         (r[7] >> 8) & 3, (r[7] >> 10) & 3, (r[7] >> 12) & 3, (r[7] >> 14) & 3);
-        if (ctx->hooks.debug && r[5])
-            std::fprintf(stderr, "pngloss_hip:   light pixels per chain wave %d %d %d %d %d; rows on the round-1 chains by the adaptive choice %d (last cycles per pixel: band-leader %d, round-1 %d)\n", r[16], r[17], r[18], r[19], r[20], r[21], r[22], r[23]);
-        if (ctx->hooks.segprof && r[16])   /* (engine built with PL_SEGPROF) */
-            for (int w = 0; w < 4; w++)
-                std::fprintf(stderr, "pngloss_hip:   wave %d segments kcycles: head+gather %d  reductions %d  check+lut %d  tail %d\n", w,
-                             r[16 + 4 * w], r[17 + 4 * w], r[18 + 4 * w], r[19 + 4 * w]);
-        if (r[0]) {
-            std::fprintf(stderr, "pngloss_hip: image %zu: no acceptable filter row (device status %d)\n", i, r[0]);
+        pngloss_hip_result res;
+        int32_t info[PLR_INFO_WORDS];
+        pl_result_decode(r, ctx->engine[i], &res, info);
+        if (results && i < n) results[i] = res;
+        if (ctx->hooks.debug || ctx->hooks.segprof) print_engine_report(ctx, i, r, ctx->engine[i]);
+        if (res.status) {
+            std::fprintf(stderr, "pngloss_hip: image %zu: no acceptable filter row (device status %d)\n", i, res.status);
             worst = PNGLOSS_INTERNAL_ABORT;
         }
     }
@@ -1533,17 +1547,16 @@ void *pngloss_hip_pinned_alloc(size_t bytes)
 
 void pngloss_hip_pinned_free(void *p) { if (p) (void)hipHostFree(p); }
 
-int pngloss_hip_last_engine_info(pngloss_hip_ctx *ctx, size_t index, int32_t info[8])
+int pngloss_hip_last_engine_info(pngloss_hip_ctx *ctx, size_t index, int32_t info[PLR_INFO_WORDS])
 {
     ctx = chunk_of(ctx, index);
     if (!ctx || !info || index >= ctx->n_last || ctx->pending) return PNGLOSS_INVALID_ARGUMENT;
     PL_CHECK(hipSetDevice(ctx->device));
-    int32_t r[64] = { 0 };
+    int32_t r[PLR_WORDS] = { 0 };
     PL_CHECK(hipMemcpy(r, ctx->h_jobs[index].result, sizeof r, hipMemcpyDeviceToHost));
-    for (int i = 0; i < 8; i++) info[i] = 0;
-    if (r[20] == 3) { info[0] = 3; info[1] = r[5]; info[2] = r[4]; info[3] = r[6]; info[4] = r[7]; info[5] = r[17]; info[6] = ctx->seg_groups; info[7] = ctx->seg_async_wait ? 1 : 0; }
-    else if (r[20] == 4) { info[0] = 4; info[1] = r[5]; }
-    else { info[0] = 0; info[1] = r[5]; info[2] = r[4]; info[3] = r[21]; }
+    pngloss_hip_result res;
+    pl_result_decode(r, ctx->engine[index], &res, info);
+    if (ctx->engine[index] == PLR_ENGINE_SEG) { info[PLR_INFO_LAUNCH_GROUPS] = ctx->seg_groups; info[PLR_INFO_STREAM_WAIT] = ctx->seg_async_wait ? 1 : 0; }
     return PNGLOSS_SUCCESS;
 }
 

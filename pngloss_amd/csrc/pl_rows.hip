@@ -185,12 +185,12 @@ __global__ __launch_bounds__(64) void pl_rows_decide(const PlJob *__restrict__ j
         for (int q = 0; q < 4; q++) j.orig_hist[f * PL_NSYM + lane + 64 * q] = O[f][q];                /* (pl_hist is not run for this engine: pngloss_hip_last_histogram reads this) */
     }
     nz = rows_wave_sum(nz);
-    if (lane < 64) { j.result[lane] = 0; }
+    if (lane < PLR_WORDS) { j.result[lane] = 0; }
     __builtin_amdgcn_s_waitcnt(0);
     if (lane == 0) {
-        j.result[0] = (int32_t)status; j.result[1] = (int32_t)bpp; j.result[2] = (int32_t)nz; j.result[3] = 0;
-        j.result[5] = (int32_t)height;                           /* "row attempts": one per row */
-        j.result[20] = 4;                                        /* engine id: row statistics (strength 0) */
+        j.result[PLR_STATUS] = (int32_t)status; j.result[PLR_BPP] = (int32_t)bpp; j.result[PLR_UNIQUE] = (int32_t)nz; j.result[PLR_RETRIED] = 0;
+        j.result[PLR_ROWS_ROWS] = (int32_t)height;
+        j.result[PLR_ENGINE_ID] = PLR_ENGINE_ROWS;               /* (not read by the host: the batch plan says which engine ran) */
     }
 }
 

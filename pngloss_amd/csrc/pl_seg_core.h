@@ -51,6 +51,8 @@
 #include <stddef.h>
 #include <string.h>
 
+#include "pl_result.h"
+
 #if defined(__HIPCC__)
 #define PLS_HD __host__ __device__ __forceinline__
 #else
@@ -126,12 +128,6 @@ typedef SEG_AS_LDS uint16_t *seg_lds_u16;
 #define PLS_UNROLL
 #endif
 #define SEG_NFILT 5
-#ifndef SEG_EXPERIMENT_WG_SPAN
-#define SEG_EXPERIMENT_WG_SPAN 0    /* experiment build (tools/replay_clocks.sh, EXP_DEFS=-DSEG_EXPERIMENT_WG_SPAN=1): when the enumeration's workgroups start and end, relative to the launch's first */
-#endif
-#ifndef SEG_EXPERIMENT_REPLAY_CLOCKS
-#define SEG_EXPERIMENT_REPLAY_CLOCKS 0   /* (1: an experiment build in which the REPLAY's phase clocks take the enumeration's slots of the result record; tools/replay_clocks.sh) */
-#endif
 #ifndef SEG_DEBUG_ROW
 #define SEG_DEBUG_ROW(kind, failed, winner, start_none)
 #endif
@@ -333,7 +329,7 @@ struct SegJob {
     SEG_AS_GLB uint32_t *rowcopy;        /* [3][W]: the ORIGINAL pixels of rows y-1, y, y+1 (row r in copy r % 3): the image row itself is committed in place while
                                             the validation of that very row is still running, and a row attempt that is repeated wants its originals back */
     SEG_AS_GLB uint32_t *final_hist;     /* [256] */
-    SEG_AS_GLB int32_t *result;          /* [64] */
+    SEG_AS_GLB int32_t *result;          /* [PLR_WORDS]: pl_result.h */
     SEG_AS_GLB uint32_t *progress;       /* or null: host-visible word that receives the number of finished rows (-v display) */
     SEG_AS_GLB uint32_t *done_counter;   /* or null: host-visible word, +1 when this image is finished (the host stops enqueueing attempts) */
     SEG_AS_GLB uint32_t *attempt_word;   /* or null: host-visible word that receives the number of the attempt being started (launch throttle) */
@@ -973,11 +969,9 @@ PLS_HD void seg_enum_body(const SegJob &j, const SegParams &P, const SegCtlView 
     const uint32_t y = cv.y;
     const SEG_AS_GLB uint32_t *row = seg_row_orig(j, y), *nab = y ? j.img + (size_t)(y - 1u) * W : nullptr, *e0g = seg_e0(j, y);
     const SegGeo G = seg_geo((int)cv.s);
-    const bool span = SEG_EXPERIMENT_WG_SPAN && (P.engine_flags & 1) != 0 && (cv.y & 3u) == 0u;
-    const bool prof = !SEG_EXPERIMENT_WG_SPAN && (P.engine_flags & 1) != 0;
+    const bool prof = (P.engine_flags & 1) != 0;
     unsigned long long te[5] = { 0, 0, 0, 0, 0 };
-    if (prof || span) te[0] = PLS_CLOCK();
-    if (span && f == 1 && seg == 0 && chalf == 0) { PLS_THREADS(tid, NT) { if (tid == 0) PLS_ATOMIC_EXCH((uint32_t *)&j.result[47], (uint32_t)te[0]); } }   /* (the launch's first workgroup) */
+    if (prof) te[0] = PLS_CLOCK();
     PLS_THREADS(tid, NT) {
         if (tid < 8) trflag[tid] = 0u;
         for (int i = tid; i < 4 * SEG_HT; i += NT) ht[i] = 0xffffffffu;
@@ -1089,31 +1083,11 @@ PLS_HD void seg_enum_body(const SegJob &j, const SegParams &P, const SegCtlView 
             j.rout[slot] = (uint16_t)out;
             j.rst[slot] = bad ? 0xFFFFFFFFu : seg_state_pack(st);
         }
-        if (prof && tid == 0 && !SEG_EXPERIMENT_REPLAY_CLOCKS) {
+        if (prof && tid == 0) {
             te[3] = PLS_CLOCK(); te[4] = te[3];
-            for (int q = 0; q < 4; q++) { PLS_ATOMIC_MAX(&j.result[24 + q], (int32_t)(te[q + 1] - te[q])); PLS_ATOMIC_ADD((uint32_t *)&j.result[28 + q], (uint32_t)(te[q + 1] - te[q])); }
-            PLS_ATOMIC_ADD((uint32_t *)&j.result[32], 1u);
-            PLS_ATOMIC_ADD((uint32_t *)&j.result[33], trflag[1] + trflag[2] + trflag[3] + trflag[4]);
-        }
-    }
-    if (span) {
-        PLS_SYNC();
-        PLS_THREADS(tid, NT) {
-            if (tid == 0) {
-                /* start and end of this workgroup against the start of the launch's first; slots of the phase clocks: "load" = start, "first steps" = end, "remaining" = duration */
-                const uint32_t ref = PLS_ATOMIC_ADD_RET((uint32_t *)&j.result[47], 0u);
-                const int32_t ds = (int32_t)((uint32_t)te[0] - ref), de = (int32_t)((uint32_t)PLS_CLOCK() - ref);
-                if (ds >= 0 && de < 4000) {
-#if defined(__HIP_DEVICE_COMPILE__)
-                    const int32_t simd = (int32_t)__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4);      /* HW_ID.SIMD_ID of the workgroup's wave 0 */
-#else
-                    const int32_t simd = 0;
-#endif
-                    const int32_t v[4] = { ds, de, de - ds, simd * 100 };
-                    for (int q = 0; q < 4; q++) { PLS_ATOMIC_MAX(&j.result[24 + q], v[q]); PLS_ATOMIC_ADD((uint32_t *)&j.result[28 + q], (uint32_t)v[q]); }
-                    PLS_ATOMIC_ADD((uint32_t *)&j.result[32], 1u);
-                }
-            }
+            for (int q = 0; q < PLR_SEG_ENUM_PHASES; q++) { PLS_ATOMIC_MAX(&j.result[PLR_SEG_ENUM_MAX + q], (int32_t)(te[q + 1] - te[q])); PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_ENUM_SUM + q], (uint32_t)(te[q + 1] - te[q])); }
+            PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_ENUM_RUNS], 1u);
+            PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_ENUM_STATES], trflag[1] + trflag[2] + trflag[3] + trflag[4]);
         }
     }
 }
@@ -1325,11 +1299,11 @@ PLS_HD void seg_enum_seeded_body(const SegJob &j, const SegParams &P, const SegC
             }
             j.rst[slot] = bad ? 0xFFFFFFFFu : seg_state_pack(st);             /* (rout of a seeded set: the successor's id, written by seg_gather_seeded_body) */
         }
-        if (prof && tid == 0 && !SEG_EXPERIMENT_REPLAY_CLOCKS) {
+        if (prof && tid == 0) {
             te[3] = PLS_CLOCK(); te[4] = te[3];
-            for (int q = 0; q < 4; q++) { PLS_ATOMIC_MAX(&j.result[24 + q], (int32_t)(te[q + 1] - te[q])); PLS_ATOMIC_ADD((uint32_t *)&j.result[28 + q], (uint32_t)(te[q + 1] - te[q])); }
-            PLS_ATOMIC_ADD((uint32_t *)&j.result[32], 1u);
-            PLS_ATOMIC_ADD((uint32_t *)&j.result[33], two_stage ? 2u * (trflag[1] + trflag[2]) : trflag[1] + trflag[2] + trflag[3] + trflag[4]);
+            for (int q = 0; q < PLR_SEG_ENUM_PHASES; q++) { PLS_ATOMIC_MAX(&j.result[PLR_SEG_ENUM_MAX + q], (int32_t)(te[q + 1] - te[q])); PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_ENUM_SUM + q], (uint32_t)(te[q + 1] - te[q])); }
+            PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_ENUM_RUNS], 1u);
+            PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_ENUM_STATES], two_stage ? 2u * (trflag[1] + trflag[2]) : trflag[1] + trflag[2] + trflag[3] + trflag[4]);
         }
     }
 }
@@ -1797,9 +1771,9 @@ PLS_HD void seg_enum_unit_body(const SegJob &j, const SegParams &P, const SegCtl
         PLS_THREADS(tid, NT) {
             if (tid == 0) {
                 te[4] = PLS_CLOCK();
-                for (int q = 0; q < 4; q++) { PLS_ATOMIC_MAX(&j.result[24 + q], (int32_t)(te[q + 1] - te[q])); PLS_ATOMIC_ADD((uint32_t *)&j.result[28 + q], (uint32_t)(te[q + 1] - te[q])); }
-                PLS_ATOMIC_ADD((uint32_t *)&j.result[32], 1u);
-                PLS_ATOMIC_ADD((uint32_t *)&j.result[33], 4u * misc[32 + NC] / (uint32_t)NC);
+                for (int q = 0; q < PLR_SEG_ENUM_PHASES; q++) { PLS_ATOMIC_MAX(&j.result[PLR_SEG_ENUM_MAX + q], (int32_t)(te[q + 1] - te[q])); PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_ENUM_SUM + q], (uint32_t)(te[q + 1] - te[q])); }
+                PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_ENUM_RUNS], 1u);
+                PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_ENUM_STATES], 4u * misc[32 + NC] / (uint32_t)NC);
             }
         }
     }
@@ -1922,7 +1896,7 @@ PLS_HD void seg_first_body(const SegJob &j, const SegParams &P, const SegCtlView
             const uint32_t idx = seg_any_encode(P, f, px[(npix - 1u) * 4 + c], st);
             j.firstidx[(f * 4 + c) * 2] = idx;
             j.firstidx[(f * 4 + c) * 2 + 1] = seg_state_pack(st);
-            if ((P.engine_flags & 1) && tid == 0) { const unsigned long long t1 = PLS_CLOCK(); PLS_ATOMIC_MAX(&j.result[34], (int32_t)(t1 - tf0)); PLS_ATOMIC_ADD((uint32_t *)&j.result[35], (uint32_t)(t1 - tf0)); PLS_ATOMIC_ADD((uint32_t *)&j.result[36], 1u); }
+            if ((P.engine_flags & 1) && tid == 0) { const unsigned long long t1 = PLS_CLOCK(); PLS_ATOMIC_MAX(&j.result[PLR_SEG_FIRST_MAX], (int32_t)(t1 - tf0)); PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_FIRST_SUM], (uint32_t)(t1 - tf0)); PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_FIRST_RUNS], 1u); }
         }
     }
 }
@@ -2415,11 +2389,11 @@ PLS_HD void seg_chain_body(const SegJob &j, const SegParams &P, const SegCtlView
     }
     PLS_THREADS(tid, CT) {
         if (tid == 0) {
-            if (idxb[24]) PLS_ATOMIC_ADD((uint32_t *)&j.result[17], idxb[24]);       /* segments walked step by step (reported with the image's result) */
+            if (idxb[24]) PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_WALKED], idxb[24]);       /* segments walked step by step (reported with the image's result) */
             if (prof) {
-                for (int q = 0; q < 3; q++) { PLS_ATOMIC_MAX(&j.result[8 + q], (int32_t)tacc[q]); PLS_ATOMIC_ADD((uint32_t *)&j.result[12 + q], (uint32_t)tacc[q]); }
-                PLS_ATOMIC_ADD((uint32_t *)&j.result[16], 1u);
-                PLS_ATOMIC_ADD((uint32_t *)&j.result[18], nwide);
+                for (int q = 0; q < 3; q++) { PLS_ATOMIC_MAX(&j.result[PLR_SEG_CHAIN_MAX + q], (int32_t)tacc[q]); PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_CHAIN_SUM + q], (uint32_t)tacc[q]); }
+                PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_CHAIN_RUNS], 1u);
+                PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_CHAIN_WIDE], nwide);
             }
         }
     }
@@ -2503,9 +2477,6 @@ PLS_HD void seg_replay_body(const SegJob &j, const SegParams &P, const SegCtlVie
     const uint32_t *oab = y ? seg_row_orig(j, y - 1u) : nullptr; /* the ORIGINAL row above */
     const SegGeo G = seg_geo((int)cv.s);
     const bool adaptive = !j.row_filters || y == 0;           /* pngloss_image.c:210 */
-    const bool rprof = SEG_EXPERIMENT_REPLAY_CLOCKS && (P.engine_flags & 1) != 0 && walk && grp == 3;
-    unsigned long long tr_[6] = { 0, 0, 0, 0, 0, 0 };
-    if (rprof) tr_[0] = PLS_CLOCK();
     PLS_THREADS(tid, RNT) {
         /* Order of the requests: the walkers' dense ids, then everything the block stages (tables, frozen histogram, pixels), then the
          * checkpoints and entry states (which wait for the dense ids only); the stores to shared memory behind all of them. */
@@ -2581,7 +2552,6 @@ PLS_HD void seg_replay_body(const SegJob &j, const SegParams &P, const SegCtlVie
         }
     }
     PLS_SYNC();
-    if (rprof) tr_[1] = PLS_CLOCK();
     if (walk) {
         PLS_THREADS(tid, RNT) {
             if (tid < SEG_GRP * SEG_PARTS * 4 && lane[2 * tid + 1] != 0xFFFFFFFFu) {
@@ -2592,10 +2562,8 @@ PLS_HD void seg_replay_body(const SegJob &j, const SegParams &P, const SegCtlVie
             }
         }
         PLS_SYNC();
-        if (rprof) tr_[2] = PLS_CLOCK();
     }
     SegAcc &A = j.acc[par];
-    if (rprof) tr_[3] = PLS_CLOCK();
     PLS_THREADS(tid, RNT) { if (tid < 16) red[tid] = tid == 14 ? (0x80000000u ^ (uint32_t)(-(1 << 30))) : (tid == 15 ? (0x80000000u ^ (uint32_t)(1 << 30)) : 0u); }   /* ([14], [15] biased: unsigned max / min) */
     PLS_SYNC();
     {
@@ -2719,11 +2687,6 @@ PLS_HD void seg_replay_body(const SegJob &j, const SegParams &P, const SegCtlVie
                 if (adaptive) for (int g = 0; g < SEG_NFILT; g++) PLS_ATOMIC_ADD(&A.hs[f][g], red[2 + g]);
             }
             if (f == 0 && R >= 0) { PLS_ATOMIC_ADD64(&A.none_lb, *(uint64_t *)&red[10]); PLS_ATOMIC_ADD(&A.lb_valid, 1u); }
-            if (rprof) {
-                tr_[4] = PLS_CLOCK();
-                for (int q = 0; q < 4; q++) { PLS_ATOMIC_MAX(&j.result[24 + q], (int32_t)(tr_[q + 1] - tr_[q])); PLS_ATOMIC_ADD((uint32_t *)&j.result[28 + q], (uint32_t)(tr_[q + 1] - tr_[q])); }
-                PLS_ATOMIC_ADD((uint32_t *)&j.result[32], 1u);
-            }
         }
     }
 }
@@ -2887,7 +2850,7 @@ PLS_HD void seg_post_body(const SegJob &j, const SegParams &P, const SegCtlView 
     const uint32_t *row = seg_row_orig(j, y), *nab = y ? j.img + (size_t)(y - 1u) * W : nullptr, *e0g = seg_e0(j, y);
     const SegGeo G = seg_geo((int)cv.s);
     const uint32_t xg0 = seg0 * SEG_L;
-    const bool prof = (P.engine_flags & 1) != 0;                /* debugging: phase clocks (100 MHz ticks) into result[40..], max over the workgroups */
+    const bool prof = (P.engine_flags & 1) != 0;                /* debugging: phase clocks (100 MHz ticks) into the validation's slots of the result record */
     unsigned long long tk[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     if (prof) tk[0] = PLS_CLOCK();
     PLS_THREADS(tid, SEG_THREADS) {
@@ -3068,9 +3031,9 @@ PLS_HD void seg_post_body(const SegJob &j, const SegParams &P, const SegCtlView 
             if (red[8] != SEG_NOFAIL) { PLS_ATOMIC_MIN(&A.fail[f], red[8]); PLS_ATOMIC_OR(&A.failmask, 1u << f); PLS_ATOMIC_OR(&j.self->vfail[par], 1u << f); }
             if (prof) {
                 tk[4] = PLS_CLOCK(); tk[5] = tk[4];
-                for (int q = 0; q < 5; q++) { PLS_ATOMIC_MAX(&j.result[40 + q], (int32_t)(tk[q + 1] - tk[q])); PLS_ATOMIC_ADD((uint32_t *)&j.result[48 + q], (uint32_t)(tk[q + 1] - tk[q])); }
-                PLS_ATOMIC_ADD((uint32_t *)&j.result[53], 1u);
-                PLS_ATOMIC_ADD((uint32_t *)&j.result[46], red[13]);                     /* pending decisions (pass 3) */
+                for (int q = 0; q < PLR_SEG_VAL_PHASES; q++) { PLS_ATOMIC_MAX(&j.result[PLR_SEG_VAL_MAX + q], (int32_t)(tk[q + 1] - tk[q])); PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_VAL_SUM + q], (uint32_t)(tk[q + 1] - tk[q])); }
+                PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_VAL_RUNS], 1u);
+                PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_VAL_PENDING], red[13]);
             }
         }
     }
@@ -3505,7 +3468,7 @@ PLS_HD void seg_ctl_commit(const SegJob &j, const SegParams &P, int par, int cw,
             }
         }
     }
-    if (prof) { PLS_THREADS(tid, SEG_THREADS) { if (tid == 0) { const uint32_t dt = (uint32_t)(PLS_CLOCK() - tc0); PLS_ATOMIC_MAX(&j.result[58], (int32_t)dt); PLS_ATOMIC_ADD((uint32_t *)&j.result[62], dt); PLS_ATOMIC_ADD((uint32_t *)&j.result[63], 1u); PLS_ATOMIC_ADD((uint32_t *)&j.result[23], (uint32_t)(tk[0] - tc0)); PLS_ATOMIC_ADD((uint32_t *)&j.result[45], (uint32_t)(tk[1] - tk[0])); PLS_ATOMIC_ADD((uint32_t *)&j.result[54], (uint32_t)(tk[2] - tk[1])); PLS_ATOMIC_ADD((uint32_t *)&j.result[55], (uint32_t)(PLS_CLOCK() - tk[2])); } } }
+    if (prof) { PLS_THREADS(tid, SEG_THREADS) { if (tid == 0) { const uint32_t dt = (uint32_t)(PLS_CLOCK() - tc0); PLS_ATOMIC_MAX(&j.result[PLR_SEG_CTL_MAX + 2], (int32_t)dt); PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_COMMIT_SUM], dt); PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_COMMIT_RUNS], 1u); PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_COMMIT_REQ_SUM], (uint32_t)(tk[0] - tc0)); PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_COMMIT_DECIDE_SUM], (uint32_t)(tk[1] - tk[0])); PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_COMMIT_TERMS_SUM], (uint32_t)(tk[2] - tk[1])); PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_COMMIT_ROWS_SUM], (uint32_t)(PLS_CLOCK() - tk[2])); } } }
 }
 
 /* Control kernel of an attempt (par = its parity): reads what the attempt before left (control block and sums of parity prev), writes the control block
@@ -3602,9 +3565,12 @@ PLS_HD void seg_ctl_body(const SegJob &j, const SegParams &P, int par, int bx, u
                         /* epilogue: final histogram + result record (pngloss_image.c:311-325) */
                         uint32_t nz = 0;
                         for (int b = 0; b < 256; b++) { j.final_hist[b] = Hn[b]; nz += Hn[b] != 0; }
-                        for (int i = 0; i < 24; i++) if (i < 8 || i == 20 || (i != 17 && !(P.engine_flags & 1))) j.result[i] = 0;   /* (8..18: the chain kernel's phase clocks) */
-                        j.result[0] = (int32_t)cur.status; j.result[1] = (int32_t)bpp; j.result[2] = (int32_t)nz; j.result[3] = (int32_t)cur.retried;
-                        j.result[4] = (int32_t)cur.restarts_total; j.result[5] = (int32_t)cur.attempts; j.result[6] = (int32_t)cur.serial_rows; j.result[7] = (int32_t)cur.dropped_none; j.result[20] = 3;   /* engine id: segment-parallel */
+                        /* the fields and the engine id always; the chain's and the control kernel's clocks below the enumeration's unless they are on; never the
+                         * walked segments, which the chain kernel counts */
+                        for (int i = 0; i < PLR_SEG_LOW_CLOCKS_END; i++) if (i < PLR_SEG_FIELDS_END || i == PLR_ENGINE_ID || (i != PLR_SEG_WALKED && !(P.engine_flags & 1))) j.result[i] = 0;
+                        j.result[PLR_STATUS] = (int32_t)cur.status; j.result[PLR_BPP] = (int32_t)bpp; j.result[PLR_UNIQUE] = (int32_t)nz; j.result[PLR_RETRIED] = (int32_t)cur.retried;
+                        j.result[PLR_REPAIRED] = (int32_t)cur.restarts_total; j.result[PLR_SEG_ATTEMPTS] = (int32_t)cur.attempts; j.result[PLR_SEG_SERIAL_ROWS] = (int32_t)cur.serial_rows;
+                        j.result[PLR_SEG_NONE_DROPPED] = (int32_t)cur.dropped_none; j.result[PLR_ENGINE_ID] = PLR_ENGINE_SEG;   /* (not read by the host: the batch plan says which engine ran) */
                         if (j.done_counter) PLS_HOST_VISIBLE_ADD(j.done_counter, 1u);
                     }
                 }
@@ -3660,7 +3626,7 @@ PLS_HD void seg_ctl_body(const SegJob &j, const SegParams &P, int par, int bx, u
         const int sn = s_next < 0 ? 0 : s_next;
         unsigned long long tc1 = 0;
         if (prof) tc1 = PLS_CLOCK();
-        seg_build_tables(j.tables + (size_t)f * SEG_TBL_WORDS, Hn, rank, scratch, stage, sn, sn + 1, SEG_THREADS, tpart, TPARTS, prof ? &j.result[37] : nullptr);
+        seg_build_tables(j.tables + (size_t)f * SEG_TBL_WORDS, Hn, rank, scratch, stage, sn, sn + 1, SEG_THREADS, tpart, TPARTS, prof ? &j.result[PLR_SEG_TABLE_SUM] : nullptr);
         PLS_THREADS(tid, SEG_THREADS) {
             if (tpart == 0) {
                 for (int b = tid; b < 256; b += SEG_THREADS) j.base[((size_t)par * SEG_NFILT + f) * 256 + b] = 0u;
@@ -3673,7 +3639,7 @@ PLS_HD void seg_ctl_body(const SegJob &j, const SegParams &P, int par, int bx, u
                 }
             }
         }
-        if (prof) { PLS_THREADS(tid, SEG_THREADS) { if (tid == 0) { const unsigned long long t2 = PLS_CLOCK(); PLS_ATOMIC_MAX(&j.result[56], (int32_t)(tc1 - tc0)); PLS_ATOMIC_MAX(&j.result[57], (int32_t)(t2 - tc1)); PLS_ATOMIC_ADD((uint32_t *)&j.result[59], (uint32_t)(tc1 - tc0)); PLS_ATOMIC_ADD((uint32_t *)&j.result[60], (uint32_t)(t2 - tc1)); PLS_ATOMIC_ADD((uint32_t *)&j.result[61], 1u); PLS_ATOMIC_ADD((uint32_t *)&j.result[19], (uint32_t)(tq1 - tc0)); PLS_ATOMIC_ADD((uint32_t *)&j.result[21], (uint32_t)(tq2 - tq1)); PLS_ATOMIC_ADD((uint32_t *)&j.result[22], (uint32_t)(tc1 - tq2)); } } }
+        if (prof) { PLS_THREADS(tid, SEG_THREADS) { if (tid == 0) { const unsigned long long t2 = PLS_CLOCK(); PLS_ATOMIC_MAX(&j.result[PLR_SEG_CTL_MAX], (int32_t)(tc1 - tc0)); PLS_ATOMIC_MAX(&j.result[PLR_SEG_CTL_MAX + 1], (int32_t)(t2 - tc1)); PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_CAND_SUM], (uint32_t)(tc1 - tc0)); PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_CAND_SUM + 1], (uint32_t)(t2 - tc1)); PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_CAND_RUNS], 1u); PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_CAND_REQ_SUM], (uint32_t)(tq1 - tc0)); PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_CAND_DECIDE_SUM], (uint32_t)(tq2 - tq1)); PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_CAND_HIST_SUM], (uint32_t)(tc1 - tq2)); } } }
         return;
     }
     if (f == 0 && cur.active[0] == 2 && (D.start_none || D.keep_lazy)) {

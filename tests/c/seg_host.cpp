@@ -106,7 +106,7 @@ extern "C" int seg_host_optimize(unsigned char *rgba, uint32_t W, uint32_t H, un
     j.cand = A.take<uint32_t>((size_t)5 * W * 4);
     j.err0 = A.take<uint32_t>((size_t)W * 4); j.err1 = A.take<uint32_t>((size_t)W * 4);   /* (by row parity; the first control kernel zeroes what row 0 reads) */
     j.rowcopy = A.take<uint32_t>((size_t)W * 3);
-    j.final_hist = A.take<uint32_t>(256); j.result = A.take<int32_t>(64); j.progress = nullptr;
+    j.final_hist = A.take<uint32_t>(256); j.result = A.take<int32_t>(PLR_WORDS); j.progress = nullptr;
     j.nseg = (W + SEG_L - 1) / SEG_L; j.ngrp = (j.nseg + SEG_GRP - 1) / SEG_GRP;
     if (W > SEG_MAX_WIDTH) return 64;
     j.ctl = A.take<SegCtl>(3); j.base = A.take<uint32_t>(3 * 5 * 256); j.H0 = A.take<uint32_t>(3 * 256); j.acc = A.take<SegAcc>(3);
@@ -219,7 +219,7 @@ extern "C" int seg_host_optimize(unsigned char *rgba, uint32_t W, uint32_t H, un
     }
     if (getenv("SEG_HOST_VERBOSE")) fprintf(stderr, "seg_host: replay lanes from an entry state %llu (%.1f px each), from a checkpoint %llu (%.1f px each)\n", seg_dbg[0][0], seg_dbg[0][0] ? (double)seg_dbg[0][1] / seg_dbg[0][0] : 0.0, seg_dbg[1][0], seg_dbg[1][0] ? (double)seg_dbg[1][1] / seg_dbg[1][0] : 0.0);
     if (getenv("SEG_HOST_VERBOSE")) fprintf(stderr, "seg_host: chain repairs (segments walked step by step) %llu\n", seg_dbg[2][0]);
-    if (stats) { stats[0] = (uint32_t)attempt; stats[1] = fc.restarts_total; stats[2] = fc.retried; stats[3] = fc.serial_rows; stats[4] = (uint32_t)j.result[2]; stats[5] = bpp; stats[6] = (uint32_t)P.ns; stats[7] = fc.status; }
+    if (stats) { stats[0] = (uint32_t)attempt; stats[1] = fc.restarts_total; stats[2] = fc.retried; stats[3] = fc.serial_rows; stats[4] = (uint32_t)j.result[PLR_UNIQUE]; stats[5] = bpp; stats[6] = (uint32_t)P.ns; stats[7] = fc.status; }
     /* unpack (pl_unpack) */
     for (size_t i = 0; i < (size_t)W * H; i++) {
         unsigned char *p = rgba + 4 * i; const uint32_t w = img[i];

@@ -68,6 +68,23 @@ def test_no_environment_variable_of_the_shipped_library_changes_results():
     assert left == {"PNGLOSS_HIP_ENGINE", "PNGLOSS_DEVICES"}, left
 
 
+def test_result_record_slots_are_named_in_one_header():
+    """pl_result.h is the one map of the per-image result record: elsewhere no subscript of a record starts with a number, and pl_host.hip reads
+    copied records and fills engine_info through the header's names only (tests/test_result_host.py pins the decoder)."""
+    import glob
+    csrc = os.path.join(U.ROOT, "pngloss_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.h")) + glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(U.ROOT, "tests", "c", "*.cpp")))
+    assert any(f.endswith("pl_seg_core.h") for f in files) and any(f.endswith("seg_host.cpp") for f in files)
+    for fn in files:
+        if os.path.basename(fn) == "pl_result.h":
+            continue
+        hits = re.findall(r".*result\[\s*\d.*", open(fn).read())
+        assert not hits, (fn, hits[:3])
+    host = open(os.path.join(csrc, "pl_host.hip")).read()
+    assert not re.findall(r".*\br\[\s*\d.*", host)
+    assert not re.findall(r".*\binfo\[\s*\d.*", host)
+
+
 def _recip_up(d, ulps=1):
     r = np.float32(1.0) / np.float32(d)
     for _ in range(ulps):

@@ -275,6 +275,27 @@ def plan_host_lib():
     return _plan
 
 
+_result = None
+
+
+def result_host_lib():
+    """tests/c/result_host.cpp (the result record's layout and decoder, pngloss_amd/csrc/pl_result.h, behind a C ABI) built into a shared object (cached per process)."""
+    global _result
+    if _result is None:
+        import subprocess
+        import tempfile
+        so = os.path.join(tempfile.mkdtemp(prefix="result_host_"), "libresult_host.so")
+        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Werror", "-o", so, os.path.join(ROOT, "tests", "c", "result_host.cpp")], check=True)
+        lib = C.CDLL(so)
+        lib.result_host_words.restype = C.c_int
+        lib.result_host_decode.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        lib.result_host_decode.restype = None
+        lib.result_host_layout.argtypes = [C.c_int, C.c_void_p]
+        lib.result_host_layout.restype = C.c_int
+        _result = lib
+    return _result
+
+
 def run_seg_host(img, s=19, b=2, filters=True):
     """The segment-parallel engine's kernel bodies on the CPU: returns rc, out, filters, stats
     (attempts, restarts, retried rows, serial rows, unique symbols, bpp, chain states, status)."""
