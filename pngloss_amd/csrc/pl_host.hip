@@ -13,6 +13,7 @@
 #define SEG_PLAIN_POINTERS   /* host plumbing only: SegJob is filled here, never dereferenced */
 #include "pl_seg.h"
 #include "pl_plan.h"
+#include "pl_layout.h"
 
 #include <chrono>
 #include <pthread.h>
@@ -125,33 +126,10 @@ struct pngloss_hip_ctx {
 
 namespace {
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-struct WsLayout {
-    size_t jobs, flags, orig_hist, orig_rank, cand, err0, err1, old_above, final_hist, result, row_ids, out_flags, rowstat, total;
-};
-
-/* per-image workspace: everything the engine keeps outside the image itself */
-WsLayout image_ws(uint32_t width, uint32_t height, bool rows_engine = false)
-{
-    WsLayout l{};
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
-    l.flags = take(sizeof(uint32_t));
-    l.orig_hist = take(sizeof(uint32_t) * PL_NFILT * PL_NSYM);
-    l.orig_rank = take(sizeof(uint32_t) * PL_NFILT * PL_NSYM);
-    l.cand = take(sizeof(uint4) * PL_NFILT * (size_t)width);
-    l.err0 = take(sizeof(uint2) * (size_t)width);
-    l.err1 = take(sizeof(uint2) * (size_t)width);
-    l.old_above = take(sizeof(uint32_t) * (size_t)width);
-    l.final_hist = take(sizeof(uint32_t) * PL_NSYM);
-    l.result = take(sizeof(int32_t) * 64);
-    l.row_ids = take(height ? height : 1);
-    l.out_flags = take(sizeof(uint32_t));
-    l.rowstat = rows_engine ? take(sizeof(uint32_t) * PL_ROWSTAT_WORDS * (size_t)(height ? height : 1)) : 0;     /* (strength 0: pl_rows.hip) */
-    l.total = o;
-    return l;
-}
+/* what pl_layout.h (plain C++, no HIP) states about the device side */
+static_assert(PLL_UINT4 == sizeof(uint4) && PLL_UINT2 == sizeof(uint2), "pl_layout.h: element sizes of PlJob::cand, ::err0 and ::err1");
+static_assert(PLL_NFILT == PL_NFILT && PLL_NSYM == PL_NSYM && PLL_ROWSTAT_WORDS == PL_ROWSTAT_WORDS, "pl_layout.h: histogram and row counter sizes");
+static_assert(PLL_FLAG_GRAY == PL_FLAG_GRAY && PLL_FLAG_OPAQUE == PL_FLAG_OPAQUE, "pl_layout.h: class flag bits");
 
 float recip_up_host(long d)
 {
@@ -161,17 +139,20 @@ float recip_up_host(long d)
     return r;
 }
 
-int ensure_ws(pngloss_hip_ctx *ctx, size_t bytes)
+/* The context's buffers are regrown on demand and never shrink: `p` of `have` bytes comes out with room for `need` (pl_grow_bytes: the slack of
+ * each buffer is need / divisor); freed before the larger one is allocated, and null / 0 if that fails.  pinned: host memory, else the device's. */
+int grow(char *&p, size_t &have, size_t need, size_t divisor, bool pinned = false)
 {
-    if (bytes <= ctx->ws_bytes) return PNGLOSS_SUCCESS;
-    if (ctx->d_ws) PL_CHECK(hipFree(ctx->d_ws));
-    ctx->d_ws = nullptr;
-    ctx->ws_bytes = 0;
-    size_t want = align_up(bytes + bytes / 4, 1 << 20);
-    PL_CHECK(hipMalloc(reinterpret_cast<void **>(&ctx->d_ws), want));
-    ctx->ws_bytes = want;
+    const size_t want = pl_grow_bytes(need, have, divisor);
+    if (!want) return PNGLOSS_SUCCESS;
+    if (p) PL_CHECK(pinned ? hipHostFree(p) : hipFree(p));
+    p = nullptr;
+    have = 0;
+    PL_CHECK(pinned ? hipHostMalloc(reinterpret_cast<void **>(&p), want, hipHostMallocDefault) : hipMalloc(reinterpret_cast<void **>(&p), want));
+    have = want;
     return PNGLOSS_SUCCESS;
 }
+int ensure_ws(pngloss_hip_ctx *ctx, size_t bytes) { return grow(ctx->d_ws, ctx->ws_bytes, bytes, 4); }
 
 struct EmitTarget { void *d_ids; void *d_rows; uint32_t pitch; };
 
@@ -298,8 +279,8 @@ void seg_worker_main(pngloss_hip_ctx *ctx, SegGroups gs, long max_attempts)
     ctx->seg_rc.store(rc, std::memory_order_release);
 }
 
-int run_seg_engine(pngloss_hip_ctx *ctx, const PlJob *d_jobs, const PlPlan &plan, const std::vector<size_t> &seg_offs,
-                   size_t jobs_off, size_t params_off, hipStream_t stream, const uint32_t *d_sel, const PlEngineParams &prm)
+int run_seg_engine(pngloss_hip_ctx *ctx, const PlJob *d_jobs, const PlPlan &plan, const PlBatchLayout &lay, hipStream_t stream,
+                   const uint32_t *d_sel, const PlEngineParams &prm)
 {
     const std::vector<uint32_t> &list = plan.seg_list;
     const size_t n = list.size();                              /* the images of the batch this engine takes */
@@ -338,11 +319,10 @@ int run_seg_engine(pngloss_hip_ctx *ctx, const PlJob *d_jobs, const PlPlan &plan
     auto group_of = [&](size_t i) { int g = 0; while (g + 1 < ngroups && i >= gfirst[g + 1]) g++; return g; };
     ctx->h_sj.assign(n, SegJob{});
     ctx->h_seg_params = plan.params;
-    const SegParams &params = plan.params;
     for (size_t i = 0; i < n; i++) {
         const PlJob &pj = ctx->h_jobs[list[i]];
-        const PlSegLayout l = pl_seg_layout(pj.width ? pj.width : 1, (uint32_t)params.nsp, params.seeded != 0);
-        char *base = ctx->d_ws + seg_offs[i];
+        const PlSegLayout &l = lay.seg[i];
+        char *base = ctx->d_ws + lay.seg_image[i];
         SegJob &s = ctx->h_sj[i];
         s.job_index = list[i];
         s.img = pj.img; s.row_filters = pj.row_filters; s.row_ids = pj.row_ids; s.W = pj.width; s.H = pj.height; s.bpp = 0;
@@ -360,9 +340,9 @@ int run_seg_engine(pngloss_hip_ctx *ctx, const PlJob *d_jobs, const PlPlan &plan
         s.firstidx = reinterpret_cast<uint32_t *>(base + l.firstidx); s.rowmm = reinterpret_cast<int32_t *>(base + l.rowmm);
         s.nseg = pj.width ? l.nseg : 0; s.ngrp = pj.width ? l.ngrp : 0;
     }
-    SegJob *d_sj = reinterpret_cast<SegJob *>(ctx->d_ws + jobs_off);
+    SegJob *d_sj = reinterpret_cast<SegJob *>(ctx->d_ws + lay.seg_jobs);
     for (size_t i = 0; i < n; i++) ctx->h_sj[i].self = d_sj + i;
-    SegParams *d_params = reinterpret_cast<SegParams *>(ctx->d_ws + params_off);
+    SegParams *d_params = reinterpret_cast<SegParams *>(ctx->d_ws + lay.seg_params);
     PL_CHECK(hipMemcpyAsync(d_sj, ctx->h_sj.data(), sizeof(SegJob) * n, hipMemcpyHostToDevice, stream));
     PL_CHECK(hipMemcpyAsync(d_params, &ctx->h_seg_params, sizeof(SegParams), hipMemcpyHostToDevice, stream));
     SegGroups gs{};
@@ -496,7 +476,7 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
         /* the row-statistics engine keeps PL_ROWSTAT_WORDS counters per ROW of every image (5.6 MB per 1080p frame: 2.8 GB for 512 frames) -- the other engines need nothing
          * comparable.  A batch whose counters would not fit beside its images runs strength 0 the long way (the segment / workgroup engines) instead of failing: same bytes. */
         size_t rs = 0, free_b = 0, total_b = 0;
-        for (size_t i = 0; i < n; i++) rs += align_up(sizeof(uint32_t) * PL_ROWSTAT_WORDS * (size_t)(images[i].height ? images[i].height : 1), 256);
+        for (size_t i = 0; i < n; i++) rs += pl_rowstat_bytes(images[i].height);
         const size_t have = ctx->ws_bytes;                       /* (what the context's arena already holds counts as available) */
         if (rs > have && hipMemGetInfo(&free_b, &total_b) == hipSuccess && rs - have > free_b / 2) {
             if (hk.debug) std::fprintf(stderr, "pngloss_hip: strength 0: %zu MB of row counters against %zu MB free: using the other row engines for this batch\n", rs >> 20, free_b >> 20);
@@ -525,25 +505,13 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
         std::fprintf(stderr, "pngloss_hip: PNGLOSS_HIP_ENGINE=seg: nothing in this batch for the segment engine (widths beyond %u?); using the one-workgroup-per-image engine\n", SEG_MAX_WIDTH);
     const bool use_rows = plan.use_rows, use_seg = !plan.seg_list.empty();
     const std::vector<uint32_t> &wg_list = plan.wg_list;
-    std::vector<size_t> offs;
-    size_t total = align_up(sizeof(PlJob) * (n ? n : 1), 256);
-    for (size_t i = 0; i < n; i++) {
-        offs.push_back(total);
-        total += image_ws(images[i].width ? images[i].width : 1, images[i].height, use_rows).total;
-    }
-    std::vector<size_t> seg_offs;
-    size_t seg_jobs_off = 0, seg_params_off = 0, sel_off = 0;
-    if (use_seg) {
-        seg_jobs_off = total; total += align_up(sizeof(SegJob) * plan.seg_list.size(), 256);
-        seg_params_off = total; total += align_up(sizeof(SegParams), 256);
-        sel_off = total; total += align_up(sizeof(uint32_t) * (wg_list.size() ? wg_list.size() : 1), 256);
-        for (uint32_t i : plan.seg_list) { seg_offs.push_back(total); total += pl_seg_layout(images[i].width ? images[i].width : 1, (uint32_t)plan.params.nsp, plan.params.seeded != 0).total; }
-    }
-    int rc = ensure_ws(ctx, total);
+    const PlBatchLayout lay = pl_batch_layout(in.width, in.height, use_rows, plan.seg_list, wg_list.size(), (uint32_t)plan.params.nsp, plan.params.seeded != 0,
+                                              sizeof(PlJob), sizeof(SegJob));
+    int rc = ensure_ws(ctx, lay.total);
     if (rc) return rc;
     for (size_t i = 0; i < n; i++) {
-        const WsLayout l = image_ws(images[i].width ? images[i].width : 1, images[i].height, use_rows);
-        char *b = ctx->d_ws + offs[i];
+        const WsLayout &l = lay.ws[i];
+        char *b = ctx->d_ws + lay.image[i];
         PlJob j{};
         j.rowstat = use_rows ? reinterpret_cast<uint32_t *>(b + l.rowstat) : nullptr;
         j.img = static_cast<uint32_t *>(images[i].d_rgba);
@@ -597,11 +565,11 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
     const uint32_t *d_sel = nullptr;
     if (use_seg && !wg_list.empty()) {
         ctx->h_sel = wg_list;
-        PL_CHECK(hipMemcpyAsync(ctx->d_ws + sel_off, ctx->h_sel.data(), sizeof(uint32_t) * wg_list.size(), hipMemcpyHostToDevice, stream));
-        d_sel = reinterpret_cast<const uint32_t *>(ctx->d_ws + sel_off);
+        PL_CHECK(hipMemcpyAsync(ctx->d_ws + lay.sel, ctx->h_sel.data(), sizeof(uint32_t) * wg_list.size(), hipMemcpyHostToDevice, stream));
+        d_sel = reinterpret_cast<const uint32_t *>(ctx->d_ws + lay.sel);
     }
     if (use_seg) {
-        rc = run_seg_engine(ctx, d_jobs, plan, seg_offs, seg_jobs_off, seg_params_off, stream, d_sel, prm);
+        rc = run_seg_engine(ctx, d_jobs, plan, lay, stream, d_sel, prm);
         if (rc) return rc;
     } else if (use_rows) PL_CHECK(pl_launch_rows(d_jobs, ctx->h_jobs.data(), n, stream));
     else PL_CHECK(pl_launch_engine(d_jobs, nullptr, n, prm, stream));
@@ -759,17 +727,7 @@ int run_host_image(unsigned char **rows, uint32_t width, uint32_t height, uint32
     const size_t npx = (size_t)width * height;
     std::vector<uint32_t> staging;
     try { staging.resize(npx); } catch (const std::bad_alloc &) { return PNGLOSS_OUT_OF_MEMORY_ERROR; }
-    for (uint32_t y = 0; y < height; y++) {
-        const unsigned char *s = rows[y];
-        uint32_t *d = staging.data() + (size_t)y * width;
-        if (src_bpp == 4) std::memcpy(d, s, (size_t)width * 4);
-        else
-            for (uint32_t x = 0; x < width; x++) {
-                uint32_t w = 0;
-                for (uint32_t c = 0; c < src_bpp; c++) w |= (uint32_t)s[(size_t)x * src_bpp + c] << (8 * c);
-                d[x] = w;
-            }
-    }
+    for (uint32_t y = 0; y < height; y++) pl_pack_row(staging.data() + (size_t)y * width, rows[y], width, src_bpp);
     void *d_img = nullptr, *d_filt = nullptr;
     PL_CHECK(hipSetDevice(ctx->device));
     PL_CHECK(hipMalloc(&d_img, npx * 4));
@@ -812,20 +770,154 @@ int run_host_image(unsigned char **rows, uint32_t width, uint32_t height, uint32
     if (d_filt) (void)hipFree(d_filt);
     if (rc == PNGLOSS_HIP_ERROR) std::fprintf(stderr, "pngloss_hip: device transfer or kernel failure: %s\n", hipGetErrorString(hipGetLastError()));
     if (rc) return rc;
-    for (uint32_t y = 0; y < height; y++) {
-        unsigned char *d = rows[y];
-        const uint32_t *s = staging.data() + (size_t)y * width;
-        if (src_bpp == 4) std::memcpy(d, s, (size_t)width * 4);
-        else
-            for (uint32_t x = 0; x < width; x++)
-                for (uint32_t c = 0; c < src_bpp; c++) d[(size_t)x * src_bpp + c] = (unsigned char)(s[x] >> (8 * c));
-    }
+    for (uint32_t y = 0; y < height; y++) pl_unpack_row(rows[y], staging.data() + (size_t)y * width, width, src_bpp);
     if (verbose) {
         /* pngloss_image.c:309-325 */
         std::fputs("\x1B[\x01G  compression complete\n", stderr);
         std::fprintf(stderr, "  used %u unique symbols\n", res.unique_symbols);
     }
     return PNGLOSS_SUCCESS;
+}
+
+/* ---- a window of host images (pngloss_hip_optimize_batch_host*): the phases of batch_host_one ------------------------------------ */
+
+/* chunks of one host window take turns at the two phases that are bound by the host's memory (staging in, fanning out), so that
+ * chunk k+1 stages while chunk k computes instead of every chunk being in the same phase at the same time */
+struct HostTurns { std::atomic<int> stage_turn{ 0 }; std::mutex out_mu; };
+
+/* a few host threads, image i on thread i % nthreads: the copies between the caller's memory and the pinned mirror */
+template <class Fn> void for_each_image_on_threads(size_t n, Fn fn)
+{
+    const unsigned nthreads = (unsigned)std::min<size_t>(12, std::max<size_t>(1, n));
+    std::vector<std::thread> pool;
+    for (unsigned t = 0; t < nthreads; t++)
+        pool.emplace_back([&, t]() { for (size_t i = t; i < n; i += nthreads) fn(i); });
+    for (auto &th : pool) th.join();
+}
+
+/* one chunk on its way through the phases: what the caller handed in, where it lies in the arena (pl_layout.h), where the engine emits to */
+struct HostWindow {
+    pngloss_hip_ctx *ctx;
+    const pngloss_hip_host_image *images;
+    size_t n;
+    pngloss_hip_result *results;
+    pngloss_hip_scanlines *lines;
+    pngloss_hip_zstream *zs;
+    PlWindowLayout lay;
+    std::vector<EmitTarget> emits;
+    /* this image's pixels (and filter flags) come back to the caller */
+    bool comes_back(size_t i) const
+    {
+        const bool stream_only = zs && zs[i].data && (zs[i].flags & PNGLOSS_HIP_Z_STREAM_ONLY);
+        return lay.im[i].px && !stream_only && results[i].status == 0;
+    }
+};
+
+/* the caller's pixels into the pinned mirror */
+void window_stage(const HostWindow &w)
+{
+    for_each_image_on_threads(w.n, [&](size_t i) {
+        if (w.lay.im[i].px) std::memcpy(w.ctx->h_pinned + w.lay.im[i].img, w.images[i].rgba, w.lay.im[i].px * 4);
+    });
+}
+
+/* the engine's view of the arena (descs, w.emits), and the mirror's images up into it */
+int window_upload(HostWindow &w, std::vector<pngloss_hip_image_desc> &descs)
+{
+    pngloss_hip_ctx *ctx = w.ctx;
+    char *const arena = ctx->d_arena;
+    int rc = PNGLOSS_SUCCESS;
+    for (size_t i = 0; i < w.n; i++) {
+        const PlWindowImage &m = w.lay.im[i];
+        descs[i] = pngloss_hip_image_desc{ m.px ? arena + m.img : nullptr, (m.px && w.images[i].row_filters) ? arena + m.flt : nullptr, w.images[i].width, w.images[i].height };
+        w.emits[i] = EmitTarget{ m.pitch ? arena + m.ids : nullptr, m.pitch ? arena + m.rows : nullptr, m.pitch };
+        /* asynchronous DMA from pinned memory, one per image (the areas between images are filled by the kernels) */
+        if (m.px && rc == PNGLOSS_SUCCESS &&
+            hipMemcpyAsync(arena + m.img, ctx->h_pinned + m.img, m.px * 4, hipMemcpyHostToDevice, ctx->copy_stream) != hipSuccess) rc = PNGLOSS_HIP_ERROR;
+    }
+    if (rc == PNGLOSS_SUCCESS && hipStreamSynchronize(ctx->copy_stream) != hipSuccess) rc = PNGLOSS_HIP_ERROR;
+    return rc;
+}
+
+/* pixels + filter flags of every image that comes back: one copy each (PlWindowImage::span) into the pinned mirror, then fanned out on host threads */
+int window_download(const HostWindow &w, HostTurns *turns)
+{
+    pngloss_hip_ctx *ctx = w.ctx;
+    bool any_pixels = false;
+    for (size_t i = 0; i < w.n; i++) if (w.comes_back(i)) any_pixels = true;
+    if (!any_pixels) return PNGLOSS_SUCCESS;
+    for (size_t i = 0; i < w.n; i++) {
+        const PlWindowImage &m = w.lay.im[i];
+        if (w.comes_back(i) && hipMemcpyAsync(ctx->h_pinned + m.img, ctx->d_arena + m.img, m.span, hipMemcpyDeviceToHost, ctx->copy_stream) != hipSuccess) return PNGLOSS_HIP_ERROR;
+    }
+    if (hipStreamSynchronize(ctx->copy_stream) != hipSuccess) return PNGLOSS_HIP_ERROR;
+    std::unique_lock<std::mutex> out_lock;
+    if (turns) out_lock = std::unique_lock<std::mutex>(turns->out_mu);
+    for_each_image_on_threads(w.n, [&](size_t i) {
+        if (!w.comes_back(i)) return;
+        std::memcpy(w.images[i].rgba, ctx->h_pinned + w.lay.im[i].img, w.lay.im[i].px * 4);
+        if (w.images[i].row_filters) std::memcpy(w.images[i].row_filters, ctx->h_pinned + w.lay.im[i].flt, w.images[i].height);
+    });
+    return PNGLOSS_SUCCESS;
+}
+
+/* the emitted scanlines and filter types straight into the caller's memory, with the colour type they are in */
+int window_scanlines(const HostWindow &w)
+{
+    int rc = PNGLOSS_SUCCESS;
+    for (size_t i = 0; i < w.n && rc == PNGLOSS_SUCCESS; i++) {
+        if (!w.lay.im[i].px || w.results[i].status != 0 || !w.emits[i].pitch || !w.lines) continue;
+        pngloss_hip_scanlines &ln = w.lines[i];
+        uint32_t fl = 0;
+        if (hipMemcpy(&fl, w.ctx->h_jobs[i].out_flags, sizeof fl, hipMemcpyDeviceToHost) != hipSuccess) rc = PNGLOSS_HIP_ERROR;
+        ln.color_type = pl_color_type_of(fl);
+        const size_t rowbytes = (size_t)w.images[i].width * pl_emit_bpp_of(fl);
+        if (hipMemcpy(ln.filter_types, w.emits[i].d_ids, w.images[i].height, hipMemcpyDeviceToHost) != hipSuccess) rc = PNGLOSS_HIP_ERROR;
+        if (hipMemcpy2D(ln.scanlines, ln.pitch, w.emits[i].d_rows, w.emits[i].pitch, rowbytes, w.images[i].height, hipMemcpyDeviceToHost) != hipSuccess) rc = PNGLOSS_HIP_ERROR;
+    }
+    return rc;
+}
+
+/* the emitted scanlines through the device deflate into the caller's zlib streams */
+int window_deflate(const HostWindow &w)
+{
+    pngloss_hip_ctx *ctx = w.ctx;
+    pngloss_hip_zstream *zs = w.zs;
+    int rc = PNGLOSS_SUCCESS;
+    /* the colour type decides the scanline length, so it is fetched before the deflate stage is laid out */
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<pl_deflate_image> dz;
+    std::vector<size_t> who;
+    for (size_t i = 0; i < w.n && rc == PNGLOSS_SUCCESS; i++) {
+        zs[i].size = 0; zs[i].color_type = 6; zs[i].blocks[0] = zs[i].blocks[1] = zs[i].blocks[2] = 0;
+        if (!w.emits[i].pitch || w.results[i].status != 0) continue;
+        uint32_t fl = 0;
+        if (hipMemcpy(&fl, ctx->h_jobs[i].out_flags, sizeof fl, hipMemcpyDeviceToHost) != hipSuccess) { rc = PNGLOSS_HIP_ERROR; break; }
+        zs[i].color_type = pl_color_type_of(fl);
+        pl_deflate_image d{};
+        d.d_filter_types = static_cast<const uint8_t *>(w.emits[i].d_ids);
+        d.d_scanlines = static_cast<const uint8_t *>(w.emits[i].d_rows);
+        d.pitch = w.emits[i].pitch;
+        d.rowbytes = w.images[i].width * pl_emit_bpp_of(fl);
+        d.height = w.images[i].height;
+        d.out = zs[i].data;
+        d.out_capacity = zs[i].capacity;
+        dz.push_back(d);
+        who.push_back(i);
+    }
+    if (rc == PNGLOSS_SUCCESS && !dz.empty()) {
+        const hipError_t e = pl_deflate_images(dz.data(), dz.size(), nullptr);
+        if (e == hipErrorInvalidValue) rc = PNGLOSS_INVALID_ARGUMENT;
+        else if (e == hipErrorOutOfMemory) rc = PNGLOSS_OUT_OF_MEMORY_ERROR;
+        else if (e != hipSuccess) rc = PNGLOSS_HIP_ERROR;
+        for (size_t k = 0; k < dz.size() && rc == PNGLOSS_SUCCESS; k++) {
+            zs[who[k]].size = dz[k].out_size;
+            zs[who[k]].blocks[0] = dz[k].blocks_stored; zs[who[k]].blocks[1] = dz[k].blocks_fixed; zs[who[k]].blocks[2] = dz[k].blocks_dynamic;
+        }
+    }
+    ctx->deflate_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (ctx->hooks.debug_seam) std::fprintf(stderr, "pngloss_hip: host window: deflate stage %.1f ms for %zu images\n", ctx->deflate_ms, dz.size());
+    return rc;
 }
 
 } // namespace
@@ -909,10 +1001,6 @@ int pngloss_hip_optimize_batch(pngloss_hip_ctx *ctx, const pngloss_hip_image_des
     return finish(ctx, results, n);
 }
 
-/* chunks of one host window take turns at the two phases that are bound by the host's memory (staging in, fanning out), so that
- * chunk k+1 stages while chunk k computes instead of every chunk being in the same phase at the same time */
-struct HostTurns { std::atomic<int> stage_turn{ 0 }; std::mutex out_mu; };
-
 static int batch_host_one(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images, size_t n, unsigned quantization_strength,
                       long bleed_divider, pngloss_hip_result *results, pngloss_hip_scanlines *lines,
                       pngloss_hip_zstream *zs, HostTurns *turns = nullptr, int my_turn = 0)
@@ -921,83 +1009,37 @@ static int batch_host_one(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *im
     struct TurnGuard { HostTurns *t; int mine; bool passed = false; void pass() { if (t && !passed) { while (t->stage_turn.load(std::memory_order_acquire) != mine) std::this_thread::yield(); t->stage_turn.store(mine + 1, std::memory_order_release); passed = true; } } ~TurnGuard() { pass(); } } turn{ turns, my_turn };
     if (!ctx || (n && !images)) return PNGLOSS_INVALID_ARGUMENT;
     PL_CHECK(hipSetDevice(ctx->device));
-    /* one device arena for the whole batch, 256-B aligned: first [image | filter flags] of every image -- the part that has a pinned
-     * mirror on the host --, behind them [emitted ids | emitted rows] of every image (those come back straight into the caller's memory) */
-    std::vector<size_t> img_off(n), flt_off(n), ids_off(n), rows_off(n);
-    std::vector<EmitTarget> emits(n);
-    size_t total = 0;
+    std::vector<PlWindowIn> in(n);
     for (size_t i = 0; i < n; i++) {
-        const size_t px = (size_t)images[i].width * images[i].height;
-        if (px && !images[i].rgba) return PNGLOSS_INVALID_ARGUMENT;
-        img_off[i] = total; total = align_up(total + px * 4, 256);
-        flt_off[i] = total; total = align_up(total + (images[i].row_filters ? images[i].height : 0), 256);
+        if (images[i].width && images[i].height && !images[i].rgba) return PNGLOSS_INVALID_ARGUMENT;
+        in[i] = PlWindowIn{ images[i].width, images[i].height, images[i].row_filters != nullptr,
+                            (lines && lines[i].scanlines && lines[i].filter_types) || (zs && zs[i].data) };
     }
-    const size_t mirrored = total;
-    for (size_t i = 0; i < n; i++) {
-        const size_t px = (size_t)images[i].width * images[i].height;
-        const bool want = ((lines && lines[i].scanlines && lines[i].filter_types) || (zs && zs[i].data)) && px;
-        const uint32_t pitch = want ? (uint32_t)align_up((size_t)images[i].width * 4, 16) : 0;
-        if (want && lines && lines[i].pitch < (size_t)images[i].width * 4) return PNGLOSS_INVALID_ARGUMENT;
-        ids_off[i] = total; total = align_up(total + (want ? images[i].height : 0), 256);
-        rows_off[i] = total; total = align_up(total + (size_t)pitch * (want ? images[i].height : 0), 256);
-        emits[i].pitch = pitch;
-    }
+    HostWindow w{ ctx, images, n, results, lines, zs, pl_window_layout(in), std::vector<EmitTarget>(n) };
+    for (size_t i = 0; i < n; i++)
+        if (w.lay.im[i].pitch && lines && lines[i].pitch < (size_t)images[i].width * 4) return PNGLOSS_INVALID_ARGUMENT;
     /* persistent arena + pinned staging of the same layout; images are staged by a few host threads and go up as asynchronous
      * copies from pinned memory, one per image (pageable per-image copies were 0.33 s of a 1.6 s window of 256 720p files in round 1).
      * Copies and kernels of a context run on its own non-blocking stream, so that two contexts (the two halves of a window,
      * batch_host) overlap: one half's transfers with the other half's kernels. */
     const auto ta0 = std::chrono::steady_clock::now();
-    if (total > ctx->arena_bytes) {
-        if (ctx->d_arena) PL_CHECK(hipFree(ctx->d_arena));
-        ctx->d_arena = nullptr; ctx->arena_bytes = 0;
-        const size_t want = align_up(total + total / 8, 1 << 20);
-        PL_CHECK(hipMalloc(reinterpret_cast<void **>(&ctx->d_arena), want));
-        ctx->arena_bytes = want;
-    }
-    if (mirrored > ctx->pinned_bytes) {
-        if (ctx->h_pinned) PL_CHECK(hipHostFree(ctx->h_pinned));
-        ctx->h_pinned = nullptr; ctx->pinned_bytes = 0;
-        const size_t want = align_up(mirrored + mirrored / 8, 1 << 20);
-        PL_CHECK(hipHostMalloc(reinterpret_cast<void **>(&ctx->h_pinned), want, hipHostMallocDefault));
-        ctx->pinned_bytes = want;
-    }
+    int rc = grow(ctx->d_arena, ctx->arena_bytes, w.lay.total, 8);
+    if (rc == PNGLOSS_SUCCESS) rc = grow(ctx->h_pinned, ctx->pinned_bytes, w.lay.mirrored, 8, true);
+    if (rc) return rc;
     if (!ctx->copy_stream) PL_CHECK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-    if (ctx->hooks.debug_seam) std::fprintf(stderr, "pngloss_hip: host window chunk %d: arena %zu MB + pinned mirror %zu MB ready after %.1f ms\n", my_turn, total >> 20, mirrored >> 20, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ta0).count());
-    char *const arena = ctx->d_arena;
-    int rc = PNGLOSS_SUCCESS;
+    if (ctx->hooks.debug_seam) std::fprintf(stderr, "pngloss_hip: host window chunk %d: arena %zu MB + pinned mirror %zu MB ready after %.1f ms\n", my_turn, w.lay.total >> 20, w.lay.mirrored >> 20, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ta0).count());
     std::vector<pngloss_hip_image_desc> descs(n);
     if (turns) while (turns->stage_turn.load(std::memory_order_acquire) != my_turn) std::this_thread::yield();
     const auto tu0 = std::chrono::steady_clock::now();
-    {
-        const unsigned nthreads = (unsigned)std::min<size_t>(12, std::max<size_t>(1, n));
-        std::vector<std::thread> pool;
-        for (unsigned t = 0; t < nthreads; t++)
-            pool.emplace_back([&, t]() {
-                for (size_t i = t; i < n; i += nthreads) {
-                    const size_t px = (size_t)images[i].width * images[i].height;
-                    if (px) std::memcpy(ctx->h_pinned + img_off[i], images[i].rgba, px * 4);
-                }
-            });
-        for (auto &th : pool) th.join();
-    }
+    window_stage(w);
     turn.pass();                                              /* the next chunk may stage while this one uploads and computes */
-    for (size_t i = 0; i < n; i++) {
-        const size_t px = (size_t)images[i].width * images[i].height;
-        descs[i] = pngloss_hip_image_desc{ px ? arena + img_off[i] : nullptr,
-                                           (px && images[i].row_filters) ? arena + flt_off[i] : nullptr, images[i].width, images[i].height };
-        emits[i].d_ids = emits[i].pitch ? arena + ids_off[i] : nullptr;
-        emits[i].d_rows = emits[i].pitch ? arena + rows_off[i] : nullptr;
-        /* asynchronous DMA from pinned memory, one per image (the areas between images are filled by the kernels) */
-        if (px && rc == PNGLOSS_SUCCESS &&
-            hipMemcpyAsync(arena + img_off[i], ctx->h_pinned + img_off[i], px * 4, hipMemcpyHostToDevice, ctx->copy_stream) != hipSuccess) rc = PNGLOSS_HIP_ERROR;
-    }
-    if (rc == PNGLOSS_SUCCESS && hipStreamSynchronize(ctx->copy_stream) != hipSuccess) rc = PNGLOSS_HIP_ERROR;
+    rc = window_upload(w, descs);
     ctx->upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tu0).count();
     std::vector<pngloss_hip_result> own_results;
-    if (!results) { own_results.resize(n ? n : 1); results = own_results.data(); }
+    if (!results) { own_results.resize(n ? n : 1); results = w.results = own_results.data(); }
     if (rc == PNGLOSS_SUCCESS) {
         ctx->sync_call = true;                  /* (finish follows at once: no device-side wait on the copy stream, run_seg_engine) */
-        rc = enqueue(ctx, descs.data(), n, nullptr, quantization_strength, bleed_divider, ctx->copy_stream, emits.data());
+        rc = enqueue(ctx, descs.data(), n, nullptr, quantization_strength, bleed_divider, ctx->copy_stream, w.emits.data());
         ctx->sync_call = false;
     }
     if (rc == PNGLOSS_SUCCESS) rc = finish(ctx, results, n);
@@ -1006,96 +1048,13 @@ static int batch_host_one(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *im
     const bool some_aborted = rc == PNGLOSS_INTERNAL_ABORT;
     if (some_aborted) rc = PNGLOSS_SUCCESS;
     const auto td0 = std::chrono::steady_clock::now();
-    if (rc == PNGLOSS_SUCCESS) {
-        /* pixels + filter flags of every image come back as one copy into the pinned mirror, then fan out on host threads */
-        bool any_pixels = false;
-        for (size_t i = 0; i < n; i++) {
-            const bool stream_only = zs && zs[i].data && (zs[i].flags & PNGLOSS_HIP_Z_STREAM_ONLY);
-            if (!stream_only && (size_t)images[i].width * images[i].height && results[i].status == 0) any_pixels = true;
-        }
-        if (any_pixels) {
-            for (size_t i = 0; i < n && rc == PNGLOSS_SUCCESS; i++) {
-                const size_t px = (size_t)images[i].width * images[i].height;
-                const bool stream_only = zs && zs[i].data && (zs[i].flags & PNGLOSS_HIP_Z_STREAM_ONLY);
-                if (!px || stream_only || results[i].status != 0) continue;
-                /* the filter flags sit right behind the image in the arena: one copy takes both */
-                const size_t bytes = images[i].row_filters ? flt_off[i] + images[i].height - img_off[i] : px * 4;
-                if (hipMemcpyAsync(ctx->h_pinned + img_off[i], arena + img_off[i], bytes, hipMemcpyDeviceToHost, ctx->copy_stream) != hipSuccess) rc = PNGLOSS_HIP_ERROR;
-            }
-            if (rc == PNGLOSS_SUCCESS && hipStreamSynchronize(ctx->copy_stream) != hipSuccess) rc = PNGLOSS_HIP_ERROR;
-            if (rc == PNGLOSS_SUCCESS) {
-                std::unique_lock<std::mutex> out_lock;
-                if (turns) out_lock = std::unique_lock<std::mutex>(turns->out_mu);
-                const unsigned nthreads = (unsigned)std::min<size_t>(12, std::max<size_t>(1, n));
-                std::vector<std::thread> pool;
-                for (unsigned t = 0; t < nthreads; t++)
-                    pool.emplace_back([&, t]() {
-                        for (size_t i = t; i < n; i += nthreads) {
-                            const size_t px = (size_t)images[i].width * images[i].height;
-                            const bool stream_only = zs && zs[i].data && (zs[i].flags & PNGLOSS_HIP_Z_STREAM_ONLY);
-                            if (!px || stream_only || results[i].status != 0) continue;
-                            std::memcpy(images[i].rgba, ctx->h_pinned + img_off[i], px * 4);
-                            if (images[i].row_filters) std::memcpy(images[i].row_filters, ctx->h_pinned + flt_off[i], images[i].height);
-                        }
-                    });
-                for (auto &th : pool) th.join();
-            }
-        }
-    }
-    for (size_t i = 0; i < n && rc == PNGLOSS_SUCCESS; i++) {
-        const size_t px = (size_t)images[i].width * images[i].height;
-        if (!px || results[i].status != 0) continue;
-        if (emits[i].pitch && lines) {
-            uint32_t fl = 0;
-            if (hipMemcpy(&fl, ctx->h_jobs[i].out_flags, sizeof fl, hipMemcpyDeviceToHost) != hipSuccess) rc = PNGLOSS_HIP_ERROR;
-            const bool g = fl & PL_FLAG_GRAY, o = fl & PL_FLAG_OPAQUE;
-            lines[i].color_type = g ? (o ? 0 : 4) : (o ? 2 : 6);
-            const size_t rowbytes = (size_t)images[i].width * (g ? (o ? 1 : 2) : (o ? 3 : 4));
-            if (hipMemcpy(lines[i].filter_types, emits[i].d_ids, images[i].height, hipMemcpyDeviceToHost) != hipSuccess) rc = PNGLOSS_HIP_ERROR;
-            if (hipMemcpy2D(lines[i].scanlines, lines[i].pitch, emits[i].d_rows, emits[i].pitch, rowbytes, images[i].height,
-                            hipMemcpyDeviceToHost) != hipSuccess) rc = PNGLOSS_HIP_ERROR;
-        }
-    }
+    if (rc == PNGLOSS_SUCCESS) rc = window_download(w, turns);
+    if (rc == PNGLOSS_SUCCESS) rc = window_scanlines(w);
     ctx->download_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td0).count();
     if (ctx->hooks.debug_seam)
         std::fprintf(stderr, "pngloss_hip: host window chunk %d: %zu images, wait+stage+upload %.1f ms, engine %.1f ms (enqueue..finish %.1f ms), download+fan-out %.1f ms\n", my_turn, n, ctx->upload_ms, ctx->engine_ms,
                      std::chrono::duration<double, std::milli>(td0 - tu0).count() - ctx->upload_ms, ctx->download_ms);
-    if (zs && rc == PNGLOSS_SUCCESS) {
-        /* the colour type decides the scanline length, so it is fetched before the deflate stage is laid out */
-        const auto t0 = std::chrono::steady_clock::now();
-        std::vector<pl_deflate_image> dz;
-        std::vector<size_t> who;
-        for (size_t i = 0; i < n && rc == PNGLOSS_SUCCESS; i++) {
-            zs[i].size = 0; zs[i].color_type = 6; zs[i].blocks[0] = zs[i].blocks[1] = zs[i].blocks[2] = 0;
-            if (!emits[i].pitch || results[i].status != 0) continue;
-            uint32_t fl = 0;
-            if (hipMemcpy(&fl, ctx->h_jobs[i].out_flags, sizeof fl, hipMemcpyDeviceToHost) != hipSuccess) { rc = PNGLOSS_HIP_ERROR; break; }
-            const bool g = fl & PL_FLAG_GRAY, o = fl & PL_FLAG_OPAQUE;
-            zs[i].color_type = g ? (o ? 0 : 4) : (o ? 2 : 6);
-            pl_deflate_image d{};
-            d.d_filter_types = static_cast<const uint8_t *>(emits[i].d_ids);
-            d.d_scanlines = static_cast<const uint8_t *>(emits[i].d_rows);
-            d.pitch = emits[i].pitch;
-            d.rowbytes = images[i].width * (g ? (o ? 1u : 2u) : (o ? 3u : 4u));
-            d.height = images[i].height;
-            d.out = zs[i].data;
-            d.out_capacity = zs[i].capacity;
-            dz.push_back(d);
-            who.push_back(i);
-        }
-        if (rc == PNGLOSS_SUCCESS && !dz.empty()) {
-            const hipError_t e = pl_deflate_images(dz.data(), dz.size(), nullptr);
-            if (e == hipErrorInvalidValue) rc = PNGLOSS_INVALID_ARGUMENT;
-            else if (e == hipErrorOutOfMemory) rc = PNGLOSS_OUT_OF_MEMORY_ERROR;
-            else if (e != hipSuccess) rc = PNGLOSS_HIP_ERROR;
-            for (size_t k = 0; k < dz.size() && rc == PNGLOSS_SUCCESS; k++) {
-                zs[who[k]].size = dz[k].out_size;
-                zs[who[k]].blocks[0] = dz[k].blocks_stored; zs[who[k]].blocks[1] = dz[k].blocks_fixed; zs[who[k]].blocks[2] = dz[k].blocks_dynamic;
-            }
-        }
-        ctx->deflate_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        if (ctx->hooks.debug_seam) std::fprintf(stderr, "pngloss_hip: host window: deflate stage %.1f ms for %zu images\n", ctx->deflate_ms, dz.size());
-    }
+    if (zs && rc == PNGLOSS_SUCCESS) rc = window_deflate(w);
     if (rc == PNGLOSS_HIP_ERROR) std::fprintf(stderr, "pngloss_hip: batch transfer or kernel failure: %s\n", hipGetErrorString(hipGetLastError()));
     if (rc == PNGLOSS_SUCCESS && some_aborted) rc = PNGLOSS_INTERNAL_ABORT;
     return rc;
@@ -1342,19 +1301,10 @@ int png_decode_body(pngloss_hip_ctx *ctx, const pngloss_hip_png_source *src, siz
         return PNGLOSS_INVALID_ARGUMENT;
     }
     PL_CHECK(hipSetDevice(ctx->device));
-    /* one job per non-interlaced file, one per non-empty Adam7 pass of an interlaced one (pl_pngread.h); offsets below are relative to the
-     * data region behind the tables, the device pointers are filled in once the workspace is there */
-    std::vector<PrJob> jobs;
-    jobs.reserve(n);
-    struct JobAt { size_t file; uint64_t raw; size_t last, prog; };
-    std::vector<JobAt> at;
-    at.reserve(n);
-    std::vector<size_t> raw_off(n), out_off(n), z_off(n);
-    std::vector<uint64_t> raw_bytes(n);
+    std::vector<PrFormat> fmt(n);
+    std::vector<PlReadIn> in(n);
     static const unsigned char bad_stream[6] = { 0, 0, 0, 0, 0, 0 };       /* (CMF 0: not deflate) */
     std::vector<ZRef> zsub(zs ? n : 0);
-    uint32_t max_bands = 0;
-    size_t total = 0, ftotal = 0, nprog = 0;
     for (size_t i = 0; i < n; i++) {
         if ((!zs && !src[i].scanlines) || (zs && !zs[i].z) || (!d_out && !src[i].rgba)) return PNGLOSS_INVALID_ARGUMENT;
         if (src[i].interlace > 1) {
@@ -1365,85 +1315,59 @@ int png_decode_body(pngloss_hip_ctx *ctx, const pngloss_hip_png_source *src, siz
          * status 25 like any other stream the inflater refuses (it is handed a six-byte stream with an invalid header), the batch goes on */
         if (zs && (zs[i].bytes < 6 || zs[i].bytes > 0xFFFFFFF0u)) zsub[i] = ZRef{ bad_stream, sizeof bad_stream };
         else if (zs) zsub[i] = zs[i];
-        PrFormat F;
+        PrFormat &F = fmt[i];
         if (!pr_format(F, src[i].width, src[i].height, src[i].color_type, src[i].bit_depth, src[i].palette, src[i].palette_entries, src[i].trns, src[i].trns_bytes)) {
             std::fprintf(stderr, "pngloss_hip: image %zu: colour type %d with bit depth %d (or an empty image / a palette image without PLTE) is not a PNG format\n", i, src[i].color_type, src[i].bit_depth);
             return PNGLOSS_INVALID_ARGUMENT;
         }
-        uint64_t pass_off[PR_ADAM7_PASSES] = {};
-        raw_bytes[i] = src[i].interlace ? pr_adam7_bytes(F.width, F.height, F.color_type, F.bit_depth, pass_off) : pr_scanline_bytes(F.width, F.height, F.color_type, F.bit_depth, 0);
-        raw_off[i] = total; total += align_up(raw_bytes[i], 256);
-        if (zs) {
-            if (raw_bytes[i] > 0xFFFFFFF0u) return PNGLOSS_INVALID_ARGUMENT;     /* (32-bit positions in the inflater) */
-            z_off[i] = total; total += align_up(zsub[i].bytes + 16, 256);
-        }
-        const size_t out_bytes = align_up((size_t)src[i].width * src[i].height * 4, 256);
-        if (d_out) { out_off[i] = ftotal; ftotal += out_bytes; } else { out_off[i] = total; total += out_bytes; }
-        for (int p = 0; p < (src[i].interlace ? PR_ADAM7_PASSES : 1); p++) {
-            PrJob j{};
-            j.F = F;                                                              /* (a pass: the file's format with the pass's geometry) */
-            if (src[i].interlace) {
-                const PrPass ps = pr_adam7_pass(p, F.width, F.height, F.color_type, F.bit_depth);
-                if (!ps.bytes) continue;                                          /* an empty pass has no bytes in the stream */
-                j.F.width = ps.width; j.F.height = ps.height; j.F.rowbytes = ps.rowbytes;
-                j.ox = ps.x0; j.oy = ps.y0; j.sx = ps.dx; j.sy = ps.dy;
-            } else {
-                j.ox = 0; j.oy = 0; j.sx = 1; j.sy = 1;
-            }
-            j.pitch = F.width;
-            /* per band of PR_ROWS rows: its last row (for the band below) and a progress word */
-            j.nbands = (j.F.height + PR_ROWS - 1) / PR_ROWS;
-            j.lastpitch = (uint32_t)align_up(j.F.rowbytes, 256);
-            max_bands = std::max(max_bands, j.nbands);
-            at.push_back(JobAt{ i, src[i].interlace ? pass_off[p] : 0, total, nprog });
-            total += (size_t)j.lastpitch * j.nbands;
-            nprog += j.nbands;
-            jobs.push_back(j);
-        }
+        if (zs && pr_scanline_bytes(F.width, F.height, F.color_type, F.bit_depth, src[i].interlace) > 0xFFFFFFF0u) return PNGLOSS_INVALID_ARGUMENT;     /* (32-bit positions in the inflater) */
+        in[i] = PlReadIn{ F.width, F.height, F.color_type, F.bit_depth, src[i].interlace, zs ? (uint64_t)zsub[i].bytes : PL_READ_NO_STREAM };
     }
-    const size_t m = jobs.size();
-    /* tables in front: jobs, then the status words of the decode and of the inflate and the progress words (zeroed by one memset), then the
-     * inflate's streams.  (Every job carries its format, palette included: 1.1 KB a pass.  A first version whose jobs pointed at one format
-     * per file had a table 4.6 MB smaller at 768 interlaced files, but a kernel 13 % slower on plain files: DESIGN.md section 9.2) */
-    const size_t jobs_bytes = align_up(sizeof(PrJob) * m, 256), st_bytes = align_up(sizeof(int32_t) * n, 256);
-    const size_t prog_bytes = align_up(sizeof(uint32_t) * nprog, 256), zjobs_bytes = align_up(sizeof(PliStream) * n, 256);
-    const size_t head = jobs_bytes + 2 * st_bytes + prog_bytes + zjobs_bytes;
-    total += head;
+    /* where everything lies (pl_layout.h): the tables in front -- jobs, then the status words of the decode and of the inflate and the progress words
+     * (zeroed by one memset), then the inflate's streams --, the files' data behind them.  (Every job carries its format, palette included: 1.1 KB a
+     * pass.  A first version whose jobs pointed at one format per file had a table 4.6 MB smaller at 768 interlaced files, but a kernel 13 % slower
+     * on plain files: DESIGN.md section 9.2) */
+    const PlReadLayout lay = pl_read_layout(in, d_out != nullptr, sizeof(PrJob), sizeof(PliStream));
+    const size_t m = lay.job.size(), total = lay.total, ftotal = lay.ftotal;
     const auto tr0 = std::chrono::steady_clock::now();
     auto ms_since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr0).count(); };
     int rc = ensure_ws(ctx, total);
+    if (rc == PNGLOSS_SUCCESS && d_out) rc = grow(ctx->d_frames, ctx->frames_bytes, ftotal, 4);
     if (rc) return rc;
-    if (d_out && ftotal > ctx->frames_bytes) {
-        if (ctx->d_frames) PL_CHECK(hipFree(ctx->d_frames));
-        ctx->d_frames = nullptr; ctx->frames_bytes = 0;
-        const size_t want = align_up(ftotal + ftotal / 4, 1 << 20);
-        PL_CHECK(hipMalloc(reinterpret_cast<void **>(&ctx->d_frames), want));
-        ctx->frames_bytes = want;
-    }
     const double ms_ws = ms_since();
-    char *b = ctx->d_ws, *d = b + head, *fb = d_out ? ctx->d_frames : d;
-    int32_t *d_status = reinterpret_cast<int32_t *>(b + jobs_bytes), *d_zstatus = reinterpret_cast<int32_t *>(b + jobs_bytes + st_bytes);
-    uint32_t *d_prog = reinterpret_cast<uint32_t *>(b + jobs_bytes + 2 * st_bytes);
-    PliStream *d_zjobs = reinterpret_cast<PliStream *>(b + jobs_bytes + 2 * st_bytes + prog_bytes);
-    std::vector<PliStream> zjobs(zs ? n : 0);
-    PL_CHECK(hipMemsetAsync(d_status, 0, 2 * st_bytes + prog_bytes, stream));
+    /* offsets into pointers: here and nowhere else */
+    char *const b = ctx->d_ws, *const fb = d_out ? ctx->d_frames : b;
+    int32_t *d_status = reinterpret_cast<int32_t *>(b + lay.status), *d_zstatus = reinterpret_cast<int32_t *>(b + lay.zstatus);
+    uint32_t *d_prog = reinterpret_cast<uint32_t *>(b + lay.prog);
+    PliStream *d_zjobs = reinterpret_cast<PliStream *>(b + lay.zjobs);
+    auto d_raw = [&](size_t i) { return reinterpret_cast<uint8_t *>(b + lay.file[i].raw); };
+    auto d_z = [&](size_t i) { return reinterpret_cast<uint8_t *>(b + lay.file[i].z); };
+    auto d_rgba = [&](size_t i) { return fb + lay.file[i].out; };
+    std::vector<PrJob> jobs(m);
     for (size_t k = 0; k < m; k++) {
-        const size_t i = at[k].file;
-        jobs[k].raw = reinterpret_cast<const uint8_t *>(d + raw_off[i] + at[k].raw);
-        jobs[k].rgba = reinterpret_cast<uint32_t *>(fb + out_off[i]);
-        jobs[k].lastrow = reinterpret_cast<uint8_t *>(d + at[k].last);
-        jobs[k].progress = d_prog + at[k].prog;
-        jobs[k].status = d_status + i;
+        const PlReadJob &a = lay.job[k];
+        PrJob &j = jobs[k];
+        j.F = fmt[a.file];                                                    /* (a pass: the file's format with the pass's geometry) */
+        j.F.width = a.width; j.F.height = a.height; j.F.rowbytes = a.rowbytes;
+        j.ox = a.ox; j.oy = a.oy; j.sx = a.sx; j.sy = a.sy; j.pitch = a.pitch;
+        j.nbands = a.nbands; j.lastpitch = a.lastpitch;
+        j.raw = reinterpret_cast<const uint8_t *>(b + a.raw);
+        j.rgba = reinterpret_cast<uint32_t *>(d_rgba(a.file));
+        j.lastrow = reinterpret_cast<uint8_t *>(b + a.last);
+        j.progress = d_prog + a.prog;
+        j.status = d_status + a.file;
     }
+    std::vector<PliStream> zjobs(zs ? n : 0);
+    PL_CHECK(hipMemsetAsync(d_status, 0, lay.zeroed, stream));
     for (size_t i = 0; i < n; i++) {
         /* (from pinned memory -- pngloss_hip_pinned_alloc -- this is one DMA; from pageable memory the runtime stages it: 33 ms against 1.3 for 64 MiB) */
         if (zs) {
-            PL_CHECK(hipMemcpyAsync(d + z_off[i], zsub[i].z, zsub[i].bytes, hipMemcpyHostToDevice, stream));
-            zjobs[i].z = reinterpret_cast<const uint8_t *>(d + z_off[i]); zjobs[i].zbytes = (uint32_t)zsub[i].bytes;
-            zjobs[i].out = reinterpret_cast<uint8_t *>(d + raw_off[i]); zjobs[i].expect = (uint32_t)raw_bytes[i];
+            PL_CHECK(hipMemcpyAsync(d_z(i), zsub[i].z, zsub[i].bytes, hipMemcpyHostToDevice, stream));
+            zjobs[i].z = d_z(i); zjobs[i].zbytes = (uint32_t)zsub[i].bytes;
+            zjobs[i].out = d_raw(i); zjobs[i].expect = (uint32_t)lay.file[i].raw_bytes;
             zjobs[i].status = d_zstatus + i;
         } else
-        PL_CHECK(hipMemcpyAsync(d + raw_off[i], src[i].scanlines, raw_bytes[i], hipMemcpyHostToDevice, stream));
+        PL_CHECK(hipMemcpyAsync(d_raw(i), src[i].scanlines, lay.file[i].raw_bytes, hipMemcpyHostToDevice, stream));
     }
     PL_CHECK(hipMemcpyAsync(b, jobs.data(), sizeof(PrJob) * m, hipMemcpyHostToDevice, stream));
     if (zs) {
@@ -1453,13 +1377,13 @@ int png_decode_body(pngloss_hip_ctx *ctx, const pngloss_hip_png_source *src, siz
     const bool seam_dbg = ctx->hooks.debug_seam;
     double ms_up = 0, ms_k = 0;
     if (seam_dbg) { PL_CHECK(hipStreamSynchronize(stream)); ms_up = ms_since(); }
-    PL_CHECK(pl_launch_png_decode(reinterpret_cast<const PrJob *>(b), m, max_bands, stream));
+    PL_CHECK(pl_launch_png_decode(reinterpret_cast<const PrJob *>(b), m, lay.max_bands, stream));
     if (seam_dbg) { PL_CHECK(hipStreamSynchronize(stream)); ms_k = ms_since(); }
     std::vector<int32_t> st(n), zst(n, 0);
     if (zs) PL_CHECK(hipMemcpyAsync(zst.data(), d_zstatus, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
     if (!d_out)
         for (size_t i = 0; i < n; i++)
-            PL_CHECK(hipMemcpyAsync(src[i].rgba, fb + out_off[i], (size_t)src[i].width * src[i].height * 4, hipMemcpyDeviceToHost, stream));
+            PL_CHECK(hipMemcpyAsync(src[i].rgba, d_rgba(i), (size_t)src[i].width * src[i].height * 4, hipMemcpyDeviceToHost, stream));
     PL_CHECK(hipMemcpyAsync(st.data(), d_status, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
     PL_CHECK(hipStreamSynchronize(stream));
     if (seam_dbg) std::fprintf(stderr, "pngloss_hip: read side: %zu files, workspace %zu MB ready after %.1f ms, upload %.1f ms, unfilter + expand %.1f ms, %s %.1f ms\n", n, (total + ftotal) >> 20, ms_ws, ms_up - ms_ws, ms_k - ms_up, d_out ? "status (the frames stay on the device)" : "download", ms_since() - ms_k);
@@ -1467,7 +1391,7 @@ int png_decode_body(pngloss_hip_ctx *ctx, const pngloss_hip_png_source *src, siz
     per_image = true;
     int worst = PNGLOSS_SUCCESS;
     for (size_t i = 0; i < n; i++) {
-        if (d_out) d_out[i] = fb + out_off[i];
+        if (d_out) d_out[i] = d_rgba(i);
         if (zst[i]) {
             /* the stream is not one the device inflater takes (damaged, or beyond what it checks): the caller reads the file on the host */
             std::fprintf(stderr, "pngloss_hip: image %zu: the device inflater stopped (code %d): corrupt or unusual zlib stream\n", i, zst[i]);

@@ -20,7 +20,6 @@ struct PrJob {
     PrFormat F;             /* the file's format with the job's width, height and rowbytes (a pass: its own) */
 };
 
-#define PR_ROWS 64          /* rows per band: one wave, lane = row */
 hipError_t pl_launch_png_decode(const PrJob *d_jobs, size_t n, uint32_t max_bands, hipStream_t stream);
 
 #endif

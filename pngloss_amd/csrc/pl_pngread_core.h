@@ -54,6 +54,7 @@ typedef struct PrPass {
 } PrPass;
 
 #define PR_ADAM7_PASSES 7
+#define PR_ROWS 64          /* rows per band of the device reader: one wave, lane = row */
 
 PR_HD PrPass pr_adam7_pass(int p, uint32_t W, uint32_t H, int color_type, int depth)
 {

@@ -296,6 +296,47 @@ def result_host_lib():
     return _result
 
 
+_layout = None
+
+
+def layout_host_lib():
+    """tests/c/layout_host.cpp (the memory layouts of the host shim, pngloss_amd/csrc/pl_layout.h, behind a C ABI) built into a shared object (cached per process)."""
+    global _layout
+    if _layout is None:
+        import subprocess
+        import tempfile
+        so = os.path.join(tempfile.mkdtemp(prefix="layout_host_"), "liblayout_host.so")
+        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Werror", "-o", so, os.path.join(ROOT, "tests", "c", "layout_host.cpp")], check=True)
+        lib = C.CDLL(so)
+        lib.layout_host_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_int, C.c_size_t, C.c_size_t,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.layout_host_batch.restype = None
+        lib.layout_host_seg_total.argtypes = [C.c_uint32, C.c_uint32, C.c_int]
+        lib.layout_host_seg_total.restype = C.c_int64
+        lib.layout_host_seg_params_bytes.restype = C.c_int64
+        lib.layout_host_rowstat_bytes.argtypes = [C.c_uint32]
+        lib.layout_host_rowstat_bytes.restype = C.c_int64
+        lib.layout_host_window.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        lib.layout_host_window.restype = None
+        lib.layout_host_read.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.layout_host_read.restype = C.c_int64
+        lib.layout_host_adam7_pass.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p]
+        lib.layout_host_adam7_pass.restype = None
+        lib.layout_host_grow.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t]
+        lib.layout_host_grow.restype = C.c_int64
+        lib.layout_host_color_type.argtypes = [C.c_uint32]
+        lib.layout_host_color_type.restype = C.c_int
+        lib.layout_host_emit_bpp.argtypes = [C.c_uint32]
+        lib.layout_host_emit_bpp.restype = C.c_int
+        lib.layout_host_band_rows.restype = C.c_int
+        lib.layout_host_pack.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        lib.layout_host_pack.restype = None
+        lib.layout_host_unpack.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        lib.layout_host_unpack.restype = None
+        _layout = lib
+    return _layout
+
+
 def run_seg_host(img, s=19, b=2, filters=True):
     """The segment-parallel engine's kernel bodies on the CPU: returns rc, out, filters, stats
     (attempts, restarts, retried rows, serial rows, unique symbols, bpp, chain states, status)."""
