@@ -244,7 +244,7 @@ void seg_worker_main(pngloss_hip_ctx *ctx, SegGroups gs, long max_attempts)
              * the generator's frames in 0.3 %) -- goes back to the start from every state for the rest of the batch: more than one image-row in 25, sixteen to begin with (the
              * device-side rule, seg_unit_from_seeds, does the same image by image inside the kernel; this one changes the KERNEL -- for small batches seg_k_enum instead of
              * seg_k_enum_unit<1> with its slow exhaustive path).  Results do not depend on it; the count lags the launches by the look-ahead. */
-            if (gs.b[g].seeds && (uint64_t)words[2 * SEG_MAX_GROUPS + g] * 25u > (uint64_t)at * gs.b[g].n + 400u) gs.b[g].seeds = false;
+            if (gs.b[g].shape.seeds && (uint64_t)words[2 * SEG_MAX_GROUPS + g] * 25u > (uint64_t)at * gs.b[g].n + 400u) gs.b[g].shape.seeds = false;
             if (launched[g] >= 64) { const long lead = launched[g] - (long)at; lead_sum += lead; lead_n++; if (lead < lead_min) lead_min = lead; if (lead <= 2) lead_low++; }   /* (PNGLOSS_HIP_DEBUG: how far ahead of the device the launches run) */
             const hipError_t e = pl_seg_launch_attempt(gs.b[g], (int)launched[g], ctx->seg_gstream[g]);
             if (e != hipSuccess) { std::fprintf(stderr, "pngloss_hip: launching a row attempt failed: %s\n", hipGetErrorString(e)); rc = PNGLOSS_HIP_ERROR; break; }
@@ -350,9 +350,7 @@ int run_seg_engine(pngloss_hip_ctx *ctx, const PlJob *d_jobs, const PlPlan &plan
     for (int g = 0; g < ngroups; g++) {
         const PlSegGroupPlan &pg = plan.group[g];
         PlSegBatch &b = gs.b[g];
-        b.d_sj = d_sj + gfirst[g]; b.d_params = d_params; b.n = pg.n;
-        b.max_nseg = pg.max_nseg; b.max_ngrp = pg.max_ngrp; b.max_ncommit = pg.max_ncommit;
-        b.enum_nt = pg.enum_nt; b.small_ok = pg.small_ok; b.seeded = pg.seeded; b.tparts = pg.tparts; b.unit = pg.unit; b.seeds = pg.seeds;
+        b.d_sj = d_sj + gfirst[g]; b.d_params = d_params; b.n = pg.n; b.shape = pg;
     }
     PL_CHECK(pl_seg_launch_resolve(d_jobs, d_sj, n, stream));
     PL_CHECK(hipEventRecord(ctx->ev_prep, stream));

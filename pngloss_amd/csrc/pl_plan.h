@@ -10,7 +10,7 @@
 #ifndef PL_PLAN_H
 #define PL_PLAN_H
 
-#include "pl_seg_core.h"
+#include "pl_seg_launch.h"
 
 #include <algorithm>
 #include <cstring>
@@ -141,10 +141,8 @@ struct PlPlanInput {
     int opt_launch_groups = 0;              /* pngloss_hip_set_option("launch_groups", ..) */
     bool stream_wait_used = false;          /* a context of the process has put a wait for the engine on a caller's stream (g_stream_wait_used) */
 };
-struct PlSegGroupPlan {                     /* one launch group of the segment engine (PlSegBatch) */
+struct PlSegGroupPlan : SegShape {          /* one launch group of the segment engine (PlSegBatch): the shape of its attempts (pl_seg_launch.h) and the number of its images */
     size_t n;
-    uint32_t max_nseg, max_ngrp, max_ncommit, enum_nt, tparts, unit;
-    bool seeds, small_ok, seeded;
 };
 struct PlPlan {
     bool use_rows = false;                  /* strength 0: the row-statistics engine takes every image */

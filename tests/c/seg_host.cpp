@@ -1,7 +1,8 @@
 /*
  * seg_host.cpp -- TEST INFRASTRUCTURE: runs the kernel bodies of the segment-parallel row engine
  * (pngloss_amd/csrc/pl_seg_core.h, the same source hipcc compiles into pl_seg.hip's kernels) on the CPU, as plain loops
- * over (workgroup, thread), so that the CPU suite can check the engine's logic bit-exactly against the oracle without a GPU.
+ * over (workgroup, thread) -- the launches of an attempt, their grids and what each workgroup does are the shipped library's own
+ * (pngloss_amd/csrc/pl_seg_launch.h) --, so that the CPU suite can check the engine's logic bit-exactly against the oracle without a GPU.
  * Never shipped, never loaded by the product (which has no CPU path).
  *
  *   seg_host_optimize(rgba, W, H, row_filters|NULL, strength, bleed, stats[8])  -> 0, or 64 if (strength, bleed) has more
@@ -26,7 +27,7 @@ static void seg_debug_row(int kind, unsigned failed, int winner, int start_none)
 #include <cstdio>
 #include <cstdlib>
 #define SEG_DEBUG_BREAK(f, c, sg, est, y) do { if (getenv("SEG_HOST_VERBOSE") && atoi(getenv("SEG_HOST_VERBOSE")) > 1) fprintf(stderr, "seg_host: row %u broken off: candidate %d channel %d segment %u, entry state left %u cn %d th %d\n", (unsigned)(y), (int)(f), (int)(c), (unsigned)(sg), (unsigned)((est) & 255u), (int)(((est) >> 8) & 0xffffu) - 32768, (int)((est) >> 24) - 128); } while (0)
-#include "../../pngloss_amd/csrc/pl_seg_core.h"
+#include "../../pngloss_amd/csrc/pl_seg_launch.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -124,92 +125,42 @@ extern "C" int seg_host_optimize(unsigned char *rgba, uint32_t W, uint32_t H, un
     j.grpleft = A.take<uint32_t>((size_t)5 * j.ngrp);
     j.firstidx = A.take<uint32_t>(5 * 4 * 2);
     j.rowmm = A.take<int32_t>(4);
-    std::vector<unsigned char> smem(160 * 1024, 0x5A);
-    const int ncommit = (int)((W + SEG_COMMIT_W - 1) / SEG_COMMIT_W);
     j.nbreak = 0u;
     j.self = &j; for (int k = 0; k < 3; k++) { j.v[k].magic = 0u; j.v[k].finished = 0u; j.v[k].ignore = 0u; j.vfail[k] = 0u; }
     j.ctl[2].magic = 0u; j.acc[2].failmask = 0u;   /* (seg_k_resolve does this on the device: the first attempt finds no attempt behind it) */
+    /* the shape of the attempts (pl_plan_batch fills it for a launch group): this image's own, or -- SEG_HOST_GRID_PAD=k -- that of a group whose widest image has k
+     * segments more, which is what a batch does to its narrower images: every grid then has workgroups without work */
+    const uint32_t pad = getenv("SEG_HOST_GRID_PAD") ? (uint32_t)atoi(getenv("SEG_HOST_GRID_PAD")) : 0u;
+    SegShape shape{};
+    shape.max_nseg = j.nseg + pad; shape.max_ngrp = (shape.max_nseg + SEG_GRP - 1) / SEG_GRP; shape.max_ncommit = (W + pad * SEG_L + SEG_COMMIT_W - 1) / SEG_COMMIT_W;
+    /* the enumeration's workgroups come in two sizes; the product picks by row width, SEG_HOST_ENUM_NT pins one */
+    shape.enum_nt = shape.max_nseg <= SEG_ENUM_NT_SMALL_MAX_NSEG ? 512 : 1024;
+    if (getenv("SEG_HOST_ENUM_NT")) shape.enum_nt = atoi(getenv("SEG_HOST_ENUM_NT")) == 1024 ? 1024 : 512;
+    shape.tparts = (uint32_t)P.tparts; shape.unit = (uint32_t)P.unit; shape.small_ok = P.small_ok != 0; shape.seeded = P.seeded != 0;
+    /* the start from seeds with a run-in (round 6): units, or (unit = 1) segment by segment through the same bodies */
+    shape.seeds = !P.seeded && P.ns <= SEG_NSP && P.seed_n > 0 && getenv("SEG_HOST_SEEDS") != nullptr && atoi(getenv("SEG_HOST_SEEDS")) != 0;
+    if (shape.seeds && getenv("SEG_HOST_SEED_KIN")) P.seed_kin = atoi(getenv("SEG_HOST_SEED_KIN"));
+    SegLaunch launches[SEG_MAX_LAUNCHES];
+    const int nl = seg_attempt_launches(shape, launches);
     int attempt = 0;
     const long max_attempts = (long)H * ((long)strength + 1) * (2 + 2 * SEG_MAX_RESTARTS * SEG_NFILT) + 1024;   /* (the product's bound: pl_host.hip) */
-    /* One attempt = four launches: [control of this attempt + validation of the attempt before], enumerate, chain, replay.  The two halves of
-     * the first launch run side by side on the device; here one after the other, in either order (SEG_HOST_VAL_FIRST): neither may depend on it. */
+    /* One attempt = the four or five launches of seg_attempt_launches: [control of this attempt + validation of the attempt before], enumerate, (seeded sets: gather,)
+     * chain, replay; every workgroup of every grid, each launch with a buffer of exactly its LDS request (the sanitizer build, tests/test_seg_host.py, sees any
+     * byte beyond it).  The two halves of the first launch run side by side on the device; here one after the other, in either order (SEG_HOST_VAL_FIRST):
+     * neither may depend on it. */
     const bool val_first = getenv("SEG_HOST_VAL_FIRST") != nullptr;
     for (;; attempt++) {
         if (attempt > max_attempts) { fprintf(stderr, "seg_host: no progress\n"); return 65; }
-        const int par = attempt % 3, kv = (par + 2) % 3;
-        std::vector<unsigned char> cvsm((size_t)(P.tparts == SEG_TPARTS_BATCH ? SEG_SM_CTLVAL_V(SEG_VGRP_OF(SEG_TPARTS_BATCH)) : SEG_SM_CTLVAL_V(SEG_VGRP_OF(SEG_TPARTS))), 0x5A);       /* (the launch's LDS request: the sanitizer build sees an overrun) */
-        for (int half = 0; half < 2; half++) {
-            if ((half == 0) != val_first) { for (int bx = 0; bx < SEG_CTL_IMG_OF(P) + 1 + ncommit; bx++) { if (P.tparts == SEG_TPARTS_BATCH) seg_ctl_body<SEG_TPARTS_BATCH>(j, P, par, bx, cvsm.data()); else seg_ctl_body<SEG_TPARTS>(j, P, par, bx, cvsm.data()); } }
-            else if (P.tparts == SEG_TPARTS_BATCH) { for (int f = 0; f < SEG_NFILT; f++) for (uint32_t vg = 0; vg * SEG_VGRP_OF(SEG_TPARTS_BATCH) < j.nseg; vg++) seg_post_body<SEG_VGRP_OF(SEG_TPARTS_BATCH)>(j, P, seg_ctl_view(j, kv, f), kv, f, (int)vg, cvsm.data()); }
-            else { for (int f = 0; f < SEG_NFILT; f++) for (uint32_t vg = 0; vg * SEG_VGRP_OF(SEG_TPARTS) < j.nseg; vg++) seg_post_body<SEG_VGRP_OF(SEG_TPARTS)>(j, P, seg_ctl_view(j, kv, f), kv, f, (int)vg, cvsm.data()); }
+        const int par = attempt % 3;
+        for (int i = 0; i < nl; i++) {
+            const SegLaunch &L = launches[i];
+            std::vector<unsigned char> smem(L.lds_bytes, 0x5A);
+            auto run = [&](unsigned from, unsigned to) { for (unsigned bx = from; bx < to; bx++) seg_dispatch_block(L, j, P, par, bx, smem.data()); };
+            if (i == 0 && val_first) { run(L.a, L.grid_x); run(0, L.a); }      /* (L.a: the control workgroups of the first launch, the validation's behind them) */
+            else run(0, L.grid_x);
+            if (i == 0 && j.ctl[par].finished == 2u) break;
         }
         if (j.ctl[par].finished == 2u) break;
-        /* the enumeration's workgroups come in two sizes; the product picks by row width, SEG_HOST_ENUM_NT pins one */
-        int nt = j.nseg <= SEG_ENUM_NT_SMALL_MAX_NSEG ? 512 : 1024;
-        if (getenv("SEG_HOST_ENUM_NT")) nt = atoi(getenv("SEG_HOST_ENUM_NT")) == 1024 ? 1024 : 512;
-        /* the enumeration kernel is launched with exactly SEG_SM_ENUM_NT(nt) bytes of LDS: the bodies get a buffer of that size here, and the
-         * sanitizer build (tests/test_seg_host.py) sees any byte they touch beyond it */
-        std::vector<unsigned char> esm((size_t)SEG_SM_ENUM_NT(nt), 0x5A);
-        const bool seeds1 = P.unit == 1 && !P.seeded && P.ns <= SEG_NSP && P.seed_n > 0 && getenv("SEG_HOST_SEEDS") != nullptr && atoi(getenv("SEG_HOST_SEEDS")) != 0;
-        if (seeds1) {
-            /* pl_seg.hip:seg_k_enum_unit<1> (round 6: small and mid-size batches): the unit enumeration's bodies segment by segment, started from seeds */
-            if (getenv("SEG_HOST_SEED_KIN")) P.seed_kin = atoi(getenv("SEG_HOST_SEED_KIN"));
-            std::vector<unsigned char> usm((size_t)SEG_SM_ENUM_UNIT, 0x5A);
-            const uint32_t npairs = j.nseg * j.bpp;
-            for (int f = 0; f < SEG_NFILT; f++) {
-                const SegCtlView cv = seg_ctl_view(j, par, f);
-                if (seg_is_small(P, f)) { for (uint32_t g = 0; g * SEG_UNC_SMALL_OF(1) < npairs; g++) seg_enum_unit_body<SEG_NSS, 1, SEG_UNC_SMALL_OF(1)>(j, P, cv, par, f, (int)g, usm.data()); }
-                else if (seg_unit_from_seeds(j, P, cv, f, 1)) { for (uint32_t g = 0; g * SEG_UNC_SEEDS1 < npairs; g++) seg_enum_unit_body<SEG_SEED_LANES, 1, SEG_UNC_SEEDS1, true>(j, P, cv, par, f, (int)g, usm.data()); }
-                else { for (uint32_t g = 0; g * SEG_UNC < npairs; g++) seg_enum_unit_body<SEG_NSP, 1, SEG_UNC>(j, P, cv, par, f, (int)g, usm.data()); }
-            }
-            for (int f = 0; f < SEG_NFILT; f++) seg_first_body<SEG_UNT, false>(j, P, seg_ctl_view(j, par, f), par, f, usm.data());
-        } else
-        if (P.unit > 1) {
-            /* pl_seg.hip:seg_k_enum_unit: per candidate `per` workgroups of SEG_UNC (unit, channel) pairs, then the five walkers -- with the kernel's LDS size */
-            std::vector<unsigned char> usm((size_t)SEG_SM_ENUM_UNIT, 0x5A);
-            const bool seeds = getenv("SEG_HOST_SEEDS") != nullptr && atoi(getenv("SEG_HOST_SEEDS")) && P.seed_n > 0;     /* the first phase from seeds with a run-in (round 6) */
-            if (seeds && getenv("SEG_HOST_SEED_KIN")) P.seed_kin = atoi(getenv("SEG_HOST_SEED_KIN"));
-            const uint32_t perseed = (((j.nseg + SEG_UNIT - 1) / SEG_UNIT) * 4 + SEG_UNC_SEEDS - 1) / SEG_UNC_SEEDS;
-            const uint32_t perb = (((j.nseg + SEG_UNIT - 1) / SEG_UNIT) * 4 + SEG_UNC - 1) / SEG_UNC, pers = (((j.nseg + SEG_UNIT - 1) / SEG_UNIT) * 4 + SEG_UNC_SMALL - 1) / SEG_UNC_SMALL;
-            for (int f = 0; f < SEG_NFILT; f++) {
-                if (seg_is_small(P, f)) { for (uint32_t g = 0; g < pers; g++) if (g * SEG_UNC_SMALL < ((j.nseg + SEG_UNIT - 1) / SEG_UNIT) * j.bpp) seg_enum_unit_body<SEG_NSS, SEG_UNIT, SEG_UNC_SMALL>(j, P, seg_ctl_view(j, par, f), par, f, (int)g, usm.data()); }
-                else if (seeds && seg_unit_from_seeds(j, P, seg_ctl_view(j, par, f), f, 1)) { for (uint32_t g = 0; g < perseed; g++) if (g * SEG_UNC_SEEDS < ((j.nseg + SEG_UNIT - 1) / SEG_UNIT) * j.bpp) seg_enum_unit_body<SEG_SEED_LANES, SEG_UNIT, SEG_UNC_SEEDS, true>(j, P, seg_ctl_view(j, par, f), par, f, (int)g, usm.data()); }
-                else { for (uint32_t g = 0; g < perb; g++) if (g * SEG_UNC < ((j.nseg + SEG_UNIT - 1) / SEG_UNIT) * j.bpp) seg_enum_unit_body<SEG_NSP, SEG_UNIT, SEG_UNC>(j, P, seg_ctl_view(j, par, f), par, f, (int)g, usm.data()); }
-            }
-            for (int f = 0; f < SEG_NFILT; f++) seg_first_body<SEG_UNT, true>(j, P, seg_ctl_view(j, par, f), par, f, usm.data());
-        } else
-        if (P.seeded) {
-            std::vector<unsigned char> ssm((size_t)SEG_SM_ENUM_SEEDED(nt), 0x5A);
-            for (int f = 0; f < SEG_NFILT; f++)
-                for (uint32_t sg = 0; sg < j.nseg; sg++) {
-                    if (nt == 512) for (int ch = 0; ch < 2; ch++) seg_enum_seeded_body<512>(j, P, seg_ctl_view(j, par, f), par, f, (int)sg, ch, ssm.data());
-                    else seg_enum_seeded_body<1024>(j, P, seg_ctl_view(j, par, f), par, f, (int)sg, 0, ssm.data());
-                }
-        } else
-        for (int f = 0; f < SEG_NFILT; f++) {
-            if (nt == 512) {
-                if (seg_is_small(P, f)) for (uint32_t sg = 0; sg < j.nseg; sg += 4) seg_enum_small_body<512>(j, P, seg_ctl_view(j, par, f), par, f, (int)sg, esm.data());
-                else for (uint32_t sg = 0; sg < j.nseg; sg++) for (int ch = 0; ch < 2; ch++) seg_enum_body<512>(j, P, seg_ctl_view(j, par, f), par, f, (int)sg, ch, esm.data());
-            } else {
-                if (seg_is_small(P, f)) for (uint32_t sg = 0; sg < j.nseg; sg += 8) seg_enum_small_body<1024>(j, P, seg_ctl_view(j, par, f), par, f, (int)sg, esm.data());
-                else for (uint32_t sg = 0; sg < j.nseg; sg++) seg_enum_body<1024>(j, P, seg_ctl_view(j, par, f), par, f, (int)sg, 0, esm.data());
-            }
-        }
-        if (P.unit <= 1 && !seeds1) for (int f = 0; f < SEG_NFILT; f++) { if (nt == 512) seg_first_body<512, false>(j, P, seg_ctl_view(j, par, f), par, f, esm.data()); else seg_first_body<1024, false>(j, P, seg_ctl_view(j, par, f), par, f, esm.data()); }
-        if (P.seeded && j.nseg > 1) {   /* the gather kernel of seeded sets: every (filter, channel, block of segments) */
-            const unsigned nblk = (j.nseg - 1 + SEG_GS - 1) / SEG_GS;
-            for (int f = 0; f < SEG_NFILT; f++) for (int c = 0; c < 4; c++) for (unsigned b = 0; b < nblk; b++) seg_gather_seeded_body(j, seg_ctl_view(j, par, f), f, c, (int)b);
-        }
-        {   /* the chain kernel's LDS is sized by the row's segments: the same size here (the sanitizer build sees an overrun) */
-            std::vector<unsigned char> csm(P.seeded ? (size_t)SEG_SM_CHAIN(j.nseg) : (size_t)SEG_SM_CHAIN_X(P.unit > 1 ? (j.nseg + P.unit - 1) / P.unit : j.nseg), 0x5A);
-            for (int f = 0; f < SEG_NFILT; f++) for (int c = 0; c < 4; c++) {
-                if (P.seeded) seg_chain_body<true, SEG_CHAIN_THREADS, false>(j, P, seg_ctl_view(j, par, f), par, f, c, csm.data());
-                else if (P.unit > 1) seg_chain_body<false, SEG_CHAIN_THREADS_UNIT, true>(j, P, seg_ctl_view(j, par, f), par, f, c, csm.data());
-                else seg_chain_body<false, SEG_CHAIN_THREADS, false>(j, P, seg_ctl_view(j, par, f), par, f, c, csm.data());
-            }
-            if (P.unit > 1) seg_extremes_body<SEG_CHAIN_THREADS_UNIT>(j, P, seg_ctl_view(j, par, 0), par, csm.data()); else seg_extremes_body<SEG_CHAIN_THREADS>(j, P, seg_ctl_view(j, par, 0), par, csm.data());
-        }
-        { std::vector<unsigned char> rsm((size_t)SEG_SM_REPLAY, 0x5A); for (int f = 0; f < SEG_NFILT; f++) for (uint32_t g = 0; g < j.ngrp; g++) { if (P.unit > 1) seg_replay_body<SEG_REPLAY_NT_BATCH>(j, P, seg_ctl_view(j, par, f), par, f, (int)g, rsm.data()); else seg_replay_body<SEG_REPLAY_NT>(j, P, seg_ctl_view(j, par, f), par, f, (int)g, rsm.data()); } }
     }
     const SegCtl &fc = j.ctl[attempt % 3];
     if (getenv("SEG_HOST_VERBOSE")) {

@@ -337,6 +337,31 @@ def layout_host_lib():
     return _layout
 
 
+_seg_launch = None
+
+
+def seg_launch_host_lib():
+    """tests/c/seg_launch_host.cpp (the shape of a row attempt of the segment engine, pngloss_amd/csrc/pl_seg_launch.h, behind a C ABI, its dispatch functions
+    with recording stubs for kernel bodies) built into a shared object (cached per process)."""
+    global _seg_launch
+    if _seg_launch is None:
+        import subprocess
+        import tempfile
+        so = os.path.join(tempfile.mkdtemp(prefix="seg_launch_host_"), "libseg_launch_host.so")
+        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Werror", "-o", so, os.path.join(ROOT, "tests", "c", "seg_launch_host.cpp")], check=True)
+        lib = C.CDLL(so)
+        lib.seg_launch_host_constants.argtypes = [C.c_void_p]
+        lib.seg_launch_host_constants.restype = C.c_int
+        lib.seg_launch_host_sm_chain.argtypes = [C.c_int64, C.c_int]
+        lib.seg_launch_host_sm_chain.restype = C.c_int64
+        lib.seg_launch_host_launches.argtypes = [C.c_void_p, C.c_void_p]
+        lib.seg_launch_host_launches.restype = C.c_int
+        lib.seg_launch_host_visit.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]
+        lib.seg_launch_host_visit.restype = C.c_int64
+        _seg_launch = lib
+    return _seg_launch
+
+
 def run_seg_host(img, s=19, b=2, filters=True):
     """The segment-parallel engine's kernel bodies on the CPU: returns rc, out, filters, stats
     (attempts, restarts, retried rows, serial rows, unique symbols, bpp, chain states, status)."""
