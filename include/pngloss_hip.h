@@ -219,6 +219,51 @@ double pngloss_hip_last_total_ms(const pngloss_hip_ctx *ctx);
 /* Final 256-bin symbol histogram of image `index` of the last finished batch (host buffer of 256 uint32). */
 int pngloss_hip_last_histogram(pngloss_hip_ctx *ctx, size_t index, uint32_t *hist256);
 
+/* ---- How lossy a run was, measured on the device (no reference equivalent: the reference tool reports file sizes only).  The optimiser works in
+ * place, so the original is gone before a caller could compare -- and on the fast paths (device-resident batches, frames handed over by
+ * pngloss_hip_png_decode_batch_device[_z], PNGLOSS_HIP_Z_STREAM_ONLY) original and result never exist side by side on the host.  With the option
+ * "distortion" at "on" (pngloss_hip_set_option) every batch that goes through pngloss_hip_optimize_batch[_async], _batch_host, _host_emit or
+ * _host_zlib keeps a copy of its originals in an arena of the context (one more width * height * 4 bytes per image; if that cannot be had the
+ * call returns PNGLOSS_OUT_OF_MEMORY_ERROR before anything is enqueued) and compares the final RGBA8 with it: one copy kernel in front of the
+ * pipeline and one measuring kernel behind it, both on the caller's stream and inside the window pngloss_hip_last_total_ms reports.  Pixels,
+ * filter IDs, scanlines and zlib streams do not depend on the option.  The section-1 seam has no context to ask and is never measured.
+ *
+ * The record of an RGBA8 pair (a = original, b = result; channel c = 0..3 is R, G, B, A).  All integers: exact, and independent of the order of
+ * summation. */
+typedef struct {
+    uint64_t pixels;            /* width * height                                                                  */
+    uint64_t changed_pixels;    /* pixels in which any channel differs                                             */
+    uint64_t sq_err[4];         /* per channel: sum of (b_c - a_c)^2                                               */
+    uint32_t max_abs[4];        /* per channel: max of |b_c - a_c|                                                 */
+} pngloss_hip_distortion;
+
+/* Record of image `index` of the last finished batch.  PNGLOSS_INVALID_ARGUMENT when that batch ran with the option off, when the index is out of
+ * range or while a batch is pending.  After a host window that ran in chunks the index follows the chunks, as for pngloss_hip_last_histogram.
+ * The record of an image whose status != 0 is unspecified. */
+int pngloss_hip_last_distortion(pngloss_hip_ctx *ctx, size_t index, pngloss_hip_distortion *out);
+
+/* The same measurement on its own: n pairs of device-resident RGBA8 images (width * height * 4 contiguous bytes each, any alignment of 4), one
+ * launch of the same kernel, out[i] = record of pair i.  Synchronous: enqueued on `stream` (NULL = the default stream) and waited for.  A pair
+ * without pixels gives an all-zero record.  Compares the outputs of two builds or settings; independent of the option above.  Not while a batch
+ * is in flight on the context (PNGLOSS_INVALID_ARGUMENT). */
+typedef struct {
+    const void *d_a, *d_b;
+    uint32_t width, height;
+} pngloss_hip_image_pair;
+
+int pngloss_hip_compare_batch(pngloss_hip_ctx *ctx, const pngloss_hip_image_pair *pairs, size_t n, pngloss_hip_distortion *out, void *stream);
+
+/* Peak signal-to-noise ratio in dB over the channels of `channel_mask` (bit c = channel c):
+ *     10 * log10(255^2 * pixels * popcount(mask) / sum over the mask's channels of sq_err[c])
+ * +INFINITY when that sum is 0; NaN for pixels == 0, for mask 0 and for a mask above 0xF.  Host arithmetic only: needs no device.
+ * (For an image the optimiser reports as bytes_per_pixel 1, 2, 3, 4 the channels that are stored are 0x2, 0xA, 0x7, 0xF.) */
+double pngloss_hip_psnr_db(const pngloss_hip_distortion *d, unsigned channel_mask);
+
+/* pngloss_hip_set_option on every context of `multi` (the worst return code), and the record of images[index] of the last
+ * pngloss_hip_multi_optimize_batch_host call, whichever context it went to. */
+int pngloss_hip_multi_set_option(pngloss_hip_multi *multi, const char *name, const char *value);
+int pngloss_hip_multi_last_distortion(pngloss_hip_multi *multi, size_t index, pngloss_hip_distortion *out);
+
 /* ---- PNG read side behind the inflate.  Replaces what libpng does for rwpng_read_image24_libpng
  * (/root/reference/src/rwpng.c:179-400) between "inflated IDAT bytes" and "RGBA8 rows": the inverse scanline filters (a recurrence over
  * x and y, run as a row wavefront on the device) and the transformations that reader registers -- palette / low bit depths / tRNS
@@ -323,6 +368,8 @@ int pngloss_hip_last_engine_info(pngloss_hip_ctx *ctx, size_t index, int32_t inf
  *   pngloss_hip_optimize_batch_async a stream of its own: a third engine stream in the process slows every later engine run that waits on a caller's stream,
  *   so the library then runs the asynchronous entry in its blocking variant (it returns when the engine is done), and it never creates a third stream once
  *   any context of the process has used such a wait.
+ * Name "distortion", value "on" | "off" (default): measure every batch from here on (pngloss_hip_last_distortion, above).  "off" launches exactly what
+ *   the library launched before the option existed: no copy, no arena, no extra kernel.
  * Returns PNGLOSS_SUCCESS or PNGLOSS_INVALID_ARGUMENT (unknown name or value).
  * Results never depend on an option, on the engine, or on the environment: the remaining environment hooks (PNGLOSS_HIP_SEG_GROUPS, _SEG_UNIT, _ENUM_NT,
  * _NO_STREAM_WAIT, _SEGPROF, _DEBUG ...: timing and test pins) are read once, when a context is created, and none of them changes a byte; the debugging aid

@@ -11,6 +11,9 @@ from .lib import (  # noqa: F401
     PNG_FILTER_FLAGS,
     HipContext,
     HipMulti,
+    Distortion,
+    PSNR_MASK_OF_BPP,
+    psnr_db,
     multi_split,
     source_digest,
     build,
@@ -24,6 +27,6 @@ from .lib import (  # noqa: F401
 from .synth import SURVEY_FNV_BASIS, fnv1a64, synth_rgba  # noqa: F401
 
 __all__ = [
-    "PNG_FILTER_FLAGS", "HipContext", "HipMulti", "multi_split", "source_digest", "build", "hip_lib", "synth_lib", "optimize_with_rows", "optimize_with_stride",
+    "PNG_FILTER_FLAGS", "HipContext", "HipMulti", "Distortion", "PSNR_MASK_OF_BPP", "psnr_db", "multi_split", "source_digest", "build", "hip_lib", "synth_lib", "optimize_with_rows", "optimize_with_stride",
     "optimize_for_average_filter", "optimize_image", "synth_rgba", "fnv1a64", "SURVEY_FNV_BASIS",
 ]

@@ -42,6 +42,7 @@ struct options {
     bool from_stdin, to_stdout, force, skip_if_larger, strip, help, version, missing, verbose;
     bool gpu_deflate;          /* --gpu-deflate: IDAT data compressed on the device instead of by zlib level 9 */
     size_t total_files;        /* files of this call (how many GPUs are worth a context) */
+    bool distortion;           /* --distortion: one line per written file saying how far its pixels are from the input's (measured on the device) */
     bool gpu_read;             /* --gpu-read: inverse filters + expansion to RGBA8 on the device (inflate stays zlib on the decode threads) */
 };
 
@@ -63,6 +64,8 @@ static const char usage_text[] =
     "                    files several percent smaller than with zlib level 9, much faster)\n"
     "  --gpu-read        undo the PNG scanline filters and expand to RGBA on the GPU (plain or\n"
     "                    Adam7-interlaced files; the others are read with libpng as usual)\n"
+    "  --distortion      report how lossy each written file is: PSNR over the stored channels,\n"
+    "                    changed pixels, largest channel error (measured on the GPU)\n"
     "\n"
     "Lossily compresses PNGs by using more compressible colors that are close enough to the\n"
     "original values; the filter+quantise pass runs on the GPU (all files of a call as one batch).\n"
@@ -71,7 +74,7 @@ static const char usage_text[] =
 
 /* ------------------------------------------------------------------------------------------- options */
 
-enum { OPT_EXT = 256, OPT_NO_FORCE, OPT_SKIP_LARGER, OPT_STRIP, OPT_GPU_DEFLATE, OPT_GPU_READ };
+enum { OPT_EXT = 256, OPT_NO_FORCE, OPT_SKIP_LARGER, OPT_STRIP, OPT_GPU_DEFLATE, OPT_GPU_READ, OPT_DISTORTION };
 
 static bool parse_number(const char *text, unsigned long *out)
 {
@@ -93,6 +96,7 @@ static pngloss_error parse_options(int argc, char **argv, struct options *o)
         { "version", no_argument, NULL, 'V' },        { "help", no_argument, NULL, 'h' },
         { "gpu-deflate", no_argument, NULL, OPT_GPU_DEFLATE },
         { "gpu-read", no_argument, NULL, OPT_GPU_READ },
+        { "distortion", no_argument, NULL, OPT_DISTORTION },
         { NULL, 0, NULL, 0 },
     };
     for (int c; (c = getopt_long(argc, argv, "vqfo:Vhs:b:", table, NULL)) != -1;) {
@@ -106,6 +110,7 @@ static pngloss_error parse_options(int argc, char **argv, struct options *o)
         case OPT_STRIP: o->strip = true; break;
         case OPT_GPU_DEFLATE: o->gpu_deflate = true; break;
         case OPT_GPU_READ: o->gpu_read = true; break;
+        case OPT_DISTORTION: o->distortion = true; break;
         case 'h': o->help = true; break;
         case 'V': o->version = true; break;
         case 'o':
@@ -158,6 +163,8 @@ struct job {
     char *log;                /* buffered stderr text */
     size_t log_len;
     pngloss_hip_result gpu;
+    pngloss_hip_distortion distortion;   /* --distortion: the optimised pixels against the decoded input's (have_distortion: the library had a record) */
+    bool have_distortion;
     png_stream_source src;    /* --gpu-read: inflated scanlines waiting for the device (src.scanlines != NULL) */
 };
 
@@ -326,6 +333,20 @@ static pngloss_error encode_to(struct job *j, png24_image *img, unsigned char *f
     return rc;
 }
 
+/* --distortion: the line of a written file.  PSNR over the channels the file stores (gray is the G channel, pngloss_image.c:112-115) */
+static void say_distortion(struct job *j)
+{
+    const pngloss_hip_distortion *d = &j->distortion;
+    if (!d->changed_pixels) { say(j, "  distortion: none (lossless)\n"); return; }
+    const unsigned bpp = j->gpu.bytes_per_pixel;
+    const unsigned mask = bpp == 1 ? 0x2u : bpp == 2 ? 0xAu : bpp == 3 ? 0x7u : 0xFu;
+    unsigned largest = 0;
+    for (int c = 0; c < 4; c++)
+        if ((mask >> c & 1u) && d->max_abs[c] > largest) largest = d->max_abs[c];
+    say(j, "  distortion: PSNR %.2f dB, %llu of %llu pixels changed, largest channel error %u\n", pngloss_hip_psnr_db(d, mask),
+        (unsigned long long)d->changed_pixels, (unsigned long long)d->pixels, largest);
+}
+
 static void encode_job(struct job *j, const struct options *o)
 {
     if (j->status != SUCCESS) return;
@@ -334,6 +355,7 @@ static void encode_job(struct job *j, const struct options *o)
     j->out.chunks = j->in.chunks;          /* metadata travels to the output */
     j->in.chunks = NULL;
     pngloss_error rc = encode_to(j, &j->out, j->filters, o);
+    if (o->distortion && rc == SUCCESS && j->have_distortion) say_distortion(j);
     if (o->verbose) {
         if (rc == SUCCESS) {
             say(j, "  wrote %luKB file (%.1f%% of original)\n", (unsigned long)((j->out.file_size + 500UL) / 1000UL),
@@ -526,6 +548,8 @@ static pngloss_error run_window(struct job *jobs, size_t n, const struct options
                 for (size_t d = 0; d < o->total_files && at + 8 < sizeof list; d++) at += (size_t)snprintf(list + at, sizeof list - at, d ? ",%zu" : "%zu", d);
                 *ctx = pngloss_hip_multi_create(list);
             }
+            if (*ctx && o->distortion && pngloss_hip_multi_set_option(*ctx, "distortion", "on") != PNGLOSS_SUCCESS)
+                fputs("  warning: the library refused the option \"distortion\"; no distortion lines\n", stderr);
         }
         if (timing) fprintf(stderr, "  [timing] GPU contexts ready after %.3f s\n", now_s() - tc0);
         int rc = !*ctx ? PNGLOSS_HIP_ERROR
@@ -535,6 +559,7 @@ static pngloss_error run_window(struct job *jobs, size_t n, const struct options
             jobs[who[k]].gpu = res[k];
             jobs[who[k]].color_type = o->gpu_deflate ? zs[k].color_type : lines[k].color_type;
             jobs[who[k]].zsize = zs[k].size;
+            jobs[who[k]].have_distortion = o->distortion && *ctx && pngloss_hip_multi_last_distortion(*ctx, k, &jobs[who[k]].distortion) == PNGLOSS_SUCCESS;
             if (rc != PNGLOSS_SUCCESS && !(rc == PNGLOSS_INTERNAL_ABORT && res[k].status == 0)) {
                 /* (a batch in which single images failed reports PNGLOSS_INTERNAL_ABORT and leaves the others done.)
                  * Unlike the reference (pngloss.c:266 ignores the return value) a failed optimisation is an error:

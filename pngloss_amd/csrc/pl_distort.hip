@@ -1,0 +1,95 @@
+/*
+ * pl_distort.hip -- how lossy a run was, measured on the device (gfx950).  Two HBM-bound kernels around the pipeline of pl_host.hip:enqueue, both
+ * one launch for the whole batch (blockIdx.y = image), like the kernels of pl_prepost.hip:
+ *
+ *   pl_keep     copies the original RGBA8 of every image into the context's keep arena, before pl_classify / pl_repack rewrite it in place
+ *   pl_distort  behind pl_unpack: reads the kept original and the final pixels and adds the image's record up (pl_distort_core.h)
+ *
+ * pngloss_hip_compare_batch runs pl_distort alone, on two images of the caller's.  No reference equivalent.
+ */
+#include "pl_distort.h"
+
+namespace {
+
+constexpr int kThreads = 256, kWaves = kThreads / 64;
+
+__global__ __launch_bounds__(kThreads) void pl_keep(const PlDistortJob *__restrict__ jobs)
+{
+    const PlDistortJob j = jobs[blockIdx.y];
+    const size_t n = (size_t)j.pixels;
+    /* 16 B per lane per load and store where both sides allow it (the arena's side always does) */
+    const size_t n4 = pld_vector_quads(j.keep, j.img, n);
+    const uint4 *__restrict__ src4 = reinterpret_cast<const uint4 *>(j.img);
+    uint4 *__restrict__ dst4 = reinterpret_cast<uint4 *>(j.keep);
+    const size_t tid = (size_t)blockIdx.x * kThreads + threadIdx.x, nthreads = (size_t)gridDim.x * kThreads;
+    for (size_t i = tid; i < n4; i += nthreads) dst4[i] = src4[i];
+    for (size_t i = n4 * 4 + tid; i < n; i += nthreads) j.keep[i] = j.img[i];
+}
+
+__global__ __launch_bounds__(kThreads) void pl_distort(const PlDistortJob *__restrict__ jobs)
+{
+    const PlDistortJob j = jobs[blockIdx.y];
+    PldSum s = pld_thread(j.keep, j.img, (size_t)j.pixels, (size_t)blockIdx.x * kThreads + threadIdx.x, (size_t)gridDim.x * kThreads);
+    /* per wave, then per workgroup; then ONE atomic per quantity and workgroup, and none for a quantity that is zero (pl_classify's finding: same-address
+     * atomics, one per wave, were most of that kernel's time) */
+#pragma unroll
+    for (int off = 32; off; off >>= 1) {
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            s.sq[c] += __shfl_down(s.sq[c], off);
+            s.mx[c] = max(s.mx[c], __shfl_down(s.mx[c], off));
+        }
+        s.changed += __shfl_down(s.changed, off);
+    }
+    __shared__ uint64_t wsum[kWaves][5];       /* sq[0..3], changed */
+    __shared__ uint32_t wmax[kWaves][4];
+    const uint32_t wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        for (int c = 0; c < 4; c++) { wsum[wave][c] = s.sq[c]; wmax[wave][c] = s.mx[c]; }
+        wsum[wave][4] = s.changed;
+    }
+    __syncthreads();
+    const uint32_t t = threadIdx.x;
+    if (t < 5) {
+        uint64_t v = 0;
+        for (int w = 0; w < kWaves; w++) v += wsum[w][t];
+        if (v) atomicAdd(reinterpret_cast<unsigned long long *>(t < 4 ? &j.record->sq_err[t] : &j.record->changed_pixels), (unsigned long long)v);
+    } else if (t < 9) {
+        uint32_t v = 0;
+        for (int w = 0; w < kWaves; w++) v = max(v, wmax[w][t - 5]);
+        if (v) atomicMax(&j.record->max_abs[t - 5], v);
+    } else if (t == 9 && blockIdx.x == 0) j.record->pixels = j.pixels;
+}
+
+/* as pl_prepost.hip:batch_grid: enough workgroups to fill 256 CUs several times over, but never more than the batch needs; a launch takes at most
+ * 65535 images (gridDim.y) */
+constexpr size_t kMaxImages = 65535;
+dim3 distort_grid(size_t n, uint64_t max_pixels)
+{
+    size_t blocks = (size_t)((max_pixels + (uint64_t)kThreads * 16 - 1) / ((uint64_t)kThreads * 16));
+    size_t cap = (2048 + n - 1) / n;
+    if (cap < 8) cap = 8;
+    if (blocks > cap) blocks = cap;
+    if (blocks < 1) blocks = 1;
+    return dim3((unsigned)blocks, (unsigned)n, 1);
+}
+
+} // namespace
+
+hipError_t pl_launch_keep(const PlDistortJob *d_jobs, size_t n, uint64_t max_pixels, hipStream_t stream)
+{
+    for (size_t first = 0; first < n; first += kMaxImages) {
+        const size_t m = n - first < kMaxImages ? n - first : kMaxImages;
+        hipLaunchKernelGGL(pl_keep, distort_grid(m, max_pixels), dim3(kThreads), 0, stream, d_jobs + first);
+    }
+    return hipGetLastError();
+}
+
+hipError_t pl_launch_distort(const PlDistortJob *d_jobs, size_t n, uint64_t max_pixels, hipStream_t stream)
+{
+    for (size_t first = 0; first < n; first += kMaxImages) {
+        const size_t m = n - first < kMaxImages ? n - first : kMaxImages;
+        hipLaunchKernelGGL(pl_distort, distort_grid(m, max_pixels), dim3(kThreads), 0, stream, d_jobs + first);
+    }
+    return hipGetLastError();
+}

@@ -10,6 +10,7 @@
 #include "pl_deflate.h"
 #include "pl_pngread.h"
 #include "pl_inflate.h"
+#include "pl_distort.h"
 #define SEG_PLAIN_POINTERS   /* host plumbing only: SegJob is filled here, never dereferenced */
 #include "pl_seg.h"
 #include "pl_plan.h"
@@ -120,6 +121,14 @@ struct pngloss_hip_ctx {
     int seg_prio = 0;
     bool seg_prio_distinct = false;
 
+    /* option "distortion": the keep arena (pl_layout.h: job table, records, the originals pl_keep copies), regrown on demand like the others */
+    bool opt_distortion = false;     /* pngloss_hip_set_option("distortion", "on" | "off") */
+    char *d_keep = nullptr;
+    size_t keep_bytes = 0;
+    std::vector<PlDistortJob> h_dj;  /* (stays alive until the asynchronous copy that reads it is done: the next enqueue) */
+    const PlDistortRecord *d_records = nullptr;      /* the batch in flight is measured: its records, copied back by finish */
+    std::vector<pngloss_hip_distortion> distortion;  /* per image of the last finished batch; empty when it ran with the option off */
+
     std::vector<uint8_t> engine;    /* per image of the last batch: the row engine its plan gave it (PLR_ENGINE_*, pl_result.h) */
     long seg_attempts = 0;
 };
@@ -130,6 +139,10 @@ namespace {
 static_assert(PLL_UINT4 == sizeof(uint4) && PLL_UINT2 == sizeof(uint2), "pl_layout.h: element sizes of PlJob::cand, ::err0 and ::err1");
 static_assert(PLL_NFILT == PL_NFILT && PLL_NSYM == PL_NSYM && PLL_ROWSTAT_WORDS == PL_ROWSTAT_WORDS, "pl_layout.h: histogram and row counter sizes");
 static_assert(PLL_FLAG_GRAY == PL_FLAG_GRAY && PLL_FLAG_OPAQUE == PL_FLAG_OPAQUE, "pl_layout.h: class flag bits");
+/* the kernel's record IS the public one: finish copies it back as it stands */
+static_assert(sizeof(pngloss_hip_distortion) == sizeof(PlDistortRecord) && offsetof(pngloss_hip_distortion, pixels) == offsetof(PlDistortRecord, pixels) &&
+              offsetof(pngloss_hip_distortion, changed_pixels) == offsetof(PlDistortRecord, changed_pixels) && offsetof(pngloss_hip_distortion, sq_err) == offsetof(PlDistortRecord, sq_err) &&
+              offsetof(pngloss_hip_distortion, max_abs) == offsetof(PlDistortRecord, max_abs), "pngloss_hip_distortion and PlDistortRecord");
 
 float recip_up_host(long d)
 {
@@ -153,6 +166,24 @@ int grow(char *&p, size_t &have, size_t need, size_t divisor, bool pinned = fals
     return PNGLOSS_SUCCESS;
 }
 int ensure_ws(pngloss_hip_ctx *ctx, size_t bytes) { return grow(ctx->d_ws, ctx->ws_bytes, bytes, 4); }
+
+/* The job table of a measurement into the keep arena (which the caller has grown to lay.total), its records zeroed: image i is `pixels[i]` words at img[i],
+ * compared with the original at keep[i] -- or, keep == nullptr, with the place the layout gives it in the arena, for pl_keep to fill. */
+int upload_distort_jobs(pngloss_hip_ctx *ctx, const PlKeepLayout &lay, size_t n, const void *const *img, const void *const *keep, const uint64_t *pixels, hipStream_t stream)
+{
+    PlDistortRecord *const d_rec = reinterpret_cast<PlDistortRecord *>(ctx->d_keep + lay.records);
+    ctx->h_dj.assign(n, PlDistortJob{});
+    for (size_t i = 0; i < n; i++) {
+        PlDistortJob &d = ctx->h_dj[i];
+        d.keep = keep ? static_cast<uint32_t *>(const_cast<void *>(keep[i])) : reinterpret_cast<uint32_t *>(ctx->d_keep + lay.image[i]);
+        d.img = static_cast<const uint32_t *>(img[i]);
+        d.pixels = pixels[i];
+        d.record = d_rec + i;
+    }
+    PL_CHECK(hipMemcpyAsync(ctx->d_keep + lay.jobs, ctx->h_dj.data(), sizeof(PlDistortJob) * n, hipMemcpyHostToDevice, stream));
+    PL_CHECK(hipMemsetAsync(d_rec, 0, sizeof(PlDistortRecord) * n, stream));
+    return PNGLOSS_SUCCESS;
+}
 
 struct EmitTarget { void *d_ids; void *d_rows; uint32_t pitch; };
 
@@ -460,6 +491,9 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
     ctx->h_jobs.clear();
     ctx->n_last = 0;
     ctx->split_last = false;                                         /* (only a split host window sets it again: batch_host) */
+    ctx->distortion.clear();
+    ctx->d_records = nullptr;
+    const bool distort = ctx->opt_distortion;
     const PlHooks &hk = ctx->hooks;
     PlPlanInput in;
     in.strength = strength; in.bleed = bleed; in.hooks = hk;
@@ -507,6 +541,13 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
                                               sizeof(PlJob), sizeof(SegJob));
     int rc = ensure_ws(ctx, lay.total);
     if (rc) return rc;
+    /* option "distortion": room for every original beside the workspace -- or the call fails here, with nothing enqueued */
+    PlKeepLayout keep;
+    if (distort) {
+        keep = pl_keep_layout(in.width, in.height, true, sizeof(PlDistortJob), sizeof(PlDistortRecord));
+        rc = grow(ctx->d_keep, ctx->keep_bytes, keep.total, 8);
+        if (rc) return rc;
+    }
     for (size_t i = 0; i < n; i++) {
         const WsLayout &l = lay.ws[i];
         char *b = ctx->d_ws + lay.image[i];
@@ -553,7 +594,21 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
     prm.force_careful = hk.force_careful;   /* test hook, see pl_device.h */
     prm.engine_mode = plan.engine_mode;
 
+    const PlDistortJob *const d_dj = distort ? reinterpret_cast<const PlDistortJob *>(ctx->d_keep + keep.jobs) : nullptr;
+    uint64_t max_pixels = 0;
+    if (distort) {
+        std::vector<const void *> img(n);
+        std::vector<uint64_t> pixels(n);
+        for (size_t i = 0; i < n; i++) {
+            img[i] = images[i].d_rgba;
+            pixels[i] = (uint64_t)images[i].width * images[i].height;
+            max_pixels = std::max(max_pixels, pixels[i]);
+        }
+        rc = upload_distort_jobs(ctx, keep, n, img.data(), nullptr, pixels.data(), stream);
+        if (rc) return rc;
+    }
     PL_CHECK(hipEventRecord(ctx->ev[0], stream));
+    if (distort) PL_CHECK(pl_launch_keep(d_dj, n, max_pixels, stream));      /* the originals, before pl_classify / pl_repack rewrite the images in place */
     PL_CHECK(pl_launch_prepare(d_jobs, ctx->h_jobs.data(), n, stream, !use_rows));
     ctx->engine.assign(n, (uint8_t)(use_rows ? PLR_ENGINE_ROWS : PLR_ENGINE_WG));
     for (uint32_t i : plan.seg_list) ctx->engine[i] = (uint8_t)PLR_ENGINE_SEG;
@@ -575,6 +630,7 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
     {
         /* (behind this point the segment engine's launch thread may be running: it is joined before an error is returned) */
         hipError_t e = pl_launch_finish(d_jobs, ctx->h_jobs.data(), n, stream);
+        if (e == hipSuccess && distort) e = pl_launch_distort(d_dj, n, max_pixels, stream);      /* behind pl_unpack: the final RGBA8 against the kept original */
         if (e == hipSuccess) e = pl_launch_emit(d_jobs, ctx->h_jobs.data(), n, stream);
         if (e == hipSuccess) e = hipEventRecord(ctx->ev[3], stream);
         if (e != hipSuccess) {
@@ -586,6 +642,7 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
     }
     ctx->n_last = n;
     ctx->last_stream = stream;
+    if (distort) ctx->d_records = reinterpret_cast<const PlDistortRecord *>(ctx->d_keep + keep.records);
     ctx->pending = true;
     return PNGLOSS_SUCCESS;
 }
@@ -684,6 +741,11 @@ int finish(pngloss_hip_ctx *ctx, pngloss_hip_result *results, size_t n)
     ctx->engine_ms = ms;
     PL_CHECK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[3]));
     ctx->total_ms = ms;
+    if (ctx->d_records) {
+        std::vector<pngloss_hip_distortion> got(ctx->n_last);
+        PL_CHECK(hipMemcpy(got.data(), ctx->d_records, sizeof(pngloss_hip_distortion) * ctx->n_last, hipMemcpyDeviceToHost));
+        ctx->distortion.swap(got);
+    }
     int worst = PNGLOSS_SUCCESS;
     for (size_t i = 0; i < ctx->n_last; i++) {
         int32_t r[PLR_WORDS] = { 0 };
@@ -971,6 +1033,7 @@ void pngloss_hip_destroy(pngloss_hip_ctx *ctx)
     if (ctx->d_arena) (void)hipFree(ctx->d_arena);
     if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
     if (ctx->d_frames) (void)hipFree(ctx->d_frames);
+    if (ctx->d_keep) (void)hipFree(ctx->d_keep);
     if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
     if (ctx->h_progress) (void)hipHostFree(ctx->h_progress);
     if (ctx->h_seg_words) (void)hipHostFree(ctx->h_seg_words);
@@ -1079,6 +1142,7 @@ static int batch_host(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images
     }
     K = std::min(K, ctx->peers.size() + 1);
     if (K <= 1) return batch_host_one(ctx, images, n, quantization_strength, bleed_divider, results, lines, zs);
+    for (pngloss_hip_ctx *p : ctx->peers) p->opt_distortion = ctx->opt_distortion;       /* the other chunks measure what this one measures */
     std::vector<uint64_t> pixels(n);
     for (size_t i = 0; i < n; i++) pixels[i] = (uint64_t)images[i].width * images[i].height;
     const std::vector<size_t> first = pl_host_window_cut(pixels, K);
@@ -1122,6 +1186,7 @@ int pngloss_hip_optimize_batch_host(pngloss_hip_ctx *ctx, const pngloss_hip_host
  * results back in input order.  No collective: images are independent. ---------------------------------------------- */
 struct pngloss_hip_multi {
     std::vector<pngloss_hip_ctx *> ctx;
+    std::vector<std::pair<int, size_t>> where;   /* per image of the last call: the context it went to, and its index in that context's batch */
 };
 
 void pngloss_hip_multi_split(const pngloss_hip_host_image *images, size_t n, int parts, int *owner)
@@ -1197,6 +1262,11 @@ int pngloss_hip_multi_optimize_batch_host(pngloss_hip_multi *m, const pngloss_hi
     const int parts = (int)m->ctx.size();
     std::vector<int> owner(n ? n : 1, 0);
     pngloss_hip_multi_split(images, n, parts, owner.data());
+    {
+        std::vector<size_t> taken((size_t)parts, 0);
+        m->where.resize(n);
+        for (size_t i = 0; i < n; i++) m->where[i] = std::make_pair(owner[i], taken[(size_t)owner[i]]++);
+    }
     std::vector<int> rcs((size_t)parts, PNGLOSS_SUCCESS);
     std::vector<std::thread> pool;
     for (int p2 = 0; p2 < parts; p2++)
@@ -1264,6 +1334,72 @@ int pngloss_hip_last_histogram(pngloss_hip_ctx *ctx, size_t index, uint32_t *his
     PL_CHECK(hipSetDevice(ctx->device));
     PL_CHECK(hipMemcpy(hist256, ctx->h_jobs[index].final_hist, sizeof(uint32_t) * PL_NSYM, hipMemcpyDeviceToHost));
     return PNGLOSS_SUCCESS;
+}
+
+int pngloss_hip_last_distortion(pngloss_hip_ctx *ctx, size_t index, pngloss_hip_distortion *out)
+{
+    ctx = chunk_of(ctx, index);
+    if (!ctx || !out || ctx->pending || index >= ctx->n_last || index >= ctx->distortion.size()) return PNGLOSS_INVALID_ARGUMENT;
+    *out = ctx->distortion[index];
+    return PNGLOSS_SUCCESS;
+}
+
+int pngloss_hip_multi_last_distortion(pngloss_hip_multi *m, size_t index, pngloss_hip_distortion *out)
+{
+    if (!m || index >= m->where.size()) return PNGLOSS_INVALID_ARGUMENT;
+    return pngloss_hip_last_distortion(m->ctx[(size_t)m->where[index].first], m->where[index].second, out);
+}
+
+int pngloss_hip_multi_set_option(pngloss_hip_multi *m, const char *name, const char *value)
+{
+    if (!m || m->ctx.empty()) return PNGLOSS_INVALID_ARGUMENT;
+    int worst = PNGLOSS_SUCCESS;
+    for (pngloss_hip_ctx *c : m->ctx) {
+        const int rc = pngloss_hip_set_option(c, name, value);
+        if (rc != PNGLOSS_SUCCESS) worst = rc;
+    }
+    return worst;
+}
+
+int pngloss_hip_compare_batch(pngloss_hip_ctx *ctx, const pngloss_hip_image_pair *pairs, size_t n, pngloss_hip_distortion *out, void *stream_)
+{
+    if (!ctx || (n && (!pairs || !out))) return PNGLOSS_INVALID_ARGUMENT;
+    if (ctx->pending) {
+        std::fprintf(stderr, "pngloss_hip: a batch is in flight on this context; call pngloss_hip_finish first\n");
+        return PNGLOSS_INVALID_ARGUMENT;
+    }
+    if (!n) return PNGLOSS_SUCCESS;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    std::vector<const void *> a(n), b(n);
+    std::vector<uint64_t> pixels(n);
+    uint64_t max_pixels = 0;
+    for (size_t i = 0; i < n; i++) {
+        pixels[i] = (uint64_t)pairs[i].width * pairs[i].height;
+        if (pixels[i] && (!pairs[i].d_a || !pairs[i].d_b)) return PNGLOSS_INVALID_ARGUMENT;
+        a[i] = pairs[i].d_a; b[i] = pairs[i].d_b;
+        max_pixels = std::max(max_pixels, pixels[i]);
+    }
+    PL_CHECK(hipSetDevice(ctx->device));
+    const PlKeepLayout lay = pl_keep_layout(std::vector<uint32_t>(n, 0), std::vector<uint32_t>(n, 0), false, sizeof(PlDistortJob), sizeof(PlDistortRecord));
+    int rc = grow(ctx->d_keep, ctx->keep_bytes, lay.total, 8);
+    if (rc) return rc;
+    rc = upload_distort_jobs(ctx, lay, n, b.data(), a.data(), pixels.data(), stream);
+    if (rc) return rc;
+    PL_CHECK(pl_launch_distort(reinterpret_cast<const PlDistortJob *>(ctx->d_keep + lay.jobs), n, max_pixels, stream));
+    PL_CHECK(hipMemcpyAsync(out, ctx->d_keep + lay.records, sizeof(pngloss_hip_distortion) * n, hipMemcpyDeviceToHost, stream));
+    PL_CHECK(hipStreamSynchronize(stream));
+    return PNGLOSS_SUCCESS;
+}
+
+double pngloss_hip_psnr_db(const pngloss_hip_distortion *d, unsigned channel_mask)
+{
+    if (!d || !d->pixels || !channel_mask || channel_mask > 0xFu) return std::nan("");
+    uint64_t sum = 0;
+    int channels = 0;
+    for (int c = 0; c < 4; c++)
+        if (channel_mask & (1u << c)) { sum += d->sq_err[c]; channels++; }
+    if (!sum) return (double)INFINITY;
+    return 10.0 * std::log10(255.0 * 255.0 * (double)d->pixels * (double)channels / (double)sum);
 }
 
 int pngloss_hip_png_decode_batch_host(pngloss_hip_ctx *ctx, const pngloss_hip_png_source *src, size_t n)
@@ -1455,6 +1591,12 @@ int pngloss_hip_set_option(pngloss_hip_ctx *ctx, const char *name, const char *v
          * asynchronous entry a stream of its own (run_seg_engine: a third engine stream in the process halves every later engine run that waits on a caller's stream) */
         if (std::strcmp(value, "auto") == 0 || std::strcmp(value, "2") == 0) { ctx->opt_launch_groups = 0; return PNGLOSS_SUCCESS; }
         if (std::strcmp(value, "3") == 0) { ctx->opt_launch_groups = 3; return PNGLOSS_SUCCESS; }
+        return PNGLOSS_INVALID_ARGUMENT;
+    }
+    if (std::strcmp(name, "distortion") == 0) {
+        /* measure every batch from here on (pl_distort.hip): "on" | "off" (default) */
+        if (std::strcmp(value, "on") == 0) { ctx->opt_distortion = true; return PNGLOSS_SUCCESS; }
+        if (std::strcmp(value, "off") == 0) { ctx->opt_distortion = false; return PNGLOSS_SUCCESS; }
         return PNGLOSS_INVALID_ARGUMENT;
     }
     return PNGLOSS_INVALID_ARGUMENT;

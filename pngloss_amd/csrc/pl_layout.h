@@ -1,6 +1,7 @@
 /*
  * pl_layout.h -- every carve-up of a buffer the host shim makes, as pure functions from sizes to offsets: the batch workspace of enqueue(), the
- * arena of a host window (batch_host_one), the read side's workspace and frame arena (png_decode_body), and the size a buffer is regrown to.
+ * arena of a host window (batch_host_one), the keep arena of the distortion measurement, the read side's workspace and frame arena
+ * (png_decode_body), and the size a buffer is regrown to.
  * Internal.
  *
  * Plain C++17 without HIP, like pl_plan.h: pl_host.hip turns the offsets into pointers, copies and launches, and tests/c/layout_host.cpp compiles
@@ -156,6 +157,30 @@ inline PlWindowLayout pl_window_layout(const std::vector<PlWindowIn> &in)
         m.rows = take((size_t)m.pitch * (want ? in[i].height : 0));
     }
     return w;
+}
+
+/* ================================================================================================ the keep arena (option "distortion": enqueue, compare_batch) */
+
+/* The PlDistortJob table at 0, then one record per image, then -- with `originals` -- room for the original RGBA8 of every image (pl_keep fills it,
+ * pl_distort reads it).  pngloss_hip_compare_batch measures two images of the caller's and keeps nothing: tables only. */
+struct PlKeepLayout {
+    size_t jobs = 0, records = 0;
+    std::vector<size_t> image;          /* [n] the image's original: width * height * 4 bytes (all 0 without `originals`) */
+    size_t total = 0;
+};
+
+/* job_bytes, record_bytes: sizeof(PlDistortJob), sizeof(PlDistortRecord) */
+inline PlKeepLayout pl_keep_layout(const std::vector<uint32_t> &width, const std::vector<uint32_t> &height, bool originals, size_t job_bytes, size_t record_bytes)
+{
+    PlKeepLayout k;
+    const size_t n = width.size();
+    auto take = [&](size_t bytes) { size_t at = k.total; k.total = pl_align_up(k.total + bytes, PLL_ALIGN); return at; };
+    k.jobs = take(job_bytes * (n ? n : 1));
+    k.records = take(record_bytes * (n ? n : 1));
+    k.image.assign(n, 0);
+    if (originals)
+        for (size_t i = 0; i < n; i++) k.image[i] = take((size_t)width[i] * height[i] * 4);
+    return k;
 }
 
 /* ================================================================================================ the read side (png_decode_body) */

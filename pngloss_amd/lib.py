@@ -103,6 +103,34 @@ class Result(C.Structure):
                 ("retried_rows", C.c_uint32), ("repaired_pixels", C.c_uint32)]
 
 
+class Distortion(C.Structure):
+    """pngloss_hip_distortion: how far a result is from its original (a = original, b = result; channels R, G, B, A).  All exact integers."""
+    _fields_ = [("pixels", C.c_uint64), ("changed_pixels", C.c_uint64), ("sq_err", C.c_uint64 * 4), ("max_abs", C.c_uint32 * 4)]
+
+    def as_dict(self):
+        return dict(pixels=self.pixels, changed_pixels=self.changed_pixels, sq_err=list(self.sq_err), max_abs=list(self.max_abs))
+
+    def psnr_db(self, channel_mask=0xF):
+        return psnr_db(self, channel_mask)
+
+
+class ImagePair(C.Structure):
+    _fields_ = [("d_a", C.c_void_p), ("d_b", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
+#: the channels an image of `bytes_per_pixel` 1..4 stores (gray is the G channel): the mask pngloss_hip_psnr_db takes for it
+PSNR_MASK_OF_BPP = {1: 0x2, 2: 0xA, 3: 0x7, 4: 0xF}
+
+
+def psnr_db(distortion, channel_mask=0xF):
+    """pngloss_hip_psnr_db: 10 log10(255^2 * pixels * popcount(mask) / sum of sq_err over the mask's channels); inf for a sum of 0, nan for no
+    pixels or a mask outside 1..15.  `distortion`: a Distortion or the dict Distortion.as_dict() gives.  Host arithmetic: needs no GPU."""
+    if not isinstance(distortion, Distortion):
+        d = distortion
+        distortion = Distortion(d["pixels"], d["changed_pixels"], (C.c_uint64 * 4)(*d["sq_err"]), (C.c_uint32 * 4)(*d["max_abs"]))
+    return hip_lib().pngloss_hip_psnr_db(C.byref(distortion), channel_mask)
+
+
 def build(verbose: bool = False) -> None:
     """Compile libpngloss_hip.so (hipcc, gfx950) and libpngloss_synth.so (gcc) in-tree."""
     r = subprocess.run(["make", "-C", _CSRC, "-j4"], capture_output=True, text=True)
@@ -145,6 +173,7 @@ ABI_SYMBOLS = (
     "pngloss_hip_last_histogram", "pngloss_hip_last_engine_info", "pngloss_hip_png_decode_batch_host", "pngloss_hip_png_decode_batch_host_status", "pngloss_hip_png_decode_batch_device", "pngloss_hip_png_decode_batch_device_z", "pngloss_hip_pinned_alloc", "pngloss_hip_pinned_free", "pngloss_hip_set_option", "pngloss_hip_version",
     "pngloss_hip_multi_create", "pngloss_hip_multi_destroy", "pngloss_hip_multi_count", "pngloss_hip_multi_split",
     "pngloss_hip_multi_optimize_batch_host",
+    "pngloss_hip_last_distortion", "pngloss_hip_compare_batch", "pngloss_hip_psnr_db", "pngloss_hip_multi_set_option", "pngloss_hip_multi_last_distortion",
 )
 
 
@@ -208,6 +237,18 @@ def hip_lib():
             lib.pngloss_hip_last_histogram.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
             lib.pngloss_hip_last_histogram.restype = C.c_int
             lib.pngloss_hip_version.restype = C.c_char_p
+            lib.pngloss_hip_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
+            lib.pngloss_hip_set_option.restype = C.c_int
+            lib.pngloss_hip_last_distortion.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(Distortion)]
+            lib.pngloss_hip_last_distortion.restype = C.c_int
+            lib.pngloss_hip_compare_batch.argtypes = [C.c_void_p, C.POINTER(ImagePair), C.c_size_t, C.POINTER(Distortion), C.c_void_p]
+            lib.pngloss_hip_compare_batch.restype = C.c_int
+            lib.pngloss_hip_psnr_db.argtypes = [C.POINTER(Distortion), C.c_uint]
+            lib.pngloss_hip_psnr_db.restype = C.c_double
+            lib.pngloss_hip_multi_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
+            lib.pngloss_hip_multi_set_option.restype = C.c_int
+            lib.pngloss_hip_multi_last_distortion.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(Distortion)]
+            lib.pngloss_hip_multi_last_distortion.restype = C.c_int
             _hip = lib
         return _hip
 
@@ -297,8 +338,6 @@ class HipContext:
 
     def set_option(self, name, value):
         """pngloss_hip_set_option: e.g. ("engine", "seg" | "wg" | "auto")"""
-        self._lib.pngloss_hip_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
-        self._lib.pngloss_hip_set_option.restype = C.c_int
         _check(self._lib.pngloss_hip_set_option(self._ctx, name.encode(), value.encode()), "set_option")
 
     def enqueue(self, images, strength=19, bleed=2, stream=0):
@@ -484,6 +523,24 @@ class HipContext:
         _check(self._lib.pngloss_hip_last_engine_info(self._ctx, index, a), "engine_info")
         return dict(engine={3: "segment-parallel", 0: "workgroup-per-image", 4: "row-statistics (strength 0)"}.get(a[0], a[0]), attempts=a[1], restarts=a[2], serial_rows=a[3], none_dropped=a[4], walked_segments=a[5], launch_groups=a[6], stream_wait=a[7])
 
+    def distortion(self, index=0):
+        """pngloss_hip_last_distortion: the Distortion of image `index` of the last finished batch, which must have run with
+        set_option("distortion", "on") -- otherwise, for an index out of range and while a batch is pending the call fails (pngloss_error 4)."""
+        d = Distortion()
+        _check(self._lib.pngloss_hip_last_distortion(self._ctx, index, C.byref(d)), "last_distortion")
+        return d
+
+    def compare(self, pairs, stream=0):
+        """pngloss_hip_compare_batch: pairs = sequence of (d_a_ptr, d_b_ptr, width, height), device-resident RGBA8; returns one Distortion per pair
+        (b against a).  Synchronous."""
+        n = len(pairs)
+        arr = (ImagePair * max(n, 1))()
+        for i, (a, b, w, h) in enumerate(pairs):
+            arr[i] = ImagePair(a or None, b or None, w, h)
+        out = (Distortion * max(n, 1))()
+        _check(self._lib.pngloss_hip_compare_batch(self._ctx, arr, n, out, stream or None), "compare_batch")
+        return [out[i] for i in range(n)]
+
     def histogram(self, index=0):
         h = np.zeros(256, np.uint32)
         _check(self._lib.pngloss_hip_last_histogram(self._ctx, index, h.ctypes.data_as(C.c_void_p)), "histogram")
@@ -540,6 +597,16 @@ class HipMulti:
             self.close()
         except Exception:
             pass
+
+    def set_option(self, name, value):
+        """pngloss_hip_multi_set_option: the option on every context, e.g. ("distortion", "on")"""
+        _check(self._lib.pngloss_hip_multi_set_option(self._m, name.encode(), value.encode()), "multi_set_option")
+
+    def distortion(self, index=0):
+        """pngloss_hip_multi_last_distortion: the Distortion of arrays[index] of the last run_host, whichever context it went to"""
+        d = Distortion()
+        _check(self._lib.pngloss_hip_multi_last_distortion(self._m, index, C.byref(d)), "multi_last_distortion")
+        return d
 
     def run_host(self, arrays, strength=19, bleed=2, want_filters=True):
         outs = [np.ascontiguousarray(a).copy() for a in arrays]
