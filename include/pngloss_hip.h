@@ -264,6 +264,64 @@ double pngloss_hip_psnr_db(const pngloss_hip_distortion *d, unsigned channel_mas
 int pngloss_hip_multi_set_option(pngloss_hip_multi *multi, const char *name, const char *value);
 int pngloss_hip_multi_last_distortion(pngloss_hip_multi *multi, size_t index, pngloss_hip_distortion *out);
 
+/* ---- A strength per image, found from a distortion target (no reference equivalent: the reference tool takes -s and nothing else).  A strength
+ * says nothing about how the result will look, and the right one differs from image to image; the optimiser works in place, so a caller who
+ * wanted "at least 38 dB" had to reload the original for every try.  Here the original stays on the device between the probes.
+ *
+ * A probe of an image at a strength is ACCEPTED when all of these hold, rec being its pngloss_hip_distortion against the original and mask the
+ * channels its result stores (0x2 / 0xA / 0x7 / 0xF for bytes_per_pixel 1 / 2 / 3 / 4, as for pngloss_hip_psnr_db above):
+ *     its status is 0;
+ *     min_psnr_db == 0, or pngloss_hip_psnr_db(&rec, mask) >= min_psnr_db;
+ *     max_abs_error == 0, or the largest rec.max_abs[c] over the mask's channels is <= max_abs_error.
+ * An image without pixels is accepted.  PSNR is NOT monotone in the strength, so the chosen strength is defined by this procedure, per image, and
+ * not as "the largest strength that passes":
+ *     1. probe M = max_strength; if it is accepted, the chosen strength is M
+ *     2. otherwise lo = 0, hi = M (strength 0 changes no pixel and counts as accepted without a probe)
+ *     3. while hi - lo > 1: probe mid = (lo + hi) / 2, rounded down; accepted: lo = mid, otherwise hi = mid
+ *     4. the chosen strength is lo
+ * At most 1 + ceil(log2 M) probes, 1 for M <= 1.  A probe whose status is not 0 ends that image's search: the image keeps that probe's result and
+ * status, and its report names that probe's strength. */
+typedef struct {
+    double   min_psnr_db;    /* 0 = no PSNR condition; +inf = only lossless results pass; NaN or < 0: PNGLOSS_INVALID_ARGUMENT */
+    uint32_t max_abs_error;  /* 0 = no condition; 1..255 = largest allowed channel error; > 255: PNGLOSS_INVALID_ARGUMENT */
+    uint32_t max_strength;   /* M, 0..255: the search never goes above it; > 255: PNGLOSS_INVALID_ARGUMENT */
+} pngloss_hip_target;
+
+typedef struct {
+    uint32_t strength;       /* chosen */
+    uint32_t probes;         /* probes of the rule above */
+    uint32_t runs;           /* row-engine runs spent on this image */
+    uint32_t reserved;
+    pngloss_hip_distortion distortion;   /* of the result that was kept */
+} pngloss_hip_target_report;
+
+/* The search on n device-resident images.  SYNCHRONOUS.  On return image i holds what pngloss_hip_optimize_batch at reports[i].strength writes,
+ * byte for byte: pixels, d_row_filters and results[i] -- whose diagnostics slot repaired_pixels is that of the run that produced it
+ * (results and reports may be NULL).  Every round the images still searching are grouped by
+ * the strength they probe next and each group runs as one ordinary batch, one group after the other: the plan, the engine choice and the engines
+ * are those of pngloss_hip_optimize_batch.  Originals, and per image the best result so far with its row filters, live in a search arena of the
+ * context (2 * width * height * 4 + height bytes per image; if it cannot be had the call returns PNGLOSS_OUT_OF_MEMORY_ERROR before any image is
+ * touched); one batched copy kernel per round moves them, the measuring kernel of the option "distortion" compares against the search's own
+ * originals.  No engine run is repeated: runs == probes, except that an image none of whose probes was accepted (M > 0) gets strength 0 run once
+ * at the end: runs == probes + 1.  Any other error code than PNGLOSS_INTERNAL_ABORT (single images failed, the others are done) leaves the images
+ * unspecified.
+ * After the call pngloss_hip_last_distortion, _last_histogram and _last_engine_info return PNGLOSS_INVALID_ARGUMENT (no single batch exists to
+ * index); the option "distortion" is left as the caller set it and plays no part in the search. */
+int pngloss_hip_optimize_batch_target(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n,
+                                      const pngloss_hip_target *target, long bleed_divider, void *stream,
+                                      pngloss_hip_result *results, pngloss_hip_target_report *reports);
+
+/* The same for host images over every context of `multi`, for the command line tool: the images are split like pngloss_hip_multi_optimize_batch_host
+ * splits them; each context uploads its images, finds their strengths with the search above (on copies: nothing is written back), then runs the
+ * existing host-window path once per distinct chosen strength on that strength's images -- scanlines, GPU deflate, windows in chunks and
+ * PNGLOSS_HIP_Z_STREAM_ONLY as there.  Outputs equal those of pngloss_hip_multi_optimize_batch_host at reports[i].strength, image by image.  This
+ * form may spend one more run per image: runs <= probes + 1.  results, scanlines, streams, reports may be NULL (independently).  After the call
+ * pngloss_hip_multi_last_distortion returns PNGLOSS_INVALID_ARGUMENT: the records are in the reports. */
+int pngloss_hip_multi_optimize_batch_host_target(pngloss_hip_multi *multi, const pngloss_hip_host_image *images, size_t n,
+                                                 const pngloss_hip_target *target, long bleed_divider, pngloss_hip_result *results,
+                                                 pngloss_hip_scanlines *scanlines, pngloss_hip_zstream *streams,
+                                                 pngloss_hip_target_report *reports);
+
 /* ---- PNG read side behind the inflate.  Replaces what libpng does for rwpng_read_image24_libpng
  * (/root/reference/src/rwpng.c:179-400) between "inflated IDAT bytes" and "RGBA8 rows": the inverse scanline filters (a recurrence over
  * x and y, run as a row wavefront on the device) and the transformations that reader registers -- palette / low bit depths / tRNS

@@ -43,6 +43,10 @@ struct options {
     bool gpu_deflate;          /* --gpu-deflate: IDAT data compressed on the device instead of by zlib level 9 */
     size_t total_files;        /* files of this call (how many GPUs are worth a context) */
     bool distortion;           /* --distortion: one line per written file saying how far its pixels are from the input's (measured on the device) */
+    bool have_max_error;
+    bool have_target;          /* --target-psnr / --max-error: the strength is found per file, -s is its upper bound */
+    double target_psnr;        /* 0: no PSNR condition */
+    unsigned long max_error;   /* 0: no condition */
     bool gpu_read;             /* --gpu-read: inverse filters + expansion to RGBA8 on the device (inflate stays zlib on the decode threads) */
 };
 
@@ -66,6 +70,10 @@ static const char usage_text[] =
     "                    Adam7-interlaced files; the others are read with libpng as usual)\n"
     "  --distortion      report how lossy each written file is: PSNR over the stored channels,\n"
     "                    changed pixels, largest channel error (measured on the GPU)\n"
+    "  --target-psnr DB  pick each file's strength itself: the search (at most -s, by halving) for a\n"
+    "                    result with at least DB decibels of PSNR over the stored channels\n"
+    "  --max-error N     the same with a bound on the largest channel error, 1 to 255; both may\n"
+    "                    be given (searched on the GPU; -v prints the strength chosen)\n"
     "\n"
     "Lossily compresses PNGs by using more compressible colors that are close enough to the\n"
     "original values; the filter+quantise pass runs on the GPU (all files of a call as one batch).\n"
@@ -74,12 +82,21 @@ static const char usage_text[] =
 
 /* ------------------------------------------------------------------------------------------- options */
 
-enum { OPT_EXT = 256, OPT_NO_FORCE, OPT_SKIP_LARGER, OPT_STRIP, OPT_GPU_DEFLATE, OPT_GPU_READ, OPT_DISTORTION };
+enum { OPT_EXT = 256, OPT_NO_FORCE, OPT_SKIP_LARGER, OPT_STRIP, OPT_GPU_DEFLATE, OPT_GPU_READ, OPT_DISTORTION, OPT_TARGET_PSNR, OPT_MAX_ERROR };
 
 static bool parse_number(const char *text, unsigned long *out)
 {
     char *end;
     unsigned long v = strtoul(text, &end, 10);
+    if (end == text || *end) return false;
+    *out = v;
+    return true;
+}
+
+static bool parse_decibels(const char *text, double *out)
+{
+    char *end;
+    double v = strtod(text, &end);
     if (end == text || *end) return false;
     *out = v;
     return true;
@@ -97,6 +114,8 @@ static pngloss_error parse_options(int argc, char **argv, struct options *o)
         { "gpu-deflate", no_argument, NULL, OPT_GPU_DEFLATE },
         { "gpu-read", no_argument, NULL, OPT_GPU_READ },
         { "distortion", no_argument, NULL, OPT_DISTORTION },
+        { "target-psnr", required_argument, NULL, OPT_TARGET_PSNR },
+        { "max-error", required_argument, NULL, OPT_MAX_ERROR },
         { NULL, 0, NULL, 0 },
     };
     for (int c; (c = getopt_long(argc, argv, "vqfo:Vhs:b:", table, NULL)) != -1;) {
@@ -111,6 +130,15 @@ static pngloss_error parse_options(int argc, char **argv, struct options *o)
         case OPT_GPU_DEFLATE: o->gpu_deflate = true; break;
         case OPT_GPU_READ: o->gpu_read = true; break;
         case OPT_DISTORTION: o->distortion = true; break;
+        case OPT_TARGET_PSNR:
+            if (!parse_decibels(optarg, &o->target_psnr)) { fputs("--target-psnr requires a numeric argument\n", stderr); return INVALID_ARGUMENT; }
+            o->have_target = true;
+            break;
+        case OPT_MAX_ERROR:
+            if (!parse_number(optarg, &o->max_error)) { fputs("--max-error requires a numeric argument\n", stderr); return INVALID_ARGUMENT; }
+            o->have_target = true;
+            o->have_max_error = true;
+            break;
         case 'h': o->help = true; break;
         case 'V': o->version = true; break;
         case 'o':
@@ -163,6 +191,7 @@ struct job {
     char *log;                /* buffered stderr text */
     size_t log_len;
     pngloss_hip_result gpu;
+    pngloss_hip_target_report target;    /* --target-psnr / --max-error: the strength the search chose for this file */
     pngloss_hip_distortion distortion;   /* --distortion: the optimised pixels against the decoded input's (have_distortion: the library had a record) */
     bool have_distortion;
     png_stream_source src;    /* --gpu-read: inflated scanlines waiting for the device (src.scanlines != NULL) */
@@ -350,6 +379,7 @@ static void say_distortion(struct job *j)
 static void encode_job(struct job *j, const struct options *o)
 {
     if (j->status != SUCCESS) return;
+    if (o->verbose && o->have_target) say(j, "  strength %u chosen in %u probes\n", j->target.strength, j->target.probes);
     if (o->verbose) say(j, "  compression complete\n  used %u unique symbols\n", j->gpu.unique_symbols);
     if (o->skip_if_larger) j->out.maximum_file_size = j->in.file_size - 1;
     j->out.chunks = j->in.chunks;          /* metadata travels to the output */
@@ -512,8 +542,9 @@ static pngloss_error run_window(struct job *jobs, size_t n, const struct options
     pngloss_hip_scanlines *lines = calloc(n ? n : 1, sizeof *lines);
     pngloss_hip_zstream *zs = calloc(n ? n : 1, sizeof *zs);
     pngloss_hip_result *res = calloc(n ? n : 1, sizeof *res);
+    pngloss_hip_target_report *rep = calloc(n ? n : 1, sizeof *rep);
     size_t *who = calloc(n ? n : 1, sizeof *who), m = 0;
-    if (!imgs || !lines || !zs || !res || !who) { free(imgs); free(lines); free(zs); free(res); free(who); return OUT_OF_MEMORY_ERROR; }
+    if (!imgs || !lines || !zs || !res || !who || !rep) { free(imgs); free(lines); free(zs); free(res); free(who); free(rep); return OUT_OF_MEMORY_ERROR; }
     for (size_t i = 0; i < n; i++)
         if (jobs[i].status == SUCCESS) {
             imgs[m] = (pngloss_hip_host_image){ jobs[i].out.rgba_data, jobs[i].filters, jobs[i].out.width, jobs[i].out.height };
@@ -552,13 +583,22 @@ static pngloss_error run_window(struct job *jobs, size_t n, const struct options
                 fputs("  warning: the library refused the option \"distortion\"; no distortion lines\n", stderr);
         }
         if (timing) fprintf(stderr, "  [timing] GPU contexts ready after %.3f s\n", now_s() - tc0);
+        /* --target-psnr / --max-error: the library searches a strength per file, -s bounds it; the records come back in the reports */
+        const pngloss_hip_target target = { o->target_psnr, (uint32_t)o->max_error, (uint32_t)o->strength };
         int rc = !*ctx ? PNGLOSS_HIP_ERROR
+               : o->have_target ? pngloss_hip_multi_optimize_batch_host_target(*ctx, imgs, m, &target, (long)o->bleed, res, o->gpu_deflate ? NULL : lines,
+                                                                               o->gpu_deflate ? zs : NULL, rep)
                : pngloss_hip_multi_optimize_batch_host(*ctx, imgs, m, (unsigned)o->strength, (long)o->bleed, res,
                                                        o->gpu_deflate ? NULL : lines, o->gpu_deflate ? zs : NULL);
         for (size_t k = 0; k < m; k++) {
             jobs[who[k]].gpu = res[k];
             jobs[who[k]].color_type = o->gpu_deflate ? zs[k].color_type : lines[k].color_type;
             jobs[who[k]].zsize = zs[k].size;
+            if (o->have_target) {
+                jobs[who[k]].target = rep[k];
+                jobs[who[k]].distortion = rep[k].distortion;
+                jobs[who[k]].have_distortion = o->distortion && (rc == PNGLOSS_SUCCESS || rc == PNGLOSS_INTERNAL_ABORT);
+            } else
             jobs[who[k]].have_distortion = o->distortion && *ctx && pngloss_hip_multi_last_distortion(*ctx, k, &jobs[who[k]].distortion) == PNGLOSS_SUCCESS;
             if (rc != PNGLOSS_SUCCESS && !(rc == PNGLOSS_INTERNAL_ABORT && res[k].status == 0)) {
                 /* (a batch in which single images failed reports PNGLOSS_INTERNAL_ABORT and leaves the others done.)
@@ -569,7 +609,7 @@ static pngloss_error run_window(struct job *jobs, size_t n, const struct options
             }
         }
     }
-    free(imgs); free(lines); free(zs); free(res); free(who);
+    free(imgs); free(lines); free(zs); free(res); free(who); free(rep);
     const double t2 = now_s();
 
     for_each_job(jobs, n, o, encode_job);
@@ -589,6 +629,8 @@ int main(int argc, char **argv)
     if (o.missing) { print_version_banner(stderr); fputs(usage_text, stderr); return MISSING_ARGUMENT; }
     if (o.help) { print_version_banner(stdout); fputs(usage_text, stdout); return SUCCESS; }
     if (o.strength > 255) { fputs("Must specify a strength in the range 0-255.\n", stderr); return INVALID_ARGUMENT; }
+    if (o.have_target && !(o.target_psnr >= 0.0)) { fputs("Must specify a PSNR target of 0 dB or more.\n", stderr); return INVALID_ARGUMENT; }
+    if (o.have_max_error && (o.max_error < 1 || o.max_error > 255)) { fputs("Must specify a largest channel error in the range 1-255.\n", stderr); return INVALID_ARGUMENT; }
     if (o.bleed < 1 || o.bleed > 32767) { fputs("Must specify a bleed divider in the range 1-32767.\n", stderr); return INVALID_ARGUMENT; }
     if (o.extension && o.output_path) { fputs("--ext and --output options can't be used at the same time\n", stderr); return INVALID_ARGUMENT; }
     if (!o.extension) o.extension = "-loss.png";

@@ -15,6 +15,7 @@
 #ifndef PL_DISTORT_CORE_H
 #define PL_DISTORT_CORE_H
 
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -118,6 +119,19 @@ PLD_HD void pld_record(PlDistortRecord &r, const PldSum &s, uint64_t pixels)
     r.pixels = pixels;
     r.changed_pixels = s.changed;
     for (int c = 0; c < 4; c++) { r.sq_err[c] = s.sq[c]; r.max_abs[c] = s.mx[c]; }
+}
+
+/* Peak signal-to-noise ratio in dB of a record over the channels of `channel_mask` (bit c = channel c): the one formula behind pngloss_hip_psnr_db
+ * (include/pngloss_hip.h says what it returns when) and behind the acceptance rule of pl_target.h.  Host arithmetic only. */
+inline double pld_psnr_db(uint64_t pixels, const uint64_t sq_err[4], unsigned channel_mask)
+{
+    if (!pixels || !channel_mask || channel_mask > 0xFu) return (double)NAN;
+    uint64_t sum = 0;
+    int channels = 0;
+    for (int c = 0; c < 4; c++)
+        if (channel_mask & (1u << c)) { sum += sq_err[c]; channels++; }
+    if (!sum) return (double)INFINITY;
+    return 10.0 * log10(255.0 * 255.0 * (double)pixels * (double)channels / (double)sum);
 }
 
 #endif

@@ -11,6 +11,8 @@
 #include "pl_pngread.h"
 #include "pl_inflate.h"
 #include "pl_distort.h"
+#include "pl_target.h"
+#include "pl_target_dev.h"
 #define SEG_PLAIN_POINTERS   /* host plumbing only: SegJob is filled here, never dereferenced */
 #include "pl_seg.h"
 #include "pl_plan.h"
@@ -128,6 +130,10 @@ struct pngloss_hip_ctx {
     std::vector<PlDistortJob> h_dj;  /* (stays alive until the asynchronous copy that reads it is done: the next enqueue) */
     const PlDistortRecord *d_records = nullptr;      /* the batch in flight is measured: its records, copied back by finish */
     std::vector<pngloss_hip_distortion> distortion;  /* per image of the last finished batch; empty when it ran with the option off */
+
+    /* pngloss_hip_optimize_batch_target: the search arena (pl_target.h: tables, originals, best results so far), regrown on demand like the others */
+    char *d_target = nullptr;
+    size_t target_bytes = 0;
 
     std::vector<uint8_t> engine;    /* per image of the last batch: the row engine its plan gave it (PLR_ENGINE_*, pl_result.h) */
     long seg_attempts = 0;
@@ -1034,6 +1040,7 @@ void pngloss_hip_destroy(pngloss_hip_ctx *ctx)
     if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
     if (ctx->d_frames) (void)hipFree(ctx->d_frames);
     if (ctx->d_keep) (void)hipFree(ctx->d_keep);
+    if (ctx->d_target) (void)hipFree(ctx->d_target);
     if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
     if (ctx->h_progress) (void)hipHostFree(ctx->h_progress);
     if (ctx->h_seg_words) (void)hipHostFree(ctx->h_seg_words);
@@ -1297,6 +1304,317 @@ int pngloss_hip_multi_optimize_batch_host(pngloss_hip_multi *m, const pngloss_hi
     return worst;
 }
 
+/* ---- a strength per image from a distortion target: pl_target.h decides, this does what it says (include/pngloss_hip.h has the contract) ---- */
+namespace {
+struct TargetImage {
+    PlTargetSearch search;
+    pngloss_hip_result last{}, kept{};                 /* of the probe just run / of the result the image ends with */
+    pngloss_hip_distortion last_rec{}, kept_rec{};
+    long best = -1;                                    /* the strength whose (accepted) result the arena's stash holds; -1: none */
+    long in_place = -1;                                /* the strength whose result the image itself holds; -1: the original */
+    uint32_t runs = 0;
+};
+}
+
+/* images: device-resident; the arena (ctx->d_target) has been grown to lay.total.  commit: at the end every image holds the result of its chosen
+ * strength (else the images are left as the last probes left them: the host form runs the chosen strengths through the host-window path). */
+static int target_search(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n, const PlTargetLayout &lay, const pngloss_hip_target &t,
+                         long bleed, hipStream_t stream, bool commit, pngloss_hip_result *results, pngloss_hip_target_report *reports)
+{
+    /* whatever happens: the caller's option back, and no "last batch" to index */
+    struct Guard {
+        pngloss_hip_ctx *c; bool opt;
+        ~Guard() { c->opt_distortion = opt; c->n_last = 0; c->h_jobs.clear(); c->distortion.clear(); c->d_records = nullptr; c->split_last = false; }
+    } guard{ ctx, ctx->opt_distortion };
+    ctx->opt_distortion = false;                       /* the search measures against its own originals (the keep arena is laid out afresh by every enqueue) */
+    char *const arena = ctx->d_target;
+    PlMoveJob *const d_moves = reinterpret_cast<PlMoveJob *>(arena + lay.moves);
+    PlDistortJob *const d_dj = reinterpret_cast<PlDistortJob *>(arena + lay.jobs);
+    PlDistortRecord *const d_rec = reinterpret_cast<PlDistortRecord *>(arena + lay.records);
+    std::vector<TargetImage> st(n);
+    std::vector<PlTargetSearch> searches(n);
+    for (size_t i = 0; i < n; i++) st[i].search = pl_target_begin(t.max_strength);
+    auto px_bytes = [&](size_t i) { return (uint64_t)images[i].width * images[i].height * 4; };
+    auto filter_bytes = [&](size_t i) { return (uint64_t)((images[i].width && images[i].d_row_filters) ? images[i].height : 0); };
+    auto add = [](std::vector<PlMoveJob> &v, const void *src, void *dst, uint64_t bytes) { if (bytes) v.push_back(PlMoveJob{ src, dst, bytes }); };
+    /* (the host tables stay alive until the call's last synchronisation: asynchronous copies read them) */
+    std::vector<std::vector<PlMoveJob>> move_tables;
+    std::vector<std::vector<PlDistortJob>> distort_tables;
+    /* one launch of pl_move for a table of jobs */
+    auto move = [&](std::vector<PlMoveJob> jobs) -> int {
+        if (jobs.empty()) return PNGLOSS_SUCCESS;
+        uint64_t max_bytes = 0;
+        for (const PlMoveJob &j : jobs) max_bytes = std::max(max_bytes, j.bytes);
+        move_tables.push_back(std::move(jobs));
+        const std::vector<PlMoveJob> &tb = move_tables.back();
+        PL_CHECK(hipMemcpyAsync(d_moves, tb.data(), sizeof(PlMoveJob) * tb.size(), hipMemcpyHostToDevice, stream));
+        PL_CHECK(pl_launch_move(d_moves, tb.size(), max_bytes, stream));
+        return PNGLOSS_SUCCESS;
+    };
+    /* one ordinary batch: the images `who` at `strength`, through the entry the synchronous call uses */
+    auto run_group = [&](uint32_t strength, const std::vector<uint32_t> &who) -> int {
+        std::vector<pngloss_hip_image_desc> descs(who.size());
+        std::vector<pngloss_hip_result> res(who.size());
+        for (size_t k = 0; k < who.size(); k++) descs[k] = images[who[k]];
+        ctx->sync_call = true; ctx->three_groups_ok = true;
+        int rc = enqueue(ctx, descs.data(), descs.size(), nullptr, strength, bleed, stream);
+        ctx->sync_call = false; ctx->three_groups_ok = false;
+        if (rc == PNGLOSS_SUCCESS) rc = finish(ctx, res.data(), res.size());
+        if (rc != PNGLOSS_SUCCESS && rc != PNGLOSS_INTERNAL_ABORT) return rc;      /* (single images that failed say so in their status) */
+        for (size_t k = 0; k < who.size(); k++) {
+            TargetImage &s = st[who[k]];
+            s.last = res[k]; s.in_place = (long)strength; s.runs++;
+        }
+        return PNGLOSS_SUCCESS;
+    };
+    /* one launch of pl_distort: the images `who` against the search's own originals */
+    auto measure = [&](const std::vector<uint32_t> &who) -> int {
+        if (who.empty()) return PNGLOSS_SUCCESS;
+        distort_tables.emplace_back(who.size());
+        std::vector<PlDistortJob> &dj = distort_tables.back();
+        uint64_t max_pixels = 0;
+        for (size_t k = 0; k < who.size(); k++) {
+            const size_t i = who[k];
+            dj[k].keep = reinterpret_cast<uint32_t *>(arena + lay.image[i].orig);
+            dj[k].img = static_cast<const uint32_t *>(images[i].d_rgba);
+            dj[k].pixels = (uint64_t)images[i].width * images[i].height;
+            dj[k].record = d_rec + k;
+            max_pixels = std::max(max_pixels, dj[k].pixels);
+        }
+        std::vector<pngloss_hip_distortion> got(who.size());
+        PL_CHECK(hipMemcpyAsync(d_dj, dj.data(), sizeof(PlDistortJob) * dj.size(), hipMemcpyHostToDevice, stream));
+        PL_CHECK(hipMemsetAsync(d_rec, 0, sizeof(PlDistortRecord) * dj.size(), stream));
+        PL_CHECK(pl_launch_distort(d_dj, dj.size(), max_pixels, stream));
+        PL_CHECK(hipMemcpyAsync(got.data(), d_rec, sizeof(PlDistortRecord) * dj.size(), hipMemcpyDeviceToHost, stream));
+        PL_CHECK(hipStreamSynchronize(stream));
+        for (size_t k = 0; k < who.size(); k++) st[who[k]].last_rec = got[k];
+        return PNGLOSS_SUCCESS;
+    };
+
+    /* the originals, before the first probe rewrites the images in place */
+    int rc;
+    {
+        std::vector<PlMoveJob> save;
+        for (size_t i = 0; i < n; i++) add(save, images[i].d_rgba, arena + lay.image[i].orig, px_bytes(i));
+        rc = move(std::move(save));
+        if (rc) return rc;
+    }
+    for (;;) {
+        for (size_t i = 0; i < n; i++) searches[i] = st[i].search;
+        const auto groups = pl_target_groups(searches);
+        if (groups.empty()) break;
+        std::vector<PlMoveJob> back, stash;
+        std::vector<uint32_t> probed;
+        for (const auto &g : groups)
+            for (uint32_t i : g.second) {
+                if (st[i].in_place >= 0) add(back, arena + lay.image[i].orig, images[i].d_rgba, px_bytes(i));
+                probed.push_back(i);
+            }
+        rc = move(std::move(back));
+        for (size_t g = 0; g < groups.size() && rc == PNGLOSS_SUCCESS; g++) rc = run_group(groups[g].first, groups[g].second);      /* one after the other: a context takes one batch at a time */
+        if (rc == PNGLOSS_SUCCESS) rc = measure(probed);
+        if (rc) return rc;
+        for (uint32_t i : probed) {
+            TargetImage &s = st[i];
+            if (s.last.status != 0) {                            /* ends this image's search: it keeps this probe's result and status */
+                pl_target_fail(s.search);
+                s.kept = s.last; s.kept_rec = s.last_rec;
+                continue;
+            }
+            const bool accepted = pl_target_accept(t, s.last_rec, s.last.status, s.last.bytes_per_pixel);
+            const uint32_t strength = s.search.next;
+            pl_target_step(s.search, accepted);
+            if (!accepted) continue;
+            s.kept = s.last; s.kept_rec = s.last_rec; s.best = (long)strength;
+            if (s.search.done) continue;                         /* (the chosen strength's result is in place) */
+            add(stash, images[i].d_rgba, arena + lay.image[i].best, px_bytes(i));
+            add(stash, images[i].d_row_filters, arena + lay.image[i].best_filters, filter_bytes(i));
+        }
+        rc = move(std::move(stash));
+        if (rc) return rc;
+    }
+    /* the kept results back into the images whose last probe was refused; an image with no accepted probe gets strength 0, run once */
+    std::vector<PlMoveJob> fin;
+    std::vector<uint32_t> zero;
+    for (size_t i = 0; i < n; i++) {
+        TargetImage &s = st[i];
+        if (s.search.failed) continue;
+        if (s.in_place == (long)s.search.chosen) {
+            if (s.best != (long)s.search.chosen) { s.kept = s.last; s.kept_rec = s.last_rec; }
+            continue;
+        }
+        if (s.best == (long)s.search.chosen) {
+            if (commit) {
+                add(fin, arena + lay.image[i].best, images[i].d_rgba, px_bytes(i));
+                add(fin, arena + lay.image[i].best_filters, images[i].d_row_filters, filter_bytes(i));
+            }
+            continue;
+        }
+        zero.push_back((uint32_t)i);
+        s.kept = pngloss_hip_result{ 0, 0, 0, 0, 0 }; s.kept_rec = pngloss_hip_distortion{};
+        if (commit) add(fin, arena + lay.image[i].orig, images[i].d_rgba, px_bytes(i));
+    }
+    rc = move(std::move(fin));
+    if (rc == PNGLOSS_SUCCESS && commit && !zero.empty()) {
+        rc = run_group(0, zero);
+        if (rc == PNGLOSS_SUCCESS) rc = measure(zero);
+        for (uint32_t i : zero) { st[i].kept = st[i].last; st[i].kept_rec = st[i].last_rec; }
+    }
+    if (rc) return rc;
+    PL_CHECK(hipStreamSynchronize(stream));
+    int worst = PNGLOSS_SUCCESS;
+    for (size_t i = 0; i < n; i++) {
+        const TargetImage &s = st[i];
+        if (results) results[i] = s.kept;
+        if (reports) reports[i] = pngloss_hip_target_report{ s.search.chosen, s.search.probes, s.runs, 0, s.kept_rec };
+        if (s.kept.status) worst = PNGLOSS_INTERNAL_ABORT;
+    }
+    return worst;
+}
+
+static int target_arguments(const pngloss_hip_target *target, long bleed_divider)
+{
+    const int rc = pl_target_check(target);
+    if (rc) {
+        std::fprintf(stderr, "pngloss_hip: the target needs min_psnr_db >= 0 (not NaN), max_abs_error 0..255 and max_strength 0..255\n");
+        return rc;
+    }
+    if (bleed_divider < 1 || bleed_divider > 32767) {
+        std::fprintf(stderr, "pngloss_hip: bleed must be 1..32767 (got %ld)\n", bleed_divider);
+        return PNGLOSS_INVALID_ARGUMENT;
+    }
+    return PNGLOSS_SUCCESS;
+}
+
+int pngloss_hip_optimize_batch_target(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n,
+                                      const pngloss_hip_target *target, long bleed_divider, void *stream,
+                                      pngloss_hip_result *results, pngloss_hip_target_report *reports)
+{
+    int rc = target_arguments(target, bleed_divider);
+    if (rc) return rc;
+    if (!ctx || (n && !images)) return PNGLOSS_INVALID_ARGUMENT;
+    if (ctx->pending) {
+        std::fprintf(stderr, "pngloss_hip: previous batch not finished; call pngloss_hip_finish first\n");
+        return PNGLOSS_INVALID_ARGUMENT;
+    }
+    std::vector<uint32_t> width(n), height(n);
+    for (size_t i = 0; i < n; i++) {
+        if (!images[i].d_rgba && images[i].width && images[i].height) return PNGLOSS_INVALID_ARGUMENT;
+        width[i] = images[i].width; height[i] = images[i].height;
+    }
+    PL_CHECK(hipSetDevice(ctx->device));
+    /* room for every original and every best result beside the workspace -- or the call fails here, with no image touched */
+    const PlTargetLayout lay = pl_target_layout(width, height, false, sizeof(PlMoveJob), sizeof(PlDistortJob), sizeof(PlDistortRecord));
+    rc = grow(ctx->d_target, ctx->target_bytes, lay.total, 8);
+    if (rc) return rc;
+    return target_search(ctx, images, n, lay, *target, bleed_divider, static_cast<hipStream_t>(stream), true, results, reports);
+}
+
+/* one context's share of pngloss_hip_multi_optimize_batch_host_target */
+static int batch_host_target(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images, size_t n, const pngloss_hip_target &target, long bleed_divider,
+                             pngloss_hip_result *results, pngloss_hip_scanlines *lines, pngloss_hip_zstream *zs, pngloss_hip_target_report *reports)
+{
+    if (!ctx || ctx->pending) return PNGLOSS_INVALID_ARGUMENT;
+    PL_CHECK(hipSetDevice(ctx->device));
+    std::vector<uint32_t> width(n), height(n);
+    for (size_t i = 0; i < n; i++) {
+        if (images[i].width && images[i].height && !images[i].rgba) return PNGLOSS_INVALID_ARGUMENT;
+        width[i] = images[i].width; height[i] = images[i].height;
+    }
+    const PlTargetLayout lay = pl_target_layout(width, height, true, sizeof(PlMoveJob), sizeof(PlDistortJob), sizeof(PlDistortRecord));
+    int rc = grow(ctx->d_target, ctx->target_bytes, lay.total, 8);
+    if (rc) return rc;
+    if (!ctx->copy_stream) PL_CHECK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+    /* copies of the images go up and are searched on; the host images stay as they are until the chosen strengths run below */
+    std::vector<pngloss_hip_image_desc> descs(n);
+    for (size_t i = 0; i < n; i++) {
+        const size_t px = (size_t)width[i] * height[i];
+        descs[i] = pngloss_hip_image_desc{ px ? ctx->d_target + lay.image[i].img : nullptr, (px && images[i].row_filters) ? ctx->d_target + lay.image[i].filters : nullptr, width[i], height[i] };
+        if (px) PL_CHECK(hipMemcpyAsync(descs[i].d_rgba, images[i].rgba, px * 4, hipMemcpyHostToDevice, ctx->copy_stream));
+    }
+    PL_CHECK(hipStreamSynchronize(ctx->copy_stream));
+    std::vector<pngloss_hip_target_report> rep(n ? n : 1);
+    rc = target_search(ctx, descs.data(), n, lay, target, bleed_divider, ctx->copy_stream, false, nullptr, rep.data());
+    if (rc != PNGLOSS_SUCCESS && rc != PNGLOSS_INTERNAL_ABORT) return rc;
+    /* the existing host-window path, once per distinct chosen strength; measured, so that every report carries the record of what was written */
+    const bool opt = ctx->opt_distortion;
+    int worst = PNGLOSS_SUCCESS;
+    for (uint32_t strength = 0; strength < 256; strength++) {
+        std::vector<size_t> who;
+        for (size_t i = 0; i < n; i++) if (rep[i].strength == strength) who.push_back(i);
+        if (who.empty()) continue;
+        std::vector<pngloss_hip_host_image> im(who.size());
+        std::vector<pngloss_hip_result> rs(who.size());
+        std::vector<pngloss_hip_scanlines> ln(lines ? who.size() : 0);
+        std::vector<pngloss_hip_zstream> zz(zs ? who.size() : 0);
+        for (size_t k = 0; k < who.size(); k++) {
+            im[k] = images[who[k]];
+            if (lines) ln[k] = lines[who[k]];
+            if (zs) zz[k] = zs[who[k]];
+        }
+        ctx->opt_distortion = true;
+        rc = batch_host(ctx, im.data(), im.size(), strength, bleed_divider, rs.data(), lines ? ln.data() : nullptr, zs ? zz.data() : nullptr);
+        ctx->opt_distortion = opt;
+        for (size_t k = 0; k < who.size(); k++) {
+            const size_t i = who[k];
+            if (results) results[i] = rs[k];
+            if (lines) lines[i] = ln[k];
+            if (zs) zs[i] = zz[k];
+            rep[i].runs++;
+            if (rc == PNGLOSS_SUCCESS || rc == PNGLOSS_INTERNAL_ABORT) (void)pngloss_hip_last_distortion(ctx, k, &rep[i].distortion);
+        }
+        if (rc != PNGLOSS_SUCCESS && (worst == PNGLOSS_SUCCESS || worst == PNGLOSS_INTERNAL_ABORT)) worst = rc;
+    }
+    for (pngloss_hip_ctx *p : ctx->peers) if (p) { p->opt_distortion = opt; p->n_last = 0; p->distortion.clear(); }
+    ctx->n_last = 0; ctx->split_last = false; ctx->distortion.clear(); ctx->h_jobs.clear();      /* no single batch to index */
+    if (reports) for (size_t i = 0; i < n; i++) reports[i] = rep[i];
+    return worst;
+}
+
+int pngloss_hip_multi_optimize_batch_host_target(pngloss_hip_multi *m, const pngloss_hip_host_image *images, size_t n,
+                                                 const pngloss_hip_target *target, long bleed_divider, pngloss_hip_result *results,
+                                                 pngloss_hip_scanlines *scanlines, pngloss_hip_zstream *streams,
+                                                 pngloss_hip_target_report *reports)
+{
+    const int arc = target_arguments(target, bleed_divider);
+    if (arc) return arc;
+    if (!m || m->ctx.empty() || (n && !images)) return PNGLOSS_INVALID_ARGUMENT;
+    const int parts = (int)m->ctx.size();
+    std::vector<int> owner(n ? n : 1, 0);
+    pngloss_hip_multi_split(images, n, parts, owner.data());
+    m->where.clear();                                   /* (pngloss_hip_multi_last_distortion: the records are in the reports) */
+    std::vector<int> rcs((size_t)parts, PNGLOSS_SUCCESS);
+    std::vector<std::thread> pool;
+    for (int p2 = 0; p2 < parts; p2++)
+        pool.emplace_back([&, p2]() {
+            std::vector<size_t> mine;
+            for (size_t i = 0; i < n; i++) if (owner[i] == p2) mine.push_back(i);
+            if (mine.empty()) return;
+            std::vector<pngloss_hip_host_image> im(mine.size());
+            std::vector<pngloss_hip_result> rs(mine.size());
+            std::vector<pngloss_hip_target_report> rp(mine.size());
+            std::vector<pngloss_hip_scanlines> ln(scanlines ? mine.size() : 0);
+            std::vector<pngloss_hip_zstream> zz(streams ? mine.size() : 0);
+            for (size_t k = 0; k < mine.size(); k++) {
+                im[k] = images[mine[k]];
+                if (scanlines) ln[k] = scanlines[mine[k]];
+                if (streams) zz[k] = streams[mine[k]];
+            }
+            rcs[(size_t)p2] = batch_host_target(m->ctx[(size_t)p2], im.data(), im.size(), *target, bleed_divider, rs.data(),
+                                                scanlines ? ln.data() : nullptr, streams ? zz.data() : nullptr, rp.data());
+            for (size_t k = 0; k < mine.size(); k++) {
+                if (results) results[mine[k]] = rs[k];
+                if (reports) reports[mine[k]] = rp[k];
+                if (scanlines) scanlines[mine[k]] = ln[k];
+                if (streams) streams[mine[k]] = zz[k];
+            }
+        });
+    for (auto &th : pool) th.join();
+    int worst = PNGLOSS_SUCCESS;
+    for (int rc : rcs) if (rc != PNGLOSS_SUCCESS && (worst == PNGLOSS_SUCCESS || worst == PNGLOSS_INTERNAL_ABORT)) worst = rc;
+    return worst;
+}
+
 int pngloss_hip_optimize_batch_host_emit(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images, size_t n,
                                          unsigned quantization_strength, long bleed_divider, pngloss_hip_result *results,
                                          pngloss_hip_scanlines *scanlines)
@@ -1393,13 +1711,7 @@ int pngloss_hip_compare_batch(pngloss_hip_ctx *ctx, const pngloss_hip_image_pair
 
 double pngloss_hip_psnr_db(const pngloss_hip_distortion *d, unsigned channel_mask)
 {
-    if (!d || !d->pixels || !channel_mask || channel_mask > 0xFu) return std::nan("");
-    uint64_t sum = 0;
-    int channels = 0;
-    for (int c = 0; c < 4; c++)
-        if (channel_mask & (1u << c)) { sum += d->sq_err[c]; channels++; }
-    if (!sum) return (double)INFINITY;
-    return 10.0 * std::log10(255.0 * 255.0 * (double)d->pixels * (double)channels / (double)sum);
+    return d ? pld_psnr_db(d->pixels, d->sq_err, channel_mask) : std::nan("");
 }
 
 int pngloss_hip_png_decode_batch_host(pngloss_hip_ctx *ctx, const pngloss_hip_png_source *src, size_t n)

@@ -174,6 +174,7 @@ ABI_SYMBOLS = (
     "pngloss_hip_multi_create", "pngloss_hip_multi_destroy", "pngloss_hip_multi_count", "pngloss_hip_multi_split",
     "pngloss_hip_multi_optimize_batch_host",
     "pngloss_hip_last_distortion", "pngloss_hip_compare_batch", "pngloss_hip_psnr_db", "pngloss_hip_multi_set_option", "pngloss_hip_multi_last_distortion",
+    "pngloss_hip_optimize_batch_target", "pngloss_hip_multi_optimize_batch_host_target",
 )
 
 
@@ -249,6 +250,7 @@ def hip_lib():
             lib.pngloss_hip_multi_set_option.restype = C.c_int
             lib.pngloss_hip_multi_last_distortion.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(Distortion)]
             lib.pngloss_hip_multi_last_distortion.restype = C.c_int
+            _target_abi(lib)
             _hip = lib
         return _hip
 
@@ -618,3 +620,92 @@ class HipMulti:
         res = (Result * max(n, 1))()
         _check(self._lib.pngloss_hip_multi_optimize_batch_host(self._m, imgs, n, strength, bleed, res, None, None), "multi_optimize_batch_host", partial_ok=True)
         return outs, filts, [dict(status=r.status, bpp=r.bytes_per_pixel, unique_symbols=r.unique_symbols) for r in res[:n]]
+
+
+# ---- a strength per image from a distortion target ----------------------------------------------------------
+
+class Target(C.Structure):
+    """pngloss_hip_target: min_psnr_db (0 = no condition, inf = only lossless results pass), max_abs_error (0 = no condition, 1..255) and
+    max_strength (M, 0..255: the search never goes above it).  include/pngloss_hip.h states the rule."""
+    _fields_ = [("min_psnr_db", C.c_double), ("max_abs_error", C.c_uint32), ("max_strength", C.c_uint32)]
+
+    def __init__(self, min_psnr_db=0.0, max_abs_error=0, max_strength=19):
+        super().__init__(min_psnr_db, max_abs_error, max_strength)
+
+
+class TargetReport(C.Structure):
+    """pngloss_hip_target_report: the chosen strength, the probes of the rule, the row-engine runs spent and the Distortion of the result kept."""
+    _fields_ = [("strength", C.c_uint32), ("probes", C.c_uint32), ("runs", C.c_uint32), ("reserved", C.c_uint32), ("distortion", Distortion)]
+
+    def as_dict(self):
+        return dict(strength=self.strength, probes=self.probes, runs=self.runs, distortion=self.distortion.as_dict())
+
+
+def _target_abi(lib):
+    """the prototypes of the two target entry points (hip_lib sets them once)"""
+    lib.pngloss_hip_optimize_batch_target.argtypes = [C.c_void_p, C.POINTER(ImageDesc), C.c_size_t, C.POINTER(Target), C.c_long, C.c_void_p, C.POINTER(Result),
+                                                      C.POINTER(TargetReport)]
+    lib.pngloss_hip_optimize_batch_target.restype = C.c_int
+    lib.pngloss_hip_multi_optimize_batch_host_target.argtypes = [C.c_void_p, C.POINTER(HostImage), C.c_size_t, C.POINTER(Target), C.c_long, C.POINTER(Result),
+                                                                 C.POINTER(Scanlines), C.POINTER(ZStream), C.POINTER(TargetReport)]
+    lib.pngloss_hip_multi_optimize_batch_host_target.restype = C.c_int
+    return lib
+
+
+def _result_dict(r):
+    return dict(status=r.status, bpp=r.bytes_per_pixel, unique_symbols=r.unique_symbols, retried_rows=r.retried_rows, repaired_pixels=r.repaired_pixels)
+
+
+def _run_target(self, images, target, bleed=2, stream=0):
+    """pngloss_hip_optimize_batch_target: images as for run(); every image ends up as run() at its chosen strength leaves it.  Synchronous.
+    Returns (results, reports): the dicts run() returns and one TargetReport per image."""
+    n = len(images)
+    descs = (ImageDesc * max(n, 1))()
+    for i, (p, f, w, h) in enumerate(images):
+        descs[i] = ImageDesc(p or None, f or None, w, h)
+    res = (Result * max(n, 1))()
+    rep = (TargetReport * max(n, 1))()
+    self._n = 0
+    _check(self._lib.pngloss_hip_optimize_batch_target(self._ctx, descs, n, C.byref(target), bleed, stream or None, res, rep), "optimize_batch_target",
+           partial_ok=True)
+    return [_result_dict(r) for r in res[:n]], [rep[i] for i in range(n)]
+
+
+def _run_host_target(self, arrays, target, bleed=2, want_filters=True, emit=None, stream_only=False):
+    """pngloss_hip_multi_optimize_batch_host_target on a list of (H, W, 4) uint8 arrays.  emit: None, "scanlines" or "zlib".  Returns
+    (outs, filters, results, reports, emitted): emitted is None, or per image what run_host_emit / run_host_zlib return for it."""
+    outs = [np.ascontiguousarray(a).copy() for a in arrays]
+    filts = [np.zeros(a.shape[0], np.uint8) if want_filters else None for a in outs]
+    n = len(outs)
+    imgs = (HostImage * max(n, 1))()
+    for i, (a, f) in enumerate(zip(outs, filts)):
+        imgs[i] = HostImage(a.ctypes.data, f.ctypes.data if f is not None else None, a.shape[1], a.shape[0])
+    lines = zs = None
+    if emit == "scanlines":
+        lines = (Scanlines * max(n, 1))()
+        ids = [np.zeros(a.shape[0], np.uint8) for a in outs]
+        rows = [np.zeros((a.shape[0], a.shape[1] * 4), np.uint8) for a in outs]
+        for i, a in enumerate(outs):
+            lines[i] = Scanlines(ids[i].ctypes.data, rows[i].ctypes.data, a.shape[1] * 4, -1)
+    elif emit == "zlib":
+        zs = (ZStream * max(n, 1))()
+        bufs = [np.zeros(self._lib.pngloss_hip_zlib_bound(a.shape[1], a.shape[0]), np.uint8) for a in outs]
+        for i in range(n):
+            zs[i] = ZStream(bufs[i].ctypes.data, bufs[i].size, 0, -1, (C.c_uint32 * 3)(0, 0, 0), 1 if stream_only else 0)
+    elif emit is not None:
+        raise ValueError("emit: None, 'scanlines' or 'zlib'")
+    res = (Result * max(n, 1))()
+    rep = (TargetReport * max(n, 1))()
+    _check(self._lib.pngloss_hip_multi_optimize_batch_host_target(self._m, imgs, n, C.byref(target), bleed, res, lines, zs, rep),
+           "multi_optimize_batch_host_target", partial_ok=True)
+    emitted = None
+    if emit == "scanlines":
+        chans = {0: 1, 4: 2, 2: 3, 6: 4}
+        emitted = [(lines[i].color_type, ids[i], rows[i][:, : outs[i].shape[1] * chans.get(lines[i].color_type, 4)].copy()) for i in range(n)]
+    elif emit == "zlib":
+        emitted = [(zs[i].color_type, bufs[i][: zs[i].size].tobytes(), tuple(zs[i].blocks)) for i in range(n)]
+    return outs, filts, [dict(status=r.status, bpp=r.bytes_per_pixel, unique_symbols=r.unique_symbols) for r in res[:n]], [rep[i] for i in range(n)], emitted
+
+
+HipContext.run_target = _run_target
+HipMulti.run_host_target = _run_host_target
