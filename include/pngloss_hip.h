@@ -264,6 +264,48 @@ double pngloss_hip_psnr_db(const pngloss_hip_distortion *d, unsigned channel_mas
 int pngloss_hip_multi_set_option(pngloss_hip_multi *multi, const char *name, const char *value);
 int pngloss_hip_multi_last_distortion(pngloss_hip_multi *multi, size_t index, pngloss_hip_distortion *out);
 
+/* ---- Structural similarity (SSIM) per image, measured on the device (no reference equivalent).  PSNR counts every changed sample as loss; the
+ * optimiser's error diffusion deliberately trades a larger per-pixel error for a result whose local mean and structure stay put, which is what
+ * SSIM measures.  With the option "ssim" at "on" (pngloss_hip_set_option; independent of "distortion") every batch that goes through
+ * pngloss_hip_optimize_batch[_async], _batch_host, _host_emit or _host_zlib keeps its originals exactly as for "distortion" -- ONE arena and one copy
+ * kernel, whether one of the two options is on or both -- and one more measuring kernel runs behind the pipeline, on the caller's stream and
+ * inside the window pngloss_hip_last_total_ms reports.  Pixels, filter IDs, scanlines and zlib streams do not depend on the option.
+ *
+ * The record of an RGBA8 pair (a = original, b = result; channel c = 0..3 is byte c of each pixel word: R, G, B, A).  All integers: exact, and
+ * independent of the order of summation.
+ *   Windows: 8 x 8 pixels at a stride of 4 in both directions (the layout x264 and libvpx use): origins (4i, 4j) for every i, j with
+ *     4i + 8 <= width and 4j + 8 <= height; nx = width >= 8 ? (width - 8) / 4 + 1 : 0, ny likewise, windows = nx * ny.  An image narrower or
+ *     lower than 8 pixels has no windows.
+ *   Per window and channel, with the exact sums sa, sb, saa, sbb, sab over its 64 pixels, K1 = 26634 and K2 = 239708 (64^2 (0.01 * 255)^2 and
+ *     64^2 (0.03 * 255)^2, rounded):
+ *         A1 = 2 sa sb + K1                        B1 = sa sa + sb sb + K1
+ *         A2 = 2 (64 sab - sa sb) + K2             B2 = 64 (saa + sbb) - sa sa - sb sb + K2
+ *         q  = sign(A1 A2) * floor(|A1 A2| * 65536 / (B1 B2))
+ *     q lies in [-65536, 65536] and is 65536 exactly when the two windows are equal. */
+typedef struct {
+    uint64_t windows;           /* nx * ny                                                                         */
+    int64_t  sum_q16[4];        /* per channel: sum of q over all windows                                          */
+    int32_t  min_q16[4];        /* per channel: the smallest q -- the worst spot; 65536 when windows == 0          */
+    uint64_t reserved;          /* 0                                                                               */
+} pngloss_hip_ssim;
+
+/* Record of image `index` of the last finished batch.  The rules of pngloss_hip_last_distortion: PNGLOSS_INVALID_ARGUMENT when that batch ran with
+ * the option "ssim" off, when the index is out of range or while a batch is pending; after a host window that ran in chunks the index follows the
+ * chunks.  The record of an image whose status != 0 is unspecified. */
+int pngloss_hip_last_ssim(pngloss_hip_ctx *ctx, size_t index, pngloss_hip_ssim *out);
+int pngloss_hip_multi_last_ssim(pngloss_hip_multi *multi, size_t index, pngloss_hip_ssim *out);
+
+/* The same measurement on its own, as pngloss_hip_compare_batch: n pairs of device-resident RGBA8 images (any alignment of 4), one launch of the
+ * same kernel, out[i] = record of pair i.  Synchronous.  A pair without windows gives { 0, { 0, 0, 0, 0 }, { 65536, 65536, 65536, 65536 }, 0 }.
+ * Independent of the options; not while a batch is in flight on the context (PNGLOSS_INVALID_ARGUMENT). */
+int pngloss_hip_compare_batch_ssim(pngloss_hip_ctx *ctx, const pngloss_hip_image_pair *pairs, size_t n, pngloss_hip_ssim *out, void *stream);
+
+/* Mean SSIM over the channels of `channel_mask` (bit c = channel c), 1.0 for equal images:
+ *     (double)(sum over the mask's channels of sum_q16[c]) / (65536.0 * windows * popcount(mask))
+ * NaN for a NULL record, for windows == 0, for mask 0 and for a mask above 0xF.  Host arithmetic only: needs no device.  The masks are those of
+ * pngloss_hip_psnr_db (0x2, 0xA, 0x7, 0xF for bytes_per_pixel 1, 2, 3, 4). */
+double pngloss_hip_ssim_mean(const pngloss_hip_ssim *r, unsigned channel_mask);
+
 /* ---- A strength per image, found from a distortion target (no reference equivalent: the reference tool takes -s and nothing else).  A strength
  * says nothing about how the result will look, and the right one differs from image to image; the optimiser works in place, so a caller who
  * wanted "at least 38 dB" had to reload the original for every try.  Here the original stays on the device between the probes.
@@ -321,6 +363,32 @@ int pngloss_hip_multi_optimize_batch_host_target(pngloss_hip_multi *multi, const
                                                  const pngloss_hip_target *target, long bleed_divider, pngloss_hip_result *results,
                                                  pngloss_hip_scanlines *scanlines, pngloss_hip_zstream *streams,
                                                  pngloss_hip_target_report *reports);
+
+/* ---- The same search with an SSIM condition.  pngloss_hip_target has no room left, so the target grows into a second struct; the two entry points
+ * above forward here with min_ssim = 0 and behave byte for byte as before (the SSIM kernel is not launched for them).
+ * A probe is ACCEPTED when the three conditions above hold and
+ *     min_ssim == 0, or the probe's pngloss_hip_ssim has no windows, or pngloss_hip_ssim_mean(&ssim, mask) >= min_ssim
+ * with the same mask.  An image too small for one 8 x 8 window cannot be measured, so the SSIM condition does not apply to it (the others do).
+ * SSIM is no more monotone in the strength than PSNR is: the result is defined by the procedure above, which is unchanged.  With min_ssim != 0
+ * every round has one more batched launch: the SSIM kernel on the probed images against the search's own originals. */
+typedef struct {
+    double   min_psnr_db;    /* as in pngloss_hip_target */
+    uint32_t max_abs_error;  /* as in pngloss_hip_target */
+    uint32_t max_strength;   /* as in pngloss_hip_target */
+    double   min_ssim;       /* 0 = no SSIM condition; 0 < min_ssim <= 1: the smallest allowed mean SSIM over the stored channels; NaN, < 0 or > 1:
+                                PNGLOSS_INVALID_ARGUMENT */
+} pngloss_hip_target2;
+
+/* pngloss_hip_optimize_batch_target / pngloss_hip_multi_optimize_batch_host_target with a pngloss_hip_target2 and one more argument: ssim, n records
+ * of the results that were kept, indexed like images[]; may be NULL; filled only when min_ssim != 0.  After the calls pngloss_hip_last_ssim and
+ * pngloss_hip_multi_last_ssim return PNGLOSS_INVALID_ARGUMENT, like their distortion counterparts; the option "ssim" is left as the caller set it. */
+int pngloss_hip_optimize_batch_target2(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n,
+                                       const pngloss_hip_target2 *target, long bleed_divider, void *stream,
+                                       pngloss_hip_result *results, pngloss_hip_target_report *reports, pngloss_hip_ssim *ssim);
+int pngloss_hip_multi_optimize_batch_host_target2(pngloss_hip_multi *multi, const pngloss_hip_host_image *images, size_t n,
+                                                  const pngloss_hip_target2 *target, long bleed_divider, pngloss_hip_result *results,
+                                                  pngloss_hip_scanlines *scanlines, pngloss_hip_zstream *streams,
+                                                  pngloss_hip_target_report *reports, pngloss_hip_ssim *ssim);
 
 /* ---- PNG read side behind the inflate.  Replaces what libpng does for rwpng_read_image24_libpng
  * (/root/reference/src/rwpng.c:179-400) between "inflated IDAT bytes" and "RGBA8 rows": the inverse scanline filters (a recurrence over
@@ -428,6 +496,8 @@ int pngloss_hip_last_engine_info(pngloss_hip_ctx *ctx, size_t index, int32_t inf
  *   any context of the process has used such a wait.
  * Name "distortion", value "on" | "off" (default): measure every batch from here on (pngloss_hip_last_distortion, above).  "off" launches exactly what
  *   the library launched before the option existed: no copy, no arena, no extra kernel.
+ * Name "ssim", value "on" | "off" (default): measure the structural similarity of every batch from here on (pngloss_hip_last_ssim, above); independent of
+ *   "distortion".  "off" launches exactly what the library launched before the option existed.
  * Returns PNGLOSS_SUCCESS or PNGLOSS_INVALID_ARGUMENT (unknown name or value).
  * Results never depend on an option, on the engine, or on the environment: the remaining environment hooks (PNGLOSS_HIP_SEG_GROUPS, _SEG_UNIT, _ENUM_NT,
  * _NO_STREAM_WAIT, _SEGPROF, _DEBUG ...: timing and test pins) are read once, when a context is created, and none of them changes a byte; the debugging aid

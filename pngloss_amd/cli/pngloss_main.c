@@ -47,6 +47,9 @@ struct options {
     bool have_target;          /* --target-psnr / --max-error: the strength is found per file, -s is its upper bound */
     double target_psnr;        /* 0: no PSNR condition */
     unsigned long max_error;   /* 0: no condition */
+    bool ssim;                 /* --ssim: one more line per written file: mean and worst-window SSIM against the input's pixels (measured on the device) */
+    bool have_target_ssim;     /* --target-ssim: a condition of the strength search, like --target-psnr */
+    double target_ssim;        /* 0: no SSIM condition */
     bool gpu_read;             /* --gpu-read: inverse filters + expansion to RGBA8 on the device (inflate stays zlib on the decode threads) */
 };
 
@@ -74,6 +77,11 @@ static const char usage_text[] =
     "                    result with at least DB decibels of PSNR over the stored channels\n"
     "  --max-error N     the same with a bound on the largest channel error, 1 to 255; both may\n"
     "                    be given (searched on the GPU; -v prints the strength chosen)\n"
+    "  --ssim            report each written file's structural similarity to its input: mean and worst\n"
+    "                    8x8 window over the stored channels, 1 = identical (measured on the GPU; in a\n"
+    "                    strength search only together with --target-ssim)\n"
+    "  --target-ssim X   the strength search with a smallest mean SSIM, above 0 and at most 1; combines\n"
+    "                    with --target-psnr and --max-error: every condition given must hold\n"
     "\n"
     "Lossily compresses PNGs by using more compressible colors that are close enough to the\n"
     "original values; the filter+quantise pass runs on the GPU (all files of a call as one batch).\n"
@@ -82,7 +90,7 @@ static const char usage_text[] =
 
 /* ------------------------------------------------------------------------------------------- options */
 
-enum { OPT_EXT = 256, OPT_NO_FORCE, OPT_SKIP_LARGER, OPT_STRIP, OPT_GPU_DEFLATE, OPT_GPU_READ, OPT_DISTORTION, OPT_TARGET_PSNR, OPT_MAX_ERROR };
+enum { OPT_EXT = 256, OPT_NO_FORCE, OPT_SKIP_LARGER, OPT_STRIP, OPT_GPU_DEFLATE, OPT_GPU_READ, OPT_DISTORTION, OPT_TARGET_PSNR, OPT_MAX_ERROR, OPT_SSIM, OPT_TARGET_SSIM };
 
 static bool parse_number(const char *text, unsigned long *out)
 {
@@ -116,6 +124,8 @@ static pngloss_error parse_options(int argc, char **argv, struct options *o)
         { "distortion", no_argument, NULL, OPT_DISTORTION },
         { "target-psnr", required_argument, NULL, OPT_TARGET_PSNR },
         { "max-error", required_argument, NULL, OPT_MAX_ERROR },
+        { "ssim", no_argument, NULL, OPT_SSIM },
+        { "target-ssim", required_argument, NULL, OPT_TARGET_SSIM },
         { NULL, 0, NULL, 0 },
     };
     for (int c; (c = getopt_long(argc, argv, "vqfo:Vhs:b:", table, NULL)) != -1;) {
@@ -138,6 +148,12 @@ static pngloss_error parse_options(int argc, char **argv, struct options *o)
             if (!parse_number(optarg, &o->max_error)) { fputs("--max-error requires a numeric argument\n", stderr); return INVALID_ARGUMENT; }
             o->have_target = true;
             o->have_max_error = true;
+            break;
+        case OPT_SSIM: o->ssim = true; break;
+        case OPT_TARGET_SSIM:
+            if (!parse_decibels(optarg, &o->target_ssim)) { fputs("--target-ssim requires a numeric argument\n", stderr); return INVALID_ARGUMENT; }
+            o->have_target = true;
+            o->have_target_ssim = true;
             break;
         case 'h': o->help = true; break;
         case 'V': o->version = true; break;
@@ -194,6 +210,8 @@ struct job {
     pngloss_hip_target_report target;    /* --target-psnr / --max-error: the strength the search chose for this file */
     pngloss_hip_distortion distortion;   /* --distortion: the optimised pixels against the decoded input's (have_distortion: the library had a record) */
     bool have_distortion;
+    pngloss_hip_ssim ssim;               /* --ssim: the same pair's structural similarity (have_ssim: the library had a record) */
+    bool have_ssim;
     png_stream_source src;    /* --gpu-read: inflated scanlines waiting for the device (src.scanlines != NULL) */
 };
 
@@ -376,6 +394,20 @@ static void say_distortion(struct job *j)
         (unsigned long long)d->changed_pixels, (unsigned long long)d->pixels, largest);
 }
 
+/* --ssim: the line of a written file.  Mean and worst window over the channels the file stores, as for the PSNR */
+static void say_ssim(struct job *j, const struct options *o)
+{
+    const pngloss_hip_ssim *r = &j->ssim;
+    if (!j->have_ssim) { if (o->have_target) say(j, "  ssim: not measured (a strength search measures it only with --target-ssim)\n"); return; }
+    if (!r->windows) { say(j, "  ssim: not measured (smaller than one 8x8 window)\n"); return; }
+    const unsigned bpp = j->gpu.bytes_per_pixel;
+    const unsigned mask = bpp == 1 ? 0x2u : bpp == 2 ? 0xAu : bpp == 3 ? 0x7u : 0xFu;
+    int32_t worst = 65536;
+    for (int c = 0; c < 4; c++)
+        if ((mask >> c & 1u) && r->min_q16[c] < worst) worst = r->min_q16[c];
+    say(j, "  ssim: mean %.4f, worst window %.4f, %llu windows\n", pngloss_hip_ssim_mean(r, mask), (double)worst / 65536.0, (unsigned long long)r->windows);
+}
+
 static void encode_job(struct job *j, const struct options *o)
 {
     if (j->status != SUCCESS) return;
@@ -386,6 +418,7 @@ static void encode_job(struct job *j, const struct options *o)
     j->in.chunks = NULL;
     pngloss_error rc = encode_to(j, &j->out, j->filters, o);
     if (o->distortion && rc == SUCCESS && j->have_distortion) say_distortion(j);
+    if (o->ssim && rc == SUCCESS) say_ssim(j, o);
     if (o->verbose) {
         if (rc == SUCCESS) {
             say(j, "  wrote %luKB file (%.1f%% of original)\n", (unsigned long)((j->out.file_size + 500UL) / 1000UL),
@@ -543,8 +576,9 @@ static pngloss_error run_window(struct job *jobs, size_t n, const struct options
     pngloss_hip_zstream *zs = calloc(n ? n : 1, sizeof *zs);
     pngloss_hip_result *res = calloc(n ? n : 1, sizeof *res);
     pngloss_hip_target_report *rep = calloc(n ? n : 1, sizeof *rep);
+    pngloss_hip_ssim *sm = calloc(n ? n : 1, sizeof *sm);
     size_t *who = calloc(n ? n : 1, sizeof *who), m = 0;
-    if (!imgs || !lines || !zs || !res || !who || !rep) { free(imgs); free(lines); free(zs); free(res); free(who); free(rep); return OUT_OF_MEMORY_ERROR; }
+    if (!imgs || !lines || !zs || !res || !who || !rep || !sm) { free(imgs); free(lines); free(zs); free(res); free(who); free(rep); free(sm); return OUT_OF_MEMORY_ERROR; }
     for (size_t i = 0; i < n; i++)
         if (jobs[i].status == SUCCESS) {
             imgs[m] = (pngloss_hip_host_image){ jobs[i].out.rgba_data, jobs[i].filters, jobs[i].out.width, jobs[i].out.height };
@@ -581,11 +615,17 @@ static pngloss_error run_window(struct job *jobs, size_t n, const struct options
             }
             if (*ctx && o->distortion && pngloss_hip_multi_set_option(*ctx, "distortion", "on") != PNGLOSS_SUCCESS)
                 fputs("  warning: the library refused the option \"distortion\"; no distortion lines\n", stderr);
+            if (*ctx && o->ssim && pngloss_hip_multi_set_option(*ctx, "ssim", "on") != PNGLOSS_SUCCESS)
+                fputs("  warning: the library refused the option \"ssim\"; no ssim lines\n", stderr);
         }
         if (timing) fprintf(stderr, "  [timing] GPU contexts ready after %.3f s\n", now_s() - tc0);
         /* --target-psnr / --max-error: the library searches a strength per file, -s bounds it; the records come back in the reports */
+        /* (--target-ssim: one more condition, and the SSIM records of what was written come back in sm) */
         const pngloss_hip_target target = { o->target_psnr, (uint32_t)o->max_error, (uint32_t)o->strength };
+        const pngloss_hip_target2 target2 = { o->target_psnr, (uint32_t)o->max_error, (uint32_t)o->strength, o->target_ssim };
         int rc = !*ctx ? PNGLOSS_HIP_ERROR
+               : o->have_target_ssim ? pngloss_hip_multi_optimize_batch_host_target2(*ctx, imgs, m, &target2, (long)o->bleed, res, o->gpu_deflate ? NULL : lines,
+                                                                                     o->gpu_deflate ? zs : NULL, rep, sm)
                : o->have_target ? pngloss_hip_multi_optimize_batch_host_target(*ctx, imgs, m, &target, (long)o->bleed, res, o->gpu_deflate ? NULL : lines,
                                                                                o->gpu_deflate ? zs : NULL, rep)
                : pngloss_hip_multi_optimize_batch_host(*ctx, imgs, m, (unsigned)o->strength, (long)o->bleed, res,
@@ -598,8 +638,12 @@ static pngloss_error run_window(struct job *jobs, size_t n, const struct options
                 jobs[who[k]].target = rep[k];
                 jobs[who[k]].distortion = rep[k].distortion;
                 jobs[who[k]].have_distortion = o->distortion && (rc == PNGLOSS_SUCCESS || rc == PNGLOSS_INTERNAL_ABORT);
-            } else
+                jobs[who[k]].ssim = sm[k];
+                jobs[who[k]].have_ssim = o->ssim && o->have_target_ssim && (rc == PNGLOSS_SUCCESS || rc == PNGLOSS_INTERNAL_ABORT);
+            } else {
             jobs[who[k]].have_distortion = o->distortion && *ctx && pngloss_hip_multi_last_distortion(*ctx, k, &jobs[who[k]].distortion) == PNGLOSS_SUCCESS;
+            jobs[who[k]].have_ssim = o->ssim && *ctx && pngloss_hip_multi_last_ssim(*ctx, k, &jobs[who[k]].ssim) == PNGLOSS_SUCCESS;
+            }
             if (rc != PNGLOSS_SUCCESS && !(rc == PNGLOSS_INTERNAL_ABORT && res[k].status == 0)) {
                 /* (a batch in which single images failed reports PNGLOSS_INTERNAL_ABORT and leaves the others done.)
                  * Unlike the reference (pngloss.c:266 ignores the return value) a failed optimisation is an error:
@@ -609,7 +653,7 @@ static pngloss_error run_window(struct job *jobs, size_t n, const struct options
             }
         }
     }
-    free(imgs); free(lines); free(zs); free(res); free(who); free(rep);
+    free(imgs); free(lines); free(zs); free(res); free(who); free(rep); free(sm);
     const double t2 = now_s();
 
     for_each_job(jobs, n, o, encode_job);
@@ -630,6 +674,7 @@ int main(int argc, char **argv)
     if (o.help) { print_version_banner(stdout); fputs(usage_text, stdout); return SUCCESS; }
     if (o.strength > 255) { fputs("Must specify a strength in the range 0-255.\n", stderr); return INVALID_ARGUMENT; }
     if (o.have_target && !(o.target_psnr >= 0.0)) { fputs("Must specify a PSNR target of 0 dB or more.\n", stderr); return INVALID_ARGUMENT; }
+    if (o.have_target_ssim && !(o.target_ssim > 0.0 && o.target_ssim <= 1.0)) { fputs("Must specify an SSIM target above 0 and at most 1.\n", stderr); return INVALID_ARGUMENT; }
     if (o.have_max_error && (o.max_error < 1 || o.max_error > 255)) { fputs("Must specify a largest channel error in the range 1-255.\n", stderr); return INVALID_ARGUMENT; }
     if (o.bleed < 1 || o.bleed > 32767) { fputs("Must specify a bleed divider in the range 1-32767.\n", stderr); return INVALID_ARGUMENT; }
     if (o.extension && o.output_path) { fputs("--ext and --output options can't be used at the same time\n", stderr); return INVALID_ARGUMENT; }

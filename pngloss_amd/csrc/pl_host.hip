@@ -11,6 +11,7 @@
 #include "pl_pngread.h"
 #include "pl_inflate.h"
 #include "pl_distort.h"
+#include "pl_ssim.h"
 #include "pl_target.h"
 #include "pl_target_dev.h"
 #define SEG_PLAIN_POINTERS   /* host plumbing only: SegJob is filled here, never dereferenced */
@@ -131,6 +132,16 @@ struct pngloss_hip_ctx {
     const PlDistortRecord *d_records = nullptr;      /* the batch in flight is measured: its records, copied back by finish */
     std::vector<pngloss_hip_distortion> distortion;  /* per image of the last finished batch; empty when it ran with the option off */
 
+    /* option "ssim": the originals are the keep arena's (one arena, one pl_keep launch for both options); the SSIM kernel's job table and records
+     * live in a small buffer of their own (pl_layout.h: pl_ssim_layout), regrown on demand like the others */
+    bool opt_ssim = false;           /* pngloss_hip_set_option("ssim", "on" | "off") */
+    char *d_ssim = nullptr;
+    size_t ssim_bytes = 0;
+    std::vector<PlSsimJob> h_ssj;    /* (stay alive until the asynchronous copies that read them are done: the next enqueue) */
+    std::vector<PlSsimRecord> h_ssr;
+    const PlSsimRecord *d_ssim_records = nullptr;    /* the batch in flight is measured: its records, copied back by finish */
+    std::vector<pngloss_hip_ssim> ssim;              /* per image of the last finished batch; empty when it ran with the option off */
+
     /* pngloss_hip_optimize_batch_target: the search arena (pl_target.h: tables, originals, best results so far), regrown on demand like the others */
     char *d_target = nullptr;
     size_t target_bytes = 0;
@@ -149,6 +160,9 @@ static_assert(PLL_FLAG_GRAY == PL_FLAG_GRAY && PLL_FLAG_OPAQUE == PL_FLAG_OPAQUE
 static_assert(sizeof(pngloss_hip_distortion) == sizeof(PlDistortRecord) && offsetof(pngloss_hip_distortion, pixels) == offsetof(PlDistortRecord, pixels) &&
               offsetof(pngloss_hip_distortion, changed_pixels) == offsetof(PlDistortRecord, changed_pixels) && offsetof(pngloss_hip_distortion, sq_err) == offsetof(PlDistortRecord, sq_err) &&
               offsetof(pngloss_hip_distortion, max_abs) == offsetof(PlDistortRecord, max_abs), "pngloss_hip_distortion and PlDistortRecord");
+static_assert(sizeof(pngloss_hip_ssim) == sizeof(PlSsimRecord) && offsetof(pngloss_hip_ssim, windows) == offsetof(PlSsimRecord, windows) &&
+              offsetof(pngloss_hip_ssim, sum_q16) == offsetof(PlSsimRecord, sum_q16) && offsetof(pngloss_hip_ssim, min_q16) == offsetof(PlSsimRecord, min_q16) &&
+              offsetof(pngloss_hip_ssim, reserved) == offsetof(PlSsimRecord, reserved), "pngloss_hip_ssim and PlSsimRecord");
 
 float recip_up_host(long d)
 {
@@ -188,6 +202,35 @@ int upload_distort_jobs(pngloss_hip_ctx *ctx, const PlKeepLayout &lay, size_t n,
     }
     PL_CHECK(hipMemcpyAsync(ctx->d_keep + lay.jobs, ctx->h_dj.data(), sizeof(PlDistortJob) * n, hipMemcpyHostToDevice, stream));
     PL_CHECK(hipMemsetAsync(d_rec, 0, sizeof(PlDistortRecord) * n, stream));
+    return PNGLOSS_SUCCESS;
+}
+
+/* One table of SSIM jobs and their records, as pl_ssim wants them before its launch: pair i is the width[i] x height[i] image b[i] against the
+ * original a[i]; jobs[i].record = d_records + i, records[i] = the record with no window added yet.  Returns the largest tile count (sizes the grid). */
+uint64_t fill_ssim_jobs(PlSsimJob *jobs, PlSsimRecord *records, PlSsimRecord *d_records, size_t n, const void *const *a, const void *const *b,
+                        const uint32_t *width, const uint32_t *height)
+{
+    uint64_t max_tiles = 0;
+    for (size_t i = 0; i < n; i++) {
+        jobs[i] = PlSsimJob{ static_cast<const uint32_t *>(a[i]), static_cast<const uint32_t *>(b[i]), width[i], height[i], d_records + i };
+        records[i] = pls_record_begin(width[i], height[i]);
+        max_tiles = std::max(max_tiles, pls_geom(width[i], height[i]).tiles);
+    }
+    return max_tiles;
+}
+
+/* The same into the context's SSIM buffer (grown here: call it before anything of the batch is enqueued), uploaded on `stream` */
+int upload_ssim_jobs(pngloss_hip_ctx *ctx, size_t n, const void *const *a, const void *const *b, const uint32_t *width, const uint32_t *height,
+                     hipStream_t stream, PlSsimLayout &lay, uint64_t &max_tiles)
+{
+    lay = pl_ssim_layout(n, sizeof(PlSsimJob), sizeof(PlSsimRecord));
+    const int rc = grow(ctx->d_ssim, ctx->ssim_bytes, lay.total, 8);
+    if (rc) return rc;
+    ctx->h_ssj.assign(n, PlSsimJob{});
+    ctx->h_ssr.assign(n, PlSsimRecord{});
+    max_tiles = fill_ssim_jobs(ctx->h_ssj.data(), ctx->h_ssr.data(), reinterpret_cast<PlSsimRecord *>(ctx->d_ssim + lay.records), n, a, b, width, height);
+    PL_CHECK(hipMemcpyAsync(ctx->d_ssim + lay.jobs, ctx->h_ssj.data(), sizeof(PlSsimJob) * n, hipMemcpyHostToDevice, stream));
+    PL_CHECK(hipMemcpyAsync(ctx->d_ssim + lay.records, ctx->h_ssr.data(), sizeof(PlSsimRecord) * n, hipMemcpyHostToDevice, stream));
     return PNGLOSS_SUCCESS;
 }
 
@@ -499,7 +542,10 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
     ctx->split_last = false;                                         /* (only a split host window sets it again: batch_host) */
     ctx->distortion.clear();
     ctx->d_records = nullptr;
-    const bool distort = ctx->opt_distortion;
+    ctx->ssim.clear();
+    ctx->d_ssim_records = nullptr;
+    const bool distort = ctx->opt_distortion, ssim = ctx->opt_ssim;
+    const bool keep_originals = distort || ssim;     /* one arena, one pl_keep launch, whichever of the two options wants the originals */
     const PlHooks &hk = ctx->hooks;
     PlPlanInput in;
     in.strength = strength; in.bleed = bleed; in.hooks = hk;
@@ -547,9 +593,9 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
                                               sizeof(PlJob), sizeof(SegJob));
     int rc = ensure_ws(ctx, lay.total);
     if (rc) return rc;
-    /* option "distortion": room for every original beside the workspace -- or the call fails here, with nothing enqueued */
+    /* options "distortion" and "ssim": room for every original beside the workspace -- or the call fails here, with nothing enqueued */
     PlKeepLayout keep;
-    if (distort) {
+    if (keep_originals) {
         keep = pl_keep_layout(in.width, in.height, true, sizeof(PlDistortJob), sizeof(PlDistortRecord));
         rc = grow(ctx->d_keep, ctx->keep_bytes, keep.total, 8);
         if (rc) return rc;
@@ -600,9 +646,10 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
     prm.force_careful = hk.force_careful;   /* test hook, see pl_device.h */
     prm.engine_mode = plan.engine_mode;
 
-    const PlDistortJob *const d_dj = distort ? reinterpret_cast<const PlDistortJob *>(ctx->d_keep + keep.jobs) : nullptr;
-    uint64_t max_pixels = 0;
-    if (distort) {
+    const PlDistortJob *const d_dj = keep_originals ? reinterpret_cast<const PlDistortJob *>(ctx->d_keep + keep.jobs) : nullptr;
+    uint64_t max_pixels = 0, max_tiles = 0;
+    PlSsimLayout ssim_lay;
+    if (keep_originals) {
         std::vector<const void *> img(n);
         std::vector<uint64_t> pixels(n);
         for (size_t i = 0; i < n; i++) {
@@ -612,9 +659,15 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
         }
         rc = upload_distort_jobs(ctx, keep, n, img.data(), nullptr, pixels.data(), stream);
         if (rc) return rc;
+        if (ssim) {
+            std::vector<const void *> orig(n);
+            for (size_t i = 0; i < n; i++) orig[i] = ctx->d_keep + keep.image[i];
+            rc = upload_ssim_jobs(ctx, n, orig.data(), img.data(), in.width.data(), in.height.data(), stream, ssim_lay, max_tiles);
+            if (rc) return rc;
+        }
     }
     PL_CHECK(hipEventRecord(ctx->ev[0], stream));
-    if (distort) PL_CHECK(pl_launch_keep(d_dj, n, max_pixels, stream));      /* the originals, before pl_classify / pl_repack rewrite the images in place */
+    if (keep_originals) PL_CHECK(pl_launch_keep(d_dj, n, max_pixels, stream));      /* the originals, before pl_classify / pl_repack rewrite the images in place */
     PL_CHECK(pl_launch_prepare(d_jobs, ctx->h_jobs.data(), n, stream, !use_rows));
     ctx->engine.assign(n, (uint8_t)(use_rows ? PLR_ENGINE_ROWS : PLR_ENGINE_WG));
     for (uint32_t i : plan.seg_list) ctx->engine[i] = (uint8_t)PLR_ENGINE_SEG;
@@ -637,6 +690,7 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
         /* (behind this point the segment engine's launch thread may be running: it is joined before an error is returned) */
         hipError_t e = pl_launch_finish(d_jobs, ctx->h_jobs.data(), n, stream);
         if (e == hipSuccess && distort) e = pl_launch_distort(d_dj, n, max_pixels, stream);      /* behind pl_unpack: the final RGBA8 against the kept original */
+        if (e == hipSuccess && ssim) e = pl_launch_ssim(reinterpret_cast<const PlSsimJob *>(ctx->d_ssim + ssim_lay.jobs), n, max_tiles, stream);
         if (e == hipSuccess) e = pl_launch_emit(d_jobs, ctx->h_jobs.data(), n, stream);
         if (e == hipSuccess) e = hipEventRecord(ctx->ev[3], stream);
         if (e != hipSuccess) {
@@ -649,6 +703,7 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
     ctx->n_last = n;
     ctx->last_stream = stream;
     if (distort) ctx->d_records = reinterpret_cast<const PlDistortRecord *>(ctx->d_keep + keep.records);
+    if (ssim) ctx->d_ssim_records = reinterpret_cast<const PlSsimRecord *>(ctx->d_ssim + ssim_lay.records);
     ctx->pending = true;
     return PNGLOSS_SUCCESS;
 }
@@ -751,6 +806,11 @@ int finish(pngloss_hip_ctx *ctx, pngloss_hip_result *results, size_t n)
         std::vector<pngloss_hip_distortion> got(ctx->n_last);
         PL_CHECK(hipMemcpy(got.data(), ctx->d_records, sizeof(pngloss_hip_distortion) * ctx->n_last, hipMemcpyDeviceToHost));
         ctx->distortion.swap(got);
+    }
+    if (ctx->d_ssim_records) {
+        std::vector<pngloss_hip_ssim> got(ctx->n_last);
+        PL_CHECK(hipMemcpy(got.data(), ctx->d_ssim_records, sizeof(pngloss_hip_ssim) * ctx->n_last, hipMemcpyDeviceToHost));
+        ctx->ssim.swap(got);
     }
     int worst = PNGLOSS_SUCCESS;
     for (size_t i = 0; i < ctx->n_last; i++) {
@@ -1040,6 +1100,7 @@ void pngloss_hip_destroy(pngloss_hip_ctx *ctx)
     if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
     if (ctx->d_frames) (void)hipFree(ctx->d_frames);
     if (ctx->d_keep) (void)hipFree(ctx->d_keep);
+    if (ctx->d_ssim) (void)hipFree(ctx->d_ssim);
     if (ctx->d_target) (void)hipFree(ctx->d_target);
     if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
     if (ctx->h_progress) (void)hipHostFree(ctx->h_progress);
@@ -1149,7 +1210,7 @@ static int batch_host(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images
     }
     K = std::min(K, ctx->peers.size() + 1);
     if (K <= 1) return batch_host_one(ctx, images, n, quantization_strength, bleed_divider, results, lines, zs);
-    for (pngloss_hip_ctx *p : ctx->peers) p->opt_distortion = ctx->opt_distortion;       /* the other chunks measure what this one measures */
+    for (pngloss_hip_ctx *p : ctx->peers) { p->opt_distortion = ctx->opt_distortion; p->opt_ssim = ctx->opt_ssim; }       /* the other chunks measure what this one measures */
     std::vector<uint64_t> pixels(n);
     for (size_t i = 0; i < n; i++) pixels[i] = (uint64_t)images[i].width * images[i].height;
     const std::vector<size_t> first = pl_host_window_cut(pixels, K);
@@ -1310,6 +1371,7 @@ struct TargetImage {
     PlTargetSearch search;
     pngloss_hip_result last{}, kept{};                 /* of the probe just run / of the result the image ends with */
     pngloss_hip_distortion last_rec{}, kept_rec{};
+    pngloss_hip_ssim last_ssim{}, kept_ssim{};         /* (only with an SSIM condition) */
     long best = -1;                                    /* the strength whose (accepted) result the arena's stash holds; -1: none */
     long in_place = -1;                                /* the strength whose result the image itself holds; -1: the original */
     uint32_t runs = 0;
@@ -1318,19 +1380,26 @@ struct TargetImage {
 
 /* images: device-resident; the arena (ctx->d_target) has been grown to lay.total.  commit: at the end every image holds the result of its chosen
  * strength (else the images are left as the last probes left them: the host form runs the chosen strengths through the host-window path). */
-static int target_search(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n, const PlTargetLayout &lay, const pngloss_hip_target &t,
-                         long bleed, hipStream_t stream, bool commit, pngloss_hip_result *results, pngloss_hip_target_report *reports)
+static int target_search(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n, const PlTargetLayout &lay, const pngloss_hip_target2 &t,
+                         long bleed, hipStream_t stream, bool commit, pngloss_hip_result *results, pngloss_hip_target_report *reports, pngloss_hip_ssim *ssim_out)
 {
+    const bool want_ssim = t.min_ssim != 0.0;          /* without the condition the SSIM kernel is never launched */
     /* whatever happens: the caller's option back, and no "last batch" to index */
     struct Guard {
-        pngloss_hip_ctx *c; bool opt;
-        ~Guard() { c->opt_distortion = opt; c->n_last = 0; c->h_jobs.clear(); c->distortion.clear(); c->d_records = nullptr; c->split_last = false; }
-    } guard{ ctx, ctx->opt_distortion };
-    ctx->opt_distortion = false;                       /* the search measures against its own originals (the keep arena is laid out afresh by every enqueue) */
+        pngloss_hip_ctx *c; bool opt, opt_ssim;
+        ~Guard()
+        {
+            c->opt_distortion = opt; c->opt_ssim = opt_ssim; c->n_last = 0; c->h_jobs.clear(); c->distortion.clear(); c->d_records = nullptr;
+            c->ssim.clear(); c->d_ssim_records = nullptr; c->split_last = false;
+        }
+    } guard{ ctx, ctx->opt_distortion, ctx->opt_ssim };
+    ctx->opt_distortion = ctx->opt_ssim = false;       /* the search measures against its own originals (the keep arena is laid out afresh by every enqueue) */
     char *const arena = ctx->d_target;
     PlMoveJob *const d_moves = reinterpret_cast<PlMoveJob *>(arena + lay.moves);
     PlDistortJob *const d_dj = reinterpret_cast<PlDistortJob *>(arena + lay.jobs);
     PlDistortRecord *const d_rec = reinterpret_cast<PlDistortRecord *>(arena + lay.records);
+    PlSsimJob *const d_sj = reinterpret_cast<PlSsimJob *>(arena + lay.ssim_jobs);
+    PlSsimRecord *const d_srec = reinterpret_cast<PlSsimRecord *>(arena + lay.ssim_records);
     std::vector<TargetImage> st(n);
     std::vector<PlTargetSearch> searches(n);
     for (size_t i = 0; i < n; i++) st[i].search = pl_target_begin(t.max_strength);
@@ -1340,6 +1409,8 @@ static int target_search(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *ima
     /* (the host tables stay alive until the call's last synchronisation: asynchronous copies read them) */
     std::vector<std::vector<PlMoveJob>> move_tables;
     std::vector<std::vector<PlDistortJob>> distort_tables;
+    std::vector<std::vector<PlSsimJob>> ssim_tables;
+    std::vector<std::vector<PlSsimRecord>> ssim_begins;
     /* one launch of pl_move for a table of jobs */
     auto move = [&](std::vector<PlMoveJob> jobs) -> int {
         if (jobs.empty()) return PNGLOSS_SUCCESS;
@@ -1367,7 +1438,7 @@ static int target_search(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *ima
         }
         return PNGLOSS_SUCCESS;
     };
-    /* one launch of pl_distort: the images `who` against the search's own originals */
+    /* one launch of pl_distort -- and, with an SSIM condition, one of pl_ssim --: the images `who` against the search's own originals */
     auto measure = [&](const std::vector<uint32_t> &who) -> int {
         if (who.empty()) return PNGLOSS_SUCCESS;
         distort_tables.emplace_back(who.size());
@@ -1386,8 +1457,29 @@ static int target_search(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *ima
         PL_CHECK(hipMemsetAsync(d_rec, 0, sizeof(PlDistortRecord) * dj.size(), stream));
         PL_CHECK(pl_launch_distort(d_dj, dj.size(), max_pixels, stream));
         PL_CHECK(hipMemcpyAsync(got.data(), d_rec, sizeof(PlDistortRecord) * dj.size(), hipMemcpyDeviceToHost, stream));
+        std::vector<pngloss_hip_ssim> sgot(want_ssim ? who.size() : 0);
+        if (want_ssim) {
+            ssim_tables.emplace_back(who.size());
+            ssim_begins.emplace_back(who.size());
+            std::vector<PlSsimJob> &sj = ssim_tables.back();
+            std::vector<const void *> a(who.size()), b(who.size());
+            std::vector<uint32_t> w(who.size()), h(who.size());
+            for (size_t k = 0; k < who.size(); k++) {
+                const size_t i = who[k];
+                a[k] = arena + lay.image[i].orig; b[k] = images[i].d_rgba;
+                w[k] = images[i].width; h[k] = images[i].height;
+            }
+            const uint64_t max_tiles = fill_ssim_jobs(sj.data(), ssim_begins.back().data(), d_srec, who.size(), a.data(), b.data(), w.data(), h.data());
+            PL_CHECK(hipMemcpyAsync(d_sj, sj.data(), sizeof(PlSsimJob) * sj.size(), hipMemcpyHostToDevice, stream));
+            PL_CHECK(hipMemcpyAsync(d_srec, ssim_begins.back().data(), sizeof(PlSsimRecord) * sj.size(), hipMemcpyHostToDevice, stream));
+            PL_CHECK(pl_launch_ssim(d_sj, sj.size(), max_tiles, stream));
+            PL_CHECK(hipMemcpyAsync(sgot.data(), d_srec, sizeof(PlSsimRecord) * sj.size(), hipMemcpyDeviceToHost, stream));
+        }
         PL_CHECK(hipStreamSynchronize(stream));
-        for (size_t k = 0; k < who.size(); k++) st[who[k]].last_rec = got[k];
+        for (size_t k = 0; k < who.size(); k++) {
+            st[who[k]].last_rec = got[k];
+            if (want_ssim) st[who[k]].last_ssim = sgot[k];
+        }
         return PNGLOSS_SUCCESS;
     };
 
@@ -1418,14 +1510,14 @@ static int target_search(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *ima
             TargetImage &s = st[i];
             if (s.last.status != 0) {                            /* ends this image's search: it keeps this probe's result and status */
                 pl_target_fail(s.search);
-                s.kept = s.last; s.kept_rec = s.last_rec;
+                s.kept = s.last; s.kept_rec = s.last_rec; s.kept_ssim = s.last_ssim;
                 continue;
             }
-            const bool accepted = pl_target_accept(t, s.last_rec, s.last.status, s.last.bytes_per_pixel);
+            const bool accepted = pl_target_accept2(t, s.last_rec, s.last_ssim, s.last.status, s.last.bytes_per_pixel);
             const uint32_t strength = s.search.next;
             pl_target_step(s.search, accepted);
             if (!accepted) continue;
-            s.kept = s.last; s.kept_rec = s.last_rec; s.best = (long)strength;
+            s.kept = s.last; s.kept_rec = s.last_rec; s.kept_ssim = s.last_ssim; s.best = (long)strength;
             if (s.search.done) continue;                         /* (the chosen strength's result is in place) */
             add(stash, images[i].d_rgba, arena + lay.image[i].best, px_bytes(i));
             add(stash, images[i].d_row_filters, arena + lay.image[i].best_filters, filter_bytes(i));
@@ -1440,7 +1532,7 @@ static int target_search(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *ima
         TargetImage &s = st[i];
         if (s.search.failed) continue;
         if (s.in_place == (long)s.search.chosen) {
-            if (s.best != (long)s.search.chosen) { s.kept = s.last; s.kept_rec = s.last_rec; }
+            if (s.best != (long)s.search.chosen) { s.kept = s.last; s.kept_rec = s.last_rec; s.kept_ssim = s.last_ssim; }
             continue;
         }
         if (s.best == (long)s.search.chosen) {
@@ -1451,14 +1543,14 @@ static int target_search(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *ima
             continue;
         }
         zero.push_back((uint32_t)i);
-        s.kept = pngloss_hip_result{ 0, 0, 0, 0, 0 }; s.kept_rec = pngloss_hip_distortion{};
+        s.kept = pngloss_hip_result{ 0, 0, 0, 0, 0 }; s.kept_rec = pngloss_hip_distortion{}; s.kept_ssim = pngloss_hip_ssim{};
         if (commit) add(fin, arena + lay.image[i].orig, images[i].d_rgba, px_bytes(i));
     }
     rc = move(std::move(fin));
     if (rc == PNGLOSS_SUCCESS && commit && !zero.empty()) {
         rc = run_group(0, zero);
         if (rc == PNGLOSS_SUCCESS) rc = measure(zero);
-        for (uint32_t i : zero) { st[i].kept = st[i].last; st[i].kept_rec = st[i].last_rec; }
+        for (uint32_t i : zero) { st[i].kept = st[i].last; st[i].kept_rec = st[i].last_rec; st[i].kept_ssim = st[i].last_ssim; }
     }
     if (rc) return rc;
     PL_CHECK(hipStreamSynchronize(stream));
@@ -1467,16 +1559,17 @@ static int target_search(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *ima
         const TargetImage &s = st[i];
         if (results) results[i] = s.kept;
         if (reports) reports[i] = pngloss_hip_target_report{ s.search.chosen, s.search.probes, s.runs, 0, s.kept_rec };
+        if (ssim_out && want_ssim) ssim_out[i] = s.kept_ssim;
         if (s.kept.status) worst = PNGLOSS_INTERNAL_ABORT;
     }
     return worst;
 }
 
-static int target_arguments(const pngloss_hip_target *target, long bleed_divider)
+static int target_arguments(const pngloss_hip_target2 *target, long bleed_divider)
 {
-    const int rc = pl_target_check(target);
+    const int rc = pl_target_check2(target);
     if (rc) {
-        std::fprintf(stderr, "pngloss_hip: the target needs min_psnr_db >= 0 (not NaN), max_abs_error 0..255 and max_strength 0..255\n");
+        std::fprintf(stderr, "pngloss_hip: the target needs min_psnr_db >= 0 (not NaN), max_abs_error 0..255, max_strength 0..255 and min_ssim 0..1 (not NaN)\n");
         return rc;
     }
     if (bleed_divider < 1 || bleed_divider > 32767) {
@@ -1489,6 +1582,15 @@ static int target_arguments(const pngloss_hip_target *target, long bleed_divider
 int pngloss_hip_optimize_batch_target(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n,
                                       const pngloss_hip_target *target, long bleed_divider, void *stream,
                                       pngloss_hip_result *results, pngloss_hip_target_report *reports)
+{
+    if (!target) return target_arguments(nullptr, bleed_divider);
+    const pngloss_hip_target2 t2 = pl_target2_of(*target);
+    return pngloss_hip_optimize_batch_target2(ctx, images, n, &t2, bleed_divider, stream, results, reports, nullptr);
+}
+
+int pngloss_hip_optimize_batch_target2(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n,
+                                       const pngloss_hip_target2 *target, long bleed_divider, void *stream,
+                                       pngloss_hip_result *results, pngloss_hip_target_report *reports, pngloss_hip_ssim *ssim)
 {
     int rc = target_arguments(target, bleed_divider);
     if (rc) return rc;
@@ -1504,16 +1606,20 @@ int pngloss_hip_optimize_batch_target(pngloss_hip_ctx *ctx, const pngloss_hip_im
     }
     PL_CHECK(hipSetDevice(ctx->device));
     /* room for every original and every best result beside the workspace -- or the call fails here, with no image touched */
-    const PlTargetLayout lay = pl_target_layout(width, height, false, sizeof(PlMoveJob), sizeof(PlDistortJob), sizeof(PlDistortRecord));
+    const bool want_ssim = target->min_ssim != 0.0;
+    const PlTargetLayout lay = pl_target_layout(width, height, false, sizeof(PlMoveJob), sizeof(PlDistortJob), sizeof(PlDistortRecord),
+                                                want_ssim ? sizeof(PlSsimJob) : 0, want_ssim ? sizeof(PlSsimRecord) : 0);
     rc = grow(ctx->d_target, ctx->target_bytes, lay.total, 8);
     if (rc) return rc;
-    return target_search(ctx, images, n, lay, *target, bleed_divider, static_cast<hipStream_t>(stream), true, results, reports);
+    return target_search(ctx, images, n, lay, *target, bleed_divider, static_cast<hipStream_t>(stream), true, results, reports, ssim);
 }
 
 /* one context's share of pngloss_hip_multi_optimize_batch_host_target */
-static int batch_host_target(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images, size_t n, const pngloss_hip_target &target, long bleed_divider,
-                             pngloss_hip_result *results, pngloss_hip_scanlines *lines, pngloss_hip_zstream *zs, pngloss_hip_target_report *reports)
+static int batch_host_target(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images, size_t n, const pngloss_hip_target2 &target, long bleed_divider,
+                             pngloss_hip_result *results, pngloss_hip_scanlines *lines, pngloss_hip_zstream *zs, pngloss_hip_target_report *reports,
+                             pngloss_hip_ssim *ssim)
 {
+    const bool want_ssim = target.min_ssim != 0.0;
     if (!ctx || ctx->pending) return PNGLOSS_INVALID_ARGUMENT;
     PL_CHECK(hipSetDevice(ctx->device));
     std::vector<uint32_t> width(n), height(n);
@@ -1521,7 +1627,8 @@ static int batch_host_target(pngloss_hip_ctx *ctx, const pngloss_hip_host_image 
         if (images[i].width && images[i].height && !images[i].rgba) return PNGLOSS_INVALID_ARGUMENT;
         width[i] = images[i].width; height[i] = images[i].height;
     }
-    const PlTargetLayout lay = pl_target_layout(width, height, true, sizeof(PlMoveJob), sizeof(PlDistortJob), sizeof(PlDistortRecord));
+    const PlTargetLayout lay = pl_target_layout(width, height, true, sizeof(PlMoveJob), sizeof(PlDistortJob), sizeof(PlDistortRecord),
+                                                want_ssim ? sizeof(PlSsimJob) : 0, want_ssim ? sizeof(PlSsimRecord) : 0);
     int rc = grow(ctx->d_target, ctx->target_bytes, lay.total, 8);
     if (rc) return rc;
     if (!ctx->copy_stream) PL_CHECK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
@@ -1534,10 +1641,11 @@ static int batch_host_target(pngloss_hip_ctx *ctx, const pngloss_hip_host_image 
     }
     PL_CHECK(hipStreamSynchronize(ctx->copy_stream));
     std::vector<pngloss_hip_target_report> rep(n ? n : 1);
-    rc = target_search(ctx, descs.data(), n, lay, target, bleed_divider, ctx->copy_stream, false, nullptr, rep.data());
+    rc = target_search(ctx, descs.data(), n, lay, target, bleed_divider, ctx->copy_stream, false, nullptr, rep.data(), nullptr);
     if (rc != PNGLOSS_SUCCESS && rc != PNGLOSS_INTERNAL_ABORT) return rc;
-    /* the existing host-window path, once per distinct chosen strength; measured, so that every report carries the record of what was written */
-    const bool opt = ctx->opt_distortion;
+    /* the existing host-window path, once per distinct chosen strength; measured, so that every report carries the record of what was written
+     * (the SSIM record too, but only for a search with an SSIM condition) */
+    const bool opt = ctx->opt_distortion, opt_ssim = ctx->opt_ssim;
     int worst = PNGLOSS_SUCCESS;
     for (uint32_t strength = 0; strength < 256; strength++) {
         std::vector<size_t> who;
@@ -1552,9 +1660,9 @@ static int batch_host_target(pngloss_hip_ctx *ctx, const pngloss_hip_host_image 
             if (lines) ln[k] = lines[who[k]];
             if (zs) zz[k] = zs[who[k]];
         }
-        ctx->opt_distortion = true;
+        ctx->opt_distortion = true; ctx->opt_ssim = want_ssim;
         rc = batch_host(ctx, im.data(), im.size(), strength, bleed_divider, rs.data(), lines ? ln.data() : nullptr, zs ? zz.data() : nullptr);
-        ctx->opt_distortion = opt;
+        ctx->opt_distortion = opt; ctx->opt_ssim = opt_ssim;
         for (size_t k = 0; k < who.size(); k++) {
             const size_t i = who[k];
             if (results) results[i] = rs[k];
@@ -1562,11 +1670,12 @@ static int batch_host_target(pngloss_hip_ctx *ctx, const pngloss_hip_host_image 
             if (zs) zs[i] = zz[k];
             rep[i].runs++;
             if (rc == PNGLOSS_SUCCESS || rc == PNGLOSS_INTERNAL_ABORT) (void)pngloss_hip_last_distortion(ctx, k, &rep[i].distortion);
+            if (ssim && want_ssim && (rc == PNGLOSS_SUCCESS || rc == PNGLOSS_INTERNAL_ABORT)) (void)pngloss_hip_last_ssim(ctx, k, &ssim[i]);
         }
         if (rc != PNGLOSS_SUCCESS && (worst == PNGLOSS_SUCCESS || worst == PNGLOSS_INTERNAL_ABORT)) worst = rc;
     }
-    for (pngloss_hip_ctx *p : ctx->peers) if (p) { p->opt_distortion = opt; p->n_last = 0; p->distortion.clear(); }
-    ctx->n_last = 0; ctx->split_last = false; ctx->distortion.clear(); ctx->h_jobs.clear();      /* no single batch to index */
+    for (pngloss_hip_ctx *p : ctx->peers) if (p) { p->opt_distortion = opt; p->opt_ssim = opt_ssim; p->n_last = 0; p->distortion.clear(); p->ssim.clear(); }
+    ctx->n_last = 0; ctx->split_last = false; ctx->distortion.clear(); ctx->ssim.clear(); ctx->h_jobs.clear();      /* no single batch to index */
     if (reports) for (size_t i = 0; i < n; i++) reports[i] = rep[i];
     return worst;
 }
@@ -1575,6 +1684,16 @@ int pngloss_hip_multi_optimize_batch_host_target(pngloss_hip_multi *m, const png
                                                  const pngloss_hip_target *target, long bleed_divider, pngloss_hip_result *results,
                                                  pngloss_hip_scanlines *scanlines, pngloss_hip_zstream *streams,
                                                  pngloss_hip_target_report *reports)
+{
+    if (!target) return target_arguments(nullptr, bleed_divider);
+    const pngloss_hip_target2 t2 = pl_target2_of(*target);
+    return pngloss_hip_multi_optimize_batch_host_target2(m, images, n, &t2, bleed_divider, results, scanlines, streams, reports, nullptr);
+}
+
+int pngloss_hip_multi_optimize_batch_host_target2(pngloss_hip_multi *m, const pngloss_hip_host_image *images, size_t n,
+                                                  const pngloss_hip_target2 *target, long bleed_divider, pngloss_hip_result *results,
+                                                  pngloss_hip_scanlines *scanlines, pngloss_hip_zstream *streams,
+                                                  pngloss_hip_target_report *reports, pngloss_hip_ssim *ssim)
 {
     const int arc = target_arguments(target, bleed_divider);
     if (arc) return arc;
@@ -1593,6 +1712,7 @@ int pngloss_hip_multi_optimize_batch_host_target(pngloss_hip_multi *m, const png
             std::vector<pngloss_hip_host_image> im(mine.size());
             std::vector<pngloss_hip_result> rs(mine.size());
             std::vector<pngloss_hip_target_report> rp(mine.size());
+            std::vector<pngloss_hip_ssim> sm(mine.size());
             std::vector<pngloss_hip_scanlines> ln(scanlines ? mine.size() : 0);
             std::vector<pngloss_hip_zstream> zz(streams ? mine.size() : 0);
             for (size_t k = 0; k < mine.size(); k++) {
@@ -1601,10 +1721,11 @@ int pngloss_hip_multi_optimize_batch_host_target(pngloss_hip_multi *m, const png
                 if (streams) zz[k] = streams[mine[k]];
             }
             rcs[(size_t)p2] = batch_host_target(m->ctx[(size_t)p2], im.data(), im.size(), *target, bleed_divider, rs.data(),
-                                                scanlines ? ln.data() : nullptr, streams ? zz.data() : nullptr, rp.data());
+                                                scanlines ? ln.data() : nullptr, streams ? zz.data() : nullptr, rp.data(), sm.data());
             for (size_t k = 0; k < mine.size(); k++) {
                 if (results) results[mine[k]] = rs[k];
                 if (reports) reports[mine[k]] = rp[k];
+                if (ssim && target->min_ssim != 0.0) ssim[mine[k]] = sm[k];
                 if (scanlines) scanlines[mine[k]] = ln[k];
                 if (streams) streams[mine[k]] = zz[k];
             }
@@ -1668,6 +1789,20 @@ int pngloss_hip_multi_last_distortion(pngloss_hip_multi *m, size_t index, pnglos
     return pngloss_hip_last_distortion(m->ctx[(size_t)m->where[index].first], m->where[index].second, out);
 }
 
+int pngloss_hip_last_ssim(pngloss_hip_ctx *ctx, size_t index, pngloss_hip_ssim *out)
+{
+    ctx = chunk_of(ctx, index);
+    if (!ctx || !out || ctx->pending || index >= ctx->n_last || index >= ctx->ssim.size()) return PNGLOSS_INVALID_ARGUMENT;
+    *out = ctx->ssim[index];
+    return PNGLOSS_SUCCESS;
+}
+
+int pngloss_hip_multi_last_ssim(pngloss_hip_multi *m, size_t index, pngloss_hip_ssim *out)
+{
+    if (!m || index >= m->where.size()) return PNGLOSS_INVALID_ARGUMENT;
+    return pngloss_hip_last_ssim(m->ctx[(size_t)m->where[index].first], m->where[index].second, out);
+}
+
 int pngloss_hip_multi_set_option(pngloss_hip_multi *m, const char *name, const char *value)
 {
     if (!m || m->ctx.empty()) return PNGLOSS_INVALID_ARGUMENT;
@@ -1707,6 +1842,38 @@ int pngloss_hip_compare_batch(pngloss_hip_ctx *ctx, const pngloss_hip_image_pair
     PL_CHECK(hipMemcpyAsync(out, ctx->d_keep + lay.records, sizeof(pngloss_hip_distortion) * n, hipMemcpyDeviceToHost, stream));
     PL_CHECK(hipStreamSynchronize(stream));
     return PNGLOSS_SUCCESS;
+}
+
+int pngloss_hip_compare_batch_ssim(pngloss_hip_ctx *ctx, const pngloss_hip_image_pair *pairs, size_t n, pngloss_hip_ssim *out, void *stream_)
+{
+    if (!ctx || (n && (!pairs || !out))) return PNGLOSS_INVALID_ARGUMENT;
+    if (ctx->pending) {
+        std::fprintf(stderr, "pngloss_hip: a batch is in flight on this context; call pngloss_hip_finish first\n");
+        return PNGLOSS_INVALID_ARGUMENT;
+    }
+    if (!n) return PNGLOSS_SUCCESS;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    std::vector<const void *> a(n), b(n);
+    std::vector<uint32_t> width(n), height(n);
+    for (size_t i = 0; i < n; i++) {
+        if (pairs[i].width && pairs[i].height && (!pairs[i].d_a || !pairs[i].d_b)) return PNGLOSS_INVALID_ARGUMENT;
+        a[i] = pairs[i].d_a; b[i] = pairs[i].d_b;
+        width[i] = pairs[i].width; height[i] = pairs[i].height;
+    }
+    PL_CHECK(hipSetDevice(ctx->device));
+    PlSsimLayout lay;
+    uint64_t max_tiles = 0;
+    const int rc = upload_ssim_jobs(ctx, n, a.data(), b.data(), width.data(), height.data(), stream, lay, max_tiles);
+    if (rc) return rc;
+    PL_CHECK(pl_launch_ssim(reinterpret_cast<const PlSsimJob *>(ctx->d_ssim + lay.jobs), n, max_tiles, stream));
+    PL_CHECK(hipMemcpyAsync(out, ctx->d_ssim + lay.records, sizeof(pngloss_hip_ssim) * n, hipMemcpyDeviceToHost, stream));
+    PL_CHECK(hipStreamSynchronize(stream));
+    return PNGLOSS_SUCCESS;
+}
+
+double pngloss_hip_ssim_mean(const pngloss_hip_ssim *r, unsigned channel_mask)
+{
+    return r ? pls_mean(r->windows, r->sum_q16, channel_mask) : std::nan("");
 }
 
 double pngloss_hip_psnr_db(const pngloss_hip_distortion *d, unsigned channel_mask)
@@ -1909,6 +2076,12 @@ int pngloss_hip_set_option(pngloss_hip_ctx *ctx, const char *name, const char *v
         /* measure every batch from here on (pl_distort.hip): "on" | "off" (default) */
         if (std::strcmp(value, "on") == 0) { ctx->opt_distortion = true; return PNGLOSS_SUCCESS; }
         if (std::strcmp(value, "off") == 0) { ctx->opt_distortion = false; return PNGLOSS_SUCCESS; }
+        return PNGLOSS_INVALID_ARGUMENT;
+    }
+    if (std::strcmp(name, "ssim") == 0) {
+        /* measure the structural similarity of every batch from here on (pl_ssim.hip): "on" | "off" (default) */
+        if (std::strcmp(value, "on") == 0) { ctx->opt_ssim = true; return PNGLOSS_SUCCESS; }
+        if (std::strcmp(value, "off") == 0) { ctx->opt_ssim = false; return PNGLOSS_SUCCESS; }
         return PNGLOSS_INVALID_ARGUMENT;
     }
     return PNGLOSS_INVALID_ARGUMENT;

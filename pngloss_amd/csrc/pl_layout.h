@@ -1,6 +1,6 @@
 /*
  * pl_layout.h -- every carve-up of a buffer the host shim makes, as pure functions from sizes to offsets: the batch workspace of enqueue(), the
- * arena of a host window (batch_host_one), the keep arena of the distortion measurement, the read side's workspace and frame arena
+ * arena of a host window (batch_host_one), the keep arena of the distortion measurement, the tables of the SSIM measurement, the read side's workspace and frame arena
  * (png_decode_body), and the size a buffer is regrown to.
  * Internal.
  *
@@ -181,6 +181,22 @@ inline PlKeepLayout pl_keep_layout(const std::vector<uint32_t> &width, const std
     if (originals)
         for (size_t i = 0; i < n; i++) k.image[i] = take((size_t)width[i] * height[i] * 4);
     return k;
+}
+
+/* ================================================================================================ the SSIM tables (option "ssim": enqueue, compare_batch_ssim) */
+
+/* The PlSsimJob table at 0, then one record per image: a small buffer of its own.  The originals the jobs point at are the keep arena's, which the
+ * options "distortion" and "ssim" share (pngloss_hip_compare_batch_ssim measures two images of the caller's). */
+struct PlSsimLayout { size_t jobs = 0, records = 0, total = 0; };
+
+/* job_bytes, record_bytes: sizeof(PlSsimJob), sizeof(PlSsimRecord) */
+inline PlSsimLayout pl_ssim_layout(size_t n, size_t job_bytes, size_t record_bytes)
+{
+    PlSsimLayout l;
+    l.jobs = 0;
+    l.records = pl_align_up(job_bytes * (n ? n : 1), PLL_ALIGN);
+    l.total = l.records + pl_align_up(record_bytes * (n ? n : 1), PLL_ALIGN);
+    return l;
 }
 
 /* ================================================================================================ the read side (png_decode_body) */

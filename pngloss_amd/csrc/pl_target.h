@@ -14,12 +14,16 @@
  *   3. while hi - lo > 1: probe mid = (lo + hi) / 2; accepted: lo = mid, else hi = mid
  *   4. the chosen strength is lo
  * At most 1 + ceil(log2 M) probes, 1 for M <= 1.  A probe whose status is not 0 ends the search: the image keeps that probe's result.
+ *
+ * pngloss_hip_optimize_batch_target2 adds a smallest mean SSIM to the target (pngloss_hip_target2): the same procedure, one more condition in the
+ * acceptance rule (pl_target_accept2), one more record table in the arena.  The older target is the newer one with min_ssim = 0.
  */
 #ifndef PL_TARGET_H
 #define PL_TARGET_H
 
 #include "../../include/pngloss_hip.h"
 #include "pl_distort_core.h"
+#include "pl_ssim_core.h"
 
 #include <cstddef>
 #include <cstdint>
@@ -32,6 +36,22 @@ inline int pl_target_check(const pngloss_hip_target *t)
     if (!t) return PNGLOSS_INVALID_ARGUMENT;
     if (t->min_psnr_db != t->min_psnr_db || t->min_psnr_db < 0.0) return PNGLOSS_INVALID_ARGUMENT;      /* NaN, negative */
     if (t->max_abs_error > 255u || t->max_strength > 255u) return PNGLOSS_INVALID_ARGUMENT;
+    return PNGLOSS_SUCCESS;
+}
+
+/* the older target as the newer one: no SSIM condition */
+inline pngloss_hip_target2 pl_target2_of(const pngloss_hip_target &t)
+{
+    return pngloss_hip_target2{ t.min_psnr_db, t.max_abs_error, t.max_strength, 0.0 };
+}
+
+/* the same for a pngloss_hip_target2: min_ssim is 0 (no condition) or in (0, 1] */
+inline int pl_target_check2(const pngloss_hip_target2 *t)
+{
+    if (!t) return PNGLOSS_INVALID_ARGUMENT;
+    const pngloss_hip_target old = { t->min_psnr_db, t->max_abs_error, t->max_strength };
+    if (pl_target_check(&old) != PNGLOSS_SUCCESS) return PNGLOSS_INVALID_ARGUMENT;
+    if (t->min_ssim != t->min_ssim || t->min_ssim < 0.0 || t->min_ssim > 1.0) return PNGLOSS_INVALID_ARGUMENT;   /* NaN, negative, above 1 */
     return PNGLOSS_SUCCESS;
 }
 
@@ -55,6 +75,16 @@ inline bool pl_target_accept(const pngloss_hip_target &t, const pngloss_hip_dist
         if (largest > t.max_abs_error) return false;
     }
     return true;
+}
+
+/* The same with the SSIM condition: `srec` is the probe's SSIM record (not looked at when min_ssim == 0).  An image without windows -- narrower or
+ * lower than 8 pixels -- cannot be measured: the condition does not apply to it. */
+inline bool pl_target_accept2(const pngloss_hip_target2 &t, const pngloss_hip_distortion &rec, const pngloss_hip_ssim &srec, int32_t status, uint32_t bytes_per_pixel)
+{
+    const pngloss_hip_target old = { t.min_psnr_db, t.max_abs_error, t.max_strength };
+    if (!pl_target_accept(old, rec, status, bytes_per_pixel)) return false;
+    if (t.min_ssim == 0.0 || !rec.pixels || !srec.windows) return true;
+    return pls_mean(srec.windows, srec.sum_q16, pl_target_mask_of_bpp(bytes_per_pixel)) >= t.min_ssim;
 }
 
 /* The search of one image.  While !done, `next` is the strength to probe; pl_target_step takes that probe's verdict. */
@@ -121,18 +151,21 @@ inline std::vector<std::pair<uint32_t, std::vector<uint32_t>>> pl_target_groups(
 
 /* ---- the search arena of a context: apart from the workspace and from the keep arena of the option "distortion" (every enqueue() lays that one
  * out afresh, which would lose the originals of the images outside the current group).  In front the tables -- the move jobs of one launch (at
- * most three per image: pixels, filters, and pixels of another kind in the last launch), the measuring jobs and their records --, behind them per
+ * most three per image: pixels, filters, and pixels of another kind in the last launch), the measuring jobs and their records, with an SSIM
+ * condition also the SSIM kernel's jobs and records --, behind them per
  * image its original, the best result so far and that result's row filters; for host images also the image itself and its filters. */
 constexpr size_t PLT_ALIGN = 256;
 constexpr size_t PLT_MOVES_PER_IMAGE = 3;
 struct PlTargetImage { size_t orig = 0, best = 0, best_filters = 0, img = 0, filters = 0; };
 struct PlTargetLayout {
     size_t moves = 0, jobs = 0, records = 0, total = 0;
+    size_t ssim_jobs = 0, ssim_records = 0;        /* the SSIM kernel's job table and records (no bytes when the search has no SSIM condition) */
     std::vector<PlTargetImage> image;
 };
 
 inline PlTargetLayout pl_target_layout(const std::vector<uint32_t> &width, const std::vector<uint32_t> &height, bool host_images,
-                                       size_t move_job_bytes, size_t distort_job_bytes, size_t record_bytes)
+                                       size_t move_job_bytes, size_t distort_job_bytes, size_t record_bytes,
+                                       size_t ssim_job_bytes = 0, size_t ssim_record_bytes = 0)
 {
     auto up = [](size_t v) { return (v + PLT_ALIGN - 1) / PLT_ALIGN * PLT_ALIGN; };
     const size_t n = width.size();
@@ -141,6 +174,8 @@ inline PlTargetLayout pl_target_layout(const std::vector<uint32_t> &width, const
     lay.moves = at; at = up(at + move_job_bytes * PLT_MOVES_PER_IMAGE * n);
     lay.jobs = at; at = up(at + distort_job_bytes * n);
     lay.records = at; at = up(at + record_bytes * n);
+    lay.ssim_jobs = at; at = up(at + ssim_job_bytes * n);
+    lay.ssim_records = at; at = up(at + ssim_record_bytes * n);
     lay.image.resize(n);
     for (size_t i = 0; i < n; i++) {
         const size_t px = (size_t)width[i] * height[i] * 4, rows = width[i] ? height[i] : 0;

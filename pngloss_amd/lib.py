@@ -114,6 +114,18 @@ class Distortion(C.Structure):
         return psnr_db(self, channel_mask)
 
 
+class Ssim(C.Structure):
+    """pngloss_hip_ssim: the structural similarity of a result to its original over 8x8 windows at a stride of 4 (channels R, G, B, A).  All exact
+    integers: sum_q16[c] is the sum and min_q16[c] the smallest of the windows' q (65536 = equal windows)."""
+    _fields_ = [("windows", C.c_uint64), ("sum_q16", C.c_int64 * 4), ("min_q16", C.c_int32 * 4), ("reserved", C.c_uint64)]
+
+    def as_dict(self):
+        return dict(windows=self.windows, sum_q16=list(self.sum_q16), min_q16=list(self.min_q16), reserved=self.reserved)
+
+    def mean(self, channel_mask=0xF):
+        return ssim_mean(self, channel_mask)
+
+
 class ImagePair(C.Structure):
     _fields_ = [("d_a", C.c_void_p), ("d_b", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32)]
 
@@ -129,6 +141,15 @@ def psnr_db(distortion, channel_mask=0xF):
         d = distortion
         distortion = Distortion(d["pixels"], d["changed_pixels"], (C.c_uint64 * 4)(*d["sq_err"]), (C.c_uint32 * 4)(*d["max_abs"]))
     return hip_lib().pngloss_hip_psnr_db(C.byref(distortion), channel_mask)
+
+
+def ssim_mean(ssim, channel_mask=0xF):
+    """pngloss_hip_ssim_mean: the sum of sum_q16 over the mask's channels / (65536 * windows * popcount(mask)); nan for no windows or a mask outside
+    1..15.  `ssim`: an Ssim or the dict Ssim.as_dict() gives.  Host arithmetic: needs no GPU."""
+    if not isinstance(ssim, Ssim):
+        d = ssim
+        ssim = Ssim(d["windows"], (C.c_int64 * 4)(*d["sum_q16"]), (C.c_int32 * 4)(*d["min_q16"]), d.get("reserved", 0))
+    return hip_lib().pngloss_hip_ssim_mean(C.byref(ssim), channel_mask)
 
 
 def build(verbose: bool = False) -> None:
@@ -175,6 +196,8 @@ ABI_SYMBOLS = (
     "pngloss_hip_multi_optimize_batch_host",
     "pngloss_hip_last_distortion", "pngloss_hip_compare_batch", "pngloss_hip_psnr_db", "pngloss_hip_multi_set_option", "pngloss_hip_multi_last_distortion",
     "pngloss_hip_optimize_batch_target", "pngloss_hip_multi_optimize_batch_host_target",
+    "pngloss_hip_last_ssim", "pngloss_hip_multi_last_ssim", "pngloss_hip_compare_batch_ssim", "pngloss_hip_ssim_mean",
+    "pngloss_hip_optimize_batch_target2", "pngloss_hip_multi_optimize_batch_host_target2",
 )
 
 
@@ -250,6 +273,14 @@ def hip_lib():
             lib.pngloss_hip_multi_set_option.restype = C.c_int
             lib.pngloss_hip_multi_last_distortion.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(Distortion)]
             lib.pngloss_hip_multi_last_distortion.restype = C.c_int
+            lib.pngloss_hip_last_ssim.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(Ssim)]
+            lib.pngloss_hip_last_ssim.restype = C.c_int
+            lib.pngloss_hip_multi_last_ssim.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(Ssim)]
+            lib.pngloss_hip_multi_last_ssim.restype = C.c_int
+            lib.pngloss_hip_compare_batch_ssim.argtypes = [C.c_void_p, C.POINTER(ImagePair), C.c_size_t, C.POINTER(Ssim), C.c_void_p]
+            lib.pngloss_hip_compare_batch_ssim.restype = C.c_int
+            lib.pngloss_hip_ssim_mean.argtypes = [C.POINTER(Ssim), C.c_uint]
+            lib.pngloss_hip_ssim_mean.restype = C.c_double
             _target_abi(lib)
             _hip = lib
         return _hip
@@ -532,6 +563,23 @@ class HipContext:
         _check(self._lib.pngloss_hip_last_distortion(self._ctx, index, C.byref(d)), "last_distortion")
         return d
 
+    def ssim(self, index=0):
+        """pngloss_hip_last_ssim: the Ssim of image `index` of the last finished batch, which must have run with set_option("ssim", "on") --
+        otherwise, for an index out of range and while a batch is pending the call fails (pngloss_error 4)."""
+        r = Ssim()
+        _check(self._lib.pngloss_hip_last_ssim(self._ctx, index, C.byref(r)), "last_ssim")
+        return r
+
+    def compare_ssim(self, pairs, stream=0):
+        """pngloss_hip_compare_batch_ssim: pairs as for compare(); returns one Ssim per pair (b against a).  Synchronous."""
+        n = len(pairs)
+        arr = (ImagePair * max(n, 1))()
+        for i, (a, b, w, h) in enumerate(pairs):
+            arr[i] = ImagePair(a or None, b or None, w, h)
+        out = (Ssim * max(n, 1))()
+        _check(self._lib.pngloss_hip_compare_batch_ssim(self._ctx, arr, n, out, stream or None), "compare_batch_ssim")
+        return [out[i] for i in range(n)]
+
     def compare(self, pairs, stream=0):
         """pngloss_hip_compare_batch: pairs = sequence of (d_a_ptr, d_b_ptr, width, height), device-resident RGBA8; returns one Distortion per pair
         (b against a).  Synchronous."""
@@ -610,6 +658,12 @@ class HipMulti:
         _check(self._lib.pngloss_hip_multi_last_distortion(self._m, index, C.byref(d)), "multi_last_distortion")
         return d
 
+    def ssim(self, index=0):
+        """pngloss_hip_multi_last_ssim: the Ssim of arrays[index] of the last run_host, whichever context it went to"""
+        r = Ssim()
+        _check(self._lib.pngloss_hip_multi_last_ssim(self._m, index, C.byref(r)), "multi_last_ssim")
+        return r
+
     def run_host(self, arrays, strength=19, bleed=2, want_filters=True):
         outs = [np.ascontiguousarray(a).copy() for a in arrays]
         filts = [np.zeros(a.shape[0], np.uint8) if want_filters else None for a in outs]
@@ -633,6 +687,14 @@ class Target(C.Structure):
         super().__init__(min_psnr_db, max_abs_error, max_strength)
 
 
+class Target2(C.Structure):
+    """pngloss_hip_target2: a Target with min_ssim, the smallest allowed mean SSIM over the stored channels (0 = no condition, else in (0, 1])."""
+    _fields_ = [("min_psnr_db", C.c_double), ("max_abs_error", C.c_uint32), ("max_strength", C.c_uint32), ("min_ssim", C.c_double)]
+
+    def __init__(self, min_psnr_db=0.0, max_abs_error=0, max_strength=19, min_ssim=0.0):
+        super().__init__(min_psnr_db, max_abs_error, max_strength, min_ssim)
+
+
 class TargetReport(C.Structure):
     """pngloss_hip_target_report: the chosen strength, the probes of the rule, the row-engine runs spent and the Distortion of the result kept."""
     _fields_ = [("strength", C.c_uint32), ("probes", C.c_uint32), ("runs", C.c_uint32), ("reserved", C.c_uint32), ("distortion", Distortion)]
@@ -649,6 +711,12 @@ def _target_abi(lib):
     lib.pngloss_hip_multi_optimize_batch_host_target.argtypes = [C.c_void_p, C.POINTER(HostImage), C.c_size_t, C.POINTER(Target), C.c_long, C.POINTER(Result),
                                                                  C.POINTER(Scanlines), C.POINTER(ZStream), C.POINTER(TargetReport)]
     lib.pngloss_hip_multi_optimize_batch_host_target.restype = C.c_int
+    lib.pngloss_hip_optimize_batch_target2.argtypes = [C.c_void_p, C.POINTER(ImageDesc), C.c_size_t, C.POINTER(Target2), C.c_long, C.c_void_p, C.POINTER(Result),
+                                                       C.POINTER(TargetReport), C.POINTER(Ssim)]
+    lib.pngloss_hip_optimize_batch_target2.restype = C.c_int
+    lib.pngloss_hip_multi_optimize_batch_host_target2.argtypes = [C.c_void_p, C.POINTER(HostImage), C.c_size_t, C.POINTER(Target2), C.c_long, C.POINTER(Result),
+                                                                  C.POINTER(Scanlines), C.POINTER(ZStream), C.POINTER(TargetReport), C.POINTER(Ssim)]
+    lib.pngloss_hip_multi_optimize_batch_host_target2.restype = C.c_int
     return lib
 
 
@@ -658,7 +726,8 @@ def _result_dict(r):
 
 def _run_target(self, images, target, bleed=2, stream=0):
     """pngloss_hip_optimize_batch_target: images as for run(); every image ends up as run() at its chosen strength leaves it.  Synchronous.
-    Returns (results, reports): the dicts run() returns and one TargetReport per image."""
+    Returns (results, reports): the dicts run() returns and one TargetReport per image.  With a Target2 the call is
+    pngloss_hip_optimize_batch_target2 and returns (results, reports, ssim): one Ssim per image, filled when target.min_ssim != 0."""
     n = len(images)
     descs = (ImageDesc * max(n, 1))()
     for i, (p, f, w, h) in enumerate(images):
@@ -666,6 +735,11 @@ def _run_target(self, images, target, bleed=2, stream=0):
     res = (Result * max(n, 1))()
     rep = (TargetReport * max(n, 1))()
     self._n = 0
+    if isinstance(target, Target2):
+        ssim = (Ssim * max(n, 1))()
+        _check(self._lib.pngloss_hip_optimize_batch_target2(self._ctx, descs, n, C.byref(target), bleed, stream or None, res, rep, ssim), "optimize_batch_target2",
+               partial_ok=True)
+        return [_result_dict(r) for r in res[:n]], [rep[i] for i in range(n)], [ssim[i] for i in range(n)]
     _check(self._lib.pngloss_hip_optimize_batch_target(self._ctx, descs, n, C.byref(target), bleed, stream or None, res, rep), "optimize_batch_target",
            partial_ok=True)
     return [_result_dict(r) for r in res[:n]], [rep[i] for i in range(n)]
@@ -673,7 +747,8 @@ def _run_target(self, images, target, bleed=2, stream=0):
 
 def _run_host_target(self, arrays, target, bleed=2, want_filters=True, emit=None, stream_only=False):
     """pngloss_hip_multi_optimize_batch_host_target on a list of (H, W, 4) uint8 arrays.  emit: None, "scanlines" or "zlib".  Returns
-    (outs, filters, results, reports, emitted): emitted is None, or per image what run_host_emit / run_host_zlib return for it."""
+    (outs, filters, results, reports, emitted): emitted is None, or per image what run_host_emit / run_host_zlib return for it.  With a Target2 the
+    call is pngloss_hip_multi_optimize_batch_host_target2 and a sixth element follows: one Ssim per image, filled when target.min_ssim != 0."""
     outs = [np.ascontiguousarray(a).copy() for a in arrays]
     filts = [np.zeros(a.shape[0], np.uint8) if want_filters else None for a in outs]
     n = len(outs)
@@ -696,15 +771,21 @@ def _run_host_target(self, arrays, target, bleed=2, want_filters=True, emit=None
         raise ValueError("emit: None, 'scanlines' or 'zlib'")
     res = (Result * max(n, 1))()
     rep = (TargetReport * max(n, 1))()
-    _check(self._lib.pngloss_hip_multi_optimize_batch_host_target(self._m, imgs, n, C.byref(target), bleed, res, lines, zs, rep),
-           "multi_optimize_batch_host_target", partial_ok=True)
+    ssim = (Ssim * max(n, 1))() if isinstance(target, Target2) else None
+    if ssim is not None:
+        _check(self._lib.pngloss_hip_multi_optimize_batch_host_target2(self._m, imgs, n, C.byref(target), bleed, res, lines, zs, rep, ssim),
+               "multi_optimize_batch_host_target2", partial_ok=True)
+    else:
+        _check(self._lib.pngloss_hip_multi_optimize_batch_host_target(self._m, imgs, n, C.byref(target), bleed, res, lines, zs, rep),
+               "multi_optimize_batch_host_target", partial_ok=True)
     emitted = None
     if emit == "scanlines":
         chans = {0: 1, 4: 2, 2: 3, 6: 4}
         emitted = [(lines[i].color_type, ids[i], rows[i][:, : outs[i].shape[1] * chans.get(lines[i].color_type, 4)].copy()) for i in range(n)]
     elif emit == "zlib":
         emitted = [(zs[i].color_type, bufs[i][: zs[i].size].tobytes(), tuple(zs[i].blocks)) for i in range(n)]
-    return outs, filts, [dict(status=r.status, bpp=r.bytes_per_pixel, unique_symbols=r.unique_symbols) for r in res[:n]], [rep[i] for i in range(n)], emitted
+    out = (outs, filts, [dict(status=r.status, bpp=r.bytes_per_pixel, unique_symbols=r.unique_symbols) for r in res[:n]], [rep[i] for i in range(n)], emitted)
+    return out + ([ssim[i] for i in range(n)],) if ssim is not None else out
 
 
 HipContext.run_target = _run_target
