@@ -390,6 +390,72 @@ int pngloss_hip_multi_optimize_batch_host_target2(pngloss_hip_multi *multi, cons
                                                   pngloss_hip_scanlines *scanlines, pngloss_hip_zstream *streams,
                                                   pngloss_hip_target_report *reports, pngloss_hip_ssim *ssim);
 
+/* ---- A strength per image, found from a BYTE BUDGET (no reference equivalent).  The other half of a lossy compressor's contract: "make this
+ * stream at most N bytes".  The originals stay on the device between the probes, the scanlines of every probe are emitted on the device, and the
+ * device deflate -- the one that writes the streams of pngloss_hip_optimize_batch_host_zlib -- measures each probe's exact stream size without
+ * writing the stream.
+ *
+ * A probe of an image at a strength is ACCEPTED when its status is 0 and its stream size is at most the image's max_bytes.  The stream size is
+ * that of the complete zlib stream, 78 DA ... Adler-32: the number pngloss_hip_zstream.size reports for pngloss_hip_optimize_batch_host_zlib at
+ * that strength.  The size is NOT guaranteed to be monotone in the strength, so the chosen strength is defined by this procedure, per image, with
+ * M = max_strength:
+ *     1. probe M; if it is refused, the chosen strength is M and reached = 0: the budget cannot be met below M, the image keeps the M result
+ *     2. otherwise lo = -1 (virtual, refused), hi = M
+ *     3. while hi - lo > 1: probe mid = (lo + hi) / 2, rounded down; accepted: hi = mid, otherwise lo = mid
+ *     4. the chosen strength is hi and reached = 1
+ * At most 1 + ceil(log2(M + 1)) probes.  Strength 0 is probed only when every probe above it passed: the lossless result, when it already fits.
+ * A probe whose status is not 0 ends that image's search: the image keeps that probe's result and status, reached = 0.  An image without pixels
+ * is chosen 0 with 0 probes (reached = 1, bytes = 0: it has no stream).
+ * PNGLOSS_INVALID_ARGUMENT, before any image is touched: max_strength > 255; max_bytes NULL or max_bytes[i] == 0 for an image that has pixels; an
+ * image with more than 1 GiB of scanlines ((4 * width + 1) * height, as for the _zlib form). */
+typedef struct {
+    const uint64_t *max_bytes;   /* n entries, indexed like images[]: the largest allowed zlib stream of image i */
+    uint32_t max_strength;       /* M, 0..255: the search never goes above it */
+    uint32_t reserved;           /* 0 */
+} pngloss_hip_size_target;
+
+typedef struct {
+    uint32_t strength;           /* chosen */
+    uint32_t probes;             /* probes of the rule above */
+    uint32_t runs;               /* row-engine runs spent on this image */
+    uint32_t reached;            /* 1: bytes <= max_bytes[i]; 0: not even M fits (or a probe failed) */
+    uint64_t bytes;              /* measured size of the kept result's zlib stream; 0 for an image without pixels or a failed probe */
+    int32_t  color_type;         /* of the kept result's scanlines: 0, 2, 4 or 6 */
+    uint32_t reserved;           /* 0 */
+    pngloss_hip_distortion distortion;   /* of the result that was kept, against the original */
+} pngloss_hip_size_report;
+
+/* The search on n device-resident images.  SYNCHRONOUS.  On return image i holds what pngloss_hip_optimize_batch at reports[i].strength writes,
+ * byte for byte: pixels, d_row_filters and results[i] (results and reports may be NULL).  Every round the images still searching are grouped by
+ * the strength they probe next; each group runs as one ordinary batch whose scanlines are emitted into the search arena, then ONE measuring
+ * deflate takes the sizes of all images probed in the round and one copy of n small records brings them to the host (and one small copy per group
+ * the colour types).  The plan, the engine choice
+ * and the engines are those of pngloss_hip_optimize_batch.  No engine run is repeated: runs == probes.  The arena holds per image the original,
+ * the best result so far with its row filters, and the scanlines of the current probe -- with `streams` also those of the best result so far --
+ * (about 3, with streams 4, times width * height * 4 bytes per image; if it cannot be had the call returns PNGLOSS_OUT_OF_MEMORY_ERROR before any
+ * image is touched).
+ * streams: NULL, or n entries as for pngloss_hip_optimize_batch_host_zlib (data / capacity: room for pngloss_hip_zlib_bound(width, height) bytes;
+ * flags are ignored).  One writing deflate over the kept results then fills them: streams[i] is byte for byte the stream _host_zlib gives for the
+ * same image at reports[i].strength (with row filters when d_row_filters is given, without when it is NULL), and streams[i].size ==
+ * reports[i].bytes.  This is also the way to a zlib stream of DEVICE-RESIDENT frames -- those of pngloss_hip_png_decode_batch_device, say --
+ * without a host round trip of the pixels: a budget no stream can meet (1 byte) and max_strength = s is "strength s, stream wanted" -- one probe,
+ * the image keeps the s result, reached = 0, and streams[i] is its stream.
+ * After the call pngloss_hip_last_distortion, _last_ssim, _last_histogram and _last_engine_info return PNGLOSS_INVALID_ARGUMENT (no single batch
+ * exists to index); the options "distortion" and "ssim" are left as the caller set them and play no part in the search. */
+int pngloss_hip_optimize_batch_size(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n,
+                                    const pngloss_hip_size_target *target, long bleed_divider, void *stream,
+                                    pngloss_hip_result *results, pngloss_hip_zstream *streams, pngloss_hip_size_report *reports);
+
+/* The same for host images over every context of `multi`, for the command line tool, as pngloss_hip_multi_optimize_batch_host_target: the images
+ * are split over the contexts; each context uploads its images, finds their strengths with the search above (on copies: nothing is written
+ * back), then runs the existing host-window path once per distinct chosen strength.  Outputs equal those of
+ * pngloss_hip_multi_optimize_batch_host at reports[i].strength, image by image; this form spends one more run per image: runs == probes + 1.
+ * results, scanlines, streams, reports may be NULL (independently).  After the call the _multi_last_* accessors return PNGLOSS_INVALID_ARGUMENT. */
+int pngloss_hip_multi_optimize_batch_host_size(pngloss_hip_multi *multi, const pngloss_hip_host_image *images, size_t n,
+                                               const pngloss_hip_size_target *target, long bleed_divider, pngloss_hip_result *results,
+                                               pngloss_hip_scanlines *scanlines, pngloss_hip_zstream *streams,
+                                               pngloss_hip_size_report *reports);
+
 /* ---- PNG read side behind the inflate.  Replaces what libpng does for rwpng_read_image24_libpng
  * (/root/reference/src/rwpng.c:179-400) between "inflated IDAT bytes" and "RGBA8 rows": the inverse scanline filters (a recurrence over
  * x and y, run as a row wavefront on the device) and the transformations that reader registers -- palette / low bit depths / tRNS

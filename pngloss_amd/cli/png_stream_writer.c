@@ -15,7 +15,7 @@
 #include <string.h>
 #include <zlib.h>
 
-#define IDAT_SLICE 8192u          /* libpng's default zbuffer_size */
+#define IDAT_SLICE ((unsigned)PNG_STREAM_ZLIB_IDAT_SLICE)          /* libpng's default zbuffer_size */
 
 typedef struct { FILE *fp; size_t total; pngloss_error status; } sink;
 
@@ -159,7 +159,7 @@ pngloss_error png_stream_write(FILE *out, const png_stream_image *im, size_t *by
 
     if (im->zdata) {
         /* ---- IDAT from a zlib stream that was compressed on the GPU: framing only (a chunk holds < 2^31 bytes) ---- */
-        const size_t slice = (size_t)1 << 30;
+        const size_t slice = PNG_STREAM_GPU_IDAT_SLICE;
         for (size_t off = 0; off < im->zsize; off += slice)
             put_chunk(&s, "IDAT", im->zdata + off, im->zsize - off < slice ? im->zsize - off : slice);
     } else {
@@ -173,4 +173,40 @@ pngloss_error png_stream_write(FILE *out, const png_stream_image *im, size_t *by
     if (bytes_written) *bytes_written = s.total;
     if (metadata_bytes) *metadata_bytes = meta;
     return SUCCESS;       /* like the reference, a short write is not reported (rwpng.c:631-636 only checks the size cap) */
+}
+
+/* the chunks put_passthrough copies, all three positions: 12 bytes of framing and the data, each */
+static size_t passthrough_bytes(const struct rwpng_chunk *list)
+{
+    size_t total = 0;
+    for (const struct rwpng_chunk *c = list; c; c = c->next) {
+        const int where = top_location(c->location);
+        if (where != PNG_STREAM_HAVE_IHDR && where != PNG_STREAM_HAVE_PLTE && where != PNG_STREAM_AFTER_IDAT) continue;
+        if (!(c->name[3] & 0x20)) continue;
+        total += c->size + 12;
+    }
+    return total;
+}
+
+size_t png_stream_file_size(const png_stream_image *im, size_t stream_bytes, size_t idat_slice)
+{
+    const size_t container = 8 + (12 + 13) + (im->tag_gamma ? 12 + 4 : 0) + (im->tag_srgb ? 12 + 1 : 0) + passthrough_bytes(im->chunks) + 12;
+    const size_t idat_chunks = (stream_bytes + idat_slice - 1) / idat_slice;
+    return container + stream_bytes + 12 * idat_chunks;
+}
+
+size_t png_stream_largest_stream(const png_stream_image *im, size_t file_budget, size_t idat_slice)
+{
+    const size_t container = png_stream_file_size(im, 0, idat_slice);
+    if (file_budget < container + 12 + 1) return 0;
+    /* k chunks hold at most k * idat_slice bytes and cost 12 * k: the most chunks whose framing and one byte more still fit */
+    const size_t room = file_budget - container;
+    size_t best = 0;
+    for (size_t k = 1; 12 * k < room; k++) {
+        size_t z = room - 12 * k;
+        if (z > k * idat_slice) z = k * idat_slice;
+        if (z > (k - 1) * idat_slice && z > best) best = z;
+        if (z < k * idat_slice) break;              /* more chunks only add framing */
+    }
+    return best;
 }

@@ -29,6 +29,19 @@ typedef struct {
 
 pngloss_error png_stream_write(FILE *out, const png_stream_image *image, size_t *bytes_written, size_t *metadata_bytes);
 
+/* How IDAT data is cut into chunks: zlib's output in libpng's 8192-byte slices; a finished stream from the GPU in chunks of 1 GiB (so: one) */
+#define PNG_STREAM_ZLIB_IDAT_SLICE ((size_t)8192)
+#define PNG_STREAM_GPU_IDAT_SLICE  ((size_t)1 << 30)
+
+/* The size of the file png_stream_write writes for `image` when its zlib stream has stream_bytes bytes and goes out in IDAT chunks of at most
+ * idat_slice bytes: signature, IHDR, the gAMA / sRGB tags, the pass-through chunks that will be copied, 12 bytes of framing per IDAT chunk, IEND.
+ * Only width-independent fields of `image` are read (tags and chunks): rows, filter ids and zdata may be NULL. */
+size_t png_stream_file_size(const png_stream_image *image, size_t stream_bytes, size_t idat_slice);
+
+/* The other way round: the largest stream whose file is at most file_budget bytes; 0 when not even a 1-byte stream fits (the budget is smaller
+ * than the container alone). */
+size_t png_stream_largest_stream(const png_stream_image *image, size_t file_budget, size_t idat_slice);
+
 #ifdef __cplusplus
 }
 #endif

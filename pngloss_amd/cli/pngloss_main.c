@@ -15,6 +15,7 @@
  * the overwrite rule, temp-file + atomic rename, --skip-if-larger, --strip, stdin/stdout with "-", and the exit code
  * is the error of the last failing file.  Verbose messages are buffered per file and printed in file order.
  */
+#include <errno.h>
 #include <getopt.h>
 #include <pthread.h>
 #include "png_stream_reader.h"
@@ -50,6 +51,9 @@ struct options {
     bool ssim;                 /* --ssim: one more line per written file: mean and worst-window SSIM against the input's pixels (measured on the device) */
     bool have_target_ssim;     /* --target-ssim: a condition of the strength search, like --target-psnr */
     double target_ssim;        /* 0: no SSIM condition */
+    bool have_size;            /* --target-size: the strength is found per file from a byte budget for the written file, -s is its upper bound */
+    bool size_percent;         /* ... given as a percentage of each input file's size */
+    unsigned long long size_value;   /* bytes, or percent */
     bool gpu_read;             /* --gpu-read: inverse filters + expansion to RGBA8 on the device (inflate stays zlib on the decode threads) */
 };
 
@@ -82,6 +86,11 @@ static const char usage_text[] =
     "                    strength search only together with --target-ssim)\n"
     "  --target-ssim X   the strength search with a smallest mean SSIM, above 0 and at most 1; combines\n"
     "                    with --target-psnr and --max-error: every condition given must hold\n"
+    "  --target-size N   pick each file's strength itself: the smallest (at most -s, by halving) whose\n"
+    "                    written file has at most N bytes (suffix k or M: powers of 1024), or P% of\n"
+    "                    the input file's size; implies --gpu-deflate; a budget that -s does not\n"
+    "                    reach writes the file at -s with a warning; not with the other --target\n"
+    "                    switches or --max-error (--ssim has no record in this search)\n"
     "\n"
     "Lossily compresses PNGs by using more compressible colors that are close enough to the\n"
     "original values; the filter+quantise pass runs on the GPU (all files of a call as one batch).\n"
@@ -90,7 +99,7 @@ static const char usage_text[] =
 
 /* ------------------------------------------------------------------------------------------- options */
 
-enum { OPT_EXT = 256, OPT_NO_FORCE, OPT_SKIP_LARGER, OPT_STRIP, OPT_GPU_DEFLATE, OPT_GPU_READ, OPT_DISTORTION, OPT_TARGET_PSNR, OPT_MAX_ERROR, OPT_SSIM, OPT_TARGET_SSIM };
+enum { OPT_EXT = 256, OPT_NO_FORCE, OPT_SKIP_LARGER, OPT_STRIP, OPT_GPU_DEFLATE, OPT_GPU_READ, OPT_DISTORTION, OPT_TARGET_PSNR, OPT_MAX_ERROR, OPT_SSIM, OPT_TARGET_SSIM, OPT_TARGET_SIZE };
 
 static bool parse_number(const char *text, unsigned long *out)
 {
@@ -110,6 +119,23 @@ static bool parse_decibels(const char *text, double *out)
     return true;
 }
 
+/* --target-size: N, Nk, NM (powers of 1024) or P% */
+static bool parse_size(const char *text, unsigned long long *value, bool *percent)
+{
+    if (*text < '0' || *text > '9') return false;
+    char *end;
+    errno = 0;
+    unsigned long long v = strtoull(text, &end, 10);
+    if (errno == ERANGE) return false;
+    *percent = false;
+    if (*end == '%') { *percent = true; end++; }
+    else if (*end == 'k' || *end == 'K') { if (v > (~0ull >> 10)) return false; v <<= 10; end++; }
+    else if (*end == 'M') { if (v > (~0ull >> 20)) return false; v <<= 20; end++; }
+    if (*end) return false;
+    *value = v;
+    return true;
+}
+
 static pngloss_error parse_options(int argc, char **argv, struct options *o)
 {
     static const struct option table[] = {
@@ -126,6 +152,7 @@ static pngloss_error parse_options(int argc, char **argv, struct options *o)
         { "max-error", required_argument, NULL, OPT_MAX_ERROR },
         { "ssim", no_argument, NULL, OPT_SSIM },
         { "target-ssim", required_argument, NULL, OPT_TARGET_SSIM },
+        { "target-size", required_argument, NULL, OPT_TARGET_SIZE },
         { NULL, 0, NULL, 0 },
     };
     for (int c; (c = getopt_long(argc, argv, "vqfo:Vhs:b:", table, NULL)) != -1;) {
@@ -154,6 +181,10 @@ static pngloss_error parse_options(int argc, char **argv, struct options *o)
             if (!parse_decibels(optarg, &o->target_ssim)) { fputs("--target-ssim requires a numeric argument\n", stderr); return INVALID_ARGUMENT; }
             o->have_target = true;
             o->have_target_ssim = true;
+            break;
+        case OPT_TARGET_SIZE:
+            if (!parse_size(optarg, &o->size_value, &o->size_percent)) { fputs("--target-size requires a number of bytes (suffix k or M) or a percentage\n", stderr); return INVALID_ARGUMENT; }
+            o->have_size = true;
             break;
         case 'h': o->help = true; break;
         case 'V': o->version = true; break;
@@ -207,6 +238,8 @@ struct job {
     char *log;                /* buffered stderr text */
     size_t log_len;
     pngloss_hip_result gpu;
+    pngloss_hip_size_report size;        /* --target-size: what the search found for this file */
+    size_t size_budget;                  /* ... and the file's budget in bytes */
     pngloss_hip_target_report target;    /* --target-psnr / --max-error: the strength the search chose for this file */
     pngloss_hip_distortion distortion;   /* --distortion: the optimised pixels against the decoded input's (have_distortion: the library had a record) */
     bool have_distortion;
@@ -398,6 +431,7 @@ static void say_distortion(struct job *j)
 static void say_ssim(struct job *j, const struct options *o)
 {
     const pngloss_hip_ssim *r = &j->ssim;
+    if (!j->have_ssim && o->have_size) { say(j, "  ssim: not measured (the size search keeps no SSIM record)\n"); return; }
     if (!j->have_ssim) { if (o->have_target) say(j, "  ssim: not measured (a strength search measures it only with --target-ssim)\n"); return; }
     if (!r->windows) { say(j, "  ssim: not measured (smaller than one 8x8 window)\n"); return; }
     const unsigned bpp = j->gpu.bytes_per_pixel;
@@ -412,11 +446,15 @@ static void encode_job(struct job *j, const struct options *o)
 {
     if (j->status != SUCCESS) return;
     if (o->verbose && o->have_target) say(j, "  strength %u chosen in %u probes\n", j->target.strength, j->target.probes);
+    if (o->verbose && o->have_size) say(j, "  strength %u chosen in %u probes\n", j->size.strength, j->size.probes);
     if (o->verbose) say(j, "  compression complete\n  used %u unique symbols\n", j->gpu.unique_symbols);
     if (o->skip_if_larger) j->out.maximum_file_size = j->in.file_size - 1;
     j->out.chunks = j->in.chunks;          /* metadata travels to the output */
     j->in.chunks = NULL;
     pngloss_error rc = encode_to(j, &j->out, j->filters, o);
+    /* a budget that was not reached (or is smaller than the container alone): the file was written at -s; one line says so, the exit status stays */
+    if (o->have_size && rc == SUCCESS && (!j->size.reached || j->out.file_size > j->size_budget))
+        say(j, "  warning: %s: budget of %zu bytes not reached, wrote %zu bytes at strength %u\n", j->in_name, j->size_budget, (size_t)j->out.file_size, j->size.strength);
     if (o->distortion && rc == SUCCESS && j->have_distortion) say_distortion(j);
     if (o->ssim && rc == SUCCESS) say_ssim(j, o);
     if (o->verbose) {
@@ -577,8 +615,10 @@ static pngloss_error run_window(struct job *jobs, size_t n, const struct options
     pngloss_hip_result *res = calloc(n ? n : 1, sizeof *res);
     pngloss_hip_target_report *rep = calloc(n ? n : 1, sizeof *rep);
     pngloss_hip_ssim *sm = calloc(n ? n : 1, sizeof *sm);
+    pngloss_hip_size_report *srep = calloc(n ? n : 1, sizeof *srep);
+    uint64_t *budget = calloc(n ? n : 1, sizeof *budget);
     size_t *who = calloc(n ? n : 1, sizeof *who), m = 0;
-    if (!imgs || !lines || !zs || !res || !who || !rep || !sm) { free(imgs); free(lines); free(zs); free(res); free(who); free(rep); free(sm); return OUT_OF_MEMORY_ERROR; }
+    if (!imgs || !lines || !zs || !res || !who || !rep || !sm || !srep || !budget) { free(imgs); free(lines); free(zs); free(res); free(who); free(rep); free(sm); free(srep); free(budget); return OUT_OF_MEMORY_ERROR; }
     for (size_t i = 0; i < n; i++)
         if (jobs[i].status == SUCCESS) {
             imgs[m] = (pngloss_hip_host_image){ jobs[i].out.rgba_data, jobs[i].filters, jobs[i].out.width, jobs[i].out.height };
@@ -621,9 +661,25 @@ static pngloss_error run_window(struct job *jobs, size_t n, const struct options
         if (timing) fprintf(stderr, "  [timing] GPU contexts ready after %.3f s\n", now_s() - tc0);
         /* --target-psnr / --max-error: the library searches a strength per file, -s bounds it; the records come back in the reports */
         /* (--target-ssim: one more condition, and the SSIM records of what was written come back in sm) */
+        /* --target-size: each file's budget for the WRITTEN FILE, turned into the largest zlib stream that fits it (png_stream_writer.c knows the
+         * container); a budget below the container alone can never be met: the library gets a budget of 1 byte, which writes the file at -s */
+        if (o->have_size)
+            for (size_t k = 0; k < m; k++) {
+                struct job *j = &jobs[who[k]];
+                unsigned long long want = o->size_percent ? (unsigned long long)((long double)j->in.file_size * (long double)o->size_value / 100.0L) : o->size_value;
+                if (want < 1) want = 1;
+                j->size_budget = (size_t)want;
+                const png_stream_image si = { j->out.width, j->out.height, 6, NULL, NULL, 0, j->out.gamma,
+                                              j->out.output_color != RWPNG_GAMA_ONLY && j->out.output_color != RWPNG_NONE, j->out.output_color == RWPNG_SRGB,
+                                              j->in.chunks, 0, NULL, 0 };
+                const size_t largest = png_stream_largest_stream(&si, j->size_budget, PNG_STREAM_GPU_IDAT_SLICE);
+                budget[k] = largest ? largest : 1;
+            }
+        const pngloss_hip_size_target size_target = { budget, (uint32_t)o->strength, 0 };
         const pngloss_hip_target target = { o->target_psnr, (uint32_t)o->max_error, (uint32_t)o->strength };
         const pngloss_hip_target2 target2 = { o->target_psnr, (uint32_t)o->max_error, (uint32_t)o->strength, o->target_ssim };
         int rc = !*ctx ? PNGLOSS_HIP_ERROR
+               : o->have_size ? pngloss_hip_multi_optimize_batch_host_size(*ctx, imgs, m, &size_target, (long)o->bleed, res, NULL, zs, srep)
                : o->have_target_ssim ? pngloss_hip_multi_optimize_batch_host_target2(*ctx, imgs, m, &target2, (long)o->bleed, res, o->gpu_deflate ? NULL : lines,
                                                                                      o->gpu_deflate ? zs : NULL, rep, sm)
                : o->have_target ? pngloss_hip_multi_optimize_batch_host_target(*ctx, imgs, m, &target, (long)o->bleed, res, o->gpu_deflate ? NULL : lines,
@@ -634,7 +690,12 @@ static pngloss_error run_window(struct job *jobs, size_t n, const struct options
             jobs[who[k]].gpu = res[k];
             jobs[who[k]].color_type = o->gpu_deflate ? zs[k].color_type : lines[k].color_type;
             jobs[who[k]].zsize = zs[k].size;
-            if (o->have_target) {
+            if (o->have_size) {
+                jobs[who[k]].size = srep[k];
+                jobs[who[k]].distortion = srep[k].distortion;
+                jobs[who[k]].have_distortion = o->distortion && (rc == PNGLOSS_SUCCESS || rc == PNGLOSS_INTERNAL_ABORT);
+                jobs[who[k]].have_ssim = false;
+            } else if (o->have_target) {
                 jobs[who[k]].target = rep[k];
                 jobs[who[k]].distortion = rep[k].distortion;
                 jobs[who[k]].have_distortion = o->distortion && (rc == PNGLOSS_SUCCESS || rc == PNGLOSS_INTERNAL_ABORT);
@@ -653,7 +714,7 @@ static pngloss_error run_window(struct job *jobs, size_t n, const struct options
             }
         }
     }
-    free(imgs); free(lines); free(zs); free(res); free(who); free(rep); free(sm);
+    free(imgs); free(lines); free(zs); free(res); free(who); free(rep); free(sm); free(srep); free(budget);
     const double t2 = now_s();
 
     for_each_job(jobs, n, o, encode_job);
@@ -676,6 +737,9 @@ int main(int argc, char **argv)
     if (o.have_target && !(o.target_psnr >= 0.0)) { fputs("Must specify a PSNR target of 0 dB or more.\n", stderr); return INVALID_ARGUMENT; }
     if (o.have_target_ssim && !(o.target_ssim > 0.0 && o.target_ssim <= 1.0)) { fputs("Must specify an SSIM target above 0 and at most 1.\n", stderr); return INVALID_ARGUMENT; }
     if (o.have_max_error && (o.max_error < 1 || o.max_error > 255)) { fputs("Must specify a largest channel error in the range 1-255.\n", stderr); return INVALID_ARGUMENT; }
+    if (o.have_size && o.have_target) { fputs("--target-size cannot be combined with --target-psnr, --target-ssim or --max-error.\n", stderr); return INVALID_ARGUMENT; }
+    if (o.have_size && o.size_value < 1) { fputs("Must specify a size target of at least 1 byte or 1 percent.\n", stderr); return INVALID_ARGUMENT; }
+    if (o.have_size) o.gpu_deflate = true;          /* the budget is for the file the device deflate writes: zlib-9's size is not what the device measures */
     if (o.bleed < 1 || o.bleed > 32767) { fputs("Must specify a bleed divider in the range 1-32767.\n", stderr); return INVALID_ARGUMENT; }
     if (o.extension && o.output_path) { fputs("--ext and --output options can't be used at the same time\n", stderr); return INVALID_ARGUMENT; }
     if (!o.extension) o.extension = "-loss.png";

@@ -24,4 +24,11 @@ typedef struct {
 size_t pl_deflate_bound(uint32_t width, uint32_t height);     /* capacity that always suffices (4 channels) */
 hipError_t pl_deflate_images(pl_deflate_image *imgs, size_t n, hipStream_t stream);
 
+/* Only HOW LARGE the streams would be: the same match search and the same encoder in its measure-only mode, no output arena, no gather, and one
+ * copy of n records (pl_layout.h: PlSizeRecord) as the only download.  h_out[i].bytes is the out_size pl_deflate_images would report for imgs[i];
+ * imgs[i].out / out_capacity are not looked at and imgs[] is not written.  Same grouping by PL_DEFLATE_MAX_STREAM, same
+ * PNGLOSS_HIP_DEFLATE_GROUP_BYTES test hook.  Synchronous on `stream`. */
+struct PlSizeRecord;
+hipError_t pl_deflate_measure(const pl_deflate_image *imgs, size_t n, PlSizeRecord *h_out, hipStream_t stream);
+
 #endif

@@ -10,6 +10,9 @@
  *   per level:    dfl_keys -> radix sort of (key, position) -> dfl_flags + max-scan -> dfl_match   (all position-parallel)
  *   dfl_encode    one workgroup per deflate block (pl_deflate_coop.h): parse, Huffman codes, bits; byte-aligned outputs
  *   dfl_gather    compacts the block outputs into one buffer per image
+ * or, to learn only how large the streams would be (pl_deflate_measure: the size search of pl_host.hip), after the same search levels:
+ *   dfl_encode    in DFL_MODE_MEASURE: everything but the bits, which are counted; no output arena exists
+ *   dfl_sizes     one wave per image: its blocks' results folded into one PlSizeRecord; one copy of n records is the only download
  *
  * Positions are 32-bit: a call handles at most DFL_MAX_STREAM bytes of scanlines at a time (the caller's images are
  * processed in groups).  Everything is HBM-resident; the only host round trip is the table of block sizes.
@@ -25,6 +28,7 @@
 
 #include "pl_deflate.h"
 #include "pl_deflate_coop.h"
+#include "pl_layout.h"
 
 namespace {
 
@@ -98,7 +102,9 @@ __global__ __launch_bounds__(kThreads) void dfl_match(const uint32_t *sorted, co
     if (m != best || !longer_key_bytes) match[p] = m;
 }
 
-/* one 256-thread workgroup per deflate block: pl_deflate_coop.h; `arena` must be zero (the bits are OR-ed in) */
+/* one 256-thread workgroup per deflate block: pl_deflate_coop.h; DFL_MODE_WRITE: `arena` must be zero (the bits are OR-ed in); DFL_MODE_MEASURE:
+ * there is no arena (nullptr), only `result` is written */
+template <uint32_t MODE>
 __global__ __launch_bounds__(kThreads) void dfl_encode(const dfl_block_desc *desc, const uint8_t *s, const uint32_t *match, const uint32_t *near,
                                                        dfl_params prm, uint32_t *tok, uint32_t *choice, uint8_t *arena,
                                                        dfl_block_result *result)
@@ -106,8 +112,38 @@ __global__ __launch_bounds__(kThreads) void dfl_encode(const dfl_block_desc *des
     __shared__ dfl_coop shared;
     const dfl_block_desc d = desc[blockIdx.x];
     dfl_team team = { threadIdx.x, kThreads, nullptr, nullptr };
-    const dfl_block_result res = dfl_encode_block_coop(&team, s, match, near, &d, &prm, tok + d.begin, choice, arena + d.out_offset, &shared);
+    uint8_t *const out = MODE == DFL_MODE_MEASURE ? nullptr : arena + d.out_offset;
+    const dfl_block_result res = dfl_encode_block_coop_mode(&team, s, match, near, &d, &prm, tok + d.begin, choice, out, &shared, MODE);
     if (threadIdx.x == 0) result[blockIdx.x] = res;
+}
+
+/* one wave per image: the results of its blocks [first_block[i], first_block[i + 1]) folded into record i.  Sizes and kinds are summed over the
+ * lanes; the Adler fold composes in stream order, so lane 0 walks the blocks (at most 4096 of them: 1 GiB in 256 KiB blocks). */
+constexpr uint32_t kSizeLanes = 64;
+static_assert(sizeof(dfl_size_record) == sizeof(PlSizeRecord) && offsetof(dfl_size_record, bytes) == offsetof(PlSizeRecord, bytes) &&
+              offsetof(dfl_size_record, adler) == offsetof(PlSizeRecord, adler) && offsetof(dfl_size_record, kinds) == offsetof(PlSizeRecord, kinds),
+              "dfl_size_record and PlSizeRecord");
+
+__global__ __launch_bounds__(kSizeLanes) void dfl_sizes(const dfl_block_desc *desc, const dfl_block_result *result, const uint32_t *first_block,
+                                                        uint32_t nimg, dfl_size_record *records)
+{
+    const uint32_t i = blockIdx.x;
+    if (i >= nimg) return;
+    const uint32_t first = first_block[i], last = first_block[i + 1];
+    uint64_t bytes;
+    uint32_t kinds[3];
+    dfl_size_partial(result, first, last, threadIdx.x, kSizeLanes, &bytes, kinds);
+    for (int o = kSizeLanes / 2; o > 0; o >>= 1) {
+        bytes += __shfl_xor(bytes, o, kSizeLanes);
+        for (int k = 0; k < 3; k++) kinds[k] += __shfl_xor(kinds[k], o, kSizeLanes);
+    }
+    if (threadIdx.x == 0) {
+        dfl_size_record r;
+        r.bytes = first == last ? 0u : DFL_ZLIB_HEAD_BYTES + bytes + DFL_ZLIB_TAIL_BYTES;      /* an image without blocks gets no stream */
+        r.adler = dfl_size_adler(result, desc, first, last);
+        r.kinds[0] = kinds[0]; r.kinds[1] = kinds[1]; r.kinds[2] = kinds[2];
+        records[i] = r;
+    }
 }
 
 __global__ __launch_bounds__(kThreads) void dfl_gather(const dfl_block_desc *desc, const dfl_block_result *result,
@@ -132,9 +168,13 @@ __global__ __launch_bounds__(kThreads) void dfl_gather(const dfl_block_desc *des
 
 template <class T> hipError_t dev_alloc(T **p, size_t count) { return hipMalloc(reinterpret_cast<void **>(p), count * sizeof(T)); }
 
-/* one group of images whose streams fit 32-bit positions */
-hipError_t deflate_group(pl_deflate_image *imgs, size_t n, const dfl_params &prm, hipStream_t stream)
+/* one group of images whose streams fit 32-bit positions: imgs[] is only read.  Exactly one of the two outputs is given.  written: the streams go
+ * into written[i].out and written[i] gets size and block kinds (pl_deflate_images passes imgs itself).  measured: nothing is written anywhere,
+ * measured[i] says what image i's stream would be. */
+hipError_t deflate_group(const pl_deflate_image *imgs, size_t n, const dfl_params &prm, hipStream_t stream, pl_deflate_image *written, PlSizeRecord *measured)
 {
+    const bool measure = measured != nullptr;
+    if (measure == (written != nullptr)) return hipErrorInvalidValue;
     hipError_t rc = hipSuccess;
     std::vector<dfl_block_desc> desc;
     std::vector<DflImageDev> dev_img(n);
@@ -155,7 +195,8 @@ hipError_t deflate_group(pl_deflate_image *imgs, size_t n, const dfl_params &prm
     }
     first_block[n] = (uint32_t)desc.size();
     const uint32_t nblocks = (uint32_t)desc.size();
-    for (size_t i = 0; i < n; i++) imgs[i].out_size = 0;
+    if (measure) for (size_t i = 0; i < n; i++) measured[i] = PlSizeRecord{ 0, 1, { 0, 0, 0 } };
+    else for (size_t i = 0; i < n; i++) written[i].out_size = 0;
     if (!nblocks) return hipSuccess;
 
     uint8_t *d_s = nullptr, *d_arena = nullptr, *d_compact = nullptr, *d_temp = nullptr;
@@ -169,7 +210,8 @@ hipError_t deflate_group(pl_deflate_image *imgs, size_t n, const dfl_params &prm
     std::vector<dfl_block_result> result(nblocks);
     std::vector<uint32_t> dest(nblocks);
     std::vector<uint32_t> img_off(n + 1, 0), img_begin;
-    uint32_t *d_img_begin = nullptr;
+    uint32_t *d_img_begin = nullptr, *d_first_block = nullptr;
+    dfl_size_record *d_records = nullptr;
     const dim3 pos_grid((max_block + kThreads - 1) / kThreads, nblocks);
 
     const bool debug = std::getenv("PNGLOSS_HIP_DEBUG") != nullptr;
@@ -185,10 +227,14 @@ hipError_t deflate_group(pl_deflate_image *imgs, size_t n, const dfl_params &prm
     DFL_CHECK(dev_alloc(&d_match, total));
     DFL_CHECK(dev_alloc(&d_near, total));
     DFL_CHECK(dev_alloc(&d_tok, total));
-    DFL_CHECK(dev_alloc(&d_arena, arena_bytes));
+    if (!measure) DFL_CHECK(dev_alloc(&d_arena, arena_bytes));
     DFL_CHECK(dev_alloc(&d_desc, nblocks));
     DFL_CHECK(dev_alloc(&d_result, nblocks));
-    DFL_CHECK(dev_alloc(&d_dest, nblocks));
+    if (!measure) DFL_CHECK(dev_alloc(&d_dest, nblocks));
+    if (measure) {
+        DFL_CHECK(dev_alloc(&d_first_block, n + 1));
+        DFL_CHECK(dev_alloc(&d_records, n));
+    }
     DFL_CHECK(dev_alloc(&d_img, n));
     DFL_CHECK(dev_alloc(&d_img_begin, n + 1));
     DFL_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, d_key[0], d_key[1], d_val[0], d_val[1], total, 0, DFL_KEY_BITS, stream));
@@ -218,8 +264,20 @@ hipError_t deflate_group(pl_deflate_image *imgs, size_t n, const dfl_params &prm
         dfl_match<<<(total + kThreads - 1) / kThreads, kThreads, 0, stream>>>(d_val[1], d_gstart, total, d_s, d_img_begin, (uint32_t)n,
                                                                                   dfl_level_chain(prm.max_chain, kLevels[lv]), kLevels[lv], lv ? kLevels[lv - 1] : 0u, d_match);
     }
+    if (measure) {
+        /* the same encoder, counting instead of writing; then the fold per image and ONE small download */
+        DFL_CHECK(hipMemcpyAsync(d_first_block, first_block.data(), sizeof(uint32_t) * (n + 1), hipMemcpyHostToDevice, stream));
+        dfl_encode<DFL_MODE_MEASURE><<<nblocks, kThreads, 0, stream>>>(d_desc, d_s, d_match, d_near, prm, d_tok, d_choice, nullptr, d_result);
+        DFL_CHECK(hipGetLastError());
+        dfl_sizes<<<(uint32_t)n, kSizeLanes, 0, stream>>>(d_desc, d_result, d_first_block, (uint32_t)n, d_records);
+        DFL_CHECK(hipGetLastError());
+        DFL_CHECK(hipMemcpyAsync(measured, d_records, sizeof(PlSizeRecord) * n, hipMemcpyDeviceToHost, stream));
+        DFL_CHECK(hipStreamSynchronize(stream));
+        ms_kernels = ms_since(t_begin) - ms_alloc;
+        goto done;
+    }
     DFL_CHECK(hipMemsetAsync(d_arena, 0, arena_bytes, stream));
-    dfl_encode<<<nblocks, kThreads, 0, stream>>>(d_desc, d_s, d_match, d_near, prm, d_tok, d_choice, d_arena, d_result);
+    dfl_encode<DFL_MODE_WRITE><<<nblocks, kThreads, 0, stream>>>(d_desc, d_s, d_match, d_near, prm, d_tok, d_choice, d_arena, d_result);
     DFL_CHECK(hipGetLastError());
     DFL_CHECK(hipMemcpyAsync(result.data(), d_result, sizeof(dfl_block_result) * nblocks, hipMemcpyDeviceToHost, stream));
     DFL_CHECK(hipStreamSynchronize(stream));
@@ -255,18 +313,18 @@ hipError_t deflate_group(pl_deflate_image *imgs, size_t n, const dfl_params &prm
         }
         unsigned char *t = o + 2 + body;                                   /* the last block carried BFINAL */
         t[0] = (unsigned char)(adler >> 24); t[1] = (unsigned char)(adler >> 16); t[2] = (unsigned char)(adler >> 8); t[3] = (unsigned char)adler;
-        imgs[i].out_size = need;
-        imgs[i].blocks_stored = kinds[0]; imgs[i].blocks_fixed = kinds[1]; imgs[i].blocks_dynamic = kinds[2];
+        written[i].out_size = need;
+        written[i].blocks_stored = kinds[0]; written[i].blocks_fixed = kinds[1]; written[i].blocks_dynamic = kinds[2];
     }
     ms_copy = ms_since(t_begin) - ms_alloc - ms_kernels - ms_gather;
 done:
     (void)hipFree(d_s); (void)hipFree(d_key[0]); (void)hipFree(d_key[1]); (void)hipFree(d_val[0]); (void)hipFree(d_val[1]);
     (void)hipFree(d_choice); (void)hipFree(d_match); (void)hipFree(d_near); (void)hipFree(d_tok); (void)hipFree(d_arena); (void)hipFree(d_desc);
     (void)hipFree(d_result); (void)hipFree(d_dest); (void)hipFree(d_img); (void)hipFree(d_temp); (void)hipFree(d_compact);
-    (void)hipFree(d_img_begin);
+    (void)hipFree(d_img_begin); (void)hipFree(d_first_block); (void)hipFree(d_records);
     if (debug)
-        std::fprintf(stderr, "pngloss_hip deflate: %zu images, %u bytes, %u blocks: alloc %.2f ms, kernels %.2f ms, gather %.2f ms, "
-                             "download %.2f ms, free %.2f ms\n", n, total, nblocks, ms_alloc, ms_kernels, ms_gather, ms_copy,
+        std::fprintf(stderr, "pngloss_hip deflate%s: %zu images, %u bytes, %u blocks: alloc %.2f ms, kernels %.2f ms, gather %.2f ms, "
+                             "download %.2f ms, free %.2f ms\n", measure ? " (measure only)" : "", n, total, nblocks, ms_alloc, ms_kernels, ms_gather, ms_copy,
                      ms_since(t_begin) - ms_alloc - ms_kernels - ms_gather - ms_copy);
     return rc;
 }
@@ -280,7 +338,9 @@ size_t pl_deflate_bound(uint32_t width, uint32_t height)
     return DFL_ZLIB_HEAD_BYTES + DFL_ZLIB_TAIL_BYTES + len + blocks * (5 * (PL_DEFLATE_BLOCK_BYTES / 65535 + 1) + 80);
 }
 
-hipError_t pl_deflate_images(pl_deflate_image *imgs, size_t n, hipStream_t stream)
+namespace {
+/* the images in groups of at most PL_DEFLATE_MAX_STREAM bytes of scanlines: written (into `written`, indexed like imgs) or measured (into `measured`) */
+hipError_t deflate_in_groups(const pl_deflate_image *imgs, size_t n, pl_deflate_image *written, PlSizeRecord *measured, hipStream_t stream)
 {
     dfl_params prm = { PL_DEFLATE_MAX_CHAIN, DFL_KEY_BYTES, PL_DEFLATE_BLOCK_BYTES };
     if (const char *e = std::getenv("PNGLOSS_HIP_DEFLATE_CHAIN")) prm.max_chain = (uint32_t)std::max(1, std::atoi(e));
@@ -298,9 +358,18 @@ hipError_t pl_deflate_images(pl_deflate_image *imgs, size_t n, hipStream_t strea
             bytes += len;
             ++j;
         }
-        const hipError_t rc = deflate_group(imgs + i, j - i, prm, stream);
+        const hipError_t rc = deflate_group(imgs + i, j - i, prm, stream, written ? written + i : nullptr, measured ? measured + i : nullptr);
         if (rc != hipSuccess) return rc;
         i = j;
     }
     return hipSuccess;
+}
+} // namespace
+
+hipError_t pl_deflate_images(pl_deflate_image *imgs, size_t n, hipStream_t stream) { return deflate_in_groups(imgs, n, imgs, nullptr, stream); }
+
+hipError_t pl_deflate_measure(const pl_deflate_image *imgs, size_t n, PlSizeRecord *h_out, hipStream_t stream)
+{
+    if (n && (!imgs || !h_out)) return hipErrorInvalidValue;
+    return deflate_in_groups(imgs, n, nullptr, h_out, stream);
 }

@@ -233,25 +233,18 @@ DFL_HD void dfl_or_finish(dfl_orbits *b)
     if (b->nbits && (uint32_t)b->acc) DFL_OUT_OR(&b->out[b->word], (uint32_t)b->acc);
 }
 
-DFL_HD uint32_t dfl_token_bits(uint32_t tk, const dfl_work *w)
-{
-    if (!DFL_IS_MATCH(tk)) return w->len_ll[tk];
-    uint32_t sym, eb, ex, bits;
-    dfl_len_symbol(DFL_TOK_LEN(tk), &sym, &eb, &ex);
-    bits = w->len_ll[sym] + eb;
-    dfl_dist_symbol(DFL_TOK_DIST(tk), &sym, &eb, &ex);
-    return bits + w->len_d[sym] + eb;
-}
-
 /* ---------------------------------------------------------------------------------------------------------------
  * The block.  All threads of the team call this with the same arguments; `out` must be zero-initialised, 4-byte
  * aligned and dfl_block_bound(L) long; `choice` is per-position scratch (NULL: single parse by length).  The result
  * is returned to every thread.
+ * mode DFL_MODE_MEASURE: everything up to the choice of the block's kind runs as it does for writing; the bits stage keeps its scan of
+ * the runs' bit counts, which gives the block's size, and writes nothing -- `out` is not touched and may be NULL.  The same record comes back.
  * ------------------------------------------------------------------------------------------------------------- */
-DFL_HD dfl_block_result dfl_encode_block_coop(const dfl_team *t, const uint8_t *s, const uint32_t *match, const uint32_t *near,
-                                              const dfl_block_desc *d, const dfl_params *prm, uint32_t *tok,
-                                              uint32_t *choice, uint8_t *out, dfl_coop *sh)
+DFL_HD dfl_block_result dfl_encode_block_coop_mode(const dfl_team *t, const uint8_t *s, const uint32_t *match, const uint32_t *near,
+                                                   const dfl_block_desc *d, const dfl_params *prm, uint32_t *tok,
+                                                   uint32_t *choice, uint8_t *out, dfl_coop *sh, uint32_t mode)
 {
+    const bool measure = mode == DFL_MODE_MEASURE;
     static const uint8_t cl_order[DFL_NUM_CL] = { 16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15 };
     dfl_work *w = &sh->w;
     const uint32_t L = d->end - d->begin;
@@ -363,12 +356,12 @@ DFL_HD dfl_block_result dfl_encode_block_coop(const dfl_team *t, const uint8_t *
 
     if (sh->kind == 0) {
         const uint32_t chunks = L ? (L + 65534u) / 65535u : 1u;
-        for (uint32_t c = t->tid; c < chunks; c += t->nthreads) {
+        for (uint32_t c = t->tid; !measure && c < chunks; c += t->nthreads) {
             const uint32_t off = c * 65535u, len = L - off > 65535u ? 65535u : L - off;
             uint8_t *h = out + (size_t)c * 65540u;
             h[0] = (d->last && c + 1 == chunks) ? 1 : 0; h[1] = (uint8_t)len; h[2] = (uint8_t)(len >> 8); h[3] = (uint8_t)~len; h[4] = (uint8_t)(~len >> 8);
         }
-        for (uint32_t i = t->tid; i < L; i += t->nthreads) out[(size_t)(i / 65535u) * 65540u + 5u + i % 65535u] = s[d->begin + i];
+        for (uint32_t i = t->tid; !measure && i < L; i += t->nthreads) out[(size_t)(i / 65535u) * 65540u + 5u + i % 65535u] = s[d->begin + i];
         if (t->tid == 0) sh->res.bytes = L + 5u * chunks;
         DFL_SYNC(t);
         return sh->res;
@@ -376,7 +369,7 @@ DFL_HD dfl_block_result dfl_encode_block_coop(const dfl_team *t, const uint8_t *
 
     DFL_PROF(6);
     /* header by thread 0, tokens by everyone */
-    if (t->tid == 0) {
+    if (t->tid == 0 && !measure) {
         dfl_orbits bw;
         dfl_or_init(&bw, out, 0);
         if (sh->kind == 1) {
@@ -403,7 +396,7 @@ DFL_HD dfl_block_result dfl_encode_block_coop(const dfl_team *t, const uint8_t *
     for (uint32_t k = k0; k < k1; k++) bits += dfl_token_bits(tok[k], w);
     sh->part[t->tid] = bits;
     dfl_team_scan(t, sh);
-    {
+    if (!measure) {
         dfl_orbits bw;
         dfl_or_init(&bw, out, sh->header_bits + sh->part[t->tid]);
         for (uint32_t k = k0; k < k1; k++) {
@@ -421,7 +414,11 @@ DFL_HD dfl_block_result dfl_encode_block_coop(const dfl_team *t, const uint8_t *
         dfl_or_finish(&bw);
     }
     DFL_PROF(7);
-    if (t->tid == 0) {
+    if (t->tid == 0 && measure) {                                  /* the sizes the writer below arrives at */
+        const uint32_t at = sh->header_bits + sh->part[t->nthreads] + w->len_ll[256];
+        sh->res.bytes = d->last ? (at + 7u) / 8u : (at + 3u + 7u) / 8u + 4u;
+    }
+    if (t->tid == 0 && !measure) {
         dfl_orbits bw;
         uint32_t at = sh->header_bits + sh->part[t->nthreads];
         dfl_or_init(&bw, out, at);
@@ -448,6 +445,13 @@ DFL_HD dfl_block_result dfl_encode_block_coop(const dfl_team *t, const uint8_t *
     }
     DFL_SYNC(t);
     return sh->res;
+}
+
+DFL_HD dfl_block_result dfl_encode_block_coop(const dfl_team *t, const uint8_t *s, const uint32_t *match, const uint32_t *near,
+                                              const dfl_block_desc *d, const dfl_params *prm, uint32_t *tok,
+                                              uint32_t *choice, uint8_t *out, dfl_coop *sh)
+{
+    return dfl_encode_block_coop_mode(t, s, match, near, d, prm, tok, choice, out, sh, DFL_MODE_WRITE);
 }
 
 #endif

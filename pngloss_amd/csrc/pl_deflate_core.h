@@ -74,6 +74,18 @@ typedef struct {
     uint64_t adler_b;        /* sum of (L - i) * byte[i] */
 } dfl_block_result;
 
+/* What an encoder does with the block's bits.  DFL_MODE_MEASURE runs parse, optimal parse, codes and the stored / fixed / dynamic choice exactly as
+ * DFL_MODE_WRITE does and returns the same dfl_block_result, but only totals the bit counts: `out` is never touched (and may be NULL). */
+#define DFL_MODE_WRITE   0u
+#define DFL_MODE_MEASURE 1u
+
+/* the blocks of one image folded into what its zlib stream would be: dfl_sizes (pl_deflate.hip) writes one per image */
+typedef struct {
+    uint64_t bytes;          /* head + blocks + tail; 0 for an image without blocks (it gets no stream) */
+    uint32_t adler;          /* Adler-32 of the image's scanlines */
+    uint32_t kinds[3];       /* blocks stored / fixed / dynamic */
+} dfl_size_record;
+
 /* scratch of one block; lives in LDS on the device */
 typedef struct {
     uint32_t freq_ll[DFL_NUM_LL], freq_d[DFL_NUM_D], freq_cl[DFL_NUM_CL];
@@ -564,12 +576,24 @@ DFL_HD void dfl_canonical(const uint8_t *len, uint32_t n, uint16_t *code)
     for (uint32_t i = 0; i < n; i++) code[i] = len[i] ? (uint16_t)dfl_bitrev(next_code[len[i]]++, len[i]) : 0;
 }
 
+/* bits of one token under the block's final codes */
+DFL_HD uint32_t dfl_token_bits(uint32_t tk, const dfl_work *w)
+{
+    if (!DFL_IS_MATCH(tk)) return w->len_ll[tk];
+    uint32_t sym, eb, ex, bits;
+    dfl_len_symbol(DFL_TOK_LEN(tk), &sym, &eb, &ex);
+    bits = w->len_ll[sym] + eb;
+    dfl_dist_symbol(DFL_TOK_DIST(tk), &sym, &eb, &ex);
+    return bits + w->len_d[sym] + eb;
+}
+
 /* ---------------------------------------------------------------------------------------------------------------
  * 3c. one whole block: parse, code, choose the representation, write.  `out` must be 4-byte aligned, zero-offset for
  * this block, with room for the stored form (input + 5 bytes per 65535 + 16).  Returns the result record.
+ * mode DFL_MODE_MEASURE: the same record, nothing written (the bits stage adds up the tokens' bit counts instead).
  * ------------------------------------------------------------------------------------------------------------- */
-DFL_HD dfl_block_result dfl_encode_block(const uint8_t *s, const uint32_t *match, const uint32_t *near, const dfl_block_desc *d,
-                                         const dfl_params *prm, uint32_t *tok, uint32_t *choice, uint8_t *out, dfl_work *w)
+DFL_HD dfl_block_result dfl_encode_block_mode(const uint8_t *s, const uint32_t *match, const uint32_t *near, const dfl_block_desc *d,
+                                              const dfl_params *prm, uint32_t *tok, uint32_t *choice, uint8_t *out, dfl_work *w, uint32_t mode)
 {
     static const uint8_t cl_order[DFL_NUM_CL] = { 16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15 };
     dfl_block_result res;
@@ -609,7 +633,7 @@ DFL_HD dfl_block_result dfl_encode_block(const uint8_t *s, const uint32_t *match
     for (uint32_t i = 0; i < 30; i++) fixed_bits += (uint64_t)w->freq_d[i] * 5;
 
     /* dynamic: codes, header */
-    uint64_t dyn_bits = 3 + 14 + extra_bits;
+    uint64_t header_bits = 3 + 14;
     uint64_t body = 0;
     dfl_build_code(w->freq_ll, 286, 15, w->len_ll, w->code_ll, w);
     dfl_build_code(w->freq_d, 30, 15, w->len_d, w->code_d, w);
@@ -627,13 +651,13 @@ DFL_HD dfl_block_result dfl_encode_block(const uint8_t *s, const uint32_t *match
     dfl_build_code(w->freq_cl, DFL_NUM_CL, 7, w->len_cl, w->code_cl, w);
     uint32_t hclen = DFL_NUM_CL;
     while (hclen > 4 && !w->len_cl[cl_order[hclen - 1]]) --hclen;
-    dyn_bits += 3ull * hclen;
+    header_bits += 3ull * hclen;
     for (uint32_t i = 0; i < items; i++) {
         const uint32_t sy = w->cl_sym[i];
-        dyn_bits += w->len_cl[sy] + (sy == 16 ? 2u : (sy == 17 ? 3u : (sy == 18 ? 7u : 0u)));
+        header_bits += w->len_cl[sy] + (sy == 16 ? 2u : (sy == 17 ? 3u : (sy == 18 ? 7u : 0u)));
     }
     /* forced symbols were given frequency 1 and are counted in `body`; at most 2+2 codes, harmless over-estimate */
-    dyn_bits += body;
+    const uint64_t dyn_bits = header_bits + extra_bits + body;
 
     const uint32_t chunks = L ? (L + 65534u) / 65535u : 1u;
     const uint64_t stored_bits = 8ull * ((uint64_t)L + 5ull * chunks);
@@ -643,6 +667,7 @@ DFL_HD dfl_block_result dfl_encode_block(const uint8_t *s, const uint32_t *match
     bw.out = out; bw.pos = 0; bw.acc = 0; bw.nbits = 0;
     if (stored_bits <= fixed_bits + sync_bits && stored_bits <= dyn_bits + sync_bits) {
         res.kind = 0;
+        if (mode == DFL_MODE_MEASURE) { res.bytes = L + 5u * chunks; return res; }
         uint32_t off = 0;
         for (uint32_t c = 0; c < chunks; c++) {
             const uint32_t len = L - off > 65535u ? 65535u : L - off;
@@ -655,14 +680,22 @@ DFL_HD dfl_block_result dfl_encode_block(const uint8_t *s, const uint32_t *match
         res.bytes = bw.pos;
         return res;
     }
-    if (fixed_bits <= dyn_bits) {
-        res.kind = 1;
-        dfl_fixed_lengths(w->len_ll, w->len_d);
+    res.kind = fixed_bits <= dyn_bits ? 1u : 2u;
+    if (res.kind == 1) dfl_fixed_lengths(w->len_ll, w->len_d);
+    if (mode == DFL_MODE_MEASURE) {
+        /* the bits the writer below would put, counted: header, tokens, end of block, then the closing of the block */
+        uint64_t bits = res.kind == 1 ? 3u : header_bits;
+        for (uint32_t i = 0; i < ntok; i++) bits += dfl_token_bits(tok[i], w);
+        bits += w->len_ll[256];
+        if (d->last) res.bytes = (uint32_t)((bits + 7u) / 8u);
+        else res.bytes = (uint32_t)((bits + 3u + 7u) / 8u) + 4u;
+        return res;
+    }
+    if (res.kind == 1) {
         dfl_canonical(w->len_ll, DFL_NUM_LL, w->code_ll);
         dfl_canonical(w->len_d, DFL_NUM_D, w->code_d);
         dfl_put(&bw, d->last | (1u << 1), 3);                     /* BFINAL, BTYPE 01 */
     } else {
-        res.kind = 2;
         dfl_put(&bw, d->last | (2u << 1), 3);                     /* BFINAL, BTYPE 10 */
         dfl_put(&bw, hlit - 257u, 5);
         dfl_put(&bw, hdist - 1u, 5);
@@ -701,6 +734,12 @@ DFL_HD dfl_block_result dfl_encode_block(const uint8_t *s, const uint32_t *match
     return res;
 }
 
+DFL_HD dfl_block_result dfl_encode_block(const uint8_t *s, const uint32_t *match, const uint32_t *near, const dfl_block_desc *d,
+                                         const dfl_params *prm, uint32_t *tok, uint32_t *choice, uint8_t *out, dfl_work *w)
+{
+    return dfl_encode_block_mode(s, match, near, d, prm, tok, choice, out, w, DFL_MODE_WRITE);
+}
+
 /* capacity the output of one block needs (stored form is the worst case; the coded forms are only chosen when
  * they are not larger than it, plus slack for the writer's 4-byte granularity) */
 DFL_HD uint32_t dfl_block_bound(uint32_t input_bytes)
@@ -729,6 +768,26 @@ DFL_HD uint32_t dfl_adler_fold(uint32_t adler, uint32_t a, uint64_t b, uint32_t 
     s2 = (s2 + (L % P) * s1 + b % P) % P;
     s1 = (s1 + a % P) % P;
     return (uint32_t)(s2 << 16 | s1);
+}
+
+/* The per-image fold of dfl_sizes, lane `lane` of `nlanes`: sizes and kinds of the blocks [first, last) it owns (every nlanes-th); the caller
+ * adds the lanes up. */
+DFL_HD void dfl_size_partial(const dfl_block_result *res, uint32_t first, uint32_t last, uint32_t lane, uint32_t nlanes,
+                             uint64_t *bytes, uint32_t kinds[3])
+{
+    uint64_t b = 0;
+    uint32_t k[3] = { 0, 0, 0 };
+    for (uint32_t i = first + lane; i < last; i += nlanes) { b += res[i].bytes; k[res[i].kind < 3 ? res[i].kind : 0]++; }
+    *bytes = b;
+    kinds[0] = k[0]; kinds[1] = k[1]; kinds[2] = k[2];
+}
+
+/* ... and the Adler-32 of the image from its blocks' partial sums, in stream order */
+DFL_HD uint32_t dfl_size_adler(const dfl_block_result *res, const dfl_block_desc *desc, uint32_t first, uint32_t last)
+{
+    uint32_t adler = 1;
+    for (uint32_t i = first; i < last; i++) adler = dfl_adler_fold(adler, res[i].adler_a, res[i].adler_b, desc[i].end - desc[i].begin);
+    return adler;
 }
 
 /* zlib framing around the concatenated blocks: 78 DA | blocks (the last one carries BFINAL) | Adler-32 (BE) */

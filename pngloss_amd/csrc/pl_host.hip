@@ -13,6 +13,7 @@
 #include "pl_distort.h"
 #include "pl_ssim.h"
 #include "pl_target.h"
+#include "pl_size.h"
 #include "pl_target_dev.h"
 #define SEG_PLAIN_POINTERS   /* host plumbing only: SegJob is filled here, never dereferenced */
 #include "pl_seg.h"
@@ -1726,6 +1727,399 @@ int pngloss_hip_multi_optimize_batch_host_target2(pngloss_hip_multi *m, const pn
                 if (results) results[mine[k]] = rs[k];
                 if (reports) reports[mine[k]] = rp[k];
                 if (ssim && target->min_ssim != 0.0) ssim[mine[k]] = sm[k];
+                if (scanlines) scanlines[mine[k]] = ln[k];
+                if (streams) streams[mine[k]] = zz[k];
+            }
+        });
+    for (auto &th : pool) th.join();
+    int worst = PNGLOSS_SUCCESS;
+    for (int rc : rcs) if (rc != PNGLOSS_SUCCESS && (worst == PNGLOSS_SUCCESS || worst == PNGLOSS_INTERNAL_ABORT)) worst = rc;
+    return worst;
+}
+
+/* ---- a strength per image from a byte budget: pl_size.h decides, this does what it says (include/pngloss_hip.h has the contract) ---- */
+namespace {
+struct SizeImage {
+    PlSizeSearch search;
+    pngloss_hip_result last{}, kept{};                 /* of the probe just run / of the result the image ends with */
+    uint32_t last_flags = 0, kept_flags = 0;           /* their out-flags words: colour type and bytes per pixel of the scanlines */
+    PlSizeRecord last_size{}, kept_size{};             /* their measured streams */
+    long best = -1;                                    /* the strength whose (accepted) result the arena's stash holds; -1: none */
+    long in_place = -1;                                /* the strength whose result the image itself holds; -1: the original */
+    bool kept_in_stash = false;                        /* the kept result's scanlines are the stash's (else the probe region's) */
+    uint32_t runs = 0;
+};
+
+int deflate_rc(hipError_t e)
+{
+    return e == hipSuccess ? PNGLOSS_SUCCESS : e == hipErrorInvalidValue ? PNGLOSS_INVALID_ARGUMENT : e == hipErrorOutOfMemory ? PNGLOSS_OUT_OF_MEMORY_ERROR : PNGLOSS_HIP_ERROR;
+}
+}
+
+/* images: device-resident; the arena (ctx->d_target) has been grown to lay.total, laid out with a scanline region (and, with `streams`, the best
+ * result's).  commit: at the end every image holds the result of its chosen strength and `streams` (may be nullptr) are written; else the images are
+ * left as the last probes left them (the host form runs the chosen strengths through the host-window path). */
+static int size_search(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n, const PlTargetLayout &lay, const pngloss_hip_size_target &t,
+                       long bleed, hipStream_t stream, bool commit, pngloss_hip_result *results, pngloss_hip_zstream *streams, pngloss_hip_size_report *reports)
+{
+    /* whatever happens: the caller's options back, and no "last batch" to index */
+    struct Guard {
+        pngloss_hip_ctx *c; bool opt, opt_ssim;
+        ~Guard()
+        {
+            c->opt_distortion = opt; c->opt_ssim = opt_ssim; c->n_last = 0; c->h_jobs.clear(); c->distortion.clear(); c->d_records = nullptr;
+            c->ssim.clear(); c->d_ssim_records = nullptr; c->split_last = false;
+        }
+    } guard{ ctx, ctx->opt_distortion, ctx->opt_ssim };
+    ctx->opt_distortion = ctx->opt_ssim = false;       /* the search measures against its own originals */
+    const bool want_streams = commit && streams;
+    char *const arena = ctx->d_target;
+    PlMoveJob *const d_moves = reinterpret_cast<PlMoveJob *>(arena + lay.moves);
+    PlDistortJob *const d_dj = reinterpret_cast<PlDistortJob *>(arena + lay.jobs);
+    PlDistortRecord *const d_rec = reinterpret_cast<PlDistortRecord *>(arena + lay.records);
+    std::vector<SizeImage> st(n);
+    std::vector<PlSizeSearch> searches(n);
+    auto px_bytes = [&](size_t i) { return (uint64_t)images[i].width * images[i].height * 4; };
+    auto filter_bytes = [&](size_t i) { return (uint64_t)((images[i].width && images[i].d_row_filters) ? images[i].height : 0); };
+    auto row_bytes = [&](size_t i) { return (uint64_t)lay.image[i].pitch * images[i].height; };
+    auto id_bytes = [&](size_t i) { return (uint64_t)(lay.image[i].pitch ? images[i].height : 0); };
+    for (size_t i = 0; i < n; i++) st[i].search = pl_size_begin(t.max_strength, px_bytes(i) != 0);
+    auto add = [](std::vector<PlMoveJob> &v, const void *src, void *dst, uint64_t bytes) { if (bytes) v.push_back(PlMoveJob{ src, dst, bytes }); };
+    std::vector<std::vector<PlMoveJob>> move_tables;   /* (the host tables stay alive until the call's last synchronisation: asynchronous copies read them) */
+    auto move = [&](std::vector<PlMoveJob> jobs) -> int {
+        if (jobs.empty()) return PNGLOSS_SUCCESS;
+        uint64_t max_bytes = 0;
+        for (const PlMoveJob &j : jobs) max_bytes = std::max(max_bytes, j.bytes);
+        move_tables.push_back(std::move(jobs));
+        const std::vector<PlMoveJob> &tb = move_tables.back();
+        PL_CHECK(hipMemcpyAsync(d_moves, tb.data(), sizeof(PlMoveJob) * tb.size(), hipMemcpyHostToDevice, stream));
+        PL_CHECK(pl_launch_move(d_moves, tb.size(), max_bytes, stream));
+        return PNGLOSS_SUCCESS;
+    };
+    /* one ordinary batch WITH emit descriptors: the images `who` at `strength`, their scanlines into the arena's probe regions */
+    auto run_group = [&](uint32_t strength, const std::vector<uint32_t> &who) -> int {
+        std::vector<pngloss_hip_image_desc> descs(who.size());
+        std::vector<EmitTarget> emits(who.size());
+        std::vector<pngloss_hip_result> res(who.size());
+        for (size_t k = 0; k < who.size(); k++) {
+            const PlTargetImage &m = lay.image[who[k]];
+            descs[k] = images[who[k]];
+            emits[k] = EmitTarget{ m.pitch ? arena + m.ids : nullptr, m.pitch ? arena + m.rows : nullptr, m.pitch };
+        }
+        ctx->sync_call = true; ctx->three_groups_ok = true;
+        int rc = enqueue(ctx, descs.data(), descs.size(), nullptr, strength, bleed, stream, emits.data());
+        ctx->sync_call = false; ctx->three_groups_ok = false;
+        if (rc == PNGLOSS_SUCCESS) rc = finish(ctx, res.data(), res.size());
+        if (rc != PNGLOSS_SUCCESS && rc != PNGLOSS_INTERNAL_ABORT) return rc;      /* (single images that failed say so in their status) */
+        /* the group's out-flags words (colour type of the scanlines): gathered on the device, ONE copy */
+        std::vector<PlMoveJob> gather;
+        uint32_t *const d_flags = reinterpret_cast<uint32_t *>(arena + lay.flags);
+        for (size_t k = 0; k < who.size(); k++) gather.push_back(PlMoveJob{ ctx->h_jobs[k].out_flags, d_flags + k, sizeof(uint32_t) });
+        std::vector<uint32_t> flags(who.size(), 0);
+        rc = move(std::move(gather));
+        if (rc) return rc;
+        PL_CHECK(hipMemcpyAsync(flags.data(), d_flags, sizeof(uint32_t) * who.size(), hipMemcpyDeviceToHost, stream));
+        PL_CHECK(hipStreamSynchronize(stream));
+        for (size_t k = 0; k < who.size(); k++) {
+            SizeImage &s = st[who[k]];
+            s.last = res[k]; s.in_place = (long)strength; s.runs++;
+            s.last_flags = (res[k].status == 0 && emits[k].pitch) ? flags[k] : 0;
+        }
+        return PNGLOSS_SUCCESS;
+    };
+    /* what the deflate is to look at: image i's scanlines in the probe region or in the stash, in the colour type `flags` says */
+    auto deflate_image = [&](size_t i, bool stash, uint32_t flags) {
+        const PlTargetImage &m = lay.image[i];
+        pl_deflate_image d{};
+        d.d_filter_types = reinterpret_cast<const uint8_t *>(arena + (stash ? m.best_ids : m.ids));
+        d.d_scanlines = reinterpret_cast<const uint8_t *>(arena + (stash ? m.best_rows : m.rows));
+        d.pitch = m.pitch;
+        d.rowbytes = images[i].width * pl_emit_bpp_of(flags);
+        d.height = images[i].height;
+        return d;
+    };
+
+    /* the originals, before the first probe rewrites the images in place */
+    int rc;
+    {
+        std::vector<PlMoveJob> save;
+        for (size_t i = 0; i < n; i++) add(save, images[i].d_rgba, arena + lay.image[i].orig, px_bytes(i));
+        rc = move(std::move(save));
+        if (rc) return rc;
+    }
+    for (;;) {
+        for (size_t i = 0; i < n; i++) searches[i] = st[i].search;
+        const auto groups = pl_size_groups(searches);
+        if (groups.empty()) break;
+        std::vector<PlMoveJob> back, stash;
+        std::vector<uint32_t> probed;
+        for (const auto &g : groups)
+            for (uint32_t i : g.second) {
+                if (st[i].in_place >= 0) add(back, arena + lay.image[i].orig, images[i].d_rgba, px_bytes(i));
+                probed.push_back(i);
+            }
+        rc = move(std::move(back));
+        for (size_t g = 0; g < groups.size() && rc == PNGLOSS_SUCCESS; g++) rc = run_group(groups[g].first, groups[g].second);      /* one after the other: a context takes one batch at a time */
+        if (rc) return rc;
+        /* ONE measuring deflate over every image probed in this round whose run succeeded */
+        std::vector<pl_deflate_image> dz;
+        std::vector<uint32_t> measured;
+        for (uint32_t i : probed)
+            if (st[i].last.status == 0) { dz.push_back(deflate_image(i, false, st[i].last_flags)); measured.push_back(i); }
+        std::vector<PlSizeRecord> sizes(dz.size());
+        if (!dz.empty()) {
+            rc = deflate_rc(pl_deflate_measure(dz.data(), dz.size(), sizes.data(), stream));
+            if (rc) return rc;
+        }
+        for (size_t k = 0; k < measured.size(); k++) st[measured[k]].last_size = sizes[k];
+        for (uint32_t i : probed) {
+            SizeImage &s = st[i];
+            if (s.last.status != 0) {                            /* ends this image's search: it keeps this probe's result and status */
+                pl_size_fail(s.search);
+                s.kept = s.last; s.kept_flags = 0; s.kept_size = PlSizeRecord{ 0, 1, { 0, 0, 0 } }; s.kept_in_stash = false;
+                continue;
+            }
+            const bool accepted = pl_size_accept(s.last.status, s.last_size.bytes, t.max_bytes[i]);
+            const bool first = s.search.first;
+            const uint32_t strength = s.search.next;
+            pl_size_step(s.search, accepted);
+            if (!accepted) {
+                if (first) { s.kept = s.last; s.kept_flags = s.last_flags; s.kept_size = s.last_size; s.kept_in_stash = false; }    /* M does not fit: the image keeps the M result */
+                continue;
+            }
+            /* the accepted probe with the smallest strength so far: every accepted probe lies below the one before it */
+            s.kept = s.last; s.kept_flags = s.last_flags; s.kept_size = s.last_size; s.best = (long)strength; s.kept_in_stash = false;
+            if (s.search.done) continue;                         /* (the chosen strength's result is in place) */
+            add(stash, images[i].d_rgba, arena + lay.image[i].best, px_bytes(i));
+            add(stash, images[i].d_row_filters, arena + lay.image[i].best_filters, filter_bytes(i));
+            if (want_streams) {
+                add(stash, arena + lay.image[i].rows, arena + lay.image[i].best_rows, row_bytes(i));
+                add(stash, arena + lay.image[i].ids, arena + lay.image[i].best_ids, id_bytes(i));
+                s.kept_in_stash = true;
+            }
+        }
+        rc = move(std::move(stash));
+        if (rc) return rc;
+    }
+    /* the kept results back into the images whose last probe was refused */
+    std::vector<PlMoveJob> fin;
+    for (size_t i = 0; i < n; i++) {
+        SizeImage &s = st[i];
+        if (s.search.failed || !px_bytes(i) || s.in_place == (long)s.search.chosen) continue;
+        if (commit) {                                            /* (s.best == chosen: the rule ends on an accepted probe) */
+            add(fin, arena + lay.image[i].best, images[i].d_rgba, px_bytes(i));
+            add(fin, arena + lay.image[i].best_filters, images[i].d_row_filters, filter_bytes(i));
+        }
+    }
+    rc = move(std::move(fin));
+    if (rc) return rc;
+    /* one launch of pl_distort: the kept results against the search's own originals, for the reports */
+    std::vector<pngloss_hip_distortion> recs(n);
+    if (commit && n) {
+        std::vector<PlDistortJob> dj(n);
+        uint64_t max_pixels = 0;
+        for (size_t i = 0; i < n; i++) {
+            dj[i].keep = reinterpret_cast<uint32_t *>(arena + lay.image[i].orig);
+            dj[i].img = static_cast<const uint32_t *>(images[i].d_rgba);
+            dj[i].pixels = (uint64_t)images[i].width * images[i].height;
+            dj[i].record = d_rec + i;
+            max_pixels = std::max(max_pixels, dj[i].pixels);
+        }
+        PL_CHECK(hipMemcpyAsync(d_dj, dj.data(), sizeof(PlDistortJob) * n, hipMemcpyHostToDevice, stream));
+        PL_CHECK(hipMemsetAsync(d_rec, 0, sizeof(PlDistortRecord) * n, stream));
+        PL_CHECK(pl_launch_distort(d_dj, n, max_pixels, stream));
+        PL_CHECK(hipMemcpyAsync(recs.data(), d_rec, sizeof(PlDistortRecord) * n, hipMemcpyDeviceToHost, stream));
+    }
+    PL_CHECK(hipStreamSynchronize(stream));
+    /* one writing deflate over the kept results' scanlines: each stream's size is the measured size of the kept probe */
+    if (want_streams) {
+        std::vector<pl_deflate_image> dz;
+        std::vector<size_t> who;
+        for (size_t i = 0; i < n; i++) {
+            streams[i].size = 0; streams[i].color_type = 6; streams[i].blocks[0] = streams[i].blocks[1] = streams[i].blocks[2] = 0;
+            if (!px_bytes(i) || st[i].kept.status != 0) continue;
+            streams[i].color_type = pl_color_type_of(st[i].kept_flags);
+            pl_deflate_image d = deflate_image(i, st[i].kept_in_stash, st[i].kept_flags);
+            d.out = streams[i].data;
+            d.out_capacity = streams[i].capacity;
+            dz.push_back(d);
+            who.push_back(i);
+        }
+        if (!dz.empty()) {
+            rc = deflate_rc(pl_deflate_images(dz.data(), dz.size(), stream));
+            if (rc) return rc;
+        }
+        for (size_t k = 0; k < dz.size(); k++) {
+            pngloss_hip_zstream &z = streams[who[k]];
+            z.size = dz[k].out_size;
+            z.blocks[0] = dz[k].blocks_stored; z.blocks[1] = dz[k].blocks_fixed; z.blocks[2] = dz[k].blocks_dynamic;
+            if ((uint64_t)z.size != st[who[k]].kept_size.bytes) {
+                std::fprintf(stderr, "pngloss_hip: image %zu: the written stream has %zu bytes, the measured one had %llu\n", who[k], z.size, (unsigned long long)st[who[k]].kept_size.bytes);
+                return PNGLOSS_HIP_ERROR;
+            }
+        }
+    }
+    int worst = PNGLOSS_SUCCESS;
+    for (size_t i = 0; i < n; i++) {
+        const SizeImage &s = st[i];
+        if (results) results[i] = s.kept;
+        if (reports) {
+            pngloss_hip_size_report r{};
+            r.strength = s.search.chosen; r.probes = s.search.probes; r.runs = s.runs; r.reached = s.search.reached;
+            r.bytes = s.kept_size.bytes;
+            r.color_type = pl_color_type_of(s.kept_flags);
+            r.distortion = recs[i];
+            reports[i] = r;
+        }
+        if (s.kept.status) worst = PNGLOSS_INTERNAL_ABORT;
+    }
+    return worst;
+}
+
+static int size_arguments(const pngloss_hip_size_target *target, size_t n, const uint32_t *width, const uint32_t *height, long bleed_divider)
+{
+    const int rc = pl_size_check(target, n, width, height);
+    if (rc) {
+        std::fprintf(stderr, "pngloss_hip: the size target needs max_strength 0..255, a budget above 0 for every image that has pixels, and images of at most 1 GiB of scanlines\n");
+        return rc;
+    }
+    if (bleed_divider < 1 || bleed_divider > 32767) {
+        std::fprintf(stderr, "pngloss_hip: bleed must be 1..32767 (got %ld)\n", bleed_divider);
+        return PNGLOSS_INVALID_ARGUMENT;
+    }
+    return PNGLOSS_SUCCESS;
+}
+
+int pngloss_hip_optimize_batch_size(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n,
+                                    const pngloss_hip_size_target *target, long bleed_divider, void *stream,
+                                    pngloss_hip_result *results, pngloss_hip_zstream *streams, pngloss_hip_size_report *reports)
+{
+    if (n && !images) return PNGLOSS_INVALID_ARGUMENT;
+    std::vector<uint32_t> width(n), height(n);
+    for (size_t i = 0; i < n; i++) { width[i] = images[i].width; height[i] = images[i].height; }
+    int rc = size_arguments(target, n, width.data(), height.data(), bleed_divider);
+    if (rc) return rc;
+    if (!ctx) return PNGLOSS_INVALID_ARGUMENT;
+    if (ctx->pending) {
+        std::fprintf(stderr, "pngloss_hip: previous batch not finished; call pngloss_hip_finish first\n");
+        return PNGLOSS_INVALID_ARGUMENT;
+    }
+    for (size_t i = 0; i < n; i++) {
+        if (!images[i].d_rgba && width[i] && height[i]) return PNGLOSS_INVALID_ARGUMENT;
+        if (streams && width[i] && height[i] && (!streams[i].data || streams[i].capacity < pl_deflate_bound(width[i], height[i]))) return PNGLOSS_INVALID_ARGUMENT;
+    }
+    PL_CHECK(hipSetDevice(ctx->device));
+    /* room for every original, every best result and the scanlines beside the workspace -- or the call fails here, with no image touched */
+    const PlTargetLayout lay = pl_target_layout(width, height, false, sizeof(PlMoveJob), sizeof(PlDistortJob), sizeof(PlDistortRecord), 0, 0,
+                                                streams ? PLT_SCANLINES_PROBE_AND_BEST : PLT_SCANLINES_PROBE);
+    rc = grow(ctx->d_target, ctx->target_bytes, lay.total, 8);
+    if (rc) return rc;
+    return size_search(ctx, images, n, lay, *target, bleed_divider, static_cast<hipStream_t>(stream), true, results, streams, reports);
+}
+
+/* one context's share of pngloss_hip_multi_optimize_batch_host_size */
+static int batch_host_size(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images, size_t n, const pngloss_hip_size_target &target, long bleed_divider,
+                           pngloss_hip_result *results, pngloss_hip_scanlines *lines, pngloss_hip_zstream *zs, pngloss_hip_size_report *reports)
+{
+    if (!ctx || ctx->pending) return PNGLOSS_INVALID_ARGUMENT;
+    PL_CHECK(hipSetDevice(ctx->device));
+    std::vector<uint32_t> width(n), height(n);
+    for (size_t i = 0; i < n; i++) {
+        if (images[i].width && images[i].height && !images[i].rgba) return PNGLOSS_INVALID_ARGUMENT;
+        width[i] = images[i].width; height[i] = images[i].height;
+    }
+    const PlTargetLayout lay = pl_target_layout(width, height, true, sizeof(PlMoveJob), sizeof(PlDistortJob), sizeof(PlDistortRecord), 0, 0, PLT_SCANLINES_PROBE);
+    int rc = grow(ctx->d_target, ctx->target_bytes, lay.total, 8);
+    if (rc) return rc;
+    if (!ctx->copy_stream) PL_CHECK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+    /* copies of the images go up and are searched on; the host images stay as they are until the chosen strengths run below */
+    std::vector<pngloss_hip_image_desc> descs(n);
+    for (size_t i = 0; i < n; i++) {
+        const size_t px = (size_t)width[i] * height[i];
+        descs[i] = pngloss_hip_image_desc{ px ? ctx->d_target + lay.image[i].img : nullptr, (px && images[i].row_filters) ? ctx->d_target + lay.image[i].filters : nullptr, width[i], height[i] };
+        if (px) PL_CHECK(hipMemcpyAsync(descs[i].d_rgba, images[i].rgba, px * 4, hipMemcpyHostToDevice, ctx->copy_stream));
+    }
+    PL_CHECK(hipStreamSynchronize(ctx->copy_stream));
+    std::vector<pngloss_hip_size_report> rep(n ? n : 1);
+    rc = size_search(ctx, descs.data(), n, lay, target, bleed_divider, ctx->copy_stream, false, nullptr, nullptr, rep.data());
+    if (rc != PNGLOSS_SUCCESS && rc != PNGLOSS_INTERNAL_ABORT) return rc;
+    /* the existing host-window path, once per distinct chosen strength; measured, so that every report carries the record of what was written */
+    const bool opt = ctx->opt_distortion, opt_ssim = ctx->opt_ssim;
+    int worst = PNGLOSS_SUCCESS;
+    for (uint32_t strength = 0; strength < 256; strength++) {
+        std::vector<size_t> who;
+        for (size_t i = 0; i < n; i++) if (rep[i].strength == strength) who.push_back(i);
+        if (who.empty()) continue;
+        std::vector<pngloss_hip_host_image> im(who.size());
+        std::vector<pngloss_hip_result> rs(who.size());
+        std::vector<pngloss_hip_scanlines> ln(lines ? who.size() : 0);
+        std::vector<pngloss_hip_zstream> zz(zs ? who.size() : 0);
+        for (size_t k = 0; k < who.size(); k++) {
+            im[k] = images[who[k]];
+            if (lines) ln[k] = lines[who[k]];
+            if (zs) zz[k] = zs[who[k]];
+        }
+        ctx->opt_distortion = true; ctx->opt_ssim = false;
+        rc = batch_host(ctx, im.data(), im.size(), strength, bleed_divider, rs.data(), lines ? ln.data() : nullptr, zs ? zz.data() : nullptr);
+        ctx->opt_distortion = opt; ctx->opt_ssim = opt_ssim;
+        for (size_t k = 0; k < who.size(); k++) {
+            const size_t i = who[k];
+            if (results) results[i] = rs[k];
+            if (lines) lines[i] = ln[k];
+            if (zs) zs[i] = zz[k];
+            if ((size_t)width[i] * height[i]) rep[i].runs++;
+            if (rc == PNGLOSS_SUCCESS || rc == PNGLOSS_INTERNAL_ABORT) (void)pngloss_hip_last_distortion(ctx, k, &rep[i].distortion);
+        }
+        if (rc != PNGLOSS_SUCCESS && (worst == PNGLOSS_SUCCESS || worst == PNGLOSS_INTERNAL_ABORT)) worst = rc;
+    }
+    for (pngloss_hip_ctx *p : ctx->peers) if (p) { p->opt_distortion = opt; p->opt_ssim = opt_ssim; p->n_last = 0; p->distortion.clear(); p->ssim.clear(); }
+    ctx->n_last = 0; ctx->split_last = false; ctx->distortion.clear(); ctx->ssim.clear(); ctx->h_jobs.clear();      /* no single batch to index */
+    if (reports) for (size_t i = 0; i < n; i++) reports[i] = rep[i];
+    return worst;
+}
+
+int pngloss_hip_multi_optimize_batch_host_size(pngloss_hip_multi *m, const pngloss_hip_host_image *images, size_t n,
+                                               const pngloss_hip_size_target *target, long bleed_divider, pngloss_hip_result *results,
+                                               pngloss_hip_scanlines *scanlines, pngloss_hip_zstream *streams,
+                                               pngloss_hip_size_report *reports)
+{
+    if (n && !images) return PNGLOSS_INVALID_ARGUMENT;
+    {
+        std::vector<uint32_t> width(n), height(n);
+        for (size_t i = 0; i < n; i++) { width[i] = images[i].width; height[i] = images[i].height; }
+        const int arc = size_arguments(target, n, width.data(), height.data(), bleed_divider);
+        if (arc) return arc;
+    }
+    if (!m || m->ctx.empty()) return PNGLOSS_INVALID_ARGUMENT;
+    const int parts = (int)m->ctx.size();
+    std::vector<int> owner(n ? n : 1, 0);
+    pngloss_hip_multi_split(images, n, parts, owner.data());
+    m->where.clear();                                   /* (pngloss_hip_multi_last_distortion: the records are in the reports) */
+    std::vector<int> rcs((size_t)parts, PNGLOSS_SUCCESS);
+    std::vector<std::thread> pool;
+    for (int p2 = 0; p2 < parts; p2++)
+        pool.emplace_back([&, p2]() {
+            std::vector<size_t> mine;
+            for (size_t i = 0; i < n; i++) if (owner[i] == p2) mine.push_back(i);
+            if (mine.empty()) return;
+            std::vector<pngloss_hip_host_image> im(mine.size());
+            std::vector<pngloss_hip_result> rs(mine.size());
+            std::vector<pngloss_hip_size_report> rp(mine.size());
+            std::vector<uint64_t> budget(mine.size(), 0);
+            std::vector<pngloss_hip_scanlines> ln(scanlines ? mine.size() : 0);
+            std::vector<pngloss_hip_zstream> zz(streams ? mine.size() : 0);
+            for (size_t k = 0; k < mine.size(); k++) {
+                im[k] = images[mine[k]];
+                if (target->max_bytes) budget[k] = target->max_bytes[mine[k]];
+                if (scanlines) ln[k] = scanlines[mine[k]];
+                if (streams) zz[k] = streams[mine[k]];
+            }
+            const pngloss_hip_size_target mine_t = { budget.data(), target->max_strength, 0 };
+            rcs[(size_t)p2] = batch_host_size(m->ctx[(size_t)p2], im.data(), im.size(), mine_t, bleed_divider, rs.data(),
+                                              scanlines ? ln.data() : nullptr, streams ? zz.data() : nullptr, rp.data());
+            for (size_t k = 0; k < mine.size(); k++) {
+                if (results) results[mine[k]] = rs[k];
+                if (reports) reports[mine[k]] = rp[k];
                 if (scanlines) scanlines[mine[k]] = ln[k];
                 if (streams) streams[mine[k]] = zz[k];
             }

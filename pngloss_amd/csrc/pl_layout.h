@@ -199,6 +199,18 @@ inline PlSsimLayout pl_ssim_layout(size_t n, size_t job_bytes, size_t record_byt
     return l;
 }
 
+/* ================================================================================================ the size measurement (pl_deflate_measure) */
+
+/* One record per image, as dfl_sizes (pl_deflate.hip) leaves it on the device and one copy brings it to the host: what the image's zlib stream
+ * would be, had the deflate written it.  The device side's twin is dfl_size_record (pl_deflate_core.h); pl_deflate.hip pins the two together. */
+struct PlSizeRecord {
+    uint64_t bytes;         /* the complete stream, 78 DA ... Adler-32; 0 for an image without pixels (it gets no stream) */
+    uint32_t adler;         /* Adler-32 of the scanlines */
+    uint32_t kinds[3];      /* deflate blocks stored / fixed / dynamic */
+};
+constexpr size_t PLL_SIZE_RECORD = 24;                 /* sizeof(PlSizeRecord), sizeof(dfl_size_record) */
+static_assert(sizeof(PlSizeRecord) == PLL_SIZE_RECORD, "PlSizeRecord has no padding");
+
 /* ================================================================================================ the read side (png_decode_body) */
 
 constexpr uint64_t PL_READ_NO_STREAM = ~(uint64_t)0;

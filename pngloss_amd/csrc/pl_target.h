@@ -153,29 +153,41 @@ inline std::vector<std::pair<uint32_t, std::vector<uint32_t>>> pl_target_groups(
  * out afresh, which would lose the originals of the images outside the current group).  In front the tables -- the move jobs of one launch (at
  * most three per image: pixels, filters, and pixels of another kind in the last launch), the measuring jobs and their records, with an SSIM
  * condition also the SSIM kernel's jobs and records --, behind them per
- * image its original, the best result so far and that result's row filters; for host images also the image itself and its filters. */
+ * image its original, the best result so far and that result's row filters; for host images also the image itself and its filters.  The size search
+ * (pl_size.h) asks for one more region per image, `scanlines`: the rows pl_emit writes for a probe -- height rows of `pitch` bytes, the pitch
+ * pl_window_layout gives emitted rows (4 * width rounded up to 16: pl_emit stores whole 16-byte groups) -- and the row's filter ids, height
+ * bytes; PLT_SCANLINES_PROBE_AND_BEST adds the same again for the best result so far.  Without it the layout is what it was before the region existed. */
 constexpr size_t PLT_ALIGN = 256;
 constexpr size_t PLT_MOVES_PER_IMAGE = 3;
-struct PlTargetImage { size_t orig = 0, best = 0, best_filters = 0, img = 0, filters = 0; };
+constexpr size_t PLT_SIZE_MOVES_PER_IMAGE = 4;     /* the size search stashes pixels, filters, rows and ids of an accepted probe in one launch */
+constexpr int PLT_SCANLINES_OFF = 0, PLT_SCANLINES_PROBE = 1, PLT_SCANLINES_PROBE_AND_BEST = 2;
+struct PlTargetImage {
+    size_t orig = 0, best = 0, best_filters = 0, img = 0, filters = 0;
+    size_t rows = 0, ids = 0;       /* with `scanlines`: the emitted rows and their filter ids */
+    size_t best_rows = 0, best_ids = 0;     /* PLT_SCANLINES_PROBE_AND_BEST: those of the best result so far (the caller wants its stream written) */
+    uint32_t pitch = 0;             /* ... and the rows' pitch; 0: the image has no pixels, nothing is emitted */
+};
 struct PlTargetLayout {
     size_t moves = 0, jobs = 0, records = 0, total = 0;
     size_t ssim_jobs = 0, ssim_records = 0;        /* the SSIM kernel's job table and records (no bytes when the search has no SSIM condition) */
+    size_t flags = 0;                              /* with `scanlines`: one out-flags word per image, gathered by pl_move so that ONE copy brings a group's to the host */
     std::vector<PlTargetImage> image;
 };
 
 inline PlTargetLayout pl_target_layout(const std::vector<uint32_t> &width, const std::vector<uint32_t> &height, bool host_images,
                                        size_t move_job_bytes, size_t distort_job_bytes, size_t record_bytes,
-                                       size_t ssim_job_bytes = 0, size_t ssim_record_bytes = 0)
+                                       size_t ssim_job_bytes = 0, size_t ssim_record_bytes = 0, int scanlines = PLT_SCANLINES_OFF)
 {
     auto up = [](size_t v) { return (v + PLT_ALIGN - 1) / PLT_ALIGN * PLT_ALIGN; };
     const size_t n = width.size();
     PlTargetLayout lay;
     size_t at = 0;
-    lay.moves = at; at = up(at + move_job_bytes * PLT_MOVES_PER_IMAGE * n);
+    lay.moves = at; at = up(at + move_job_bytes * (scanlines ? PLT_SIZE_MOVES_PER_IMAGE : PLT_MOVES_PER_IMAGE) * n);
     lay.jobs = at; at = up(at + distort_job_bytes * n);
     lay.records = at; at = up(at + record_bytes * n);
     lay.ssim_jobs = at; at = up(at + ssim_job_bytes * n);
     lay.ssim_records = at; at = up(at + ssim_record_bytes * n);
+    if (scanlines) { lay.flags = at; at = up(at + sizeof(uint32_t) * n); }
     lay.image.resize(n);
     for (size_t i = 0; i < n; i++) {
         const size_t px = (size_t)width[i] * height[i] * 4, rows = width[i] ? height[i] : 0;
@@ -186,6 +198,15 @@ inline PlTargetLayout pl_target_layout(const std::vector<uint32_t> &width, const
         if (host_images) {
             m.img = at; at = up(at + px);
             m.filters = at; at = up(at + rows);
+        }
+        if (scanlines) {
+            m.pitch = px ? (uint32_t)(((size_t)width[i] * 4 + 15) / 16 * 16) : 0;
+            m.rows = at; at = up(at + (size_t)m.pitch * height[i]);
+            m.ids = at; at = up(at + (m.pitch ? height[i] : 0));
+            if (scanlines == PLT_SCANLINES_PROBE_AND_BEST) {
+                m.best_rows = at; at = up(at + (size_t)m.pitch * height[i]);
+                m.best_ids = at; at = up(at + (m.pitch ? height[i] : 0));
+            }
         }
     }
     lay.total = at;

@@ -198,6 +198,7 @@ ABI_SYMBOLS = (
     "pngloss_hip_optimize_batch_target", "pngloss_hip_multi_optimize_batch_host_target",
     "pngloss_hip_last_ssim", "pngloss_hip_multi_last_ssim", "pngloss_hip_compare_batch_ssim", "pngloss_hip_ssim_mean",
     "pngloss_hip_optimize_batch_target2", "pngloss_hip_multi_optimize_batch_host_target2",
+    "pngloss_hip_optimize_batch_size", "pngloss_hip_multi_optimize_batch_host_size",
 )
 
 
@@ -282,6 +283,7 @@ def hip_lib():
             lib.pngloss_hip_ssim_mean.argtypes = [C.POINTER(Ssim), C.c_uint]
             lib.pngloss_hip_ssim_mean.restype = C.c_double
             _target_abi(lib)
+            _size_abi(lib)
             _hip = lib
         return _hip
 
@@ -790,3 +792,101 @@ def _run_host_target(self, arrays, target, bleed=2, want_filters=True, emit=None
 
 HipContext.run_target = _run_target
 HipMulti.run_host_target = _run_host_target
+
+
+# ---- a strength per image from a byte budget -----------------------------------------------------------------
+
+class SizeTarget(C.Structure):
+    """pngloss_hip_size_target: max_bytes (one budget per image: the largest allowed zlib stream) and max_strength (M, 0..255: the search never
+    goes above it).  include/pngloss_hip.h states the rule.  max_bytes: a ctypes array of c_uint64, a sequence of ints, or None."""
+    _fields_ = [("max_bytes", C.POINTER(C.c_uint64)), ("max_strength", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def __init__(self, max_bytes=None, max_strength=19):
+        if max_bytes is not None and not isinstance(max_bytes, C.Array):
+            max_bytes = (C.c_uint64 * max(len(max_bytes), 1))(*max_bytes)
+        self._budgets = max_bytes                          # (keeps the array alive)
+        super().__init__(C.cast(max_bytes, C.POINTER(C.c_uint64)) if max_bytes is not None else None, max_strength, 0)
+
+
+class SizeReport(C.Structure):
+    """pngloss_hip_size_report: the chosen strength, the probes of the rule, the row-engine runs spent, whether the budget was reached, the measured
+    stream size and colour type of the result kept, and its Distortion."""
+    _fields_ = [("strength", C.c_uint32), ("probes", C.c_uint32), ("runs", C.c_uint32), ("reached", C.c_uint32), ("bytes", C.c_uint64),
+                ("color_type", C.c_int32), ("reserved", C.c_uint32), ("distortion", Distortion)]
+
+    def as_dict(self):
+        return dict(strength=self.strength, probes=self.probes, runs=self.runs, reached=self.reached, bytes=self.bytes, color_type=self.color_type,
+                    distortion=self.distortion.as_dict())
+
+
+def _size_abi(lib):
+    """the prototypes of the two size entry points (hip_lib sets them once)"""
+    lib.pngloss_hip_optimize_batch_size.argtypes = [C.c_void_p, C.POINTER(ImageDesc), C.c_size_t, C.POINTER(SizeTarget), C.c_long, C.c_void_p, C.POINTER(Result),
+                                                    C.POINTER(ZStream), C.POINTER(SizeReport)]
+    lib.pngloss_hip_optimize_batch_size.restype = C.c_int
+    lib.pngloss_hip_multi_optimize_batch_host_size.argtypes = [C.c_void_p, C.POINTER(HostImage), C.c_size_t, C.POINTER(SizeTarget), C.c_long, C.POINTER(Result),
+                                                               C.POINTER(Scanlines), C.POINTER(ZStream), C.POINTER(SizeReport)]
+    lib.pngloss_hip_multi_optimize_batch_host_size.restype = C.c_int
+    return lib
+
+
+def _run_size(self, images, max_bytes, max_strength=19, bleed=2, stream=0, want_streams=False):
+    """pngloss_hip_optimize_batch_size: images as for run(), max_bytes one budget per image; every image ends up as run() at its chosen strength
+    leaves it.  Synchronous.  Returns (results, reports, streams): the dicts run() returns, one SizeReport per image and -- with want_streams --
+    per image (color_type, zlib stream, blocks), else None."""
+    n = len(images)
+    descs = (ImageDesc * max(n, 1))()
+    for i, (p, f, w, h) in enumerate(images):
+        descs[i] = ImageDesc(p or None, f or None, w, h)
+    res = (Result * max(n, 1))()
+    rep = (SizeReport * max(n, 1))()
+    zs = bufs = None
+    if want_streams:
+        zs = (ZStream * max(n, 1))()
+        bufs = [np.zeros(self._lib.pngloss_hip_zlib_bound(w, h), np.uint8) for (_, _, w, h) in images]
+        for i in range(n):
+            zs[i] = ZStream(bufs[i].ctypes.data, bufs[i].size, 0, -1, (C.c_uint32 * 3)(0, 0, 0), 0)
+    target = SizeTarget(list(max_bytes), max_strength)
+    self._n = 0
+    _check(self._lib.pngloss_hip_optimize_batch_size(self._ctx, descs, n, C.byref(target), bleed, stream or None, res, zs, rep), "optimize_batch_size",
+           partial_ok=True)
+    streams = [(zs[i].color_type, bufs[i][: zs[i].size].tobytes(), tuple(zs[i].blocks)) for i in range(n)] if want_streams else None
+    return [_result_dict(r) for r in res[:n]], [rep[i] for i in range(n)], streams
+
+
+def _run_host_size(self, arrays, max_bytes, max_strength=19, bleed=2, want_filters=True, emit=None):
+    """pngloss_hip_multi_optimize_batch_host_size on a list of (H, W, 4) uint8 arrays.  emit: None, "scanlines", "zlib" or "both".  Returns
+    (outs, filters, results, reports, scanlines, streams): the last two None, or per image what run_host_emit / run_host_zlib return for it."""
+    outs = [np.ascontiguousarray(a).copy() for a in arrays]
+    filts = [np.zeros(a.shape[0], np.uint8) if want_filters else None for a in outs]
+    n = len(outs)
+    imgs = (HostImage * max(n, 1))()
+    for i, (a, f) in enumerate(zip(outs, filts)):
+        imgs[i] = HostImage(a.ctypes.data, f.ctypes.data if f is not None else None, a.shape[1], a.shape[0])
+    if emit not in (None, "scanlines", "zlib", "both"):
+        raise ValueError("emit: None, 'scanlines', 'zlib' or 'both'")
+    lines = zs = None
+    if emit in ("scanlines", "both"):
+        lines = (Scanlines * max(n, 1))()
+        ids = [np.zeros(a.shape[0], np.uint8) for a in outs]
+        rows = [np.zeros((a.shape[0], a.shape[1] * 4), np.uint8) for a in outs]
+        for i, a in enumerate(outs):
+            lines[i] = Scanlines(ids[i].ctypes.data, rows[i].ctypes.data, a.shape[1] * 4, -1)
+    if emit in ("zlib", "both"):
+        zs = (ZStream * max(n, 1))()
+        bufs = [np.zeros(self._lib.pngloss_hip_zlib_bound(a.shape[1], a.shape[0]), np.uint8) for a in outs]
+        for i in range(n):
+            zs[i] = ZStream(bufs[i].ctypes.data, bufs[i].size, 0, -1, (C.c_uint32 * 3)(0, 0, 0), 0)
+    res = (Result * max(n, 1))()
+    rep = (SizeReport * max(n, 1))()
+    target = SizeTarget(list(max_bytes), max_strength)
+    _check(self._lib.pngloss_hip_multi_optimize_batch_host_size(self._m, imgs, n, C.byref(target), bleed, res, lines, zs, rep),
+           "multi_optimize_batch_host_size", partial_ok=True)
+    chans = {0: 1, 4: 2, 2: 3, 6: 4}
+    scan = [(lines[i].color_type, ids[i], rows[i][:, : outs[i].shape[1] * chans.get(lines[i].color_type, 4)].copy()) for i in range(n)] if lines is not None else None
+    streams = [(zs[i].color_type, bufs[i][: zs[i].size].tobytes(), tuple(zs[i].blocks)) for i in range(n)] if zs is not None else None
+    return outs, filts, [dict(status=r.status, bpp=r.bytes_per_pixel, unique_symbols=r.unique_symbols) for r in res[:n]], [rep[i] for i in range(n)], scan, streams
+
+
+HipContext.run_size = _run_size
+HipMulti.run_host_size = _run_host_size
