@@ -637,8 +637,25 @@ PLS_HD int seg_mul24(int a, int b)
 #endif
 }
 PLS_HD bool seg_bad(int acc) { return ((uint32_t)acc >> 11) != 0u; }      /* what seg_step_fast accumulates: did any step leave the split table? */
+/* What a step reads in shared memory, formed ONCE per run of steps (seg_step_mem).  On the device these are LDS byte addresses with the workgroup's
+ * dynamic LDS base already in them -- the compiler does not know that base (it is a symbol the linker fills in) and, given pointers, added it to every
+ * address of every step behind the select and the mask: three instructions a step on the dependent path.  With the base inside the operands of the select
+ * (pre / suf: the two halves of the tables, SEG_TOFF included) and inside the one add that joins it to the offset (cls, lut) no step adds it on its own.
+ * The CPU build keeps plain pointers (and its clamp of the key). */
+#if defined(__HIP_DEVICE_COMPILE__)
+struct SegStepMem { uint32_t pre, suf, cls, lut; };
+PLS_HD SegStepMem seg_step_mem(seg_lds_cu32 tw, seg_lds_cu32 lut)
+{
+    SegStepMem M;
+    M.pre = (uint32_t)tw + 4u * SEG_TOFF; M.suf = M.pre + 8u * SEG_TN; M.cls = (uint32_t)tw + 16u * SEG_TN; M.lut = (uint32_t)lut;
+    return M;
+}
+#else
+struct SegStepMem { seg_lds_cu32 tw; seg_lds_cu8 cls; seg_lds_cu32 lut; };
+PLS_HD SegStepMem seg_step_mem(seg_lds_cu32 tw, seg_lds_cu32 lut) { SegStepMem M; M.tw = tw; M.cls = SEG_LDS_CU8(tw + 4 * SEG_TN); M.lut = lut; return M; }
+#endif
 template <int F, bool TRX>
-PLS_HD uint32_t seg_step_fast(const SegPix &p, SegState &st, int &bad, seg_lds_cu32 tw, seg_lds_cu8 cls, const SegGeo &g, seg_lds_cu32 lut)
+PLS_HD uint32_t seg_step_fast(const SegPix &p, SegState &st, int &bad, const SegStepMem &M, const SegGeo &g)
 {
     /* TRX: the range holds a fully transparent pixel (optimize_state.c:158-164): only then the forced-alpha selects are compiled in.
      * bad accumulates (OR) the split table's offset of every step: seg_bad() tells whether one of them lay outside the table */
@@ -657,12 +674,15 @@ PLS_HD uint32_t seg_step_fast(const SegPix &p, SegState &st, int &bad, seg_lds_c
     const int vd = seg_min(v0, hi);
     const bool usesuf = v0 > bandlo;
     int key = usesuf ? v0 : v1;
-#if !defined(__HIP_DEVICE_COMPILE__)
-    key = seg_min(seg_max(key, -SEG_TOFF), SEG_TOFF - 1);      /* (only a degenerate band can point beyond the tables, and its entry is not used: on the device the read
-                                                                   beyond the workgroup's shared memory returns zero -- one instruction less per step) */
+#if defined(__HIP_DEVICE_COMPILE__)
+    /* (only a degenerate band can point beyond the tables, and its entry is not used: the read beyond the workgroup's shared memory returns zero -- no clamp) */
+    const uint32_t e = *(seg_lds_cu32)((usesuf ? M.suf : M.pre) + (uint32_t)(sgn & (4 * SEG_TN)) + ((uint32_t)key << 2));
+    const uint32_t c_os = (uint32_t)*(seg_lds_cu8)(M.cls + (uint32_t)((osym & 255) | (sgn & 256)));
+#else
+    key = seg_min(seg_max(key, -SEG_TOFF), SEG_TOFF - 1);
+    const uint32_t e = M.tw[(usesuf ? 2 * SEG_TN : 0) + (sgn & SEG_TN) + key + SEG_TOFF];
+    const uint32_t c_os = (uint32_t)M.cls[(osym & 255) | (sgn & 256)];
 #endif
-    const uint32_t e = tw[(usesuf ? 2 * SEG_TN : 0) + (sgn & SEG_TN) + key + SEG_TOFF];
-    const uint32_t c_os = (uint32_t)cls[(osym & 255) | (sgn & 256)];
     const int L = (int)(e & 0xffffu) - 1024;
     const bool tie = osym >= v0 && osym <= v1 && c_os == ((e >> 16) & 255u);
     int v = tie ? osym : L;
@@ -676,7 +696,11 @@ PLS_HD uint32_t seg_step_fast(const SegPix &p, SegState &st, int &bad, seg_lds_c
      * step, says that the lane left the table (seg_bad): one OR per step instead of an absolute value, a subtraction and a maximum */
     const int t4 = (int)((uint32_t)d32 << 2) + 1024;
     bad |= t4;
-    const uint32_t le = *(seg_lds_cu32)((seg_lds_cu8)lut + (t4 & 0x7fc));
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t le = *(seg_lds_cu32)(M.lut + (uint32_t)(t4 & 0x7fc));
+#else
+    const uint32_t le = *(seg_lds_cu32)((seg_lds_cu8)M.lut + (t4 & 0x7fc));
+#endif
     st.left = back; st.cn = seg_sext16((int)le) + st.th; st.th = (int)le >> 16;
     const int diff = seg_sext16(d32);
     return seg_cand_pack(back, diff, bin);
@@ -899,34 +923,59 @@ inline bool seg_build_params(SegParams &P, int strength, int bleed, bool force_s
 #define SEG_SM_CTL ((8 + 512 + (sizeof(SegCtl) + 7) / 8 * 2 + (sizeof(SegAcc) + 7) / 8 * 2 + 56 + SEG_NFILT * (SEG_COMMIT_W + 4) * 4 + SEG_COMMIT_W * 4 + (SEG_NFILT + 1) * 256 + 16) * 4)   /* what a commit workgroup carves out (seg_ctl_commit: split table, control block + sums, decision, five tiles, err1 of both parities, spec): 33.8 KB; a candidate workgroup needs 4 x 256 + SEG_TBL_WORDS words */
 static_assert((1024 + SEG_TBL_WORDS) * 4 <= SEG_SM_CTL, "a candidate workgroup of the control kernel (histograms + table staging) fits the commit workgroups' request");
 
-/* run `n` steps of filter f from pixel record px[0] (stride pstride records per pixel); returns bad > 0 when the lane left the tables */
-template <int F, bool TRX>
-PLS_HD int seg_run_fast(const SegPix *px, int pstride, int n, SegState &st, seg_lds_cu32 tw, seg_lds_cu8 cls, const SegGeo &g, seg_lds_cu32 lut)
+/* bump counters of ONE segment, four bins a word (a segment has at most SEG_L * 4 = 128 decisions: a byte holds its count of any bin) -- a quarter of the
+ * shared memory of a word per bin, which is what lets a CU hold three replay workgroups instead of two */
+PLS_HD void seg_cnt_add(uint32_t *cnt, int bin, uint32_t v) { PLS_ATOMIC_ADD(&cnt[bin >> 2], v << (8 * (bin & 3))); }
+PLS_HD uint32_t seg_cnt_get(const uint32_t *cnt, int bin) { return (cnt[bin >> 2] >> (8 * (bin & 3))) & 255u; }
+static_assert(SEG_L * 4 <= 255, "a segment's bump count of a bin fits a byte");
+/* THE step loop -- of the enumeration's runs (seg_run_fast) and of the walks (seg_walk): `n` steps of filter F from pixel record px[0] (stride pstride records per
+ * pixel), the next record on its way while a step runs.  N > 0: the count is a compile-time value and n is not looked at -- the steps come out as straight-line
+ * code; a count the compiler cannot see through stays a rolled loop (profiles/r08_enum_isa.txt).  out: candidate words (stride 4 words per pixel) or null;
+ * cnt: the segment's bump counters (seg_cnt_add: 64 words) or null.  Returns what seg_step_fast accumulates (seg_bad). */
+template <int F, bool TRX, int N = 0>
+PLS_HD int seg_steps(const SegPix *px, int pstride, int n, SegState &st, const SegStepMem &M, const SegGeo &g, uint32_t *out, uint32_t *cnt)
 {
+    const int nn = N > 0 ? N : n;
     int bad = 0;
+    if (nn <= 0) return 0;
     SegPix p = px[0];
-    for (int k = 0; k < n; k++) {
-        const SegPix pn = px[(k + 1 < n ? k + 1 : k) * pstride];     /* the next record is on its way while this step runs */
-        (void)seg_step_fast<F, TRX>(p, st, bad, tw, cls, g, lut);
+    for (int k = 0; k < nn; k++) {
+        const SegPix pn = px[(size_t)(k + 1 < nn ? k + 1 : k) * pstride];
+        const uint32_t w = seg_step_fast<F, TRX>(p, st, bad, M, g);
+        if (out) out[(size_t)k * 4] = w;
+        if (cnt) seg_cnt_add(cnt, seg_cand_bin(w), 1u);
         p = pn;
     }
-    return seg_bad(bad) ? 1 : 0;
+    return bad;
 }
-template <bool TRX>
-PLS_HD int seg_run_fast_t(int f, const SegPix *px, int pstride, int n, SegState &st, seg_lds_cu32 tw, seg_lds_cu8 cls, const SegGeo &g, seg_lds_cu32 lut)
+/* run `n` (N > 0: N) steps of filter F; returns 1 when the lane left the tables */
+template <int F, bool TRX, int N = 0>
+PLS_HD int seg_run_fast(const SegPix *px, int pstride, int n, SegState &st, seg_lds_cu32 tw, const SegGeo &g, seg_lds_cu32 lut)
+{
+    return seg_bad(seg_steps<F, TRX, N>(px, pstride, n, st, seg_step_mem(tw, lut), g, nullptr, nullptr)) ? 1 : 0;
+}
+template <bool TRX, int N = 0>
+PLS_HD int seg_run_fast_t(int f, const SegPix *px, int pstride, int n, SegState &st, seg_lds_cu32 tw, const SegGeo &g, seg_lds_cu32 lut)
 {
     switch (f) {
-    case 1: return seg_run_fast<1, TRX>(px, pstride, n, st, tw, cls, g, lut);
-    case 2: return seg_run_fast<2, TRX>(px, pstride, n, st, tw, cls, g, lut);
-    case 3: return seg_run_fast<3, TRX>(px, pstride, n, st, tw, cls, g, lut);
-    case 4: return seg_run_fast<4, TRX>(px, pstride, n, st, tw, cls, g, lut);
-    default: return seg_run_fast<0, TRX>(px, pstride, n, st, tw, cls, g, lut);
+    case 1: return seg_run_fast<1, TRX, N>(px, pstride, n, st, tw, g, lut);
+    case 2: return seg_run_fast<2, TRX, N>(px, pstride, n, st, tw, g, lut);
+    case 3: return seg_run_fast<3, TRX, N>(px, pstride, n, st, tw, g, lut);
+    case 4: return seg_run_fast<4, TRX, N>(px, pstride, n, st, tw, g, lut);
+    default: return seg_run_fast<0, TRX, N>(px, pstride, n, st, tw, g, lut);
     }
 }
 /* trx: some pixel of the range is fully transparent (uniform over the workgroup) */
-PLS_HD int seg_run_fast_f(int f, bool trx, const SegPix *px, int pstride, int n, SegState &st, seg_lds_cu32 tw, seg_lds_cu8 cls, const SegGeo &g, seg_lds_cu32 lut)
+PLS_HD int seg_run_fast_f(int f, bool trx, const SegPix *px, int pstride, int n, SegState &st, seg_lds_cu32 tw, const SegGeo &g, seg_lds_cu32 lut)
 {
-    return trx ? seg_run_fast_t<true>(f, px, pstride, n, st, tw, cls, g, lut) : seg_run_fast_t<false>(f, px, pstride, n, st, tw, cls, g, lut);
+    return trx ? seg_run_fast_t<true>(f, px, pstride, n, st, tw, g, lut) : seg_run_fast_t<false>(f, px, pstride, n, st, tw, g, lut);
+}
+/* ... N steps, N a compile-time count */
+template <int N>
+PLS_HD int seg_run_fast_f(int f, bool trx, const SegPix *px, int pstride, SegState &st, seg_lds_cu32 tw, const SegGeo &g, seg_lds_cu32 lut)
+{
+    static_assert(N > 0, "a compile-time count of steps");
+    return trx ? seg_run_fast_t<true, N>(f, px, pstride, N, st, tw, g, lut) : seg_run_fast_t<false, N>(f, px, pstride, N, st, tw, g, lut);
 }
 
 /* ---- ENUMERATE, filters that look at the left pixel: task (f, seg), SEG_THREADS lanes = 4 channels x SEG_NSP states --------
@@ -943,9 +992,12 @@ PLS_HD int seg_run_fast_f(int f, bool trx, const SegPix *px, int pstride, int n,
 #endif
 PLS_HD int seg_k1(int ns) { return ns <= SEG_NSP ? SEG_K1_ONE_CHUNK : SEG_K1; }
 #define SEG_HT 512
-template <int NT>
-PLS_HD void seg_enum_body(const SegJob &j, const SegParams &P, const SegCtlView &cv, int par, int f, int seg, int chalf, unsigned char *smem)
+/* K1 = the steps before the dedupe, a compile-time value: both legs of the first part -- K1 steps from every state, SEG_PL - K1 of the distinct ones -- have
+ * constant counts like the parts behind them (seg_run_fast: N) */
+template <int NT, int K1>
+PLS_HD void seg_enum_body_k(const SegJob &j, const SegParams &P, const SegCtlView &cv, int par, int f, int seg, int chalf, unsigned char *smem)
 {
+    static_assert(K1 > 0 && K1 < SEG_PL, "the dedupe lies inside the first part");
     if (cv.finished || cv.active != 1) return;
     const uint32_t W = j.W, bpp = j.bpp;
     constexpr int NCH = NT / SEG_NSP;                        /* channels of this workgroup: c0 .. c0 + NCH - 1 */
@@ -1001,7 +1053,6 @@ PLS_HD void seg_enum_body(const SegJob &j, const SegParams &P, const SegCtlView 
      *    so only the first lane of a run of equal keys ("head") goes to the hash table with an atomic, the others look their key up
      *    afterwards.  Every entry index gets the DENSE id of its state: that is the segment's entry map -- */
     uint32_t *keys = (uint32_t *)(lslot + NT);       /* [NT] state key of every lane after SEG_K1 steps, ~0 = none */
-    const int K1 = seg_k1(P.ns);
     SEG_AS_GLB uint16_t *dmap = j.maps + (((size_t)f * j.nseg + seg) * 4) * (size_t)P.nsp;
     for (int i0 = 0; i0 < P.ns; i0 += SEG_NSP) {
         PLS_THREADS(tid, NT) {
@@ -1010,7 +1061,7 @@ PLS_HD void seg_enum_body(const SegJob &j, const SegParams &P, const SegCtlView 
             if ((uint32_t)c < bpp && i < P.ns) {
                 SegState st;
                 if (seg_state_decode(P, i, px[c], st)) {
-                    const int bad = seg_run_fast_f(f, trx, px + 4 + c, 4, K1, st, SEG_LDS_CU32(tw), SEG_LDS_CU8(tw + 4 * SEG_TN), G, SEG_LDS_CU32(lut));
+                    const int bad = seg_run_fast_f<K1>(f, trx, px + 4 + c, 4, st, SEG_LDS_CU32(tw), G, SEG_LDS_CU32(lut));
                     if (!bad && st.cn >= -128 && st.cn <= 127) key = (uint32_t)(st.left & 255) | ((uint32_t)(st.cn & 255) << 8) | ((uint32_t)(st.th & 255) << 16);
                 }
             }
@@ -1074,10 +1125,10 @@ PLS_HD void seg_enum_body(const SegJob &j, const SegParams &P, const SegCtlView 
             uint32_t out = SEG_INVALID;
             /* to the end of part 0, then part by part: the state at every cut is a checkpoint the replay starts a lane from */
             const size_t slot = (((size_t)f * j.nseg + seg) * 4 + c) * SEG_NSP + i;
-            int bad = seg_run_fast_f(f, trx, px + (1 + K1) * 4 + c, 4, SEG_PL - K1, st, SEG_LDS_CU32(tw), SEG_LDS_CU8(tw + 4 * SEG_TN), G, SEG_LDS_CU32(lut));
+            int bad = seg_run_fast_f<SEG_PL - K1>(f, trx, px + (1 + K1) * 4 + c, 4, st, SEG_LDS_CU32(tw), G, SEG_LDS_CU32(lut));
             for (int part = 1; part < SEG_PARTS; part++) {
                 j.rck[slot * (SEG_PARTS - 1) + (part - 1)] = bad ? 0xFFFFFFFFu : seg_state_pack(st);
-                bad |= seg_run_fast_f(f, trx, px + (1 + part * SEG_PL) * 4 + c, 4, SEG_PL, st, SEG_LDS_CU32(tw), SEG_LDS_CU8(tw + 4 * SEG_TN), G, SEG_LDS_CU32(lut));
+                bad |= seg_run_fast_f<SEG_PL>(f, trx, px + (1 + part * SEG_PL) * 4 + c, 4, st, SEG_LDS_CU32(tw), G, SEG_LDS_CU32(lut));
             }
             if (!bad) out = seg_state_encode(P, px[SEG_L * 4 + c], st);
             j.rout[slot] = (uint16_t)out;
@@ -1090,6 +1141,17 @@ PLS_HD void seg_enum_body(const SegJob &j, const SegParams &P, const SegCtlView 
             PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_ENUM_STATES], trflag[1] + trflag[2] + trflag[3] + trflag[4]);
         }
     }
+}
+/* the one branch on the count, at the top: the two values that exist (seg_k1), one body where a build gives both the same */
+template <int NT>
+PLS_HD void seg_enum_body(const SegJob &j, const SegParams &P, const SegCtlView &cv, int par, int f, int seg, int chalf, unsigned char *smem)
+{
+#if SEG_K1_ONE_CHUNK == SEG_K1
+    seg_enum_body_k<NT, SEG_K1>(j, P, cv, par, f, seg, chalf, smem);         /* (no branch on P.ns where both counts are the same: it would hold the body twice) */
+#else
+    if (P.ns <= SEG_NSP) seg_enum_body_k<NT, SEG_K1_ONE_CHUNK>(j, P, cv, par, f, seg, chalf, smem);
+    else seg_enum_body_k<NT, SEG_K1>(j, P, cv, par, f, seg, chalf, smem);
+#endif
 }
 
 /* ---- ENUMERATE, SEEDED (state sets beyond SEG_NS_MAX; every filter): task (f, seg), NT lanes = NT / SEG_NSP channels x SEG_NSP seeds ----
@@ -1185,7 +1247,7 @@ PLS_HD void seg_enum_seeded_body(const SegJob &j, const SegParams &P, const SegC
             }
             if (ok) {
                 const int nst = two_stage ? SEG_KA : nrun;
-                const int bad = nst ? seg_run_fast_f(f, trx, px + 4 + c, 4, nst, st, SEG_LDS_CU32(tw), SEG_LDS_CU8(tw + 4 * SEG_TN), G, SEG_LDS_CU32(lut)) : 0;
+                const int bad = nst ? seg_run_fast_f(f, trx, px + 4 + c, 4, nst, st, SEG_LDS_CU32(tw), G, SEG_LDS_CU32(lut)) : 0;
                 if (!bad) key = seg_eh_key(st.left, st.cn, st.th);
             }
         }
@@ -1219,7 +1281,7 @@ PLS_HD void seg_enum_seeded_body(const SegJob &j, const SegParams &P, const SegC
                 const int lc = (uint32_t)tid < DA0 ? 0 : 1, c = c0 + lc;
                 const uint32_t i = lc ? (uint32_t)tid - DA0 : (uint32_t)tid;
                 SegState st = seg_eh_state(uniq[(2 + lc) * SEG_NSP + i]);
-                const int bad = seg_run_fast_f(f, trx, px + (1 + SEG_KA) * 4 + c, 4, nrun - SEG_KA, st, SEG_LDS_CU32(tw), SEG_LDS_CU8(tw + 4 * SEG_TN), G, SEG_LDS_CU32(lut));
+                const int bad = seg_run_fast_f(f, trx, px + (1 + SEG_KA) * 4 + c, 4, nrun - SEG_KA, st, SEG_LDS_CU32(tw), G, SEG_LDS_CU32(lut));
                 if (!bad) key = seg_eh_key(st.left, st.cn, st.th);
             }
             keys[tid] = key;
@@ -1295,7 +1357,7 @@ PLS_HD void seg_enum_seeded_body(const SegJob &j, const SegParams &P, const SegC
             int bad = 0;
             for (int part = 0; part < SEG_PARTS; part++) {
                 if (part) j.rck[slot * (SEG_PARTS - 1) + (part - 1)] = bad ? 0xFFFFFFFFu : seg_state_pack(st);
-                bad |= seg_run_fast_f(f, trx, ps + part * SEG_PL * 4, 4, SEG_PL, st, SEG_LDS_CU32(tw), SEG_LDS_CU8(tw + 4 * SEG_TN), G, SEG_LDS_CU32(lut));
+                bad |= seg_run_fast_f(f, trx, ps + part * SEG_PL * 4, 4, SEG_PL, st, SEG_LDS_CU32(tw), G, SEG_LDS_CU32(lut));
             }
             j.rst[slot] = bad ? 0xFFFFFFFFu : seg_state_pack(st);             /* (rout of a seeded set: the successor's id, written by seg_gather_seeded_body) */
         }
@@ -1354,7 +1416,7 @@ PLS_HD void seg_enum_small_body(const SegJob &j, const SegParams &P, const SegCt
                 int bad = 0;
                 for (int part = 0; part < SEG_PARTS; part++) {
                     if (part) j.rck[slot * (SEG_PARTS - 1) + (part - 1)] = bad ? 0xFFFFFFFFu : seg_state_pack(st);
-                    bad |= seg_run_fast_f(f, trx, px + (sl * SEG_L + part * SEG_PL) * 4 + c, 4, SEG_PL, st, SEG_LDS_CU32(tw), SEG_LDS_CU8(tw + 4 * SEG_TN), G, SEG_LDS_CU32(lut));
+                    bad |= seg_run_fast_f<SEG_PL>(f, trx, px + (sl * SEG_L + part * SEG_PL) * 4 + c, 4, st, SEG_LDS_CU32(tw), G, SEG_LDS_CU32(lut));
                 }
                 if (!bad) out = seg_small_encode(P, st);
             } else {
@@ -1509,7 +1571,7 @@ PLS_HD void seg_enum_unit_body(const SegJob &j, const SegParams &P, const SegCtl
                     else if (i < P.seed_n) {
                         SegState st;
                         if (seg_state_decode(P, (int)P.seed_idx[i], pk[0], st)) {
-                            const int bad = seg_run_fast_f(f, trx1, pk + 1, 1, KR, st, SEG_LDS_CU32(tw), SEG_LDS_CU8(tw + 4 * SEG_TN), G, SEG_LDS_CU32(lut));
+                            const int bad = seg_run_fast_f(f, trx1, pk + 1, 1, KR, st, SEG_LDS_CU32(tw), G, SEG_LDS_CU32(lut));
                             const uint32_t idx = bad ? (uint32_t)SEG_INVALID : seg_state_encode(P, pk[KR], st);
                             if (idx != (uint32_t)SEG_INVALID) key = (uint32_t)(st.left & 255) | ((uint32_t)(st.cn & 255) << 8) | ((uint32_t)(st.th & 255) << 16) | (idx << 24);
                         }
@@ -1560,7 +1622,7 @@ PLS_HD void seg_enum_unit_body(const SegJob &j, const SegParams &P, const SegCtl
                     const SegPix *pk = px1 + (size_t)k * NP1;
                     SegState st;
                     if (seg_any_decode(P, f, i, pk[0], st)) {
-                        const int bad = seg_run_fast_f(f, trx1, pk + 1, 1, K1, st, SEG_LDS_CU32(tw), SEG_LDS_CU8(tw + 4 * SEG_TN), G, SEG_LDS_CU32(lut));
+                        const int bad = seg_run_fast_f(f, trx1, pk + 1, 1, K1, st, SEG_LDS_CU32(tw), G, SEG_LDS_CU32(lut));
                         if (!bad && st.cn >= -128 && st.cn <= 127) key = (uint32_t)(st.left & 255) | ((uint32_t)(st.cn & 255) << 8) | ((uint32_t)(st.th & 255) << 16);
                     }
                 }
@@ -1683,7 +1745,7 @@ PLS_HD void seg_enum_unit_body(const SegJob &j, const SegParams &P, const SegCtl
             for (int part = 0; part < SEG_PARTS; part++) {
                 if (part) j.rck[slot * (SEG_PARTS - 1) + (part - 1)] = bad ? 0xFFFFFFFFu : seg_state_pack(st);
                 const int skip = part == 0 ? K1 : 0;
-                bad |= seg_run_fast_f(f, trx, pk + 1 + part * SEG_PL + skip, 1, SEG_PL - skip, st, SEG_LDS_CU32(tw), SEG_LDS_CU8(tw + 4 * SEG_TN), G, SEG_LDS_CU32(lut));
+                bad |= seg_run_fast_f(f, trx, pk + 1 + part * SEG_PL + skip, 1, SEG_PL - skip, st, SEG_LDS_CU32(tw), G, SEG_LDS_CU32(lut));
             }
             const uint32_t ps0 = bad ? 0xFFFFFFFFu : seg_state_pack(st);
             j.rst[slot] = ps0;
@@ -1757,7 +1819,7 @@ PLS_HD void seg_enum_unit_body(const SegJob &j, const SegParams &P, const SegCtl
                     const size_t slot = (((size_t)f * nseg + sg0 + sl) * 4 + c) * SEG_NSP + i;
                     for (int part = 0; part < SEG_PARTS; part++) {
                         if (part) j.rck[slot * (SEG_PARTS - 1) + (part - 1)] = bad ? 0xFFFFFFFFu : seg_state_pack(st);
-                        bad |= seg_run_fast_f(f, trx, pk + 1 + sl * SEG_L + part * SEG_PL, 1, SEG_PL, st, SEG_LDS_CU32(tw), SEG_LDS_CU8(tw + 4 * SEG_TN), G, SEG_LDS_CU32(lut));
+                        bad |= seg_run_fast_f(f, trx, pk + 1 + sl * SEG_L + part * SEG_PL, 1, SEG_PL, st, SEG_LDS_CU32(tw), G, SEG_LDS_CU32(lut));
                     }
                     j.rst[slot] = bad ? 0xFFFFFFFFu : seg_state_pack(st);
                     SEG_DEBUG_STATE(f, (long)cv.y * 100000 + (long)cq, sl, i, bad ? 0xFFFFFFFFu : seg_state_pack(st));
@@ -1799,11 +1861,6 @@ PLS_HD void seg_load_frozen(const SegJob &j, int par, int f, uint32_t *Hf, uint3
     }
 }
 
-/* bump counters of ONE segment, four bins a word (a segment has at most SEG_L * 4 = 128 decisions: a byte holds its count of any bin) -- a quarter of the
- * shared memory of a word per bin, which is what lets a CU hold three replay workgroups instead of two */
-PLS_HD void seg_cnt_add(uint32_t *cnt, int bin, uint32_t v) { PLS_ATOMIC_ADD(&cnt[bin >> 2], v << (8 * (bin & 3))); }
-PLS_HD uint32_t seg_cnt_get(const uint32_t *cnt, int bin) { return (cnt[bin >> 2] >> (8 * (bin & 3))) & 255u; }
-static_assert(SEG_L * 4 <= 255, "a segment's bump count of a bin fits a byte");
 /* pixels [xa, xe) of one channel from state st: the table steps, and if a lane leaves what the tables cover, once more by scanning.
  * out: candidate words (stride 4 words per pixel) or null; cnt: the segment's bump counters (seg_cnt_add: 64 words) or null. */
 PLS_HD void seg_walk(int f, const SegPix *px, int pstride, uint32_t xa, uint32_t xe, SegState &st, seg_lds_cu32 tw, seg_lds_cu32 lut, const uint32_t *Hf,
@@ -1811,19 +1868,14 @@ PLS_HD void seg_walk(int f, const SegPix *px, int pstride, uint32_t xa, uint32_t
 {
     const SegState st0 = st;
     int bad = 0;
-    const seg_lds_cu8 cls = SEG_LDS_CU8(tw + 4 * SEG_TN);
-    for (uint32_t x = xa; x < xe; x++) {
-        uint32_t w;
-        const SegPix &p = px[(size_t)(x - xa) * pstride];
-        switch (f) {
-        case 1: w = seg_step_fast<1, true>(p, st, bad, tw, cls, G, lut); break;
-        case 2: w = seg_step_fast<2, true>(p, st, bad, tw, cls, G, lut); break;
-        case 3: w = seg_step_fast<3, true>(p, st, bad, tw, cls, G, lut); break;
-        case 4: w = seg_step_fast<4, true>(p, st, bad, tw, cls, G, lut); break;
-        default: w = seg_step_fast<0, true>(p, st, bad, tw, cls, G, lut); break;
-        }
-        if (out) out[(size_t)(x - xa) * 4] = w;
-        if (cnt) seg_cnt_add(cnt, seg_cand_bin(w), 1u);
+    const SegStepMem M = seg_step_mem(tw, lut);
+    const int n = xa < xe ? (int)(xe - xa) : 0;
+    switch (f) {                                     /* (the choice of the filter around the loop, not inside it) */
+    case 1: bad = seg_steps<1, true>(px, pstride, n, st, M, G, out, cnt); break;
+    case 2: bad = seg_steps<2, true>(px, pstride, n, st, M, G, out, cnt); break;
+    case 3: bad = seg_steps<3, true>(px, pstride, n, st, M, G, out, cnt); break;
+    case 4: bad = seg_steps<4, true>(px, pstride, n, st, M, G, out, cnt); break;
+    default: bad = seg_steps<0, true>(px, pstride, n, st, M, G, out, cnt); break;
     }
     if (seg_bad(bad)) {
         /* (rare) take the bumps back and do the range again by scanning */
