@@ -18,6 +18,7 @@
 #define SEG_PLAIN_POINTERS   /* host plumbing only: SegJob is filled here, never dereferenced */
 #include "pl_seg.h"
 #include "pl_plan.h"
+#include "pl_deal.h"
 #include "pl_layout.h"
 
 #include <chrono>
@@ -187,6 +188,55 @@ int grow(char *&p, size_t &have, size_t need, size_t divisor, bool pinned = fals
     return PNGLOSS_SUCCESS;
 }
 int ensure_ws(pngloss_hip_ctx *ctx, size_t bytes) { return grow(ctx->d_ws, ctx->ws_bytes, bytes, 4); }
+
+/* what the device deflate (pl_deflate.h) answers, as a code of the ABI */
+int deflate_rc(hipError_t e)
+{
+    return e == hipSuccess ? PNGLOSS_SUCCESS : e == hipErrorInvalidValue ? PNGLOSS_INVALID_ARGUMENT : e == hipErrorOutOfMemory ? PNGLOSS_OUT_OF_MEMORY_ERROR : PNGLOSS_HIP_ERROR;
+}
+
+/* The context has no "last batch" to index (pngloss_hip_last_*): what enqueue does before every batch.  (The two record pointers are read by finish
+ * alone, for the batch an enqueue has just set them for, and a peer never has split_last set: clearing them is for the searches, and is not seen.) */
+void forget_last_batch(pngloss_hip_ctx *c)
+{
+    c->n_last = 0; c->h_jobs.clear(); c->distortion.clear(); c->d_records = nullptr; c->ssim.clear(); c->d_ssim_records = nullptr; c->split_last = false;
+}
+/* A search runs many batches of its own on the context: whatever happens, the caller's options back, and no "last batch" to index */
+struct SearchGuard {
+    pngloss_hip_ctx *c; bool opt, opt_ssim;
+    ~SearchGuard() { c->opt_distortion = opt; c->opt_ssim = opt_ssim; forget_last_batch(c); }
+};
+
+/* The images `who` of a batch of host images as a batch of their own: images / lines / zs gathered into contiguous vectors (an array the caller
+ * does not have stays empty and is handed on as nullptr), the results owned here; scatter puts results / lines / zs back through the same list.
+ * Further per-image arrays of a call (reports, SSIM records, budgets) are its caller's, with the same list. */
+struct HostSubset {
+    const std::vector<size_t> &who;
+    std::vector<pngloss_hip_host_image> images;
+    std::vector<pngloss_hip_result> results;
+    std::vector<pngloss_hip_scanlines> ln;
+    std::vector<pngloss_hip_zstream> zz;
+    HostSubset(const std::vector<size_t> &who_, const pngloss_hip_host_image *im, const pngloss_hip_scanlines *lines_, const pngloss_hip_zstream *zs_)
+        : who(who_), images(who_.size()), results(who_.size()), ln(lines_ ? who_.size() : 0), zz(zs_ ? who_.size() : 0)
+    {
+        for (size_t k = 0; k < who.size(); k++) {
+            images[k] = im[who[k]];
+            if (lines_) ln[k] = lines_[who[k]];
+            if (zs_) zz[k] = zs_[who[k]];
+        }
+    }
+    size_t n() const { return who.size(); }
+    pngloss_hip_scanlines *lines() { return ln.empty() ? nullptr : ln.data(); }
+    pngloss_hip_zstream *zs() { return zz.empty() ? nullptr : zz.data(); }
+    void scatter(pngloss_hip_result *results_, pngloss_hip_scanlines *lines_, pngloss_hip_zstream *zs_) const
+    {
+        for (size_t k = 0; k < who.size(); k++) {
+            if (results_) results_[who[k]] = results[k];
+            if (lines_) lines_[who[k]] = ln[k];
+            if (zs_) zs_[who[k]] = zz[k];
+        }
+    }
+};
 
 /* The job table of a measurement into the keep arena (which the caller has grown to lay.total), its records zeroed: image i is `pixels[i]` words at img[i],
  * compared with the original at keep[i] -- or, keep == nullptr, with the place the layout gives it in the arena, for pl_keep to fill. */
@@ -1033,10 +1083,7 @@ int window_deflate(const HostWindow &w)
         who.push_back(i);
     }
     if (rc == PNGLOSS_SUCCESS && !dz.empty()) {
-        const hipError_t e = pl_deflate_images(dz.data(), dz.size(), nullptr);
-        if (e == hipErrorInvalidValue) rc = PNGLOSS_INVALID_ARGUMENT;
-        else if (e == hipErrorOutOfMemory) rc = PNGLOSS_OUT_OF_MEMORY_ERROR;
-        else if (e != hipSuccess) rc = PNGLOSS_HIP_ERROR;
+        rc = deflate_rc(pl_deflate_images(dz.data(), dz.size(), nullptr));
         for (size_t k = 0; k < dz.size() && rc == PNGLOSS_SUCCESS; k++) {
             zs[who[k]].size = dz[k].out_size;
             zs[who[k]].blocks[0] = dz[k].blocks_stored; zs[who[k]].blocks[1] = dz[k].blocks_fixed; zs[who[k]].blocks[2] = dz[k].blocks_dynamic;
@@ -1236,12 +1283,7 @@ static int batch_host(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images
         ctx->total_ms = std::max(ctx->total_ms, p->total_ms);
         ctx->upload_ms += p->upload_ms; ctx->download_ms += p->download_ms;
     }
-    bool aborted = false;
-    for (size_t c = 0; c < K; c++) {
-        if (rcs[c] == PNGLOSS_INTERNAL_ABORT) aborted = true;
-        else if (rcs[c] != PNGLOSS_SUCCESS) return rcs[c];
-    }
-    return aborted ? PNGLOSS_INTERNAL_ABORT : PNGLOSS_SUCCESS;
+    return pl_fold_rc(rcs);
 }
 
 int pngloss_hip_optimize_batch_host(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images, size_t n,
@@ -1260,22 +1302,10 @@ struct pngloss_hip_multi {
 
 void pngloss_hip_multi_split(const pngloss_hip_host_image *images, size_t n, int parts, int *owner)
 {
-    /* LPT greedy, deterministic: items by descending pixel count (ties: lower index first), each to the least loaded part
-     * (ties: lower part) -- the same rule as pngloss_amd/shard.py:lpt_partition */
-    if (parts < 1) parts = 1;
-    std::vector<size_t> order(n);
-    for (size_t i = 0; i < n; i++) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) {
-        return (uint64_t)images[a].width * images[a].height > (uint64_t)images[b].width * images[b].height;
-    });
-    std::vector<uint64_t> load((size_t)parts, 0);
-    for (size_t k = 0; k < n; k++) {
-        const size_t i = order[k];
-        int best = 0;
-        for (int p2 = 1; p2 < parts; p2++) if (load[(size_t)p2] < load[(size_t)best]) best = p2;
-        owner[i] = best;
-        load[(size_t)best] += (uint64_t)images[i].width * images[i].height;
-    }
+    std::vector<uint64_t> pixels(n);
+    for (size_t i = 0; i < n; i++) pixels[i] = (uint64_t)images[i].width * images[i].height;
+    const std::vector<int> own = pl_deal_owners(pixels, parts);      /* (the LPT rule: pl_deal.h) */
+    std::copy(own.begin(), own.end(), owner);
 }
 
 pngloss_hip_multi *pngloss_hip_multi_create(const char *devices)
@@ -1323,47 +1353,101 @@ void pngloss_hip_multi_destroy(pngloss_hip_multi *m)
 
 int pngloss_hip_multi_count(const pngloss_hip_multi *m) { return m ? (int)m->ctx.size() : 0; }
 
+extern "C++" {       /* (templates: no C linkage) */
+/* A batch of host images over the contexts of the node, the one shape of every pngloss_hip_multi_optimize_batch_host* call: the split, a host thread per
+ * context that got an image, share(context, its images as a HostSubset) -> code on each, results / scanlines / streams back in input order, the codes folded
+ * (pl_deal.h).  indexes_last: the call leaves a last batch per context that pngloss_hip_multi_last_* index through `where`; else `where` is cleared (the
+ * searches' records are in their reports). */
+template <class Share>
+static int deal_over_contexts(pngloss_hip_multi *m, const pngloss_hip_host_image *images, size_t n, pngloss_hip_result *results,
+                              pngloss_hip_scanlines *scanlines, pngloss_hip_zstream *streams, bool indexes_last, Share share)
+{
+    const int parts = (int)m->ctx.size();
+    std::vector<int> owner(n ? n : 1, 0);
+    pngloss_hip_multi_split(images, n, parts, owner.data());
+    PlDeal deal = pl_deal(owner.data(), n, parts);
+    if (indexes_last) m->where.swap(deal.where);
+    else m->where.clear();
+    std::vector<int> rcs((size_t)parts, PNGLOSS_SUCCESS);
+    std::vector<std::thread> pool;
+    for (size_t p2 = 0; p2 < (size_t)parts; p2++) {
+        if (deal.part[p2].empty()) continue;
+        pool.emplace_back([&, p2]() {
+            HostSubset mine(deal.part[p2], images, scanlines, streams);
+            rcs[p2] = share(m->ctx[p2], mine);
+            mine.scatter(results, scanlines, streams);
+        });
+    }
+    for (auto &th : pool) th.join();
+    return pl_fold_rc(rcs);
+}
+
+/* One context's share of a search on host images, the one shape of both host forms.  Copies of the images go up into the search arena (laid out with the
+ * SSIM tables and the scanline regions its caller names) and search(copies, layout, reports) -> code runs on them without committing; the host images stay as
+ * they are until the chosen strengths run through the host-window path, once per distinct strength (pl_strength_groups) -- measured, so that every report
+ * carries the record of what was written (with want_ssim the SSIM record too, into `ssim` where the caller has one).  Report: .strength, .runs, .distortion.
+ * empty_images_run: the rerun counts in the report of an image without pixels as well. */
+template <class Report, class Search>
+static int batch_host_searched(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images, size_t n, long bleed_divider, pngloss_hip_result *results,
+                               pngloss_hip_scanlines *lines, pngloss_hip_zstream *zs, Report *reports, bool want_ssim, pngloss_hip_ssim *ssim,
+                               int scanlines, bool empty_images_run, Search search)
+{
+    if (!ctx || ctx->pending) return PNGLOSS_INVALID_ARGUMENT;
+    PL_CHECK(hipSetDevice(ctx->device));
+    std::vector<uint32_t> width(n), height(n), chosen(n);
+    for (size_t i = 0; i < n; i++) {
+        if (images[i].width && images[i].height && !images[i].rgba) return PNGLOSS_INVALID_ARGUMENT;
+        width[i] = images[i].width; height[i] = images[i].height;
+    }
+    const PlTargetLayout lay = pl_target_layout(width, height, true, sizeof(PlMoveJob), sizeof(PlDistortJob), sizeof(PlDistortRecord),
+                                                want_ssim ? sizeof(PlSsimJob) : 0, want_ssim ? sizeof(PlSsimRecord) : 0, scanlines);
+    int rc = grow(ctx->d_target, ctx->target_bytes, lay.total, 8);
+    if (rc) return rc;
+    if (!ctx->copy_stream) PL_CHECK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+    std::vector<pngloss_hip_image_desc> descs(n);
+    for (size_t i = 0; i < n; i++) {
+        const size_t px = (size_t)width[i] * height[i];
+        descs[i] = pngloss_hip_image_desc{ px ? ctx->d_target + lay.image[i].img : nullptr, (px && images[i].row_filters) ? ctx->d_target + lay.image[i].filters : nullptr, width[i], height[i] };
+        if (px) PL_CHECK(hipMemcpyAsync(descs[i].d_rgba, images[i].rgba, px * 4, hipMemcpyHostToDevice, ctx->copy_stream));
+    }
+    PL_CHECK(hipStreamSynchronize(ctx->copy_stream));
+    std::vector<Report> rep(n ? n : 1);
+    rc = search(descs.data(), lay, rep.data());
+    if (pl_rc_is_hard(rc)) return rc;
+    for (size_t i = 0; i < n; i++) chosen[i] = rep[i].strength;
+    const bool opt = ctx->opt_distortion, opt_ssim = ctx->opt_ssim;
+    int worst = PNGLOSS_SUCCESS;
+    for (const auto &group : pl_strength_groups(chosen)) {
+        HostSubset sub(group.second, images, lines, zs);
+        ctx->opt_distortion = true; ctx->opt_ssim = want_ssim;
+        rc = batch_host(ctx, sub.images.data(), sub.n(), group.first, bleed_divider, sub.results.data(), sub.lines(), sub.zs());
+        ctx->opt_distortion = opt; ctx->opt_ssim = opt_ssim;
+        sub.scatter(results, lines, zs);
+        for (size_t k = 0; k < sub.n(); k++) {
+            const size_t i = group.second[k];
+            if (empty_images_run || (size_t)width[i] * height[i]) rep[i].runs++;
+            if (pl_rc_is_hard(rc)) continue;
+            (void)pngloss_hip_last_distortion(ctx, k, &rep[i].distortion);
+            if (ssim && want_ssim) (void)pngloss_hip_last_ssim(ctx, k, &ssim[i]);
+        }
+        worst = pl_fold_rc(worst, rc);
+    }
+    /* no single batch to index, here or on the peers the host windows ran their other chunks on */
+    for (pngloss_hip_ctx *p : ctx->peers) if (p) { p->opt_distortion = opt; p->opt_ssim = opt_ssim; forget_last_batch(p); }
+    forget_last_batch(ctx);
+    if (reports) for (size_t i = 0; i < n; i++) reports[i] = rep[i];
+    return worst;
+}
+}
+
 int pngloss_hip_multi_optimize_batch_host(pngloss_hip_multi *m, const pngloss_hip_host_image *images, size_t n,
                                           unsigned quantization_strength, long bleed_divider, pngloss_hip_result *results,
                                           pngloss_hip_scanlines *scanlines, pngloss_hip_zstream *streams)
 {
     if (!m || m->ctx.empty() || (n && !images)) return PNGLOSS_INVALID_ARGUMENT;
-    const int parts = (int)m->ctx.size();
-    std::vector<int> owner(n ? n : 1, 0);
-    pngloss_hip_multi_split(images, n, parts, owner.data());
-    {
-        std::vector<size_t> taken((size_t)parts, 0);
-        m->where.resize(n);
-        for (size_t i = 0; i < n; i++) m->where[i] = std::make_pair(owner[i], taken[(size_t)owner[i]]++);
-    }
-    std::vector<int> rcs((size_t)parts, PNGLOSS_SUCCESS);
-    std::vector<std::thread> pool;
-    for (int p2 = 0; p2 < parts; p2++)
-        pool.emplace_back([&, p2]() {
-            std::vector<size_t> mine;
-            for (size_t i = 0; i < n; i++) if (owner[i] == p2) mine.push_back(i);
-            if (mine.empty()) return;
-            std::vector<pngloss_hip_host_image> im(mine.size());
-            std::vector<pngloss_hip_result> rs(mine.size());
-            std::vector<pngloss_hip_scanlines> ln(scanlines ? mine.size() : 0);
-            std::vector<pngloss_hip_zstream> zz(streams ? mine.size() : 0);
-            for (size_t k = 0; k < mine.size(); k++) {
-                im[k] = images[mine[k]];
-                if (scanlines) ln[k] = scanlines[mine[k]];
-                if (streams) zz[k] = streams[mine[k]];
-            }
-            rcs[(size_t)p2] = batch_host(m->ctx[(size_t)p2], im.data(), im.size(), quantization_strength, bleed_divider, rs.data(),
-                                         scanlines ? ln.data() : nullptr, streams ? zz.data() : nullptr);
-            for (size_t k = 0; k < mine.size(); k++) {
-                if (results) results[mine[k]] = rs[k];
-                if (scanlines) scanlines[mine[k]] = ln[k];
-                if (streams) streams[mine[k]] = zz[k];
-            }
-        });
-    for (auto &th : pool) th.join();
-    int worst = PNGLOSS_SUCCESS;
-    for (int rc : rcs) if (rc != PNGLOSS_SUCCESS && (worst == PNGLOSS_SUCCESS || worst == PNGLOSS_INTERNAL_ABORT)) worst = rc;
-    return worst;
+    return deal_over_contexts(m, images, n, results, scanlines, streams, true, [&](pngloss_hip_ctx *ctx, HostSubset &mine) {
+        return batch_host(ctx, mine.images.data(), mine.n(), quantization_strength, bleed_divider, mine.results.data(), mine.lines(), mine.zs());
+    });
 }
 
 /* ---- a strength per image from a distortion target: pl_target.h decides, this does what it says (include/pngloss_hip.h has the contract) ---- */
@@ -1386,14 +1470,7 @@ static int target_search(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *ima
 {
     const bool want_ssim = t.min_ssim != 0.0;          /* without the condition the SSIM kernel is never launched */
     /* whatever happens: the caller's option back, and no "last batch" to index */
-    struct Guard {
-        pngloss_hip_ctx *c; bool opt, opt_ssim;
-        ~Guard()
-        {
-            c->opt_distortion = opt; c->opt_ssim = opt_ssim; c->n_last = 0; c->h_jobs.clear(); c->distortion.clear(); c->d_records = nullptr;
-            c->ssim.clear(); c->d_ssim_records = nullptr; c->split_last = false;
-        }
-    } guard{ ctx, ctx->opt_distortion, ctx->opt_ssim };
+    SearchGuard guard{ ctx, ctx->opt_distortion, ctx->opt_ssim };
     ctx->opt_distortion = ctx->opt_ssim = false;       /* the search measures against its own originals (the keep arena is laid out afresh by every enqueue) */
     char *const arena = ctx->d_target;
     PlMoveJob *const d_moves = reinterpret_cast<PlMoveJob *>(arena + lay.moves);
@@ -1615,70 +1692,15 @@ int pngloss_hip_optimize_batch_target2(pngloss_hip_ctx *ctx, const pngloss_hip_i
     return target_search(ctx, images, n, lay, *target, bleed_divider, static_cast<hipStream_t>(stream), true, results, reports, ssim);
 }
 
-/* one context's share of pngloss_hip_multi_optimize_batch_host_target */
+/* one context's share of pngloss_hip_multi_optimize_batch_host_target: the rerun of the chosen strength counts for every image */
 static int batch_host_target(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images, size_t n, const pngloss_hip_target2 &target, long bleed_divider,
                              pngloss_hip_result *results, pngloss_hip_scanlines *lines, pngloss_hip_zstream *zs, pngloss_hip_target_report *reports,
                              pngloss_hip_ssim *ssim)
 {
-    const bool want_ssim = target.min_ssim != 0.0;
-    if (!ctx || ctx->pending) return PNGLOSS_INVALID_ARGUMENT;
-    PL_CHECK(hipSetDevice(ctx->device));
-    std::vector<uint32_t> width(n), height(n);
-    for (size_t i = 0; i < n; i++) {
-        if (images[i].width && images[i].height && !images[i].rgba) return PNGLOSS_INVALID_ARGUMENT;
-        width[i] = images[i].width; height[i] = images[i].height;
-    }
-    const PlTargetLayout lay = pl_target_layout(width, height, true, sizeof(PlMoveJob), sizeof(PlDistortJob), sizeof(PlDistortRecord),
-                                                want_ssim ? sizeof(PlSsimJob) : 0, want_ssim ? sizeof(PlSsimRecord) : 0);
-    int rc = grow(ctx->d_target, ctx->target_bytes, lay.total, 8);
-    if (rc) return rc;
-    if (!ctx->copy_stream) PL_CHECK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-    /* copies of the images go up and are searched on; the host images stay as they are until the chosen strengths run below */
-    std::vector<pngloss_hip_image_desc> descs(n);
-    for (size_t i = 0; i < n; i++) {
-        const size_t px = (size_t)width[i] * height[i];
-        descs[i] = pngloss_hip_image_desc{ px ? ctx->d_target + lay.image[i].img : nullptr, (px && images[i].row_filters) ? ctx->d_target + lay.image[i].filters : nullptr, width[i], height[i] };
-        if (px) PL_CHECK(hipMemcpyAsync(descs[i].d_rgba, images[i].rgba, px * 4, hipMemcpyHostToDevice, ctx->copy_stream));
-    }
-    PL_CHECK(hipStreamSynchronize(ctx->copy_stream));
-    std::vector<pngloss_hip_target_report> rep(n ? n : 1);
-    rc = target_search(ctx, descs.data(), n, lay, target, bleed_divider, ctx->copy_stream, false, nullptr, rep.data(), nullptr);
-    if (rc != PNGLOSS_SUCCESS && rc != PNGLOSS_INTERNAL_ABORT) return rc;
-    /* the existing host-window path, once per distinct chosen strength; measured, so that every report carries the record of what was written
-     * (the SSIM record too, but only for a search with an SSIM condition) */
-    const bool opt = ctx->opt_distortion, opt_ssim = ctx->opt_ssim;
-    int worst = PNGLOSS_SUCCESS;
-    for (uint32_t strength = 0; strength < 256; strength++) {
-        std::vector<size_t> who;
-        for (size_t i = 0; i < n; i++) if (rep[i].strength == strength) who.push_back(i);
-        if (who.empty()) continue;
-        std::vector<pngloss_hip_host_image> im(who.size());
-        std::vector<pngloss_hip_result> rs(who.size());
-        std::vector<pngloss_hip_scanlines> ln(lines ? who.size() : 0);
-        std::vector<pngloss_hip_zstream> zz(zs ? who.size() : 0);
-        for (size_t k = 0; k < who.size(); k++) {
-            im[k] = images[who[k]];
-            if (lines) ln[k] = lines[who[k]];
-            if (zs) zz[k] = zs[who[k]];
-        }
-        ctx->opt_distortion = true; ctx->opt_ssim = want_ssim;
-        rc = batch_host(ctx, im.data(), im.size(), strength, bleed_divider, rs.data(), lines ? ln.data() : nullptr, zs ? zz.data() : nullptr);
-        ctx->opt_distortion = opt; ctx->opt_ssim = opt_ssim;
-        for (size_t k = 0; k < who.size(); k++) {
-            const size_t i = who[k];
-            if (results) results[i] = rs[k];
-            if (lines) lines[i] = ln[k];
-            if (zs) zs[i] = zz[k];
-            rep[i].runs++;
-            if (rc == PNGLOSS_SUCCESS || rc == PNGLOSS_INTERNAL_ABORT) (void)pngloss_hip_last_distortion(ctx, k, &rep[i].distortion);
-            if (ssim && want_ssim && (rc == PNGLOSS_SUCCESS || rc == PNGLOSS_INTERNAL_ABORT)) (void)pngloss_hip_last_ssim(ctx, k, &ssim[i]);
-        }
-        if (rc != PNGLOSS_SUCCESS && (worst == PNGLOSS_SUCCESS || worst == PNGLOSS_INTERNAL_ABORT)) worst = rc;
-    }
-    for (pngloss_hip_ctx *p : ctx->peers) if (p) { p->opt_distortion = opt; p->opt_ssim = opt_ssim; p->n_last = 0; p->distortion.clear(); p->ssim.clear(); }
-    ctx->n_last = 0; ctx->split_last = false; ctx->distortion.clear(); ctx->ssim.clear(); ctx->h_jobs.clear();      /* no single batch to index */
-    if (reports) for (size_t i = 0; i < n; i++) reports[i] = rep[i];
-    return worst;
+    return batch_host_searched(ctx, images, n, bleed_divider, results, lines, zs, reports, target.min_ssim != 0.0, ssim, PLT_SCANLINES_OFF, true,
+                               [&](const pngloss_hip_image_desc *copies, const PlTargetLayout &lay, pngloss_hip_target_report *rep) {
+                                   return target_search(ctx, copies, n, lay, target, bleed_divider, ctx->copy_stream, false, nullptr, rep, nullptr);
+                               });
 }
 
 int pngloss_hip_multi_optimize_batch_host_target(pngloss_hip_multi *m, const pngloss_hip_host_image *images, size_t n,
@@ -1699,42 +1721,16 @@ int pngloss_hip_multi_optimize_batch_host_target2(pngloss_hip_multi *m, const pn
     const int arc = target_arguments(target, bleed_divider);
     if (arc) return arc;
     if (!m || m->ctx.empty() || (n && !images)) return PNGLOSS_INVALID_ARGUMENT;
-    const int parts = (int)m->ctx.size();
-    std::vector<int> owner(n ? n : 1, 0);
-    pngloss_hip_multi_split(images, n, parts, owner.data());
-    m->where.clear();                                   /* (pngloss_hip_multi_last_distortion: the records are in the reports) */
-    std::vector<int> rcs((size_t)parts, PNGLOSS_SUCCESS);
-    std::vector<std::thread> pool;
-    for (int p2 = 0; p2 < parts; p2++)
-        pool.emplace_back([&, p2]() {
-            std::vector<size_t> mine;
-            for (size_t i = 0; i < n; i++) if (owner[i] == p2) mine.push_back(i);
-            if (mine.empty()) return;
-            std::vector<pngloss_hip_host_image> im(mine.size());
-            std::vector<pngloss_hip_result> rs(mine.size());
-            std::vector<pngloss_hip_target_report> rp(mine.size());
-            std::vector<pngloss_hip_ssim> sm(mine.size());
-            std::vector<pngloss_hip_scanlines> ln(scanlines ? mine.size() : 0);
-            std::vector<pngloss_hip_zstream> zz(streams ? mine.size() : 0);
-            for (size_t k = 0; k < mine.size(); k++) {
-                im[k] = images[mine[k]];
-                if (scanlines) ln[k] = scanlines[mine[k]];
-                if (streams) zz[k] = streams[mine[k]];
-            }
-            rcs[(size_t)p2] = batch_host_target(m->ctx[(size_t)p2], im.data(), im.size(), *target, bleed_divider, rs.data(),
-                                                scanlines ? ln.data() : nullptr, streams ? zz.data() : nullptr, rp.data(), sm.data());
-            for (size_t k = 0; k < mine.size(); k++) {
-                if (results) results[mine[k]] = rs[k];
-                if (reports) reports[mine[k]] = rp[k];
-                if (ssim && target->min_ssim != 0.0) ssim[mine[k]] = sm[k];
-                if (scanlines) scanlines[mine[k]] = ln[k];
-                if (streams) streams[mine[k]] = zz[k];
-            }
-        });
-    for (auto &th : pool) th.join();
-    int worst = PNGLOSS_SUCCESS;
-    for (int rc : rcs) if (rc != PNGLOSS_SUCCESS && (worst == PNGLOSS_SUCCESS || worst == PNGLOSS_INTERNAL_ABORT)) worst = rc;
-    return worst;
+    return deal_over_contexts(m, images, n, results, scanlines, streams, false, [&](pngloss_hip_ctx *ctx, HostSubset &mine) {
+        std::vector<pngloss_hip_target_report> rp(mine.n());
+        std::vector<pngloss_hip_ssim> sm(mine.n());
+        const int rc = batch_host_target(ctx, mine.images.data(), mine.n(), *target, bleed_divider, mine.results.data(), mine.lines(), mine.zs(), rp.data(), sm.data());
+        for (size_t k = 0; k < mine.n(); k++) {
+            if (reports) reports[mine.who[k]] = rp[k];
+            if (ssim && target->min_ssim != 0.0) ssim[mine.who[k]] = sm[k];
+        }
+        return rc;
+    });
 }
 
 /* ---- a strength per image from a byte budget: pl_size.h decides, this does what it says (include/pngloss_hip.h has the contract) ---- */
@@ -1749,11 +1745,6 @@ struct SizeImage {
     bool kept_in_stash = false;                        /* the kept result's scanlines are the stash's (else the probe region's) */
     uint32_t runs = 0;
 };
-
-int deflate_rc(hipError_t e)
-{
-    return e == hipSuccess ? PNGLOSS_SUCCESS : e == hipErrorInvalidValue ? PNGLOSS_INVALID_ARGUMENT : e == hipErrorOutOfMemory ? PNGLOSS_OUT_OF_MEMORY_ERROR : PNGLOSS_HIP_ERROR;
-}
 }
 
 /* images: device-resident; the arena (ctx->d_target) has been grown to lay.total, laid out with a scanline region (and, with `streams`, the best
@@ -1763,14 +1754,7 @@ static int size_search(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *image
                        long bleed, hipStream_t stream, bool commit, pngloss_hip_result *results, pngloss_hip_zstream *streams, pngloss_hip_size_report *reports)
 {
     /* whatever happens: the caller's options back, and no "last batch" to index */
-    struct Guard {
-        pngloss_hip_ctx *c; bool opt, opt_ssim;
-        ~Guard()
-        {
-            c->opt_distortion = opt; c->opt_ssim = opt_ssim; c->n_last = 0; c->h_jobs.clear(); c->distortion.clear(); c->d_records = nullptr;
-            c->ssim.clear(); c->d_ssim_records = nullptr; c->split_last = false;
-        }
-    } guard{ ctx, ctx->opt_distortion, ctx->opt_ssim };
+    SearchGuard guard{ ctx, ctx->opt_distortion, ctx->opt_ssim };
     ctx->opt_distortion = ctx->opt_ssim = false;       /* the search measures against its own originals */
     const bool want_streams = commit && streams;
     char *const arena = ctx->d_target;
@@ -2017,65 +2001,15 @@ int pngloss_hip_optimize_batch_size(pngloss_hip_ctx *ctx, const pngloss_hip_imag
     return size_search(ctx, images, n, lay, *target, bleed_divider, static_cast<hipStream_t>(stream), true, results, streams, reports);
 }
 
-/* one context's share of pngloss_hip_multi_optimize_batch_host_size */
+/* one context's share of pngloss_hip_multi_optimize_batch_host_size: no SSIM, scanline regions for the probes, and the rerun of the chosen strength counts
+ * only for an image that has pixels (one without ends with 0 runs) */
 static int batch_host_size(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images, size_t n, const pngloss_hip_size_target &target, long bleed_divider,
                            pngloss_hip_result *results, pngloss_hip_scanlines *lines, pngloss_hip_zstream *zs, pngloss_hip_size_report *reports)
 {
-    if (!ctx || ctx->pending) return PNGLOSS_INVALID_ARGUMENT;
-    PL_CHECK(hipSetDevice(ctx->device));
-    std::vector<uint32_t> width(n), height(n);
-    for (size_t i = 0; i < n; i++) {
-        if (images[i].width && images[i].height && !images[i].rgba) return PNGLOSS_INVALID_ARGUMENT;
-        width[i] = images[i].width; height[i] = images[i].height;
-    }
-    const PlTargetLayout lay = pl_target_layout(width, height, true, sizeof(PlMoveJob), sizeof(PlDistortJob), sizeof(PlDistortRecord), 0, 0, PLT_SCANLINES_PROBE);
-    int rc = grow(ctx->d_target, ctx->target_bytes, lay.total, 8);
-    if (rc) return rc;
-    if (!ctx->copy_stream) PL_CHECK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-    /* copies of the images go up and are searched on; the host images stay as they are until the chosen strengths run below */
-    std::vector<pngloss_hip_image_desc> descs(n);
-    for (size_t i = 0; i < n; i++) {
-        const size_t px = (size_t)width[i] * height[i];
-        descs[i] = pngloss_hip_image_desc{ px ? ctx->d_target + lay.image[i].img : nullptr, (px && images[i].row_filters) ? ctx->d_target + lay.image[i].filters : nullptr, width[i], height[i] };
-        if (px) PL_CHECK(hipMemcpyAsync(descs[i].d_rgba, images[i].rgba, px * 4, hipMemcpyHostToDevice, ctx->copy_stream));
-    }
-    PL_CHECK(hipStreamSynchronize(ctx->copy_stream));
-    std::vector<pngloss_hip_size_report> rep(n ? n : 1);
-    rc = size_search(ctx, descs.data(), n, lay, target, bleed_divider, ctx->copy_stream, false, nullptr, nullptr, rep.data());
-    if (rc != PNGLOSS_SUCCESS && rc != PNGLOSS_INTERNAL_ABORT) return rc;
-    /* the existing host-window path, once per distinct chosen strength; measured, so that every report carries the record of what was written */
-    const bool opt = ctx->opt_distortion, opt_ssim = ctx->opt_ssim;
-    int worst = PNGLOSS_SUCCESS;
-    for (uint32_t strength = 0; strength < 256; strength++) {
-        std::vector<size_t> who;
-        for (size_t i = 0; i < n; i++) if (rep[i].strength == strength) who.push_back(i);
-        if (who.empty()) continue;
-        std::vector<pngloss_hip_host_image> im(who.size());
-        std::vector<pngloss_hip_result> rs(who.size());
-        std::vector<pngloss_hip_scanlines> ln(lines ? who.size() : 0);
-        std::vector<pngloss_hip_zstream> zz(zs ? who.size() : 0);
-        for (size_t k = 0; k < who.size(); k++) {
-            im[k] = images[who[k]];
-            if (lines) ln[k] = lines[who[k]];
-            if (zs) zz[k] = zs[who[k]];
-        }
-        ctx->opt_distortion = true; ctx->opt_ssim = false;
-        rc = batch_host(ctx, im.data(), im.size(), strength, bleed_divider, rs.data(), lines ? ln.data() : nullptr, zs ? zz.data() : nullptr);
-        ctx->opt_distortion = opt; ctx->opt_ssim = opt_ssim;
-        for (size_t k = 0; k < who.size(); k++) {
-            const size_t i = who[k];
-            if (results) results[i] = rs[k];
-            if (lines) lines[i] = ln[k];
-            if (zs) zs[i] = zz[k];
-            if ((size_t)width[i] * height[i]) rep[i].runs++;
-            if (rc == PNGLOSS_SUCCESS || rc == PNGLOSS_INTERNAL_ABORT) (void)pngloss_hip_last_distortion(ctx, k, &rep[i].distortion);
-        }
-        if (rc != PNGLOSS_SUCCESS && (worst == PNGLOSS_SUCCESS || worst == PNGLOSS_INTERNAL_ABORT)) worst = rc;
-    }
-    for (pngloss_hip_ctx *p : ctx->peers) if (p) { p->opt_distortion = opt; p->opt_ssim = opt_ssim; p->n_last = 0; p->distortion.clear(); p->ssim.clear(); }
-    ctx->n_last = 0; ctx->split_last = false; ctx->distortion.clear(); ctx->ssim.clear(); ctx->h_jobs.clear();      /* no single batch to index */
-    if (reports) for (size_t i = 0; i < n; i++) reports[i] = rep[i];
-    return worst;
+    return batch_host_searched(ctx, images, n, bleed_divider, results, lines, zs, reports, false, nullptr, PLT_SCANLINES_PROBE, false,
+                               [&](const pngloss_hip_image_desc *copies, const PlTargetLayout &lay, pngloss_hip_size_report *rep) {
+                                   return size_search(ctx, copies, n, lay, target, bleed_divider, ctx->copy_stream, false, nullptr, nullptr, rep);
+                               });
 }
 
 int pngloss_hip_multi_optimize_batch_host_size(pngloss_hip_multi *m, const pngloss_hip_host_image *images, size_t n,
@@ -2091,43 +2025,15 @@ int pngloss_hip_multi_optimize_batch_host_size(pngloss_hip_multi *m, const pnglo
         if (arc) return arc;
     }
     if (!m || m->ctx.empty()) return PNGLOSS_INVALID_ARGUMENT;
-    const int parts = (int)m->ctx.size();
-    std::vector<int> owner(n ? n : 1, 0);
-    pngloss_hip_multi_split(images, n, parts, owner.data());
-    m->where.clear();                                   /* (pngloss_hip_multi_last_distortion: the records are in the reports) */
-    std::vector<int> rcs((size_t)parts, PNGLOSS_SUCCESS);
-    std::vector<std::thread> pool;
-    for (int p2 = 0; p2 < parts; p2++)
-        pool.emplace_back([&, p2]() {
-            std::vector<size_t> mine;
-            for (size_t i = 0; i < n; i++) if (owner[i] == p2) mine.push_back(i);
-            if (mine.empty()) return;
-            std::vector<pngloss_hip_host_image> im(mine.size());
-            std::vector<pngloss_hip_result> rs(mine.size());
-            std::vector<pngloss_hip_size_report> rp(mine.size());
-            std::vector<uint64_t> budget(mine.size(), 0);
-            std::vector<pngloss_hip_scanlines> ln(scanlines ? mine.size() : 0);
-            std::vector<pngloss_hip_zstream> zz(streams ? mine.size() : 0);
-            for (size_t k = 0; k < mine.size(); k++) {
-                im[k] = images[mine[k]];
-                if (target->max_bytes) budget[k] = target->max_bytes[mine[k]];
-                if (scanlines) ln[k] = scanlines[mine[k]];
-                if (streams) zz[k] = streams[mine[k]];
-            }
-            const pngloss_hip_size_target mine_t = { budget.data(), target->max_strength, 0 };
-            rcs[(size_t)p2] = batch_host_size(m->ctx[(size_t)p2], im.data(), im.size(), mine_t, bleed_divider, rs.data(),
-                                              scanlines ? ln.data() : nullptr, streams ? zz.data() : nullptr, rp.data());
-            for (size_t k = 0; k < mine.size(); k++) {
-                if (results) results[mine[k]] = rs[k];
-                if (reports) reports[mine[k]] = rp[k];
-                if (scanlines) scanlines[mine[k]] = ln[k];
-                if (streams) streams[mine[k]] = zz[k];
-            }
-        });
-    for (auto &th : pool) th.join();
-    int worst = PNGLOSS_SUCCESS;
-    for (int rc : rcs) if (rc != PNGLOSS_SUCCESS && (worst == PNGLOSS_SUCCESS || worst == PNGLOSS_INTERNAL_ABORT)) worst = rc;
-    return worst;
+    return deal_over_contexts(m, images, n, results, scanlines, streams, false, [&](pngloss_hip_ctx *ctx, HostSubset &mine) {
+        std::vector<pngloss_hip_size_report> rp(mine.n());
+        std::vector<uint64_t> budget(mine.n(), 0);
+        for (size_t k = 0; k < mine.n(); k++) if (target->max_bytes) budget[k] = target->max_bytes[mine.who[k]];
+        const pngloss_hip_size_target mine_t = { budget.data(), target->max_strength, 0 };
+        const int rc = batch_host_size(ctx, mine.images.data(), mine.n(), mine_t, bleed_divider, mine.results.data(), mine.lines(), mine.zs(), rp.data());
+        for (size_t k = 0; k < mine.n(); k++) if (reports) reports[mine.who[k]] = rp[k];
+        return rc;
+    });
 }
 
 int pngloss_hip_optimize_batch_host_emit(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images, size_t n,

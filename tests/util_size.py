@@ -81,6 +81,11 @@ def build_size_host(tmp_path):
     return _build(tmp_path, "size_host")
 
 
+def build_deal_host(tmp_path):
+    """tests/c/deal_host.cpp with -fsanitize=address,undefined; returns the executable"""
+    return _build(tmp_path, "deal_host")
+
+
 def build_deflate_measure_host(tmp_path):
     """tests/c/deflate_measure_host.cpp with -fsanitize=address,undefined; returns the executable"""
     return _build(tmp_path, "deflate_measure_host", ["-lpthread"])
