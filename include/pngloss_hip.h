@@ -306,6 +306,30 @@ int pngloss_hip_compare_batch_ssim(pngloss_hip_ctx *ctx, const pngloss_hip_image
  * pngloss_hip_psnr_db (0x2, 0xA, 0x7, 0xF for bytes_per_pixel 1, 2, 3, 4). */
 double pngloss_hip_ssim_mean(const pngloss_hip_ssim *r, unsigned channel_mask);
 
+/* ---- Measuring over visible pixels (no reference equivalent).  The two records above treat RGBA8 as four equal channels over width * height pixels.
+ * A pixel whose alpha is 0 in the original and in the result cannot be seen, yet it counts in the denominators and almost always adds no error: on
+ * images with transparent areas PSNR and mean SSIM come out better than what a viewer sees.  The option "measure" at "visible"
+ * (pngloss_hip_set_option; "all" is the default and is what is described above) changes what the measuring kernels of "distortion" and "ssim" count
+ * and what the target searches below accept or refuse on; it changes no pixel, filter ID, scanline or stream.  Definitions, all integers:
+ *   pm(p), the premultiplied pixel: alpha as it is; each of R, G, B becomes the integer nearest to c * A / 255, (c * A + 127) / 255 with floor
+ *     division (255 is odd: never a tie; at most 255).
+ *   A pixel is VISIBLE when its alpha is non-zero in the original or in the result.
+ *   pngloss_hip_distortion in visible mode: pixels = the number of visible pixels; changed_pixels = pixels with pm(a) != pm(b) as words; sq_err[c]
+ *     and max_abs[c] taken on pm(a) and pm(b) (channel 3 is plain alpha).  An invisible pixel adds 0 to every sum.
+ *   pngloss_hip_ssim in visible mode: the window arithmetic above on pm(a) and pm(b); a window counts only if at least one of its 64 pixels is
+ *     visible; windows = the number of counted windows; the others add nothing to sum_q16 and do not lower min_q16.  Without a counted window the
+ *     record is { 0, { 0, 0, 0, 0 }, { 65536, 65536, 65536, 65536 }, 0 }.
+ * Over a background colour g the composited error of a pixel is e_pm - g * e_A / 255 (e_pm, e_A: the errors of a premultiplied channel and of
+ * alpha), so the premultiplied channels and alpha together bound the error over every background.
+ * pngloss_hip_psnr_db, pngloss_hip_ssim_mean, the byte-per-pixel masks and the acceptance rule below work on visible-mode records as they are; an
+ * image without a visible pixel has pixels == 0: nothing to measure.
+ *
+ * pngloss_hip_compare_batch_visible: the stand-alone measurement in visible mode, pairs as for pngloss_hip_compare_batch; out_distortion[i] and
+ * out_ssim[i] = the visible-mode records of pair i; either output may be NULL (its kernel is then not launched).  Synchronous, independent of the
+ * options; not while a batch is in flight on the context (PNGLOSS_INVALID_ARGUMENT). */
+int pngloss_hip_compare_batch_visible(pngloss_hip_ctx *ctx, const pngloss_hip_image_pair *pairs, size_t n, pngloss_hip_distortion *out_distortion,
+                                      pngloss_hip_ssim *out_ssim, void *stream);
+
 /* ---- A strength per image, found from a distortion target (no reference equivalent: the reference tool takes -s and nothing else).  A strength
  * says nothing about how the result will look, and the right one differs from image to image; the optimiser works in place, so a caller who
  * wanted "at least 38 dB" had to reload the original for every try.  Here the original stays on the device between the probes.
@@ -564,6 +588,10 @@ int pngloss_hip_last_engine_info(pngloss_hip_ctx *ctx, size_t index, int32_t inf
  *   the library launched before the option existed: no copy, no arena, no extra kernel.
  * Name "ssim", value "on" | "off" (default): measure the structural similarity of every batch from here on (pngloss_hip_last_ssim, above); independent of
  *   "distortion".  "off" launches exactly what the library launched before the option existed.
+ * Name "measure", value "all" (default) | "visible": what the measuring kernels behind a batch ("distortion", "ssim") and the probes of the target searches
+ *   (pngloss_hip_optimize_batch_target[2], pngloss_hip_multi_optimize_batch_host_target[2]) count: every pixel, or the visible ones on alpha-premultiplied
+ *   channels ("Measuring over visible pixels", above).  No effect unless one of those measures; the byte-budget search always reports over all pixels.
+ *   "all" launches exactly what the library launched before the option existed.
  * Returns PNGLOSS_SUCCESS or PNGLOSS_INVALID_ARGUMENT (unknown name or value).
  * Results never depend on an option, on the engine, or on the environment: the remaining environment hooks (PNGLOSS_HIP_SEG_GROUPS, _SEG_UNIT, _ENUM_NT,
  * _NO_STREAM_WAIT, _SEGPROF, _DEBUG ...: timing and test pins) are read once, when a context is created, and none of them changes a byte; the debugging aid

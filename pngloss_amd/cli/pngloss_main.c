@@ -54,6 +54,7 @@ struct options {
     bool have_size;            /* --target-size: the strength is found per file from a byte budget for the written file, -s is its upper bound */
     bool size_percent;         /* ... given as a percentage of each input file's size */
     unsigned long long size_value;   /* bytes, or percent */
+    bool visible;              /* --visible: --distortion, --ssim and the --target searches measure over visible pixels (the library's option "measure") */
     bool gpu_read;             /* --gpu-read: inverse filters + expansion to RGBA8 on the device (inflate stays zlib on the decode threads) */
 };
 
@@ -91,6 +92,10 @@ static const char usage_text[] =
     "                    the input file's size; implies --gpu-deflate; a budget that -s does not\n"
     "                    reach writes the file at -s with a warning; not with the other --target\n"
     "                    switches or --max-error (--ssim has no record in this search)\n"
+    "  --visible         measure over visible pixels: --distortion, --ssim, --target-psnr, --max-error and\n"
+    "                    --target-ssim then take alpha-premultiplied colour plus alpha, and leave out\n"
+    "                    pixels that are fully transparent in the input and in the result; needs one of\n"
+    "                    those five; not with --target-size; the written files do not depend on it\n"
     "\n"
     "Lossily compresses PNGs by using more compressible colors that are close enough to the\n"
     "original values; the filter+quantise pass runs on the GPU (all files of a call as one batch).\n"
@@ -99,7 +104,7 @@ static const char usage_text[] =
 
 /* ------------------------------------------------------------------------------------------- options */
 
-enum { OPT_EXT = 256, OPT_NO_FORCE, OPT_SKIP_LARGER, OPT_STRIP, OPT_GPU_DEFLATE, OPT_GPU_READ, OPT_DISTORTION, OPT_TARGET_PSNR, OPT_MAX_ERROR, OPT_SSIM, OPT_TARGET_SSIM, OPT_TARGET_SIZE };
+enum { OPT_EXT = 256, OPT_NO_FORCE, OPT_SKIP_LARGER, OPT_STRIP, OPT_GPU_DEFLATE, OPT_GPU_READ, OPT_DISTORTION, OPT_TARGET_PSNR, OPT_MAX_ERROR, OPT_SSIM, OPT_TARGET_SSIM, OPT_TARGET_SIZE, OPT_VISIBLE };
 
 static bool parse_number(const char *text, unsigned long *out)
 {
@@ -153,6 +158,7 @@ static pngloss_error parse_options(int argc, char **argv, struct options *o)
         { "ssim", no_argument, NULL, OPT_SSIM },
         { "target-ssim", required_argument, NULL, OPT_TARGET_SSIM },
         { "target-size", required_argument, NULL, OPT_TARGET_SIZE },
+        { "visible", no_argument, NULL, OPT_VISIBLE },
         { NULL, 0, NULL, 0 },
     };
     for (int c; (c = getopt_long(argc, argv, "vqfo:Vhs:b:", table, NULL)) != -1;) {
@@ -186,6 +192,7 @@ static pngloss_error parse_options(int argc, char **argv, struct options *o)
             if (!parse_size(optarg, &o->size_value, &o->size_percent)) { fputs("--target-size requires a number of bytes (suffix k or M) or a percentage\n", stderr); return INVALID_ARGUMENT; }
             o->have_size = true;
             break;
+        case OPT_VISIBLE: o->visible = true; break;
         case 'h': o->help = true; break;
         case 'V': o->version = true; break;
         case 'o':
@@ -414,16 +421,19 @@ static pngloss_error encode_to(struct job *j, png24_image *img, unsigned char *f
 }
 
 /* --distortion: the line of a written file.  PSNR over the channels the file stores (gray is the G channel, pngloss_image.c:112-115) */
-static void say_distortion(struct job *j)
+static void say_distortion(struct job *j, const struct options *o)
 {
     const pngloss_hip_distortion *d = &j->distortion;
+    if (!d->changed_pixels && o->visible) { say(j, "  distortion (visible): none, %llu visible pixels\n", (unsigned long long)d->pixels); return; }
     if (!d->changed_pixels) { say(j, "  distortion: none (lossless)\n"); return; }
     const unsigned bpp = j->gpu.bytes_per_pixel;
     const unsigned mask = bpp == 1 ? 0x2u : bpp == 2 ? 0xAu : bpp == 3 ? 0x7u : 0xFu;
     unsigned largest = 0;
     for (int c = 0; c < 4; c++)
         if ((mask >> c & 1u) && d->max_abs[c] > largest) largest = d->max_abs[c];
-    say(j, "  distortion: PSNR %.2f dB, %llu of %llu pixels changed, largest channel error %u\n", pngloss_hip_psnr_db(d, mask),
+    /* --visible: the record is over premultiplied channels, `pixels` counts the visible ones */
+    say(j, o->visible ? "  distortion (visible): PSNR %.2f dB, %llu of %llu visible pixels changed, largest channel error %u\n"
+                      : "  distortion: PSNR %.2f dB, %llu of %llu pixels changed, largest channel error %u\n", pngloss_hip_psnr_db(d, mask),
         (unsigned long long)d->changed_pixels, (unsigned long long)d->pixels, largest);
 }
 
@@ -433,13 +443,13 @@ static void say_ssim(struct job *j, const struct options *o)
     const pngloss_hip_ssim *r = &j->ssim;
     if (!j->have_ssim && o->have_size) { say(j, "  ssim: not measured (the size search keeps no SSIM record)\n"); return; }
     if (!j->have_ssim) { if (o->have_target) say(j, "  ssim: not measured (a strength search measures it only with --target-ssim)\n"); return; }
-    if (!r->windows) { say(j, "  ssim: not measured (smaller than one 8x8 window)\n"); return; }
+    if (!r->windows) { say(j, o->visible ? "  ssim (visible): not measured (no 8x8 window with a visible pixel)\n" : "  ssim: not measured (smaller than one 8x8 window)\n"); return; }
     const unsigned bpp = j->gpu.bytes_per_pixel;
     const unsigned mask = bpp == 1 ? 0x2u : bpp == 2 ? 0xAu : bpp == 3 ? 0x7u : 0xFu;
     int32_t worst = 65536;
     for (int c = 0; c < 4; c++)
         if ((mask >> c & 1u) && r->min_q16[c] < worst) worst = r->min_q16[c];
-    say(j, "  ssim: mean %.4f, worst window %.4f, %llu windows\n", pngloss_hip_ssim_mean(r, mask), (double)worst / 65536.0, (unsigned long long)r->windows);
+    say(j, o->visible ? "  ssim (visible): mean %.4f, worst window %.4f, %llu windows with visible pixels\n" : "  ssim: mean %.4f, worst window %.4f, %llu windows\n", pngloss_hip_ssim_mean(r, mask), (double)worst / 65536.0, (unsigned long long)r->windows);
 }
 
 static void encode_job(struct job *j, const struct options *o)
@@ -455,7 +465,7 @@ static void encode_job(struct job *j, const struct options *o)
     /* a budget that was not reached (or is smaller than the container alone): the file was written at -s; one line says so, the exit status stays */
     if (o->have_size && rc == SUCCESS && (!j->size.reached || j->out.file_size > j->size_budget))
         say(j, "  warning: %s: budget of %zu bytes not reached, wrote %zu bytes at strength %u\n", j->in_name, j->size_budget, (size_t)j->out.file_size, j->size.strength);
-    if (o->distortion && rc == SUCCESS && j->have_distortion) say_distortion(j);
+    if (o->distortion && rc == SUCCESS && j->have_distortion) say_distortion(j, o);
     if (o->ssim && rc == SUCCESS) say_ssim(j, o);
     if (o->verbose) {
         if (rc == SUCCESS) {
@@ -657,6 +667,12 @@ static pngloss_error run_window(struct job *jobs, size_t n, const struct options
                 fputs("  warning: the library refused the option \"distortion\"; no distortion lines\n", stderr);
             if (*ctx && o->ssim && pngloss_hip_multi_set_option(*ctx, "ssim", "on") != PNGLOSS_SUCCESS)
                 fputs("  warning: the library refused the option \"ssim\"; no ssim lines\n", stderr);
+            /* --visible: what those two and the searches measure.  A library that refuses it would measure something else than the lines say */
+            if (*ctx && o->visible && pngloss_hip_multi_set_option(*ctx, "measure", "visible") != PNGLOSS_SUCCESS) {
+                fputs("  error: the library refused the option \"measure\"\n", stderr);
+                pngloss_hip_multi_destroy(*ctx);
+                *ctx = NULL;
+            }
         }
         if (timing) fprintf(stderr, "  [timing] GPU contexts ready after %.3f s\n", now_s() - tc0);
         /* --target-psnr / --max-error: the library searches a strength per file, -s bounds it; the records come back in the reports */
@@ -738,6 +754,8 @@ int main(int argc, char **argv)
     if (o.have_target_ssim && !(o.target_ssim > 0.0 && o.target_ssim <= 1.0)) { fputs("Must specify an SSIM target above 0 and at most 1.\n", stderr); return INVALID_ARGUMENT; }
     if (o.have_max_error && (o.max_error < 1 || o.max_error > 255)) { fputs("Must specify a largest channel error in the range 1-255.\n", stderr); return INVALID_ARGUMENT; }
     if (o.have_size && o.have_target) { fputs("--target-size cannot be combined with --target-psnr, --target-ssim or --max-error.\n", stderr); return INVALID_ARGUMENT; }
+    if (o.visible && !(o.distortion || o.ssim || o.have_target)) { fputs("--visible needs one of --distortion, --ssim, --target-psnr, --max-error or --target-ssim.\n", stderr); return INVALID_ARGUMENT; }
+    if (o.visible && o.have_size) { fputs("--visible cannot be combined with --target-size.\n", stderr); return INVALID_ARGUMENT; }
     if (o.have_size && o.size_value < 1) { fputs("Must specify a size target of at least 1 byte or 1 percent.\n", stderr); return INVALID_ARGUMENT; }
     if (o.have_size) o.gpu_deflate = true;          /* the budget is for the file the device deflate writes: zlib-9's size is not what the device measures */
     if (o.bleed < 1 || o.bleed > 32767) { fputs("Must specify a bleed divider in the range 1-32767.\n", stderr); return INVALID_ARGUMENT; }

@@ -14,8 +14,9 @@ struct PlDistortJob {
     PlDistortRecord *record;    /* device, zeroed before pl_distort is launched */
 };
 
-/* max_pixels: the largest `pixels` of the n jobs (sizes the grid) */
+/* max_pixels: the largest `pixels` of the n jobs (sizes the grid).  visible: measure over visible pixels (pl_distort_core.h): record->pixels is then counted
+ * by the kernel, from the zero the caller put there. */
 hipError_t pl_launch_keep(const PlDistortJob *d_jobs, size_t n, uint64_t max_pixels, hipStream_t stream);
-hipError_t pl_launch_distort(const PlDistortJob *d_jobs, size_t n, uint64_t max_pixels, hipStream_t stream);
+hipError_t pl_launch_distort(const PlDistortJob *d_jobs, size_t n, uint64_t max_pixels, hipStream_t stream, bool visible = false);
 
 #endif

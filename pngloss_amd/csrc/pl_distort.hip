@@ -4,6 +4,7 @@
  *
  *   pl_keep     copies the original RGBA8 of every image into the context's keep arena, before pl_classify / pl_repack rewrite it in place
  *   pl_distort  behind pl_unpack: reads the kept original and the final pixels and adds the image's record up (pl_distort_core.h)
+ *   pl_distort_visible  the same over visible pixels (option "measure" at "visible"): premultiplies after the load and counts the visible pixels
  *
  * pngloss_hip_compare_batch runs pl_distort alone, on two images of the caller's.  No reference equivalent.
  */
@@ -26,10 +27,13 @@ __global__ __launch_bounds__(kThreads) void pl_keep(const PlDistortJob *__restri
     for (size_t i = n4 * 4 + tid; i < n; i += nthreads) j.keep[i] = j.img[i];
 }
 
-__global__ __launch_bounds__(kThreads) void pl_distort(const PlDistortJob *__restrict__ jobs)
+/* Visible: the visible mode of pl_distort_core.h -- the sums over premultiplied pixels, and the image's `pixels` is the count of visible ones, merged
+ * like the other sums (the record is zeroed before the launch).  Without it: `pixels` is the job's, written once. */
+template <bool Visible>
+__device__ __forceinline__ void distort_body(const PlDistortJob *__restrict__ jobs)
 {
     const PlDistortJob j = jobs[blockIdx.y];
-    PldSum s = pld_thread(j.keep, j.img, (size_t)j.pixels, (size_t)blockIdx.x * kThreads + threadIdx.x, (size_t)gridDim.x * kThreads);
+    PldSum s = pld_thread<Visible>(j.keep, j.img, (size_t)j.pixels, (size_t)blockIdx.x * kThreads + threadIdx.x, (size_t)gridDim.x * kThreads);
     /* per wave, then per workgroup; then ONE atomic per quantity and workgroup, and none for a quantity that is zero (pl_classify's finding: same-address
      * atomics, one per wave, were most of that kernel's time) */
 #pragma unroll
@@ -40,13 +44,16 @@ __global__ __launch_bounds__(kThreads) void pl_distort(const PlDistortJob *__res
             s.mx[c] = max(s.mx[c], __shfl_down(s.mx[c], off));
         }
         s.changed += __shfl_down(s.changed, off);
+        if (Visible) s.visible += __shfl_down(s.visible, off);
     }
-    __shared__ uint64_t wsum[kWaves][5];       /* sq[0..3], changed */
+    constexpr uint32_t kSums = Visible ? 6 : 5;
+    __shared__ uint64_t wsum[kWaves][kSums];   /* sq[0..3], changed; visible */
     __shared__ uint32_t wmax[kWaves][4];
     const uint32_t wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
         for (int c = 0; c < 4; c++) { wsum[wave][c] = s.sq[c]; wmax[wave][c] = s.mx[c]; }
         wsum[wave][4] = s.changed;
+        if (Visible) wsum[wave][kSums - 1] = s.visible;
     }
     __syncthreads();
     const uint32_t t = threadIdx.x;
@@ -58,8 +65,17 @@ __global__ __launch_bounds__(kThreads) void pl_distort(const PlDistortJob *__res
         uint32_t v = 0;
         for (int w = 0; w < kWaves; w++) v = max(v, wmax[w][t - 5]);
         if (v) atomicMax(&j.record->max_abs[t - 5], v);
+    } else if (Visible) {
+        if (t == 9) {
+            uint64_t v = 0;
+            for (int w = 0; w < kWaves; w++) v += wsum[w][kSums - 1];
+            if (v) atomicAdd(reinterpret_cast<unsigned long long *>(&j.record->pixels), (unsigned long long)v);
+        }
     } else if (t == 9 && blockIdx.x == 0) j.record->pixels = j.pixels;
 }
+
+__global__ __launch_bounds__(kThreads) void pl_distort(const PlDistortJob *__restrict__ jobs) { distort_body<false>(jobs); }
+__global__ __launch_bounds__(kThreads) void pl_distort_visible(const PlDistortJob *__restrict__ jobs) { distort_body<true>(jobs); }
 
 /* as pl_prepost.hip:batch_grid: enough workgroups to fill 256 CUs several times over, but never more than the batch needs; a launch takes at most
  * 65535 images (gridDim.y) */
@@ -85,11 +101,11 @@ hipError_t pl_launch_keep(const PlDistortJob *d_jobs, size_t n, uint64_t max_pix
     return hipGetLastError();
 }
 
-hipError_t pl_launch_distort(const PlDistortJob *d_jobs, size_t n, uint64_t max_pixels, hipStream_t stream)
+hipError_t pl_launch_distort(const PlDistortJob *d_jobs, size_t n, uint64_t max_pixels, hipStream_t stream, bool visible)
 {
     for (size_t first = 0; first < n; first += kMaxImages) {
         const size_t m = n - first < kMaxImages ? n - first : kMaxImages;
-        hipLaunchKernelGGL(pl_distort, distort_grid(m, max_pixels), dim3(kThreads), 0, stream, d_jobs + first);
+        hipLaunchKernelGGL(visible ? pl_distort_visible : pl_distort, distort_grid(m, max_pixels), dim3(kThreads), 0, stream, d_jobs + first);
     }
     return hipGetLastError();
 }

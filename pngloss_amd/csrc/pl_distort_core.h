@@ -8,9 +8,11 @@
  *     pixels          width * height
  * Everything is an integer, so the record does not depend on the order the pixels are summed in: the kernel's thousands of lanes and a loop on the
  * CPU give the same 64 bytes.
+ * In visible mode (pld_thread<true>; below) the same sums are taken on alpha-premultiplied pixels and `pixels` counts the visible ones.
  *
  * Shared by the HIP kernel (pl_distort.hip: one thread runs pld_thread, the sums of the threads are merged through the wave, the workgroup and one
- * atomic per quantity) and by tests/c/distort_host.cpp (test infrastructure), which runs the same thread loop on the CPU under the sanitizers.
+ * atomic per quantity) and by tests/c/distort_host.cpp and tests/c/visible_host.cpp (test infrastructure), which run the same thread loop on the CPU
+ * under the sanitizers.
  */
 #ifndef PL_DISTORT_CORE_H
 #define PL_DISTORT_CORE_H
@@ -41,14 +43,31 @@ constexpr uint32_t PLD_LANE_PIXELS_MAX = 0xFFFFFFFFu / PLD_CHANNEL_SQ_MAX;
 constexpr uint32_t PLD_FLUSH_PIXELS = 16384;
 static_assert(PLD_FLUSH_PIXELS + 3 <= PLD_LANE_PIXELS_MAX, "a lane's 32-bit sums would overflow before they are flushed");
 
-struct PldLane { uint32_t sq[4], mx[4], changed; };          /* of at most PLD_FLUSH_PIXELS + 3 pixels */
-struct PldSum { uint64_t sq[4], changed; uint32_t mx[4]; };  /* of any number of pixels */
+struct PldLane { uint32_t sq[4], mx[4], changed, visible; };          /* of at most PLD_FLUSH_PIXELS + 3 pixels */
+struct PldSum { uint64_t sq[4], changed; uint32_t mx[4]; uint64_t visible; };  /* of any number of pixels (visible: counted in visible mode only) */
 
 /* four pixels behind one 16-byte load */
 struct alignas(16) PldQuad { uint32_t px[4]; };
 
+/* ---- visible mode (include/pngloss_hip.h, "Measuring over visible pixels"): the same sums over the alpha-premultiplied pixels pm(a), pm(b), and
+ * two counts that need the alpha of both: a pixel is visible when its alpha is non-zero in a or in b.  pm keeps alpha and turns each of R, G, B
+ * into the integer nearest to c * A / 255 (255 is odd: no ties), at most 255 -- so every bound above holds as it stands.  An invisible pixel is
+ * the word 0 in both images once premultiplied and adds nothing to any sum. ---- */
+PLD_HD uint32_t pld_pm(uint32_t p)
+{
+    const uint32_t A = p >> 24;
+    return ((( p        & 255u) * A + 127u) / 255u) | ((((p >> 8) & 255u) * A + 127u) / 255u) << 8 | ((((p >> 16) & 255u) * A + 127u) / 255u) << 16 |
+           (p & 0xFF000000u);
+}
+
+template <bool Visible = false>
 PLD_HD void pld_pixel(PldLane &l, uint32_t a, uint32_t b)
 {
+    if (Visible) {
+        l.visible += ((a | b) >> 24) ? 1u : 0u;
+        a = pld_pm(a);
+        b = pld_pm(b);
+    }
 #if defined(__HIPCC__)
 #pragma unroll
 #endif
@@ -69,7 +88,8 @@ PLD_HD void pld_flush(PldSum &s, PldLane &l)
         l.sq[c] = 0;
     }
     s.changed += l.changed;
-    l.changed = 0;
+    s.visible += l.visible;
+    l.changed = l.visible = 0;
 }
 
 PLD_HD void pld_merge(PldSum &s, const PldSum &o)
@@ -79,6 +99,7 @@ PLD_HD void pld_merge(PldSum &s, const PldSum &o)
         s.mx[c] = o.mx[c] > s.mx[c] ? o.mx[c] : s.mx[c];
     }
     s.changed += o.changed;
+    s.visible += o.visible;
 }
 
 /* how many leading groups of four pixels go through 16-byte loads: all of them when both images start on a 16-byte boundary, else none
@@ -88,7 +109,9 @@ PLD_HD size_t pld_vector_quads(const void *a, const void *b, size_t n)
     return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u) ? 0 : n / 4;
 }
 
-/* the share of thread `tid` of `nthreads`: quads tid, tid + nthreads, ... of the vector part, then words at the same stride of the rest */
+/* the share of thread `tid` of `nthreads`: quads tid, tid + nthreads, ... of the vector part, then words at the same stride of the rest.
+ * Visible: the visible mode above (the sums on premultiplied pixels, s.visible counted); without it s.visible stays 0 and is never read. */
+template <bool Visible = false>
 PLD_HD PldSum pld_thread(const uint32_t *a, const uint32_t *b, size_t n, size_t tid, size_t nthreads)
 {
     PldSum s = {};
@@ -98,22 +121,22 @@ PLD_HD PldSum pld_thread(const uint32_t *a, const uint32_t *b, size_t n, size_t 
     const PldQuad *a4 = reinterpret_cast<const PldQuad *>(a), *b4 = reinterpret_cast<const PldQuad *>(b);
     for (size_t i = tid; i < n4; i += nthreads) {
         const PldQuad va = a4[i], vb = b4[i];
-        pld_pixel(l, va.px[0], vb.px[0]);
-        pld_pixel(l, va.px[1], vb.px[1]);
-        pld_pixel(l, va.px[2], vb.px[2]);
-        pld_pixel(l, va.px[3], vb.px[3]);
+        pld_pixel<Visible>(l, va.px[0], vb.px[0]);
+        pld_pixel<Visible>(l, va.px[1], vb.px[1]);
+        pld_pixel<Visible>(l, va.px[2], vb.px[2]);
+        pld_pixel<Visible>(l, va.px[3], vb.px[3]);
         held += 4;
         if (held >= PLD_FLUSH_PIXELS) { pld_flush(s, l); held = 0; }
     }
     for (size_t i = n4 * 4 + tid; i < n; i += nthreads) {
-        pld_pixel(l, a[i], b[i]);
+        pld_pixel<Visible>(l, a[i], b[i]);
         if (++held >= PLD_FLUSH_PIXELS) { pld_flush(s, l); held = 0; }
     }
     pld_flush(s, l);
     return s;
 }
 
-/* the sums of all threads of an image, and its pixel count, as its record */
+/* the sums of all threads of an image, and its pixel count (visible mode: s.visible), as its record */
 PLD_HD void pld_record(PlDistortRecord &r, const PldSum &s, uint64_t pixels)
 {
     r.pixels = pixels;

@@ -137,6 +137,9 @@ struct pngloss_hip_ctx {
     /* option "ssim": the originals are the keep arena's (one arena, one pl_keep launch for both options); the SSIM kernel's job table and records
      * live in a small buffer of their own (pl_layout.h: pl_ssim_layout), regrown on demand like the others */
     bool opt_ssim = false;           /* pngloss_hip_set_option("ssim", "on" | "off") */
+    /* option "measure": what the two measuring kernels count, behind a batch and in the probes of the target searches: every pixel, or the visible ones
+     * (pl_distort_core.h, pl_ssim_core.h).  The pipeline never sees it. */
+    bool opt_visible = false;        /* pngloss_hip_set_option("measure", "all" | "visible") */
     char *d_ssim = nullptr;
     size_t ssim_bytes = 0;
     std::vector<PlSsimJob> h_ssj;    /* (stay alive until the asynchronous copies that read them are done: the next enqueue) */
@@ -257,14 +260,14 @@ int upload_distort_jobs(pngloss_hip_ctx *ctx, const PlKeepLayout &lay, size_t n,
 }
 
 /* One table of SSIM jobs and their records, as pl_ssim wants them before its launch: pair i is the width[i] x height[i] image b[i] against the
- * original a[i]; jobs[i].record = d_records + i, records[i] = the record with no window added yet.  Returns the largest tile count (sizes the grid). */
+ * original a[i]; jobs[i].record = d_records + i, records[i] = the record with no window added yet (visible: as pl_ssim_visible wants it).  Returns the largest tile count (sizes the grid). */
 uint64_t fill_ssim_jobs(PlSsimJob *jobs, PlSsimRecord *records, PlSsimRecord *d_records, size_t n, const void *const *a, const void *const *b,
-                        const uint32_t *width, const uint32_t *height)
+                        const uint32_t *width, const uint32_t *height, bool visible)
 {
     uint64_t max_tiles = 0;
     for (size_t i = 0; i < n; i++) {
         jobs[i] = PlSsimJob{ static_cast<const uint32_t *>(a[i]), static_cast<const uint32_t *>(b[i]), width[i], height[i], d_records + i };
-        records[i] = pls_record_begin(width[i], height[i]);
+        records[i] = visible ? pls_record_begin_visible() : pls_record_begin(width[i], height[i]);
         max_tiles = std::max(max_tiles, pls_geom(width[i], height[i]).tiles);
     }
     return max_tiles;
@@ -272,14 +275,14 @@ uint64_t fill_ssim_jobs(PlSsimJob *jobs, PlSsimRecord *records, PlSsimRecord *d_
 
 /* The same into the context's SSIM buffer (grown here: call it before anything of the batch is enqueued), uploaded on `stream` */
 int upload_ssim_jobs(pngloss_hip_ctx *ctx, size_t n, const void *const *a, const void *const *b, const uint32_t *width, const uint32_t *height,
-                     hipStream_t stream, PlSsimLayout &lay, uint64_t &max_tiles)
+                     hipStream_t stream, PlSsimLayout &lay, uint64_t &max_tiles, bool visible)
 {
     lay = pl_ssim_layout(n, sizeof(PlSsimJob), sizeof(PlSsimRecord));
     const int rc = grow(ctx->d_ssim, ctx->ssim_bytes, lay.total, 8);
     if (rc) return rc;
     ctx->h_ssj.assign(n, PlSsimJob{});
     ctx->h_ssr.assign(n, PlSsimRecord{});
-    max_tiles = fill_ssim_jobs(ctx->h_ssj.data(), ctx->h_ssr.data(), reinterpret_cast<PlSsimRecord *>(ctx->d_ssim + lay.records), n, a, b, width, height);
+    max_tiles = fill_ssim_jobs(ctx->h_ssj.data(), ctx->h_ssr.data(), reinterpret_cast<PlSsimRecord *>(ctx->d_ssim + lay.records), n, a, b, width, height, visible);
     PL_CHECK(hipMemcpyAsync(ctx->d_ssim + lay.jobs, ctx->h_ssj.data(), sizeof(PlSsimJob) * n, hipMemcpyHostToDevice, stream));
     PL_CHECK(hipMemcpyAsync(ctx->d_ssim + lay.records, ctx->h_ssr.data(), sizeof(PlSsimRecord) * n, hipMemcpyHostToDevice, stream));
     return PNGLOSS_SUCCESS;
@@ -595,7 +598,7 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
     ctx->d_records = nullptr;
     ctx->ssim.clear();
     ctx->d_ssim_records = nullptr;
-    const bool distort = ctx->opt_distortion, ssim = ctx->opt_ssim;
+    const bool distort = ctx->opt_distortion, ssim = ctx->opt_ssim, visible = ctx->opt_visible;
     const bool keep_originals = distort || ssim;     /* one arena, one pl_keep launch, whichever of the two options wants the originals */
     const PlHooks &hk = ctx->hooks;
     PlPlanInput in;
@@ -713,7 +716,7 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
         if (ssim) {
             std::vector<const void *> orig(n);
             for (size_t i = 0; i < n; i++) orig[i] = ctx->d_keep + keep.image[i];
-            rc = upload_ssim_jobs(ctx, n, orig.data(), img.data(), in.width.data(), in.height.data(), stream, ssim_lay, max_tiles);
+            rc = upload_ssim_jobs(ctx, n, orig.data(), img.data(), in.width.data(), in.height.data(), stream, ssim_lay, max_tiles, visible);
             if (rc) return rc;
         }
     }
@@ -740,8 +743,8 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
     {
         /* (behind this point the segment engine's launch thread may be running: it is joined before an error is returned) */
         hipError_t e = pl_launch_finish(d_jobs, ctx->h_jobs.data(), n, stream);
-        if (e == hipSuccess && distort) e = pl_launch_distort(d_dj, n, max_pixels, stream);      /* behind pl_unpack: the final RGBA8 against the kept original */
-        if (e == hipSuccess && ssim) e = pl_launch_ssim(reinterpret_cast<const PlSsimJob *>(ctx->d_ssim + ssim_lay.jobs), n, max_tiles, stream);
+        if (e == hipSuccess && distort) e = pl_launch_distort(d_dj, n, max_pixels, stream, visible);      /* behind pl_unpack: the final RGBA8 against the kept original */
+        if (e == hipSuccess && ssim) e = pl_launch_ssim(reinterpret_cast<const PlSsimJob *>(ctx->d_ssim + ssim_lay.jobs), n, max_tiles, stream, visible);
         if (e == hipSuccess) e = pl_launch_emit(d_jobs, ctx->h_jobs.data(), n, stream);
         if (e == hipSuccess) e = hipEventRecord(ctx->ev[3], stream);
         if (e != hipSuccess) {
@@ -1258,7 +1261,7 @@ static int batch_host(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images
     }
     K = std::min(K, ctx->peers.size() + 1);
     if (K <= 1) return batch_host_one(ctx, images, n, quantization_strength, bleed_divider, results, lines, zs);
-    for (pngloss_hip_ctx *p : ctx->peers) { p->opt_distortion = ctx->opt_distortion; p->opt_ssim = ctx->opt_ssim; }       /* the other chunks measure what this one measures */
+    for (pngloss_hip_ctx *p : ctx->peers) { p->opt_distortion = ctx->opt_distortion; p->opt_ssim = ctx->opt_ssim; p->opt_visible = ctx->opt_visible; }       /* the other chunks measure what this one measures */
     std::vector<uint64_t> pixels(n);
     for (size_t i = 0; i < n; i++) pixels[i] = (uint64_t)images[i].width * images[i].height;
     const std::vector<size_t> first = pl_host_window_cut(pixels, K);
@@ -1469,6 +1472,7 @@ static int target_search(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *ima
                          long bleed, hipStream_t stream, bool commit, pngloss_hip_result *results, pngloss_hip_target_report *reports, pngloss_hip_ssim *ssim_out)
 {
     const bool want_ssim = t.min_ssim != 0.0;          /* without the condition the SSIM kernel is never launched */
+    const bool visible = ctx->opt_visible;             /* option "measure": the probes are accepted or refused on records over visible pixels */
     /* whatever happens: the caller's option back, and no "last batch" to index */
     SearchGuard guard{ ctx, ctx->opt_distortion, ctx->opt_ssim };
     ctx->opt_distortion = ctx->opt_ssim = false;       /* the search measures against its own originals (the keep arena is laid out afresh by every enqueue) */
@@ -1533,7 +1537,7 @@ static int target_search(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *ima
         std::vector<pngloss_hip_distortion> got(who.size());
         PL_CHECK(hipMemcpyAsync(d_dj, dj.data(), sizeof(PlDistortJob) * dj.size(), hipMemcpyHostToDevice, stream));
         PL_CHECK(hipMemsetAsync(d_rec, 0, sizeof(PlDistortRecord) * dj.size(), stream));
-        PL_CHECK(pl_launch_distort(d_dj, dj.size(), max_pixels, stream));
+        PL_CHECK(pl_launch_distort(d_dj, dj.size(), max_pixels, stream, visible));
         PL_CHECK(hipMemcpyAsync(got.data(), d_rec, sizeof(PlDistortRecord) * dj.size(), hipMemcpyDeviceToHost, stream));
         std::vector<pngloss_hip_ssim> sgot(want_ssim ? who.size() : 0);
         if (want_ssim) {
@@ -1547,10 +1551,10 @@ static int target_search(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *ima
                 a[k] = arena + lay.image[i].orig; b[k] = images[i].d_rgba;
                 w[k] = images[i].width; h[k] = images[i].height;
             }
-            const uint64_t max_tiles = fill_ssim_jobs(sj.data(), ssim_begins.back().data(), d_srec, who.size(), a.data(), b.data(), w.data(), h.data());
+            const uint64_t max_tiles = fill_ssim_jobs(sj.data(), ssim_begins.back().data(), d_srec, who.size(), a.data(), b.data(), w.data(), h.data(), visible);
             PL_CHECK(hipMemcpyAsync(d_sj, sj.data(), sizeof(PlSsimJob) * sj.size(), hipMemcpyHostToDevice, stream));
             PL_CHECK(hipMemcpyAsync(d_srec, ssim_begins.back().data(), sizeof(PlSsimRecord) * sj.size(), hipMemcpyHostToDevice, stream));
-            PL_CHECK(pl_launch_ssim(d_sj, sj.size(), max_tiles, stream));
+            PL_CHECK(pl_launch_ssim(d_sj, sj.size(), max_tiles, stream, visible));
             PL_CHECK(hipMemcpyAsync(sgot.data(), d_srec, sizeof(PlSsimRecord) * sj.size(), hipMemcpyDeviceToHost, stream));
         }
         PL_CHECK(hipStreamSynchronize(stream));
@@ -2006,6 +2010,9 @@ int pngloss_hip_optimize_batch_size(pngloss_hip_ctx *ctx, const pngloss_hip_imag
 static int batch_host_size(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images, size_t n, const pngloss_hip_size_target &target, long bleed_divider,
                            pngloss_hip_result *results, pngloss_hip_scanlines *lines, pngloss_hip_zstream *zs, pngloss_hip_size_report *reports)
 {
+    /* the byte budget reports over all pixels, whatever the option "measure" says */
+    struct AllPixels { pngloss_hip_ctx *c; bool was; ~AllPixels() { c->opt_visible = was; } } all{ ctx, ctx && ctx->opt_visible };
+    if (ctx) ctx->opt_visible = false;
     return batch_host_searched(ctx, images, n, bleed_divider, results, lines, zs, reports, false, nullptr, PLT_SCANLINES_PROBE, false,
                                [&](const pngloss_hip_image_desc *copies, const PlTargetLayout &lay, pngloss_hip_size_report *rep) {
                                    return size_search(ctx, copies, n, lay, target, bleed_divider, ctx->copy_stream, false, nullptr, nullptr, rep);
@@ -2114,15 +2121,9 @@ int pngloss_hip_multi_set_option(pngloss_hip_multi *m, const char *name, const c
     return worst;
 }
 
-int pngloss_hip_compare_batch(pngloss_hip_ctx *ctx, const pngloss_hip_image_pair *pairs, size_t n, pngloss_hip_distortion *out, void *stream_)
+/* the three stand-alone measurements: one launch of pl_distort / pl_ssim (visible: of their visible forms) on the caller's pairs */
+static int compare_distortion(pngloss_hip_ctx *ctx, const pngloss_hip_image_pair *pairs, size_t n, pngloss_hip_distortion *out, hipStream_t stream, bool visible)
 {
-    if (!ctx || (n && (!pairs || !out))) return PNGLOSS_INVALID_ARGUMENT;
-    if (ctx->pending) {
-        std::fprintf(stderr, "pngloss_hip: a batch is in flight on this context; call pngloss_hip_finish first\n");
-        return PNGLOSS_INVALID_ARGUMENT;
-    }
-    if (!n) return PNGLOSS_SUCCESS;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
     std::vector<const void *> a(n), b(n);
     std::vector<uint64_t> pixels(n);
     uint64_t max_pixels = 0;
@@ -2138,21 +2139,14 @@ int pngloss_hip_compare_batch(pngloss_hip_ctx *ctx, const pngloss_hip_image_pair
     if (rc) return rc;
     rc = upload_distort_jobs(ctx, lay, n, b.data(), a.data(), pixels.data(), stream);
     if (rc) return rc;
-    PL_CHECK(pl_launch_distort(reinterpret_cast<const PlDistortJob *>(ctx->d_keep + lay.jobs), n, max_pixels, stream));
+    PL_CHECK(pl_launch_distort(reinterpret_cast<const PlDistortJob *>(ctx->d_keep + lay.jobs), n, max_pixels, stream, visible));
     PL_CHECK(hipMemcpyAsync(out, ctx->d_keep + lay.records, sizeof(pngloss_hip_distortion) * n, hipMemcpyDeviceToHost, stream));
     PL_CHECK(hipStreamSynchronize(stream));
     return PNGLOSS_SUCCESS;
 }
 
-int pngloss_hip_compare_batch_ssim(pngloss_hip_ctx *ctx, const pngloss_hip_image_pair *pairs, size_t n, pngloss_hip_ssim *out, void *stream_)
+static int compare_ssim(pngloss_hip_ctx *ctx, const pngloss_hip_image_pair *pairs, size_t n, pngloss_hip_ssim *out, hipStream_t stream, bool visible)
 {
-    if (!ctx || (n && (!pairs || !out))) return PNGLOSS_INVALID_ARGUMENT;
-    if (ctx->pending) {
-        std::fprintf(stderr, "pngloss_hip: a batch is in flight on this context; call pngloss_hip_finish first\n");
-        return PNGLOSS_INVALID_ARGUMENT;
-    }
-    if (!n) return PNGLOSS_SUCCESS;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
     std::vector<const void *> a(n), b(n);
     std::vector<uint32_t> width(n), height(n);
     for (size_t i = 0; i < n; i++) {
@@ -2163,12 +2157,46 @@ int pngloss_hip_compare_batch_ssim(pngloss_hip_ctx *ctx, const pngloss_hip_image
     PL_CHECK(hipSetDevice(ctx->device));
     PlSsimLayout lay;
     uint64_t max_tiles = 0;
-    const int rc = upload_ssim_jobs(ctx, n, a.data(), b.data(), width.data(), height.data(), stream, lay, max_tiles);
+    const int rc = upload_ssim_jobs(ctx, n, a.data(), b.data(), width.data(), height.data(), stream, lay, max_tiles, visible);
     if (rc) return rc;
-    PL_CHECK(pl_launch_ssim(reinterpret_cast<const PlSsimJob *>(ctx->d_ssim + lay.jobs), n, max_tiles, stream));
+    PL_CHECK(pl_launch_ssim(reinterpret_cast<const PlSsimJob *>(ctx->d_ssim + lay.jobs), n, max_tiles, stream, visible));
     PL_CHECK(hipMemcpyAsync(out, ctx->d_ssim + lay.records, sizeof(pngloss_hip_ssim) * n, hipMemcpyDeviceToHost, stream));
     PL_CHECK(hipStreamSynchronize(stream));
     return PNGLOSS_SUCCESS;
+}
+
+static bool compare_refused(pngloss_hip_ctx *ctx)
+{
+    if (!ctx->pending) return false;
+    std::fprintf(stderr, "pngloss_hip: a batch is in flight on this context; call pngloss_hip_finish first\n");
+    return true;
+}
+
+int pngloss_hip_compare_batch(pngloss_hip_ctx *ctx, const pngloss_hip_image_pair *pairs, size_t n, pngloss_hip_distortion *out, void *stream_)
+{
+    if (!ctx || (n && (!pairs || !out))) return PNGLOSS_INVALID_ARGUMENT;
+    if (compare_refused(ctx)) return PNGLOSS_INVALID_ARGUMENT;
+    if (!n) return PNGLOSS_SUCCESS;
+    return compare_distortion(ctx, pairs, n, out, static_cast<hipStream_t>(stream_), false);
+}
+
+int pngloss_hip_compare_batch_ssim(pngloss_hip_ctx *ctx, const pngloss_hip_image_pair *pairs, size_t n, pngloss_hip_ssim *out, void *stream_)
+{
+    if (!ctx || (n && (!pairs || !out))) return PNGLOSS_INVALID_ARGUMENT;
+    if (compare_refused(ctx)) return PNGLOSS_INVALID_ARGUMENT;
+    if (!n) return PNGLOSS_SUCCESS;
+    return compare_ssim(ctx, pairs, n, out, static_cast<hipStream_t>(stream_), false);
+}
+
+int pngloss_hip_compare_batch_visible(pngloss_hip_ctx *ctx, const pngloss_hip_image_pair *pairs, size_t n, pngloss_hip_distortion *out_distortion,
+                                      pngloss_hip_ssim *out_ssim, void *stream_)
+{
+    if (!ctx || (n && !pairs)) return PNGLOSS_INVALID_ARGUMENT;
+    if (compare_refused(ctx)) return PNGLOSS_INVALID_ARGUMENT;
+    if (!n) return PNGLOSS_SUCCESS;
+    int rc = out_distortion ? compare_distortion(ctx, pairs, n, out_distortion, static_cast<hipStream_t>(stream_), true) : PNGLOSS_SUCCESS;
+    if (rc == PNGLOSS_SUCCESS && out_ssim) rc = compare_ssim(ctx, pairs, n, out_ssim, static_cast<hipStream_t>(stream_), true);
+    return rc;
 }
 
 double pngloss_hip_ssim_mean(const pngloss_hip_ssim *r, unsigned channel_mask)
@@ -2376,6 +2404,12 @@ int pngloss_hip_set_option(pngloss_hip_ctx *ctx, const char *name, const char *v
         /* measure every batch from here on (pl_distort.hip): "on" | "off" (default) */
         if (std::strcmp(value, "on") == 0) { ctx->opt_distortion = true; return PNGLOSS_SUCCESS; }
         if (std::strcmp(value, "off") == 0) { ctx->opt_distortion = false; return PNGLOSS_SUCCESS; }
+        return PNGLOSS_INVALID_ARGUMENT;
+    }
+    if (std::strcmp(name, "measure") == 0) {
+        /* what "distortion", "ssim" and the target searches measure from here on: "all" (default) | "visible" (pl_distort_core.h, pl_ssim_core.h) */
+        if (std::strcmp(value, "all") == 0) { ctx->opt_visible = false; return PNGLOSS_SUCCESS; }
+        if (std::strcmp(value, "visible") == 0) { ctx->opt_visible = true; return PNGLOSS_SUCCESS; }
         return PNGLOSS_INVALID_ARGUMENT;
     }
     if (std::strcmp(name, "ssim") == 0) {

@@ -7,7 +7,7 @@
  * where the rows allow it, a thread per 4x4 cell -- go into the LDS table as four words per cell and channel; then every (window, channel) pair of
  * the tile is formed from its 2x2 cells (four 16-byte LDS reads) and its q is added to the thread's partial record.  A thread only ever sees
  * channel threadIdx.x % 4, so the partial record is one sum and one minimum.  At the end: through the wave (lanes of equal channel), through LDS,
- * then ONE atomic per quantity and workgroup, as in pl_distort.
+ * then ONE atomic per quantity and workgroup, as in pl_distort.  pl_ssim_visible is the same over visible pixels (option "measure" at "visible").
  */
 #include "pl_ssim.h"
 
@@ -16,16 +16,19 @@ namespace {
 constexpr int kThreads = 256, kWaves = kThreads / 64;
 static_assert(kThreads % 4 == 0, "a thread's (window, channel) pairs must all be of one channel");
 
-__global__ __launch_bounds__(kThreads) void pl_ssim(const PlSsimJob *__restrict__ jobs)
+/* Visible: the visible mode of pl_ssim_core.h -- premultiplied pixels, windows without a visible pixel skipped, and the image's `windows` counted here
+ * (the record starts with 0 windows): the lanes of channel 3 hold the counts, merged like the sums. */
+template <bool Visible>
+__device__ __forceinline__ void ssim_body(const PlSsimJob *__restrict__ jobs)
 {
     __shared__ PlsCell table[PLS_TILE_CELLS * 4];
     const PlSsimJob j = jobs[blockIdx.y];
     const PlsGeom g = pls_geom(j.width, j.height);
     PlsPart p = pls_part();
     for (uint64_t tile = blockIdx.x; tile < g.tiles; tile += gridDim.x) {      /* (the same trips for every thread of the workgroup) */
-        pls_thread_cells(table, j.a, j.b, j.width, j.height, g, tile, threadIdx.x, kThreads);
+        pls_thread_cells<Visible>(table, j.a, j.b, j.width, j.height, g, tile, threadIdx.x, kThreads);
         __syncthreads();
-        pls_thread_windows(p, table, g, tile, threadIdx.x, kThreads);
+        pls_thread_windows<Visible>(p, table, g, tile, threadIdx.x, kThreads);
         __syncthreads();
     }
     /* lanes l, l + 4, l + 8, ... hold the same channel */
@@ -33,11 +36,14 @@ __global__ __launch_bounds__(kThreads) void pl_ssim(const PlSsimJob *__restrict_
     for (int off = 32; off >= 4; off >>= 1) {
         p.sum += __shfl_down(p.sum, off);
         p.mn = min(p.mn, __shfl_down(p.mn, off));
+        if (Visible) p.windows += __shfl_down(p.windows, off);
     }
     __shared__ int64_t wsum[kWaves][4];
     __shared__ int32_t wmin[kWaves][4];
+    __shared__ uint32_t wcnt[Visible ? kWaves : 1];
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (lane < 4) { wsum[wave][lane] = p.sum; wmin[wave][lane] = p.mn; }
+    if (Visible && lane == 3) wcnt[wave] = p.windows;
     __syncthreads();
     const uint32_t t = threadIdx.x;
     if (t < 4) {
@@ -49,8 +55,15 @@ __global__ __launch_bounds__(kThreads) void pl_ssim(const PlSsimJob *__restrict_
         int32_t v = PLS_ONE;
         for (int w = 0; w < kWaves; w++) v = min(v, wmin[w][t - 4]);
         if (v < PLS_ONE) atomicMin(&j.record->min_q16[t - 4], v);
+    } else if (Visible && t == 8) {
+        uint64_t v = 0;
+        for (int w = 0; w < kWaves; w++) v += wcnt[w];
+        if (v) atomicAdd(reinterpret_cast<unsigned long long *>(&j.record->windows), (unsigned long long)v);
     }
 }
+
+__global__ __launch_bounds__(kThreads) void pl_ssim(const PlSsimJob *__restrict__ jobs) { ssim_body<false>(jobs); }
+__global__ __launch_bounds__(kThreads) void pl_ssim_visible(const PlSsimJob *__restrict__ jobs) { ssim_body<true>(jobs); }
 
 /* enough workgroups to fill 256 CUs several times over, but never more than the batch needs (pl_distort.hip:distort_grid); a launch takes at most
  * 65535 images (gridDim.y) */
@@ -67,11 +80,11 @@ dim3 ssim_grid(size_t n, uint64_t max_tiles)
 
 } // namespace
 
-hipError_t pl_launch_ssim(const PlSsimJob *d_jobs, size_t n, uint64_t max_tiles, hipStream_t stream)
+hipError_t pl_launch_ssim(const PlSsimJob *d_jobs, size_t n, uint64_t max_tiles, hipStream_t stream, bool visible)
 {
     for (size_t first = 0; first < n; first += kMaxImages) {
         const size_t m = n - first < kMaxImages ? n - first : kMaxImages;
-        hipLaunchKernelGGL(pl_ssim, ssim_grid(m, max_tiles), dim3(kThreads), 0, stream, d_jobs + first);
+        hipLaunchKernelGGL(visible ? pl_ssim_visible : pl_ssim, ssim_grid(m, max_tiles), dim3(kThreads), 0, stream, d_jobs + first);
     }
     return hipGetLastError();
 }

@@ -14,8 +14,9 @@
  * window of the tile is formed from the table.
  *
  * Shared by the HIP kernel (pl_ssim.hip: a workgroup per tile, thread t runs pls_thread_cells and pls_thread_windows, the partial records are
- * merged through the wave, the workgroup and one atomic per quantity) and by tests/c/ssim_host.cpp (test infrastructure), which runs the same
- * two thread loops on the CPU under the sanitizers.
+ * merged through the wave, the workgroup and one atomic per quantity) and by tests/c/ssim_host.cpp and tests/c/visible_host.cpp (test
+ * infrastructure), which run the same two thread loops on the CPU under the sanitizers.  In visible mode (the <true> instantiations; below) the
+ * sums are those of alpha-premultiplied pixels and only windows that hold a visible pixel count.
  */
 #ifndef PL_SSIM_CORE_H
 #define PL_SSIM_CORE_H
@@ -105,8 +106,21 @@ PLS_HD void pls_load4(uint32_t out[4], const uint32_t *row, bool vec)
     }
 }
 
+/* ---- visible mode (include/pngloss_hip.h, "Measuring over visible pixels"): the same arithmetic on the alpha-premultiplied pixels pm(a), pm(b) -- pm
+ * keeps alpha and turns each of R, G, B into the integer nearest to c * A / 255, at most 255, so the PLS_*_MAX bounds hold as they stand -- and a
+ * window counts only when one of its 64 pixels has a non-zero alpha in a or in b: when the alpha sums of its four cells, which the table holds
+ * anyway, are not all zero. ---- */
+PLS_HD uint32_t pls_pm(uint32_t p)
+{
+    const uint32_t A = p >> 24;
+    return ((( p        & 255u) * A + 127u) / 255u) | ((((p >> 8) & 255u) * A + 127u) / 255u) << 8 | ((((p >> 16) & 255u) * A + 127u) / 255u) << 16 |
+           (p & 0xFF000000u);
+}
+
 /* ---- the cells of a tile.  Thread `tid` of `nthreads` takes cells tid, tid + nthreads, ... of the tile's PLS_TILE_CELLS and writes the four
- * channels of each to table[cell * 4 + c].  A cell that is not wholly inside the image belongs to no window: it is not read and not written. ---- */
+ * channels of each to table[cell * 4 + c].  A cell that is not wholly inside the image belongs to no window: it is not read and not written.
+ * Visible: the sums are those of the premultiplied pixels. ---- */
+template <bool Visible = false>
 PLS_HD void pls_thread_cells(PlsCell *table, const uint32_t *a, const uint32_t *b, uint32_t width, uint32_t height, const PlsGeom &g, uint64_t tile,
                              uint32_t tid, uint32_t nthreads)
 {
@@ -125,6 +139,8 @@ PLS_HD void pls_thread_cells(PlsCell *table, const uint32_t *a, const uint32_t *
             uint32_t pa[4], pb[4];
             pls_load4(pa, a + at, vec);
             pls_load4(pb, b + at, vec);
+            if (Visible)
+                for (int k = 0; k < 4; k++) { pa[k] = pls_pm(pa[k]); pb[k] = pls_pm(pb[k]); }
 #if defined(__HIPCC__)
 #pragma unroll
 #endif
@@ -167,9 +183,12 @@ PLS_HD int32_t pls_q16(uint32_t sa, uint32_t sb, uint32_t saa, uint32_t sbb, uin
 
 /* ---- the windows of a tile.  The partial record of a thread: its (window, channel) pairs tid, tid + nthreads, ... of the tile's PLS_TILE_ITEMS,
  * channel = pair % 4 -- so with nthreads a multiple of 4 a thread only ever sees channel tid % 4, and its record is that channel's. ---- */
-struct PlsPart { int64_t sum; int32_t mn; };
-PLS_HD PlsPart pls_part() { return PlsPart{ 0, PLS_ONE }; }
+struct PlsPart { int64_t sum; int32_t mn; uint32_t windows; };    /* windows: visible mode only, and only in the records of channel 3 */
+PLS_HD PlsPart pls_part() { return PlsPart{ 0, PLS_ONE, 0 }; }
 
+/* Visible: a window whose alpha sums (channel 3 of its four cells, both images) are all zero is skipped -- nothing added, no minimum lowered --
+ * and the others are counted, once each: by the pair of channel 3. */
+template <bool Visible = false>
 PLS_HD void pls_thread_windows(PlsPart &p, const PlsCell *table, const PlsGeom &g, uint64_t tile, uint32_t tid, uint32_t nthreads)
 {
     const uint32_t tx = (uint32_t)(tile % g.tiles_x), ty = (uint32_t)(tile / g.tiles_x);
@@ -177,6 +196,11 @@ PLS_HD void pls_thread_windows(PlsPart &p, const PlsCell *table, const PlsGeom &
         const uint32_t c = item & 3u, w = item >> 2, wx = w % PLS_TILE_WX, wy = w / PLS_TILE_WX;
         if (tx * PLS_TILE_WX + wx >= g.nx || ty * PLS_TILE_WY + wy >= g.ny) continue;
         const PlsCell *t = table + (size_t)(wy * PLS_TILE_CX + wx) * 4 + c;
+        if (Visible) {
+            const PlsCell *al = t + (3 - c);
+            if (!(al[0].s | al[4].s | al[PLS_TILE_CX * 4].s | al[PLS_TILE_CX * 4 + 4].s)) continue;
+            p.windows += c == 3 ? 1u : 0u;
+        }
         const PlsCell c00 = t[0], c10 = t[4], c01 = t[PLS_TILE_CX * 4], c11 = t[PLS_TILE_CX * 4 + 4];
         const uint32_t s = c00.s + c10.s + c01.s + c11.s;              /* both halves stay below 2^16: 64 * 255 */
         const int32_t q = pls_q16(s & 0xFFFFu, s >> 16, c00.aa + c10.aa + c01.aa + c11.aa, c00.bb + c10.bb + c01.bb + c11.bb,
@@ -190,12 +214,19 @@ PLS_HD void pls_merge(PlsPart &p, const PlsPart &o)
 {
     p.sum += o.sum;
     p.mn = o.mn < p.mn ? o.mn : p.mn;
+    p.windows += o.windows;
 }
 
 /* the record before any window is added: what the launcher writes (the kernel adds to the sums and lowers the minima) */
 inline PlSsimRecord pls_record_begin(uint32_t width, uint32_t height)
 {
     return PlSsimRecord{ pls_geom(width, height).windows, { 0, 0, 0, 0 }, { PLS_ONE, PLS_ONE, PLS_ONE, PLS_ONE }, 0 };
+}
+
+/* ... in visible mode: the kernel counts the windows as well */
+inline PlSsimRecord pls_record_begin_visible()
+{
+    return PlSsimRecord{ 0, { 0, 0, 0, 0 }, { PLS_ONE, PLS_ONE, PLS_ONE, PLS_ONE }, 0 };
 }
 
 /* Mean SSIM of a record over the channels of `channel_mask` (bit c = channel c): the one formula behind pngloss_hip_ssim_mean

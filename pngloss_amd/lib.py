@@ -199,6 +199,7 @@ ABI_SYMBOLS = (
     "pngloss_hip_last_ssim", "pngloss_hip_multi_last_ssim", "pngloss_hip_compare_batch_ssim", "pngloss_hip_ssim_mean",
     "pngloss_hip_optimize_batch_target2", "pngloss_hip_multi_optimize_batch_host_target2",
     "pngloss_hip_optimize_batch_size", "pngloss_hip_multi_optimize_batch_host_size",
+    "pngloss_hip_compare_batch_visible",
 )
 
 
@@ -282,6 +283,8 @@ def hip_lib():
             lib.pngloss_hip_compare_batch_ssim.restype = C.c_int
             lib.pngloss_hip_ssim_mean.argtypes = [C.POINTER(Ssim), C.c_uint]
             lib.pngloss_hip_ssim_mean.restype = C.c_double
+            lib.pngloss_hip_compare_batch_visible.argtypes = [C.c_void_p, C.POINTER(ImagePair), C.c_size_t, C.POINTER(Distortion), C.POINTER(Ssim), C.c_void_p]
+            lib.pngloss_hip_compare_batch_visible.restype = C.c_int
             _target_abi(lib)
             _size_abi(lib)
             _hip = lib
@@ -372,7 +375,7 @@ class HipContext:
             pass
 
     def set_option(self, name, value):
-        """pngloss_hip_set_option: e.g. ("engine", "seg" | "wg" | "auto")"""
+        """pngloss_hip_set_option: e.g. ("engine", "seg" | "wg" | "auto"), ("measure", "all" | "visible")"""
         _check(self._lib.pngloss_hip_set_option(self._ctx, name.encode(), value.encode()), "set_option")
 
     def enqueue(self, images, strength=19, bleed=2, stream=0):
@@ -581,6 +584,19 @@ class HipContext:
         out = (Ssim * max(n, 1))()
         _check(self._lib.pngloss_hip_compare_batch_ssim(self._ctx, arr, n, out, stream or None), "compare_batch_ssim")
         return [out[i] for i in range(n)]
+
+    def compare_visible(self, pairs, distortion=True, ssim=True, stream=0):
+        """pngloss_hip_compare_batch_visible: pairs as for compare(), measured over visible pixels (alpha-premultiplied channels plus alpha; whatever
+        set_option("measure", ...) says).  Returns (list of Distortion or None, list of Ssim or None): None for an output that was not asked for.
+        Synchronous."""
+        n = len(pairs)
+        arr = (ImagePair * max(n, 1))()
+        for i, (a, b, w, h) in enumerate(pairs):
+            arr[i] = ImagePair(a or None, b or None, w, h)
+        d = (Distortion * max(n, 1))() if distortion else None
+        s = (Ssim * max(n, 1))() if ssim else None
+        _check(self._lib.pngloss_hip_compare_batch_visible(self._ctx, arr, n, d, s, stream or None), "compare_batch_visible")
+        return ([d[i] for i in range(n)] if distortion else None), ([s[i] for i in range(n)] if ssim else None)
 
     def compare(self, pairs, stream=0):
         """pngloss_hip_compare_batch: pairs = sequence of (d_a_ptr, d_b_ptr, width, height), device-resident RGBA8; returns one Distortion per pair
