@@ -20,6 +20,7 @@
 #include "pl_plan.h"
 #include "pl_deal.h"
 #include "pl_layout.h"
+#include "pl_search.h"
 
 #include <chrono>
 #include <pthread.h>
@@ -1453,16 +1454,96 @@ int pngloss_hip_multi_optimize_batch_host(pngloss_hip_multi *m, const pngloss_hi
     });
 }
 
-/* ---- a strength per image from a distortion target: pl_target.h decides, this does what it says (include/pngloss_hip.h has the contract) ---- */
+/* ---- a strength per image, searched: pl_target.h and pl_size.h have the two rules, pl_search.h decides what is kept and which arena regions are copied
+ * where, and this does what they say (include/pngloss_hip.h has the contracts) ---- */
 namespace {
-struct TargetImage {
-    PlTargetSearch search;
-    pngloss_hip_result last{}, kept{};                 /* of the probe just run / of the result the image ends with */
-    pngloss_hip_distortion last_rec{}, kept_rec{};
-    pngloss_hip_ssim last_ssim{}, kept_ssim{};         /* (only with an SSIM condition) */
-    long best = -1;                                    /* the strength whose (accepted) result the arena's stash holds; -1: none */
-    long in_place = -1;                                /* the strength whose result the image itself holds; -1: the original */
-    uint32_t runs = 0;
+/* What both searches do on the device: region moves, batches and distortion measurements on the search arena (ctx->d_target, laid out as `lay`).  The host
+ * tables stay alive until the call's last synchronisation: asynchronous copies read them. */
+struct SearchDevice {
+    pngloss_hip_ctx *ctx;
+    const pngloss_hip_image_desc *images;
+    const PlTargetLayout &lay;
+    long bleed;
+    hipStream_t stream;
+    std::vector<std::vector<PlMoveJob>> move_tables;
+    std::vector<std::vector<PlDistortJob>> distort_tables;
+
+    char *at(size_t offset) const { return ctx->d_target + offset; }
+    void *address(uint32_t i, PlArenaRegion r) const
+    {
+        const PlTargetImage &m = lay.image[i];
+        switch (r) {
+        case PLA_IMAGE: return images[i].d_rgba;
+        case PLA_FILTERS: return images[i].d_row_filters;
+        case PLA_ORIG: return at(m.orig);
+        case PLA_BEST: return at(m.best);
+        case PLA_BEST_FILTERS: return at(m.best_filters);
+        case PLA_ROWS: return at(m.rows);
+        case PLA_IDS: return at(m.ids);
+        case PLA_BEST_ROWS: return at(m.best_rows);
+        case PLA_BEST_IDS: return at(m.best_ids);
+        default: return nullptr;
+        }
+    }
+    /* one launch of pl_move for a table of jobs */
+    int move(std::vector<PlMoveJob> jobs)
+    {
+        if (jobs.empty()) return PNGLOSS_SUCCESS;
+        uint64_t max_bytes = 0;
+        for (const PlMoveJob &j : jobs) max_bytes = std::max(max_bytes, j.bytes);
+        move_tables.push_back(std::move(jobs));
+        const std::vector<PlMoveJob> &tb = move_tables.back();
+        PlMoveJob *const d_moves = reinterpret_cast<PlMoveJob *>(at(lay.moves));
+        PL_CHECK(hipMemcpyAsync(d_moves, tb.data(), sizeof(PlMoveJob) * tb.size(), hipMemcpyHostToDevice, stream));
+        PL_CHECK(pl_launch_move(d_moves, tb.size(), max_bytes, stream));
+        return PNGLOSS_SUCCESS;
+    }
+    /* ... for the moves pl_search.h asks for: each with its addresses and its bytes; one of 0 bytes is no job */
+    int move(const std::vector<PlSearchMove> &moves)
+    {
+        std::vector<PlMoveJob> jobs;
+        for (const PlSearchMove &m : moves) {
+            const pngloss_hip_image_desc &im = images[m.image];
+            const uint64_t bytes = pl_search_region_bytes(m.src, im.width, im.height, im.d_row_filters != nullptr, lay.image[m.image].pitch);
+            if (bytes) jobs.push_back(PlMoveJob{ address(m.image, m.src), address(m.image, m.dst), bytes });
+        }
+        return move(std::move(jobs));
+    }
+    /* one ordinary batch: the images `who` at `strength`, through the entry the synchronous call uses.  emits: nullptr, or where each one's scanlines go */
+    int run(uint32_t strength, const std::vector<uint32_t> &who, const EmitTarget *emits, std::vector<pngloss_hip_result> &res)
+    {
+        std::vector<pngloss_hip_image_desc> descs(who.size());
+        res.assign(who.size(), pngloss_hip_result{});
+        for (size_t k = 0; k < who.size(); k++) descs[k] = images[who[k]];
+        ctx->sync_call = true; ctx->three_groups_ok = true;
+        int rc = enqueue(ctx, descs.data(), descs.size(), nullptr, strength, bleed, stream, emits);
+        ctx->sync_call = false; ctx->three_groups_ok = false;
+        if (rc == PNGLOSS_SUCCESS) rc = finish(ctx, res.data(), res.size());
+        return pl_rc_is_hard(rc) ? rc : PNGLOSS_SUCCESS;           /* (single images that failed say so in their status) */
+    }
+    /* one launch of pl_distort: the images `who` against the search's own originals, the records on their way into got[0 .. who.size()) -- the caller
+     * synchronises */
+    int distort(const std::vector<uint32_t> &who, bool visible, pngloss_hip_distortion *got)
+    {
+        distort_tables.emplace_back(who.size());
+        std::vector<PlDistortJob> &dj = distort_tables.back();
+        PlDistortJob *const d_dj = reinterpret_cast<PlDistortJob *>(at(lay.jobs));
+        PlDistortRecord *const d_rec = reinterpret_cast<PlDistortRecord *>(at(lay.records));
+        uint64_t max_pixels = 0;
+        for (size_t k = 0; k < who.size(); k++) {
+            const size_t i = who[k];
+            dj[k].keep = reinterpret_cast<uint32_t *>(at(lay.image[i].orig));
+            dj[k].img = static_cast<const uint32_t *>(images[i].d_rgba);
+            dj[k].pixels = (uint64_t)images[i].width * images[i].height;
+            dj[k].record = d_rec + k;
+            max_pixels = std::max(max_pixels, dj[k].pixels);
+        }
+        PL_CHECK(hipMemcpyAsync(d_dj, dj.data(), sizeof(PlDistortJob) * dj.size(), hipMemcpyHostToDevice, stream));
+        PL_CHECK(hipMemsetAsync(d_rec, 0, sizeof(PlDistortRecord) * dj.size(), stream));
+        PL_CHECK(pl_launch_distort(d_dj, dj.size(), max_pixels, stream, visible));
+        PL_CHECK(hipMemcpyAsync(got, d_rec, sizeof(PlDistortRecord) * dj.size(), hipMemcpyDeviceToHost, stream));
+        return PNGLOSS_SUCCESS;
+    }
 };
 }
 
@@ -1476,69 +1557,26 @@ static int target_search(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *ima
     /* whatever happens: the caller's option back, and no "last batch" to index */
     SearchGuard guard{ ctx, ctx->opt_distortion, ctx->opt_ssim };
     ctx->opt_distortion = ctx->opt_ssim = false;       /* the search measures against its own originals (the keep arena is laid out afresh by every enqueue) */
-    char *const arena = ctx->d_target;
-    PlMoveJob *const d_moves = reinterpret_cast<PlMoveJob *>(arena + lay.moves);
-    PlDistortJob *const d_dj = reinterpret_cast<PlDistortJob *>(arena + lay.jobs);
-    PlDistortRecord *const d_rec = reinterpret_cast<PlDistortRecord *>(arena + lay.records);
-    PlSsimJob *const d_sj = reinterpret_cast<PlSsimJob *>(arena + lay.ssim_jobs);
-    PlSsimRecord *const d_srec = reinterpret_cast<PlSsimRecord *>(arena + lay.ssim_records);
-    std::vector<TargetImage> st(n);
-    std::vector<PlTargetSearch> searches(n);
+    SearchDevice dev{ ctx, images, lay, bleed, stream, {}, {} };
+    PlSsimJob *const d_sj = reinterpret_cast<PlSsimJob *>(dev.at(lay.ssim_jobs));
+    PlSsimRecord *const d_srec = reinterpret_cast<PlSsimRecord *>(dev.at(lay.ssim_records));
+    std::vector<PlTargetTrack> st(n);
     for (size_t i = 0; i < n; i++) st[i].search = pl_target_begin(t.max_strength);
-    auto px_bytes = [&](size_t i) { return (uint64_t)images[i].width * images[i].height * 4; };
-    auto filter_bytes = [&](size_t i) { return (uint64_t)((images[i].width && images[i].d_row_filters) ? images[i].height : 0); };
-    auto add = [](std::vector<PlMoveJob> &v, const void *src, void *dst, uint64_t bytes) { if (bytes) v.push_back(PlMoveJob{ src, dst, bytes }); };
-    /* (the host tables stay alive until the call's last synchronisation: asynchronous copies read them) */
-    std::vector<std::vector<PlMoveJob>> move_tables;
-    std::vector<std::vector<PlDistortJob>> distort_tables;
-    std::vector<std::vector<PlSsimJob>> ssim_tables;
+    std::vector<std::vector<PlSsimJob>> ssim_tables;   /* (alive until the last synchronisation, like the tables of `dev`) */
     std::vector<std::vector<PlSsimRecord>> ssim_begins;
-    /* one launch of pl_move for a table of jobs */
-    auto move = [&](std::vector<PlMoveJob> jobs) -> int {
-        if (jobs.empty()) return PNGLOSS_SUCCESS;
-        uint64_t max_bytes = 0;
-        for (const PlMoveJob &j : jobs) max_bytes = std::max(max_bytes, j.bytes);
-        move_tables.push_back(std::move(jobs));
-        const std::vector<PlMoveJob> &tb = move_tables.back();
-        PL_CHECK(hipMemcpyAsync(d_moves, tb.data(), sizeof(PlMoveJob) * tb.size(), hipMemcpyHostToDevice, stream));
-        PL_CHECK(pl_launch_move(d_moves, tb.size(), max_bytes, stream));
-        return PNGLOSS_SUCCESS;
-    };
-    /* one ordinary batch: the images `who` at `strength`, through the entry the synchronous call uses */
     auto run_group = [&](uint32_t strength, const std::vector<uint32_t> &who) -> int {
-        std::vector<pngloss_hip_image_desc> descs(who.size());
-        std::vector<pngloss_hip_result> res(who.size());
-        for (size_t k = 0; k < who.size(); k++) descs[k] = images[who[k]];
-        ctx->sync_call = true; ctx->three_groups_ok = true;
-        int rc = enqueue(ctx, descs.data(), descs.size(), nullptr, strength, bleed, stream);
-        ctx->sync_call = false; ctx->three_groups_ok = false;
-        if (rc == PNGLOSS_SUCCESS) rc = finish(ctx, res.data(), res.size());
-        if (rc != PNGLOSS_SUCCESS && rc != PNGLOSS_INTERNAL_ABORT) return rc;      /* (single images that failed say so in their status) */
-        for (size_t k = 0; k < who.size(); k++) {
-            TargetImage &s = st[who[k]];
-            s.last = res[k]; s.in_place = (long)strength; s.runs++;
-        }
+        std::vector<pngloss_hip_result> res;
+        const int rc = dev.run(strength, who, nullptr, res);
+        if (rc) return rc;
+        for (size_t k = 0; k < who.size(); k++) pl_search_ran(st[who[k]], strength, res[k]);
         return PNGLOSS_SUCCESS;
     };
     /* one launch of pl_distort -- and, with an SSIM condition, one of pl_ssim --: the images `who` against the search's own originals */
     auto measure = [&](const std::vector<uint32_t> &who) -> int {
         if (who.empty()) return PNGLOSS_SUCCESS;
-        distort_tables.emplace_back(who.size());
-        std::vector<PlDistortJob> &dj = distort_tables.back();
-        uint64_t max_pixels = 0;
-        for (size_t k = 0; k < who.size(); k++) {
-            const size_t i = who[k];
-            dj[k].keep = reinterpret_cast<uint32_t *>(arena + lay.image[i].orig);
-            dj[k].img = static_cast<const uint32_t *>(images[i].d_rgba);
-            dj[k].pixels = (uint64_t)images[i].width * images[i].height;
-            dj[k].record = d_rec + k;
-            max_pixels = std::max(max_pixels, dj[k].pixels);
-        }
         std::vector<pngloss_hip_distortion> got(who.size());
-        PL_CHECK(hipMemcpyAsync(d_dj, dj.data(), sizeof(PlDistortJob) * dj.size(), hipMemcpyHostToDevice, stream));
-        PL_CHECK(hipMemsetAsync(d_rec, 0, sizeof(PlDistortRecord) * dj.size(), stream));
-        PL_CHECK(pl_launch_distort(d_dj, dj.size(), max_pixels, stream, visible));
-        PL_CHECK(hipMemcpyAsync(got.data(), d_rec, sizeof(PlDistortRecord) * dj.size(), hipMemcpyDeviceToHost, stream));
+        const int rc = dev.distort(who, visible, got.data());
+        if (rc) return rc;
         std::vector<pngloss_hip_ssim> sgot(want_ssim ? who.size() : 0);
         if (want_ssim) {
             ssim_tables.emplace_back(who.size());
@@ -1548,7 +1586,7 @@ static int target_search(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *ima
             std::vector<uint32_t> w(who.size()), h(who.size());
             for (size_t k = 0; k < who.size(); k++) {
                 const size_t i = who[k];
-                a[k] = arena + lay.image[i].orig; b[k] = images[i].d_rgba;
+                a[k] = dev.address(who[k], PLA_ORIG); b[k] = images[i].d_rgba;
                 w[k] = images[i].width; h[k] = images[i].height;
             }
             const uint64_t max_tiles = fill_ssim_jobs(sj.data(), ssim_begins.back().data(), d_srec, who.size(), a.data(), b.data(), w.data(), h.data(), visible);
@@ -1559,90 +1597,41 @@ static int target_search(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *ima
         }
         PL_CHECK(hipStreamSynchronize(stream));
         for (size_t k = 0; k < who.size(); k++) {
-            st[who[k]].last_rec = got[k];
-            if (want_ssim) st[who[k]].last_ssim = sgot[k];
+            st[who[k]].last.rec = got[k];
+            if (want_ssim) st[who[k]].last.ssim = sgot[k];
         }
         return PNGLOSS_SUCCESS;
     };
 
-    /* the originals, before the first probe rewrites the images in place */
-    int rc;
-    {
-        std::vector<PlMoveJob> save;
-        for (size_t i = 0; i < n; i++) add(save, images[i].d_rgba, arena + lay.image[i].orig, px_bytes(i));
-        rc = move(std::move(save));
-        if (rc) return rc;
-    }
+    int rc = dev.move(pl_search_open(n));
+    if (rc) return rc;
     for (;;) {
-        for (size_t i = 0; i < n; i++) searches[i] = st[i].search;
-        const auto groups = pl_target_groups(searches);
-        if (groups.empty()) break;
-        std::vector<PlMoveJob> back, stash;
-        std::vector<uint32_t> probed;
-        for (const auto &g : groups)
-            for (uint32_t i : g.second) {
-                if (st[i].in_place >= 0) add(back, arena + lay.image[i].orig, images[i].d_rgba, px_bytes(i));
-                probed.push_back(i);
-            }
-        rc = move(std::move(back));
-        for (size_t g = 0; g < groups.size() && rc == PNGLOSS_SUCCESS; g++) rc = run_group(groups[g].first, groups[g].second);      /* one after the other: a context takes one batch at a time */
-        if (rc == PNGLOSS_SUCCESS) rc = measure(probed);
+        const PlSearchRound round = pl_search_round(st);
+        if (round.groups.empty()) break;
+        rc = dev.move(round.back);
+        for (size_t g = 0; g < round.groups.size() && rc == PNGLOSS_SUCCESS; g++) rc = run_group(round.groups[g].first, round.groups[g].second);      /* one after the other: a context takes one batch at a time */
+        if (rc == PNGLOSS_SUCCESS) rc = measure(round.probed);
         if (rc) return rc;
-        for (uint32_t i : probed) {
-            TargetImage &s = st[i];
-            if (s.last.status != 0) {                            /* ends this image's search: it keeps this probe's result and status */
-                pl_target_fail(s.search);
-                s.kept = s.last; s.kept_rec = s.last_rec; s.kept_ssim = s.last_ssim;
-                continue;
-            }
-            const bool accepted = pl_target_accept2(t, s.last_rec, s.last_ssim, s.last.status, s.last.bytes_per_pixel);
-            const uint32_t strength = s.search.next;
-            pl_target_step(s.search, accepted);
-            if (!accepted) continue;
-            s.kept = s.last; s.kept_rec = s.last_rec; s.kept_ssim = s.last_ssim; s.best = (long)strength;
-            if (s.search.done) continue;                         /* (the chosen strength's result is in place) */
-            add(stash, images[i].d_rgba, arena + lay.image[i].best, px_bytes(i));
-            add(stash, images[i].d_row_filters, arena + lay.image[i].best_filters, filter_bytes(i));
-        }
-        rc = move(std::move(stash));
+        rc = dev.move(pl_target_settle(st, round.probed, t));
         if (rc) return rc;
     }
     /* the kept results back into the images whose last probe was refused; an image with no accepted probe gets strength 0, run once */
-    std::vector<PlMoveJob> fin;
-    std::vector<uint32_t> zero;
-    for (size_t i = 0; i < n; i++) {
-        TargetImage &s = st[i];
-        if (s.search.failed) continue;
-        if (s.in_place == (long)s.search.chosen) {
-            if (s.best != (long)s.search.chosen) { s.kept = s.last; s.kept_rec = s.last_rec; s.kept_ssim = s.last_ssim; }
-            continue;
-        }
-        if (s.best == (long)s.search.chosen) {
-            if (commit) {
-                add(fin, arena + lay.image[i].best, images[i].d_rgba, px_bytes(i));
-                add(fin, arena + lay.image[i].best_filters, images[i].d_row_filters, filter_bytes(i));
-            }
-            continue;
-        }
-        zero.push_back((uint32_t)i);
-        s.kept = pngloss_hip_result{ 0, 0, 0, 0, 0 }; s.kept_rec = pngloss_hip_distortion{}; s.kept_ssim = pngloss_hip_ssim{};
-        if (commit) add(fin, arena + lay.image[i].orig, images[i].d_rgba, px_bytes(i));
-    }
-    rc = move(std::move(fin));
-    if (rc == PNGLOSS_SUCCESS && commit && !zero.empty()) {
-        rc = run_group(0, zero);
-        if (rc == PNGLOSS_SUCCESS) rc = measure(zero);
-        for (uint32_t i : zero) { st[i].kept = st[i].last; st[i].kept_rec = st[i].last_rec; st[i].kept_ssim = st[i].last_ssim; }
+    const PlTargetClose close = pl_target_close(st, commit);
+    rc = dev.move(close.fin);
+    if (rc == PNGLOSS_SUCCESS && commit && !close.zero.empty()) {
+        rc = run_group(0, close.zero);
+        if (rc == PNGLOSS_SUCCESS) rc = measure(close.zero);
+        pl_target_reran(st, close.zero);
     }
     if (rc) return rc;
     PL_CHECK(hipStreamSynchronize(stream));
     int worst = PNGLOSS_SUCCESS;
     for (size_t i = 0; i < n; i++) {
-        const TargetImage &s = st[i];
-        if (results) results[i] = s.kept;
-        if (reports) reports[i] = pngloss_hip_target_report{ s.search.chosen, s.search.probes, s.runs, 0, s.kept_rec };
-        if (ssim_out && want_ssim) ssim_out[i] = s.kept_ssim;
-        if (s.kept.status) worst = PNGLOSS_INTERNAL_ABORT;
+        const PlTargetTrack &s = st[i];
+        if (results) results[i] = s.kept.result;
+        if (reports) reports[i] = pngloss_hip_target_report{ s.search.chosen, s.search.probes, s.runs, 0, s.kept.rec };
+        if (ssim_out && want_ssim) ssim_out[i] = s.kept.ssim;
+        if (s.kept.result.status) worst = PNGLOSS_INTERNAL_ABORT;
     }
     return worst;
 }
@@ -1737,20 +1726,7 @@ int pngloss_hip_multi_optimize_batch_host_target2(pngloss_hip_multi *m, const pn
     });
 }
 
-/* ---- a strength per image from a byte budget: pl_size.h decides, this does what it says (include/pngloss_hip.h has the contract) ---- */
-namespace {
-struct SizeImage {
-    PlSizeSearch search;
-    pngloss_hip_result last{}, kept{};                 /* of the probe just run / of the result the image ends with */
-    uint32_t last_flags = 0, kept_flags = 0;           /* their out-flags words: colour type and bytes per pixel of the scanlines */
-    PlSizeRecord last_size{}, kept_size{};             /* their measured streams */
-    long best = -1;                                    /* the strength whose (accepted) result the arena's stash holds; -1: none */
-    long in_place = -1;                                /* the strength whose result the image itself holds; -1: the original */
-    bool kept_in_stash = false;                        /* the kept result's scanlines are the stash's (else the probe region's) */
-    uint32_t runs = 0;
-};
-}
-
+/* ---- a strength per image from a byte budget: pl_size.h has the rule, pl_search.h the bookkeeping (SearchDevice: in front of target_search) ---- */
 /* images: device-resident; the arena (ctx->d_target) has been grown to lay.total, laid out with a scanline region (and, with `streams`, the best
  * result's).  commit: at the end every image holds the result of its chosen strength and `streams` (may be nullptr) are written; else the images are
  * left as the last probes left them (the host form runs the chosen strengths through the host-window path). */
@@ -1761,162 +1737,78 @@ static int size_search(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *image
     SearchGuard guard{ ctx, ctx->opt_distortion, ctx->opt_ssim };
     ctx->opt_distortion = ctx->opt_ssim = false;       /* the search measures against its own originals */
     const bool want_streams = commit && streams;
-    char *const arena = ctx->d_target;
-    PlMoveJob *const d_moves = reinterpret_cast<PlMoveJob *>(arena + lay.moves);
-    PlDistortJob *const d_dj = reinterpret_cast<PlDistortJob *>(arena + lay.jobs);
-    PlDistortRecord *const d_rec = reinterpret_cast<PlDistortRecord *>(arena + lay.records);
-    std::vector<SizeImage> st(n);
-    std::vector<PlSizeSearch> searches(n);
-    auto px_bytes = [&](size_t i) { return (uint64_t)images[i].width * images[i].height * 4; };
-    auto filter_bytes = [&](size_t i) { return (uint64_t)((images[i].width && images[i].d_row_filters) ? images[i].height : 0); };
-    auto row_bytes = [&](size_t i) { return (uint64_t)lay.image[i].pitch * images[i].height; };
-    auto id_bytes = [&](size_t i) { return (uint64_t)(lay.image[i].pitch ? images[i].height : 0); };
-    for (size_t i = 0; i < n; i++) st[i].search = pl_size_begin(t.max_strength, px_bytes(i) != 0);
-    auto add = [](std::vector<PlMoveJob> &v, const void *src, void *dst, uint64_t bytes) { if (bytes) v.push_back(PlMoveJob{ src, dst, bytes }); };
-    std::vector<std::vector<PlMoveJob>> move_tables;   /* (the host tables stay alive until the call's last synchronisation: asynchronous copies read them) */
-    auto move = [&](std::vector<PlMoveJob> jobs) -> int {
-        if (jobs.empty()) return PNGLOSS_SUCCESS;
-        uint64_t max_bytes = 0;
-        for (const PlMoveJob &j : jobs) max_bytes = std::max(max_bytes, j.bytes);
-        move_tables.push_back(std::move(jobs));
-        const std::vector<PlMoveJob> &tb = move_tables.back();
-        PL_CHECK(hipMemcpyAsync(d_moves, tb.data(), sizeof(PlMoveJob) * tb.size(), hipMemcpyHostToDevice, stream));
-        PL_CHECK(pl_launch_move(d_moves, tb.size(), max_bytes, stream));
-        return PNGLOSS_SUCCESS;
-    };
+    SearchDevice dev{ ctx, images, lay, bleed, stream, {}, {} };
+    std::vector<PlSizeTrack> st(n);
+    auto has_pixels = [&](size_t i) { return images[i].width != 0 && images[i].height != 0; };
+    for (size_t i = 0; i < n; i++) st[i].search = pl_size_begin(t.max_strength, has_pixels(i));
     /* one ordinary batch WITH emit descriptors: the images `who` at `strength`, their scanlines into the arena's probe regions */
     auto run_group = [&](uint32_t strength, const std::vector<uint32_t> &who) -> int {
-        std::vector<pngloss_hip_image_desc> descs(who.size());
         std::vector<EmitTarget> emits(who.size());
-        std::vector<pngloss_hip_result> res(who.size());
+        std::vector<pngloss_hip_result> res;
         for (size_t k = 0; k < who.size(); k++) {
-            const PlTargetImage &m = lay.image[who[k]];
-            descs[k] = images[who[k]];
-            emits[k] = EmitTarget{ m.pitch ? arena + m.ids : nullptr, m.pitch ? arena + m.rows : nullptr, m.pitch };
+            const uint32_t pitch = lay.image[who[k]].pitch;
+            emits[k] = EmitTarget{ pitch ? dev.address(who[k], PLA_IDS) : nullptr, pitch ? dev.address(who[k], PLA_ROWS) : nullptr, pitch };
         }
-        ctx->sync_call = true; ctx->three_groups_ok = true;
-        int rc = enqueue(ctx, descs.data(), descs.size(), nullptr, strength, bleed, stream, emits.data());
-        ctx->sync_call = false; ctx->three_groups_ok = false;
-        if (rc == PNGLOSS_SUCCESS) rc = finish(ctx, res.data(), res.size());
-        if (rc != PNGLOSS_SUCCESS && rc != PNGLOSS_INTERNAL_ABORT) return rc;      /* (single images that failed say so in their status) */
+        int rc = dev.run(strength, who, emits.data(), res);
+        if (rc) return rc;
         /* the group's out-flags words (colour type of the scanlines): gathered on the device, ONE copy */
         std::vector<PlMoveJob> gather;
-        uint32_t *const d_flags = reinterpret_cast<uint32_t *>(arena + lay.flags);
+        uint32_t *const d_flags = reinterpret_cast<uint32_t *>(dev.at(lay.flags));
         for (size_t k = 0; k < who.size(); k++) gather.push_back(PlMoveJob{ ctx->h_jobs[k].out_flags, d_flags + k, sizeof(uint32_t) });
         std::vector<uint32_t> flags(who.size(), 0);
-        rc = move(std::move(gather));
+        rc = dev.move(std::move(gather));
         if (rc) return rc;
         PL_CHECK(hipMemcpyAsync(flags.data(), d_flags, sizeof(uint32_t) * who.size(), hipMemcpyDeviceToHost, stream));
         PL_CHECK(hipStreamSynchronize(stream));
         for (size_t k = 0; k < who.size(); k++) {
-            SizeImage &s = st[who[k]];
-            s.last = res[k]; s.in_place = (long)strength; s.runs++;
-            s.last_flags = (res[k].status == 0 && emits[k].pitch) ? flags[k] : 0;
+            pl_search_ran(st[who[k]], strength, res[k]);
+            st[who[k]].last.flags = (res[k].status == 0 && emits[k].pitch) ? flags[k] : 0;
         }
         return PNGLOSS_SUCCESS;
     };
     /* what the deflate is to look at: image i's scanlines in the probe region or in the stash, in the colour type `flags` says */
     auto deflate_image = [&](size_t i, bool stash, uint32_t flags) {
-        const PlTargetImage &m = lay.image[i];
         pl_deflate_image d{};
-        d.d_filter_types = reinterpret_cast<const uint8_t *>(arena + (stash ? m.best_ids : m.ids));
-        d.d_scanlines = reinterpret_cast<const uint8_t *>(arena + (stash ? m.best_rows : m.rows));
-        d.pitch = m.pitch;
+        d.d_filter_types = static_cast<const uint8_t *>(dev.address((uint32_t)i, stash ? PLA_BEST_IDS : PLA_IDS));
+        d.d_scanlines = static_cast<const uint8_t *>(dev.address((uint32_t)i, stash ? PLA_BEST_ROWS : PLA_ROWS));
+        d.pitch = lay.image[i].pitch;
         d.rowbytes = images[i].width * pl_emit_bpp_of(flags);
         d.height = images[i].height;
         return d;
     };
 
-    /* the originals, before the first probe rewrites the images in place */
-    int rc;
-    {
-        std::vector<PlMoveJob> save;
-        for (size_t i = 0; i < n; i++) add(save, images[i].d_rgba, arena + lay.image[i].orig, px_bytes(i));
-        rc = move(std::move(save));
-        if (rc) return rc;
-    }
+    int rc = dev.move(pl_search_open(n));
+    if (rc) return rc;
     for (;;) {
-        for (size_t i = 0; i < n; i++) searches[i] = st[i].search;
-        const auto groups = pl_size_groups(searches);
-        if (groups.empty()) break;
-        std::vector<PlMoveJob> back, stash;
-        std::vector<uint32_t> probed;
-        for (const auto &g : groups)
-            for (uint32_t i : g.second) {
-                if (st[i].in_place >= 0) add(back, arena + lay.image[i].orig, images[i].d_rgba, px_bytes(i));
-                probed.push_back(i);
-            }
-        rc = move(std::move(back));
-        for (size_t g = 0; g < groups.size() && rc == PNGLOSS_SUCCESS; g++) rc = run_group(groups[g].first, groups[g].second);      /* one after the other: a context takes one batch at a time */
+        const PlSearchRound round = pl_search_round(st);
+        if (round.groups.empty()) break;
+        rc = dev.move(round.back);
+        for (size_t g = 0; g < round.groups.size() && rc == PNGLOSS_SUCCESS; g++) rc = run_group(round.groups[g].first, round.groups[g].second);      /* one after the other: a context takes one batch at a time */
         if (rc) return rc;
         /* ONE measuring deflate over every image probed in this round whose run succeeded */
         std::vector<pl_deflate_image> dz;
         std::vector<uint32_t> measured;
-        for (uint32_t i : probed)
-            if (st[i].last.status == 0) { dz.push_back(deflate_image(i, false, st[i].last_flags)); measured.push_back(i); }
+        for (uint32_t i : round.probed)
+            if (st[i].last.result.status == 0) { dz.push_back(deflate_image(i, false, st[i].last.flags)); measured.push_back(i); }
         std::vector<PlSizeRecord> sizes(dz.size());
         if (!dz.empty()) {
             rc = deflate_rc(pl_deflate_measure(dz.data(), dz.size(), sizes.data(), stream));
             if (rc) return rc;
         }
-        for (size_t k = 0; k < measured.size(); k++) st[measured[k]].last_size = sizes[k];
-        for (uint32_t i : probed) {
-            SizeImage &s = st[i];
-            if (s.last.status != 0) {                            /* ends this image's search: it keeps this probe's result and status */
-                pl_size_fail(s.search);
-                s.kept = s.last; s.kept_flags = 0; s.kept_size = PlSizeRecord{ 0, 1, { 0, 0, 0 } }; s.kept_in_stash = false;
-                continue;
-            }
-            const bool accepted = pl_size_accept(s.last.status, s.last_size.bytes, t.max_bytes[i]);
-            const bool first = s.search.first;
-            const uint32_t strength = s.search.next;
-            pl_size_step(s.search, accepted);
-            if (!accepted) {
-                if (first) { s.kept = s.last; s.kept_flags = s.last_flags; s.kept_size = s.last_size; s.kept_in_stash = false; }    /* M does not fit: the image keeps the M result */
-                continue;
-            }
-            /* the accepted probe with the smallest strength so far: every accepted probe lies below the one before it */
-            s.kept = s.last; s.kept_flags = s.last_flags; s.kept_size = s.last_size; s.best = (long)strength; s.kept_in_stash = false;
-            if (s.search.done) continue;                         /* (the chosen strength's result is in place) */
-            add(stash, images[i].d_rgba, arena + lay.image[i].best, px_bytes(i));
-            add(stash, images[i].d_row_filters, arena + lay.image[i].best_filters, filter_bytes(i));
-            if (want_streams) {
-                add(stash, arena + lay.image[i].rows, arena + lay.image[i].best_rows, row_bytes(i));
-                add(stash, arena + lay.image[i].ids, arena + lay.image[i].best_ids, id_bytes(i));
-                s.kept_in_stash = true;
-            }
-        }
-        rc = move(std::move(stash));
+        for (size_t k = 0; k < measured.size(); k++) st[measured[k]].last.size = sizes[k];
+        rc = dev.move(pl_size_settle(st, round.probed, t.max_bytes, want_streams));
         if (rc) return rc;
     }
     /* the kept results back into the images whose last probe was refused */
-    std::vector<PlMoveJob> fin;
-    for (size_t i = 0; i < n; i++) {
-        SizeImage &s = st[i];
-        if (s.search.failed || !px_bytes(i) || s.in_place == (long)s.search.chosen) continue;
-        if (commit) {                                            /* (s.best == chosen: the rule ends on an accepted probe) */
-            add(fin, arena + lay.image[i].best, images[i].d_rgba, px_bytes(i));
-            add(fin, arena + lay.image[i].best_filters, images[i].d_row_filters, filter_bytes(i));
-        }
-    }
-    rc = move(std::move(fin));
+    rc = dev.move(pl_size_close(st, commit));
     if (rc) return rc;
     /* one launch of pl_distort: the kept results against the search's own originals, for the reports */
     std::vector<pngloss_hip_distortion> recs(n);
     if (commit && n) {
-        std::vector<PlDistortJob> dj(n);
-        uint64_t max_pixels = 0;
-        for (size_t i = 0; i < n; i++) {
-            dj[i].keep = reinterpret_cast<uint32_t *>(arena + lay.image[i].orig);
-            dj[i].img = static_cast<const uint32_t *>(images[i].d_rgba);
-            dj[i].pixels = (uint64_t)images[i].width * images[i].height;
-            dj[i].record = d_rec + i;
-            max_pixels = std::max(max_pixels, dj[i].pixels);
-        }
-        PL_CHECK(hipMemcpyAsync(d_dj, dj.data(), sizeof(PlDistortJob) * n, hipMemcpyHostToDevice, stream));
-        PL_CHECK(hipMemsetAsync(d_rec, 0, sizeof(PlDistortRecord) * n, stream));
-        PL_CHECK(pl_launch_distort(d_dj, n, max_pixels, stream));
-        PL_CHECK(hipMemcpyAsync(recs.data(), d_rec, sizeof(PlDistortRecord) * n, hipMemcpyDeviceToHost, stream));
+        std::vector<uint32_t> all(n);
+        for (size_t i = 0; i < n; i++) all[i] = (uint32_t)i;
+        rc = dev.distort(all, false, recs.data());
+        if (rc) return rc;
     }
     PL_CHECK(hipStreamSynchronize(stream));
     /* one writing deflate over the kept results' scanlines: each stream's size is the measured size of the kept probe */
@@ -1925,9 +1817,9 @@ static int size_search(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *image
         std::vector<size_t> who;
         for (size_t i = 0; i < n; i++) {
             streams[i].size = 0; streams[i].color_type = 6; streams[i].blocks[0] = streams[i].blocks[1] = streams[i].blocks[2] = 0;
-            if (!px_bytes(i) || st[i].kept.status != 0) continue;
-            streams[i].color_type = pl_color_type_of(st[i].kept_flags);
-            pl_deflate_image d = deflate_image(i, st[i].kept_in_stash, st[i].kept_flags);
+            if (!has_pixels(i) || st[i].kept.result.status != 0) continue;
+            streams[i].color_type = pl_color_type_of(st[i].kept.flags);
+            pl_deflate_image d = deflate_image(i, st[i].kept_in_stash, st[i].kept.flags);
             d.out = streams[i].data;
             d.out_capacity = streams[i].capacity;
             dz.push_back(d);
@@ -1941,25 +1833,25 @@ static int size_search(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *image
             pngloss_hip_zstream &z = streams[who[k]];
             z.size = dz[k].out_size;
             z.blocks[0] = dz[k].blocks_stored; z.blocks[1] = dz[k].blocks_fixed; z.blocks[2] = dz[k].blocks_dynamic;
-            if ((uint64_t)z.size != st[who[k]].kept_size.bytes) {
-                std::fprintf(stderr, "pngloss_hip: image %zu: the written stream has %zu bytes, the measured one had %llu\n", who[k], z.size, (unsigned long long)st[who[k]].kept_size.bytes);
+            if ((uint64_t)z.size != st[who[k]].kept.size.bytes) {
+                std::fprintf(stderr, "pngloss_hip: image %zu: the written stream has %zu bytes, the measured one had %llu\n", who[k], z.size, (unsigned long long)st[who[k]].kept.size.bytes);
                 return PNGLOSS_HIP_ERROR;
             }
         }
     }
     int worst = PNGLOSS_SUCCESS;
     for (size_t i = 0; i < n; i++) {
-        const SizeImage &s = st[i];
-        if (results) results[i] = s.kept;
+        const PlSizeTrack &s = st[i];
+        if (results) results[i] = s.kept.result;
         if (reports) {
             pngloss_hip_size_report r{};
             r.strength = s.search.chosen; r.probes = s.search.probes; r.runs = s.runs; r.reached = s.search.reached;
-            r.bytes = s.kept_size.bytes;
-            r.color_type = pl_color_type_of(s.kept_flags);
+            r.bytes = s.kept.size.bytes;
+            r.color_type = pl_color_type_of(s.kept.flags);
             r.distortion = recs[i];
             reports[i] = r;
         }
-        if (s.kept.status) worst = PNGLOSS_INTERNAL_ABORT;
+        if (s.kept.result.status) worst = PNGLOSS_INTERNAL_ABORT;
     }
     return worst;
 }

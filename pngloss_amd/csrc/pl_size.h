@@ -3,8 +3,9 @@
  * equivalent (the reference tool takes a strength and reports the size it got).
  *
  * Plain C++ without HIP types, like pl_target.h, whose search this mirrors in the other direction: everything the search DECIDES is here, so that
- * tests/c/size_host.cpp drives it on the CPU.  pl_host.hip does what these functions say: it restores originals, runs the groups through
- * enqueue() / finish() with emit descriptors, measures the emitted scanlines with pl_deflate_measure and moves results with pl_move.
+ * tests/c/size_host.cpp drives it on the CPU.  pl_search.h keeps the books of a whole search on top of these functions (what is kept, which
+ * regions are copied where), and pl_host.hip does what the two say: it runs the groups through enqueue() / finish() with emit descriptors,
+ * measures the emitted scanlines with pl_deflate_measure and carries out the moves with pl_move.
  *
  * A probe is ACCEPTED when its status is 0 and its stream -- the complete zlib stream, 78 DA ... Adler-32 -- has at most max_bytes bytes.
  * The size is not guaranteed to be monotone in the strength, so the result is defined by this procedure, per image (include/pngloss_hip.h states
@@ -20,6 +21,7 @@
 #define PL_SIZE_H
 
 #include "../../include/pngloss_hip.h"
+#include "pl_target.h"
 
 #include <cstddef>
 #include <cstdint>
@@ -95,18 +97,7 @@ inline uint32_t pl_size_probe_bound(uint32_t max_strength)
     return b;
 }
 
-/* One round, in the shape of pl_target_groups: the images still searching, grouped by the strength they probe next -- ascending strengths, images
- * in input order.  Each group runs as one ordinary batch. */
-inline std::vector<std::pair<uint32_t, std::vector<uint32_t>>> pl_size_groups(const std::vector<PlSizeSearch> &s)
-{
-    std::vector<std::pair<uint32_t, std::vector<uint32_t>>> out;
-    for (uint32_t strength = 0; strength < 256; strength++) {
-        std::vector<uint32_t> who;
-        for (size_t i = 0; i < s.size(); i++)
-            if (!s[i].done && s[i].next == strength) who.push_back((uint32_t)i);
-        if (!who.empty()) out.emplace_back(strength, std::move(who));
-    }
-    return out;
-}
+/* One round: pl_search_groups (pl_target.h) over the size searches, under the name tests/c/size_host.cpp pins it */
+inline std::vector<std::pair<uint32_t, std::vector<uint32_t>>> pl_size_groups(const std::vector<PlSizeSearch> &s) { return pl_search_groups(s); }
 
 #endif

@@ -4,8 +4,9 @@
  *
  * Plain C++ without HIP types, like pl_plan.h: everything the search DECIDES is here -- whether a target is valid, whether a probe is accepted,
  * which strength an image probes next and which one it ends with, which images of a round share a batch, and where the search arena keeps what --
- * so that tests/c/target_host.cpp drives it on the CPU.  pl_host.hip does what these functions say: it restores originals, runs the groups
- * through enqueue() / finish(), measures with pl_distort and moves results with pl_move (pl_target.hip).
+ * so that tests/c/target_host.cpp drives it on the CPU.  pl_search.h keeps the books of a whole search on top of these functions (what is kept,
+ * which regions are copied where), and pl_host.hip does what the two say: it runs the groups through enqueue() / finish(), measures with
+ * pl_distort and carries out the moves with pl_move (pl_target.hip).
  *
  * The rule, per image (include/pngloss_hip.h states it for callers).  PSNR is not monotone in the strength, so the result is defined by this
  * procedure and not by "the largest strength that passes":
@@ -135,9 +136,10 @@ inline uint32_t pl_target_probe_bound(uint32_t max_strength)
     return b;
 }
 
-/* One round: the images still searching, grouped by the strength they probe next -- ascending strengths, images in input order.  Each group
- * runs as one ordinary batch. */
-inline std::vector<std::pair<uint32_t, std::vector<uint32_t>>> pl_target_groups(const std::vector<PlTargetSearch> &s)
+/* One round of either search: the images still searching, grouped by the strength they probe next -- ascending strengths, images in input order.
+ * Each group runs as one ordinary batch.  Search: PlTargetSearch or PlSizeSearch (pl_size.h); pl_search.h begins every round with it. */
+template <class Search>
+inline std::vector<std::pair<uint32_t, std::vector<uint32_t>>> pl_search_groups(const std::vector<Search> &s)
 {
     std::vector<std::pair<uint32_t, std::vector<uint32_t>>> out;
     for (uint32_t strength = 0; strength < 256; strength++) {
@@ -148,6 +150,8 @@ inline std::vector<std::pair<uint32_t, std::vector<uint32_t>>> pl_target_groups(
     }
     return out;
 }
+/* (the name tests/c/target_host.cpp pins it under) */
+inline std::vector<std::pair<uint32_t, std::vector<uint32_t>>> pl_target_groups(const std::vector<PlTargetSearch> &s) { return pl_search_groups(s); }
 
 /* ---- the search arena of a context: apart from the workspace and from the keep arena of the option "distortion" (every enqueue() lays that one
  * out afresh, which would lose the originals of the images outside the current group).  In front the tables -- the move jobs of one launch (at

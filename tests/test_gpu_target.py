@@ -23,7 +23,11 @@ OUR_CLI = os.path.join(U.ROOT, "pngloss_amd", "cli", "pngloss")
 #: the one call that carries every fixed case, an image without pixels and a 48 x 12 mode-5 image: a call has ONE target, so the mixed batch runs under
 #: the two targets of the fixed cases -- its searches part ways round by round (tests/test_target_oracle.py counts the strengths per round)
 MIXED = [c[0] for c in T.CASES] + [(0, 0, 0), (48, 12, 5)]
-SETUPS = [("case%d" % k, [c[0]], (c[2], c[3], c[1])) for k, c in enumerate(T.CASES)] + [("mixed_35dB_M19", MIXED, (35.0, 0, 19)), ("mixed_39dB_err8_M40", MIXED, (39.0, 8, 40))]
+#: Under 51.6 dB with M = 3 the mixed batch ends on the two closing paths that share the last move table: three images accept strength 1 and are refused at 2
+#: afterwards (the stash goes back), the other three accept nothing (the original goes back and strength 0 runs once) -- on the oracle strength 1 gives
+#: 51.84 / 51.12 / 51.72 / 52.47 / 50.97 / 51.41 dB in the order of MIXED.  Under the two targets above an image ends either in place or from the stash.
+SETUPS = [("case%d" % k, [c[0]], (c[2], c[3], c[1])) for k, c in enumerate(T.CASES)] + [("mixed_35dB_M19", MIXED, (35.0, 0, 19)), ("mixed_39dB_err8_M40", MIXED, (39.0, 8, 40)),
+                                                                                     ("mixed_51.6dB_M3", MIXED, (51.6, 0, 3))]
 REFERENCE_FIELDS = ("status", "bpp", "unique_symbols", "retried_rows")
 
 

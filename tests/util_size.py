@@ -86,6 +86,11 @@ def build_deal_host(tmp_path):
     return _build(tmp_path, "deal_host")
 
 
+def build_search_host(tmp_path):
+    """tests/c/search_host.cpp with -fsanitize=address,undefined; returns the executable"""
+    return _build(tmp_path, "search_host")
+
+
 def build_deflate_measure_host(tmp_path):
     """tests/c/deflate_measure_host.cpp with -fsanitize=address,undefined; returns the executable"""
     return _build(tmp_path, "deflate_measure_host", ["-lpthread"])
