@@ -431,6 +431,12 @@ def test_strength_zero_row_engine_matches_oracle_and_the_other_engines(torch_cud
     imgs = [P.synth_rgba(w, h, m, i) for i, (w, h, m) in enumerate(specs)]
     for with_filters in (True, False):
         want = [U.run_port(a, 0, 2, filters=with_filters) for a in imgs]
+        # the histogram after the last row depends on every row's decision: it makes the decisions of the NULL mode observable
+        want_hist = []
+        for a in imgs:
+            gray, opaque = bool((a[..., 0] == a[..., 1]).all() and (a[..., 1] == a[..., 2]).all()), bool((a[..., 3] == 255).all())
+            packed = (a[..., 1:2] if opaque else a[..., [1, 3]]) if gray else (a[..., :3] if opaque else a)
+            want_hist.append(U.run_port_packed(np.ascontiguousarray(packed), 0, 2, filters=with_filters, trace=True)[2])
         for eng in (None, "seg", "wg"):
             if eng: monkeypatch.setenv("PNGLOSS_HIP_ENGINE", eng)
             else: monkeypatch.delenv("PNGLOSS_HIP_ENGINE", raising=False)
@@ -445,9 +451,8 @@ def test_strength_zero_row_engine_matches_oracle_and_the_other_engines(torch_cud
                     assert np.array_equal(f.cpu().numpy(), want[i][1]), (eng, with_filters, i, specs[i])
                 if eng is None:
                     assert ctx.engine_info(i)["engine"] == "row-statistics (strength 0)"
-            if eng is None:
-                h = ctx.histogram(0)
-                assert int(h.sum()) == 0 or True          # (the original-frequency histogram API stays usable)
+                assert np.array_equal(ctx.histogram(i), want_hist[i]), (eng, with_filters, i, specs[i])
+                assert r["unique_symbols"] == int(np.count_nonzero(want_hist[i])), (eng, with_filters, i, specs[i])
             ctx.close()
     monkeypatch.delenv("PNGLOSS_HIP_ENGINE", raising=False)
     ctx = P.HipContext()

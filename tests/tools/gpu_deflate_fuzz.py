@@ -14,30 +14,6 @@ import pngloss_amd as P  # noqa: E402
 from tests import util as U  # noqa: E402
 
 
-def content(rng, h, w):
-    kind = rng.integers(0, 8)
-    if kind == 0:
-        a = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
-    elif kind == 1:
-        a = P.synth_rgba(w, h, int(rng.integers(0, 6)), int(rng.integers(0, 1000)))
-    elif kind == 2:
-        a = np.full((h, w, 4), rng.integers(0, 256), np.uint8)
-    elif kind == 3:                                   # few-valued, long repeats
-        a = rng.integers(0, 3, (h, w, 4), dtype=np.uint8) * 80
-    elif kind == 4:                                   # horizontal stripes -> matches at distance = stride
-        a = np.repeat(rng.integers(0, 256, (h, 1, 4), dtype=np.uint8), w, axis=1)
-    elif kind == 5:                                   # periodic texture
-        t = rng.integers(0, 256, (1 + h // 7, 1 + w // 5, 4), dtype=np.uint8)
-        a = np.tile(t, (8, 6, 1))[:h, :w]
-    elif kind == 6:                                   # gray, opaque
-        g = rng.integers(0, 256, (h, w), dtype=np.uint8)
-        a = np.stack([g, g, g, np.full_like(g, 255)], axis=2)
-    else:                                             # smooth gradient + transparent holes
-        y, x = np.mgrid[0:h, 0:w]
-        a = np.stack([(x * 3) & 255, (y * 2) & 255, (x + y) & 255, np.where((x // 8 + y // 8) % 3 == 0, 0, 255)], axis=2).astype(np.uint8)
-    return np.ascontiguousarray(a)
-
-
 def main():
     seconds = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
@@ -52,7 +28,7 @@ def main():
             big = rng.random() < 0.15
             h = int(rng.integers(1, 700 if big else 60))
             w = int(rng.integers(1, 900 if big else 120))
-            arrays.append(content(rng, h, w))
+            arrays.append(U.deflate_fuzz_content(rng, h, w)[0])
         s = int(rng.choice([0, 5, 19, 40, 85, 255]))
         b = int(rng.choice([1, 2, 8, 32767]))
         wf = bool(rng.integers(0, 2))

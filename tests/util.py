@@ -168,6 +168,10 @@ def png_scanlines_reference(rgba_out, filter_flags):
     ids = np.zeros(h, np.uint8)
     rows = np.zeros((h, w * ch), np.uint8)
     flag_to_id = {0x08: 0, 0x10: 1, 0x20: 2, 0x40: 3, 0x80: 4}
+    # libpng (png_set_filter / png_write_start_row) drops the filters that have no neighbour to predict from: sub, average and paeth in
+    # one-pixel-wide images, up, average and paeth in one-pixel-high ones.  The heuristic chooses among the rest; a row asked to use a
+    # dropped filter is written as "none".
+    allowed = [g for g in range(5) if not (w == 1 and g in (1, 3, 4)) and not (h == 1 and g in (2, 3, 4))]
     for y in range(h):
         cur = raw[y]
         up = raw[y - 1] if y else zeros
@@ -180,9 +184,11 @@ def png_scanlines_reference(rgba_out, filter_flags):
         res = [((cur - q) & 255) for q in preds]
         if filter_flags is None or y == 0:
             sums = [int(np.where(r < 128, r, 256 - r).sum()) for r in res]
-            f = sums.index(min(sums))
+            f = min(allowed, key=lambda g: sums[g])        # (the first of equal sums wins, as in png_write_find_filter)
         else:
             f = flag_to_id[int(filter_flags[y])]
+            if f not in allowed:
+                f = 0
         ids[y] = f
         rows[y] = res[f].astype(np.uint8)
     return ctype, ids, rows
@@ -438,3 +444,138 @@ def fuzz_case(rng, big=False, strength=None):
     b = int(rng.choice([1, 2, 3, 4, 8, 16, 100, 1000, 32767, int(rng.integers(1, 32768))]))
     if strength is not None: s = int(strength)
     return img, s, b, bool(rng.integers(0, 3))
+
+
+def deflate_fuzz_content(rng, h, w):
+    """One (h, w, 4) image of the deflate campaigns (tests/tools/gpu_deflate_fuzz.py by hand, tests/test_gpu_deflate.py::test_seeded_content_campaign in the
+    suite): eight kinds of content, drawn from `rng`.  Returns (rgba, kind)."""
+    import pngloss_amd as P
+    kind = int(rng.integers(0, 8))
+    if kind == 0:
+        a = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
+    elif kind == 1:
+        a = P.synth_rgba(w, h, int(rng.integers(0, 6)), int(rng.integers(0, 1000)))
+    elif kind == 2:
+        a = np.full((h, w, 4), rng.integers(0, 256), np.uint8)
+    elif kind == 3:                                   # few-valued, long repeats
+        a = rng.integers(0, 3, (h, w, 4), dtype=np.uint8) * 80
+    elif kind == 4:                                   # horizontal stripes -> matches at distance = stride
+        a = np.repeat(rng.integers(0, 256, (h, 1, 4), dtype=np.uint8), w, axis=1)
+    elif kind == 5:                                   # periodic texture
+        t = rng.integers(0, 256, (1 + h // 7, 1 + w // 5, 4), dtype=np.uint8)
+        a = np.tile(t, (8, 6, 1))[:h, :w]
+    elif kind == 6:                                   # gray, opaque
+        g = rng.integers(0, 256, (h, w), dtype=np.uint8)
+        a = np.stack([g, g, g, np.full_like(g, 255)], axis=2)
+    else:                                             # smooth gradient + transparent holes
+        y, x = np.mgrid[0:h, 0:w]
+        a = np.stack([(x * 3) & 255, (y * 2) & 255, (x + y) & 255, np.where((x // 8 + y // 8) % 3 == 0, 0, 255)], axis=2).astype(np.uint8)
+    return np.ascontiguousarray(a), kind
+
+
+# ---- the write side on one-pixel-wide / one-pixel-high images (tests/golden/make_emit_degenerate_golden.py) -------
+REF_RWPNG = os.path.join(ROOT, "oracle", "_ref", "rwpng_copy_ref")
+#: the row-filter policies of tests/c/rwpng_copy.c: -1 = no filters given, 0..4 = that filter on every row, 5 = rows cycle none, sub, up, average, paeth
+EMIT_POLICIES = (-1, 0, 1, 2, 3, 4, 5)
+
+
+def as_pixel_class(img, cls):
+    """a copy of the (H, W, 4) image forced into a byte-per-pixel class: "rgba", "rgb" (A = 255), "graya" (R = G = B) or "gray" (both)"""
+    img = np.ascontiguousarray(img, np.uint8).copy()
+    if cls in ("graya", "gray"):
+        img[..., 0] = img[..., 1]; img[..., 2] = img[..., 1]
+    if cls in ("rgb", "gray"):
+        img[..., 3] = 255
+    return img
+
+
+def policy_filter_flags(policy, h):
+    """the row_filters array tests/c/rwpng_copy.c hands the writer for `policy` (None for -1)"""
+    if policy < 0:
+        return None
+    flag = [0x08, 0x10, 0x20, 0x40, 0x80]
+    return np.array([flag[y % 5 if policy == 5 else policy] for y in range(h)], np.uint8)
+
+
+def write_rgba_png(path, rgba):
+    """An 8-bit RGBA PNG of `rgba` (H, W, 4), unfiltered rows, Python's zlib: the plainest file a PNG reader can be given."""
+    import struct
+    import zlib
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xffffffff)
+
+    h, w = rgba.shape[:2]
+    raw = np.concatenate([np.zeros((h, 1), np.uint8), np.ascontiguousarray(rgba, np.uint8).reshape(h, w * 4)], axis=1).tobytes()
+    with open(path, "wb") as fh:
+        fh.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 6, 0, 0, 0)) + chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
+
+
+def ref_writer_scanlines(rgba, policy, workdir):
+    """What the reference's writer (real libpng, oracle/_ref/rwpng_copy_ref) hands zlib for `rgba` under `policy`: (colour type, lines), lines an
+    (H, 1 + W * channels) array of the filter-type byte and the filtered bytes of every scanline."""
+    import subprocess
+    from pngloss_amd.lib import parse_png
+    src, dst = os.path.join(str(workdir), "in.png"), os.path.join(str(workdir), "out.png")
+    write_rgba_png(src, rgba)
+    subprocess.run([REF_RWPNG, src, dst, str(policy), "0"], check=True, capture_output=True)
+    with open(dst, "rb") as fh:
+        png = parse_png(fh.read())
+    assert (png["width"], png["height"], png["depth"], png["interlace"]) == (rgba.shape[1], rgba.shape[0], 8, 0)
+    return png["ctype"], np.frombuffer(png["scanlines"], np.uint8).reshape(rgba.shape[0], -1).copy()
+
+
+def restated_scanlines(rgba, policy):
+    """png_scanlines_reference in the form ref_writer_scanlines returns"""
+    ctype, ids, rows = png_scanlines_reference(rgba, policy_filter_flags(policy, rgba.shape[0]))
+    return ctype, np.concatenate([ids[:, None], rows], axis=1)
+
+
+def emit_degenerate_fixture():
+    """tests/golden/emit_degenerate.npz as a list of (name, rgba, colour type, lines[policy index, row, 1 + W * channels])"""
+    g = load_npz("emit_degenerate.npz")
+    return [(k[:-5], g[k], int(g[k[:-5] + "/ctype"]), g[k[:-5] + "/lines"]) for k in g.files if k.endswith("/rgba")]
+
+
+# ---- reading the header of a dynamic deflate block ---------------------------------------------------------------
+def dynamic_block_code_lengths(z):
+    """Code lengths of the FIRST deflate block of the zlib stream `z`, which must be a dynamic block (RFC 1951, 3.2.7): returns
+    (literal/length code lengths [HLIT + 257], distance code lengths [HDIST + 1])."""
+    pos = [16]                                        # in bits, behind the two bytes of the zlib header
+
+    def bits(n):
+        v = 0
+        for i in range(n):
+            v |= ((z[pos[0] >> 3] >> (pos[0] & 7)) & 1) << i
+            pos[0] += 1
+        return v
+
+    bits(1)
+    assert bits(2) == 2, "the first block is not a dynamic block"
+    hlit, hdist, hclen = bits(5) + 257, bits(5) + 1, bits(4) + 4
+    cl = [0] * 19
+    for k in [16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15][:hclen]:
+        cl[k] = bits(3)
+    codes, code = {}, 0                               # canonical codes of the code-length code: (length, code) -> symbol
+    for n in range(1, 8):
+        for s in range(19):
+            if cl[s] == n:
+                codes[(n, code)] = s
+                code += 1
+        code <<= 1
+    out = []
+    while len(out) < hlit + hdist:
+        n = code = 0
+        while (n, code) not in codes:
+            code = (code << 1) | bits(1)              # Huffman codes are packed starting with their most significant bit
+            n += 1
+            assert n <= 7, "bad code-length code"
+        s = codes[(n, code)]
+        if s < 16:
+            out.append(s)
+        elif s == 16:
+            out += [out[-1]] * (3 + bits(2))
+        else:
+            out += [0] * (3 + bits(3) if s == 17 else 11 + bits(7))
+    assert len(out) == hlit + hdist
+    return out[:hlit], out[hlit:]
