@@ -2,8 +2,10 @@
  * pl_host.hip -- the thin C-ABI shim of libpngloss_hip.so (see include/pngloss_hip.h for the contract).
  *
  * Host side only: context + workspace management, job tables, stream/event plumbing, and the host-pointer
- * drop-in entry points that replace /root/reference/src/pngloss_image.c:29-156.  No arithmetic of the hot path is
- * done here and there is no CPU fallback: without a usable HIP device every entry point fails loudly.
+ * drop-in entry points that replace the reference's src/pngloss_image.c:29-156.  No arithmetic of the hot path is
+ * done here and there is no CPU fallback: without a usable HIP device every entry point fails loudly.  What it
+ * DECIDES is in plain headers that the CPU suite pins: pl_plan.h (the batch, the segment engine's workspace table),
+ * pl_seg_pace.h (the pace of the segment engine's launch thread), pl_layout.h, pl_deal.h, pl_search.h, pl_result.h.
  */
 #include "../../include/pngloss_hip.h"
 #include "pl_device.h"
@@ -18,6 +20,7 @@
 #define SEG_PLAIN_POINTERS   /* host plumbing only: SegJob is filled here, never dereferenced */
 #include "pl_seg.h"
 #include "pl_plan.h"
+#include "pl_seg_pace.h"
 #include "pl_deal.h"
 #include "pl_layout.h"
 #include "pl_search.h"
@@ -326,91 +329,76 @@ struct SegStreamPool {
 SegStreamPool &seg_stream_pool() { static SegStreamPool *p = new SegStreamPool; return *p; }      /* (never destroyed: contexts may outlive static destruction order) */
 
 struct SegGroups { PlSegBatch b[SEG_MAX_GROUPS]; int n = 1; };
+int64_t steady_ns() { return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+/* The launch thread: the calls; when a group gets its next attempt, when the loop gives up and how it backs off is pl_seg_pace.h's to say. */
 void seg_worker_main(pngloss_hip_ctx *ctx, SegGroups gs, long max_attempts)
 {
-    /* words: [2g] images of group g that are finished, [2g + 1] the attempt group g's first image is working on */
     volatile uint32_t *words = ctx->h_seg_words;
     int rc = PNGLOSS_SUCCESS;
     if (hipSetDevice(ctx->device) != hipSuccess) rc = PNGLOSS_HIP_ERROR;
-    /* Round 6: the launch thread has a CPU of its own.  It must issue four launches every 45 - 100 us for as long as the engine runs; on a node every rank (or every context of
-     * pngloss_hip_multi) has one, next to the threads that stage images.  CPU (2 * slot + 1) of the process's affinity set, slot = the context's device ordinal or its serial
-     * number in the process, whichever is larger: eight ranks with one device each and eight contexts of one process get eight different CPUs; skipped when the set is too
-     * small for that, or with PNGLOSS_HIP_PIN=0.  (Measured on one box, eight contexts on one device: profiles/r06_host_side.txt: no measurable difference with 256 CPUs visible and a quota of 16 -- 181.56 against 181.62 ms for the headline frame, 1730 - 1751 against 1742 - 1796 ms for configs[3] on eight contexts of one device; all of it on TWO CPUs: 1938 ms.) */
-    if (ctx->hooks.pin != 0) {
+    /* Round 6: the launch thread has a CPU of its own (pl_seg_pin_cpu).  It must issue four launches every 45 - 100 us for as long as the engine runs; on a node every rank (or every
+     * context of pngloss_hip_multi) has one, next to the threads that stage images.  (Measured on one box, eight contexts on one device: profiles/r06_host_side.txt: no measurable difference with 256 CPUs visible and a quota of 16 -- 181.56 against 181.62 ms for the headline frame, 1730 - 1751 against 1742 - 1796 ms for configs[3] on eight contexts of one device; all of it on TWO CPUs: 1938 ms.) */
+    {
         cpu_set_t allowed;
         CPU_ZERO(&allowed);
-        if (sched_getaffinity(0, sizeof allowed, &allowed) == 0) {
-            std::vector<int> cpus;
+        std::vector<int> cpus;
+        if (sched_getaffinity(0, sizeof allowed, &allowed) == 0)
             for (int c = 0; c < CPU_SETSIZE; c++) if (CPU_ISSET(c, &allowed)) cpus.push_back(c);
-            const size_t want = (size_t)(2 * ctx->pin_slot + 1);
-            if (cpus.size() >= 4 && want < cpus.size()) {
-                cpu_set_t one;
-                CPU_ZERO(&one);
-                CPU_SET(cpus[want], &one);
-                (void)pthread_setaffinity_np(pthread_self(), sizeof one, &one);       /* (a refusal is not an error: the thread stays where the scheduler puts it) */
-            }
+        const int cpu = pl_seg_pin_cpu(cpus.data(), cpus.size(), ctx->pin_slot, ctx->hooks.pin);
+        if (cpu >= 0) {
+            cpu_set_t one;
+            CPU_ZERO(&one);
+            CPU_SET(cpu, &one);
+            (void)pthread_setaffinity_np(pthread_self(), sizeof one, &one);       /* (a refusal is not an error: the thread stays where the scheduler puts it) */
         }
     }
     /* The engine's streams never wait for another stream ON THE DEVICE: streams share a few hardware queues, a queue is served in order,
      * and the callers' streams hold waits for the finished words -- with twelve contexts, engine j's attempts sat behind engine k's wait
      * for k's inputs, whose kernels sat behind caller j's wait for engine j.  So this thread waits for the inputs, on the host. */
     if (rc == PNGLOSS_SUCCESS && hipEventSynchronize(ctx->ev_prep) != hipSuccess) rc = PNGLOSS_HIP_ERROR;
-    const long lookahead = 32;                                  /* attempts queued ahead of the one the device works on */
-    long launched[SEG_MAX_GROUPS] = {};
-    auto t_last = std::chrono::steady_clock::now();
-    uint32_t seen[SEG_MAX_GROUPS] = {};
-    int idle = 0;
-    long lead_sum = 0, lead_n = 0, lead_min = 1 << 30, lead_low = 0;
-    for (;;) {
-        if (rc != PNGLOSS_SUCCESS) break;
+    PlSegPace pace = pl_seg_pace_begin(gs.n, max_attempts, steady_ns());
+    for (int g = 0; g < gs.n; g++) pl_seg_pace_group(pace, g, gs.b[g].n, gs.b[g].shape.seeds);
+    while (rc == PNGLOSS_SUCCESS) {
         bool all_done = true, any_launched = false;
+        const int64_t now = steady_ns();
         for (int g = 0; g < gs.n && rc == PNGLOSS_SUCCESS; g++) {
-            if (words[2 * g] >= (uint32_t)gs.b[g].n) continue;       /* this group's images are finished */
+            const PlSegStep step = pl_seg_pace_poll(pace, g, pl_seg_words_read(words, g), now);
+            if (step == PlSegStep::Finished) continue;
             all_done = false;
-            const uint32_t at = words[2 * g + 1];
-            if (at != seen[g]) { seen[g] = at; t_last = std::chrono::steady_clock::now(); idle = 0; }
-            if (launched[g] - (long)at > lookahead) continue;       /* the device is busy with what is queued for this group */
-            if (launched[g] > max_attempts) {
+            if (step == PlSegStep::Busy) continue;
+            if (step == PlSegStep::Runaway) {
                 std::fprintf(stderr, "pngloss_hip: the segment engine needed more than %ld attempts\n", max_attempts);
                 rc = PNGLOSS_HIP_ERROR;
                 break;
             }
-            /* a group whose rows keep breaking off -- its images hold fixed points and cycles the seeds do not reach (flat content; real photographs break in ~5 % of their rows,
-             * the generator's frames in 0.3 %) -- goes back to the start from every state for the rest of the batch: more than one image-row in 25, sixteen to begin with (the
-             * device-side rule, seg_unit_from_seeds, does the same image by image inside the kernel; this one changes the KERNEL -- for small batches seg_k_enum instead of
-             * seg_k_enum_unit<1> with its slow exhaustive path).  Results do not depend on it; the count lags the launches by the look-ahead. */
-            if (gs.b[g].shape.seeds && (uint64_t)words[2 * SEG_MAX_GROUPS + g] * 25u > (uint64_t)at * gs.b[g].n + 400u) gs.b[g].shape.seeds = false;
-            if (launched[g] >= 64) { const long lead = launched[g] - (long)at; lead_sum += lead; lead_n++; if (lead < lead_min) lead_min = lead; if (lead <= 2) lead_low++; }   /* (PNGLOSS_HIP_DEBUG: how far ahead of the device the launches run) */
-            const hipError_t e = pl_seg_launch_attempt(gs.b[g], (int)launched[g], ctx->seg_gstream[g]);
+            gs.b[g].shape.seeds = pace.g[g].seeds;
+            const hipError_t e = pl_seg_launch_attempt(gs.b[g], (int)pace.g[g].launched, ctx->seg_gstream[g]);
             if (e != hipSuccess) { std::fprintf(stderr, "pngloss_hip: launching a row attempt failed: %s\n", hipGetErrorString(e)); rc = PNGLOSS_HIP_ERROR; break; }
-            launched[g]++;
+            pl_seg_pace_launched(pace, g);
             any_launched = true;
         }
         if (all_done || rc != PNGLOSS_SUCCESS) break;
-        if (!any_launched) {
-            if (std::chrono::steady_clock::now() - t_last > std::chrono::seconds(20)) {
-                std::fprintf(stderr, "pngloss_hip: the segment engine stopped making progress (attempts of the first groups: %u %u %u %u)\n", seen[0], seen[1], seen[2], seen[3]);
-                rc = PNGLOSS_HIP_ERROR;
-                break;
-            }
-            /* every group has its look-ahead queued: leave the core to others (a row attempt takes 50 - 200 us) */
-            if (++idle < 4) std::this_thread::yield(); else std::this_thread::sleep_for(std::chrono::microseconds(100));
+        if (any_launched) continue;
+        switch (pl_seg_pace_idle(pace, steady_ns())) {
+        case PlSegIdle::Stalled:
+            std::fprintf(stderr, "pngloss_hip: the segment engine stopped making progress (attempts of the first groups: %u %u %u %u)\n", pace.g[0].seen, pace.g[1].seen, pace.g[2].seen, pace.g[3].seen);
+            rc = PNGLOSS_HIP_ERROR;
+            break;
+        case PlSegIdle::Yield: std::this_thread::yield(); break;
+        case PlSegIdle::Sleep: std::this_thread::sleep_for(std::chrono::microseconds(100)); break;
         }
     }
     for (int g = 0; g < gs.n; g++)
         if (hipEventRecord(ctx->ev_seg_gdone[g], ctx->seg_gstream[g]) != hipSuccess) rc = PNGLOSS_HIP_ERROR;
     if (rc != PNGLOSS_SUCCESS) {
-        /* whatever went wrong, the caller's stream must not wait for ever: release it (the images are NOT finished: the error is
-         * reported by pngloss_hip_finish), then let what is queued drain */
-        for (int g = 0; g < gs.n; g++) words[2 * g] = (uint32_t)gs.b[g].n;
+        /* release the caller's stream, then let what is queued drain */
+        for (int g = 0; g < gs.n; g++) pl_seg_words_release(words, g, gs.b[g].n);
         for (int g = 0; g < gs.n; g++) (void)hipStreamSynchronize(ctx->seg_gstream[g]);
     }
-    if (ctx->hooks.debug && lead_n)
+    if (ctx->hooks.debug && pace.lead_n)
         std::fprintf(stderr, "pngloss_hip: launch thread: %d group(s), %ld launches of an attempt; attempts queued ahead of the device when launching: average %.1f, least %ld, at most two ahead in %ld launches (look-ahead %ld)\n",
-                     gs.n, lead_n, (double)lead_sum / (double)lead_n, lead_min, lead_low, lookahead);
-    long mx = 0;
-    for (int g = 0; g < gs.n; g++) mx = std::max(mx, launched[g]);
-    ctx->seg_attempts = mx;
+                     gs.n, pace.lead_n, (double)pace.lead_sum / (double)pace.lead_n, pace.lead_min, pace.lead_low, PL_SEG_LOOKAHEAD);
+    ctx->seg_attempts = pl_seg_pace_attempts(pace);
     ctx->seg_rc.store(rc, std::memory_order_release);
 }
 
@@ -420,7 +408,7 @@ int run_seg_engine(pngloss_hip_ctx *ctx, const PlJob *d_jobs, const PlPlan &plan
     const std::vector<uint32_t> &list = plan.seg_list;
     const size_t n = list.size();                              /* the images of the batch this engine takes */
     const int ngroups = plan.ngroups;                          /* (launch groups: pl_plan_batch) */
-    if (!ctx->h_seg_words) PL_CHECK(hipHostMalloc(reinterpret_cast<void **>(&ctx->h_seg_words), 16 * SEG_MAX_GROUPS, hipHostMallocMapped | hipHostMallocCoherent));
+    if (!ctx->h_seg_words) PL_CHECK(hipHostMalloc(reinterpret_cast<void **>(&ctx->h_seg_words), sizeof(uint32_t) * PL_SEG_WORDS, hipHostMallocMapped | hipHostMallocCoherent));
     if (!ctx->seg_stream) {
         /* a stream of the HIGHEST priority: streams of one priority share a few hardware queues, and a queue whose head is a caller's
          * wait for the finished word holds up everything behind it -- the engine's attempts must never sit in such a queue (twelve
@@ -449,31 +437,23 @@ int run_seg_engine(pngloss_hip_ctx *ctx, const PlJob *d_jobs, const PlPlan &plan
     void *d_words = nullptr;
     PL_CHECK(hipHostGetDevicePointer(&d_words, ctx->h_seg_words, 0));
     volatile uint32_t *words = ctx->h_seg_words;
-    for (int q = 0; q < 4 * SEG_MAX_GROUPS; q++) words[q] = 0;       /* ([2g], [2g + 1]: see seg_worker_main; [2 * SEG_MAX_GROUPS + g]: rows of group g the chain kernel broke off) */
+    for (int q = 0; q < PL_SEG_WORDS; q++) words[q] = 0;
+    uint32_t *const d_word = static_cast<uint32_t *>(d_words);
     const size_t *gfirst = plan.gfirst;
     auto group_of = [&](size_t i) { int g = 0; while (g + 1 < ngroups && i >= gfirst[g + 1]) g++; return g; };
     ctx->h_sj.assign(n, SegJob{});
     ctx->h_seg_params = plan.params;
     for (size_t i = 0; i < n; i++) {
         const PlJob &pj = ctx->h_jobs[list[i]];
-        const PlSegLayout &l = lay.seg[i];
         char *base = ctx->d_ws + lay.seg_image[i];
         SegJob &s = ctx->h_sj[i];
         s.job_index = list[i];
         s.img = pj.img; s.row_filters = pj.row_filters; s.row_ids = pj.row_ids; s.W = pj.width; s.H = pj.height; s.bpp = 0;
         s.orig_rank = pj.orig_rank; s.cand = reinterpret_cast<uint32_t *>(pj.cand);
-        s.err0 = reinterpret_cast<uint32_t *>(base + l.err0); s.err1 = reinterpret_cast<uint32_t *>(base + l.err1); s.rowcopy = reinterpret_cast<uint32_t *>(base + l.rowcopy);
         s.final_hist = pj.final_hist; s.result = pj.result; s.progress = pj.progress;
-        s.break_word = static_cast<uint32_t *>(d_words) + 2 * SEG_MAX_GROUPS + group_of(i);
-        { const int g = group_of(i); s.done_counter = static_cast<uint32_t *>(d_words) + 2 * g; s.attempt_word = i == gfirst[g] ? static_cast<uint32_t *>(d_words) + 2 * g + 1 : nullptr; }
-        s.ctl = reinterpret_cast<SegCtl *>(base + l.ctl); s.base = reinterpret_cast<uint32_t *>(base + l.base);
-        s.H0 = reinterpret_cast<uint32_t *>(base + l.h0); s.acc = reinterpret_cast<SegAcc *>(base + l.acc);
-        s.tables = reinterpret_cast<uint32_t *>(base + l.tables); s.maps = reinterpret_cast<uint16_t *>(base + l.maps); s.ehash = reinterpret_cast<uint32_t *>(base + l.ehash);
-        s.rout = reinterpret_cast<uint16_t *>(base + l.rout); s.rst = reinterpret_cast<uint32_t *>(base + l.rst); s.rck = reinterpret_cast<uint32_t *>(base + l.rck); s.dnout = reinterpret_cast<uint16_t *>(base + l.dnout); s.dcnt = reinterpret_cast<uint32_t *>(base + l.dcnt);
-        s.entry = reinterpret_cast<uint32_t *>(base + l.entry); s.segcnt = reinterpret_cast<uint16_t *>(base + l.segcnt);
-        s.grpcnt = reinterpret_cast<uint32_t *>(base + l.grpcnt); s.grpleft = reinterpret_cast<uint32_t *>(base + l.grpleft);
-        s.firstidx = reinterpret_cast<uint32_t *>(base + l.firstidx); s.rowmm = reinterpret_cast<int32_t *>(base + l.rowmm);
-        s.nseg = pj.width ? l.nseg : 0; s.ngrp = pj.width ? l.ngrp : 0;
+        const int g = group_of(i);
+        s.done_counter = d_word + pl_seg_done_word(g); s.attempt_word = i == gfirst[g] ? d_word + pl_seg_attempt_word(g) : nullptr; s.break_word = d_word + pl_seg_break_word(g);
+        pl_seg_bind(s, lay.seg[i], pj.width, [&](const PlSegArray &a) { return base + a.off; });
     }
     SegJob *d_sj = reinterpret_cast<SegJob *>(ctx->d_ws + lay.seg_jobs);
     for (size_t i = 0; i < n; i++) ctx->h_sj[i].self = d_sj + i;
@@ -493,23 +473,20 @@ int run_seg_engine(pngloss_hip_ctx *ctx, const PlJob *d_jobs, const PlPlan &plan
     ctx->seg_rc.store(PNGLOSS_SUCCESS, std::memory_order_relaxed);
     /* (round 5, measured with tools/gpu_r5_benchlegs.sh: the stream memory operation on the caller's stream is not free -- its queue polls the finished word while
      *  the engine runs -- : without it the headline frame is 1.4 % faster, the seeded 8192 x 8192 points up to 7 %.  The synchronous entry point has no use for it.) */
-    bool waiting = ctx->stream_wait_ok != 0 && ctx->seg_prio_distinct && !ctx->sync_call && !g_third_engine_stream.load(std::memory_order_relaxed);
-    if (waiting && stream) {
-        /* (a caller's stream of the engine's own priority could share its queue: no wait on that one) */
-        int prio = 0;
-        if (hipStreamGetPriority(stream, &prio) != hipSuccess || prio == ctx->seg_prio) waiting = false;
-    }
+    int prio = 0;
+    const bool prio_known = stream && hipStreamGetPriority(stream, &prio) == hipSuccess;
+    bool waiting = pl_seg_wait_on_device(ctx->stream_wait_ok != 0, ctx->seg_prio_distinct, ctx->sync_call, g_third_engine_stream.load(std::memory_order_relaxed), !stream, prio_known, prio, ctx->seg_prio);
     if (waiting) {
         /* the caller's stream goes on behind the engine: when every image has counted itself finished */
         for (int g = 0; g < ngroups && waiting; g++) {
-            const hipError_t e = hipStreamWaitValue32(stream, static_cast<uint32_t *>(d_words) + 2 * g, (uint32_t)gs.b[g].n, hipStreamWaitValueGte, 0xFFFFFFFFu);
+            const hipError_t e = hipStreamWaitValue32(stream, d_word + pl_seg_done_word(g), (uint32_t)gs.b[g].n, hipStreamWaitValueGte, 0xFFFFFFFFu);
             if (e != hipSuccess) { (void)hipGetLastError(); ctx->stream_wait_ok = 0; waiting = false; }     /* (a wait already enqueued is satisfied when its group finishes: harmless) */
             else g_stream_wait_used.store(true, std::memory_order_relaxed);
         }
     }
     ctx->seg_async_wait = waiting;
     try { ctx->seg_worker = std::thread(seg_worker_main, ctx, gs, plan.max_attempts); }
-    catch (...) { std::fprintf(stderr, "pngloss_hip: cannot start the launch thread\n"); for (int g = 0; g < ngroups; g++) words[2 * g] = (uint32_t)gs.b[g].n; return PNGLOSS_HIP_ERROR; }
+    catch (...) { std::fprintf(stderr, "pngloss_hip: cannot start the launch thread\n"); for (int g = 0; g < ngroups; g++) pl_seg_words_release(words, g, gs.b[g].n); return PNGLOSS_HIP_ERROR; }
     if (!waiting) {
         /* no stream memory operations on this device: wait for the launch loop here, and order the caller's stream behind the engine's */
         ctx->seg_worker.join();

@@ -1,11 +1,12 @@
 /*
  * pl_plan.h -- every decision the library makes about a batch, as pure functions of plain inputs: the pin of the row engine, which row engine
- * takes which image (the cost model), the segment engine's launch groups and enumeration kind, the runaway bound of its launch loop, and the
- * chunks of a host window.  Internal.
+ * takes which image (the cost model), the segment engine's per-image workspace (one table of its arrays: their sizes, offsets and the pointers of a
+ * job record), its launch groups and enumeration kind, the runaway bound of its launch loop (pl_seg_max_attempts; the loop's other rules: pl_seg_pace.h),
+ * and the chunks of a host window.  Internal.
  *
  * Plain C++17 without HIP: pl_host.hip carries the plan out (workspace, job tables, streams, launches), and tests/c/plan_host.cpp compiles the
- * same header with g++ so that the CPU suite pins the decisions (tests/test_plan_host.py).  Nothing here changes results: every engine, group
- * and enumeration kind gives the reference's bytes; the plan decides how fast.
+ * same header with g++ so that the CPU suite pins the decisions (tests/test_plan_host.py); tests/c/seg_host.cpp binds the workspace of the kernel bodies it
+ * runs through the same table.  Nothing here changes results: every engine, group and enumeration kind gives the reference's bytes; the plan decides how fast.
  */
 #ifndef PL_PLAN_H
 #define PL_PLAN_H
@@ -55,7 +56,7 @@ struct PlHooks {
     int kin = -1;                /* PNGLOSS_HIP_KIN: run-in pixels of the seeded enumeration */
     int seg_seeds = -1;          /* PNGLOSS_HIP_SEG_SEEDS: 0 = units start from every state, as in round 5 (-1 / 1: from seeds where the pair has a seed set) */
     int seg_seeds1 = -1;         /* PNGLOSS_HIP_SEG_SEEDS1: 0 / 1 pins the per-segment enumeration from seeds (seg_k_enum_unit<1>; -1: batches of two or more images) */
-    int pin = -1;                /* PNGLOSS_HIP_PIN: 0 = the launch thread is not pinned to a CPU (-1 / 1: pinned when the affinity set has room, run_seg_engine) */
+    int pin = -1;                /* PNGLOSS_HIP_PIN: 0 = the launch thread is not pinned to a CPU (-1 / 1: pinned when the affinity set has room, pl_seg_pace.h:pl_seg_pin_cpu) */
     int calib = -1;              /* PNGLOSS_HIP_CALIB: 1 = the cost model that picks the row engine of a batch is calibrated on this device by a probe (engine_calib; off by default: see enqueue) */
     int seed_kin = -1;           /* PNGLOSS_HIP_SEED_KIN: run-in pixels of the units' seeds (1 .. SEG_SEED_KMAX) */
     bool segprof = false;        /* PNGLOSS_HIP_SEGPROF: phase clocks inside the kernels (slows them down) */
@@ -66,39 +67,61 @@ struct PlHooks {
     int split = 0;               /* PNGLOSS_HIP_SPLIT: chunks of a host window */
 };
 
-/* ---- the segment engine's per-image workspace (offsets into one 256-B aligned carve) and its segment / group counts ---------------------------------------- */
-struct PlSegLayout { size_t ctl, base, h0, acc, err0, err1, rowcopy, tables, maps, ehash, rout, rst, rck, dnout, dcnt, entry, segcnt, grpcnt, grpleft, firstidx, rowmm, total; uint32_t nseg, ngrp; };
-/* nsp, seeded: SegParams::nsp / ::seeded of the (strength, bleed) pair */
+/* ---- the segment engine's per-image workspace, stated ONCE: one 256-B aligned carve per image, its arrays in this order --------------------------------------
+ * X(field of SegJob, elements): the element type is the field's own (pl_seg_core.h says what each array holds); the counts may use width, nseg, ngrp, nsp and
+ * seeded.  pl_seg_layout() turns the table into offsets and exact byte sizes, pl_seg_bind() into the pointers of a SegJob -- for the library at base + offset
+ * (run_seg_engine), for the CPU harness a heap block of exactly the array's bytes each (tests/c/seg_host.cpp: the sanitizers check the product's sizes). */
+#define PL_SEG_ARRAYS(X)                                                                       \
+    X(ctl, 3)                                                                                  \
+    X(base, 3 * SEG_NFILT * 256)                                                               \
+    X(H0, 3 * 256)                                                                             \
+    X(acc, 3)                                                                                  \
+    X(err0, (size_t)width * 4)                                                                 \
+    X(err1, (size_t)width * 4)                                                                 \
+    X(rowcopy, (size_t)width * 3)                                                              \
+    X(tables, (size_t)SEG_NFILT * SEG_TBL_WORDS)                                               \
+    X(maps, seeded ? 0 : (size_t)SEG_NFILT * nseg * 4 * nsp)                                   \
+    X(ehash, seeded ? (size_t)SEG_NFILT * nseg * 4 * SEG_EH_WORDS : 0)                         \
+    X(rout, (size_t)SEG_NFILT * nseg * 4 * SEG_NSP)                                            \
+    X(rst, (size_t)SEG_NFILT * nseg * 4 * SEG_NSP)                                             \
+    X(rck, (size_t)SEG_NFILT * nseg * 4 * SEG_NSP * (SEG_PARTS - 1))                           \
+    X(dnout, (size_t)SEG_NFILT * nseg * 4)                                                     \
+    X(dcnt, (size_t)SEG_NFILT * nseg * 4)                                                      \
+    X(entry, (size_t)SEG_NFILT * nseg * 4)                                                     \
+    X(segcnt, (size_t)SEG_NFILT * nseg * 256)                                                  \
+    X(grpcnt, (size_t)SEG_NFILT * ngrp * 256)                                                  \
+    X(grpleft, (size_t)SEG_NFILT * ngrp)                                                       \
+    X(firstidx, SEG_NFILT * 4 * 2)                                                             \
+    X(rowmm, 2 * 2)
+struct PlSegArray { size_t off, bytes; };       /* bytes: what the array holds, exactly; the carve gives an empty one 4 bytes and rounds every one up to 256 */
+struct PlSegLayout {
+#define PL_SEG_X(name, count) PlSegArray name;
+    PL_SEG_ARRAYS(PL_SEG_X)
+#undef PL_SEG_X
+    size_t total; uint32_t nseg, ngrp;
+};
+/* width: the image's, 1 for an image without pixels (w ? w : 1); nsp, seeded: SegParams::nsp / ::seeded of the (strength, bleed) pair */
 inline PlSegLayout pl_seg_layout(uint32_t width, uint32_t nsp, bool seeded)
 {
     PlSegLayout l{};
-    l.nseg = (width + SEG_L - 1) / SEG_L;
-    l.ngrp = (l.nseg + SEG_GRP - 1) / SEG_GRP;
+    const uint32_t nseg = l.nseg = (width + SEG_L - 1) / SEG_L;
+    const uint32_t ngrp = l.ngrp = (nseg + SEG_GRP - 1) / SEG_GRP;
     size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o = (o + (bytes ? bytes : 4) + 255) / 256 * 256; return at; };
-    l.ctl = take(3 * sizeof(SegCtl));
-    l.base = take(3 * SEG_NFILT * 256 * 4);
-    l.h0 = take(3 * 256 * 4);
-    l.acc = take(3 * sizeof(SegAcc));
-    l.err0 = take((size_t)width * 16);
-    l.err1 = take((size_t)width * 16);
-    l.rowcopy = take((size_t)width * 12);
-    l.tables = take((size_t)SEG_NFILT * SEG_TBL_WORDS * 4);
-    l.maps = take(seeded ? 0 : (size_t)SEG_NFILT * l.nseg * 4 * nsp * 2);
-    l.ehash = take(seeded ? (size_t)SEG_NFILT * l.nseg * 4 * SEG_EH_WORDS * 4 : 0);
-    l.rout = take((size_t)SEG_NFILT * l.nseg * 4 * SEG_NSP * 2);
-    l.rst = take((size_t)SEG_NFILT * l.nseg * 4 * SEG_NSP * 4);
-    l.rck = take((size_t)SEG_NFILT * l.nseg * 4 * SEG_NSP * (SEG_PARTS - 1) * 4);
-    l.dnout = take((size_t)SEG_NFILT * l.nseg * 4 * 2);
-    l.dcnt = take((size_t)SEG_NFILT * l.nseg * 4 * 4);
-    l.entry = take((size_t)SEG_NFILT * l.nseg * 4 * 4);
-    l.segcnt = take((size_t)SEG_NFILT * l.nseg * 256 * 2);
-    l.grpcnt = take((size_t)SEG_NFILT * l.ngrp * 256 * 4);
-    l.grpleft = take((size_t)SEG_NFILT * l.ngrp * 4);
-    l.firstidx = take(SEG_NFILT * 4 * 2 * 4);
-    l.rowmm = take(16);
+    auto take = [&](size_t bytes) { const PlSegArray a{ o, bytes }; o = (o + (bytes ? bytes : 4) + 255) / 256 * 256; return a; };
+#define PL_SEG_X(name, count) l.name = take(sizeof(*SegJob::name) * (size_t)(count));
+    PL_SEG_ARRAYS(PL_SEG_X)
+#undef PL_SEG_X
     l.total = o;
     return l;
+}
+/* ctl .. rowmm, nseg and ngrp of a SegJob whose image is `width` pixels wide (0: no segments): storage(a) is where array a lives */
+template <class Storage>
+inline void pl_seg_bind(SegJob &j, const PlSegLayout &l, uint32_t width, Storage &&storage)
+{
+#define PL_SEG_X(name, count) j.name = (decltype(j.name))storage(l.name);
+    PL_SEG_ARRAYS(PL_SEG_X)
+#undef PL_SEG_X
+    j.nseg = width ? l.nseg : 0; j.ngrp = width ? l.ngrp : 0;
 }
 
 /* ---- how the segment engine enumerates a row's segments ------------------------------------------------------------------------------------------------------
@@ -158,6 +181,15 @@ struct PlPlan {
     PlSegGroupPlan group[SEG_MAX_GROUPS] = {};
     long max_attempts = 0;
 };
+
+/* The runaway bound of the segment engine's launch loop (pl_seg_pace.h), for images of up to max_h rows: every row needs one attempt per strength it is tried at
+ * (pngloss_image.c:266-274: down to 0 in the worst case), every epoch two more (the attempt under way when its validation fails is void): a bound far above
+ * anything real, there to stop a runaway loop -- the stall detector of the launch thread is the other net.  (Seen: 1813 attempts for a 63 x 2 image at strength
+ * 200, all rows adaptive.) */
+inline long pl_seg_max_attempts(uint32_t max_h, int strength)
+{
+    return (long)std::min<double>(2.0e9, (double)max_h * ((double)strength + 1.0) * (2.0 + 2.0 * SEG_MAX_RESTARTS * SEG_NFILT) + 1024.0);
+}
 
 /* STRENGTH 0 has a row engine of its own (pl_rows.hip: nothing is quantised, the five candidate rows are the original row, what is left is the filter search): every
  * image of the batch, unless a test pins another engine -- and unless its counters do not fit (rows_fit).  "rows" pins it (a no-op at other strengths). */
@@ -324,10 +356,7 @@ inline PlPlan pl_plan_batch(const PlPlanInput &in)
         b.enum_nt = (size_t)b.max_nseg * b.n <= SEG_ENUM_NT_SMALL_MAX_NSEG ? 512u : 1024u;     /* (the images of THIS group: gridDim.y of its launches) */
         if (hk.enum_nt == 512 || hk.enum_nt == 1024) b.enum_nt = (uint32_t)hk.enum_nt;   /* test hook */
     }
-    /* every row needs one attempt per strength it is tried at (pngloss_image.c:266-274: down to 0 in the worst case), every epoch two more (the
-     * attempt under way when its validation fails is void): a bound far above anything real, there to stop a runaway loop -- the stall
-     * detector of the launch thread is the other net.  (Seen: 1813 attempts for a 63 x 2 image at strength 200, all rows adaptive.) */
-    p.max_attempts = (long)std::min<double>(2.0e9, (double)max_h * ((double)sp.strength + 1.0) * (2.0 + 2.0 * SEG_MAX_RESTARTS * SEG_NFILT) + 1024.0);
+    p.max_attempts = pl_seg_max_attempts(max_h, sp.strength);
     return p;
 }
 

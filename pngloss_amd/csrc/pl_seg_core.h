@@ -334,7 +334,7 @@ struct SegJob {
     SEG_AS_GLB uint32_t *done_counter;   /* or null: host-visible word, +1 when this image is finished (the host stops enqueueing attempts) */
     SEG_AS_GLB uint32_t *attempt_word;   /* or null: host-visible word that receives the number of the attempt being started (launch throttle) */
     SEG_AS_GLB uint32_t *break_word;     /* or null: host-visible word of the image's launch group, +1 for every row the chain kernel breaks off (the launch thread takes a group whose rows keep breaking
-                                            off the start from seeds: pl_host.hip:seg_worker_main) */
+                                            off the start from seeds: pl_seg_pace.h:pl_seg_pace_poll) */
     SEG_AS_GLB SegCtl *ctl;              /* [3]: by attempt % 3, like base, H0, acc */
     SEG_AS_GLB uint32_t *base;           /* [3][5][256] bumps of the validated prefix [0, start_x) */
     SEG_AS_GLB uint32_t *H0;             /* [3][256] committed histogram */

@@ -27,10 +27,12 @@ static void seg_debug_row(int kind, unsigned failed, int winner, int start_none)
 #include <cstdio>
 #include <cstdlib>
 #define SEG_DEBUG_BREAK(f, c, sg, est, y) do { if (getenv("SEG_HOST_VERBOSE") && atoi(getenv("SEG_HOST_VERBOSE")) > 1) fprintf(stderr, "seg_host: row %u broken off: candidate %d channel %d segment %u, entry state left %u cn %d th %d\n", (unsigned)(y), (int)(f), (int)(c), (unsigned)(sg), (unsigned)((est) & 255u), (int)(((est) >> 8) & 0xffffu) - 32768, (int)((est) >> 24) - 128); } while (0)
-#include "../../pngloss_amd/csrc/pl_seg_launch.h"
+#include "../../pngloss_amd/csrc/pl_plan.h"
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <memory>
 #include <vector>
 
 namespace {
@@ -40,6 +42,9 @@ int paeth_i(int a, int d, int l) { return seg_paeth(a, d, l); }
 struct Arena {
     std::vector<std::vector<unsigned char>> bufs;
     template <class T> T *take(size_t n) { bufs.emplace_back((n ? n : 1) * sizeof(T) + 64, (unsigned char)0xA5); return (T *)bufs.back().data(); }   /* junk-filled: nothing may rely on zeroed memory */
+    /* the engine's own arrays: a block of exactly `bytes` (none at all for an empty array), so that the sanitizers see the first byte behind what the library allocates */
+    std::vector<std::unique_ptr<unsigned char[]>> exact;
+    unsigned char *take_exact(size_t bytes) { exact.emplace_back(new unsigned char[bytes]); std::memset(exact.back().get(), 0xA5, bytes); return exact.back().get(); }
 };
 
 } // namespace
@@ -105,26 +110,10 @@ extern "C" int seg_host_optimize(unsigned char *rgba, uint32_t W, uint32_t H, un
     j.row_ids = A.take<uint8_t>(H);
     j.orig_rank = rank.data();
     j.cand = A.take<uint32_t>((size_t)5 * W * 4);
-    j.err0 = A.take<uint32_t>((size_t)W * 4); j.err1 = A.take<uint32_t>((size_t)W * 4);   /* (by row parity; the first control kernel zeroes what row 0 reads) */
-    j.rowcopy = A.take<uint32_t>((size_t)W * 3);
     j.final_hist = A.take<uint32_t>(256); j.result = A.take<int32_t>(PLR_WORDS); j.progress = nullptr;
-    j.nseg = (W + SEG_L - 1) / SEG_L; j.ngrp = (j.nseg + SEG_GRP - 1) / SEG_GRP;
     if (W > SEG_MAX_WIDTH) return 64;
-    j.ctl = A.take<SegCtl>(3); j.base = A.take<uint32_t>(3 * 5 * 256); j.H0 = A.take<uint32_t>(3 * 256); j.acc = A.take<SegAcc>(3);
-    j.tables = A.take<uint32_t>(5 * SEG_TBL_WORDS);
-    j.maps = A.take<uint16_t>((size_t)5 * j.nseg * 4 * P.nsp);
-    j.ehash = A.take<uint32_t>(P.seeded ? (size_t)5 * j.nseg * 4 * SEG_EH_WORDS : 4);
-    j.rout = A.take<uint16_t>((size_t)5 * j.nseg * 4 * SEG_NSP);
-    j.rst = A.take<uint32_t>((size_t)5 * j.nseg * 4 * SEG_NSP);
-    j.rck = A.take<uint32_t>((size_t)5 * j.nseg * 4 * SEG_NSP * (SEG_PARTS - 1));
-    j.dnout = A.take<uint16_t>((size_t)5 * j.nseg * 4);
-    j.dcnt = A.take<uint32_t>((size_t)5 * j.nseg * 4);
-    j.entry = A.take<uint32_t>((size_t)5 * j.nseg * 4);
-    j.segcnt = A.take<uint16_t>((size_t)5 * j.nseg * 256);
-    j.grpcnt = A.take<uint32_t>((size_t)5 * j.ngrp * 256);
-    j.grpleft = A.take<uint32_t>((size_t)5 * j.ngrp);
-    j.firstidx = A.take<uint32_t>(5 * 4 * 2);
-    j.rowmm = A.take<int32_t>(4);
+    /* the workspace of the image as the library lays it out (pl_seg_layout: its sizes, not the harness's own), every array a heap block of its own */
+    pl_seg_bind(j, pl_seg_layout(W ? W : 1, (uint32_t)P.nsp, P.seeded != 0), W, [&](const PlSegArray &a) { return A.take_exact(a.bytes); });
     j.nbreak = 0u;
     j.self = &j; for (int k = 0; k < 3; k++) { j.v[k].magic = 0u; j.v[k].finished = 0u; j.v[k].ignore = 0u; j.vfail[k] = 0u; }
     j.ctl[2].magic = 0u; j.acc[2].failmask = 0u;   /* (seg_k_resolve does this on the device: the first attempt finds no attempt behind it) */
@@ -143,7 +132,7 @@ extern "C" int seg_host_optimize(unsigned char *rgba, uint32_t W, uint32_t H, un
     SegLaunch launches[SEG_MAX_LAUNCHES];
     const int nl = seg_attempt_launches(shape, launches);
     int attempt = 0;
-    const long max_attempts = (long)H * ((long)strength + 1) * (2 + 2 * SEG_MAX_RESTARTS * SEG_NFILT) + 1024;   /* (the product's bound: pl_host.hip) */
+    const long max_attempts = pl_seg_max_attempts(H, (int)strength);
     /* One attempt = the four or five launches of seg_attempt_launches: [control of this attempt + validation of the attempt before], enumerate, (seeded sets: gather,)
      * chain, replay; every workgroup of every grid, each launch with a buffer of exactly its LDS request (the sanitizer build, tests/test_seg_host.py, sees any
      * byte beyond it).  The two halves of the first launch run side by side on the device; here one after the other, in either order (SEG_HOST_VAL_FIRST):

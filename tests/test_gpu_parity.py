@@ -990,6 +990,31 @@ def test_engine_option_of_the_abi_pins_the_row_engine(torch_cuda, monkeypatch):
     ctx.close()
 
 
+def test_segment_engine_workspace_binding_at_the_smallest_shapes(torch_cuda, monkeypatch):
+    """The per-image workspace of the segment engine is bound to its job record through one table (pl_plan.h: pl_seg_layout, pl_seg_bind): the shapes at which a size or
+    a binding can be wrong -- one segment, SEG_L pixels and one more, a second replay group, a width that is no multiple of anything -- in ONE batch with an empty image,
+    which goes to the other engine (a mixed batch: the selection list is used), at a state set within the lanes and at a seeded one, which has no `maps`."""
+    torch = torch_cuda
+    monkeypatch.delenv("PNGLOSS_HIP_ENGINE", raising=False)
+    specs = [(1, 2, 1), (32, 3, 0), (33, 3, 5), (513, 3, 2), (700, 4, 0), (0, 0, 0)]
+    imgs = [P.synth_rgba(w, h, m, i) if w else np.zeros((0, 0, 4), np.uint8) for i, (w, h, m) in enumerate(specs)]
+    ctx = P.HipContext()
+    ctx.set_option("engine", "seg")
+    for s, b in [(19, 2), (85, 1)]:
+        dev = [torch.from_numpy(a.copy()).cuda() for a in imgs]
+        filt = [torch.zeros(a.shape[0], dtype=torch.uint8, device="cuda") for a in imgs]
+        res = ctx.run([(d.data_ptr() if a.size else 0, f.data_ptr() if a.size else 0, a.shape[1], a.shape[0]) for d, f, a in zip(dev, filt, imgs)], s, b)
+        torch.cuda.synchronize()
+        for i, (a, d, f, r) in enumerate(zip(imgs, dev, filt, res)):
+            assert r["status"] == 0, (s, b, specs[i], r)
+            if not a.size:
+                continue
+            assert ctx.engine_info(i)["engine"] == "segment-parallel", (s, b, specs[i])
+            want, wf = U.run_port(a, s, b)
+            assert np.array_equal(d.cpu().numpy(), want) and np.array_equal(f.cpu().numpy(), wf), (s, b, specs[i])
+    ctx.close()
+
+
 @pytest.mark.parametrize("hooks", [dict(PNGLOSS_HIP_SEG_UNIT="1"), dict(PNGLOSS_HIP_SEG_UNIT="0", PNGLOSS_HIP_SEG_SEEDS1="1"), dict(PNGLOSS_HIP_SEG_UNIT="1", PNGLOSS_HIP_SEG_SEEDS="0"), dict()],
                          ids=["units-from-seeds", "segments-from-seeds", "units-from-every-state", "library-choice"])
 def test_segment_engine_batches_from_seeds_match_the_oracle(torch_cuda, monkeypatch, hooks):

@@ -170,6 +170,28 @@ def test_seg_engine_bodies_clean_under_asan_and_ubsan(tmp_path):
     assert r.returncode == 0 and "sanitized ok" in r.stdout and "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-2000:]
 
 
+def test_seg_engine_bodies_stay_inside_the_librarys_arrays(tmp_path):
+    """The harness binds the engine's arrays through the library's own table (pl_plan.h: pl_seg_layout, pl_seg_bind), each a heap block of EXACTLY the bytes
+    the library allocates for it -- none at all for `maps` of a seeded state set.  tests/c/seg_sizes_main.cpp, a program of its own built with
+    -fsanitize=address,undefined, runs the smallest shapes at which a size or a binding can be wrong (widths 1, 32, 33, 513 at (19, 2), (85, 1), (255, 1))
+    against the restatement: equal pixels and filter bytes, no report."""
+    import os
+    import subprocess
+    san = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"]
+    objs = []
+    for src in (os.path.join(U.ROOT, "pngloss_amd", "csrc", "pngloss_synth.c"), os.path.join(U.ROOT, "oracle", "pngloss_port.c")):
+        objs.append(str(tmp_path / (os.path.basename(src) + ".o")))
+        subprocess.run(["gcc", "-std=gnu11", "-Wno-unknown-pragmas", "-Wno-unused-function"] + san + ["-c", "-o", objs[-1], src], check=True, capture_output=True)
+    exe = str(tmp_path / "seg_sizes")
+    subprocess.run(["g++", "-std=c++17", "-w"] + san + ["-o", exe, os.path.join(U.ROOT, "tests", "c", "seg_sizes_main.cpp"), os.path.join(U.ROOT, "tests", "c", "seg_host.cpp")] + objs,
+                   check=True, capture_output=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr and "LeakSanitizer" not in r.stderr, r.stderr[-2000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 12 and all(" equal " in line for line in lines), r.stdout
+
+
 
 @pytest.mark.parametrize("w,h,mode,s,b", [(333, 37, 1, 19, 2), (600, 12, 5, 19, 2), (520, 16, 3, 19, 2), (200, 20, 0, 85, 1), (97, 33, 2, 7, 3), (1, 7, 1, 19, 2), (150, 12, 3, 255, 1)])
 def test_seg_engine_validation_and_control_in_either_order(monkeypatch, w, h, mode, s, b):

@@ -91,6 +91,11 @@ def build_search_host(tmp_path):
     return _build(tmp_path, "search_host")
 
 
+def build_pace_host(tmp_path):
+    """tests/c/pace_host.cpp with -fsanitize=address,undefined; returns the executable"""
+    return _build(tmp_path, "pace_host")
+
+
 def build_deflate_measure_host(tmp_path):
     """tests/c/deflate_measure_host.cpp with -fsanitize=address,undefined; returns the executable"""
     return _build(tmp_path, "deflate_measure_host", ["-lpthread"])
