@@ -25,6 +25,8 @@ _hip = None
 _synth = None
 
 
+# ---- the header's structs (STRUCTS below names them; tests/test_abi.py compares every size and offset with the compiler's) ----------
+
 class PnglossImage(C.Structure):
     _fields_ = [("rows", C.POINTER(C.c_void_p)), ("width", C.c_uint32), ("height", C.c_uint32),
                 ("bytes_per_pixel", C.c_uint8)]
@@ -57,34 +59,6 @@ class PngSource(C.Structure):
     def __init__(self, scanlines=None, width=0, height=0, color_type=0, bit_depth=0, palette=None, palette_entries=0, trns=None, trns_bytes=0,
                  rgba=None, interlace=0):
         super().__init__(scanlines, width, height, color_type, bit_depth, interlace, palette, palette_entries, trns, trns_bytes, rgba)
-
-
-def parse_png(data):
-    """Chunk walk + inflate of a PNG file (what pngloss_amd/cli/png_stream_reader.c does in C with zlib): dict(width, height, depth, ctype,
-    interlace, plte, trns, zstream, scanlines)."""
-    import struct
-    import zlib
-    data = bytes(data)
-    if data[:8] != b"\x89PNG\r\n\x1a\n":
-        raise ValueError("not a PNG file")
-    o, out, idat = 8, dict(plte=None, trns=None), []
-    while o + 8 <= len(data):
-        n, tag = struct.unpack(">I4s", data[o:o + 8])
-        body = data[o + 8:o + 8 + n]
-        o += 12 + n
-        if tag == b"IHDR":
-            out["width"], out["height"], out["depth"], out["ctype"], _, _, out["interlace"] = struct.unpack(">IIBBBBB", body)
-        elif tag == b"PLTE":
-            out["plte"] = body
-        elif tag == b"tRNS":
-            out["trns"] = body
-        elif tag == b"IDAT":
-            idat.append(body)
-        elif tag == b"IEND":
-            break
-    out["zstream"] = b"".join(idat)
-    out["scanlines"] = zlib.decompress(out["zstream"])
-    return out
 
 
 class PngZSource(C.Structure):
@@ -130,8 +104,161 @@ class ImagePair(C.Structure):
     _fields_ = [("d_a", C.c_void_p), ("d_b", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32)]
 
 
+class Target(C.Structure):
+    """pngloss_hip_target: min_psnr_db (0 = no condition, inf = only lossless results pass), max_abs_error (0 = no condition, 1..255) and
+    max_strength (M, 0..255: the search never goes above it).  include/pngloss_hip.h states the rule."""
+    _fields_ = [("min_psnr_db", C.c_double), ("max_abs_error", C.c_uint32), ("max_strength", C.c_uint32)]
+
+    def __init__(self, min_psnr_db=0.0, max_abs_error=0, max_strength=19):
+        super().__init__(min_psnr_db, max_abs_error, max_strength)
+
+
+class Target2(C.Structure):
+    """pngloss_hip_target2: a Target with min_ssim, the smallest allowed mean SSIM over the stored channels (0 = no condition, else in (0, 1])."""
+    _fields_ = [("min_psnr_db", C.c_double), ("max_abs_error", C.c_uint32), ("max_strength", C.c_uint32), ("min_ssim", C.c_double)]
+
+    def __init__(self, min_psnr_db=0.0, max_abs_error=0, max_strength=19, min_ssim=0.0):
+        super().__init__(min_psnr_db, max_abs_error, max_strength, min_ssim)
+
+
+class TargetReport(C.Structure):
+    """pngloss_hip_target_report: the chosen strength, the probes of the rule, the row-engine runs spent and the Distortion of the result kept."""
+    _fields_ = [("strength", C.c_uint32), ("probes", C.c_uint32), ("runs", C.c_uint32), ("reserved", C.c_uint32), ("distortion", Distortion)]
+
+    def as_dict(self):
+        return dict(strength=self.strength, probes=self.probes, runs=self.runs, distortion=self.distortion.as_dict())
+
+
+class SizeTarget(C.Structure):
+    """pngloss_hip_size_target: max_bytes (one budget per image: the largest allowed zlib stream) and max_strength (M, 0..255: the search never
+    goes above it).  include/pngloss_hip.h states the rule.  max_bytes: a ctypes array of c_uint64, a sequence of ints, or None."""
+    _fields_ = [("max_bytes", C.POINTER(C.c_uint64)), ("max_strength", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def __init__(self, max_bytes=None, max_strength=19):
+        if max_bytes is not None and not isinstance(max_bytes, C.Array):
+            max_bytes = (C.c_uint64 * max(len(max_bytes), 1))(*max_bytes)
+        self._budgets = max_bytes                          # (keeps the array alive)
+        super().__init__(C.cast(max_bytes, C.POINTER(C.c_uint64)) if max_bytes is not None else None, max_strength, 0)
+
+
+class SizeReport(C.Structure):
+    """pngloss_hip_size_report: the chosen strength, the probes of the rule, the row-engine runs spent, whether the budget was reached, the measured
+    stream size and colour type of the result kept, and its Distortion."""
+    _fields_ = [("strength", C.c_uint32), ("probes", C.c_uint32), ("runs", C.c_uint32), ("reached", C.c_uint32), ("bytes", C.c_uint64),
+                ("color_type", C.c_int32), ("reserved", C.c_uint32), ("distortion", Distortion)]
+
+    def as_dict(self):
+        return dict(strength=self.strength, probes=self.probes, runs=self.runs, reached=self.reached, bytes=self.bytes, color_type=self.color_type,
+                    distortion=self.distortion.as_dict())
+
+
+#: the header's name of every struct it defines -> its mirror above
+STRUCTS = {
+    "pngloss_image": PnglossImage, "pngloss_hip_image_desc": ImageDesc, "pngloss_hip_result": Result, "pngloss_hip_host_image": HostImage,
+    "pngloss_hip_scanlines": Scanlines, "pngloss_hip_zstream": ZStream, "pngloss_hip_distortion": Distortion, "pngloss_hip_image_pair": ImagePair,
+    "pngloss_hip_ssim": Ssim, "pngloss_hip_target": Target, "pngloss_hip_target_report": TargetReport, "pngloss_hip_target2": Target2,
+    "pngloss_hip_size_target": SizeTarget, "pngloss_hip_size_report": SizeReport, "pngloss_hip_png_source": PngSource,
+    "pngloss_hip_png_zsource": PngZSource,
+}
+
+
+def _prototypes():
+    """name -> (restype, [argtypes]) for every function include/pngloss_hip.h declares, in the header's order"""
+    ptr, vp, cp, sz, i, u, lg, dbl, u32 = C.POINTER, C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_uint, C.c_long, C.c_double, C.c_uint32
+    quant = [C.c_bool, C.c_uint8, lg]                                        # verbose, quantization_strength, bleed_divider of the seam
+    device = [vp, ptr(ImageDesc), sz]                                        # ctx, images, n
+    host = [vp, ptr(HostImage), sz]                                          # ctx or multi, images, n
+    res, lines, zs = ptr(Result), ptr(Scanlines), ptr(ZStream)
+    decoded = [ptr(vp), ptr(i), vp]                                          # d_rgba, status, stream
+    return {
+        "optimize_with_rows": (i, [ptr(vp), u32, u32, vp] + quant),
+        "optimize_with_stride": (None, [vp, u32, u32, u32] + quant),
+        "optimizeForAverageFilter": (None, [vp, i, i, i]),
+        "optimize_image": (i, [ptr(PnglossImage), vp] + quant),
+        "pngloss_hip_device_count": (i, []),
+        "pngloss_hip_create": (vp, [i]),
+        "pngloss_hip_destroy": (None, [vp]),
+        "pngloss_hip_optimize_batch_async": (i, device + [u, lg, vp]),
+        "pngloss_hip_finish": (i, [vp, res, sz]),
+        "pngloss_hip_optimize_batch": (i, device + [u, lg, vp, res]),
+        "pngloss_hip_optimize_batch_host": (i, host + [u, lg, res]),
+        "pngloss_hip_multi_create": (vp, [cp]),
+        "pngloss_hip_multi_destroy": (None, [vp]),
+        "pngloss_hip_multi_count": (i, [vp]),
+        "pngloss_hip_multi_split": (None, [ptr(HostImage), sz, i, ptr(i)]),
+        "pngloss_hip_optimize_batch_host_emit": (i, host + [u, lg, res, lines]),
+        "pngloss_hip_zlib_bound": (sz, [u32, u32]),
+        "pngloss_hip_multi_optimize_batch_host": (i, host + [u, lg, res, lines, zs]),
+        "pngloss_hip_optimize_batch_host_zlib": (i, host + [u, lg, res, zs]),
+        "pngloss_hip_last_deflate_ms": (dbl, [vp]),
+        "pngloss_hip_last_engine_ms": (dbl, [vp]),
+        "pngloss_hip_last_total_ms": (dbl, [vp]),
+        "pngloss_hip_last_histogram": (i, [vp, sz, vp]),
+        "pngloss_hip_last_distortion": (i, [vp, sz, ptr(Distortion)]),
+        "pngloss_hip_compare_batch": (i, [vp, ptr(ImagePair), sz, ptr(Distortion), vp]),
+        "pngloss_hip_psnr_db": (dbl, [ptr(Distortion), u]),
+        "pngloss_hip_multi_set_option": (i, [vp, cp, cp]),
+        "pngloss_hip_multi_last_distortion": (i, [vp, sz, ptr(Distortion)]),
+        "pngloss_hip_last_ssim": (i, [vp, sz, ptr(Ssim)]),
+        "pngloss_hip_multi_last_ssim": (i, [vp, sz, ptr(Ssim)]),
+        "pngloss_hip_compare_batch_ssim": (i, [vp, ptr(ImagePair), sz, ptr(Ssim), vp]),
+        "pngloss_hip_ssim_mean": (dbl, [ptr(Ssim), u]),
+        "pngloss_hip_compare_batch_visible": (i, [vp, ptr(ImagePair), sz, ptr(Distortion), ptr(Ssim), vp]),
+        "pngloss_hip_optimize_batch_target": (i, device + [ptr(Target), lg, vp, res, ptr(TargetReport)]),
+        "pngloss_hip_multi_optimize_batch_host_target": (i, host + [ptr(Target), lg, res, lines, zs, ptr(TargetReport)]),
+        "pngloss_hip_optimize_batch_target2": (i, device + [ptr(Target2), lg, vp, res, ptr(TargetReport), ptr(Ssim)]),
+        "pngloss_hip_multi_optimize_batch_host_target2": (i, host + [ptr(Target2), lg, res, lines, zs, ptr(TargetReport), ptr(Ssim)]),
+        "pngloss_hip_optimize_batch_size": (i, device + [ptr(SizeTarget), lg, vp, res, zs, ptr(SizeReport)]),
+        "pngloss_hip_multi_optimize_batch_host_size": (i, host + [ptr(SizeTarget), lg, res, lines, zs, ptr(SizeReport)]),
+        "pngloss_hip_png_decode_batch_host": (i, [vp, ptr(PngSource), sz]),
+        "pngloss_hip_png_decode_batch_host_status": (i, [vp, ptr(PngSource), sz, ptr(i)]),
+        "pngloss_hip_png_decode_batch_device": (i, [vp, ptr(PngSource), sz] + decoded),
+        "pngloss_hip_png_decode_batch_device_z": (i, [vp, ptr(PngZSource), sz] + decoded),
+        "pngloss_hip_pinned_alloc": (vp, [sz]),
+        "pngloss_hip_pinned_free": (None, [vp]),
+        "pngloss_hip_last_engine_info": (i, [vp, sz, vp]),
+        "pngloss_hip_set_option": (i, [vp, cp, cp]),
+        "pngloss_hip_version": (cp, []),
+    }
+
+
+#: the C ABI as ctypes sees it; hip_lib() applies it when it loads the library, and tests/test_abi.py checks every entry (return class, argument
+#: count, each argument's class) against the header's declarations, as it checks STRUCTS against the header's layouts
+PROTOTYPES = _prototypes()
+
+#: every symbol include/pngloss_hip.h declares (tests/test_host_logic.py checks the names against the header and that the .so exports each)
+ABI_SYMBOLS = tuple(PROTOTYPES)
+
 #: the channels an image of `bytes_per_pixel` 1..4 stores (gray is the G channel): the mask pngloss_hip_psnr_db takes for it
 PSNR_MASK_OF_BPP = {1: 0x2, 2: 0xA, 3: 0x7, 4: 0xF}
+
+
+def parse_png(data):
+    """Chunk walk + inflate of a PNG file (what pngloss_amd/cli/png_stream_reader.c does in C with zlib): dict(width, height, depth, ctype,
+    interlace, plte, trns, zstream, scanlines)."""
+    import struct
+    import zlib
+    data = bytes(data)
+    if data[:8] != b"\x89PNG\r\n\x1a\n":
+        raise ValueError("not a PNG file")
+    o, out, idat = 8, dict(plte=None, trns=None), []
+    while o + 8 <= len(data):
+        n, tag = struct.unpack(">I4s", data[o:o + 8])
+        body = data[o + 8:o + 8 + n]
+        o += 12 + n
+        if tag == b"IHDR":
+            out["width"], out["height"], out["depth"], out["ctype"], _, _, out["interlace"] = struct.unpack(">IIBBBBB", body)
+        elif tag == b"PLTE":
+            out["plte"] = body
+        elif tag == b"tRNS":
+            out["trns"] = body
+        elif tag == b"IDAT":
+            idat.append(body)
+        elif tag == b"IEND":
+            break
+    out["zstream"] = b"".join(idat)
+    out["scanlines"] = zlib.decompress(out["zstream"])
+    return out
 
 
 def psnr_db(distortion, channel_mask=0xF):
@@ -185,24 +312,6 @@ def synth_lib():
         return _synth
 
 
-#: every symbol include/pngloss_hip.h declares (tests/test_abi.py checks the .so exports each of them)
-ABI_SYMBOLS = (
-    "optimize_with_rows", "optimize_with_stride", "optimizeForAverageFilter", "optimize_image",
-    "pngloss_hip_device_count", "pngloss_hip_create", "pngloss_hip_destroy", "pngloss_hip_optimize_batch_async",
-    "pngloss_hip_finish", "pngloss_hip_optimize_batch", "pngloss_hip_optimize_batch_host", "pngloss_hip_optimize_batch_host_emit",
-    "pngloss_hip_optimize_batch_host_zlib", "pngloss_hip_zlib_bound", "pngloss_hip_last_deflate_ms", "pngloss_hip_last_engine_ms", "pngloss_hip_last_total_ms",
-    "pngloss_hip_last_histogram", "pngloss_hip_last_engine_info", "pngloss_hip_png_decode_batch_host", "pngloss_hip_png_decode_batch_host_status", "pngloss_hip_png_decode_batch_device", "pngloss_hip_png_decode_batch_device_z", "pngloss_hip_pinned_alloc", "pngloss_hip_pinned_free", "pngloss_hip_set_option", "pngloss_hip_version",
-    "pngloss_hip_multi_create", "pngloss_hip_multi_destroy", "pngloss_hip_multi_count", "pngloss_hip_multi_split",
-    "pngloss_hip_multi_optimize_batch_host",
-    "pngloss_hip_last_distortion", "pngloss_hip_compare_batch", "pngloss_hip_psnr_db", "pngloss_hip_multi_set_option", "pngloss_hip_multi_last_distortion",
-    "pngloss_hip_optimize_batch_target", "pngloss_hip_multi_optimize_batch_host_target",
-    "pngloss_hip_last_ssim", "pngloss_hip_multi_last_ssim", "pngloss_hip_compare_batch_ssim", "pngloss_hip_ssim_mean",
-    "pngloss_hip_optimize_batch_target2", "pngloss_hip_multi_optimize_batch_host_target2",
-    "pngloss_hip_optimize_batch_size", "pngloss_hip_multi_optimize_batch_host_size",
-    "pngloss_hip_compare_batch_visible",
-)
-
-
 def hip_lib():
     global _hip
     with _lock:
@@ -216,82 +325,11 @@ def hip_lib():
                 except ImportError:
                     pass
             lib = _load(os.environ.get("PNGLOSS_HIP_LIBNAME", "libpngloss_hip.so"))
-            rows_t = C.POINTER(C.c_void_p)
-            lib.optimize_with_rows.argtypes = [rows_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_bool, C.c_uint8, C.c_long]
-            lib.optimize_with_rows.restype = C.c_int
-            lib.optimize_with_stride.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_bool, C.c_uint8, C.c_long]
-            lib.optimize_with_stride.restype = None
-            lib.optimizeForAverageFilter.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
-            lib.optimizeForAverageFilter.restype = None
-            lib.optimize_image.argtypes = [C.POINTER(PnglossImage), C.c_void_p, C.c_bool, C.c_uint8, C.c_long]
-            lib.optimize_image.restype = C.c_int
-            lib.pngloss_hip_device_count.restype = C.c_int
-            lib.pngloss_hip_create.argtypes = [C.c_int]
-            lib.pngloss_hip_create.restype = C.c_void_p
-            lib.pngloss_hip_destroy.argtypes = [C.c_void_p]
-            lib.pngloss_hip_destroy.restype = None
-            lib.pngloss_hip_optimize_batch_async.argtypes = [C.c_void_p, C.POINTER(ImageDesc), C.c_size_t, C.c_uint, C.c_long, C.c_void_p]
-            lib.pngloss_hip_optimize_batch_async.restype = C.c_int
-            lib.pngloss_hip_finish.argtypes = [C.c_void_p, C.POINTER(Result), C.c_size_t]
-            lib.pngloss_hip_finish.restype = C.c_int
-            lib.pngloss_hip_optimize_batch.argtypes = [C.c_void_p, C.POINTER(ImageDesc), C.c_size_t, C.c_uint, C.c_long, C.c_void_p, C.POINTER(Result)]
-            lib.pngloss_hip_optimize_batch.restype = C.c_int
-            lib.pngloss_hip_optimize_batch_host.argtypes = [C.c_void_p, C.POINTER(HostImage), C.c_size_t, C.c_uint, C.c_long, C.POINTER(Result)]
-            lib.pngloss_hip_optimize_batch_host.restype = C.c_int
-            lib.pngloss_hip_optimize_batch_host_emit.argtypes = [C.c_void_p, C.POINTER(HostImage), C.c_size_t, C.c_uint, C.c_long, C.POINTER(Result), C.POINTER(Scanlines)]
-            lib.pngloss_hip_optimize_batch_host_emit.restype = C.c_int
-            lib.pngloss_hip_multi_create.argtypes = [C.c_char_p]
-            lib.pngloss_hip_multi_create.restype = C.c_void_p
-            lib.pngloss_hip_multi_destroy.argtypes = [C.c_void_p]
-            lib.pngloss_hip_multi_destroy.restype = None
-            lib.pngloss_hip_multi_count.argtypes = [C.c_void_p]
-            lib.pngloss_hip_multi_count.restype = C.c_int
-            lib.pngloss_hip_multi_split.argtypes = [C.POINTER(HostImage), C.c_size_t, C.c_int, C.POINTER(C.c_int)]
-            lib.pngloss_hip_multi_split.restype = None
-            lib.pngloss_hip_multi_optimize_batch_host.argtypes = [C.c_void_p, C.POINTER(HostImage), C.c_size_t, C.c_uint, C.c_long, C.POINTER(Result), C.POINTER(Scanlines), C.POINTER(ZStream)]
-            lib.pngloss_hip_multi_optimize_batch_host.restype = C.c_int
-            lib.pngloss_hip_optimize_batch_host_zlib.argtypes = [C.c_void_p, C.POINTER(HostImage), C.c_size_t, C.c_uint, C.c_long, C.POINTER(Result), C.POINTER(ZStream)]
-            lib.pngloss_hip_optimize_batch_host_zlib.restype = C.c_int
-            lib.pngloss_hip_zlib_bound.argtypes = [C.c_uint32, C.c_uint32]
-            lib.pngloss_hip_zlib_bound.restype = C.c_size_t
-            lib.pngloss_hip_last_deflate_ms.argtypes = [C.c_void_p]
-            lib.pngloss_hip_last_deflate_ms.restype = C.c_double
-            lib.pngloss_hip_last_engine_ms.argtypes = [C.c_void_p]
-            lib.pngloss_hip_last_engine_ms.restype = C.c_double
-            lib.pngloss_hip_last_total_ms.argtypes = [C.c_void_p]
-            lib.pngloss_hip_last_total_ms.restype = C.c_double
-            lib.pngloss_hip_last_histogram.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
-            lib.pngloss_hip_last_histogram.restype = C.c_int
-            lib.pngloss_hip_version.restype = C.c_char_p
-            lib.pngloss_hip_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
-            lib.pngloss_hip_set_option.restype = C.c_int
-            lib.pngloss_hip_last_distortion.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(Distortion)]
-            lib.pngloss_hip_last_distortion.restype = C.c_int
-            lib.pngloss_hip_compare_batch.argtypes = [C.c_void_p, C.POINTER(ImagePair), C.c_size_t, C.POINTER(Distortion), C.c_void_p]
-            lib.pngloss_hip_compare_batch.restype = C.c_int
-            lib.pngloss_hip_psnr_db.argtypes = [C.POINTER(Distortion), C.c_uint]
-            lib.pngloss_hip_psnr_db.restype = C.c_double
-            lib.pngloss_hip_multi_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
-            lib.pngloss_hip_multi_set_option.restype = C.c_int
-            lib.pngloss_hip_multi_last_distortion.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(Distortion)]
-            lib.pngloss_hip_multi_last_distortion.restype = C.c_int
-            lib.pngloss_hip_last_ssim.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(Ssim)]
-            lib.pngloss_hip_last_ssim.restype = C.c_int
-            lib.pngloss_hip_multi_last_ssim.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(Ssim)]
-            lib.pngloss_hip_multi_last_ssim.restype = C.c_int
-            lib.pngloss_hip_compare_batch_ssim.argtypes = [C.c_void_p, C.POINTER(ImagePair), C.c_size_t, C.POINTER(Ssim), C.c_void_p]
-            lib.pngloss_hip_compare_batch_ssim.restype = C.c_int
-            lib.pngloss_hip_ssim_mean.argtypes = [C.POINTER(Ssim), C.c_uint]
-            lib.pngloss_hip_ssim_mean.restype = C.c_double
-            lib.pngloss_hip_compare_batch_visible.argtypes = [C.c_void_p, C.POINTER(ImagePair), C.c_size_t, C.POINTER(Distortion), C.POINTER(Ssim), C.c_void_p]
-            lib.pngloss_hip_compare_batch_visible.restype = C.c_int
-            _target_abi(lib)
-            _size_abi(lib)
+            for name, (ret, args) in PROTOTYPES.items():
+                fn = getattr(lib, name)
+                fn.restype, fn.argtypes = ret, args
             _hip = lib
         return _hip
-
-
-PNGLOSS_INTERNAL_ABORT = 65
 
 
 def _check(rc, what, partial_ok=False):
@@ -302,11 +340,115 @@ def _check(rc, what, partial_ok=False):
         raise RuntimeError(f"{what} failed with pngloss_error {rc}")
 
 
+# ---- marshalling: each table of the C ABI is filled in one place, and read back in one place ----------------------------------------------------
+# The arrays a helper returns beside a table are what the table points into: the caller keeps them in locals until the C call has returned.
+
+def _array(ctype, n):
+    """n elements of ctype; one for n = 0, so that an empty batch still hands the C side a valid pointer"""
+    return (ctype * max(n, 1))()
+
+
 def _row_pointers(arr: np.ndarray):
     h = arr.shape[0]
     stride = arr.strides[0]
     base = arr.ctypes.data
-    return (C.c_void_p * h)(*[base + y * stride for y in range(h)])
+    return (C.c_void_p * max(h, 1))(*[base + y * stride for y in range(h)])
+
+
+def _image_descs(images):
+    """(d_rgba_ptr, d_filters_ptr_or_0, width, height) tuples -> ImageDesc table"""
+    descs = _array(ImageDesc, len(images))
+    for i, (p, f, w, h) in enumerate(images):
+        descs[i] = ImageDesc(p or None, f or None, w, h)
+    return descs
+
+
+def _image_pairs(pairs):
+    """(d_a_ptr, d_b_ptr, width, height) tuples -> ImagePair table"""
+    arr = _array(ImagePair, len(pairs))
+    for i, (a, b, w, h) in enumerate(pairs):
+        arr[i] = ImagePair(a or None, b or None, w, h)
+    return arr
+
+
+def _host_images(arrays, want_filters=True, inplace=False):
+    """(H, W, 4) uint8 arrays -> (outs, filts, HostImage table).  outs: copies for the C call to rewrite, or with inplace the arrays themselves
+    (C-contiguous uint8); filts: one zeroed (H,) array each, or None each without want_filters (the table then carries NULL)."""
+    outs = list(arrays) if inplace else [np.ascontiguousarray(a).copy() for a in arrays]
+    if inplace:
+        assert all(a.flags["C_CONTIGUOUS"] and a.dtype == np.uint8 for a in outs)
+    filts = [np.zeros(a.shape[0], np.uint8) if want_filters else None for a in outs]
+    imgs = _array(HostImage, len(outs))
+    for i, (a, f) in enumerate(zip(outs, filts)):
+        imgs[i] = HostImage(a.ctypes.data, f.ctypes.data if f is not None else None, a.shape[1], a.shape[0])
+    return outs, filts, imgs
+
+
+def _scanline_buffers(outs):
+    """room for the filtered scanlines of every array of outs -> (Scanlines table, ids, rows): ids[i] (H,), rows[i] (H, W * 4), the pitch RGBA's"""
+    ids = [np.zeros(a.shape[0], np.uint8) for a in outs]
+    rows = [np.zeros((a.shape[0], a.shape[1] * 4), np.uint8) for a in outs]
+    lines = _array(Scanlines, len(outs))
+    for i, (f, r) in enumerate(zip(ids, rows)):
+        lines[i] = Scanlines(f.ctypes.data, r.ctypes.data, r.shape[1], -1)
+    return lines, ids, rows
+
+
+def _scanlines_back(lines, ids, rows):
+    """per image (color_type, filter_types[H], scanlines[H, W * channels]): the colour type the call detected says how much of a row it wrote"""
+    channels = {0: 1, 4: 2, 2: 3, 6: 4}
+    return [(lines[i].color_type, f, r[:, : r.shape[1] // 4 * channels.get(lines[i].color_type, 4)].copy()) for i, (f, r) in enumerate(zip(ids, rows))]
+
+
+def _zstreams(lib, shapes, stream_only=False):
+    """room for the zlib stream of every (width, height) of shapes -> (ZStream table, bufs); stream_only: PNGLOSS_HIP_Z_STREAM_ONLY"""
+    bufs = [np.zeros(lib.pngloss_hip_zlib_bound(w, h), np.uint8) for (w, h) in shapes]
+    zs = _array(ZStream, len(bufs))
+    for i, b in enumerate(bufs):
+        zs[i] = ZStream(b.ctypes.data, b.size, 0, -1, (C.c_uint32 * 3)(0, 0, 0), 1 if stream_only else 0)
+    return zs, bufs
+
+
+def _zstreams_back(zs, bufs):
+    """per image (color_type, zlib stream bytes, blocks)"""
+    return [(zs[i].color_type, b[: zs[i].size].tobytes(), tuple(zs[i].blocks)) for i, b in enumerate(bufs)]
+
+
+def _shapes(arrays):
+    return [(a.shape[1], a.shape[0]) for a in arrays]
+
+
+def _png_chunks(p):
+    """the palette and tRNS members both source structs end their common part with, from a parse_png dict"""
+    return p["plte"], len(p["plte"]) // 3 if p["plte"] else 0, p["trns"], len(p["trns"]) if p["trns"] else 0
+
+
+def _png_sources(parsed, outs=None, scanlines=None):
+    """parse_png dicts -> PngSource table.  outs: the (H, W, 4) arrays the host forms decode into (the device forms use no rgba);
+    scanlines: what to send in place of the parsed files' own (page-locked copies)."""
+    src = _array(PngSource, len(parsed))
+    for i, p in enumerate(parsed):
+        src[i] = PngSource(scanlines[i] if scanlines is not None else p["scanlines"], p["width"], p["height"], p["ctype"], p["depth"], *_png_chunks(p),
+                           outs[i].ctypes.data if outs is not None else None, interlace=p["interlace"])
+    return src
+
+
+def _decode_outputs(parsed):
+    return [np.zeros((p["height"], p["width"], 4), np.uint8) for p in parsed]
+
+
+def _frames(ptrs, parsed):
+    return [(ptrs[i], p["width"], p["height"]) for i, p in enumerate(parsed)]
+
+
+def _result_dict(r):
+    """what the device-resident calls report per image"""
+    return dict(status=r.status, bpp=r.bytes_per_pixel, unique_symbols=r.unique_symbols, retried_rows=r.retried_rows, repaired_pixels=r.repaired_pixels)
+
+
+def _host_result_dict(r):
+    """what the host-memory calls report per image"""
+    return dict(status=r.status, bpp=r.bytes_per_pixel, unique_symbols=r.unique_symbols)
 
 
 # ---- host-pointer seam, same names as the reference ---------------------------------------------------------
@@ -317,8 +459,7 @@ def optimize_with_rows(rgba: np.ndarray, strength: int = 19, bleed: int = 2, wan
     out = np.ascontiguousarray(rgba).copy()
     h, w = out.shape[:2]
     filt = np.zeros(h, np.uint8) if want_filters else None
-    rows = _row_pointers(out) if h else (C.c_void_p * 1)()
-    rc = hip_lib().optimize_with_rows(rows, w, h, filt.ctypes.data_as(C.c_void_p) if want_filters else None, verbose, strength, bleed)
+    rc = hip_lib().optimize_with_rows(_row_pointers(out), w, h, filt.ctypes.data_as(C.c_void_p) if want_filters else None, verbose, strength, bleed)
     _check(rc, "optimize_with_rows")
     return out, filt
 
@@ -345,7 +486,7 @@ def optimize_image(packed: np.ndarray, strength: int = 19, bleed: int = 2, want_
     out = np.ascontiguousarray(packed).copy()
     h, w, bpp = out.shape
     filt = np.zeros(h, np.uint8) if want_filters else None
-    rows = _row_pointers(out) if h else (C.c_void_p * 1)()
+    rows = _row_pointers(out)
     img = PnglossImage(C.cast(rows, C.POINTER(C.c_void_p)), w, h, bpp)
     rc = hip_lib().optimize_image(C.byref(img), filt.ctypes.data_as(C.c_void_p) if want_filters else None, False, strength, bleed)
     _check(rc, "optimize_image")
@@ -359,6 +500,7 @@ class HipContext:
 
     def __init__(self, device: int = -1):
         self._lib = hip_lib()
+        self._n = 0
         self._ctx = self._lib.pngloss_hip_create(device)
         if not self._ctx:
             raise RuntimeError("pngloss_hip_create failed: no usable HIP device (there is no CPU fallback)")
@@ -381,79 +523,79 @@ class HipContext:
     def enqueue(self, images, strength=19, bleed=2, stream=0):
         """images: sequence of (d_rgba_ptr, d_filters_ptr_or_0, width, height). Asynchronous."""
         n = len(images)
-        descs = (ImageDesc * max(n, 1))()
-        for i, (p, f, w, h) in enumerate(images):
-            descs[i] = ImageDesc(p, f or None, w, h)
-        _check(self._lib.pngloss_hip_optimize_batch_async(self._ctx, descs, n, strength, bleed, stream or None), "enqueue")
+        _check(self._lib.pngloss_hip_optimize_batch_async(self._ctx, _image_descs(images), n, strength, bleed, stream or None), "enqueue")
         self._n = n
 
     def finish(self):
-        n = getattr(self, "_n", 0)
-        res = (Result * max(n, 1))()
+        n = self._n
+        res = _array(Result, n)
         _check(self._lib.pngloss_hip_finish(self._ctx, res, n), "finish", partial_ok=True)
-        return [dict(status=r.status, bpp=r.bytes_per_pixel, unique_symbols=r.unique_symbols, retried_rows=r.retried_rows, repaired_pixels=r.repaired_pixels) for r in res[:n]]
+        return [_result_dict(r) for r in res[:n]]
 
     def run(self, images, strength=19, bleed=2, stream=0):
         """pngloss_hip_optimize_batch: the SYNCHRONOUS entry point (enqueue + finish in one call; the library then spares the caller's stream the device-side
         wait for the engine that the asynchronous entry needs)."""
         n = len(images)
-        descs = (ImageDesc * max(n, 1))()
-        for i, (p, f, w, h) in enumerate(images):
-            descs[i] = ImageDesc(p, f or None, w, h)
-        res = (Result * max(n, 1))()
+        res = _array(Result, n)
         self._n = n
-        _check(self._lib.pngloss_hip_optimize_batch(self._ctx, descs, n, strength, bleed, stream or None, res), "optimize_batch", partial_ok=True)
-        return [dict(status=r.status, bpp=r.bytes_per_pixel, unique_symbols=r.unique_symbols, retried_rows=r.retried_rows, repaired_pixels=r.repaired_pixels) for r in res[:n]]
+        _check(self._lib.pngloss_hip_optimize_batch(self._ctx, _image_descs(images), n, strength, bleed, stream or None, res), "optimize_batch", partial_ok=True)
+        return [_result_dict(r) for r in res[:n]]
 
     def run_host(self, arrays, strength=19, bleed=2, want_filters=True, inplace=False):
         """pngloss_hip_optimize_batch_host on a list of (H, W, 4) uint8 arrays.  Returns (outs, filters, results).
         inplace: the arrays (C-contiguous uint8) are optimised where they are, like the C call does; otherwise copies are."""
-        outs = list(arrays) if inplace else [np.ascontiguousarray(a).copy() for a in arrays]
-        if inplace:
-            assert all(a.flags["C_CONTIGUOUS"] and a.dtype == np.uint8 for a in outs)
-        filts = [np.zeros(a.shape[0], np.uint8) if want_filters else None for a in outs]
+        outs, filts, imgs = _host_images(arrays, want_filters, inplace)
         n = len(outs)
-        imgs = (HostImage * max(n, 1))()
-        for i, (a, f) in enumerate(zip(outs, filts)):
-            imgs[i] = HostImage(a.ctypes.data, f.ctypes.data if f is not None else None, a.shape[1], a.shape[0])
-        res = (Result * max(n, 1))()
+        res = _array(Result, n)
         _check(self._lib.pngloss_hip_optimize_batch_host(self._ctx, imgs, n, strength, bleed, res), "optimize_batch_host", partial_ok=True)
-        return outs, filts, [dict(status=r.status, bpp=r.bytes_per_pixel, unique_symbols=r.unique_symbols) for r in res[:n]]
+        return outs, filts, [_host_result_dict(r) for r in res[:n]]
 
     def run_host_emit(self, arrays, strength=19, bleed=2, want_filters=True):
         """pngloss_hip_optimize_batch_host_emit: like run_host, plus per image (color_type, filter_types[H], scanlines[H, W*ch])."""
-        outs = [np.ascontiguousarray(a).copy() for a in arrays]
-        filts = [np.zeros(a.shape[0], np.uint8) if want_filters else None for a in outs]
+        outs, filts, imgs = _host_images(arrays, want_filters)
+        lines, ids, rows = _scanline_buffers(outs)
         n = len(outs)
-        imgs = (HostImage * max(n, 1))()
-        lines = (Scanlines * max(n, 1))()
-        ids = [np.zeros(a.shape[0], np.uint8) for a in outs]
-        rows = [np.zeros((a.shape[0], a.shape[1] * 4), np.uint8) for a in outs]
-        for i, (a, f) in enumerate(zip(outs, filts)):
-            imgs[i] = HostImage(a.ctypes.data, f.ctypes.data if f is not None else None, a.shape[1], a.shape[0])
-            lines[i] = Scanlines(ids[i].ctypes.data, rows[i].ctypes.data, a.shape[1] * 4, -1)
-        res = (Result * max(n, 1))()
-        _check(self._lib.pngloss_hip_optimize_batch_host_emit(self._ctx, imgs, n, strength, bleed, res, lines), "optimize_batch_host_emit", partial_ok=True)
-        chans = {0: 1, 4: 2, 2: 3, 6: 4}
-        emitted = [(lines[i].color_type, ids[i], rows[i][:, : outs[i].shape[1] * chans.get(lines[i].color_type, 4)].copy()) for i in range(n)]
-        return outs, filts, emitted
+        _check(self._lib.pngloss_hip_optimize_batch_host_emit(self._ctx, imgs, n, strength, bleed, _array(Result, n), lines), "optimize_batch_host_emit",
+               partial_ok=True)
+        return outs, filts, _scanlines_back(lines, ids, rows)
 
     def run_host_zlib(self, arrays, strength=19, bleed=2, want_filters=True, stream_only=False):
         """pngloss_hip_optimize_batch_host_zlib: like run_host, plus per image (color_type, zlib stream bytes, blocks).
         stream_only: PNGLOSS_HIP_Z_STREAM_ONLY -- the returned pixel arrays are then the unmodified inputs."""
-        outs = [np.ascontiguousarray(a).copy() for a in arrays]
-        filts = [np.zeros(a.shape[0], np.uint8) if want_filters else None for a in outs]
+        outs, filts, imgs = _host_images(arrays, want_filters)
+        zs, bufs = _zstreams(self._lib, _shapes(outs), stream_only)
         n = len(outs)
-        imgs = (HostImage * max(n, 1))()
-        zs = (ZStream * max(n, 1))()
-        bufs = [np.zeros(self._lib.pngloss_hip_zlib_bound(a.shape[1], a.shape[0]), np.uint8) for a in outs]
-        for i, (a, f) in enumerate(zip(outs, filts)):
-            imgs[i] = HostImage(a.ctypes.data, f.ctypes.data if f is not None else None, a.shape[1], a.shape[0])
-            zs[i] = ZStream(bufs[i].ctypes.data, bufs[i].size, 0, -1, (C.c_uint32 * 3)(0, 0, 0), 1 if stream_only else 0)
-        res = (Result * max(n, 1))()
-        _check(self._lib.pngloss_hip_optimize_batch_host_zlib(self._ctx, imgs, n, strength, bleed, res, zs), "optimize_batch_host_zlib", partial_ok=True)
-        streams = [(zs[i].color_type, bufs[i][: zs[i].size].tobytes(), tuple(zs[i].blocks)) for i in range(n)]
-        return outs, filts, streams
+        _check(self._lib.pngloss_hip_optimize_batch_host_zlib(self._ctx, imgs, n, strength, bleed, _array(Result, n), zs), "optimize_batch_host_zlib",
+               partial_ok=True)
+        return outs, filts, _zstreams_back(zs, bufs)
+
+    def run_target(self, images, target, bleed=2, stream=0):
+        """pngloss_hip_optimize_batch_target: images as for run(); every image ends up as run() at its chosen strength leaves it.  Synchronous.
+        Returns (results, reports): the dicts run() returns and one TargetReport per image.  With a Target2 the call is
+        pngloss_hip_optimize_batch_target2 and returns (results, reports, ssim): one Ssim per image, filled when target.min_ssim != 0."""
+        n = len(images)
+        res, rep = _array(Result, n), _array(TargetReport, n)
+        args = (self._ctx, _image_descs(images), n, C.byref(target), bleed, stream or None, res, rep)
+        self._n = 0
+        if isinstance(target, Target2):
+            ssim = _array(Ssim, n)
+            _check(self._lib.pngloss_hip_optimize_batch_target2(*args, ssim), "optimize_batch_target2", partial_ok=True)
+            return [_result_dict(r) for r in res[:n]], list(rep[:n]), list(ssim[:n])
+        _check(self._lib.pngloss_hip_optimize_batch_target(*args), "optimize_batch_target", partial_ok=True)
+        return [_result_dict(r) for r in res[:n]], list(rep[:n])
+
+    def run_size(self, images, max_bytes, max_strength=19, bleed=2, stream=0, want_streams=False):
+        """pngloss_hip_optimize_batch_size: images as for run(), max_bytes one budget per image; every image ends up as run() at its chosen strength
+        leaves it.  Synchronous.  Returns (results, reports, streams): the dicts run() returns, one SizeReport per image and -- with want_streams --
+        per image (color_type, zlib stream, blocks), else None."""
+        n = len(images)
+        res, rep = _array(Result, n), _array(SizeReport, n)
+        zs, bufs = _zstreams(self._lib, [(w, h) for (_, _, w, h) in images]) if want_streams else (None, None)
+        target = SizeTarget(list(max_bytes), max_strength)
+        self._n = 0
+        _check(self._lib.pngloss_hip_optimize_batch_size(self._ctx, _image_descs(images), n, C.byref(target), bleed, stream or None, res, zs, rep),
+               "optimize_batch_size", partial_ok=True)
+        return [_result_dict(r) for r in res[:n]], list(rep[:n]), _zstreams_back(zs, bufs) if want_streams else None
 
     @property
     def deflate_ms(self):
@@ -471,15 +613,18 @@ class HipContext:
         """pngloss_hip_png_decode_batch_host on a list of PNG file contents (bytes): chunk parsing and inflate on the host (parse_png), the
         inverse filters and the expansion to RGBA8 on the device.  Returns a list of (H, W, 4) uint8 arrays."""
         parsed = [parse_png(f) for f in files]
-        outs = [np.zeros((p["height"], p["width"], 4), np.uint8) for p in parsed]
-        src = (PngSource * max(1, len(parsed)))()
-        for i, (p, o) in enumerate(zip(parsed, outs)):
-            src[i] = PngSource(p["scanlines"], p["width"], p["height"], p["ctype"], p["depth"], p["plte"], len(p["plte"]) // 3 if p["plte"] else 0,
-                               p["trns"], len(p["trns"]) if p["trns"] else 0, o.ctypes.data, interlace=p["interlace"])
-        self._lib.pngloss_hip_png_decode_batch_host.argtypes = [C.c_void_p, C.POINTER(PngSource), C.c_size_t]
-        self._lib.pngloss_hip_png_decode_batch_host.restype = C.c_int
-        _check(self._lib.pngloss_hip_png_decode_batch_host(self._ctx, src, len(parsed)), "png_decode")
+        outs = _decode_outputs(parsed)
+        _check(self._lib.pngloss_hip_png_decode_batch_host(self._ctx, _png_sources(parsed, outs), len(parsed)), "png_decode")
         return outs
+
+    def png_decode_status(self, files):
+        """pngloss_hip_png_decode_batch_host_status: like png_decode, but a damaged file only fails itself.  Returns (outs, status list, return code)."""
+        parsed = [parse_png(f) for f in files]
+        n = len(parsed)
+        outs = _decode_outputs(parsed)
+        st = _array(C.c_int, n)
+        rc = self._lib.pngloss_hip_png_decode_batch_host_status(self._ctx, _png_sources(parsed, outs), n, st)
+        return outs, list(st)[:n], rc
 
     def png_decode_device(self, files, stream=0, pinned=True):
         """pngloss_hip_png_decode_batch_device: the decoded RGBA8 frames STAY on the device.  Returns a list of (device pointer, width, height)
@@ -487,35 +632,26 @@ class HipContext:
         (pngloss_hip_pinned_alloc), as the command line tool does."""
         parsed = [parse_png(f) for f in files]
         n = len(parsed)
-        src = (PngSource * max(1, n))()
-        self._lib.pngloss_hip_pinned_alloc.argtypes = [C.c_size_t]
-        self._lib.pngloss_hip_pinned_alloc.restype = C.c_void_p
-        self._lib.pngloss_hip_pinned_free.argtypes = [C.c_void_p]
-        self._lib.pngloss_hip_pinned_free.restype = None
-        staged = []
-        for i, p in enumerate(parsed):
-            sl = p["scanlines"]
-            if pinned and len(sl):
-                buf = self._lib.pngloss_hip_pinned_alloc(len(sl))
-                if not buf:
-                    raise RuntimeError("pngloss_hip_pinned_alloc failed")
-                C.memmove(buf, sl, len(sl))
-                staged.append(buf)
-                sl = C.cast(buf, C.c_char_p)
-            src[i] = PngSource(sl, p["width"], p["height"], p["ctype"], p["depth"], p["plte"], len(p["plte"]) // 3 if p["plte"] else 0,
-                               p["trns"], len(p["trns"]) if p["trns"] else 0, None, interlace=p["interlace"])
-        ptrs = (C.c_void_p * max(1, n))()
-        st = (C.c_int * max(1, n))()
-        self._lib.pngloss_hip_png_decode_batch_device.argtypes = [C.c_void_p, C.POINTER(PngSource), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p]
-        self._lib.pngloss_hip_png_decode_batch_device.restype = C.c_int
+        staged, scanlines = [], []
+        ptrs, st = _array(C.c_void_p, n), _array(C.c_int, n)
         try:
-            rc = self._lib.pngloss_hip_png_decode_batch_device(self._ctx, src, n, ptrs, st, stream or None)
+            for p in parsed:
+                sl = p["scanlines"]
+                if pinned and len(sl):
+                    buf = self._lib.pngloss_hip_pinned_alloc(len(sl))
+                    if not buf:
+                        raise RuntimeError("pngloss_hip_pinned_alloc failed")
+                    staged.append(buf)
+                    C.memmove(buf, sl, len(sl))
+                    sl = C.cast(buf, C.c_char_p)
+                scanlines.append(sl)
+            rc = self._lib.pngloss_hip_png_decode_batch_device(self._ctx, _png_sources(parsed, scanlines=scanlines), n, ptrs, st, stream or None)
         finally:
             for b in staged:
                 self._lib.pngloss_hip_pinned_free(b)
         if rc not in (0, 25):
             _check(rc, "png_decode_device")
-        return [(ptrs[i], parsed[i]["width"], parsed[i]["height"]) for i in range(n)], list(st)[:n]
+        return _frames(ptrs, parsed), list(st)[:n]
 
     def png_decode_device_z(self, files, stream=0, zstreams=None):
         """pngloss_hip_png_decode_batch_device_z: the compressed image data goes up, inflate + inverse filters + expansion run on the device, the
@@ -523,41 +659,19 @@ class HipContext:
         streams (tests hand damaged ones in)."""
         parsed = [parse_png(f) for f in files]
         n = len(parsed)
-        src = (PngZSource * max(1, n))()
-        keep = []
-        for i, p in enumerate(parsed):
-            z = zstreams[i] if zstreams is not None else p["zstream"]
-            keep.append(z)
-            src[i] = PngZSource(z, len(z), p["width"], p["height"], p["ctype"], p["depth"], p["plte"], len(p["plte"]) // 3 if p["plte"] else 0,
-                                p["trns"], len(p["trns"]) if p["trns"] else 0, interlace=p["interlace"])
-        ptrs = (C.c_void_p * max(1, n))()
-        st = (C.c_int * max(1, n))()
-        self._lib.pngloss_hip_png_decode_batch_device_z.argtypes = [C.c_void_p, C.POINTER(PngZSource), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p]
-        self._lib.pngloss_hip_png_decode_batch_device_z.restype = C.c_int
+        src = _array(PngZSource, n)
+        keep = [zstreams[i] if zstreams is not None else p["zstream"] for i, p in enumerate(parsed)]
+        for i, (p, z) in enumerate(zip(parsed, keep)):
+            src[i] = PngZSource(z, len(z), p["width"], p["height"], p["ctype"], p["depth"], *_png_chunks(p), interlace=p["interlace"])
+        ptrs, st = _array(C.c_void_p, n), _array(C.c_int, n)
         rc = self._lib.pngloss_hip_png_decode_batch_device_z(self._ctx, src, n, ptrs, st, stream or None)
         if rc not in (0, 25):
             _check(rc, "png_decode_device_z")
-        return [(ptrs[i], parsed[i]["width"], parsed[i]["height"]) for i in range(n)], list(st)[:n], rc
-
-    def png_decode_status(self, files):
-        """pngloss_hip_png_decode_batch_host_status: like png_decode, but a damaged file only fails itself.  Returns (outs, status list, return code)."""
-        parsed = [parse_png(f) for f in files]
-        outs = [np.zeros((p["height"], p["width"], 4), np.uint8) for p in parsed]
-        src = (PngSource * max(1, len(parsed)))()
-        for i, (p, o) in enumerate(zip(parsed, outs)):
-            src[i] = PngSource(p["scanlines"], p["width"], p["height"], p["ctype"], p["depth"], p["plte"], len(p["plte"]) // 3 if p["plte"] else 0,
-                               p["trns"], len(p["trns"]) if p["trns"] else 0, o.ctypes.data, interlace=p["interlace"])
-        st = (C.c_int * max(1, len(parsed)))()
-        self._lib.pngloss_hip_png_decode_batch_host_status.argtypes = [C.c_void_p, C.POINTER(PngSource), C.c_size_t, C.POINTER(C.c_int)]
-        self._lib.pngloss_hip_png_decode_batch_host_status.restype = C.c_int
-        rc = self._lib.pngloss_hip_png_decode_batch_host_status(self._ctx, src, len(parsed), st)
-        return outs, list(st)[:len(parsed)], rc
+        return _frames(ptrs, parsed), list(st)[:n], rc
 
     def engine_info(self, index=0):
         """pngloss_hip_last_engine_info: dict(engine, attempts, restarts, serial_rows, none_dropped) for image `index`."""
         a = (C.c_int32 * 8)()
-        self._lib.pngloss_hip_last_engine_info.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
-        self._lib.pngloss_hip_last_engine_info.restype = C.c_int
         _check(self._lib.pngloss_hip_last_engine_info(self._ctx, index, a), "engine_info")
         return dict(engine={3: "segment-parallel", 0: "workgroup-per-image", 4: "row-statistics (strength 0)"}.get(a[0], a[0]), attempts=a[1], restarts=a[2], serial_rows=a[3], none_dropped=a[4], walked_segments=a[5], launch_groups=a[6], stream_wait=a[7])
 
@@ -575,39 +689,30 @@ class HipContext:
         _check(self._lib.pngloss_hip_last_ssim(self._ctx, index, C.byref(r)), "last_ssim")
         return r
 
+    def compare(self, pairs, stream=0):
+        """pngloss_hip_compare_batch: pairs = sequence of (d_a_ptr, d_b_ptr, width, height), device-resident RGBA8; returns one Distortion per pair
+        (b against a).  Synchronous."""
+        n = len(pairs)
+        out = _array(Distortion, n)
+        _check(self._lib.pngloss_hip_compare_batch(self._ctx, _image_pairs(pairs), n, out, stream or None), "compare_batch")
+        return list(out[:n])
+
     def compare_ssim(self, pairs, stream=0):
         """pngloss_hip_compare_batch_ssim: pairs as for compare(); returns one Ssim per pair (b against a).  Synchronous."""
         n = len(pairs)
-        arr = (ImagePair * max(n, 1))()
-        for i, (a, b, w, h) in enumerate(pairs):
-            arr[i] = ImagePair(a or None, b or None, w, h)
-        out = (Ssim * max(n, 1))()
-        _check(self._lib.pngloss_hip_compare_batch_ssim(self._ctx, arr, n, out, stream or None), "compare_batch_ssim")
-        return [out[i] for i in range(n)]
+        out = _array(Ssim, n)
+        _check(self._lib.pngloss_hip_compare_batch_ssim(self._ctx, _image_pairs(pairs), n, out, stream or None), "compare_batch_ssim")
+        return list(out[:n])
 
     def compare_visible(self, pairs, distortion=True, ssim=True, stream=0):
         """pngloss_hip_compare_batch_visible: pairs as for compare(), measured over visible pixels (alpha-premultiplied channels plus alpha; whatever
         set_option("measure", ...) says).  Returns (list of Distortion or None, list of Ssim or None): None for an output that was not asked for.
         Synchronous."""
         n = len(pairs)
-        arr = (ImagePair * max(n, 1))()
-        for i, (a, b, w, h) in enumerate(pairs):
-            arr[i] = ImagePair(a or None, b or None, w, h)
-        d = (Distortion * max(n, 1))() if distortion else None
-        s = (Ssim * max(n, 1))() if ssim else None
-        _check(self._lib.pngloss_hip_compare_batch_visible(self._ctx, arr, n, d, s, stream or None), "compare_batch_visible")
-        return ([d[i] for i in range(n)] if distortion else None), ([s[i] for i in range(n)] if ssim else None)
-
-    def compare(self, pairs, stream=0):
-        """pngloss_hip_compare_batch: pairs = sequence of (d_a_ptr, d_b_ptr, width, height), device-resident RGBA8; returns one Distortion per pair
-        (b against a).  Synchronous."""
-        n = len(pairs)
-        arr = (ImagePair * max(n, 1))()
-        for i, (a, b, w, h) in enumerate(pairs):
-            arr[i] = ImagePair(a or None, b or None, w, h)
-        out = (Distortion * max(n, 1))()
-        _check(self._lib.pngloss_hip_compare_batch(self._ctx, arr, n, out, stream or None), "compare_batch")
-        return [out[i] for i in range(n)]
+        d = _array(Distortion, n) if distortion else None
+        s = _array(Ssim, n) if ssim else None
+        _check(self._lib.pngloss_hip_compare_batch_visible(self._ctx, _image_pairs(pairs), n, d, s, stream or None), "compare_batch_visible")
+        return (list(d[:n]) if distortion else None), (list(s[:n]) if ssim else None)
 
     def histogram(self, index=0):
         h = np.zeros(256, np.uint32)
@@ -632,13 +737,12 @@ def source_digest():
 
 def multi_split(shapes, parts):
     """pngloss_hip_multi_split (the C host's LPT split) for a list of (width, height); returns owner indices.  No GPU needed."""
-    lib = hip_lib()
     n = len(shapes)
-    imgs = (HostImage * max(n, 1))()
+    imgs = _array(HostImage, n)
     for i, (w, h) in enumerate(shapes):
         imgs[i] = HostImage(None, None, w, h)
-    owner = (C.c_int * max(n, 1))()
-    lib.pngloss_hip_multi_split(imgs, n, parts, owner)
+    owner = _array(C.c_int, n)
+    hip_lib().pngloss_hip_multi_split(imgs, n, parts, owner)
     return list(owner[:n])
 
 
@@ -683,226 +787,45 @@ class HipMulti:
         return r
 
     def run_host(self, arrays, strength=19, bleed=2, want_filters=True):
-        outs = [np.ascontiguousarray(a).copy() for a in arrays]
-        filts = [np.zeros(a.shape[0], np.uint8) if want_filters else None for a in outs]
+        outs, filts, imgs = _host_images(arrays, want_filters)
         n = len(outs)
-        imgs = (HostImage * max(n, 1))()
-        for i, (a, f) in enumerate(zip(outs, filts)):
-            imgs[i] = HostImage(a.ctypes.data, f.ctypes.data if f is not None else None, a.shape[1], a.shape[0])
-        res = (Result * max(n, 1))()
+        res = _array(Result, n)
         _check(self._lib.pngloss_hip_multi_optimize_batch_host(self._m, imgs, n, strength, bleed, res, None, None), "multi_optimize_batch_host", partial_ok=True)
-        return outs, filts, [dict(status=r.status, bpp=r.bytes_per_pixel, unique_symbols=r.unique_symbols) for r in res[:n]]
+        return outs, filts, [_host_result_dict(r) for r in res[:n]]
 
+    def run_host_target(self, arrays, target, bleed=2, want_filters=True, emit=None, stream_only=False):
+        """pngloss_hip_multi_optimize_batch_host_target on a list of (H, W, 4) uint8 arrays.  emit: None, "scanlines" or "zlib".  Returns
+        (outs, filters, results, reports, emitted): emitted is None, or per image what run_host_emit / run_host_zlib return for it.  With a Target2 the
+        call is pngloss_hip_multi_optimize_batch_host_target2 and a sixth element follows: one Ssim per image, filled when target.min_ssim != 0."""
+        if emit not in (None, "scanlines", "zlib"):
+            raise ValueError("emit: None, 'scanlines' or 'zlib'")
+        outs, filts, imgs = _host_images(arrays, want_filters)
+        n = len(outs)
+        lines, ids, rows = _scanline_buffers(outs) if emit == "scanlines" else (None, None, None)
+        zs, bufs = _zstreams(self._lib, _shapes(outs), stream_only) if emit == "zlib" else (None, None)
+        res, rep = _array(Result, n), _array(TargetReport, n)
+        args = (self._m, imgs, n, C.byref(target), bleed, res, lines, zs, rep)
+        ssim = _array(Ssim, n) if isinstance(target, Target2) else None
+        if ssim is not None:
+            _check(self._lib.pngloss_hip_multi_optimize_batch_host_target2(*args, ssim), "multi_optimize_batch_host_target2", partial_ok=True)
+        else:
+            _check(self._lib.pngloss_hip_multi_optimize_batch_host_target(*args), "multi_optimize_batch_host_target", partial_ok=True)
+        emitted = _scanlines_back(lines, ids, rows) if lines is not None else _zstreams_back(zs, bufs) if zs is not None else None
+        out = (outs, filts, [_host_result_dict(r) for r in res[:n]], list(rep[:n]), emitted)
+        return out + (list(ssim[:n]),) if ssim is not None else out
 
-# ---- a strength per image from a distortion target ----------------------------------------------------------
-
-class Target(C.Structure):
-    """pngloss_hip_target: min_psnr_db (0 = no condition, inf = only lossless results pass), max_abs_error (0 = no condition, 1..255) and
-    max_strength (M, 0..255: the search never goes above it).  include/pngloss_hip.h states the rule."""
-    _fields_ = [("min_psnr_db", C.c_double), ("max_abs_error", C.c_uint32), ("max_strength", C.c_uint32)]
-
-    def __init__(self, min_psnr_db=0.0, max_abs_error=0, max_strength=19):
-        super().__init__(min_psnr_db, max_abs_error, max_strength)
-
-
-class Target2(C.Structure):
-    """pngloss_hip_target2: a Target with min_ssim, the smallest allowed mean SSIM over the stored channels (0 = no condition, else in (0, 1])."""
-    _fields_ = [("min_psnr_db", C.c_double), ("max_abs_error", C.c_uint32), ("max_strength", C.c_uint32), ("min_ssim", C.c_double)]
-
-    def __init__(self, min_psnr_db=0.0, max_abs_error=0, max_strength=19, min_ssim=0.0):
-        super().__init__(min_psnr_db, max_abs_error, max_strength, min_ssim)
-
-
-class TargetReport(C.Structure):
-    """pngloss_hip_target_report: the chosen strength, the probes of the rule, the row-engine runs spent and the Distortion of the result kept."""
-    _fields_ = [("strength", C.c_uint32), ("probes", C.c_uint32), ("runs", C.c_uint32), ("reserved", C.c_uint32), ("distortion", Distortion)]
-
-    def as_dict(self):
-        return dict(strength=self.strength, probes=self.probes, runs=self.runs, distortion=self.distortion.as_dict())
-
-
-def _target_abi(lib):
-    """the prototypes of the two target entry points (hip_lib sets them once)"""
-    lib.pngloss_hip_optimize_batch_target.argtypes = [C.c_void_p, C.POINTER(ImageDesc), C.c_size_t, C.POINTER(Target), C.c_long, C.c_void_p, C.POINTER(Result),
-                                                      C.POINTER(TargetReport)]
-    lib.pngloss_hip_optimize_batch_target.restype = C.c_int
-    lib.pngloss_hip_multi_optimize_batch_host_target.argtypes = [C.c_void_p, C.POINTER(HostImage), C.c_size_t, C.POINTER(Target), C.c_long, C.POINTER(Result),
-                                                                 C.POINTER(Scanlines), C.POINTER(ZStream), C.POINTER(TargetReport)]
-    lib.pngloss_hip_multi_optimize_batch_host_target.restype = C.c_int
-    lib.pngloss_hip_optimize_batch_target2.argtypes = [C.c_void_p, C.POINTER(ImageDesc), C.c_size_t, C.POINTER(Target2), C.c_long, C.c_void_p, C.POINTER(Result),
-                                                       C.POINTER(TargetReport), C.POINTER(Ssim)]
-    lib.pngloss_hip_optimize_batch_target2.restype = C.c_int
-    lib.pngloss_hip_multi_optimize_batch_host_target2.argtypes = [C.c_void_p, C.POINTER(HostImage), C.c_size_t, C.POINTER(Target2), C.c_long, C.POINTER(Result),
-                                                                  C.POINTER(Scanlines), C.POINTER(ZStream), C.POINTER(TargetReport), C.POINTER(Ssim)]
-    lib.pngloss_hip_multi_optimize_batch_host_target2.restype = C.c_int
-    return lib
-
-
-def _result_dict(r):
-    return dict(status=r.status, bpp=r.bytes_per_pixel, unique_symbols=r.unique_symbols, retried_rows=r.retried_rows, repaired_pixels=r.repaired_pixels)
-
-
-def _run_target(self, images, target, bleed=2, stream=0):
-    """pngloss_hip_optimize_batch_target: images as for run(); every image ends up as run() at its chosen strength leaves it.  Synchronous.
-    Returns (results, reports): the dicts run() returns and one TargetReport per image.  With a Target2 the call is
-    pngloss_hip_optimize_batch_target2 and returns (results, reports, ssim): one Ssim per image, filled when target.min_ssim != 0."""
-    n = len(images)
-    descs = (ImageDesc * max(n, 1))()
-    for i, (p, f, w, h) in enumerate(images):
-        descs[i] = ImageDesc(p or None, f or None, w, h)
-    res = (Result * max(n, 1))()
-    rep = (TargetReport * max(n, 1))()
-    self._n = 0
-    if isinstance(target, Target2):
-        ssim = (Ssim * max(n, 1))()
-        _check(self._lib.pngloss_hip_optimize_batch_target2(self._ctx, descs, n, C.byref(target), bleed, stream or None, res, rep, ssim), "optimize_batch_target2",
-               partial_ok=True)
-        return [_result_dict(r) for r in res[:n]], [rep[i] for i in range(n)], [ssim[i] for i in range(n)]
-    _check(self._lib.pngloss_hip_optimize_batch_target(self._ctx, descs, n, C.byref(target), bleed, stream or None, res, rep), "optimize_batch_target",
-           partial_ok=True)
-    return [_result_dict(r) for r in res[:n]], [rep[i] for i in range(n)]
-
-
-def _run_host_target(self, arrays, target, bleed=2, want_filters=True, emit=None, stream_only=False):
-    """pngloss_hip_multi_optimize_batch_host_target on a list of (H, W, 4) uint8 arrays.  emit: None, "scanlines" or "zlib".  Returns
-    (outs, filters, results, reports, emitted): emitted is None, or per image what run_host_emit / run_host_zlib return for it.  With a Target2 the
-    call is pngloss_hip_multi_optimize_batch_host_target2 and a sixth element follows: one Ssim per image, filled when target.min_ssim != 0."""
-    outs = [np.ascontiguousarray(a).copy() for a in arrays]
-    filts = [np.zeros(a.shape[0], np.uint8) if want_filters else None for a in outs]
-    n = len(outs)
-    imgs = (HostImage * max(n, 1))()
-    for i, (a, f) in enumerate(zip(outs, filts)):
-        imgs[i] = HostImage(a.ctypes.data, f.ctypes.data if f is not None else None, a.shape[1], a.shape[0])
-    lines = zs = None
-    if emit == "scanlines":
-        lines = (Scanlines * max(n, 1))()
-        ids = [np.zeros(a.shape[0], np.uint8) for a in outs]
-        rows = [np.zeros((a.shape[0], a.shape[1] * 4), np.uint8) for a in outs]
-        for i, a in enumerate(outs):
-            lines[i] = Scanlines(ids[i].ctypes.data, rows[i].ctypes.data, a.shape[1] * 4, -1)
-    elif emit == "zlib":
-        zs = (ZStream * max(n, 1))()
-        bufs = [np.zeros(self._lib.pngloss_hip_zlib_bound(a.shape[1], a.shape[0]), np.uint8) for a in outs]
-        for i in range(n):
-            zs[i] = ZStream(bufs[i].ctypes.data, bufs[i].size, 0, -1, (C.c_uint32 * 3)(0, 0, 0), 1 if stream_only else 0)
-    elif emit is not None:
-        raise ValueError("emit: None, 'scanlines' or 'zlib'")
-    res = (Result * max(n, 1))()
-    rep = (TargetReport * max(n, 1))()
-    ssim = (Ssim * max(n, 1))() if isinstance(target, Target2) else None
-    if ssim is not None:
-        _check(self._lib.pngloss_hip_multi_optimize_batch_host_target2(self._m, imgs, n, C.byref(target), bleed, res, lines, zs, rep, ssim),
-               "multi_optimize_batch_host_target2", partial_ok=True)
-    else:
-        _check(self._lib.pngloss_hip_multi_optimize_batch_host_target(self._m, imgs, n, C.byref(target), bleed, res, lines, zs, rep),
-               "multi_optimize_batch_host_target", partial_ok=True)
-    emitted = None
-    if emit == "scanlines":
-        chans = {0: 1, 4: 2, 2: 3, 6: 4}
-        emitted = [(lines[i].color_type, ids[i], rows[i][:, : outs[i].shape[1] * chans.get(lines[i].color_type, 4)].copy()) for i in range(n)]
-    elif emit == "zlib":
-        emitted = [(zs[i].color_type, bufs[i][: zs[i].size].tobytes(), tuple(zs[i].blocks)) for i in range(n)]
-    out = (outs, filts, [dict(status=r.status, bpp=r.bytes_per_pixel, unique_symbols=r.unique_symbols) for r in res[:n]], [rep[i] for i in range(n)], emitted)
-    return out + ([ssim[i] for i in range(n)],) if ssim is not None else out
-
-
-HipContext.run_target = _run_target
-HipMulti.run_host_target = _run_host_target
-
-
-# ---- a strength per image from a byte budget -----------------------------------------------------------------
-
-class SizeTarget(C.Structure):
-    """pngloss_hip_size_target: max_bytes (one budget per image: the largest allowed zlib stream) and max_strength (M, 0..255: the search never
-    goes above it).  include/pngloss_hip.h states the rule.  max_bytes: a ctypes array of c_uint64, a sequence of ints, or None."""
-    _fields_ = [("max_bytes", C.POINTER(C.c_uint64)), ("max_strength", C.c_uint32), ("reserved", C.c_uint32)]
-
-    def __init__(self, max_bytes=None, max_strength=19):
-        if max_bytes is not None and not isinstance(max_bytes, C.Array):
-            max_bytes = (C.c_uint64 * max(len(max_bytes), 1))(*max_bytes)
-        self._budgets = max_bytes                          # (keeps the array alive)
-        super().__init__(C.cast(max_bytes, C.POINTER(C.c_uint64)) if max_bytes is not None else None, max_strength, 0)
-
-
-class SizeReport(C.Structure):
-    """pngloss_hip_size_report: the chosen strength, the probes of the rule, the row-engine runs spent, whether the budget was reached, the measured
-    stream size and colour type of the result kept, and its Distortion."""
-    _fields_ = [("strength", C.c_uint32), ("probes", C.c_uint32), ("runs", C.c_uint32), ("reached", C.c_uint32), ("bytes", C.c_uint64),
-                ("color_type", C.c_int32), ("reserved", C.c_uint32), ("distortion", Distortion)]
-
-    def as_dict(self):
-        return dict(strength=self.strength, probes=self.probes, runs=self.runs, reached=self.reached, bytes=self.bytes, color_type=self.color_type,
-                    distortion=self.distortion.as_dict())
-
-
-def _size_abi(lib):
-    """the prototypes of the two size entry points (hip_lib sets them once)"""
-    lib.pngloss_hip_optimize_batch_size.argtypes = [C.c_void_p, C.POINTER(ImageDesc), C.c_size_t, C.POINTER(SizeTarget), C.c_long, C.c_void_p, C.POINTER(Result),
-                                                    C.POINTER(ZStream), C.POINTER(SizeReport)]
-    lib.pngloss_hip_optimize_batch_size.restype = C.c_int
-    lib.pngloss_hip_multi_optimize_batch_host_size.argtypes = [C.c_void_p, C.POINTER(HostImage), C.c_size_t, C.POINTER(SizeTarget), C.c_long, C.POINTER(Result),
-                                                               C.POINTER(Scanlines), C.POINTER(ZStream), C.POINTER(SizeReport)]
-    lib.pngloss_hip_multi_optimize_batch_host_size.restype = C.c_int
-    return lib
-
-
-def _run_size(self, images, max_bytes, max_strength=19, bleed=2, stream=0, want_streams=False):
-    """pngloss_hip_optimize_batch_size: images as for run(), max_bytes one budget per image; every image ends up as run() at its chosen strength
-    leaves it.  Synchronous.  Returns (results, reports, streams): the dicts run() returns, one SizeReport per image and -- with want_streams --
-    per image (color_type, zlib stream, blocks), else None."""
-    n = len(images)
-    descs = (ImageDesc * max(n, 1))()
-    for i, (p, f, w, h) in enumerate(images):
-        descs[i] = ImageDesc(p or None, f or None, w, h)
-    res = (Result * max(n, 1))()
-    rep = (SizeReport * max(n, 1))()
-    zs = bufs = None
-    if want_streams:
-        zs = (ZStream * max(n, 1))()
-        bufs = [np.zeros(self._lib.pngloss_hip_zlib_bound(w, h), np.uint8) for (_, _, w, h) in images]
-        for i in range(n):
-            zs[i] = ZStream(bufs[i].ctypes.data, bufs[i].size, 0, -1, (C.c_uint32 * 3)(0, 0, 0), 0)
-    target = SizeTarget(list(max_bytes), max_strength)
-    self._n = 0
-    _check(self._lib.pngloss_hip_optimize_batch_size(self._ctx, descs, n, C.byref(target), bleed, stream or None, res, zs, rep), "optimize_batch_size",
-           partial_ok=True)
-    streams = [(zs[i].color_type, bufs[i][: zs[i].size].tobytes(), tuple(zs[i].blocks)) for i in range(n)] if want_streams else None
-    return [_result_dict(r) for r in res[:n]], [rep[i] for i in range(n)], streams
-
-
-def _run_host_size(self, arrays, max_bytes, max_strength=19, bleed=2, want_filters=True, emit=None):
-    """pngloss_hip_multi_optimize_batch_host_size on a list of (H, W, 4) uint8 arrays.  emit: None, "scanlines", "zlib" or "both".  Returns
-    (outs, filters, results, reports, scanlines, streams): the last two None, or per image what run_host_emit / run_host_zlib return for it."""
-    outs = [np.ascontiguousarray(a).copy() for a in arrays]
-    filts = [np.zeros(a.shape[0], np.uint8) if want_filters else None for a in outs]
-    n = len(outs)
-    imgs = (HostImage * max(n, 1))()
-    for i, (a, f) in enumerate(zip(outs, filts)):
-        imgs[i] = HostImage(a.ctypes.data, f.ctypes.data if f is not None else None, a.shape[1], a.shape[0])
-    if emit not in (None, "scanlines", "zlib", "both"):
-        raise ValueError("emit: None, 'scanlines', 'zlib' or 'both'")
-    lines = zs = None
-    if emit in ("scanlines", "both"):
-        lines = (Scanlines * max(n, 1))()
-        ids = [np.zeros(a.shape[0], np.uint8) for a in outs]
-        rows = [np.zeros((a.shape[0], a.shape[1] * 4), np.uint8) for a in outs]
-        for i, a in enumerate(outs):
-            lines[i] = Scanlines(ids[i].ctypes.data, rows[i].ctypes.data, a.shape[1] * 4, -1)
-    if emit in ("zlib", "both"):
-        zs = (ZStream * max(n, 1))()
-        bufs = [np.zeros(self._lib.pngloss_hip_zlib_bound(a.shape[1], a.shape[0]), np.uint8) for a in outs]
-        for i in range(n):
-            zs[i] = ZStream(bufs[i].ctypes.data, bufs[i].size, 0, -1, (C.c_uint32 * 3)(0, 0, 0), 0)
-    res = (Result * max(n, 1))()
-    rep = (SizeReport * max(n, 1))()
-    target = SizeTarget(list(max_bytes), max_strength)
-    _check(self._lib.pngloss_hip_multi_optimize_batch_host_size(self._m, imgs, n, C.byref(target), bleed, res, lines, zs, rep),
-           "multi_optimize_batch_host_size", partial_ok=True)
-    chans = {0: 1, 4: 2, 2: 3, 6: 4}
-    scan = [(lines[i].color_type, ids[i], rows[i][:, : outs[i].shape[1] * chans.get(lines[i].color_type, 4)].copy()) for i in range(n)] if lines is not None else None
-    streams = [(zs[i].color_type, bufs[i][: zs[i].size].tobytes(), tuple(zs[i].blocks)) for i in range(n)] if zs is not None else None
-    return outs, filts, [dict(status=r.status, bpp=r.bytes_per_pixel, unique_symbols=r.unique_symbols) for r in res[:n]], [rep[i] for i in range(n)], scan, streams
-
-
-HipContext.run_size = _run_size
-HipMulti.run_host_size = _run_host_size
+    def run_host_size(self, arrays, max_bytes, max_strength=19, bleed=2, want_filters=True, emit=None):
+        """pngloss_hip_multi_optimize_batch_host_size on a list of (H, W, 4) uint8 arrays.  emit: None, "scanlines", "zlib" or "both".  Returns
+        (outs, filters, results, reports, scanlines, streams): the last two None, or per image what run_host_emit / run_host_zlib return for it."""
+        if emit not in (None, "scanlines", "zlib", "both"):
+            raise ValueError("emit: None, 'scanlines', 'zlib' or 'both'")
+        outs, filts, imgs = _host_images(arrays, want_filters)
+        n = len(outs)
+        lines, ids, rows = _scanline_buffers(outs) if emit in ("scanlines", "both") else (None, None, None)
+        zs, bufs = _zstreams(self._lib, _shapes(outs)) if emit in ("zlib", "both") else (None, None)
+        res, rep = _array(Result, n), _array(SizeReport, n)
+        target = SizeTarget(list(max_bytes), max_strength)
+        _check(self._lib.pngloss_hip_multi_optimize_batch_host_size(self._m, imgs, n, C.byref(target), bleed, res, lines, zs, rep),
+               "multi_optimize_batch_host_size", partial_ok=True)
+        return (outs, filts, [_host_result_dict(r) for r in res[:n]], list(rep[:n]),
+                _scanlines_back(lines, ids, rows) if lines is not None else None, _zstreams_back(zs, bufs) if zs is not None else None)

@@ -110,8 +110,6 @@ def test_stream_of_the_callers_option_distortion_and_the_context_afterwards():
         first = [r.as_dict() for r in _check_call(ctx, shapes, target, stream=st.cuda_stream)]
         # right after the call no single batch exists to index
         out, hist, info = P.Distortion(), np.zeros(256, np.uint32), (L.C.c_int32 * 8)()
-        lib.pngloss_hip_last_engine_info.argtypes = [L.C.c_void_p, L.C.c_size_t, L.C.c_void_p]
-        lib.pngloss_hip_last_engine_info.restype = L.C.c_int
 
         def queries():
             return (lib.pngloss_hip_last_distortion(ctx._ctx, 0, out), lib.pngloss_hip_last_histogram(ctx._ctx, 0, hist.ctypes.data_as(L.C.c_void_p)),

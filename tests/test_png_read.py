@@ -64,9 +64,6 @@ def test_device_reader_rejects_what_is_not_png():
     out = np.zeros((p["height"], p["width"], 4), np.uint8)
     src = (L.PngSource * 1)(L.PngSource(bytes(bad_rows), p["width"], p["height"], p["ctype"], p["depth"], None, 0, None, 0, out.ctypes.data))
     lib = P.hip_lib()
-    import ctypes as C
-    lib.pngloss_hip_png_decode_batch_host.argtypes = [C.c_void_p, C.POINTER(L.PngSource), C.c_size_t]      # (set here too: the test must not depend on an earlier one having called the wrapper)
-    lib.pngloss_hip_png_decode_batch_host.restype = C.c_int
     assert lib.pngloss_hip_png_decode_batch_host(ctx._ctx, src, 1) == 25
     src[0] = L.PngSource(p["scanlines"], p["width"], p["height"], 2, 4, None, 0, None, 0, out.ctypes.data)   # RGB with 4 bits: no such format
     assert lib.pngloss_hip_png_decode_batch_host(ctx._ctx, src, 1) == 4
@@ -92,8 +89,6 @@ def test_device_reader_one_damaged_file_fails_alone():
     import ctypes as C
     st = (C.c_int * len(parsed))()
     lib = P.hip_lib()
-    lib.pngloss_hip_png_decode_batch_host_status.restype = C.c_int
-    lib.pngloss_hip_png_decode_batch_host_status.argtypes = [C.c_void_p, C.POINTER(L.PngSource), C.c_size_t, C.POINTER(C.c_int)]
     rc = lib.pngloss_hip_png_decode_batch_host_status(ctx._ctx, src, len(parsed), st)
     assert rc == 25 and list(st) == [0, 25] + [0] * (len(parsed) - 2)
     for i, (o, g) in enumerate(zip(outs, good_outs)):
@@ -125,8 +120,6 @@ def test_device_reader_many_bands_and_blocks(w, h, ctype, depth):
     src = (L.PngSource * 1)(L.PngSource(scan, w, h, ctype, depth, plte, 16 if plte else 0, trns, 9 if trns else 0, got.ctypes.data))
     ctx = P.HipContext()
     lib = P.hip_lib()
-    lib.pngloss_hip_png_decode_batch_host.restype = C.c_int
-    lib.pngloss_hip_png_decode_batch_host.argtypes = [C.c_void_p, C.POINTER(L.PngSource), C.c_size_t]
     assert lib.pngloss_hip_png_decode_batch_host(ctx._ctx, src, 1) == 0
     assert np.array_equal(got, want), np.argwhere((got != want).any(axis=2))[:3].tolist()
     ctx.close()

@@ -254,8 +254,6 @@ def test_device_frames_of_interlaced_files_feed_the_optimiser():
 
 def _host_status(ctx, srcs):
     lib = P.hip_lib()
-    lib.pngloss_hip_png_decode_batch_host_status.restype = C.c_int
-    lib.pngloss_hip_png_decode_batch_host_status.argtypes = [C.c_void_p, C.POINTER(L.PngSource), C.c_size_t, C.POINTER(C.c_int)]
     arr = (L.PngSource * len(srcs))(*srcs)
     st = (C.c_int * len(srcs))()
     rc = lib.pngloss_hip_png_decode_batch_host_status(ctx._ctx, arr, len(srcs), st)
@@ -299,8 +297,6 @@ def test_device_reader_rejects_unknown_interlace_methods():
     rc, st = _host_status(ctx, [_source(p, p["scanlines"], out, 2)])
     assert rc == 4 and st == [4]
     lib = P.hip_lib()
-    lib.pngloss_hip_png_decode_batch_device_z.argtypes = [C.c_void_p, C.POINTER(L.PngZSource), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p]
-    lib.pngloss_hip_png_decode_batch_device_z.restype = C.c_int
     z = p["zstream"]
     zs = (L.PngZSource * 1)(L.PngZSource(z, len(z), p["width"], p["height"], p["ctype"], p["depth"], p["plte"], len(p["plte"]) // 3 if p["plte"] else 0,
                                          p["trns"], len(p["trns"]) if p["trns"] else 0, interlace=2))

@@ -13,8 +13,6 @@ host.inflate_host_stats.argtypes = [C.c_void_p]
 s = U.load_npz("suite_png.npz")
 ctx = P.HipContext()
 lib = P.hip_lib()
-lib.pngloss_hip_png_decode_batch_device_z.argtypes = [C.c_void_p, C.POINTER(L.PngZSource), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p]
-lib.pngloss_hip_png_decode_batch_device.argtypes = [C.c_void_p, C.POINTER(L.PngSource), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p]
 print("file                  pixels   scanline bytes  compressed   literals    matches (bytes)      device inflate        zlib, one host thread")
 tot_b = 0; tot_t = 0.0
 for k in sorted(s.files):

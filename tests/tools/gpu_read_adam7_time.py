@@ -66,13 +66,6 @@ def captured(fn):
 
 def main():
     lib = P.hip_lib()
-    lib.pngloss_hip_png_decode_batch_device.argtypes = [C.c_void_p, C.POINTER(L.PngSource), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p]
-    lib.pngloss_hip_png_decode_batch_device.restype = C.c_int
-    lib.pngloss_hip_png_decode_batch_device_z.argtypes = [C.c_void_p, C.POINTER(L.PngZSource), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p]
-    lib.pngloss_hip_png_decode_batch_device_z.restype = C.c_int
-    lib.pngloss_hip_pinned_alloc.argtypes = [C.c_size_t]
-    lib.pngloss_hip_pinned_alloc.restype = C.c_void_p
-    lib.pngloss_hip_pinned_free.argtypes = [C.c_void_p]
     ctx = P.HipContext()
     for label, n, w, h, c, z_reps in [("1 x 4096x4096 RGBA8", 1, 4096, 4096, 4, 1), ("32 x 1280x720 RGB8", 32, 1280, 720, 3, reps)]:
         frames = [P.synth_rgba(w, h, 0, i)[:, :, :c].copy() for i in range(n)]

@@ -1,14 +1,12 @@
 """Timing aid: pngloss_hip_png_decode_batch_host on one large random scanline stream per pixel format (whole call: upload + unfilter + expand +
 download, from pageable memory), and the kernel alone when run under rocprofv3.  usage: read_formats.py [W H]"""
-import ctypes as C, os, sys, time
+import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pngloss_amd as P
 from pngloss_amd import lib as L
 w, h = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (4096, 4096)
 lib = P.hip_lib()
-lib.pngloss_hip_png_decode_batch_host.restype = C.c_int
-lib.pngloss_hip_png_decode_batch_host.argtypes = [C.c_void_p, C.POINTER(L.PngSource), C.c_size_t]
 ctx = P.HipContext()
 rng = np.random.default_rng(1)
 for ctype, depth in [(6, 8), (2, 8), (0, 8), (4, 8), (6, 16), (2, 16), (3, 8), (0, 1)]:
