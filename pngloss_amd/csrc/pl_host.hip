@@ -6,6 +6,10 @@
  * done here and there is no CPU fallback: without a usable HIP device every entry point fails loudly.  What it
  * DECIDES is in plain headers that the CPU suite pins: pl_plan.h (the batch, the segment engine's workspace table),
  * pl_seg_pace.h (the pace of the segment engine's launch thread), pl_layout.h, pl_deal.h, pl_search.h, pl_result.h.
+ *
+ * The context (pngloss_hip_ctx) holds what outlives a call: the caller's options (assigned by pngloss_hip_set_option and nowhere else), the buffers that
+ * grow on demand (GrowBuf), streams and events, and the last batch for pngloss_hip_last_*.  What ONE call asks of a batch -- strength, stream, emit targets,
+ * a synchronous caller, what to measure behind it -- is an argument (BatchCall) of enqueue: no function tells another what to run by writing into the context.
  */
 #include "../../include/pngloss_hip.h"
 #include "pl_device.h"
@@ -74,14 +78,35 @@ static PlHooks from_env()
     return h;
 }
 
+namespace {
+/* A buffer of the context's, regrown on demand and never shrunk: device memory, or (pinned) host memory. */
+struct GrowBuf {
+    char *p = nullptr;
+    size_t bytes = 0;
+    const bool pinned;
+    explicit GrowBuf(bool pinned_ = false) : pinned(pinned_) {}
+    /* room for `need` bytes (pl_grow_bytes: the slack of each buffer is need / divisor); freed before the larger one is allocated, and null / 0 if that fails */
+    int grow(size_t need, size_t divisor)
+    {
+        const size_t want = pl_grow_bytes(need, bytes, divisor);
+        if (!want) return PNGLOSS_SUCCESS;
+        if (p) PL_CHECK(pinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr; bytes = 0;
+        PL_CHECK(pinned ? hipHostMalloc(reinterpret_cast<void **>(&p), want, hipHostMallocDefault) : hipMalloc(reinterpret_cast<void **>(&p), want));
+        bytes = want;
+        return PNGLOSS_SUCCESS;
+    }
+    void release() { if (p) (void)(pinned ? hipHostFree(p) : hipFree(p)); p = nullptr; bytes = 0; }
+};
+}
+
 struct pngloss_hip_ctx {
     int device = 0;
     PlHooks hooks;                   /* (from the environment, at creation) */
     int pin_slot = 0;                /* which pair of CPUs of the affinity set this context's launch thread is pinned into: max(device, contexts created before it in the process) */
     int opt_launch_groups = 0;       /* pngloss_hip_set_option("launch_groups", "2" | "3" | "auto"): see run_seg_engine */
     /* one device arena, regrown on demand, carved per batch */
-    char *d_ws = nullptr;
-    size_t ws_bytes = 0;
+    GrowBuf d_ws;
     std::vector<PlJob> h_jobs;
     size_t n_last = 0;
     hipStream_t last_stream = nullptr;
@@ -90,18 +115,14 @@ struct pngloss_hip_ctx {
     bool pending = false;
     /* host-pointer batches (pngloss_hip_optimize_batch_host*): a persistent device arena and a persistent pinned staging
      * buffer of the same layout, both regrown on demand -- no hipMalloc/hipFree and no pageable copies per call */
-    char *d_arena = nullptr;
-    size_t arena_bytes = 0;
-    char *h_pinned = nullptr;
-    size_t pinned_bytes = 0;
+    GrowBuf d_arena;
+    GrowBuf h_pinned{ true };
     PlEnginePin opt_engine = PlEnginePin::Auto;   /* pngloss_hip_set_option("engine", ...): Auto = the cost model (or, for tests, $PNGLOSS_HIP_ENGINE) */
-    char *d_frames = nullptr;        /* device frames of pngloss_hip_png_decode_batch_device: decoded RGBA8 that stays on the device for the optimiser */
-    size_t frames_bytes = 0;
+    GrowBuf d_frames;                /* device frames of pngloss_hip_png_decode_batch_device: decoded RGBA8 that stays on the device for the optimiser */
     hipStream_t copy_stream = nullptr;
     double upload_ms = -1.0, download_ms = -1.0;
-    /* -v progress display of the single-image seam: a host-mapped word the engine writes the finished row count to */
+    /* -v progress display of the single-image seam: a host-mapped word the engine writes the finished row count to (BatchCall::want_progress) */
     uint32_t *h_progress = nullptr;
-    bool want_progress = false;
     /* segment-parallel engine: two host-mapped words (images finished, attempt being started) the control kernel writes and the
      * launch loop reads, and what the last batch did */
     bool split_last = false;         /* the last host window ran in chunks: images behind n_last are the peers' */
@@ -115,10 +136,6 @@ struct pngloss_hip_ctx {
     hipEvent_t ev_seg_gdone[SEG_MAX_GROUPS] = {};
     int seg_groups = 1;
     bool seg_async_wait = false;     /* the last batch on the segment engine put a wait for the engine on the caller's stream (the asynchronous entry's non-blocking variant) */
-    bool three_groups_ok = false;    /* ... and it is the device-resident synchronous entry point itself: a batch may run as three launch groups (the host-pointer entry points, which the
-                                        multi-device wrapper calls from a thread per context, stay at two: several contexts of one process share its hardware queues) */
-    bool sync_call = false;          /* the batch under way was started by a SYNCHRONOUS entry point (pngloss_hip_optimize_batch): the caller waits on the host anyway, so the
-                                        caller's stream gets no device-side wait for the engine's finished word (run_seg_engine) */
     hipEvent_t ev_prep = nullptr;    /* caller's stream: everything the engine reads is in place */
     hipEvent_t ev_seg_done = nullptr;/* engine's stream: behind the last attempt the launch thread enqueued */
     std::thread seg_worker;
@@ -132,8 +149,7 @@ struct pngloss_hip_ctx {
 
     /* option "distortion": the keep arena (pl_layout.h: job table, records, the originals pl_keep copies), regrown on demand like the others */
     bool opt_distortion = false;     /* pngloss_hip_set_option("distortion", "on" | "off") */
-    char *d_keep = nullptr;
-    size_t keep_bytes = 0;
+    GrowBuf d_keep;
     std::vector<PlDistortJob> h_dj;  /* (stays alive until the asynchronous copy that reads it is done: the next enqueue) */
     const PlDistortRecord *d_records = nullptr;      /* the batch in flight is measured: its records, copied back by finish */
     std::vector<pngloss_hip_distortion> distortion;  /* per image of the last finished batch; empty when it ran with the option off */
@@ -144,18 +160,16 @@ struct pngloss_hip_ctx {
     /* option "measure": what the two measuring kernels count, behind a batch and in the probes of the target searches: every pixel, or the visible ones
      * (pl_distort_core.h, pl_ssim_core.h).  The pipeline never sees it. */
     bool opt_visible = false;        /* pngloss_hip_set_option("measure", "all" | "visible") */
-    char *d_ssim = nullptr;
-    size_t ssim_bytes = 0;
+    GrowBuf d_ssim;
     std::vector<PlSsimJob> h_ssj;    /* (stay alive until the asynchronous copies that read them are done: the next enqueue) */
     std::vector<PlSsimRecord> h_ssr;
     const PlSsimRecord *d_ssim_records = nullptr;    /* the batch in flight is measured: its records, copied back by finish */
     std::vector<pngloss_hip_ssim> ssim;              /* per image of the last finished batch; empty when it ran with the option off */
 
     /* pngloss_hip_optimize_batch_target: the search arena (pl_target.h: tables, originals, best results so far), regrown on demand like the others */
-    char *d_target = nullptr;
-    size_t target_bytes = 0;
+    GrowBuf d_target;
 
-    std::vector<uint8_t> engine;    /* per image of the last batch: the row engine its plan gave it (PLR_ENGINE_*, pl_result.h) */
+    std::vector<uint8_t> engine;   /* per image of the last batch: the row engine its plan gave it (PLR_ENGINE_*, pl_result.h) */
     long seg_attempts = 0;
 };
 
@@ -181,20 +195,7 @@ float recip_up_host(long d)
     return r;
 }
 
-/* The context's buffers are regrown on demand and never shrink: `p` of `have` bytes comes out with room for `need` (pl_grow_bytes: the slack of
- * each buffer is need / divisor); freed before the larger one is allocated, and null / 0 if that fails.  pinned: host memory, else the device's. */
-int grow(char *&p, size_t &have, size_t need, size_t divisor, bool pinned = false)
-{
-    const size_t want = pl_grow_bytes(need, have, divisor);
-    if (!want) return PNGLOSS_SUCCESS;
-    if (p) PL_CHECK(pinned ? hipHostFree(p) : hipFree(p));
-    p = nullptr;
-    have = 0;
-    PL_CHECK(pinned ? hipHostMalloc(reinterpret_cast<void **>(&p), want, hipHostMallocDefault) : hipMalloc(reinterpret_cast<void **>(&p), want));
-    have = want;
-    return PNGLOSS_SUCCESS;
-}
-int ensure_ws(pngloss_hip_ctx *ctx, size_t bytes) { return grow(ctx->d_ws, ctx->ws_bytes, bytes, 4); }
+int ensure_ws(pngloss_hip_ctx *ctx, size_t bytes) { return ctx->d_ws.grow(bytes, 4); }
 
 /* what the device deflate (pl_deflate.h) answers, as a code of the ABI */
 int deflate_rc(hipError_t e)
@@ -202,16 +203,36 @@ int deflate_rc(hipError_t e)
     return e == hipSuccess ? PNGLOSS_SUCCESS : e == hipErrorInvalidValue ? PNGLOSS_INVALID_ARGUMENT : e == hipErrorOutOfMemory ? PNGLOSS_OUT_OF_MEMORY_ERROR : PNGLOSS_HIP_ERROR;
 }
 
-/* The context has no "last batch" to index (pngloss_hip_last_*): what enqueue does before every batch.  (The two record pointers are read by finish
- * alone, for the batch an enqueue has just set them for, and a peer never has split_last set: clearing them is for the searches, and is not seen.) */
+/* The context has no "last batch" to index (pngloss_hip_last_*): enqueue begins every batch with it (only a split host window sets split_last again: batch_host) */
 void forget_last_batch(pngloss_hip_ctx *c)
 {
     c->n_last = 0; c->h_jobs.clear(); c->distortion.clear(); c->d_records = nullptr; c->ssim.clear(); c->d_ssim_records = nullptr; c->split_last = false;
 }
-/* A search runs many batches of its own on the context: whatever happens, the caller's options back, and no "last batch" to index */
+/* A search runs many batches of its own on the context: whatever happens, no "last batch" to index behind it -- for the host forms (peers), none
+ * on the peers the host windows ran their other chunks on either */
 struct SearchGuard {
-    pngloss_hip_ctx *c; bool opt, opt_ssim;
-    ~SearchGuard() { c->opt_distortion = opt; c->opt_ssim = opt_ssim; forget_last_batch(c); }
+    pngloss_hip_ctx *c; bool peers;
+    ~SearchGuard() { forget_last_batch(c); if (peers) for (pngloss_hip_ctx *p : c->peers) if (p) forget_last_batch(p); }
+};
+
+struct EmitTarget { void *d_ids; void *d_rows; uint32_t pitch; };
+
+/* What to measure behind a batch: the distortion records, the SSIM records, and whether the two count the visible pixels or all of them
+ * (pl_distort_core.h, pl_ssim_core.h).  The pipeline never sees it. */
+struct Measure { bool distortion = false, ssim = false, visible = false; };
+/* ... as the caller's options ask for it: what the plain entry points hand on (no context: nothing; the call fails where it always did) */
+Measure measure_of_options(const pngloss_hip_ctx *c) { return c ? Measure{ c->opt_distortion, c->opt_ssim, c->opt_visible } : Measure{}; }
+
+/* What one call asks of a batch (enqueue): written down by its entry point, read by enqueue and run_seg_engine, kept nowhere */
+struct BatchCall {
+    unsigned strength; long bleed; hipStream_t stream;
+    Measure measure;
+    bool sync_call = false;               /* started by a SYNCHRONOUS entry point: the caller waits on the host anyway, so its stream gets no device-side wait for the engine's finished word (run_seg_engine) */
+    bool three_groups_ok = false;         /* ... and by the device-resident one itself: the batch may run as three launch groups (the host-pointer entry points, which the multi-device wrapper calls
+                                             from a thread per context, stay at two: several contexts of one process share its hardware queues) */
+    bool want_progress = false;           /* the engine writes image 0's finished row count to ctx->h_progress (the -v display of the single-image seam) */
+    const uint32_t *forced_bpp = nullptr; /* per image, or nullptr */
+    const EmitTarget *emits = nullptr;    /* per image: where its scanlines go, or nullptr */
 };
 
 /* The images `who` of a batch of host images as a batch of their own: images / lines / zs gathered into contiguous vectors (an array the caller
@@ -249,16 +270,16 @@ struct HostSubset {
  * compared with the original at keep[i] -- or, keep == nullptr, with the place the layout gives it in the arena, for pl_keep to fill. */
 int upload_distort_jobs(pngloss_hip_ctx *ctx, const PlKeepLayout &lay, size_t n, const void *const *img, const void *const *keep, const uint64_t *pixels, hipStream_t stream)
 {
-    PlDistortRecord *const d_rec = reinterpret_cast<PlDistortRecord *>(ctx->d_keep + lay.records);
+    PlDistortRecord *const d_rec = reinterpret_cast<PlDistortRecord *>(ctx->d_keep.p + lay.records);
     ctx->h_dj.assign(n, PlDistortJob{});
     for (size_t i = 0; i < n; i++) {
         PlDistortJob &d = ctx->h_dj[i];
-        d.keep = keep ? static_cast<uint32_t *>(const_cast<void *>(keep[i])) : reinterpret_cast<uint32_t *>(ctx->d_keep + lay.image[i]);
+        d.keep = keep ? static_cast<uint32_t *>(const_cast<void *>(keep[i])) : reinterpret_cast<uint32_t *>(ctx->d_keep.p + lay.image[i]);
         d.img = static_cast<const uint32_t *>(img[i]);
         d.pixels = pixels[i];
         d.record = d_rec + i;
     }
-    PL_CHECK(hipMemcpyAsync(ctx->d_keep + lay.jobs, ctx->h_dj.data(), sizeof(PlDistortJob) * n, hipMemcpyHostToDevice, stream));
+    PL_CHECK(hipMemcpyAsync(ctx->d_keep.p + lay.jobs, ctx->h_dj.data(), sizeof(PlDistortJob) * n, hipMemcpyHostToDevice, stream));
     PL_CHECK(hipMemsetAsync(d_rec, 0, sizeof(PlDistortRecord) * n, stream));
     return PNGLOSS_SUCCESS;
 }
@@ -282,17 +303,15 @@ int upload_ssim_jobs(pngloss_hip_ctx *ctx, size_t n, const void *const *a, const
                      hipStream_t stream, PlSsimLayout &lay, uint64_t &max_tiles, bool visible)
 {
     lay = pl_ssim_layout(n, sizeof(PlSsimJob), sizeof(PlSsimRecord));
-    const int rc = grow(ctx->d_ssim, ctx->ssim_bytes, lay.total, 8);
+    const int rc = ctx->d_ssim.grow(lay.total, 8);
     if (rc) return rc;
     ctx->h_ssj.assign(n, PlSsimJob{});
     ctx->h_ssr.assign(n, PlSsimRecord{});
-    max_tiles = fill_ssim_jobs(ctx->h_ssj.data(), ctx->h_ssr.data(), reinterpret_cast<PlSsimRecord *>(ctx->d_ssim + lay.records), n, a, b, width, height, visible);
-    PL_CHECK(hipMemcpyAsync(ctx->d_ssim + lay.jobs, ctx->h_ssj.data(), sizeof(PlSsimJob) * n, hipMemcpyHostToDevice, stream));
-    PL_CHECK(hipMemcpyAsync(ctx->d_ssim + lay.records, ctx->h_ssr.data(), sizeof(PlSsimRecord) * n, hipMemcpyHostToDevice, stream));
+    max_tiles = fill_ssim_jobs(ctx->h_ssj.data(), ctx->h_ssr.data(), reinterpret_cast<PlSsimRecord *>(ctx->d_ssim.p + lay.records), n, a, b, width, height, visible);
+    PL_CHECK(hipMemcpyAsync(ctx->d_ssim.p + lay.jobs, ctx->h_ssj.data(), sizeof(PlSsimJob) * n, hipMemcpyHostToDevice, stream));
+    PL_CHECK(hipMemcpyAsync(ctx->d_ssim.p + lay.records, ctx->h_ssr.data(), sizeof(PlSsimRecord) * n, hipMemcpyHostToDevice, stream));
     return PNGLOSS_SUCCESS;
 }
-
-struct EmitTarget { void *d_ids; void *d_rows; uint32_t pitch; };
 
 /* The segment-parallel engine on the batch in ctx->h_jobs.  All control flow of the algorithm is on the device; the host only keeps
  * a stream fed with row attempts (five kernels each, pl_seg.hip) until every image has reported that it is finished -- how many that
@@ -402,9 +421,10 @@ void seg_worker_main(pngloss_hip_ctx *ctx, SegGroups gs, long max_attempts)
     ctx->seg_rc.store(rc, std::memory_order_release);
 }
 
-int run_seg_engine(pngloss_hip_ctx *ctx, const PlJob *d_jobs, const PlPlan &plan, const PlBatchLayout &lay, hipStream_t stream,
+int run_seg_engine(pngloss_hip_ctx *ctx, const PlJob *d_jobs, const PlPlan &plan, const PlBatchLayout &lay, const BatchCall &call,
                    const uint32_t *d_sel, const PlEngineParams &prm)
 {
+    const hipStream_t stream = call.stream;
     const std::vector<uint32_t> &list = plan.seg_list;
     const size_t n = list.size();                              /* the images of the batch this engine takes */
     const int ngroups = plan.ngroups;                          /* (launch groups: pl_plan_batch) */
@@ -445,7 +465,7 @@ int run_seg_engine(pngloss_hip_ctx *ctx, const PlJob *d_jobs, const PlPlan &plan
     ctx->h_seg_params = plan.params;
     for (size_t i = 0; i < n; i++) {
         const PlJob &pj = ctx->h_jobs[list[i]];
-        char *base = ctx->d_ws + lay.seg_image[i];
+        char *base = ctx->d_ws.p + lay.seg_image[i];
         SegJob &s = ctx->h_sj[i];
         s.job_index = list[i];
         s.img = pj.img; s.row_filters = pj.row_filters; s.row_ids = pj.row_ids; s.W = pj.width; s.H = pj.height; s.bpp = 0;
@@ -455,9 +475,9 @@ int run_seg_engine(pngloss_hip_ctx *ctx, const PlJob *d_jobs, const PlPlan &plan
         s.done_counter = d_word + pl_seg_done_word(g); s.attempt_word = i == gfirst[g] ? d_word + pl_seg_attempt_word(g) : nullptr; s.break_word = d_word + pl_seg_break_word(g);
         pl_seg_bind(s, lay.seg[i], pj.width, [&](const PlSegArray &a) { return base + a.off; });
     }
-    SegJob *d_sj = reinterpret_cast<SegJob *>(ctx->d_ws + lay.seg_jobs);
+    SegJob *d_sj = reinterpret_cast<SegJob *>(ctx->d_ws.p + lay.seg_jobs);
     for (size_t i = 0; i < n; i++) ctx->h_sj[i].self = d_sj + i;
-    SegParams *d_params = reinterpret_cast<SegParams *>(ctx->d_ws + lay.seg_params);
+    SegParams *d_params = reinterpret_cast<SegParams *>(ctx->d_ws.p + lay.seg_params);
     PL_CHECK(hipMemcpyAsync(d_sj, ctx->h_sj.data(), sizeof(SegJob) * n, hipMemcpyHostToDevice, stream));
     PL_CHECK(hipMemcpyAsync(d_params, &ctx->h_seg_params, sizeof(SegParams), hipMemcpyHostToDevice, stream));
     SegGroups gs{};
@@ -475,7 +495,7 @@ int run_seg_engine(pngloss_hip_ctx *ctx, const PlJob *d_jobs, const PlPlan &plan
      *  the engine runs -- : without it the headline frame is 1.4 % faster, the seeded 8192 x 8192 points up to 7 %.  The synchronous entry point has no use for it.) */
     int prio = 0;
     const bool prio_known = stream && hipStreamGetPriority(stream, &prio) == hipSuccess;
-    bool waiting = pl_seg_wait_on_device(ctx->stream_wait_ok != 0, ctx->seg_prio_distinct, ctx->sync_call, g_third_engine_stream.load(std::memory_order_relaxed), !stream, prio_known, prio, ctx->seg_prio);
+    bool waiting = pl_seg_wait_on_device(ctx->stream_wait_ok != 0, ctx->seg_prio_distinct, call.sync_call, g_third_engine_stream.load(std::memory_order_relaxed), !stream, prio_known, prio, ctx->seg_prio);
     if (waiting) {
         /* the caller's stream goes on behind the engine: when every image has counted itself finished */
         for (int g = 0; g < ngroups && waiting; g++) {
@@ -555,10 +575,11 @@ EngineCalib engine_calib(int device, bool debug)
     return c;
 }
 
-int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n, const uint32_t *forced_bpp,
-            unsigned strength, long bleed, hipStream_t stream, const EmitTarget *emits = nullptr)
+int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n, const BatchCall &call)
 {
     if (!ctx) return PNGLOSS_INVALID_ARGUMENT;
+    const unsigned strength = call.strength; const long bleed = call.bleed;
+    const hipStream_t stream = call.stream;
     if (strength > 255 || bleed < 1 || bleed > 32767) {
         std::fprintf(stderr, "pngloss_hip: strength must be 0..255 and bleed 1..32767 (got %u, %ld)\n", strength, bleed);
         return PNGLOSS_INVALID_ARGUMENT;
@@ -569,14 +590,8 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
     }
     PL_CHECK(hipSetDevice(ctx->device));
     if (ctx->seg_worker.joinable()) ctx->seg_worker.join();          /* (a batch that failed half-way) */
-    ctx->h_jobs.clear();
-    ctx->n_last = 0;
-    ctx->split_last = false;                                         /* (only a split host window sets it again: batch_host) */
-    ctx->distortion.clear();
-    ctx->d_records = nullptr;
-    ctx->ssim.clear();
-    ctx->d_ssim_records = nullptr;
-    const bool distort = ctx->opt_distortion, ssim = ctx->opt_ssim, visible = ctx->opt_visible;
+    forget_last_batch(ctx);
+    const bool distort = call.measure.distortion, ssim = call.measure.ssim, visible = call.measure.visible;
     const bool keep_originals = distort || ssim;     /* one arena, one pl_keep launch, whichever of the two options wants the originals */
     const PlHooks &hk = ctx->hooks;
     PlPlanInput in;
@@ -593,7 +608,7 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
          * comparable.  A batch whose counters would not fit beside its images runs strength 0 the long way (the segment / workgroup engines) instead of failing: same bytes. */
         size_t rs = 0, free_b = 0, total_b = 0;
         for (size_t i = 0; i < n; i++) rs += pl_rowstat_bytes(images[i].height);
-        const size_t have = ctx->ws_bytes;                       /* (what the context's arena already holds counts as available) */
+        const size_t have = ctx->d_ws.bytes;                      /* (what the context's arena already holds counts as available) */
         if (rs > have && hipMemGetInfo(&free_b, &total_b) == hipSuccess && rs - have > free_b / 2) {
             if (hk.debug) std::fprintf(stderr, "pngloss_hip: strength 0: %zu MB of row counters against %zu MB free: using the other row engines for this batch\n", rs >> 20, free_b >> 20);
             in.rows_fit = false;
@@ -605,7 +620,7 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
         in.height.push_back(images[i].height);
     }
     { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) == hipSuccess && cus > 0) in.cus = (double)cus; }
-    in.sync_call = ctx->sync_call; in.three_groups_ok = ctx->three_groups_ok; in.opt_launch_groups = ctx->opt_launch_groups;
+    in.sync_call = call.sync_call; in.three_groups_ok = call.three_groups_ok; in.opt_launch_groups = ctx->opt_launch_groups;
     in.stream_wait_used = g_stream_wait_used.load(std::memory_order_relaxed);
     PlPlan plan = pl_plan_batch(in);
     /* OPT-IN (PNGLOSS_HIP_CALIB=1) since it was measured inside bench.py: the probe is 2 - 6 ms of GPU work, and what it finds depends on what the process did before it
@@ -629,19 +644,19 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
     PlKeepLayout keep;
     if (keep_originals) {
         keep = pl_keep_layout(in.width, in.height, true, sizeof(PlDistortJob), sizeof(PlDistortRecord));
-        rc = grow(ctx->d_keep, ctx->keep_bytes, keep.total, 8);
+        rc = ctx->d_keep.grow(keep.total, 8);
         if (rc) return rc;
     }
     for (size_t i = 0; i < n; i++) {
         const WsLayout &l = lay.ws[i];
-        char *b = ctx->d_ws + lay.image[i];
+        char *b = ctx->d_ws.p + lay.image[i];
         PlJob j{};
         j.rowstat = use_rows ? reinterpret_cast<uint32_t *>(b + l.rowstat) : nullptr;
         j.img = static_cast<uint32_t *>(images[i].d_rgba);
         j.row_filters = static_cast<uint8_t *>(images[i].d_row_filters);
         j.width = images[i].width;
         j.height = (images[i].width == 0) ? 0 : images[i].height;
-        j.forced_bpp = forced_bpp ? forced_bpp[i] : 0;
+        j.forced_bpp = call.forced_bpp ? call.forced_bpp[i] : 0;
         j.flags = reinterpret_cast<uint32_t *>(b + l.flags);
         j.orig_hist = reinterpret_cast<uint32_t *>(b + l.orig_hist);
         j.orig_rank = reinterpret_cast<uint32_t *>(b + l.orig_rank);
@@ -653,21 +668,21 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
         j.result = reinterpret_cast<int32_t *>(b + l.result);
         j.row_ids = reinterpret_cast<uint8_t *>(b + l.row_ids);
         j.out_flags = reinterpret_cast<uint32_t *>(b + l.out_flags);
-        if (emits && emits[i].d_rows) {
-            j.emit_ids = static_cast<uint8_t *>(emits[i].d_ids);
-            j.emit_rows = static_cast<uint8_t *>(emits[i].d_rows);
-            j.emit_pitch = emits[i].pitch;
+        if (call.emits && call.emits[i].d_rows) {
+            j.emit_ids = static_cast<uint8_t *>(call.emits[i].d_ids);
+            j.emit_rows = static_cast<uint8_t *>(call.emits[i].d_rows);
+            j.emit_pitch = call.emits[i].pitch;
             j.emit_adaptive_all = images[i].d_row_filters ? 0u : 1u;
         }
         j.progress = nullptr;
-        if (ctx->want_progress && i == 0 && ctx->h_progress) {
+        if (call.want_progress && i == 0 && ctx->h_progress) {
             void *dp = nullptr;
             if (hipHostGetDevicePointer(&dp, ctx->h_progress, 0) == hipSuccess) j.progress = static_cast<uint32_t *>(dp);
         }
         ctx->h_jobs.push_back(j);
     }
     if (!n) return PNGLOSS_SUCCESS;
-    PlJob *d_jobs = reinterpret_cast<PlJob *>(ctx->d_ws);
+    PlJob *d_jobs = reinterpret_cast<PlJob *>(ctx->d_ws.p);
     PL_CHECK(hipMemcpyAsync(d_jobs, ctx->h_jobs.data(), sizeof(PlJob) * n, hipMemcpyHostToDevice, stream));
 
     PlEngineParams prm{};
@@ -678,7 +693,7 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
     prm.force_careful = hk.force_careful;   /* test hook, see pl_device.h */
     prm.engine_mode = plan.engine_mode;
 
-    const PlDistortJob *const d_dj = keep_originals ? reinterpret_cast<const PlDistortJob *>(ctx->d_keep + keep.jobs) : nullptr;
+    const PlDistortJob *const d_dj = keep_originals ? reinterpret_cast<const PlDistortJob *>(ctx->d_keep.p + keep.jobs) : nullptr;
     uint64_t max_pixels = 0, max_tiles = 0;
     PlSsimLayout ssim_lay;
     if (keep_originals) {
@@ -693,7 +708,7 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
         if (rc) return rc;
         if (ssim) {
             std::vector<const void *> orig(n);
-            for (size_t i = 0; i < n; i++) orig[i] = ctx->d_keep + keep.image[i];
+            for (size_t i = 0; i < n; i++) orig[i] = ctx->d_keep.p + keep.image[i];
             rc = upload_ssim_jobs(ctx, n, orig.data(), img.data(), in.width.data(), in.height.data(), stream, ssim_lay, max_tiles, visible);
             if (rc) return rc;
         }
@@ -709,11 +724,11 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
     const uint32_t *d_sel = nullptr;
     if (use_seg && !wg_list.empty()) {
         ctx->h_sel = wg_list;
-        PL_CHECK(hipMemcpyAsync(ctx->d_ws + lay.sel, ctx->h_sel.data(), sizeof(uint32_t) * wg_list.size(), hipMemcpyHostToDevice, stream));
-        d_sel = reinterpret_cast<const uint32_t *>(ctx->d_ws + lay.sel);
+        PL_CHECK(hipMemcpyAsync(ctx->d_ws.p + lay.sel, ctx->h_sel.data(), sizeof(uint32_t) * wg_list.size(), hipMemcpyHostToDevice, stream));
+        d_sel = reinterpret_cast<const uint32_t *>(ctx->d_ws.p + lay.sel);
     }
     if (use_seg) {
-        rc = run_seg_engine(ctx, d_jobs, plan, lay, stream, d_sel, prm);
+        rc = run_seg_engine(ctx, d_jobs, plan, lay, call, d_sel, prm);
         if (rc) return rc;
     } else if (use_rows) PL_CHECK(pl_launch_rows(d_jobs, ctx->h_jobs.data(), n, stream));
     else PL_CHECK(pl_launch_engine(d_jobs, nullptr, n, prm, stream));
@@ -722,7 +737,7 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
         /* (behind this point the segment engine's launch thread may be running: it is joined before an error is returned) */
         hipError_t e = pl_launch_finish(d_jobs, ctx->h_jobs.data(), n, stream);
         if (e == hipSuccess && distort) e = pl_launch_distort(d_dj, n, max_pixels, stream, visible);      /* behind pl_unpack: the final RGBA8 against the kept original */
-        if (e == hipSuccess && ssim) e = pl_launch_ssim(reinterpret_cast<const PlSsimJob *>(ctx->d_ssim + ssim_lay.jobs), n, max_tiles, stream, visible);
+        if (e == hipSuccess && ssim) e = pl_launch_ssim(reinterpret_cast<const PlSsimJob *>(ctx->d_ssim.p + ssim_lay.jobs), n, max_tiles, stream, visible);
         if (e == hipSuccess) e = pl_launch_emit(d_jobs, ctx->h_jobs.data(), n, stream);
         if (e == hipSuccess) e = hipEventRecord(ctx->ev[3], stream);
         if (e != hipSuccess) {
@@ -734,8 +749,8 @@ int enqueue(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n
     }
     ctx->n_last = n;
     ctx->last_stream = stream;
-    if (distort) ctx->d_records = reinterpret_cast<const PlDistortRecord *>(ctx->d_keep + keep.records);
-    if (ssim) ctx->d_ssim_records = reinterpret_cast<const PlSsimRecord *>(ctx->d_ssim + ssim_lay.records);
+    if (distort) ctx->d_records = reinterpret_cast<const PlDistortRecord *>(ctx->d_keep.p + keep.records);
+    if (ssim) ctx->d_ssim_records = reinterpret_cast<const PlSsimRecord *>(ctx->d_ssim.p + ssim_lay.records);
     ctx->pending = true;
     return PNGLOSS_SUCCESS;
 }
@@ -902,11 +917,11 @@ int run_host_image(unsigned char **rows, uint32_t width, uint32_t height, uint32
             hipHostMalloc(reinterpret_cast<void **>(&ctx->h_progress), sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
             ctx->h_progress = nullptr;                     /* no display then; not an error */
         if (ctx->h_progress) *ctx->h_progress = 0;
-        ctx->want_progress = verbose && ctx->h_progress;
-        ctx->sync_call = !ctx->want_progress;            /* (the progress display polls while the engine runs: it needs the call back at once; else the host waits anyway) */
-        rc = enqueue(ctx, &desc, 1, forced_bpp ? &forced_bpp : nullptr, strength, bleed, nullptr);
-        ctx->sync_call = false;
-        ctx->want_progress = false;
+        BatchCall call{ strength, bleed, nullptr, measure_of_options(ctx) };
+        call.want_progress = verbose && ctx->h_progress;
+        call.sync_call = !call.want_progress;            /* (the progress display polls while the engine runs: it needs the call back at once; else the host waits anyway) */
+        call.forced_bpp = forced_bpp ? &forced_bpp : nullptr;
+        rc = enqueue(ctx, &desc, 1, call);
         if (rc) break;
         if (verbose && ctx->h_progress) {
             /* the progress display of pngloss_image.c:214-237: spinner at 10 Hz and the share of finished rows, on stderr */
@@ -975,7 +990,7 @@ struct HostWindow {
 void window_stage(const HostWindow &w)
 {
     for_each_image_on_threads(w.n, [&](size_t i) {
-        if (w.lay.im[i].px) std::memcpy(w.ctx->h_pinned + w.lay.im[i].img, w.images[i].rgba, w.lay.im[i].px * 4);
+        if (w.lay.im[i].px) std::memcpy(w.ctx->h_pinned.p + w.lay.im[i].img, w.images[i].rgba, w.lay.im[i].px * 4);
     });
 }
 
@@ -983,7 +998,7 @@ void window_stage(const HostWindow &w)
 int window_upload(HostWindow &w, std::vector<pngloss_hip_image_desc> &descs)
 {
     pngloss_hip_ctx *ctx = w.ctx;
-    char *const arena = ctx->d_arena;
+    char *const arena = ctx->d_arena.p;
     int rc = PNGLOSS_SUCCESS;
     for (size_t i = 0; i < w.n; i++) {
         const PlWindowImage &m = w.lay.im[i];
@@ -991,7 +1006,7 @@ int window_upload(HostWindow &w, std::vector<pngloss_hip_image_desc> &descs)
         w.emits[i] = EmitTarget{ m.pitch ? arena + m.ids : nullptr, m.pitch ? arena + m.rows : nullptr, m.pitch };
         /* asynchronous DMA from pinned memory, one per image (the areas between images are filled by the kernels) */
         if (m.px && rc == PNGLOSS_SUCCESS &&
-            hipMemcpyAsync(arena + m.img, ctx->h_pinned + m.img, m.px * 4, hipMemcpyHostToDevice, ctx->copy_stream) != hipSuccess) rc = PNGLOSS_HIP_ERROR;
+            hipMemcpyAsync(arena + m.img, ctx->h_pinned.p + m.img, m.px * 4, hipMemcpyHostToDevice, ctx->copy_stream) != hipSuccess) rc = PNGLOSS_HIP_ERROR;
     }
     if (rc == PNGLOSS_SUCCESS && hipStreamSynchronize(ctx->copy_stream) != hipSuccess) rc = PNGLOSS_HIP_ERROR;
     return rc;
@@ -1006,15 +1021,15 @@ int window_download(const HostWindow &w, HostTurns *turns)
     if (!any_pixels) return PNGLOSS_SUCCESS;
     for (size_t i = 0; i < w.n; i++) {
         const PlWindowImage &m = w.lay.im[i];
-        if (w.comes_back(i) && hipMemcpyAsync(ctx->h_pinned + m.img, ctx->d_arena + m.img, m.span, hipMemcpyDeviceToHost, ctx->copy_stream) != hipSuccess) return PNGLOSS_HIP_ERROR;
+        if (w.comes_back(i) && hipMemcpyAsync(ctx->h_pinned.p + m.img, ctx->d_arena.p + m.img, m.span, hipMemcpyDeviceToHost, ctx->copy_stream) != hipSuccess) return PNGLOSS_HIP_ERROR;
     }
     if (hipStreamSynchronize(ctx->copy_stream) != hipSuccess) return PNGLOSS_HIP_ERROR;
     std::unique_lock<std::mutex> out_lock;
     if (turns) out_lock = std::unique_lock<std::mutex>(turns->out_mu);
     for_each_image_on_threads(w.n, [&](size_t i) {
         if (!w.comes_back(i)) return;
-        std::memcpy(w.images[i].rgba, ctx->h_pinned + w.lay.im[i].img, w.lay.im[i].px * 4);
-        if (w.images[i].row_filters) std::memcpy(w.images[i].row_filters, ctx->h_pinned + w.lay.im[i].flt, w.images[i].height);
+        std::memcpy(w.images[i].rgba, ctx->h_pinned.p + w.lay.im[i].img, w.lay.im[i].px * 4);
+        if (w.images[i].row_filters) std::memcpy(w.images[i].row_filters, ctx->h_pinned.p + w.lay.im[i].flt, w.images[i].height);
     });
     return PNGLOSS_SUCCESS;
 }
@@ -1124,13 +1139,7 @@ void pngloss_hip_destroy(pngloss_hip_ctx *ctx)
     if (ctx->ev_seg_done) (void)hipEventDestroy(ctx->ev_seg_done);
     for (auto &e : ctx->ev)
         if (e) (void)hipEventDestroy(e);
-    if (ctx->d_ws) (void)hipFree(ctx->d_ws);
-    if (ctx->d_arena) (void)hipFree(ctx->d_arena);
-    if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
-    if (ctx->d_frames) (void)hipFree(ctx->d_frames);
-    if (ctx->d_keep) (void)hipFree(ctx->d_keep);
-    if (ctx->d_ssim) (void)hipFree(ctx->d_ssim);
-    if (ctx->d_target) (void)hipFree(ctx->d_target);
+    for (GrowBuf *b : { &ctx->d_ws, &ctx->d_arena, &ctx->h_pinned, &ctx->d_frames, &ctx->d_keep, &ctx->d_ssim, &ctx->d_target }) b->release();
     if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
     if (ctx->h_progress) (void)hipHostFree(ctx->h_progress);
     if (ctx->h_seg_words) (void)hipHostFree(ctx->h_seg_words);
@@ -1142,7 +1151,7 @@ void pngloss_hip_destroy(pngloss_hip_ctx *ctx)
 int pngloss_hip_optimize_batch_async(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n,
                                      unsigned quantization_strength, long bleed_divider, void *stream)
 {
-    return enqueue(ctx, images, n, nullptr, quantization_strength, bleed_divider, static_cast<hipStream_t>(stream));
+    return enqueue(ctx, images, n, BatchCall{ quantization_strength, bleed_divider, static_cast<hipStream_t>(stream), measure_of_options(ctx) });
 }
 
 int pngloss_hip_finish(pngloss_hip_ctx *ctx, pngloss_hip_result *results, size_t n) { return finish(ctx, results, n); }
@@ -1152,15 +1161,15 @@ int pngloss_hip_optimize_batch(pngloss_hip_ctx *ctx, const pngloss_hip_image_des
                                pngloss_hip_result *results)
 {
     if (!ctx) return PNGLOSS_INVALID_ARGUMENT;
-    ctx->sync_call = true; ctx->three_groups_ok = true;
-    int rc = enqueue(ctx, images, n, nullptr, quantization_strength, bleed_divider, static_cast<hipStream_t>(stream));
-    ctx->sync_call = false; ctx->three_groups_ok = false;
+    BatchCall call{ quantization_strength, bleed_divider, static_cast<hipStream_t>(stream), measure_of_options(ctx) };
+    call.sync_call = call.three_groups_ok = true;
+    const int rc = enqueue(ctx, images, n, call);
     if (rc) return rc;
     return finish(ctx, results, n);
 }
 
 static int batch_host_one(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images, size_t n, unsigned quantization_strength,
-                      long bleed_divider, pngloss_hip_result *results, pngloss_hip_scanlines *lines,
+                      long bleed_divider, Measure measure, pngloss_hip_result *results, pngloss_hip_scanlines *lines,
                       pngloss_hip_zstream *zs, HostTurns *turns = nullptr, int my_turn = 0)
 {
     /* whatever happens below, the next chunk must get its turn */
@@ -1181,8 +1190,8 @@ static int batch_host_one(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *im
      * Copies and kernels of a context run on its own non-blocking stream, so that two contexts (the two halves of a window,
      * batch_host) overlap: one half's transfers with the other half's kernels. */
     const auto ta0 = std::chrono::steady_clock::now();
-    int rc = grow(ctx->d_arena, ctx->arena_bytes, w.lay.total, 8);
-    if (rc == PNGLOSS_SUCCESS) rc = grow(ctx->h_pinned, ctx->pinned_bytes, w.lay.mirrored, 8, true);
+    int rc = ctx->d_arena.grow(w.lay.total, 8);
+    if (rc == PNGLOSS_SUCCESS) rc = ctx->h_pinned.grow(w.lay.mirrored, 8);
     if (rc) return rc;
     if (!ctx->copy_stream) PL_CHECK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
     if (ctx->hooks.debug_seam) std::fprintf(stderr, "pngloss_hip: host window chunk %d: arena %zu MB + pinned mirror %zu MB ready after %.1f ms\n", my_turn, w.lay.total >> 20, w.lay.mirrored >> 20, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ta0).count());
@@ -1196,9 +1205,10 @@ static int batch_host_one(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *im
     std::vector<pngloss_hip_result> own_results;
     if (!results) { own_results.resize(n ? n : 1); results = w.results = own_results.data(); }
     if (rc == PNGLOSS_SUCCESS) {
-        ctx->sync_call = true;                  /* (finish follows at once: no device-side wait on the copy stream, run_seg_engine) */
-        rc = enqueue(ctx, descs.data(), n, nullptr, quantization_strength, bleed_divider, ctx->copy_stream, w.emits.data());
-        ctx->sync_call = false;
+        BatchCall call{ quantization_strength, bleed_divider, ctx->copy_stream, measure };
+        call.sync_call = true;                  /* (finish follows at once: no device-side wait on the copy stream, run_seg_engine) */
+        call.emits = w.emits.data();
+        rc = enqueue(ctx, descs.data(), n, call);
     }
     if (rc == PNGLOSS_SUCCESS) rc = finish(ctx, results, n);
     /* a row without an acceptable filter (device status 65, pngloss_image.c:268-271) fails THAT image only: the others of
@@ -1224,22 +1234,21 @@ static int batch_host_one(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *im
  * (profiles/r02_host_seam.txt: staging + PCIe were 0.26 s next to a 0.28 s engine for 256 x 720p, one after the other).  The deflate
  * stage (zs) keeps its single pass: it sorts the whole window's scanlines as one stream. */
 static int batch_host(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images, size_t n, unsigned quantization_strength,
-                      long bleed_divider, pngloss_hip_result *results, pngloss_hip_scanlines *lines,
+                      long bleed_divider, Measure measure, pngloss_hip_result *results, pngloss_hip_scanlines *lines,
                       pngloss_hip_zstream *zs = nullptr)
 {
     if (!ctx || (n && !images)) return PNGLOSS_INVALID_ARGUMENT;
     ctx->split_last = false;
     /* chunks, each on its own context and stream, staggered by the staging turns (pl_host_window_chunks) */
     size_t K = pl_host_window_chunks(n, ctx->hooks, zs != nullptr);
-    if (K <= 1) return batch_host_one(ctx, images, n, quantization_strength, bleed_divider, results, lines, zs);
+    if (K <= 1) return batch_host_one(ctx, images, n, quantization_strength, bleed_divider, measure, results, lines, zs);
     while (ctx->peers.size() < K - 1) {
         pngloss_hip_ctx *p = pngloss_hip_create(ctx->device);
         if (!p) break;
         ctx->peers.push_back(p);
     }
     K = std::min(K, ctx->peers.size() + 1);
-    if (K <= 1) return batch_host_one(ctx, images, n, quantization_strength, bleed_divider, results, lines, zs);
-    for (pngloss_hip_ctx *p : ctx->peers) { p->opt_distortion = ctx->opt_distortion; p->opt_ssim = ctx->opt_ssim; p->opt_visible = ctx->opt_visible; }       /* the other chunks measure what this one measures */
+    if (K <= 1) return batch_host_one(ctx, images, n, quantization_strength, bleed_divider, measure, results, lines, zs);
     std::vector<uint64_t> pixels(n);
     for (size_t i = 0; i < n; i++) pixels[i] = (uint64_t)images[i].width * images[i].height;
     const std::vector<size_t> first = pl_host_window_cut(pixels, K);
@@ -1249,7 +1258,7 @@ static int batch_host(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images
     std::vector<int> rcs(K, PNGLOSS_SUCCESS);
     auto run_chunk = [&](size_t c) {
         pngloss_hip_ctx *cc = c == 0 ? ctx : ctx->peers[c - 1];
-        rcs[c] = batch_host_one(cc, images + first[c], first[c + 1] - first[c], quantization_strength, bleed_divider, results + first[c],
+        rcs[c] = batch_host_one(cc, images + first[c], first[c + 1] - first[c], quantization_strength, bleed_divider, measure, results + first[c],       /* (every chunk measures the same) */
                                 lines ? lines + first[c] : nullptr, nullptr, &turns, (int)c);
     };
     std::vector<std::thread> others;
@@ -1270,7 +1279,7 @@ static int batch_host(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images
 int pngloss_hip_optimize_batch_host(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images, size_t n,
                                     unsigned quantization_strength, long bleed_divider, pngloss_hip_result *results)
 {
-    return batch_host(ctx, images, n, quantization_strength, bleed_divider, results, nullptr);
+    return batch_host(ctx, images, n, quantization_strength, bleed_divider, measure_of_options(ctx), results, nullptr);
 }
 
 /* ---- all the GPUs of the node (replaces the one-file-at-a-time loop of /root/reference/src/pngloss.c:173-208 for a whole
@@ -1366,11 +1375,11 @@ static int deal_over_contexts(pngloss_hip_multi *m, const pngloss_hip_host_image
 /* One context's share of a search on host images, the one shape of both host forms.  Copies of the images go up into the search arena (laid out with the
  * SSIM tables and the scanline regions its caller names) and search(copies, layout, reports) -> code runs on them without committing; the host images stay as
  * they are until the chosen strengths run through the host-window path, once per distinct strength (pl_strength_groups) -- measured, so that every report
- * carries the record of what was written (with want_ssim the SSIM record too, into `ssim` where the caller has one).  Report: .strength, .runs, .distortion.
+ * carries the record of what was written (with want_ssim the SSIM record too, into `ssim` where the caller has one; visible: both over visible pixels).  Report: .strength, .runs, .distortion.
  * empty_images_run: the rerun counts in the report of an image without pixels as well. */
 template <class Report, class Search>
 static int batch_host_searched(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images, size_t n, long bleed_divider, pngloss_hip_result *results,
-                               pngloss_hip_scanlines *lines, pngloss_hip_zstream *zs, Report *reports, bool want_ssim, pngloss_hip_ssim *ssim,
+                               pngloss_hip_scanlines *lines, pngloss_hip_zstream *zs, Report *reports, bool want_ssim, bool visible, pngloss_hip_ssim *ssim,
                                int scanlines, bool empty_images_run, Search search)
 {
     if (!ctx || ctx->pending) return PNGLOSS_INVALID_ARGUMENT;
@@ -1382,27 +1391,25 @@ static int batch_host_searched(pngloss_hip_ctx *ctx, const pngloss_hip_host_imag
     }
     const PlTargetLayout lay = pl_target_layout(width, height, true, sizeof(PlMoveJob), sizeof(PlDistortJob), sizeof(PlDistortRecord),
                                                 want_ssim ? sizeof(PlSsimJob) : 0, want_ssim ? sizeof(PlSsimRecord) : 0, scanlines);
-    int rc = grow(ctx->d_target, ctx->target_bytes, lay.total, 8);
+    int rc = ctx->d_target.grow(lay.total, 8);
     if (rc) return rc;
     if (!ctx->copy_stream) PL_CHECK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
     std::vector<pngloss_hip_image_desc> descs(n);
     for (size_t i = 0; i < n; i++) {
         const size_t px = (size_t)width[i] * height[i];
-        descs[i] = pngloss_hip_image_desc{ px ? ctx->d_target + lay.image[i].img : nullptr, (px && images[i].row_filters) ? ctx->d_target + lay.image[i].filters : nullptr, width[i], height[i] };
+        descs[i] = pngloss_hip_image_desc{ px ? ctx->d_target.p + lay.image[i].img : nullptr, (px && images[i].row_filters) ? ctx->d_target.p + lay.image[i].filters : nullptr, width[i], height[i] };
         if (px) PL_CHECK(hipMemcpyAsync(descs[i].d_rgba, images[i].rgba, px * 4, hipMemcpyHostToDevice, ctx->copy_stream));
     }
     PL_CHECK(hipStreamSynchronize(ctx->copy_stream));
     std::vector<Report> rep(n ? n : 1);
+    SearchGuard guard{ ctx, true };       /* no single batch to index behind this call, here or on the peers */
     rc = search(descs.data(), lay, rep.data());
     if (pl_rc_is_hard(rc)) return rc;
     for (size_t i = 0; i < n; i++) chosen[i] = rep[i].strength;
-    const bool opt = ctx->opt_distortion, opt_ssim = ctx->opt_ssim;
     int worst = PNGLOSS_SUCCESS;
     for (const auto &group : pl_strength_groups(chosen)) {
         HostSubset sub(group.second, images, lines, zs);
-        ctx->opt_distortion = true; ctx->opt_ssim = want_ssim;
-        rc = batch_host(ctx, sub.images.data(), sub.n(), group.first, bleed_divider, sub.results.data(), sub.lines(), sub.zs());
-        ctx->opt_distortion = opt; ctx->opt_ssim = opt_ssim;
+        rc = batch_host(ctx, sub.images.data(), sub.n(), group.first, bleed_divider, Measure{ true, want_ssim, visible }, sub.results.data(), sub.lines(), sub.zs());
         sub.scatter(results, lines, zs);
         for (size_t k = 0; k < sub.n(); k++) {
             const size_t i = group.second[k];
@@ -1413,9 +1420,6 @@ static int batch_host_searched(pngloss_hip_ctx *ctx, const pngloss_hip_host_imag
         }
         worst = pl_fold_rc(worst, rc);
     }
-    /* no single batch to index, here or on the peers the host windows ran their other chunks on */
-    for (pngloss_hip_ctx *p : ctx->peers) if (p) { p->opt_distortion = opt; p->opt_ssim = opt_ssim; forget_last_batch(p); }
-    forget_last_batch(ctx);
     if (reports) for (size_t i = 0; i < n; i++) reports[i] = rep[i];
     return worst;
 }
@@ -1427,7 +1431,7 @@ int pngloss_hip_multi_optimize_batch_host(pngloss_hip_multi *m, const pngloss_hi
 {
     if (!m || m->ctx.empty() || (n && !images)) return PNGLOSS_INVALID_ARGUMENT;
     return deal_over_contexts(m, images, n, results, scanlines, streams, true, [&](pngloss_hip_ctx *ctx, HostSubset &mine) {
-        return batch_host(ctx, mine.images.data(), mine.n(), quantization_strength, bleed_divider, mine.results.data(), mine.lines(), mine.zs());
+        return batch_host(ctx, mine.images.data(), mine.n(), quantization_strength, bleed_divider, measure_of_options(ctx), mine.results.data(), mine.lines(), mine.zs());
     });
 }
 
@@ -1445,7 +1449,7 @@ struct SearchDevice {
     std::vector<std::vector<PlMoveJob>> move_tables;
     std::vector<std::vector<PlDistortJob>> distort_tables;
 
-    char *at(size_t offset) const { return ctx->d_target + offset; }
+    char *at(size_t offset) const { return ctx->d_target.p + offset; }
     void *address(uint32_t i, PlArenaRegion r) const
     {
         const PlTargetImage &m = lay.image[i];
@@ -1486,15 +1490,16 @@ struct SearchDevice {
         }
         return move(std::move(jobs));
     }
-    /* one ordinary batch: the images `who` at `strength`, through the entry the synchronous call uses.  emits: nullptr, or where each one's scanlines go */
+    /* one ordinary batch: the images `who` at `strength`, as the synchronous call asks for it, with nothing measured behind it (the search measures against its
+     * own originals: the keep arena is laid out afresh by every enqueue).  emits: nullptr, or where each one's scanlines go */
     int run(uint32_t strength, const std::vector<uint32_t> &who, const EmitTarget *emits, std::vector<pngloss_hip_result> &res)
     {
         std::vector<pngloss_hip_image_desc> descs(who.size());
         res.assign(who.size(), pngloss_hip_result{});
         for (size_t k = 0; k < who.size(); k++) descs[k] = images[who[k]];
-        ctx->sync_call = true; ctx->three_groups_ok = true;
-        int rc = enqueue(ctx, descs.data(), descs.size(), nullptr, strength, bleed, stream, emits);
-        ctx->sync_call = false; ctx->three_groups_ok = false;
+        BatchCall call{ strength, bleed, stream, Measure{} };
+        call.sync_call = call.three_groups_ok = true; call.emits = emits;
+        int rc = enqueue(ctx, descs.data(), descs.size(), call);
         if (rc == PNGLOSS_SUCCESS) rc = finish(ctx, res.data(), res.size());
         return pl_rc_is_hard(rc) ? rc : PNGLOSS_SUCCESS;           /* (single images that failed say so in their status) */
     }
@@ -1526,14 +1531,11 @@ struct SearchDevice {
 
 /* images: device-resident; the arena (ctx->d_target) has been grown to lay.total.  commit: at the end every image holds the result of its chosen
  * strength (else the images are left as the last probes left them: the host form runs the chosen strengths through the host-window path). */
-static int target_search(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n, const PlTargetLayout &lay, const pngloss_hip_target2 &t,
+static int target_search(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n, const PlTargetLayout &lay, const pngloss_hip_target2 &t, bool visible,
                          long bleed, hipStream_t stream, bool commit, pngloss_hip_result *results, pngloss_hip_target_report *reports, pngloss_hip_ssim *ssim_out)
 {
-    const bool want_ssim = t.min_ssim != 0.0;          /* without the condition the SSIM kernel is never launched */
-    const bool visible = ctx->opt_visible;             /* option "measure": the probes are accepted or refused on records over visible pixels */
-    /* whatever happens: the caller's option back, and no "last batch" to index */
-    SearchGuard guard{ ctx, ctx->opt_distortion, ctx->opt_ssim };
-    ctx->opt_distortion = ctx->opt_ssim = false;       /* the search measures against its own originals (the keep arena is laid out afresh by every enqueue) */
+    const bool want_ssim = t.min_ssim != 0.0;          /* without the condition the SSIM kernel is never launched; visible: the probes are accepted or refused on records over visible pixels */
+    SearchGuard guard{ ctx, false };
     SearchDevice dev{ ctx, images, lay, bleed, stream, {}, {} };
     PlSsimJob *const d_sj = reinterpret_cast<PlSsimJob *>(dev.at(lay.ssim_jobs));
     PlSsimRecord *const d_srec = reinterpret_cast<PlSsimRecord *>(dev.at(lay.ssim_records));
@@ -1657,9 +1659,9 @@ int pngloss_hip_optimize_batch_target2(pngloss_hip_ctx *ctx, const pngloss_hip_i
     const bool want_ssim = target->min_ssim != 0.0;
     const PlTargetLayout lay = pl_target_layout(width, height, false, sizeof(PlMoveJob), sizeof(PlDistortJob), sizeof(PlDistortRecord),
                                                 want_ssim ? sizeof(PlSsimJob) : 0, want_ssim ? sizeof(PlSsimRecord) : 0);
-    rc = grow(ctx->d_target, ctx->target_bytes, lay.total, 8);
+    rc = ctx->d_target.grow(lay.total, 8);
     if (rc) return rc;
-    return target_search(ctx, images, n, lay, *target, bleed_divider, static_cast<hipStream_t>(stream), true, results, reports, ssim);
+    return target_search(ctx, images, n, lay, *target, ctx->opt_visible, bleed_divider, static_cast<hipStream_t>(stream), true, results, reports, ssim);
 }
 
 /* one context's share of pngloss_hip_multi_optimize_batch_host_target: the rerun of the chosen strength counts for every image */
@@ -1667,9 +1669,10 @@ static int batch_host_target(pngloss_hip_ctx *ctx, const pngloss_hip_host_image 
                              pngloss_hip_result *results, pngloss_hip_scanlines *lines, pngloss_hip_zstream *zs, pngloss_hip_target_report *reports,
                              pngloss_hip_ssim *ssim)
 {
-    return batch_host_searched(ctx, images, n, bleed_divider, results, lines, zs, reports, target.min_ssim != 0.0, ssim, PLT_SCANLINES_OFF, true,
+    const bool visible = measure_of_options(ctx).visible;      /* option "measure": for the probes and for the records of the reruns */
+    return batch_host_searched(ctx, images, n, bleed_divider, results, lines, zs, reports, target.min_ssim != 0.0, visible, ssim, PLT_SCANLINES_OFF, true,
                                [&](const pngloss_hip_image_desc *copies, const PlTargetLayout &lay, pngloss_hip_target_report *rep) {
-                                   return target_search(ctx, copies, n, lay, target, bleed_divider, ctx->copy_stream, false, nullptr, rep, nullptr);
+                                   return target_search(ctx, copies, n, lay, target, visible, bleed_divider, ctx->copy_stream, false, nullptr, rep, nullptr);
                                });
 }
 
@@ -1710,9 +1713,7 @@ int pngloss_hip_multi_optimize_batch_host_target2(pngloss_hip_multi *m, const pn
 static int size_search(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n, const PlTargetLayout &lay, const pngloss_hip_size_target &t,
                        long bleed, hipStream_t stream, bool commit, pngloss_hip_result *results, pngloss_hip_zstream *streams, pngloss_hip_size_report *reports)
 {
-    /* whatever happens: the caller's options back, and no "last batch" to index */
-    SearchGuard guard{ ctx, ctx->opt_distortion, ctx->opt_ssim };
-    ctx->opt_distortion = ctx->opt_ssim = false;       /* the search measures against its own originals */
+    SearchGuard guard{ ctx, false };
     const bool want_streams = commit && streams;
     SearchDevice dev{ ctx, images, lay, bleed, stream, {}, {} };
     std::vector<PlSizeTrack> st(n);
@@ -1869,7 +1870,7 @@ int pngloss_hip_optimize_batch_size(pngloss_hip_ctx *ctx, const pngloss_hip_imag
     /* room for every original, every best result and the scanlines beside the workspace -- or the call fails here, with no image touched */
     const PlTargetLayout lay = pl_target_layout(width, height, false, sizeof(PlMoveJob), sizeof(PlDistortJob), sizeof(PlDistortRecord), 0, 0,
                                                 streams ? PLT_SCANLINES_PROBE_AND_BEST : PLT_SCANLINES_PROBE);
-    rc = grow(ctx->d_target, ctx->target_bytes, lay.total, 8);
+    rc = ctx->d_target.grow(lay.total, 8);
     if (rc) return rc;
     return size_search(ctx, images, n, lay, *target, bleed_divider, static_cast<hipStream_t>(stream), true, results, streams, reports);
 }
@@ -1880,9 +1881,7 @@ static int batch_host_size(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *i
                            pngloss_hip_result *results, pngloss_hip_scanlines *lines, pngloss_hip_zstream *zs, pngloss_hip_size_report *reports)
 {
     /* the byte budget reports over all pixels, whatever the option "measure" says */
-    struct AllPixels { pngloss_hip_ctx *c; bool was; ~AllPixels() { c->opt_visible = was; } } all{ ctx, ctx && ctx->opt_visible };
-    if (ctx) ctx->opt_visible = false;
-    return batch_host_searched(ctx, images, n, bleed_divider, results, lines, zs, reports, false, nullptr, PLT_SCANLINES_PROBE, false,
+    return batch_host_searched(ctx, images, n, bleed_divider, results, lines, zs, reports, false, false, nullptr, PLT_SCANLINES_PROBE, false,
                                [&](const pngloss_hip_image_desc *copies, const PlTargetLayout &lay, pngloss_hip_size_report *rep) {
                                    return size_search(ctx, copies, n, lay, target, bleed_divider, ctx->copy_stream, false, nullptr, nullptr, rep);
                                });
@@ -1916,7 +1915,7 @@ int pngloss_hip_optimize_batch_host_emit(pngloss_hip_ctx *ctx, const pngloss_hip
                                          unsigned quantization_strength, long bleed_divider, pngloss_hip_result *results,
                                          pngloss_hip_scanlines *scanlines)
 {
-    return batch_host(ctx, images, n, quantization_strength, bleed_divider, results, scanlines);
+    return batch_host(ctx, images, n, quantization_strength, bleed_divider, measure_of_options(ctx), results, scanlines);
 }
 
 int pngloss_hip_optimize_batch_host_zlib(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images, size_t n,
@@ -1924,7 +1923,7 @@ int pngloss_hip_optimize_batch_host_zlib(pngloss_hip_ctx *ctx, const pngloss_hip
                                          pngloss_hip_zstream *streams)
 {
     if (!streams && n) return PNGLOSS_INVALID_ARGUMENT;
-    return batch_host(ctx, images, n, quantization_strength, bleed_divider, results, nullptr, streams);
+    return batch_host(ctx, images, n, quantization_strength, bleed_divider, measure_of_options(ctx), results, nullptr, streams);
 }
 
 size_t pngloss_hip_zlib_bound(uint32_t width, uint32_t height) { return pl_deflate_bound(width, height); }
@@ -2004,12 +2003,12 @@ static int compare_distortion(pngloss_hip_ctx *ctx, const pngloss_hip_image_pair
     }
     PL_CHECK(hipSetDevice(ctx->device));
     const PlKeepLayout lay = pl_keep_layout(std::vector<uint32_t>(n, 0), std::vector<uint32_t>(n, 0), false, sizeof(PlDistortJob), sizeof(PlDistortRecord));
-    int rc = grow(ctx->d_keep, ctx->keep_bytes, lay.total, 8);
+    int rc = ctx->d_keep.grow(lay.total, 8);
     if (rc) return rc;
     rc = upload_distort_jobs(ctx, lay, n, b.data(), a.data(), pixels.data(), stream);
     if (rc) return rc;
-    PL_CHECK(pl_launch_distort(reinterpret_cast<const PlDistortJob *>(ctx->d_keep + lay.jobs), n, max_pixels, stream, visible));
-    PL_CHECK(hipMemcpyAsync(out, ctx->d_keep + lay.records, sizeof(pngloss_hip_distortion) * n, hipMemcpyDeviceToHost, stream));
+    PL_CHECK(pl_launch_distort(reinterpret_cast<const PlDistortJob *>(ctx->d_keep.p + lay.jobs), n, max_pixels, stream, visible));
+    PL_CHECK(hipMemcpyAsync(out, ctx->d_keep.p + lay.records, sizeof(pngloss_hip_distortion) * n, hipMemcpyDeviceToHost, stream));
     PL_CHECK(hipStreamSynchronize(stream));
     return PNGLOSS_SUCCESS;
 }
@@ -2028,8 +2027,8 @@ static int compare_ssim(pngloss_hip_ctx *ctx, const pngloss_hip_image_pair *pair
     uint64_t max_tiles = 0;
     const int rc = upload_ssim_jobs(ctx, n, a.data(), b.data(), width.data(), height.data(), stream, lay, max_tiles, visible);
     if (rc) return rc;
-    PL_CHECK(pl_launch_ssim(reinterpret_cast<const PlSsimJob *>(ctx->d_ssim + lay.jobs), n, max_tiles, stream, visible));
-    PL_CHECK(hipMemcpyAsync(out, ctx->d_ssim + lay.records, sizeof(pngloss_hip_ssim) * n, hipMemcpyDeviceToHost, stream));
+    PL_CHECK(pl_launch_ssim(reinterpret_cast<const PlSsimJob *>(ctx->d_ssim.p + lay.jobs), n, max_tiles, stream, visible));
+    PL_CHECK(hipMemcpyAsync(out, ctx->d_ssim.p + lay.records, sizeof(pngloss_hip_ssim) * n, hipMemcpyDeviceToHost, stream));
     PL_CHECK(hipStreamSynchronize(stream));
     return PNGLOSS_SUCCESS;
 }
@@ -2142,11 +2141,11 @@ int png_decode_body(pngloss_hip_ctx *ctx, const pngloss_hip_png_source *src, siz
     const auto tr0 = std::chrono::steady_clock::now();
     auto ms_since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr0).count(); };
     int rc = ensure_ws(ctx, total);
-    if (rc == PNGLOSS_SUCCESS && d_out) rc = grow(ctx->d_frames, ctx->frames_bytes, ftotal, 4);
+    if (rc == PNGLOSS_SUCCESS && d_out) rc = ctx->d_frames.grow(ftotal, 4);
     if (rc) return rc;
     const double ms_ws = ms_since();
     /* offsets into pointers: here and nowhere else */
-    char *const b = ctx->d_ws, *const fb = d_out ? ctx->d_frames : b;
+    char *const b = ctx->d_ws.p, *const fb = d_out ? ctx->d_frames.p : b;
     int32_t *d_status = reinterpret_cast<int32_t *>(b + lay.status), *d_zstatus = reinterpret_cast<int32_t *>(b + lay.zstatus);
     uint32_t *d_prog = reinterpret_cast<uint32_t *>(b + lay.prog);
     PliStream *d_zjobs = reinterpret_cast<PliStream *>(b + lay.zjobs);

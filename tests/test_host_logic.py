@@ -70,6 +70,41 @@ def test_no_environment_variable_of_the_shipped_library_changes_results():
     assert "getenv" not in open(os.path.join(U.ROOT, "pngloss_amd", "csrc", "pl_seg_pace.h")).read()
 
 
+def _context_mode_toggles(host):
+    """what in the text of pl_host.hip tells a batch its mode through the context: lines outside pngloss_hip_set_option that assign to one of the caller's
+    measuring options, and members of struct pngloss_hip_ctx that are a call's argument (BatchCall has them)"""
+    def body(text, head):
+        start = text.index("{", text.index(head))
+        depth, k = 0, start
+        while True:
+            depth += {"{": 1, "}": -1}.get(text[k], 0)
+            if depth == 0:
+                return start, k + 1
+            k += 1
+
+    a, b = body(host, "int pngloss_hip_set_option(")
+    outside = host[:a] + re.sub(r"[^\n]", " ", host[a:b]) + host[b:]
+    found = [line.strip() for line in outside.splitlines() if re.search(r"(->|\.)\s*opt_(distortion|ssim|visible)\s*=(?!=)", line)]
+    a, b = body(host, "struct pngloss_hip_ctx {")
+    struct = re.sub(r"/\*.*?\*/", "", host[a:b], flags=re.S)
+    found += ["member " + m for m in re.findall(r"\b(sync_call|three_groups_ok|want_progress)\b", struct)]
+    return found
+
+
+def test_a_batch_gets_its_mode_as_an_argument_not_through_the_context():
+    """The caller's measuring options are assigned by pngloss_hip_set_option and nowhere else, and what one call asks of a batch (a synchronous caller, three
+    launch groups, the progress word) is no member of the context: enqueue takes it as an argument.  The scan reports an old toggle line put back."""
+    host = open(os.path.join(U.ROOT, "pngloss_amd", "csrc", "pl_host.hip")).read()
+    assert len(re.findall(r"ctx->opt_(?:distortion|ssim|visible) = (?:true|false);", host)) == 6      # (the six assignments of pngloss_hip_set_option: the scan has something to skip)
+    assert _context_mode_toggles(host) == []
+    at = host.index("rc = enqueue(ctx, descs.data(), n, call);")
+    for old in ("ctx->opt_distortion = true; ctx->opt_ssim = want_ssim;", "p->opt_visible = ctx->opt_visible;", "if (ctx) ctx->opt_visible = false;",
+                "c.opt_ssim = opt_ssim;", "ctx->opt_distortion = ctx->opt_ssim = false;"):
+        assert _context_mode_toggles(host[:at] + old + "\n" + host[at:]) == [old], old
+    at = host.index("hipStream_t copy_stream = nullptr;")
+    assert _context_mode_toggles(host[:at] + "bool sync_call = false;\n    " + host[at:]) == ["member sync_call"]
+
+
 def test_result_record_slots_are_named_in_one_header():
     """pl_result.h is the one map of the per-image result record: elsewhere no subscript of a record starts with a number, and pl_host.hip reads
     copied records and fills engine_info through the header's names only (tests/test_result_host.py pins the decoder)."""
