@@ -186,7 +186,7 @@ typedef struct {
     unsigned char *data;      /* in: caller's buffer; out: zlib stream (header 78 DA ... Adler-32) */
     size_t capacity;          /* in */
     size_t size;              /* out */
-    int color_type;           /* out: 0, 2, 4 or 6 */
+    int color_type;           /* out: 0, 2, 4 or 6; with the option "indexed" on also 3 (pngloss_hip_indexed.h: pngloss_hip_last_palette has the palette) */
     uint32_t blocks[3];       /* out: deflate blocks written as stored / fixed / dynamic */
     uint32_t flags;           /* in: PNGLOSS_HIP_Z_* */
 } pngloss_hip_zstream;
@@ -329,6 +329,10 @@ double pngloss_hip_ssim_mean(const pngloss_hip_ssim *r, unsigned channel_mask);
  * options; not while a batch is in flight on the context (PNGLOSS_INVALID_ARGUMENT). */
 int pngloss_hip_compare_batch_visible(pngloss_hip_ctx *ctx, const pngloss_hip_image_pair *pairs, size_t n, pngloss_hip_distortion *out_distortion,
                                       pngloss_hip_ssim *out_ssim, void *stream);
+
+/* ---- Indexed-colour streams: the option "indexed" (pngloss_hip_set_option, below) lets the calls that return zlib streams answer with PNG colour
+ * type 3 where that makes the smaller file.  Its definitions, its record pngloss_hip_palette and the accessors pngloss_hip_last_palette /
+ * pngloss_hip_multi_last_palette are in pngloss_hip_indexed.h, which includes this header. ---- */
 
 /* ---- A strength per image, found from a distortion target (no reference equivalent: the reference tool takes -s and nothing else).  A strength
  * says nothing about how the result will look, and the right one differs from image to image; the optimiser works in place, so a caller who
@@ -592,6 +596,9 @@ int pngloss_hip_last_engine_info(pngloss_hip_ctx *ctx, size_t index, int32_t inf
  *   (pngloss_hip_optimize_batch_target[2], pngloss_hip_multi_optimize_batch_host_target[2]) count: every pixel, or the visible ones on alpha-premultiplied
  *   channels ("Measuring over visible pixels", above).  No effect unless one of those measures; the byte-budget search always reports over all pixels.
  *   "all" launches exactly what the library launched before the option existed.
+ * Name "indexed", value "on" | "off" (default): the calls that return zlib streams may answer with colour type 3 from here on (pngloss_hip_indexed.h,
+ *   "Indexed-colour streams"; pngloss_hip_last_palette has the palette).  Like the options above it is read once, when a call begins, and travels with that batch.  "off"
+ *   launches and writes exactly what the library did before the option existed.
  * Returns PNGLOSS_SUCCESS or PNGLOSS_INVALID_ARGUMENT (unknown name or value).
  * Results never depend on an option, on the engine, or on the environment: the remaining environment hooks (PNGLOSS_HIP_SEG_GROUPS, _SEG_UNIT, _ENUM_NT,
  * _NO_STREAM_WAIT, _SEGPROF, _DEBUG ...: timing and test pins) are read once, when a context is created, and none of them changes a byte; the debugging aid

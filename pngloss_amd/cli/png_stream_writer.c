@@ -133,7 +133,10 @@ static pngloss_error put_idat_zlib(sink *sp, const png_stream_image *im, size_t 
 pngloss_error png_stream_write(FILE *out, const png_stream_image *im, size_t *bytes_written, size_t *metadata_bytes)
 {
     static const unsigned char signature[8] = { 0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n' };
-    const unsigned channels = im->color_type == 0 ? 1 : (im->color_type == 4 ? 2 : (im->color_type == 2 ? 3 : 4));
+    const unsigned channels = (im->color_type == 0 || im->color_type == 3) ? 1 : (im->color_type == 4 ? 2 : (im->color_type == 2 ? 3 : 4));
+    const bool indexed = im->color_type == 3;
+    if (indexed && (!im->palette || im->palette_entries < 1 || im->palette_entries > 256 || im->trns_entries > im->palette_entries || (im->trns_entries && !im->trns)))
+        return INVALID_ARGUMENT;
     const size_t rowbytes = (size_t)im->width * channels;
     const size_t data_size = (rowbytes + 1) * im->height;
     sink s = { out, 0, SUCCESS };
@@ -155,6 +158,11 @@ pngloss_error png_stream_write(FILE *out, const png_stream_image *im, size_t *by
         put_chunk(&s, "sRGB", &intent, 1);
     }
     put_passthrough(&s, im->chunks, PNG_STREAM_HAVE_IHDR, &meta);
+    if (indexed) {
+        /* libpng's png_write_info: PLTE, then tRNS, in front of the chunks recorded behind the input's PLTE */
+        put_chunk(&s, "PLTE", im->palette, (size_t)im->palette_entries * 3);
+        if (im->trns_entries) put_chunk(&s, "tRNS", im->trns, im->trns_entries);
+    }
     put_passthrough(&s, im->chunks, PNG_STREAM_HAVE_PLTE, &meta);
 
     if (im->zdata) {
@@ -190,7 +198,8 @@ static size_t passthrough_bytes(const struct rwpng_chunk *list)
 
 size_t png_stream_file_size(const png_stream_image *im, size_t stream_bytes, size_t idat_slice)
 {
-    const size_t container = 8 + (12 + 13) + (im->tag_gamma ? 12 + 4 : 0) + (im->tag_srgb ? 12 + 1 : 0) + passthrough_bytes(im->chunks) + 12;
+    const size_t palette = im->color_type == 3 ? 12 + (size_t)im->palette_entries * 3 + (im->trns_entries ? 12 + (size_t)im->trns_entries : 0) : 0;
+    const size_t container = 8 + (12 + 13) + (im->tag_gamma ? 12 + 4 : 0) + (im->tag_srgb ? 12 + 1 : 0) + palette + passthrough_bytes(im->chunks) + 12;
     const size_t idat_chunks = (stream_bytes + idat_slice - 1) / idat_slice;
     return container + stream_bytes + 12 * idat_chunks;
 }

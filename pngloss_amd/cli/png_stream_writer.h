@@ -15,7 +15,7 @@ extern "C" {
 
 typedef struct {
     uint32_t width, height;
-    int color_type;                    /* 0 gray, 4 gray+alpha, 2 RGB, 6 RGBA; always 8 bits per sample         */
+    int color_type;                    /* 0 gray, 4 gray+alpha, 2 RGB, 6 RGBA, 3 indexed (`palette`); always 8 bits per sample or index */
     const unsigned char *filter_ids;   /* [height] PNG filter type 0..4 of every scanline                       */
     const unsigned char *rows;         /* filtered scanline bytes, width*channels per row ...                   */
     size_t pitch;                      /* ... `pitch` bytes apart                                               */
@@ -25,6 +25,12 @@ typedef struct {
     size_t maximum_file_size;          /* 0 = unlimited, else TOO_LARGE_FILE beyond it                          */
     const unsigned char *zdata;        /* optional: the finished zlib stream of the scanlines (GPU deflate); then    */
     size_t zsize;                      /* filter_ids/rows are not read and no zlib runs here                          */
+    /* colour type 3 only (the library's option "indexed"): rows are `width` index bytes each.  PLTE follows the gAMA / sRGB tags and the chunks
+     * passed through from in front of the input's PLTE, tRNS follows PLTE, both precede the first IDAT -- where libpng writes them */
+    const unsigned char *palette;      /* palette_entries RGB triples, 1..256 of them: the PLTE payload               */
+    unsigned palette_entries;
+    const unsigned char *trns;         /* the alphas of the first trns_entries palette entries: the tRNS payload;      */
+    unsigned trns_entries;             /* 0: no tRNS chunk is written                                                  */
 } png_stream_image;
 
 pngloss_error png_stream_write(FILE *out, const png_stream_image *image, size_t *bytes_written, size_t *metadata_bytes);
@@ -35,7 +41,8 @@ pngloss_error png_stream_write(FILE *out, const png_stream_image *image, size_t 
 
 /* The size of the file png_stream_write writes for `image` when its zlib stream has stream_bytes bytes and goes out in IDAT chunks of at most
  * idat_slice bytes: signature, IHDR, the gAMA / sRGB tags, the pass-through chunks that will be copied, 12 bytes of framing per IDAT chunk, IEND.
- * Only width-independent fields of `image` are read (tags and chunks): rows, filter ids and zdata may be NULL. */
+ * Only width-independent fields of `image` are read (tags, chunks and, for colour type 3, the sizes of the palette and of tRNS): rows, filter ids
+ * and zdata may be NULL. */
 size_t png_stream_file_size(const png_stream_image *image, size_t stream_bytes, size_t idat_slice);
 
 /* The other way round: the largest stream whose file is at most file_budget bytes; 0 when not even a 1-byte stream fits (the budget is smaller

@@ -28,6 +28,7 @@
 #include <unistd.h>
 
 #include "../../include/pngloss_hip.h"
+#include "../../include/pngloss_hip_indexed.h"
 #include "png_bridge.h"
 #include "png_stream_writer.h"
 
@@ -55,6 +56,7 @@ struct options {
     bool size_percent;         /* ... given as a percentage of each input file's size */
     unsigned long long size_value;   /* bytes, or percent */
     bool visible;              /* --visible: --distortion, --ssim and the --target searches measure over visible pixels (the library's option "measure") */
+    bool indexed;              /* --indexed: a result of at most 256 colours is written as a palette file where that file is smaller (the library's option "indexed") */
     bool gpu_read;             /* --gpu-read: inverse filters + expansion to RGBA8 on the device (inflate stays zlib on the decode threads) */
 };
 
@@ -76,6 +78,10 @@ static const char usage_text[] =
     "                    files several percent smaller than with zlib level 9, much faster)\n"
     "  --gpu-read        undo the PNG scanline filters and expand to RGBA on the GPU (plain or\n"
     "                    Adam7-interlaced files; the others are read with libpng as usual)\n"
+    "  --indexed         write a result of at most 256 colours as a palette file (colour type 3) where that\n"
+    "                    makes the file smaller: both encodings are compressed on the GPU and the smaller\n"
+    "                    file is kept; implies --gpu-deflate; -v prints the colours and both sizes; not\n"
+    "                    with --target-size, --target-psnr, --target-ssim or --max-error\n"
     "  --distortion      report how lossy each written file is: PSNR over the stored channels,\n"
     "                    changed pixels, largest channel error (measured on the GPU)\n"
     "  --target-psnr DB  pick each file's strength itself: the search (at most -s, by halving) for a\n"
@@ -104,7 +110,7 @@ static const char usage_text[] =
 
 /* ------------------------------------------------------------------------------------------- options */
 
-enum { OPT_EXT = 256, OPT_NO_FORCE, OPT_SKIP_LARGER, OPT_STRIP, OPT_GPU_DEFLATE, OPT_GPU_READ, OPT_DISTORTION, OPT_TARGET_PSNR, OPT_MAX_ERROR, OPT_SSIM, OPT_TARGET_SSIM, OPT_TARGET_SIZE, OPT_VISIBLE };
+enum { OPT_EXT = 256, OPT_NO_FORCE, OPT_SKIP_LARGER, OPT_STRIP, OPT_GPU_DEFLATE, OPT_GPU_READ, OPT_DISTORTION, OPT_TARGET_PSNR, OPT_MAX_ERROR, OPT_SSIM, OPT_TARGET_SSIM, OPT_TARGET_SIZE, OPT_VISIBLE, OPT_INDEXED };
 
 static bool parse_number(const char *text, unsigned long *out)
 {
@@ -159,6 +165,7 @@ static pngloss_error parse_options(int argc, char **argv, struct options *o)
         { "target-ssim", required_argument, NULL, OPT_TARGET_SSIM },
         { "target-size", required_argument, NULL, OPT_TARGET_SIZE },
         { "visible", no_argument, NULL, OPT_VISIBLE },
+        { "indexed", no_argument, NULL, OPT_INDEXED },
         { NULL, 0, NULL, 0 },
     };
     for (int c; (c = getopt_long(argc, argv, "vqfo:Vhs:b:", table, NULL)) != -1;) {
@@ -193,6 +200,7 @@ static pngloss_error parse_options(int argc, char **argv, struct options *o)
             o->have_size = true;
             break;
         case OPT_VISIBLE: o->visible = true; break;
+        case OPT_INDEXED: o->indexed = true; break;
         case 'h': o->help = true; break;
         case 'V': o->version = true; break;
         case 'o':
@@ -252,6 +260,8 @@ struct job {
     bool have_distortion;
     pngloss_hip_ssim ssim;               /* --ssim: the same pair's structural similarity (have_ssim: the library had a record) */
     bool have_ssim;
+    pngloss_hip_palette palette;         /* --indexed: what the library decided for this file (color_type 3: the PLTE / tRNS payloads of the written file) */
+    bool have_palette;
     png_stream_source src;    /* --gpu-read: inflated scanlines waiting for the device (src.scanlines != NULL) */
 };
 
@@ -404,7 +414,9 @@ static pngloss_error encode_to(struct job *j, png24_image *img, unsigned char *f
         /* the optimised image: scanlines were filtered on the GPU, only deflate + chunk framing happen here */
         const png_stream_image si = { img->width, img->height, j->color_type, j->line_types, j->lines, (size_t)img->width * 4, img->gamma,
                                       img->output_color != RWPNG_GAMA_ONLY && img->output_color != RWPNG_NONE, img->output_color == RWPNG_SRGB,
-                                      img->chunks, img->maximum_file_size, o->gpu_deflate ? j->lines : NULL, o->gpu_deflate ? j->zsize : 0 };
+                                      img->chunks, img->maximum_file_size, o->gpu_deflate ? j->lines : NULL, o->gpu_deflate ? j->zsize : 0,
+                                      j->color_type == 3 ? &j->palette.rgb[0][0] : NULL, j->color_type == 3 ? j->palette.entries : 0,
+                                      j->color_type == 3 ? j->palette.alpha : NULL, j->color_type == 3 ? j->palette.trns_entries : 0 };
         rc = png_stream_write(f, &si, &img->file_size, &img->metadata_size);
     } else {
         rc = rwpng_write_image24(f, img, NULL);     /* the untouched original (pipe fallback): plain libpng */
@@ -458,6 +470,10 @@ static void encode_job(struct job *j, const struct options *o)
     if (o->verbose && o->have_target) say(j, "  strength %u chosen in %u probes\n", j->target.strength, j->target.probes);
     if (o->verbose && o->have_size) say(j, "  strength %u chosen in %u probes\n", j->size.strength, j->size.probes);
     if (o->verbose) say(j, "  compression complete\n  used %u unique symbols\n", j->gpu.unique_symbols);
+    if (o->verbose && j->color_type == 3)
+        say(j, "  indexed: %u colours, %llu bytes of image data and %llu of palette against %llu bytes as truecolour\n", j->palette.colors,
+            (unsigned long long)j->palette.indexed_bytes, (unsigned long long)(12u + 3u * j->palette.entries + (j->palette.trns_entries ? 12u + j->palette.trns_entries : 0u)),
+            (unsigned long long)j->palette.truecolor_bytes);
     if (o->skip_if_larger) j->out.maximum_file_size = j->in.file_size - 1;
     j->out.chunks = j->in.chunks;          /* metadata travels to the output */
     j->in.chunks = NULL;
@@ -667,6 +683,8 @@ static pngloss_error run_window(struct job *jobs, size_t n, const struct options
                 fputs("  warning: the library refused the option \"distortion\"; no distortion lines\n", stderr);
             if (*ctx && o->ssim && pngloss_hip_multi_set_option(*ctx, "ssim", "on") != PNGLOSS_SUCCESS)
                 fputs("  warning: the library refused the option \"ssim\"; no ssim lines\n", stderr);
+            if (*ctx && o->indexed && pngloss_hip_multi_set_option(*ctx, "indexed", "on") != PNGLOSS_SUCCESS)
+                fputs("  warning: the library refused the option \"indexed\"; every file is written as truecolour\n", stderr);
             /* --visible: what those two and the searches measure.  A library that refuses it would measure something else than the lines say */
             if (*ctx && o->visible && pngloss_hip_multi_set_option(*ctx, "measure", "visible") != PNGLOSS_SUCCESS) {
                 fputs("  error: the library refused the option \"measure\"\n", stderr);
@@ -687,7 +705,7 @@ static pngloss_error run_window(struct job *jobs, size_t n, const struct options
                 j->size_budget = (size_t)want;
                 const png_stream_image si = { j->out.width, j->out.height, 6, NULL, NULL, 0, j->out.gamma,
                                               j->out.output_color != RWPNG_GAMA_ONLY && j->out.output_color != RWPNG_NONE, j->out.output_color == RWPNG_SRGB,
-                                              j->in.chunks, 0, NULL, 0 };
+                                              j->in.chunks, 0, NULL, 0, NULL, 0, NULL, 0 };
                 const size_t largest = png_stream_largest_stream(&si, j->size_budget, PNG_STREAM_GPU_IDAT_SLICE);
                 budget[k] = largest ? largest : 1;
             }
@@ -720,6 +738,11 @@ static pngloss_error run_window(struct job *jobs, size_t n, const struct options
             } else {
             jobs[who[k]].have_distortion = o->distortion && *ctx && pngloss_hip_multi_last_distortion(*ctx, k, &jobs[who[k]].distortion) == PNGLOSS_SUCCESS;
             jobs[who[k]].have_ssim = o->ssim && *ctx && pngloss_hip_multi_last_ssim(*ctx, k, &jobs[who[k]].ssim) == PNGLOSS_SUCCESS;
+            jobs[who[k]].have_palette = o->indexed && *ctx && pngloss_hip_multi_last_palette(*ctx, k, &jobs[who[k]].palette) == PNGLOSS_SUCCESS;
+            }
+            if (jobs[who[k]].color_type == 3 && !jobs[who[k]].have_palette && rc == PNGLOSS_SUCCESS) {
+                say(&jobs[who[k]], "  error: the library returned an indexed stream without its palette\n");
+                jobs[who[k]].status = (pngloss_error)PNGLOSS_HIP_ERROR;
             }
             if (rc != PNGLOSS_SUCCESS && !(rc == PNGLOSS_INTERNAL_ABORT && res[k].status == 0)) {
                 /* (a batch in which single images failed reports PNGLOSS_INTERNAL_ABORT and leaves the others done.)
@@ -757,6 +780,8 @@ int main(int argc, char **argv)
     if (o.visible && !(o.distortion || o.ssim || o.have_target)) { fputs("--visible needs one of --distortion, --ssim, --target-psnr, --max-error or --target-ssim.\n", stderr); return INVALID_ARGUMENT; }
     if (o.visible && o.have_size) { fputs("--visible cannot be combined with --target-size.\n", stderr); return INVALID_ARGUMENT; }
     if (o.have_size && o.size_value < 1) { fputs("Must specify a size target of at least 1 byte or 1 percent.\n", stderr); return INVALID_ARGUMENT; }
+    if (o.indexed && (o.have_size || o.have_target)) { fputs("--indexed cannot be combined with --target-size, --target-psnr, --target-ssim or --max-error.\n", stderr); return INVALID_ARGUMENT; }
+    if (o.indexed) o.gpu_deflate = true;            /* the choice is between two streams of the device deflate */
     if (o.have_size) o.gpu_deflate = true;          /* the budget is for the file the device deflate writes: zlib-9's size is not what the device measures */
     if (o.bleed < 1 || o.bleed > 32767) { fputs("Must specify a bleed divider in the range 1-32767.\n", stderr); return INVALID_ARGUMENT; }
     if (o.extension && o.output_path) { fputs("--ext and --output options can't be used at the same time\n", stderr); return INVALID_ARGUMENT; }

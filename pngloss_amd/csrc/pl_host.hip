@@ -12,12 +12,14 @@
  * a synchronous caller, what to measure behind it -- is an argument (BatchCall) of enqueue: no function tells another what to run by writing into the context.
  */
 #include "../../include/pngloss_hip.h"
+#include "../../include/pngloss_hip_indexed.h"
 #include "pl_device.h"
 #include "pl_deflate.h"
 #include "pl_pngread.h"
 #include "pl_inflate.h"
 #include "pl_distort.h"
 #include "pl_ssim.h"
+#include "pl_index.h"
 #include "pl_target.h"
 #include "pl_size.h"
 #include "pl_target_dev.h"
@@ -166,6 +168,12 @@ struct pngloss_hip_ctx {
     const PlSsimRecord *d_ssim_records = nullptr;    /* the batch in flight is measured: its records, copied back by finish */
     std::vector<pngloss_hip_ssim> ssim;              /* per image of the last finished batch; empty when it ran with the option off */
 
+    /* option "indexed": the index workspace (pl_layout.h: pl_index_layout -- job table, counters, palette records, colour tables, index rows), regrown on
+     * demand like the others; used by the deflate stage of a host window (window_index) */
+    bool opt_indexed = false;        /* pngloss_hip_set_option("indexed", "on" | "off") */
+    GrowBuf d_index;
+    std::vector<pngloss_hip_palette> palette;        /* per image of the last finished host window that returned zlib streams with the option on; else empty */
+
     /* pngloss_hip_optimize_batch_target: the search arena (pl_target.h: tables, originals, best results so far), regrown on demand like the others */
     GrowBuf d_target;
 
@@ -206,7 +214,7 @@ int deflate_rc(hipError_t e)
 /* The context has no "last batch" to index (pngloss_hip_last_*): enqueue begins every batch with it (only a split host window sets split_last again: batch_host) */
 void forget_last_batch(pngloss_hip_ctx *c)
 {
-    c->n_last = 0; c->h_jobs.clear(); c->distortion.clear(); c->d_records = nullptr; c->ssim.clear(); c->d_ssim_records = nullptr; c->split_last = false;
+    c->n_last = 0; c->h_jobs.clear(); c->distortion.clear(); c->d_records = nullptr; c->ssim.clear(); c->d_ssim_records = nullptr; c->palette.clear(); c->split_last = false;
 }
 /* A search runs many batches of its own on the context: whatever happens, no "last batch" to index behind it -- for the host forms (peers), none
  * on the peers the host windows ran their other chunks on either */
@@ -219,9 +227,12 @@ struct EmitTarget { void *d_ids; void *d_rows; uint32_t pitch; };
 
 /* What to measure behind a batch: the distortion records, the SSIM records, and whether the two count the visible pixels or all of them
  * (pl_distort_core.h, pl_ssim_core.h).  The pipeline never sees it. */
-struct Measure { bool distortion = false, ssim = false, visible = false; };
+struct Measure {
+    bool distortion = false, ssim = false, visible = false;
+    bool indexed = false;       /* option "indexed": not a measurement, but it travels the same way -- the deflate stage of a host window (window_index) reads it, nothing else does */
+};
 /* ... as the caller's options ask for it: what the plain entry points hand on (no context: nothing; the call fails where it always did) */
-Measure measure_of_options(const pngloss_hip_ctx *c) { return c ? Measure{ c->opt_distortion, c->opt_ssim, c->opt_visible } : Measure{}; }
+Measure measure_of_options(const pngloss_hip_ctx *c) { return c ? Measure{ c->opt_distortion, c->opt_ssim, c->opt_visible, c->opt_indexed } : Measure{}; }
 
 /* What one call asks of a batch (enqueue): written down by its entry point, read by enqueue and run_seg_engine, kept nowhere */
 struct BatchCall {
@@ -978,6 +989,8 @@ struct HostWindow {
     pngloss_hip_zstream *zs;
     PlWindowLayout lay;
     std::vector<EmitTarget> emits;
+    bool indexed = false;           /* option "indexed" on a window that returns zlib streams: the deflate stage also tries colour type 3 (window_index) */
+    PlIndexLayout ilay;             /* ... in the index workspace, laid out and grown before anything is enqueued */
     /* this image's pixels (and filter flags) come back to the caller */
     bool comes_back(size_t i) const
     {
@@ -1051,6 +1064,97 @@ int window_scanlines(const HostWindow &w)
     return rc;
 }
 
+/* Option "indexed", behind the truecolour streams of the images `who` (zs[i].size = T is in place): count every image's colours; for the eligible
+ * ones build the palette and the index rows and deflate those into a buffer of the window's own -- BOTH candidates are written, and the indexed one
+ * replaces the truecolour stream in the caller's buffer where I + overhead < T (pl_index_core.h).  An image that is not eligible costs the count
+ * kernel and nothing else, and its stream is the one the call above wrote.  Leaves the palette records of the window in ctx->palette. */
+int window_index(const HostWindow &w, const std::vector<size_t> &who)
+{
+    pngloss_hip_ctx *ctx = w.ctx;
+    pngloss_hip_zstream *zs = w.zs;
+    hipStream_t stream = ctx->copy_stream;
+    ctx->palette.assign(w.n, pngloss_hip_palette{});
+    if (who.empty()) return PNGLOSS_SUCCESS;
+    char *const base = ctx->d_index.p;
+    uint32_t *const d_counts = reinterpret_cast<uint32_t *>(base + w.ilay.counts);
+    PliRecord *const d_records = reinterpret_cast<PliRecord *>(base + w.ilay.records);
+    std::vector<PlIndexJob> jobs(who.size());
+    uint64_t max_pixels = 0;
+    for (size_t k = 0; k < who.size(); k++) {
+        const size_t i = who[k];
+        const PlIndexImage &m = w.ilay.im[i];
+        ctx->palette[i].truecolor_bytes = zs[i].size;
+        jobs[k] = PlIndexJob{ reinterpret_cast<const uint32_t *>(ctx->d_arena.p + w.lay.im[i].img), (uint64_t)w.lay.im[i].px, w.images[i].width, w.images[i].height,
+                              reinterpret_cast<uint64_t *>(base + m.table), d_counts + i, d_records + i, reinterpret_cast<uint8_t *>(base + m.ids),
+                              reinterpret_cast<uint8_t *>(base + m.rows), m.pitch, 0 };
+        max_pixels = std::max<uint64_t>(max_pixels, w.lay.im[i].px);
+    }
+    std::vector<uint32_t> counts(w.n, 0);
+    PL_CHECK(hipMemsetAsync(base + w.ilay.counts, 0, w.ilay.zeroed, stream));
+    PL_CHECK(hipMemsetAsync(base + w.ilay.tables, 0xFF, w.ilay.tables_bytes, stream));
+    PL_CHECK(hipMemcpyAsync(base + w.ilay.jobs, jobs.data(), sizeof(PlIndexJob) * jobs.size(), hipMemcpyHostToDevice, stream));
+    PL_CHECK(pl_launch_index_count(reinterpret_cast<const PlIndexJob *>(base + w.ilay.jobs), jobs.size(), max_pixels, stream));
+    PL_CHECK(hipMemcpyAsync(counts.data(), d_counts, sizeof(uint32_t) * w.n, hipMemcpyDeviceToHost, stream));
+    PL_CHECK(hipStreamSynchronize(stream));
+    std::vector<PlIndexJob> elig;
+    std::vector<size_t> elig_who;
+    uint32_t max_height = 0;
+    for (size_t k = 0; k < who.size(); k++) {
+        const size_t i = who[k];
+        ctx->palette[i].colors = pli_colors_of(counts[i]);
+        if (counts[i] < 1 || counts[i] > PLI_MAX_COLORS) continue;
+        elig.push_back(jobs[k]);
+        elig_who.push_back(i);
+        max_height = std::max(max_height, w.images[i].height);
+    }
+    if (elig.empty()) return PNGLOSS_SUCCESS;
+    std::vector<PliRecord> records(elig.size());
+    PL_CHECK(hipMemcpyAsync(base + w.ilay.jobs, elig.data(), sizeof(PlIndexJob) * elig.size(), hipMemcpyHostToDevice, stream));   /* (the count kernel has read its table: synchronised above) */
+    PL_CHECK(pl_launch_index_palette(reinterpret_cast<const PlIndexJob *>(base + w.ilay.jobs), elig.size(), stream));
+    PL_CHECK(pl_launch_index_rows(reinterpret_cast<const PlIndexJob *>(base + w.ilay.jobs), elig.size(), max_height, stream));
+    for (size_t k = 0; k < elig.size(); k++) PL_CHECK(hipMemcpyAsync(&records[k], elig[k].record, sizeof(PliRecord), hipMemcpyDeviceToHost, stream));
+    PL_CHECK(hipStreamSynchronize(stream));
+    std::vector<pl_deflate_image> dz(elig.size());
+    std::vector<std::vector<unsigned char>> out(elig.size());
+    for (size_t k = 0; k < elig.size(); k++) {
+        const size_t i = elig_who[k];
+        if (records[k].entries != counts[i]) {
+            std::fprintf(stderr, "pngloss_hip: indexed: image %zu has %u colours in its table, its counter says %u\n", i, records[k].entries, counts[i]);
+            return PNGLOSS_HIP_ERROR;
+        }
+        out[k].resize(pl_deflate_bound((w.images[i].width + 3) / 4, w.images[i].height));      /* (the bound is stated for 4-byte pixels: width index bytes are at most that many) */
+        pl_deflate_image d{};
+        d.d_filter_types = elig[k].ids;
+        d.d_scanlines = elig[k].rows;
+        d.pitch = elig[k].pitch;
+        d.rowbytes = w.images[i].width;
+        d.height = w.images[i].height;
+        d.out = out[k].data();
+        d.out_capacity = out[k].size();
+        dz[k] = d;
+    }
+    const int rc = deflate_rc(pl_deflate_images(dz.data(), dz.size(), nullptr));
+    if (rc) return rc;
+    for (size_t k = 0; k < elig.size(); k++) {
+        const size_t i = elig_who[k];
+        pngloss_hip_palette &p = ctx->palette[i];
+        p.indexed_bytes = dz[k].out_size;
+        if (!pli_keep_indexed(counts[i], p.indexed_bytes, p.truecolor_bytes, records[k].trns_entries) || dz[k].out_size > zs[i].capacity) continue;
+        p.entries = records[k].entries;
+        p.trns_entries = records[k].trns_entries;
+        for (uint32_t e = 0; e < p.entries; e++) {
+            const uint32_t word = records[k].words[e];
+            p.rgb[e][0] = (uint8_t)word; p.rgb[e][1] = (uint8_t)(word >> 8); p.rgb[e][2] = (uint8_t)(word >> 16);
+            p.alpha[e] = (uint8_t)(word >> 24);
+        }
+        std::memcpy(zs[i].data, out[k].data(), dz[k].out_size);
+        zs[i].size = dz[k].out_size;
+        zs[i].color_type = 3;
+        zs[i].blocks[0] = dz[k].blocks_stored; zs[i].blocks[1] = dz[k].blocks_fixed; zs[i].blocks[2] = dz[k].blocks_dynamic;
+    }
+    return PNGLOSS_SUCCESS;
+}
+
 /* the emitted scanlines through the device deflate into the caller's zlib streams */
 int window_deflate(const HostWindow &w)
 {
@@ -1085,6 +1189,7 @@ int window_deflate(const HostWindow &w)
             zs[who[k]].blocks[0] = dz[k].blocks_stored; zs[who[k]].blocks[1] = dz[k].blocks_fixed; zs[who[k]].blocks[2] = dz[k].blocks_dynamic;
         }
     }
+    if (rc == PNGLOSS_SUCCESS && w.indexed) rc = window_index(w, who);
     ctx->deflate_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (ctx->hooks.debug_seam) std::fprintf(stderr, "pngloss_hip: host window: deflate stage %.1f ms for %zu images\n", ctx->deflate_ms, dz.size());
     return rc;
@@ -1139,7 +1244,7 @@ void pngloss_hip_destroy(pngloss_hip_ctx *ctx)
     if (ctx->ev_seg_done) (void)hipEventDestroy(ctx->ev_seg_done);
     for (auto &e : ctx->ev)
         if (e) (void)hipEventDestroy(e);
-    for (GrowBuf *b : { &ctx->d_ws, &ctx->d_arena, &ctx->h_pinned, &ctx->d_frames, &ctx->d_keep, &ctx->d_ssim, &ctx->d_target }) b->release();
+    for (GrowBuf *b : { &ctx->d_ws, &ctx->d_arena, &ctx->h_pinned, &ctx->d_frames, &ctx->d_keep, &ctx->d_ssim, &ctx->d_target, &ctx->d_index }) b->release();
     if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
     if (ctx->h_progress) (void)hipHostFree(ctx->h_progress);
     if (ctx->h_seg_words) (void)hipHostFree(ctx->h_seg_words);
@@ -1192,6 +1297,13 @@ static int batch_host_one(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *im
     const auto ta0 = std::chrono::steady_clock::now();
     int rc = ctx->d_arena.grow(w.lay.total, 8);
     if (rc == PNGLOSS_SUCCESS) rc = ctx->h_pinned.grow(w.lay.mirrored, 8);
+    if (rc == PNGLOSS_SUCCESS && zs && measure.indexed) {
+        std::vector<uint32_t> width(n), height(n);
+        for (size_t i = 0; i < n; i++) { width[i] = images[i].width; height[i] = images[i].height; }
+        w.indexed = true;
+        w.ilay = pl_index_layout(width, height, sizeof(PlIndexJob), sizeof(PliRecord));
+        rc = ctx->d_index.grow(w.ilay.total, 8);
+    }
     if (rc) return rc;
     if (!ctx->copy_stream) PL_CHECK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
     if (ctx->hooks.debug_seam) std::fprintf(stderr, "pngloss_hip: host window chunk %d: arena %zu MB + pinned mirror %zu MB ready after %.1f ms\n", my_turn, w.lay.total >> 20, w.lay.mirrored >> 20, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ta0).count());
@@ -1978,6 +2090,20 @@ int pngloss_hip_multi_last_ssim(pngloss_hip_multi *m, size_t index, pngloss_hip_
     return pngloss_hip_last_ssim(m->ctx[(size_t)m->where[index].first], m->where[index].second, out);
 }
 
+int pngloss_hip_last_palette(pngloss_hip_ctx *ctx, size_t index, pngloss_hip_palette *out)
+{
+    ctx = chunk_of(ctx, index);
+    if (!ctx || !out || ctx->pending || index >= ctx->n_last || index >= ctx->palette.size()) return PNGLOSS_INVALID_ARGUMENT;
+    *out = ctx->palette[index];
+    return PNGLOSS_SUCCESS;
+}
+
+int pngloss_hip_multi_last_palette(pngloss_hip_multi *m, size_t index, pngloss_hip_palette *out)
+{
+    if (!m || index >= m->where.size()) return PNGLOSS_INVALID_ARGUMENT;
+    return pngloss_hip_last_palette(m->ctx[(size_t)m->where[index].first], m->where[index].second, out);
+}
+
 int pngloss_hip_multi_set_option(pngloss_hip_multi *m, const char *name, const char *value)
 {
     if (!m || m->ctx.empty()) return PNGLOSS_INVALID_ARGUMENT;
@@ -2278,6 +2404,12 @@ int pngloss_hip_set_option(pngloss_hip_ctx *ctx, const char *name, const char *v
         /* what "distortion", "ssim" and the target searches measure from here on: "all" (default) | "visible" (pl_distort_core.h, pl_ssim_core.h) */
         if (std::strcmp(value, "all") == 0) { ctx->opt_visible = false; return PNGLOSS_SUCCESS; }
         if (std::strcmp(value, "visible") == 0) { ctx->opt_visible = true; return PNGLOSS_SUCCESS; }
+        return PNGLOSS_INVALID_ARGUMENT;
+    }
+    if (std::strcmp(name, "indexed") == 0) {
+        /* the calls that return zlib streams also try colour type 3 from here on (pl_index.hip, window_index): "on" | "off" (default) */
+        if (std::strcmp(value, "on") == 0) { ctx->opt_indexed = true; return PNGLOSS_SUCCESS; }
+        if (std::strcmp(value, "off") == 0) { ctx->opt_indexed = false; return PNGLOSS_SUCCESS; }
         return PNGLOSS_INVALID_ARGUMENT;
     }
     if (std::strcmp(name, "ssim") == 0) {

@@ -1,6 +1,6 @@
 /*
  * pl_layout.h -- every carve-up of a buffer the host shim makes, as pure functions from sizes to offsets: the batch workspace of enqueue(), the
- * arena of a host window (batch_host_one), the keep arena of the distortion measurement, the tables of the SSIM measurement, the read side's workspace and frame arena
+ * arena of a host window (batch_host_one), the keep arena of the distortion measurement, the tables of the SSIM measurement, the index workspace of the option "indexed", the read side's workspace and frame arena
  * (png_decode_body), and the size a buffer is regrown to.
  * Internal.
  *
@@ -14,6 +14,7 @@
 
 #include "pl_plan.h"
 #include "pl_pngread_core.h"
+#include "pl_index_core.h"
 
 #include <cstdint>
 #include <cstring>
@@ -210,6 +211,43 @@ struct PlSizeRecord {
 };
 constexpr size_t PLL_SIZE_RECORD = 24;                 /* sizeof(PlSizeRecord), sizeof(dfl_size_record) */
 static_assert(sizeof(PlSizeRecord) == PLL_SIZE_RECORD, "PlSizeRecord has no padding");
+
+/* ================================================================================================ the index workspace (option "indexed": window_deflate) */
+
+/* The PlIndexJob table at 0; the counters and the palette records of all images back to back (`zeroed` bytes from `counts`: one memset to 0); the
+ * tables of all images back to back (`tables_bytes` from `tables`: one memset to 0xFF, PLI_EMPTY in every slot); then per image with pixels its
+ * filter type bytes and its index rows, as the deflate stage reads scanlines: rows `pitch` bytes apart, the pitch a multiple of 16 as the emit
+ * stage's (pl_window_layout).  Every image gets its rows, eligible or not: which ones are is known only after the batch has run, and a buffer that
+ * cannot be had has to fail the call before anything is enqueued. */
+struct PlIndexImage { size_t table, ids, rows; uint32_t pitch; };
+struct PlIndexLayout {
+    size_t jobs = 0, counts = 0, records = 0, zeroed = 0, tables = 0, tables_bytes = 0, total = 0;
+    std::vector<PlIndexImage> im;
+};
+
+/* job_bytes, record_bytes: sizeof(PlIndexJob), sizeof(PliRecord) */
+inline PlIndexLayout pl_index_layout(const std::vector<uint32_t> &width, const std::vector<uint32_t> &height, size_t job_bytes, size_t record_bytes)
+{
+    PlIndexLayout l;
+    const size_t n = width.size(), n1 = n ? n : 1;
+    auto take = [&](size_t bytes) { size_t at = l.total; l.total = pl_align_up(l.total + bytes, PLL_ALIGN); return at; };
+    l.im.resize(n);
+    l.jobs = take(job_bytes * n1);
+    l.counts = take(sizeof(uint32_t) * n1);
+    l.records = take(record_bytes * n1);
+    l.zeroed = l.total - l.counts;
+    l.tables_bytes = sizeof(uint64_t) * PLI_SLOTS * n1;
+    l.tables = take(l.tables_bytes);
+    for (size_t i = 0; i < n; i++) {
+        PlIndexImage &m = l.im[i];
+        const bool px = width[i] && height[i];
+        m.table = l.tables + sizeof(uint64_t) * PLI_SLOTS * i;
+        m.pitch = px ? (uint32_t)pl_align_up(width[i], 16) : 0;
+        m.ids = take(px ? height[i] : 0);
+        m.rows = take((size_t)m.pitch * (px ? height[i] : 0));
+    }
+    return l;
+}
 
 /* ================================================================================================ the read side (png_decode_body) */
 

@@ -100,6 +100,23 @@ class Ssim(C.Structure):
         return ssim_mean(self, channel_mask)
 
 
+class Palette(C.Structure):
+    """pngloss_hip_palette: what the option "indexed" decided for one image and from which numbers.  entries == 0: written as truecolour; else the
+    stream is colour type 3 and rgb[:entries] / alpha[:trns_entries] are its PLTE / tRNS payloads.  colors: 257 = more than 256."""
+    _fields_ = [("entries", C.c_uint32), ("trns_entries", C.c_uint32), ("rgb", (C.c_uint8 * 3) * 256), ("alpha", C.c_uint8 * 256),
+                ("truecolor_bytes", C.c_uint64), ("indexed_bytes", C.c_uint64), ("colors", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def plte(self):
+        return bytes(bytearray(self.rgb)[: 3 * self.entries])
+
+    def trns(self):
+        return bytes(bytearray(self.alpha)[: self.trns_entries])
+
+    def as_dict(self):
+        return dict(entries=self.entries, trns_entries=self.trns_entries, plte=self.plte(), trns=self.trns(), truecolor_bytes=self.truecolor_bytes,
+                    indexed_bytes=self.indexed_bytes, colors=self.colors)
+
+
 class ImagePair(C.Structure):
     _fields_ = [("d_a", C.c_void_p), ("d_b", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32)]
 
@@ -159,6 +176,14 @@ STRUCTS = {
     "pngloss_hip_ssim": Ssim, "pngloss_hip_target": Target, "pngloss_hip_target_report": TargetReport, "pngloss_hip_target2": Target2,
     "pngloss_hip_size_target": SizeTarget, "pngloss_hip_size_report": SizeReport, "pngloss_hip_png_source": PngSource,
     "pngloss_hip_png_zsource": PngZSource,
+}
+
+#: the same two tables for include/pngloss_hip_indexed.h, the extension header of the option "indexed" (tests/test_index_host.py holds them
+#: against that header the way tests/test_abi.py holds STRUCTS and PROTOTYPES against pngloss_hip.h)
+INDEXED_STRUCTS = {"pngloss_hip_palette": Palette}
+INDEXED_PROTOTYPES = {
+    "pngloss_hip_last_palette": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(Palette)]),
+    "pngloss_hip_multi_last_palette": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(Palette)]),
 }
 
 
@@ -325,7 +350,7 @@ def hip_lib():
                 except ImportError:
                     pass
             lib = _load(os.environ.get("PNGLOSS_HIP_LIBNAME", "libpngloss_hip.so"))
-            for name, (ret, args) in PROTOTYPES.items():
+            for name, (ret, args) in {**PROTOTYPES, **INDEXED_PROTOTYPES}.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = ret, args
             _hip = lib
@@ -559,15 +584,18 @@ class HipContext:
                partial_ok=True)
         return outs, filts, _scanlines_back(lines, ids, rows)
 
-    def run_host_zlib(self, arrays, strength=19, bleed=2, want_filters=True, stream_only=False):
+    def run_host_zlib(self, arrays, strength=19, bleed=2, want_filters=True, stream_only=False, want_results=False):
         """pngloss_hip_optimize_batch_host_zlib: like run_host, plus per image (color_type, zlib stream bytes, blocks).
-        stream_only: PNGLOSS_HIP_Z_STREAM_ONLY -- the returned pixel arrays are then the unmodified inputs."""
+        stream_only: PNGLOSS_HIP_Z_STREAM_ONLY -- the returned pixel arrays are then the unmodified inputs.  want_results: a fourth element, the
+        result dicts run_host returns.  With set_option("indexed", "on") a colour type may be 3; palette(index) then has the PLTE / tRNS payloads."""
         outs, filts, imgs = _host_images(arrays, want_filters)
         zs, bufs = _zstreams(self._lib, _shapes(outs), stream_only)
         n = len(outs)
-        _check(self._lib.pngloss_hip_optimize_batch_host_zlib(self._ctx, imgs, n, strength, bleed, _array(Result, n), zs), "optimize_batch_host_zlib",
+        res = _array(Result, n)
+        _check(self._lib.pngloss_hip_optimize_batch_host_zlib(self._ctx, imgs, n, strength, bleed, res, zs), "optimize_batch_host_zlib",
                partial_ok=True)
-        return outs, filts, _zstreams_back(zs, bufs)
+        out = (outs, filts, _zstreams_back(zs, bufs))
+        return out + ([_host_result_dict(r) for r in res[:n]],) if want_results else out
 
     def run_target(self, images, target, bleed=2, stream=0):
         """pngloss_hip_optimize_batch_target: images as for run(); every image ends up as run() at its chosen strength leaves it.  Synchronous.
@@ -689,6 +717,13 @@ class HipContext:
         _check(self._lib.pngloss_hip_last_ssim(self._ctx, index, C.byref(r)), "last_ssim")
         return r
 
+    def palette(self, index=0):
+        """pngloss_hip_last_palette: the Palette of image `index` of the last finished run_host_zlib, which must have run with
+        set_option("indexed", "on") -- otherwise, for an index out of range and while a batch is pending the call fails (pngloss_error 4)."""
+        r = Palette()
+        _check(self._lib.pngloss_hip_last_palette(self._ctx, index, C.byref(r)), "last_palette")
+        return r
+
     def compare(self, pairs, stream=0):
         """pngloss_hip_compare_batch: pairs = sequence of (d_a_ptr, d_b_ptr, width, height), device-resident RGBA8; returns one Distortion per pair
         (b against a).  Synchronous."""
@@ -786,12 +821,27 @@ class HipMulti:
         _check(self._lib.pngloss_hip_multi_last_ssim(self._m, index, C.byref(r)), "multi_last_ssim")
         return r
 
+    def palette(self, index=0):
+        """pngloss_hip_multi_last_palette: the Palette of arrays[index] of the last run_host_zlib, whichever context it went to"""
+        r = Palette()
+        _check(self._lib.pngloss_hip_multi_last_palette(self._m, index, C.byref(r)), "multi_last_palette")
+        return r
+
     def run_host(self, arrays, strength=19, bleed=2, want_filters=True):
         outs, filts, imgs = _host_images(arrays, want_filters)
         n = len(outs)
         res = _array(Result, n)
         _check(self._lib.pngloss_hip_multi_optimize_batch_host(self._m, imgs, n, strength, bleed, res, None, None), "multi_optimize_batch_host", partial_ok=True)
         return outs, filts, [_host_result_dict(r) for r in res[:n]]
+
+    def run_host_zlib(self, arrays, strength=19, bleed=2, want_filters=True):
+        """pngloss_hip_multi_optimize_batch_host with streams: (outs, filters, results, streams), streams as HipContext.run_host_zlib returns them"""
+        outs, filts, imgs = _host_images(arrays, want_filters)
+        n = len(outs)
+        res = _array(Result, n)
+        zs, bufs = _zstreams(self._lib, _shapes(outs))
+        _check(self._lib.pngloss_hip_multi_optimize_batch_host(self._m, imgs, n, strength, bleed, res, None, zs), "multi_optimize_batch_host", partial_ok=True)
+        return outs, filts, [_host_result_dict(r) for r in res[:n]], _zstreams_back(zs, bufs)
 
     def run_host_target(self, arrays, target, bleed=2, want_filters=True, emit=None, stream_only=False):
         """pngloss_hip_multi_optimize_batch_host_target on a list of (H, W, 4) uint8 arrays.  emit: None, "scanlines" or "zlib".  Returns
