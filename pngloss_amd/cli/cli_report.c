@@ -1,0 +1,55 @@
+/* cli_report.c -- the lines about one written file (cli_report.h). */
+#include "cli_report.h"
+
+#include <stdio.h>
+
+unsigned cli_stored_channel_mask(unsigned bytes_per_pixel)
+{
+    return bytes_per_pixel == 1 ? 0x2u : bytes_per_pixel == 2 ? 0xAu : bytes_per_pixel == 3 ? 0x7u : 0xFu;
+}
+
+void cli_report_distortion(char *line, size_t cap, const pngloss_hip_distortion *d, unsigned bytes_per_pixel, bool visible)
+{
+    if (!d->changed_pixels && visible) { snprintf(line, cap, "  distortion (visible): none, %llu visible pixels\n", (unsigned long long)d->pixels); return; }
+    if (!d->changed_pixels) { snprintf(line, cap, "  distortion: none (lossless)\n"); return; }
+    const unsigned mask = cli_stored_channel_mask(bytes_per_pixel);
+    unsigned largest = 0;
+    for (int c = 0; c < 4; c++)
+        if ((mask >> c & 1u) && d->max_abs[c] > largest) largest = d->max_abs[c];
+    snprintf(line, cap, visible ? "  distortion (visible): PSNR %.2f dB, %llu of %llu visible pixels changed, largest channel error %u\n"
+                                : "  distortion: PSNR %.2f dB, %llu of %llu pixels changed, largest channel error %u\n", pngloss_hip_psnr_db(d, mask),
+             (unsigned long long)d->changed_pixels, (unsigned long long)d->pixels, largest);
+}
+
+void cli_report_ssim(char *line, size_t cap, const pngloss_hip_ssim *r, enum cli_search search, unsigned bytes_per_pixel, bool visible)
+{
+    if (!r) {
+        snprintf(line, cap, "%s", search == CLI_SEARCH_SIZE ? "  ssim: not measured (the size search keeps no SSIM record)\n"
+                                : search == CLI_SEARCH_QUALITY ? "  ssim: not measured (a strength search measures it only with --target-ssim)\n" : "");
+        return;
+    }
+    if (!r->windows) { snprintf(line, cap, "%s", visible ? "  ssim (visible): not measured (no 8x8 window with a visible pixel)\n" : "  ssim: not measured (smaller than one 8x8 window)\n"); return; }
+    const unsigned mask = cli_stored_channel_mask(bytes_per_pixel);
+    int32_t worst = 65536;
+    for (int c = 0; c < 4; c++)
+        if ((mask >> c & 1u) && r->min_q16[c] < worst) worst = r->min_q16[c];
+    snprintf(line, cap, visible ? "  ssim (visible): mean %.4f, worst window %.4f, %llu windows with visible pixels\n" : "  ssim: mean %.4f, worst window %.4f, %llu windows\n",
+             pngloss_hip_ssim_mean(r, mask), (double)worst / 65536.0, (unsigned long long)r->windows);
+}
+
+void cli_report_strength(char *line, size_t cap, unsigned strength, unsigned probes)
+{
+    snprintf(line, cap, "  strength %u chosen in %u probes\n", strength, probes);
+}
+
+void cli_report_indexed(char *line, size_t cap, const pngloss_hip_palette *p)
+{
+    snprintf(line, cap, "  indexed: %u colours, %llu bytes of image data and %llu of palette against %llu bytes as truecolour\n", p->colors,
+             (unsigned long long)p->indexed_bytes, (unsigned long long)(12u + 3u * p->entries + (p->trns_entries ? 12u + p->trns_entries : 0u)),
+             (unsigned long long)p->truecolor_bytes);
+}
+
+void cli_report_budget_missed(char *line, size_t cap, const char *name, size_t budget, size_t written, unsigned strength)
+{
+    snprintf(line, cap, "  warning: %s: budget of %zu bytes not reached, wrote %zu bytes at strength %u\n", name, budget, written, strength);
+}

@@ -1,0 +1,36 @@
+/* cli_report.h -- the lines the pngloss tool prints about one written file, formatted from the library's plain records into the caller's buffer
+ * (each ends in a newline; a line that does not fit is cut, as every message of the tool is).  tests/c/cli_report_host.c compares them with the
+ * Python mirrors of the GPU tests on the CPU. */
+#ifndef PNGLOSS_AMD_CLI_REPORT_H
+#define PNGLOSS_AMD_CLI_REPORT_H
+
+#include <stdbool.h>
+#include <stddef.h>
+
+#include "../../include/pngloss_hip.h"
+#include "../../include/pngloss_hip_indexed.h"
+#include "cli_options.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* the channels a result of bytes_per_pixel 1, 2, 3, 4 stores, as pngloss_hip_psnr_db and pngloss_hip_ssim_mean take them (gray is the G channel) */
+unsigned cli_stored_channel_mask(unsigned bytes_per_pixel);
+
+/* --distortion.  visible: the record is over premultiplied channels and `pixels` counts the visible ones */
+void cli_report_distortion(char *line, size_t cap, const pngloss_hip_distortion *d, unsigned bytes_per_pixel, bool visible);
+
+/* --ssim: mean and worst window over the stored channels.  r == NULL: the file has no record; the line then says why the search kept none, and
+ * is empty where there was no search */
+void cli_report_ssim(char *line, size_t cap, const pngloss_hip_ssim *r, enum cli_search search, unsigned bytes_per_pixel, bool visible);
+
+/* -v: what a search chose; what --indexed decided; and the warning of a --target-size budget that -s did not reach */
+void cli_report_strength(char *line, size_t cap, unsigned strength, unsigned probes);
+void cli_report_indexed(char *line, size_t cap, const pngloss_hip_palette *p);
+void cli_report_budget_missed(char *line, size_t cap, const char *name, size_t budget, size_t written, unsigned strength);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -68,8 +68,9 @@ int main(int argc, char **argv)
         for (size_t i = 0; i < rb; i++)
             filt[y * rb + i] = (unsigned char)(row[i] - predict(f, i >= (size_t)ch ? row[i - ch] : 0, up ? up[i] : 0, (up && i >= (size_t)ch) ? up[i - ch] : 0));
     }
-    png_stream_image si = { W, H, ctype, ids, filt, rb, img.gamma,
-                            img.output_color != RWPNG_GAMA_ONLY && img.output_color != RWPNG_NONE, img.output_color == RWPNG_SRGB, img.chunks, 0 };
+    png_stream_image si = { .width = W, .height = H, .color_type = ctype, .filter_ids = ids, .rows = filt, .pitch = rb, .gamma = img.gamma,
+                            .tag_gamma = img.output_color != RWPNG_GAMA_ONLY && img.output_color != RWPNG_NONE,
+                            .tag_srgb = img.output_color == RWPNG_SRGB, .chunks = img.chunks };
     FILE *o1 = fopen(argv[2], "wb");
     size_t n1 = 0, m1 = 0;
     rc = png_stream_write(o1, &si, &n1, &m1);

@@ -61,8 +61,9 @@ int main(int argc, char **argv)
     uLongf zcap = compressBound((uLong)((rb + 1) * H)), zsize = zcap;
     unsigned char *z = malloc(zcap);
     if (compress2(z, &zsize, packed, (uLong)((rb + 1) * H), 6) != Z_OK) return 3;
-    png_stream_image si = { W, H, ctype, ids, raw, rb, img.gamma,
-                            img.output_color != RWPNG_GAMA_ONLY && img.output_color != RWPNG_NONE, img.output_color == RWPNG_SRGB, img.chunks, 0, NULL, 0 };
+    png_stream_image si = { .width = W, .height = H, .color_type = ctype, .filter_ids = ids, .rows = raw, .pitch = rb, .gamma = img.gamma,
+                            .tag_gamma = img.output_color != RWPNG_GAMA_ONLY && img.output_color != RWPNG_NONE,
+                            .tag_srgb = img.output_color == RWPNG_SRGB, .chunks = img.chunks };
     FILE *o1 = fopen(argv[2], "wb");
     size_t n1 = 0, n2 = 0;
     rc = png_stream_write(o1, &si, &n1, NULL);

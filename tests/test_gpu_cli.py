@@ -200,6 +200,39 @@ def test_batch_cli_windows_are_pipelined_without_changing_the_outputs(tmp_path):
         assert pos == sorted(pos)
 
 
+#: -v runs whose complete stderr is pinned: the plain call with both reports, the quality search, the size search, the indexed write
+VERBOSE_RUNS = [["-v", "--distortion", "--ssim"], ["-v", "--target-psnr", "35", "-s", "19", "--distortion"],
+                ["-v", "--target-size", "50%", "-s", "40", "--distortion", "--ssim"], ["-v", "--indexed"]]
+
+
+def run_verbose(tool, tmp_path):
+    """VERBOSE_RUNS on three small images of the target tests' generator, each run in a directory of its own with relative names (the messages
+    name the files as given): [{"args", "returncode", "stderr"}].  tests/golden/make_cli_verbose_stderr.py records the same from another build"""
+    from tests import util_target as T
+    out = []
+    for k, args in enumerate(VERBOSE_RUNS):
+        d = tmp_path / f"run{k}"
+        d.mkdir()
+        for name, (w, h, mode) in zip("abc", [(64, 8, 0), (33, 16, 2), (130, 6, 3)]):
+            _write_png(str(d / f"{name}.png"), T.oracle_probe(w, h, mode, 0)[0])
+        r = subprocess.run([tool] + args + ["a.png", "b.png", "c.png"], capture_output=True, text=True, timeout=300, cwd=d)
+        out.append(dict(args=args, returncode=r.returncode, stderr=r.stderr))
+    return out
+
+
+@pytest.mark.skipif(not os.path.exists(OUR_CLI), reason="pngloss_amd/cli/pngloss is not built (no libpng headers on this box)")
+def test_verbose_stderr_is_what_the_tool_printed_before_its_main_file_was_split(tmp_path):
+    """Every line of a -v run, in order, and the exit code: the per-line tests (tests/test_cli_report_host.py) do not see the order.  Recorded on
+    an MI355X from the tool of the commit before the split (tests/golden/cli_verbose_stderr.json names it)."""
+    import json
+    with open(os.path.join(U.GOLDEN, "cli_verbose_stderr.json")) as fh:
+        want = json.load(fh)["runs"]
+    got = run_verbose(OUR_CLI, tmp_path)
+    assert [r["args"] for r in want] == VERBOSE_RUNS
+    for g, w in zip(got, want):
+        assert (g["returncode"], g["stderr"]) == (w["returncode"], w["stderr"]), g["args"]
+
+
 @needs_our_cli
 def test_batch_cli_gpu_read_writes_the_same_files(tmp_path):
     """--gpu-read: chunk walk + inflate on the decode threads, inverse filters + expansion to RGBA8 on the device.  Files of
