@@ -3,7 +3,7 @@
  * which image (pngloss_hip_multi_*), which images of a searched batch run together at their chosen strength (the host forms of the searches), and
  * what a call returns when its parts returned different codes.  Internal.
  *
- * Plain C++ without HIP, like pl_plan.h: pl_host.hip carries these out (threads, gathers, scatters), and tests/c/deal_host.cpp compiles the same
+ * Plain C++ without HIP, like pl_plan.h: pl_host_window.hip carries these out (threads, gathers, scatters), and tests/c/deal_host.cpp compiles the same
  * header with g++ so that the CPU suite pins them (tests/test_deal_host.py).
  */
 #ifndef PL_DEAL_H

@@ -10,7 +10,7 @@
  *   per level:    dfl_keys -> radix sort of (key, position) -> dfl_flags + max-scan -> dfl_match   (all position-parallel)
  *   dfl_encode    one workgroup per deflate block (pl_deflate_coop.h): parse, Huffman codes, bits; byte-aligned outputs
  *   dfl_gather    compacts the block outputs into one buffer per image
- * or, to learn only how large the streams would be (pl_deflate_measure: the size search of pl_host.hip), after the same search levels:
+ * or, to learn only how large the streams would be (pl_deflate_measure: the size search of pl_host_search.hip), after the same search levels:
  *   dfl_encode    in DFL_MODE_MEASURE: everything but the bits, which are counted; no output arena exists
  *   dfl_sizes     one wave per image: its blocks' results folded into one PlSizeRecord; one copy of n records is the only download
  *

@@ -27,7 +27,7 @@
 #define PLD_HD inline
 #endif
 
-/* the record of one image as the kernel writes it: the layout of pngloss_hip_distortion (include/pngloss_hip.h; pl_host.hip asserts it) */
+/* the record of one image as the kernel writes it: the layout of pngloss_hip_distortion (include/pngloss_hip.h; pl_host_ctx.h asserts it) */
 struct PlDistortRecord {
     uint64_t pixels, changed_pixels;
     uint64_t sq_err[4];

@@ -1,6 +1,6 @@
 /*
  * pl_index.hip -- the indexed-colour write side on the device (gfx950; option "indexed", include/pngloss_hip.h).  Three kernels behind the
- * pipeline of pl_host.hip, each one launch for its batch (blockIdx.y or .x = image); the logic is pl_index_core.h's.
+ * pipeline of pl_host_window.hip:window_index, each one launch for its batch (blockIdx.y or .x = image); the logic is pl_index_core.h's.
  *
  *   pl_index_count    every image: its distinct RGBA words into a per-image open-addressing table, with an early exit.  A workgroup takes chunks
  *                     of kChunk pixels; before each it re-reads the image's counter and leaves once that is past 256, and so does every lane

@@ -4,10 +4,10 @@
  * (png_decode_body), and the size a buffer is regrown to.
  * Internal.
  *
- * Plain C++17 without HIP, like pl_plan.h: pl_host.hip turns the offsets into pointers, copies and launches, and tests/c/layout_host.cpp compiles
+ * Plain C++17 without HIP, like pl_plan.h: the pl_host*.hip files turn the offsets into pointers, copies and launches, and tests/c/layout_host.cpp compiles
  * the same header with g++ so that the CPU suite proves alignment, disjointness and the pinned values (tests/test_layout_host.py).  The job
  * structs live in headers that include the HIP runtime, so their sizes come in as arguments; what the header states about the device side
- * itself (PLL_*) is pinned by static_asserts in pl_host.hip.
+ * itself (PLL_*) is pinned by static_asserts in pl_host_ctx.h.
  */
 #ifndef PL_LAYOUT_H
 #define PL_LAYOUT_H

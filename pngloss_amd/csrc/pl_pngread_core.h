@@ -6,7 +6,7 @@
  *     1/2/4 bits -> 8 bits, tRNS -> alpha; rwpng.c:239-242), filler alpha 255 (:242), png_set_strip_16 = the HIGH byte of every
  *     16-bit sample (:252-254; tRNS keys are compared on the full 16 bits first, libpng expands before it strips),
  *     png_set_gray_to_rgb (:256-258).  No gamma correction is applied to pixels by that reader (the gamma is only recorded).
- * Shared by the HIP kernel (pl_pngread.hip), its host set-up (pl_host.hip), the CPU checks of tests/c/pngread_host.cpp and
+ * Shared by the HIP kernel (pl_pngread.hip), its host set-up (pl_host_read.hip), the CPU checks of tests/c/pngread_host.cpp and
  * tests/c/pngread_adam7_host.cpp (test infrastructure) and -- the geometry part, which is plain C -- the command line tool's reader.
  */
 #ifndef PL_PNGREAD_CORE_H

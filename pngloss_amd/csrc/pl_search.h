@@ -5,7 +5,7 @@
  *
  * Plain C++ without HIP types, like pl_target.h and pl_size.h: the copies are SYMBOLIC here (image, source region, destination region), so that
  * tests/c/search_host.cpp simulates the device with a tag per region and drives whole searches on the CPU (tests/test_search_host.py).
- * pl_host.hip:target_search / size_search call these functions for every decision, turn the moves into pl_move jobs (one table = one launch) and
+ * pl_host_search.hip:target_search / size_search call these functions for every decision, turn the moves into pl_move jobs (one table = one launch) and
  * do the device work in between: the batches, the measurements, the reports.
  *
  * What the functions keep true:

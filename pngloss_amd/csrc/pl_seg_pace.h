@@ -4,7 +4,7 @@
  * nothing to launch (stall watchdog, back-off), what it reports, which CPU the launch thread takes and whether the caller's stream waits on the device.
  * Internal.
  *
- * Plain C++17 without HIP: pl_host.hip (seg_worker_main, run_seg_engine) makes the calls -- launches, events, yield and sleep -- and asks here what to do;
+ * Plain C++17 without HIP: pl_host_seg.hip (seg_worker_main, run_seg_engine) makes the calls -- launches, events, yield and sleep -- and asks here what to do;
  * tests/c/pace_host.cpp compiles the same header with g++ and drives it with a scripted device (tests/test_pace_host.py).  Everything is inline and fixed
  * in size: the thread issues four launches every 45 - 100 us.  Nothing here changes results: every pace gives the reference's bytes.
  */

@@ -4,7 +4,7 @@
  *
  * Plain C++ without HIP types, like pl_target.h, whose search this mirrors in the other direction: everything the search DECIDES is here, so that
  * tests/c/size_host.cpp drives it on the CPU.  pl_search.h keeps the books of a whole search on top of these functions (what is kept, which
- * regions are copied where), and pl_host.hip does what the two say: it runs the groups through enqueue() / finish() with emit descriptors,
+ * regions are copied where), and pl_host_search.hip does what the two say: it runs the groups through enqueue() / finish() with emit descriptors,
  * measures the emitted scanlines with pl_deflate_measure and carries out the moves with pl_move.
  *
  * A probe is ACCEPTED when its status is 0 and its stream -- the complete zlib stream, 78 DA ... Adler-32 -- has at most max_bytes bytes.

@@ -31,7 +31,7 @@
 #define PLS_HD inline
 #endif
 
-/* the record of one image as the kernel writes it: the layout of pngloss_hip_ssim (include/pngloss_hip.h; pl_host.hip asserts it) */
+/* the record of one image as the kernel writes it: the layout of pngloss_hip_ssim (include/pngloss_hip.h; pl_host_ctx.h asserts it) */
 struct PlSsimRecord {
     uint64_t windows;
     int64_t sum_q16[4];

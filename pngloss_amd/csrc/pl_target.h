@@ -5,7 +5,7 @@
  * Plain C++ without HIP types, like pl_plan.h: everything the search DECIDES is here -- whether a target is valid, whether a probe is accepted,
  * which strength an image probes next and which one it ends with, which images of a round share a batch, and where the search arena keeps what --
  * so that tests/c/target_host.cpp drives it on the CPU.  pl_search.h keeps the books of a whole search on top of these functions (what is kept,
- * which regions are copied where), and pl_host.hip does what the two say: it runs the groups through enqueue() / finish(), measures with
+ * which regions are copied where), and pl_host_search.hip does what the two say: it runs the groups through enqueue() / finish(), measures with
  * pl_distort and carries out the moves with pl_move (pl_target.hip).
  *
  * The rule, per image (include/pngloss_hip.h states it for callers).  PSNR is not monotone in the strength, so the result is defined by this

@@ -2,7 +2,7 @@
  * pl_target.hip -- the one kernel pngloss_hip_optimize_batch_target adds (gfx950): pl_move, a batched copy.  blockIdx.y selects a job {src, dst,
  * bytes} (pl_move_core.h); one launch saves the originals of a batch into the search arena, puts originals back in front of a probe, stashes the
  * accepted probes' pixels and row filters, or puts the kept results back at the end.  HBM-bound, shaped like pl_keep (pl_distort.hip).
- * The search itself is pl_target.h (host decisions) and pl_host.hip (the rounds); measuring is pl_distort.  No reference equivalent.
+ * The search itself is pl_target.h (host decisions) and pl_host_search.hip (the rounds); measuring is pl_distort.  No reference equivalent.
  */
 #include "pl_target_dev.h"
 

@@ -52,6 +52,15 @@ def test_product_code_never_touches_the_oracle():
     assert "port_" not in text
 
 
+def _host_text():
+    """the host shim as one text: its private header, then every pl_host*.hip (by glob: a file added later is covered without an edit here)"""
+    import glob
+    csrc = os.path.join(U.ROOT, "pngloss_amd", "csrc")
+    files = [os.path.join(csrc, "pl_host_ctx.h")] + sorted(glob.glob(os.path.join(csrc, "pl_host*.hip")))
+    assert len(files) >= 7 and os.path.join(csrc, "pl_host.hip") in files, files
+    return "\n".join(open(f).read() for f in files)
+
+
 def test_no_environment_variable_of_the_shipped_library_changes_results():
     """Round 6 (the round-5 review's item): the one hook that changed results -- "candidate f wins every row", PNGLOSS_HIP_FORCE_FILTER, a debugging aid of rounds 1-3 -- is a
     BUILD flag now (-DPL_DEBUG_FORCE_FILTER=f): the shipped library does not know the variable, its version string does not announce a debugging build, and the
@@ -60,19 +69,22 @@ def test_no_environment_variable_of_the_shipped_library_changes_results():
     so = open(os.path.join(U.ROOT, "pngloss_amd", "csrc", "libpngloss_hip.so"), "rb").read()
     assert b"PNGLOSS_HIP_FORCE_FILTER" not in so
     assert b"DEBUGGING BUILD" not in P.hip_lib().pngloss_hip_version()
-    host = open(os.path.join(U.ROOT, "pngloss_amd", "csrc", "pl_host.hip")).read()
-    body = host[host.index("static PlHooks from_env()"):]
-    body = body[body.index("return h;"):]              # (everything behind the hooks' reader)
-    import re
+    host = _host_text()
+    a = host.index("static PlHooks from_env()")
+    b = host.index("return h;", a)
+    assert host.count("static PlHooks from_env()") == 1 and 'getenv("PNGLOSS_HIP_DEBUG")' in host[a:b]
+    body = host[:a] + host[b:]                         # (every host file, without the hooks' reader)
     left = set(re.findall(r'getenv\("([A-Z_]+)"\)', body))
+    assert "getenv" not in re.sub(r'getenv\("[A-Z_]+"\)', "", body)        # (no read of a name the scan above cannot see)
     assert left == {"PNGLOSS_HIP_ENGINE", "PNGLOSS_DEVICES"}, left
     # (the launch thread's rules, which this file held until they moved: they read the hooks they are handed, never the environment)
     assert "getenv" not in open(os.path.join(U.ROOT, "pngloss_amd", "csrc", "pl_seg_pace.h")).read()
 
 
 def _context_mode_toggles(host):
-    """what in the text of pl_host.hip tells a batch its mode through the context: lines outside pngloss_hip_set_option that assign to one of the caller's
-    measuring options, and members of struct pngloss_hip_ctx that are a call's argument (BatchCall has them)"""
+    """what in the text of the host files tells a batch its mode through the context: lines outside pngloss_hip_set_option that assign to one of the caller's
+    measuring options (or hand one to something that could: a non-const reference, as the option parser takes it), and members of struct pngloss_hip_ctx that
+    are a call's argument (BatchCall has them)"""
     def body(text, head):
         start = text.index("{", text.index(head))
         depth, k = 0, start
@@ -84,7 +96,8 @@ def _context_mode_toggles(host):
 
     a, b = body(host, "int pngloss_hip_set_option(")
     outside = host[:a] + re.sub(r"[^\n]", " ", host[a:b]) + host[b:]
-    found = [line.strip() for line in outside.splitlines() if re.search(r"(->|\.)\s*opt_(distortion|ssim|visible)\s*=(?!=)", line)]
+    found = [line.strip() for line in outside.splitlines() if re.search(r"(->|\.)\s*opt_(distortion|ssim|visible)\s*=(?!=)", line)
+             or re.search(r"\bon_off\s*\(", line)]
     a, b = body(host, "struct pngloss_hip_ctx {")
     struct = re.sub(r"/\*.*?\*/", "", host[a:b], flags=re.S)
     found += ["member " + m for m in re.findall(r"\b(sync_call|three_groups_ok|want_progress)\b", struct)]
@@ -94,20 +107,26 @@ def _context_mode_toggles(host):
 def test_a_batch_gets_its_mode_as_an_argument_not_through_the_context():
     """The caller's measuring options are assigned by pngloss_hip_set_option and nowhere else, and what one call asks of a batch (a synchronous caller, three
     launch groups, the progress word) is no member of the context: enqueue takes it as an argument.  The scan reports an old toggle line put back."""
-    host = open(os.path.join(U.ROOT, "pngloss_amd", "csrc", "pl_host.hip")).read()
-    assert len(re.findall(r"ctx->opt_(?:distortion|ssim|visible) = (?:true|false);", host)) == 6      # (the six assignments of pngloss_hip_set_option: the scan has something to skip)
+    host = _host_text()
+    # (what pngloss_hip_set_option does to the three options, so that the scan has something to skip: "measure" assigns twice, "distortion" and "ssim" go through
+    #  the one on/off parser of that function, a lambda in its body, which assigns through a reference)
+    assert len(re.findall(r"ctx->opt_visible = (?:true|false);", host)) == 2
+    assert len(re.findall(r"return on_off\(ctx->opt_(?:distortion|ssim)\);", host)) == 2
+    assert len(re.findall(r"\boption = ", host)) == 1 and "auto on_off = [value](bool &option) {" in host
     assert _context_mode_toggles(host) == []
     at = host.index("rc = enqueue(ctx, descs.data(), n, call);")
     for old in ("ctx->opt_distortion = true; ctx->opt_ssim = want_ssim;", "p->opt_visible = ctx->opt_visible;", "if (ctx) ctx->opt_visible = false;",
                 "c.opt_ssim = opt_ssim;", "ctx->opt_distortion = ctx->opt_ssim = false;"):
         assert _context_mode_toggles(host[:at] + old + "\n" + host[at:]) == [old], old
+    old = "on_off(ctx->opt_ssim);"                     # (the parser's way to assign, were it reachable outside the function)
+    assert _context_mode_toggles(host[:at] + old + "\n" + host[at:]) == [old]
     at = host.index("hipStream_t copy_stream = nullptr;")
     assert _context_mode_toggles(host[:at] + "bool sync_call = false;\n    " + host[at:]) == ["member sync_call"]
 
 
 def test_result_record_slots_are_named_in_one_header():
-    """pl_result.h is the one map of the per-image result record: elsewhere no subscript of a record starts with a number, and pl_host.hip reads
-    copied records and fills engine_info through the header's names only (tests/test_result_host.py pins the decoder)."""
+    """pl_result.h is the one map of the per-image result record: elsewhere no subscript of a record starts with a number, and the host files read
+    copied records and fill engine_info through the header's names only (tests/test_result_host.py pins the decoder)."""
     import glob
     csrc = os.path.join(U.ROOT, "pngloss_amd", "csrc")
     files = sorted(glob.glob(os.path.join(csrc, "*.h")) + glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(U.ROOT, "tests", "c", "*.cpp")))
@@ -117,7 +136,8 @@ def test_result_record_slots_are_named_in_one_header():
             continue
         hits = re.findall(r".*result\[\s*\d.*", open(fn).read())
         assert not hits, (fn, hits[:3])
-    host = open(os.path.join(csrc, "pl_host.hip")).read()
+    host = _host_text()
+    assert "pl_result_decode(r, ctx->engine[i], &res, info);" in host      # (the records the two scans are about are in the text)
     assert not re.findall(r".*\br\[\s*\d.*", host)
     assert not re.findall(r".*\binfo\[\s*\d.*", host)
 
