@@ -2,7 +2,7 @@
  * pl_seg.hip -- kernels and launcher of the SEGMENT-PARALLEL row engine: one image spread over the whole MI355X.
  *
  * The algorithm, its proof obligation (the validation pass) and the kernel bodies live in pl_seg_core.h, which is also compiled
- * for the CPU by tests/c/seg_host.cpp; which launches an attempt is made of, their grids, workgroup sizes and LDS bytes, and what workgroup blockIdx.x of
+ * for the CPU by tests/c/seg_host.cpp; which launches an attempt is made of, their grids and workgroup sizes (their LDS bytes: pl_seg_lds.h), and what workgroup blockIdx.x of
  * each grid does live in pl_seg_launch.h, which the CPU harness runs too.  Here: the four gfx950 kernels of one row attempt, blockIdx.y = image of the batch,
  *
  *   seg_k_ctl     5 x 4 candidate workgroups (each a quarter of a candidate's decision tables) + 1 image-wide + W/256 commit workgroups
@@ -124,16 +124,14 @@ hipError_t chain_attr()
     static std::atomic<unsigned> done_chain{ 0 }, done_ctl{ 0 };
     static std::atomic<unsigned> done_chain_s{ 0 };
     static std::atomic<unsigned> done_chain_u{ 0 };
-    hipError_t e = pl_lds_optin((const void *)seg_k_chain<false, SEG_CHAIN_THREADS, false>, SEG_SM_CHAIN(SEG_CHAIN_CAP + 1), done_chain);
-    if (e == hipSuccess) e = pl_lds_optin((const void *)seg_k_chain<false, SEG_CHAIN_THREADS_UNIT, true>, SEG_SM_CHAIN(SEG_CHAIN_CAP + 1), done_chain_u);
-    if (e == hipSuccess) e = pl_lds_optin((const void *)seg_k_chain<true, SEG_CHAIN_THREADS, false>, SEG_SM_CHAIN(SEG_CHAIN_CAP + 1), done_chain_s);
+    hipError_t e = pl_lds_optin((const void *)seg_k_chain<false, SEG_CHAIN_THREADS, false>, seg_lds_chain_bytes<true>(SEG_CHAIN_CAP + 1), done_chain);
+    if (e == hipSuccess) e = pl_lds_optin((const void *)seg_k_chain<false, SEG_CHAIN_THREADS_UNIT, true>, seg_lds_chain_bytes<true>(SEG_CHAIN_CAP + 1), done_chain_u);
+    if (e == hipSuccess) e = pl_lds_optin((const void *)seg_k_chain<true, SEG_CHAIN_THREADS, false>, seg_lds_chain_bytes<true>(SEG_CHAIN_CAP + 1), done_chain_s);
     static std::atomic<unsigned> done_ctl1{ 0 };
-    if (e == hipSuccess && SEG_SM_CTLVAL_V(SEG_VGRP_OF(SEG_TPARTS)) > 65536) e = pl_lds_optin((const void *)seg_k_ctl<SEG_TPARTS>, SEG_SM_CTLVAL_V(SEG_VGRP_OF(SEG_TPARTS)), done_ctl);
-    if (e == hipSuccess && SEG_SM_CTLVAL_V(SEG_VGRP_OF(SEG_TPARTS_BATCH)) > 65536) e = pl_lds_optin((const void *)seg_k_ctl<SEG_TPARTS_BATCH>, SEG_SM_CTLVAL_V(SEG_VGRP_OF(SEG_TPARTS_BATCH)), done_ctl1);
+    if (e == hipSuccess && seg_lds_ctl_bytes<SEG_TPARTS>() > 65536) e = pl_lds_optin((const void *)seg_k_ctl<SEG_TPARTS>, seg_lds_ctl_bytes<SEG_TPARTS>(), done_ctl);
+    if (e == hipSuccess && seg_lds_ctl_bytes<SEG_TPARTS_BATCH>() > 65536) e = pl_lds_optin((const void *)seg_k_ctl<SEG_TPARTS_BATCH>, seg_lds_ctl_bytes<SEG_TPARTS_BATCH>(), done_ctl1);
     return e;
 }
-static_assert(SEG_SM_REPLAY <= 65536 && SEG_SM_ENUM_NT(1024) <= 65536 && SEG_SM_ENUM_SEEDED(1024) <= 65536 && SEG_SM_ENUM_UNIT <= 65536, "these kernels are launched without an LDS opt-in");
-static_assert((SEG_TBL_WORDS + 1024 + 512) * 4 + SEG_UNIT * SEG_L * 4 * 8 <= SEG_SM_ENUM_UNIT && (SEG_TBL_WORDS + 1024 + 512) * 4 + SEG_L * 4 * 8 <= SEG_SM_ENUM_NT(512), "seg_first_body's carve fits the enumeration kernels' LDS");
 
 } // namespace
 

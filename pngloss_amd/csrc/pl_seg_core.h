@@ -307,7 +307,6 @@ struct SegAcc {
 };
 
 static_assert(sizeof(SegCtl) / 4 <= 128 && sizeof(SegAcc) / 4 <= 128, "the control kernel copies both with 128 lanes each");
-static_assert((SEG_NFILT + 1) * 256 + (sizeof(SegCtl) + 7) / 8 * 2 + (sizeof(SegAcc) + 7) / 8 * 2 + 56 <= 4 * SEG_TN, "they live in the table staging area, below the classes (and the decision behind them)");
 
 /* What the workgroups of an attempt branch on, kept INSIDE the job record (three deep, like the control blocks): the record is the first thing
  * every workgroup loads, so these fields arrive with it -- one round trip to device memory less at the head of every kernel than reading them
@@ -907,21 +906,7 @@ inline bool seg_build_params(SegParams &P, int strength, int bleed, bool force_s
  * par = attempt & 1: which copy of the control block this attempt reads.
  * ========================================================================================================================= */
 
-/* shared-memory budgets (bytes) */
-#define SEG_SM_ENUM (SEG_TBL_WORDS * 4 + 2048 + SEG_SMALL_SEGS * SEG_L * 4 * 8 + 64 + 4 * 512 * 4 + 4 * 512 * 2 + 4 * SEG_NSP * 4 + 4 * SEG_NSP * 2 + SEG_THREADS * 2 + SEG_THREADS * 4 + 64)
-/* what the enumeration kernel's bodies really carve out for NT threads (seg_enum_body is the largest: tables, pixels, split table, hash table,
- * dense ids, distinct states, exits, one slot and one key per lane): 35.5 KB at 512 threads = four workgroups per CU, 38.5 KB at 1024 */
-#define SEG_SM_ENUM_NT(nt) (SEG_TBL_WORDS * 4 + (SEG_L + 1) * 4 * 8 + 2048 + 32 + 4 * SEG_HT * 4 + 4 * SEG_HT * 2 + 4 * SEG_NSP * 4 + 4 * SEG_NSP * 2 + (nt) * 2 + (nt) * 4 + 128)
-#define SEG_SM_REPLAY (4096 + SEG_TBL_WORDS * 4 + SEG_GRP * SEG_L * 4 * 8 + SEG_GRP * 256 + SEG_GRP * SEG_PARTS * 4 * 8 + SEG_GRP * SEG_L * 16 + (SEG_GRP * SEG_L + 3) * 4 + 64)
-#ifndef SEG_WATCH_OF
-#define SEG_WATCH_OF(V) ((V) > 8 ? 2 : 8)   /* slots of exact prefix counts a validation workgroup has for the bins its undecided decisions name (a bin without a slot is counted by scanning: exact, slower, rare -- 0.01 % of the decisions are undecided at all); two for whole replay groups: with 51 KB instead of 64 a CU takes a third enumeration workgroup next to such a workgroup */
-#endif
-#define SEG_SM_POST_V(V) ((768 + ((V) + 1) * 256 + ((V) * SEG_L + 2) * 4 + 64 + 512 + 2 * ((V) * SEG_L + 2) + 2 * (V) * SEG_L + 32 + 64 + (V) * SEG_L + (V) * (SEG_L + 1) + SEG_WATCH_OF(V) * ((V) * (SEG_L + 1) + 8) + 2 * 20 * 4 + 512 + 64) * 4)   /* what seg_post_body carves out, in its order (SEG_WATCH_OF(V) slots, SEG_NBAND = 20 bands): 36.9 KB for half replay groups, 51.0 KB for whole ones (round 5: 49 KB before for half groups -- the launch that carries it was short of CUs with that much free next to the enumeration of another launch group) */
-#define SEG_SM_POST SEG_SM_POST_V(SEG_VGRP)
-#define SEG_SM_CTLVAL_V(V) (SEG_SM_CTL > SEG_SM_POST_V(V) ? SEG_SM_CTL : SEG_SM_POST_V(V))
-#define SEG_SM_CTLVAL SEG_SM_CTLVAL_V(SEG_VGRP)   /* the first launch of an attempt carries control and validation workgroups */
-#define SEG_SM_CTL ((8 + 512 + (sizeof(SegCtl) + 7) / 8 * 2 + (sizeof(SegAcc) + 7) / 8 * 2 + 56 + SEG_NFILT * (SEG_COMMIT_W + 4) * 4 + SEG_COMMIT_W * 4 + (SEG_NFILT + 1) * 256 + 16) * 4)   /* what a commit workgroup carves out (seg_ctl_commit: split table, control block + sums, decision, five tiles, err1 of both parities, spec): 33.8 KB; a candidate workgroup needs 4 x 256 + SEG_TBL_WORDS words */
-static_assert((1024 + SEG_TBL_WORDS) * 4 <= SEG_SM_CTL, "a candidate workgroup of the control kernel (histograms + table staging) fits the commit workgroups' request");
+#include "pl_seg_lds.h"      /* the shared memory of every body below: its pointers and its launch's bytes */
 
 /* bump counters of ONE segment, four bins a word (a segment has at most SEG_L * 4 = 128 decisions: a byte holds its count of any bin) -- a quarter of the
  * shared memory of a word per bin, which is what lets a CU hold three replay workgroups instead of two */
@@ -991,7 +976,6 @@ PLS_HD int seg_run_fast_f(int f, bool trx, const SegPix *px, int pstride, SegSta
                                     channels' ~35 + 35 distinct states no longer fit one wave, after four their ~17 + 17 do */
 #endif
 PLS_HD int seg_k1(int ns) { return ns <= SEG_NSP ? SEG_K1_ONE_CHUNK : SEG_K1; }
-#define SEG_HT 512
 /* K1 = the steps before the dedupe, a compile-time value: both legs of the first part -- K1 steps from every state, SEG_PL - K1 of the distinct ones -- have
  * constant counts like the parts behind them (seg_run_fast: N) */
 template <int NT, int K1>
@@ -1009,15 +993,10 @@ PLS_HD void seg_enum_body_k(const SegJob &j, const SegParams &P, const SegCtlVie
                                                                  seg_first_body.  A fresh row starts from the known state in front of pixel 0,
                                                                  which has an index like any other (boundary record = zeros): segment 0 is
                                                                  enumerated with the rest */
-    uint32_t *tw = (uint32_t *)smem;
-    SegPix *px = (SegPix *)(smem + SEG_TBL_WORDS * 4);        /* [(SEG_L + 1)][4]: slot 0 = boundary pixel x0-1 */
-    uint32_t *lut = (uint32_t *)(px + (SEG_L + 1) * 4);       /* the split table */
-    uint32_t *trflag = lut + 512;                             /* [0] some pixel of the segment is fully transparent, [1..4] distinct states per channel */
-    uint32_t *ht = trflag + 8;                                /* [4][SEG_HT] hash table: packed state or ~0 */
-    uint16_t *dense = (uint16_t *)(ht + 4 * SEG_HT);          /* [4][SEG_HT] slot -> rank among the distinct states */
-    uint32_t *uniq = (uint32_t *)(dense + 4 * SEG_HT);        /* [4][SEG_NSP] the distinct states, packed */
-    uint16_t *res = (uint16_t *)(uniq + 4 * SEG_NSP);         /* [4][SEG_NSP] exit index of each distinct state */
-    uint16_t *lslot = res + 4 * SEG_NSP;                      /* [NT] the hash slot of every lane's state (or 0xffff) */
+    typedef SegLdsEnum<NT> LDS;
+    uint32_t *tw = LDS::tw(smem), *lut = LDS::lut(smem), *trflag = LDS::trflag(smem), *ht = LDS::ht(smem), *uniq = LDS::uniq(smem);
+    SegPix *px = LDS::px(smem);
+    uint16_t *dense = LDS::dense(smem);
     const uint32_t y = cv.y;
     const SEG_AS_GLB uint32_t *row = seg_row_orig(j, y), *nab = y ? j.img + (size_t)(y - 1u) * W : nullptr, *e0g = seg_e0(j, y);
     const SegGeo G = seg_geo((int)cv.s);
@@ -1043,16 +1022,16 @@ PLS_HD void seg_enum_body_k(const SegJob &j, const SegParams &P, const SegCtlVie
         if (tid < 512) lut[tid] = vl;
         if (tid < SEG_L + 1) {
             seg_pix_split4(px + tid * 4, vp, bpp, x0 - 1 + (uint32_t)tid, W);
-            if ((bpp & 1u) == 0u && (px[tid * 4 + (bpp - 1u)].w >> 24)) PLS_ATOMIC_OR(trflag, 1u);
+            if ((bpp & 1u) == 0u && (px[tid * 4 + (bpp - 1u)].w >> 24)) PLS_ATOMIC_OR(&trflag[SEG_TF_TRANSPARENT], 1u);
         }
     }
     PLS_SYNC();
-    const bool trx = trflag[0] != 0u;
+    const bool trx = trflag[SEG_TF_TRANSPARENT] != 0u;
     if (prof) te[1] = PLS_CLOCK();
     /* -- the first SEG_K1 steps from every state, SEG_NSP states per channel at a time; neighbouring lanes mostly end in the same state,
      *    so only the first lane of a run of equal keys ("head") goes to the hash table with an atomic, the others look their key up
      *    afterwards.  Every entry index gets the DENSE id of its state: that is the segment's entry map -- */
-    uint32_t *keys = (uint32_t *)(lslot + NT);       /* [NT] state key of every lane after SEG_K1 steps, ~0 = none */
+    uint32_t *keys = LDS::keys(smem);                 /* [NT] state key of every lane after SEG_K1 steps, ~0 = none */
     SEG_AS_GLB uint16_t *dmap = j.maps + (((size_t)f * j.nseg + seg) * 4) * (size_t)P.nsp;
     for (int i0 = 0; i0 < P.ns; i0 += SEG_NSP) {
         PLS_THREADS(tid, NT) {
@@ -1076,7 +1055,7 @@ PLS_HD void seg_enum_body_k(const SegJob &j, const SegParams &P, const SegCtlVie
                 for (int probe = 0; probe < SEG_HT; probe++) {
                     const uint32_t old = PLS_ATOMIC_CAS(&ht[c * SEG_HT + h], 0xffffffffu, key);
                     if (old == 0xffffffffu) {                                     /* the representative of a new state */
-                        const uint32_t d = PLS_ATOMIC_ADD_RET(&trflag[1 + c], 1u);
+                        const uint32_t d = PLS_ATOMIC_ADD_RET(&trflag[SEG_TF_NDISTINCT + c], 1u);
                         dense[c * SEG_HT + h] = (uint16_t)(d < SEG_NSP ? d : 0xffffu);          /* more distinct states than lanes: the surplus has no id */
                         if (d < SEG_NSP) uniq[c * SEG_NSP + d] = key;
                         break;
@@ -1111,13 +1090,13 @@ PLS_HD void seg_enum_body_k(const SegJob &j, const SegParams &P, const SegCtlVie
          * for all of them, and what this phase costs is the instruction issue of the waves that have a live lane (the workgroups of a CU share its
          * four SIMDs: waves x steps is the currency, the other waves end here) */
         uint32_t Dc[NCH];
-        for (int k = 0; k < NCH; k++) Dc[k] = trflag[1 + k] < SEG_NSP ? trflag[1 + k] : SEG_NSP;
+        for (int k = 0; k < NCH; k++) Dc[k] = trflag[SEG_TF_NDISTINCT + k] < SEG_NSP ? trflag[SEG_TF_NDISTINCT + k] : SEG_NSP;
         int lc = 0, i = tid;
         uint32_t D = Dc[0];
         PLS_UNROLL
         for (int k = 0; k + 1 < NCH; k++) if (lc == k && (uint32_t)i >= Dc[k]) { i -= (int)Dc[k]; lc = k + 1; D = Dc[k + 1]; }
         const int c = c0 + lc;
-        if (tid < NCH && (uint32_t)(c0 + tid) < bpp) j.dcnt[((size_t)f * j.nseg + seg) * 4 + c0 + tid] = trflag[1 + tid] < SEG_NSP ? trflag[1 + tid] : SEG_NSP;
+        if (tid < NCH && (uint32_t)(c0 + tid) < bpp) j.dcnt[((size_t)f * j.nseg + seg) * 4 + c0 + tid] = trflag[SEG_TF_NDISTINCT + tid] < SEG_NSP ? trflag[SEG_TF_NDISTINCT + tid] : SEG_NSP;
         if ((uint32_t)c < bpp && (uint32_t)i < D) {
             const uint32_t key = uniq[lc * SEG_NSP + i];
             SegState st;
@@ -1138,7 +1117,7 @@ PLS_HD void seg_enum_body_k(const SegJob &j, const SegParams &P, const SegCtlVie
             te[3] = PLS_CLOCK(); te[4] = te[3];
             for (int q = 0; q < PLR_SEG_ENUM_PHASES; q++) { PLS_ATOMIC_MAX(&j.result[PLR_SEG_ENUM_MAX + q], (int32_t)(te[q + 1] - te[q])); PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_ENUM_SUM + q], (uint32_t)(te[q + 1] - te[q])); }
             PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_ENUM_RUNS], 1u);
-            PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_ENUM_STATES], trflag[1] + trflag[2] + trflag[3] + trflag[4]);
+            PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_ENUM_STATES], trflag[SEG_TF_NDISTINCT] + trflag[SEG_TF_NDISTINCT + 1] + trflag[SEG_TF_NDISTINCT + 2] + trflag[SEG_TF_NDISTINCT + 3]);
         }
     }
 }
@@ -1162,7 +1141,6 @@ PLS_HD void seg_enum_body(const SegJob &j, const SegParams &P, const SegCtlView 
  * is the segment's ENTRY SET: hashed by value (exported: the chain kernel looks the exit states of the segment in front up in it), given dense
  * ids, and run through the segment like the distinct states of seg_enum_body.  A state of the reference's own path that is in no entry set
  * (1e-4 .. 1e-3 of the boundaries, oracle/seed_study.c) costs time, not correctness: the chain kernel walks that segment step by step. */
-#define SEG_SM_ENUM_SEEDED(nt) (SEG_TBL_WORDS * 4 + (SEG_KIN + SEG_L + 1) * 4 * 8 + 2048 + 32 + 4 * SEG_EH_WORDS * 4 + 4 * SEG_EH_WORDS * 2 + 4 * SEG_NSP * 4 + (nt) * 4 + 128)
 template <int NT>
 PLS_HD void seg_enum_seeded_body(const SegJob &j, const SegParams &P, const SegCtlView &cv, int par, int f, int seg, int chalf, unsigned char *smem)
 {
@@ -1177,14 +1155,10 @@ PLS_HD void seg_enum_seeded_body(const SegJob &j, const SegParams &P, const SegC
     const uint32_t kin = (uint32_t)P.kin;
     const uint32_t xs = x0 >= kin ? x0 - kin : 0u;            /* first pixel of the run-in */
     const int nrun = (int)(x0 - xs);
-    uint32_t *tw = (uint32_t *)smem;
-    SegPix *px = (SegPix *)(smem + SEG_TBL_WORDS * 4);        /* [(SEG_KIN + SEG_L + 1)][4]: slot 0 = boundary pixel xs-1 */
-    uint32_t *lut = (uint32_t *)(px + (SEG_KIN + SEG_L + 1) * 4);
-    uint32_t *trflag = lut + 512;                             /* [0] some pixel of the window is fully transparent, [1..4] distinct entry states per channel */
-    uint32_t *ht = trflag + 8;                                /* [4][SEG_EH_WORDS] key or ~0 */
-    uint16_t *dense = (uint16_t *)(ht + 4 * SEG_EH_WORDS);    /* [4][SEG_EH_WORDS] slot -> dense id */
-    uint32_t *uniq = (uint32_t *)(dense + 4 * SEG_EH_WORDS);  /* [4][SEG_NSP] the entry states (keys) by dense id */
-    uint32_t *keys = uniq + 4 * SEG_NSP;                      /* [NT] */
+    typedef SegLdsSeeded<NT> LDS;
+    uint32_t *tw = LDS::tw(smem), *lut = LDS::lut(smem), *trflag = LDS::trflag(smem), *ht = LDS::ht(smem), *uniq = LDS::uniq(smem), *keys = LDS::keys(smem);
+    SegPix *px = LDS::px(smem);
+    uint16_t *dense = LDS::dense(smem);
     const uint32_t y = cv.y;
     const SEG_AS_GLB uint32_t *row = seg_row_orig(j, y), *nab = y ? j.img + (size_t)(y - 1u) * W : nullptr, *e0g = seg_e0(j, y);
     const SegGeo G = seg_geo((int)cv.s);
@@ -1210,11 +1184,11 @@ PLS_HD void seg_enum_seeded_body(const SegJob &j, const SegParams &P, const SegC
         if (tid < 512) lut[tid] = vl;
         if (tid < npx) {
             seg_pix_split4(px + tid * 4, vp, bpp, xs - 1 + (uint32_t)tid, W);
-            if ((bpp & 1u) == 0u && (px[tid * 4 + (bpp - 1u)].w >> 24)) PLS_ATOMIC_OR(trflag, 1u);
+            if ((bpp & 1u) == 0u && (px[tid * 4 + (bpp - 1u)].w >> 24)) PLS_ATOMIC_OR(&trflag[SEG_TF_TRANSPARENT], 1u);
         }
     }
     PLS_SYNC();
-    const bool trx = trflag[0] != 0u;
+    const bool trx = trflag[SEG_TF_TRANSPARENT] != 0u;
     if (prof) te[1] = PLS_CLOCK();
     /* -- the seeds, through the run-in.  A workgroup of a channel PAIR does it in two stages (round 5): SEG_KA steps from every seed, then only the DISTINCT states
      *    that are left (a few dozen of the 256 per channel: the seeds differ in the left byte, and the left bytes fall into the bands' phases at once) through the
@@ -1255,7 +1229,7 @@ PLS_HD void seg_enum_seeded_body(const SegJob &j, const SegParams &P, const SegC
     }
     PLS_SYNC();
     if (two_stage) {
-        /* the distinct states after SEG_KA steps: list uniq[2 + lc][], count trflag[3 + lc] */
+        /* the distinct states after SEG_KA steps: list uniq[2 + lc][], count trflag[SEG_TF_NRUNIN + lc] */
         PLS_THREADS(tid, NT) {
             const int lc = tid / SEG_NSP, i = tid % SEG_NSP;
             const uint32_t key = keys[tid];
@@ -1264,7 +1238,7 @@ PLS_HD void seg_enum_seeded_body(const SegJob &j, const SegParams &P, const SegC
                 for (int q = 0; q < SEG_EHW; q++) {
                     const uint32_t old = PLS_ATOMIC_CAS(&ht[(2 + lc) * SEG_EH_WORDS + base + q], SEG_NOKEY, key);
                     if (old == SEG_NOKEY) {
-                        const uint32_t d = PLS_ATOMIC_ADD_RET(&trflag[3 + lc], 1u);
+                        const uint32_t d = PLS_ATOMIC_ADD_RET(&trflag[SEG_TF_NRUNIN + lc], 1u);
                         if (d < SEG_NSP) uniq[(2 + lc) * SEG_NSP + d] = key;
                         break;
                     }
@@ -1274,7 +1248,7 @@ PLS_HD void seg_enum_seeded_body(const SegJob &j, const SegParams &P, const SegC
         }
         PLS_SYNC();
         /* ... through the rest of the run-in, one lane each */
-        const uint32_t DA0 = trflag[3] < SEG_NSP ? trflag[3] : SEG_NSP, DA1 = trflag[4] < SEG_NSP ? trflag[4] : SEG_NSP;
+        const uint32_t DA0 = trflag[SEG_TF_NRUNIN] < SEG_NSP ? trflag[SEG_TF_NRUNIN] : SEG_NSP, DA1 = trflag[SEG_TF_NRUNIN + 1] < SEG_NSP ? trflag[SEG_TF_NRUNIN + 1] : SEG_NSP;
         PLS_THREADS(tid, NT) {
             uint32_t key = SEG_NOKEY;
             if ((uint32_t)tid < DA0 + DA1) {
@@ -1298,7 +1272,7 @@ PLS_HD void seg_enum_seeded_body(const SegJob &j, const SegParams &P, const SegC
                     for (int q = 0; q < SEG_EHW; q++) {
                         const uint32_t old = PLS_ATOMIC_CAS(&ht[c * SEG_EH_WORDS + base + q], SEG_NOKEY, key);
                         if (old == SEG_NOKEY) {
-                            const uint32_t d = PLS_ATOMIC_ADD_RET(&trflag[1 + c], 1u);
+                            const uint32_t d = PLS_ATOMIC_ADD_RET(&trflag[SEG_TF_NDISTINCT + c], 1u);
                             dense[c * SEG_EH_WORDS + base + q] = (uint16_t)(d < SEG_NSP ? d : 0xffffu);
                             if (d < SEG_NSP) uniq[c * SEG_NSP + d] = key;
                             break;
@@ -1319,7 +1293,7 @@ PLS_HD void seg_enum_seeded_body(const SegJob &j, const SegParams &P, const SegC
             for (int q = 0; q < SEG_EHW; q++) {
                 const uint32_t old = PLS_ATOMIC_CAS(&ht[c * SEG_EH_WORDS + base + q], SEG_NOKEY, key);
                 if (old == SEG_NOKEY) {
-                    const uint32_t d = PLS_ATOMIC_ADD_RET(&trflag[1 + c], 1u);
+                    const uint32_t d = PLS_ATOMIC_ADD_RET(&trflag[SEG_TF_NDISTINCT + c], 1u);
                     dense[c * SEG_EH_WORDS + base + q] = (uint16_t)(d < SEG_NSP ? d : 0xffffu);
                     if (d < SEG_NSP) uniq[c * SEG_NSP + d] = key;
                     break;
@@ -1343,13 +1317,13 @@ PLS_HD void seg_enum_seeded_body(const SegJob &j, const SegParams &P, const SegC
     PLS_THREADS(tid, NT) {
         /* (the entry states of the workgroup's channels packed into its first lanes, like the distinct states of seg_enum_body) */
         uint32_t Dc[NCH];
-        for (int k = 0; k < NCH; k++) Dc[k] = trflag[1 + k] < SEG_NSP ? trflag[1 + k] : SEG_NSP;
+        for (int k = 0; k < NCH; k++) Dc[k] = trflag[SEG_TF_NDISTINCT + k] < SEG_NSP ? trflag[SEG_TF_NDISTINCT + k] : SEG_NSP;
         int lc = 0, i = tid;
         uint32_t D = Dc[0];
         PLS_UNROLL
         for (int k = 0; k + 1 < NCH; k++) if (lc == k && (uint32_t)i >= Dc[k]) { i -= (int)Dc[k]; lc = k + 1; D = Dc[k + 1]; }
         const int c = c0 + lc;
-        if (tid < NCH && (uint32_t)(c0 + tid) < bpp) j.dcnt[((size_t)f * j.nseg + seg) * 4 + c0 + tid] = trflag[1 + tid] < SEG_NSP ? trflag[1 + tid] : SEG_NSP;
+        if (tid < NCH && (uint32_t)(c0 + tid) < bpp) j.dcnt[((size_t)f * j.nseg + seg) * 4 + c0 + tid] = trflag[SEG_TF_NDISTINCT + tid] < SEG_NSP ? trflag[SEG_TF_NDISTINCT + tid] : SEG_NSP;
         if ((uint32_t)c < bpp && (uint32_t)i < D) {
             SegState st = seg_eh_state(uniq[lc * SEG_NSP + i]);
             const size_t slot = (((size_t)f * j.nseg + seg) * 4 + c) * SEG_NSP + i;
@@ -1365,7 +1339,7 @@ PLS_HD void seg_enum_seeded_body(const SegJob &j, const SegParams &P, const SegC
             te[3] = PLS_CLOCK(); te[4] = te[3];
             for (int q = 0; q < PLR_SEG_ENUM_PHASES; q++) { PLS_ATOMIC_MAX(&j.result[PLR_SEG_ENUM_MAX + q], (int32_t)(te[q + 1] - te[q])); PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_ENUM_SUM + q], (uint32_t)(te[q + 1] - te[q])); }
             PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_ENUM_RUNS], 1u);
-            PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_ENUM_STATES], two_stage ? 2u * (trflag[1] + trflag[2]) : trflag[1] + trflag[2] + trflag[3] + trflag[4]);
+            PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_ENUM_STATES], two_stage ? 2u * (trflag[SEG_TF_NDISTINCT] + trflag[SEG_TF_NDISTINCT + 1]) : trflag[SEG_TF_NDISTINCT] + trflag[SEG_TF_NDISTINCT + 1] + trflag[SEG_TF_NDISTINCT + 2] + trflag[SEG_TF_NDISTINCT + 3]);
         }
     }
 }
@@ -1378,13 +1352,13 @@ PLS_HD void seg_enum_small_body(const SegJob &j, const SegParams &P, const SegCt
     const uint32_t W = j.W, bpp = j.bpp;
     constexpr int NSEGS = NT / (4 * SEG_NSS);                 /* segments of this workgroup */
     if ((uint32_t)(seg0 + NSEGS) * SEG_L <= cv.start_x) return;
-    uint32_t *tw = (uint32_t *)smem;
-    uint32_t *lut = tw + SEG_TBL_WORDS;
-    SegPix *px = (SegPix *)(lut + 512);                        /* [NSEGS][SEG_L][4] */
+    typedef SegLdsSmall<NT> LDS;
+    uint32_t *tw = LDS::tw(smem), *lut = LDS::lut(smem);
+    SegPix *px = LDS::px(smem);                                /* [NSEGS][SEG_L][4] */
     const uint32_t y = cv.y;
     const uint32_t *row = seg_row_orig(j, y), *nab = y ? j.img + (size_t)(y - 1u) * W : nullptr, *e0g = seg_e0(j, y);
     const SegGeo G = seg_geo((int)cv.s);
-    uint32_t *trflag = (uint32_t *)(px + NSEGS * SEG_L * 4);
+    uint32_t *trflag = LDS::trflag(smem);
     PLS_THREADS(tid, NT) { if (tid == 0) *trflag = 0u; }
     PLS_SYNC();
     PLS_THREADS(tid, NT) {
@@ -1443,23 +1417,6 @@ PLS_HD void seg_enum_small_body(const SegJob &j, const SegParams &P, const SegCt
  *   - none / up (LANES = 32: their state is (cn, th)) go through the same body, dedupe included: ~3 distinct states per pair instead of 17 lanes,
  *     twenty pairs a workgroup.
  * The chain kernel composes UNITS (seg_chain_body reads SegParams::unit); replay and validation do not know the difference. */
-#ifndef SEG_UNC_SMALL
-#define SEG_UNC_SMALL (SEG_UNIT <= 3 ? 20 : (SEG_UNIT <= 4 ? 15 : (SEG_UNIT <= 6 ? 10 : 7)))          /* (unit, channel) pairs per workgroup for none / up with their small state set */
-#endif
-#define SEG_UNC_SMALL_OF(unit) ((unit) == SEG_UNIT ? SEG_UNC_SMALL : (SEG_UNC_SMALL < 20 ? SEG_UNC_SMALL : 20))      /* ... and segment by segment (round 6: seg_k_enum_unit<1>) */
-#define SEG_UNPX (SEG_UNC_SMALL * (SEG_UNIT * SEG_L + 1))   /* pixel records of a workgroup's pairs */
-/* LDS of the unit enumeration: tables, split table, the pool, the first records of every pair, bookkeeping -- and ONE region that holds the first phase's
- * scratch (hash tables, per-turn lists, keys: 10 KB) and then, for the second phase, the pairs' full pixel records (15.5 KB for the twenty pairs of none / up):
- * 35.8 KB = four workgroups per CU.  (The first version carved both side by side: 52 KB, three per CU, and the CUs' slots, not their issue, set the kernel's
- * time; the second was sized for 1024 threads: 39.9 KB.  Sixteen / twelve pairs of none / up = 32.5 / 28.6 KB = FIVE per CU were measured: 464 / 451 Mpx/s
- * for 32 frames against 465 -- the slots are not what it is short of; the 4 KB less are worth 1.3 %, though: the other launch groups' control, validation and
- * replay workgroups want 37 - 50 KB next to two or three of these.) */
-#define SEG_UN_K1MAX 4
-#define SEG_UN_SCRATCH (2 * SEG_UNT * 4 + 2 * SEG_UNT * 2 + SEG_UNT * 4 + SEG_UNT * 4)        /* hash tables (a turn's pairs x twice their lanes), dense ids, the turn's lists, one key a thread */
-#define SEG_UN_PHASE2 (SEG_UNPX * 8 + SEG_UPOOL * 4)      /* the pairs' records and the second list of distinct states (behind the unit's first segment) */
-#define SEG_UN_SEEDX (SEG_UN_SCRATCH + (SEG_UNC_SEEDS > SEG_UNC_SEEDS1 ? SEG_UNC_SEEDS : SEG_UNC_SEEDS1) * (SEG_SEED_KMAX + 1) * 8 + (SEG_UNT / SEG_SEED_LANES) * 512)   /* (from seeds: the run-in's records and a turn's staged entry maps behind the scratch) */
-#define SEG_UN_REGION ((SEG_UN_SCRATCH > SEG_UN_PHASE2 ? SEG_UN_SCRATCH : SEG_UN_PHASE2) > SEG_UN_SEEDX ? (SEG_UN_SCRATCH > SEG_UN_PHASE2 ? SEG_UN_SCRATCH : SEG_UN_PHASE2) : SEG_UN_SEEDX)
-#define SEG_SM_ENUM_UNIT (SEG_TBL_WORDS * 4 + 2048 + SEG_UPOOL * 4 + SEG_UNC_SMALL * (SEG_UN_K1MAX + 1) * 8 + 512 + SEG_UN_REGION)
 /* set bits among bits [a, b) of a bit array */
 PLS_HD uint32_t seg_bits_count(const uint32_t *bits, uint32_t a, uint32_t b)
 {
@@ -1492,29 +1449,20 @@ PLS_HD void seg_enum_unit_body(const SegJob &j, const SegParams &P, const SegCtl
     /* an epoch that starts inside the row: the unit that holds its first pixel (and everything in front) is walked by seg_first_body */
     { const uint32_t ql = seg_umin(q0 + NC, ncombo) - 1u; if (sx && (ql / bpp) * UL <= sx) return; }
     constexpr uint32_t NP1 = SEEDS ? SEG_SEED_KMAX + 1 : SEG_UN_K1MAX + 1;   /* records of a pair the first phase reads: the boundary pixel and SEG_K1 more (SEEDS: the pixel in front of the run-in and the run-in) */
-    uint32_t *tw = (uint32_t *)smem;
-    uint32_t *lut = tw + SEG_TBL_WORDS;
-    uint32_t *pool = lut + 512;                               /* [SEG_UPOOL] the distinct states of all pairs, pair behind pair */
-    SegPix *px1_std = (SegPix *)(pool + SEG_UPOOL);           /* [NC][NP1]: one channel's first records of a pair, slot 0 = the boundary pixel in front of the unit */
-    uint32_t *misc = (uint32_t *)(px1_std + SEG_UNC_SMALL * (SEG_UN_K1MAX + 1)); /* [0] transparent pixel seen, [8 + kk] distinct states of the turn's pair kk, [32 + k] first pool slot of pair k (.. [32 + NC] = total),
-                                                                 [64 + k] the same for the SECOND list (.. [64 + NC] = its total), [96 .. 127] one bit per lane: it represents a state of the second list */
-    /* first phase: */
-    uint32_t *ht = misc + 128;                                /* [CPR][HT] key or ~0 (this turn) */
-    uint16_t *dense = (uint16_t *)(ht + 2 * SEG_UNT);         /* [CPR][HT] slot -> dense id */
-    uint32_t *uniqr = (uint32_t *)(dense + 2 * SEG_UNT);      /* [CPR][LANES] this turn's distinct states by dense id */
-    uint32_t *keys = uniqr + SEG_UNT;                         /* [NT] */
-    /* SEEDS: the run-in's records and the turn's entry maps, behind the first phase's scratch (the region is as large as the second phase's records) */
-    SegPix *px1 = SEEDS ? (SegPix *)(keys + SEG_UNT) : px1_std;
-    uint16_t *mapl = (uint16_t *)(px1 + NC * NP1);            /* (SEEDS) [CPR][256]: entry index -> dense id of the turn's pairs, staged here and stored coalesced */
-    static_assert(!SEEDS || (SEG_UN_SCRATCH + NC * (int)NP1 * 8 + CPR * 512 <= SEG_UN_REGION), "the run-in's records and the staged maps fit behind the scratch");
+    typedef SegLdsUnit<LANES, UNIT, NC, SEEDS> LDS;
+    uint32_t *tw = LDS::tw(smem), *lut = LDS::lut(smem), *pool = LDS::pool(smem), *misc = LDS::misc(smem);
+    /* first phase (SEEDS: the run-in's records and the turn's entry maps behind its scratch): */
+    uint32_t *ht = LDS::ht(smem), *uniqr = LDS::uniqr(smem), *keys = LDS::keys(smem);
+    uint16_t *dense = LDS::dense(smem), *mapl = LDS::mapl(smem);
+    SegPix *px1 = SEEDS ? LDS::px1_seeds(smem) : LDS::px1_std(smem);   /* [NC][NP1] */
     static_assert(!SEEDS || LANES == SEG_SEED_LANES, "one lane per seed");
     /* the run-in: P.seed_kin pixels (8) -- and half as many again for an image that has had rows broken off (SegJob::nbreak): real photographs lose the true state at a boundary in
      * ~1e-3 of the cases after 8 pixels and a quarter of that after 12 (oracle/seed_study.c on the suite's lena: sub 17 -> 4 of 23 040, paeth 5 -> 2), the generator's frames next to never
      * either way, and the longer run-in costs every workgroup 1 - 3 % */
     const int KR = SEEDS ? seg_min(seg_max(j.nbreak >= SEG_SEED_LONG_AFTER ? P.seed_kin + P.seed_kin / 2 : P.seed_kin, 1), SEG_SEED_KMAX) : 0;
     /* second phase, in the same place: */
-    SegPix *px = (SegPix *)(misc + 128);                      /* [NC][NPX]: all records of a pair */
-    uint32_t *pool2 = (uint32_t *)(px + SEG_UNPX);            /* [SEG_UPOOL] the states that are still distinct behind the unit's first segment, at the pairs' places of the first list */
+    SegPix *px = LDS::px(smem);
+    uint32_t *pool2 = LDS::pool2(smem);
     static_assert(SEG_K1 <= SEG_UN_K1MAX && SEG_K1_ONE_CHUNK <= SEG_UN_K1MAX, "the first phase's records");
     const uint32_t y = cv.y;
     const SEG_AS_GLB uint32_t *row = seg_row_orig(j, y), *nab = y ? j.img + (size_t)(y - 1u) * W : nullptr, *e0g = seg_e0(j, y);
@@ -1545,17 +1493,17 @@ PLS_HD void seg_enum_unit_body(const SegJob &j, const SegParams &P, const SegCtl
         PLS_UNROLL
         for (int q = 0; q < NTW; q++) { const int i = tid + q * NT; if (i < SEG_TBL_WORDS) tw[i] = vt[q]; }
         if (tid < 512) lut[tid] = vl;
-        if ((uint32_t)tid < (uint32_t)NC * NP1) { px1[tid] = vp; if (vp.w >> 24) PLS_ATOMIC_OR(&misc[0], 1u); }
+        if ((uint32_t)tid < (uint32_t)NC * NP1) { px1[tid] = vp; if (vp.w >> 24) PLS_ATOMIC_OR(&misc[SEG_UM_TRANSPARENT], 1u); }
     }
     PLS_SYNC();
-    const bool trx1 = misc[0] != 0u;
+    const bool trx1 = misc[SEG_UM_TRANSPARENT] != 0u;
     if (prof) te[1] = PLS_CLOCK();
     const int K1 = SEEDS ? 0 : seg_k1(nstates);
     /* -- first phase, a turn of CPR pairs at a time: SEG_K1 steps from every state, the dedupe, the pair's entry map (entry index -> dense id) -- */
     for (int r = 0; r < ROUNDS; r++) {
         PLS_THREADS(tid, NT) {
             for (int i = tid; i < CPR * HT; i += NT) ht[i] = 0xffffffffu;
-            if (tid < CPR) misc[8 + tid] = 0u;
+            if (tid < CPR) misc[SEG_UM_TURN_N + tid] = 0u;
             if (SEEDS) for (int i = tid; i < CPR * 128; i += NT) ((uint32_t *)mapl)[i] = 0xffffffffu;
         }
         PLS_SYNC();
@@ -1588,7 +1536,7 @@ PLS_HD void seg_enum_unit_body(const SegJob &j, const SegParams &P, const SegCtl
                     for (int probe = 0; probe < HT; probe++) {
                         const uint32_t old = PLS_ATOMIC_CAS(&ht[kk * HT + h], 0xffffffffu, key);
                         if (old == 0xffffffffu) {
-                            const uint32_t d = PLS_ATOMIC_ADD_RET(&misc[8 + kk], 1u);
+                            const uint32_t d = PLS_ATOMIC_ADD_RET(&misc[SEG_UM_TURN_N + kk], 1u);
                             dense[kk * HT + h] = (uint16_t)d;
                             uniqr[kk * LANES + d] = key;
                             mapl[kk * 256 + (key >> 24)] = (uint16_t)d;
@@ -1637,7 +1585,7 @@ PLS_HD void seg_enum_unit_body(const SegJob &j, const SegParams &P, const SegCtl
                     for (int probe = 0; probe < HT; probe++) {
                         const uint32_t old = PLS_ATOMIC_CAS(&ht[kk * HT + h], 0xffffffffu, key);
                         if (old == 0xffffffffu) {
-                            const uint32_t d = PLS_ATOMIC_ADD_RET(&misc[8 + kk], 1u);
+                            const uint32_t d = PLS_ATOMIC_ADD_RET(&misc[SEG_UM_TURN_N + kk], 1u);
                             dense[kk * HT + h] = (uint16_t)(d < (uint32_t)LANES ? d : 0xffffu);
                             if (d < (uint32_t)LANES) uniqr[kk * LANES + d] = key;
                             break;
@@ -1676,18 +1624,18 @@ PLS_HD void seg_enum_unit_body(const SegJob &j, const SegParams &P, const SegCtl
                 for (int kk = 0; kk < CPR; kk++) {
                     const int k = r * CPR + kk;
                     if (k >= NC) break;
-                    uint32_t D = misc[8 + kk] < (uint32_t)LANES ? misc[8 + kk] : (uint32_t)LANES;
-                    const uint32_t b0 = misc[32 + k];
+                    uint32_t D = misc[SEG_UM_TURN_N + kk] < (uint32_t)LANES ? misc[SEG_UM_TURN_N + kk] : (uint32_t)LANES;
+                    const uint32_t b0 = misc[SEG_UM_POOL + k];
                     if (b0 + D > SEG_UPOOL) D = SEG_UPOOL - b0;
-                    misc[8 + kk] = D;
-                    misc[32 + k + 1] = b0 + D;
+                    misc[SEG_UM_TURN_N + kk] = D;
+                    misc[SEG_UM_POOL + k + 1] = b0 + D;
                 }
             }
         }
         PLS_SYNC();
         PLS_THREADS(tid, NT) {
             const int kk = tid / LANES, k = r * CPR + kk, i = tid % LANES;
-            if (kk < CPR && k < NC && (uint32_t)i < misc[8 + kk]) pool[misc[32 + k] + (uint32_t)i] = uniqr[kk * LANES + i];
+            if (kk < CPR && k < NC && (uint32_t)i < misc[SEG_UM_TURN_N + kk]) pool[misc[SEG_UM_POOL + k] + (uint32_t)i] = uniqr[kk * LANES + i];
         }
         PLS_SYNC();
     }
@@ -1700,7 +1648,7 @@ PLS_HD void seg_enum_unit_body(const SegJob &j, const SegParams &P, const SegCtl
         for (int q = 0; q < NPI; q++) {
             const uint32_t t = (uint32_t)tid + (uint32_t)q * NT, k = t / NPX, pq = t % NPX, cq = q0 + k;
             vp[q] = seg_pix_make(0, 0, 0, 0, 0);
-            if (k < (uint32_t)NC && cq < ncombo && misc[32 + k + 1] != misc[32 + k]) {            /* (a pair without a lane needs no records) */
+            if (k < (uint32_t)NC && cq < ncombo && misc[SEG_UM_POOL + k + 1] != misc[SEG_UM_POOL + k]) {            /* (a pair without a lane needs no records) */
                 const uint32_t u = cq / bpp, c = cq % bpp, x = u * UL + pq - 1u;
                 if (x < W) vp[q] = seg_pix_load(row, nab, e0g, bpp, x, (int)c);
             }
@@ -1708,33 +1656,33 @@ PLS_HD void seg_enum_unit_body(const SegJob &j, const SegParams &P, const SegCtl
         PLS_UNROLL
         for (int q = 0; q < NPI; q++) {
             const uint32_t t = (uint32_t)tid + (uint32_t)q * NT;
-            if (t < (uint32_t)NC * NPX) { px[t] = vp[q]; if (vp[q].w >> 24) PLS_ATOMIC_OR(&misc[0], 1u); }
+            if (t < (uint32_t)NC * NPX) { px[t] = vp[q]; if (vp[q].w >> 24) PLS_ATOMIC_OR(&misc[SEG_UM_TRANSPARENT], 1u); }
         }
     }
     PLS_SYNC();
-    const bool trx = misc[0] != 0u;
+    const bool trx = misc[SEG_UM_TRANSPARENT] != 0u;
 #if defined(__HIP_DEVICE_COMPILE__)
-    /* From here on only the first misc[32 + NC] lanes have work.  The waves behind them END here: a workgroup of 16 waves keeps 16 of the CU's 32 wave slots
+    /* From here on only the first misc[SEG_UM_POOL + NC] lanes have work.  The waves behind them END here: a workgroup of 16 waves keeps 16 of the CU's 32 wave slots
      * as long as its waves sit in the barriers below -- with them gone the CU takes the next workgroup (measured: profiles/r05_unit_groups.txt).  A barrier
      * counts the waves that have not ended, so the ones that stay are not held up.  Wave 0 always stays: its first NC lanes write the pairs' dcnt below -- also when
      * EVERY state of every pair left the tables in the first phase (pool total 0): the chain kernel must find "no distinct states" there, not an earlier row's count. */
-    if (threadIdx.x >= 64u && (threadIdx.x & ~63u) >= misc[32 + NC]) return;
+    if (threadIdx.x >= 64u && (threadIdx.x & ~63u) >= misc[SEG_UM_POOL + NC]) return;
 #endif
     /* -- second phase: the distinct states of all pairs, one lane each, through the unit's FIRST segment -- */
     PLS_THREADS(tid, NT) {
-        const uint32_t total = misc[32 + NC];
+        const uint32_t total = misc[SEG_UM_POOL + NC];
         if (tid < NC) {
             const uint32_t cq = q0 + (uint32_t)tid;
             if (cq < ncombo && !(sx && (cq / bpp) * UL <= sx)) {
-                const uint32_t u = cq / bpp, c = cq % bpp, D = misc[32 + tid + 1] - misc[32 + tid];
+                const uint32_t u = cq / bpp, c = cq % bpp, D = misc[SEG_UM_POOL + tid + 1] - misc[SEG_UM_POOL + tid];
                 for (uint32_t sg = u * E; sg < seg_umin(u * E + E, nseg); sg++) j.dcnt[((size_t)f * nseg + sg) * 4 + c] = D;
             }
         }
         if ((uint32_t)tid < total) {
             int k = 0;
             PLS_UNROLL
-            for (int q = 1; q < NC; q++) k += (uint32_t)tid >= misc[32 + q] ? 1 : 0;
-            const uint32_t i = (uint32_t)tid - misc[32 + k], cq = q0 + (uint32_t)k, u = cq / bpp, c = cq % bpp;
+            for (int q = 1; q < NC; q++) k += (uint32_t)tid >= misc[SEG_UM_POOL + q] ? 1 : 0;
+            const uint32_t i = (uint32_t)tid - misc[SEG_UM_POOL + k], cq = q0 + (uint32_t)k, u = cq / bpp, c = cq % bpp;
             const uint32_t key = pool[tid];
             SegState st;
             st.left = (int)(key & 255u); st.cn = seg_sext8((int)(key >> 8)); st.th = seg_sext8((int)(key >> 16));
@@ -1762,27 +1710,27 @@ PLS_HD void seg_enum_unit_body(const SegJob &j, const SegParams &P, const SegCtl
          *    list, rout of the unit's first segment takes an id of the first list to its id in the second, and only the second list runs on. -- */
         PLS_SYNC();
         PLS_THREADS(tid, NT) {
-            const uint32_t total = misc[32 + NC];
+            const uint32_t total = misc[SEG_UM_POOL + NC];
             if ((uint32_t)tid < total) {
                 const uint32_t ps = pool[tid];
                 if (ps != 0xFFFFFFFFu) {
                     int k = 0;
                     PLS_UNROLL
-                    for (int q = 1; q < NC; q++) k += (uint32_t)tid >= misc[32 + q] ? 1 : 0;
+                    for (int q = 1; q < NC; q++) k += (uint32_t)tid >= misc[SEG_UM_POOL + q] ? 1 : 0;
                     uint32_t rep = (uint32_t)tid;
-                    for (uint32_t jj = misc[32 + k]; jj < (uint32_t)tid; jj++) if (pool[jj] == ps) { rep = jj; break; }
-                    if (rep == (uint32_t)tid) PLS_ATOMIC_OR(&misc[96 + (tid >> 5)], 1u << (tid & 31));
+                    for (uint32_t jj = misc[SEG_UM_POOL + k]; jj < (uint32_t)tid; jj++) if (pool[jj] == ps) { rep = jj; break; }
+                    if (rep == (uint32_t)tid) PLS_ATOMIC_OR(&misc[SEG_UM_LANEBITS + (tid >> 5)], 1u << (tid & 31));
                 }
             }
         }
         PLS_SYNC();
         PLS_THREADS(tid, NT) {
-            const uint32_t total = misc[32 + NC];
+            const uint32_t total = misc[SEG_UM_POOL + NC];
             if ((uint32_t)tid < total) {
                 int k = 0;
                 PLS_UNROLL
-                for (int q = 1; q < NC; q++) k += (uint32_t)tid >= misc[32 + q] ? 1 : 0;
-                const uint32_t b0 = misc[32 + k], i = (uint32_t)tid - b0, cq = q0 + (uint32_t)k, u = cq / bpp, c = cq % bpp;
+                for (int q = 1; q < NC; q++) k += (uint32_t)tid >= misc[SEG_UM_POOL + q] ? 1 : 0;
+                const uint32_t b0 = misc[SEG_UM_POOL + k], i = (uint32_t)tid - b0, cq = q0 + (uint32_t)k, u = cq / bpp, c = cq % bpp;
                 const uint32_t sg0 = u * E, nsg = seg_umin(E, nseg - sg0);
                 if (nsg > 1u) {
                     const uint32_t ps = pool[tid];
@@ -1790,28 +1738,28 @@ PLS_HD void seg_enum_unit_body(const SegJob &j, const SegParams &P, const SegCtl
                     if (ps != 0xFFFFFFFFu) {
                         uint32_t rep = (uint32_t)tid;
                         for (uint32_t jj = b0; jj < (uint32_t)tid; jj++) if (pool[jj] == ps) { rep = jj; break; }
-                        dB = seg_bits_count(misc + 96, b0, rep);
+                        dB = seg_bits_count(misc + SEG_UM_LANEBITS, b0, rep);
                         if (rep == (uint32_t)tid) pool2[b0 + dB] = ps;
                     }
                     j.rout[(((size_t)f * nseg + sg0) * 4 + c) * SEG_NSP + i] = (uint16_t)dB;
                 }
-                if (i == 0u) misc[64 + k] = nsg > 1u ? seg_bits_count(misc + 96, b0, misc[32 + k + 1]) : 0u;
+                if (i == 0u) misc[SEG_UM_POOL2 + k] = nsg > 1u ? seg_bits_count(misc + SEG_UM_LANEBITS, b0, misc[SEG_UM_POOL + k + 1]) : 0u;
             }
         }
         PLS_SYNC();
         PLS_THREADS(tid, NT) {
-            if (tid == 0) { uint32_t run = 0; for (int k = 0; k < NC; k++) { const uint32_t cnt2 = misc[64 + k]; misc[64 + k] = run; run += cnt2; } misc[64 + NC] = run; }
+            if (tid == 0) { uint32_t run = 0; for (int k = 0; k < NC; k++) { const uint32_t cnt2 = misc[SEG_UM_POOL2 + k]; misc[SEG_UM_POOL2 + k] = run; run += cnt2; } misc[SEG_UM_POOL2 + NC] = run; }
         }
         PLS_SYNC();
         /* -- third phase: the second list through the rest of the unit -- */
         PLS_THREADS(tid, NT) {
-            const uint32_t total2 = misc[64 + NC];
+            const uint32_t total2 = misc[SEG_UM_POOL2 + NC];
             if ((uint32_t)tid < total2) {
                 int k = 0;
                 PLS_UNROLL
-                for (int q = 1; q < NC; q++) k += (uint32_t)tid >= misc[64 + q] ? 1 : 0;
-                const uint32_t i = (uint32_t)tid - misc[64 + k], cq = q0 + (uint32_t)k, u = cq / bpp, c = cq % bpp;
-                SegState st = seg_state_unpack(pool2[misc[32 + k] + i]);
+                for (int q = 1; q < NC; q++) k += (uint32_t)tid >= misc[SEG_UM_POOL2 + q] ? 1 : 0;
+                const uint32_t i = (uint32_t)tid - misc[SEG_UM_POOL2 + k], cq = q0 + (uint32_t)k, u = cq / bpp, c = cq % bpp;
+                SegState st = seg_state_unpack(pool2[misc[SEG_UM_POOL + k] + i]);
                 const SegPix *pk = px + (size_t)k * NPX;
                 const uint32_t sg0 = u * E, nsg = seg_umin(E, nseg - sg0);
                 int bad = 0;
@@ -1835,7 +1783,7 @@ PLS_HD void seg_enum_unit_body(const SegJob &j, const SegParams &P, const SegCtl
                 te[4] = PLS_CLOCK();
                 for (int q = 0; q < PLR_SEG_ENUM_PHASES; q++) { PLS_ATOMIC_MAX(&j.result[PLR_SEG_ENUM_MAX + q], (int32_t)(te[q + 1] - te[q])); PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_ENUM_SUM + q], (uint32_t)(te[q + 1] - te[q])); }
                 PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_ENUM_RUNS], 1u);
-                PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_ENUM_STATES], 4u * misc[32 + NC] / (uint32_t)NC);
+                PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_ENUM_STATES], 4u * misc[SEG_UM_POOL + NC] / (uint32_t)NC);
             }
         }
     }
@@ -1906,10 +1854,9 @@ PLS_HD void seg_first_body(const SegJob &j, const SegParams &P, const SegCtlView
     const uint32_t E = UNITS ? seg_unit_of(P, f) : 1u, ulast = seg_umin((first / E) * E + E - 1u, nseg - 1u);   /* (!UNITS: the per-segment enumeration's kernels, where E = 1 folds all of this away) */
     const uint32_t wend = seg_umin(ulast, nseg - 2u);         /* last segment walked: the row's last segment has nothing behind it */
     const uint32_t npix = (wend - first + 1u) * SEG_L;
-    uint32_t *tw = (uint32_t *)smem;
-    uint32_t *lut = tw + SEG_TBL_WORDS;
-    uint32_t *Hf = lut + 512, *rank = Hf + 256;
-    SegPix *px = (SegPix *)(rank + 256);                      /* [npix][4]: up to a unit's pixels */
+    typedef SegLdsFirst<NT, UNITS> LDS;
+    uint32_t *tw = LDS::tw(smem), *lut = LDS::lut(smem), *Hf = LDS::Hf(smem), *rank = LDS::rank(smem);
+    SegPix *px = LDS::px(smem);                               /* [npix][4]: up to a unit's pixels */
     const unsigned long long tf0 = (P.engine_flags & 1) ? PLS_CLOCK() : 0ull;
     const uint32_t y = cv.y;
     const uint32_t *row = seg_row_orig(j, y), *nab = y ? j.img + (size_t)(y - 1u) * W : nullptr, *e0g = seg_e0(j, y);
@@ -2022,20 +1969,8 @@ PLS_HD void seg_gather_seeded_body(const SegJob &j, const SegCtlView &cv, int f,
  * a pass can start anywhere -- which is how the rare segment whose entry state the enumeration did not cover is handled: the pass ends in
  * front of it, ONE lane walks it step by step from its known entry state (table steps; exact), looks the exit up in the next segment's
  * entry set, and the passes go on from there. */
-#define SEG_CBLK 16
-#define SEG_CR_SH 6
-#define SEG_CR_MAX (1 << SEG_CR_SH)                             /* the usual table stride; the exit states are staged in shared memory at this stride */
 #define SEG_NOSTATE 0xFFFFFFFFu
 #define SEG_CQ 8                                                /* gather items in flight per thread */
-#define SEG_CHAIN_CAP 256                                       /* most transitions of a pass (strides 64 and 128) */
-#define SEG_CHAIN_CAP8 224                                      /* ... at stride 256 */
-#define SEG_CHAIN_POS (SEG_CHAIN_CAP + 32)                      /* dn / entL entries */
-#define SEG_CHAIN_TROWS(n) (((n) < SEG_CHAIN_CAP8 ? (n) : SEG_CHAIN_CAP8) + SEG_CBLK + 2)
-#define SEG_CHAIN_TBYTES(n) ((size_t)SEG_CHAIN_TROWS(n) * 512)     /* T (and R behind it at the usual stride) for a row of n segments: the widest stride sets the size */
-#define SEG_CHAIN_GWORDS ((SEG_CHAIN_CAP / SEG_CBLK + 2) * 256 / 2)
-#define SEG_SM_CHAIN(nseg) ((1024 + 32 + 2 * SEG_CHAIN_POS + SEG_CHAIN_GWORDS) * 4 + SEG_CHAIN_TBYTES(nseg) + SEG_TBL_WORDS * 4 + (SEG_L + 1) * 8 + 64)
-/* (exhaustive state sets: no repair path, so no tables and pixel records behind T; npos = the row's chain positions: units) */
-#define SEG_SM_CHAIN_X(npos) ((1024 + 32 + 2 * SEG_CHAIN_POS + SEG_CHAIN_GWORDS) * 4 + SEG_CHAIN_TBYTES(npos) + 64)
 PLS_HD uint32_t seg_chain_cap(uint32_t sh) { return sh >= 8 ? (uint32_t)SEG_CHAIN_CAP8 : (uint32_t)SEG_CHAIN_CAP; }
 template <bool SEEDED, int CT, bool UNITS>
 PLS_HD void seg_chain_body(const SegJob &j, const SegParams &P, const SegCtlView &cv, int par, int f, int c, unsigned char *smem)
@@ -2059,14 +1994,11 @@ PLS_HD void seg_chain_body(const SegJob &j, const SegParams &P, const SegCtlView
     if (sx && ufirst + 1 >= nunit) return;                      /* no unit behind the walked one (seg_first_body left the entry states of its segments) */
     /* enumerated units s0 .. nunit-1 (ne of them; a fresh row: from 0) = POSITIONS 0 .. ns of the chain; ns = ne - 1 transitions */
     const uint32_t s0 = sx ? ufirst + 1 : 0u, ne = nunit - s0, ns = ne - 1;
-    seg_lds_u32 Hf = (seg_lds_u32)smem, rank = Hf + 256, lut = Hf + 512;   /* (repair only) */
-    seg_lds_u32 idxb = Hf + 1024;                               /* [32]: [24] repairs, [25] first position without an id, [26] entry state of the pass's first position, [27] most distinct states of a segment,
-                                                                   [28] dense id the pass starts with, [30] some segment has more distinct states than the stride, [31] repair tables loaded */
-    seg_lds_u32 dn = idxb + 32;                                /* [SEG_CHAIN_POS] dense id at every position of the pass */
-    seg_lds_u32 entL = dn + SEG_CHAIN_POS;                     /* [SEG_CHAIN_POS] entry state at every position of the pass (from 1; 0: idxb[26]) */
-    seg_lds_u16 G = (seg_lds_u16)(entL + SEG_CHAIN_POS);       /* [nblk + 1][stride] composed tables of the blocks */
-    seg_lds_u16 T = G + 2 * SEG_CHAIN_GWORDS;                  /* [rows][stride]: T[k] takes a dense id of position k to one of position k+1 */
-    seg_lds_u32 twr = (seg_lds_u32)((SEG_AS_LDS unsigned char *)T + SEG_CHAIN_TBYTES(nseg));   /* (repair only: seeded sets, whose launch asks for SEG_SM_CHAIN) the candidate's decision tables, then the walked segment's pixel records */
+    typedef SegLdsChain<SEEDED> LDS;
+    seg_lds_u32 Hf = LDS::Hf(smem), rank = LDS::rank(smem), lut = LDS::lut(smem);   /* (repair only) */
+    seg_lds_u32 idxb = LDS::idxb(smem), dn = LDS::dn(smem), entL = LDS::entL(smem);
+    seg_lds_u16 G = LDS::G(smem), T = LDS::T(smem);
+    seg_lds_u32 twr = LDS::twr(smem, nseg);                     /* (repair only: seeded sets) */
     const uint32_t y = cv.y;
     const SEG_AS_GLB uint32_t *row = seg_row_orig(j, y), *nab = y ? j.img + (size_t)(y - 1u) * W : nullptr, *e0g = seg_e0(j, y);
     const SEG_AS_GLB uint16_t *maps = j.maps + ((size_t)f * nseg * 4 + c) * (size_t)P.nsp;     /* + sg * 4 * nsp */
@@ -2129,7 +2061,7 @@ PLS_HD void seg_chain_body(const SegJob &j, const SegParams &P, const SegCtlView
         const uint32_t ntr = seg_umin(seg_chain_cap(sh), ns - a);
         if (ntr == 0) {
             /* only the row's last segment is left (behind a repair): it has the id the repair looked up */
-            PLS_THREADS(tid, CT) { if (tid == 0) { const uint32_t d = idxb[28]; dnout[(size_t)SEGF(s0 + a) * 4] = (uint16_t)(d < SEG_NSP ? d : SEG_INVALID); } }   /* (seeded sets: E = 1) */
+            PLS_THREADS(tid, CT) { if (tid == 0) { const uint32_t d = idxb[SEG_CI_START_ID]; dnout[(size_t)SEGF(s0 + a) * 4] = (uint16_t)(d < SEG_NSP ? d : SEG_INVALID); } }   /* (seeded sets: E = 1) */
             break;
         }
         if (prof) tc[0] = PLS_CLOCK();
@@ -2241,22 +2173,22 @@ PLS_HD void seg_chain_body(const SegJob &j, const SegParams &P, const SegCtlView
                     if (useR) R[t] = ps[q];
                 }
             }
-            if (widest > stride) { idxb[30] = 1u; PLS_ATOMIC_MAX_U(&idxb[27], widest); }
+            if (widest > stride) { idxb[SEG_CI_WIDE] = 1u; PLS_ATOMIC_MAX_U(&idxb[SEG_CI_DMAX], widest); }
             /* rows behind the last table (the landing row, then spare rows up to whole blocks): they lead to the absorbing cell */
             for (uint32_t t = (ntr << sh) + (uint32_t)tid; t < (nblk * SEG_CBLK) << sh; t += CT) T[t] = (uint16_t)dummy;
             if (starter) {
-                idxb[28] = dfirst;
-                idxb[26] = start_ps;
+                idxb[SEG_CI_START_ID] = dfirst;
+                idxb[SEG_CI_ENTRY0] = start_ps;
                 entry[(size_t)SEGF(s0) * 4] = start_ps;
             }
-            if (tid == 0) { T[dummy] = (uint16_t)dummy; idxb[25] = 0xFFFFFFFFu; }
+            if (tid == 0) { T[dummy] = (uint16_t)dummy; idxb[SEG_CI_NOID] = 0xFFFFFFFFu; }
         }
         PLS_SYNC();
-        if (idxb[30]) {
+        if (idxb[SEG_CI_WIDE]) {
             /* some segment of the pass has more distinct states than the stride holds: once more, wider (its last dense ids would alias) */
-            const uint32_t need = idxb[27];
+            const uint32_t need = idxb[SEG_CI_DMAX];
             PLS_SYNC();
-            PLS_THREADS(tid, CT) { if (tid == 0) { idxb[30] = 0u; idxb[27] = 0u; } }
+            PLS_THREADS(tid, CT) { if (tid == 0) { idxb[SEG_CI_WIDE] = 0u; idxb[SEG_CI_DMAX] = 0u; } }
             PLS_SYNC();
             while ((1u << sh) < need && sh < 8) sh++;
             nwide++;
@@ -2281,7 +2213,7 @@ PLS_HD void seg_chain_body(const SegJob &j, const SegParams &P, const SegCtlView
         PLS_SYNC();
         if (prof) tc[2] = PLS_CLOCK();
         /* -- walk: from position pos0 of the pass (0; behind a repair: the position behind the walked segment -- the tables gathered for the
-         *    pass are still good, only the walk is done again from there), whose id is idxb[28] and whose entry state idxb[26] -- */
+         *    pass are still good, only the walk is done again from there), whose id is idxb[SEG_CI_START_ID] and whose entry state idxb[SEG_CI_ENTRY0] -- */
         uint32_t pos0 = 0;
         bool done = false, next_pass = false;
         for (;;) {
@@ -2290,7 +2222,7 @@ PLS_HD void seg_chain_body(const SegJob &j, const SegParams &P, const SegCtlView
                 if ((uint32_t)tid >= bq && (uint32_t)tid < nblk) {
                     /* thread b: the true id at the head of block b (across the composed tables), then through the block.  Every lane walks the
                      * heads of ALL blocks (the same chain of loads in every lane: no lane-dependent loop) and keeps its own */
-                    const uint32_t sid = idxb[28];
+                    const uint32_t sid = idxb[SEG_CI_START_ID];
                     uint32_t g, b0 = bq;
                     if (off == 0u) g = sid < stride ? ((bq << sh) | sid) : gdummy;
                     else {
@@ -2326,7 +2258,7 @@ PLS_HD void seg_chain_body(const SegJob &j, const SegParams &P, const SegCtlView
                     uint32_t d = dn[k];
                     if ((eflags & 2) && k >= pos0 + 1u) d = SEG_INVALID;                  /* (test hook: every second segment through the repair) */
                     const uint32_t sg = s0 + a + k;
-                    if (d == SEG_INVALID) { PLS_ATOMIC_MIN(&idxb[25], k); continue; }
+                    if (d == SEG_INVALID) { PLS_ATOMIC_MIN(&idxb[SEG_CI_NOID], k); continue; }
                     dnout[(size_t)SEGF(sg) * 4] = (uint16_t)d;
                     uint32_t dL = d;                                  /* the id the unit's LAST segment keeps its records under */
                     if (E > 1u && SEGL(sg) > SEGF(sg)) {
@@ -2352,14 +2284,14 @@ PLS_HD void seg_chain_body(const SegJob &j, const SegParams &P, const SegCtlView
             }
             PLS_SYNC();
             if (prof && pos0 == 0u) { tc[3] = PLS_CLOCK(); for (int q = 0; q < 3; q++) tacc[q] += tc[q + 1] - tc[q]; }
-            uint32_t fb = idxb[25];
+            uint32_t fb = idxb[SEG_CI_NOID];
             if (fb == 0xFFFFFFFFu) {
                 /* the rest of the pass has ids: the next one starts at its landing position */
                 const uint32_t nd = dn[ntr], ne_ = entL[ntr];
                 PLS_SYNC();
                 a += ntr;
                 if (a >= ns) { done = true; break; }                   /* (the landing position was the row's last segment: its id is out) */
-                PLS_THREADS(tid, CT) { if (tid == 0) { idxb[28] = nd; idxb[26] = ne_; } }
+                PLS_THREADS(tid, CT) { if (tid == 0) { idxb[SEG_CI_START_ID] = nd; idxb[SEG_CI_ENTRY0] = ne_; } }
                 PLS_SYNC();
                 next_pass = true;
                 break;
@@ -2371,7 +2303,7 @@ PLS_HD void seg_chain_body(const SegJob &j, const SegParams &P, const SegCtlView
                  * checkpoints from its entry state), and the pixel behind it is reported as this candidate's first failed decision: an epoch starts
                  * there, as behind any failed validation (seg_ctl_body) -- exact, and two attempts instead of 16 us on the rare row. */
                 if (fb > pos0 && entL[fb] == SEG_NOSTATE) fb--;
-                const uint32_t estb = fb > pos0 ? entL[fb] : idxb[26];
+                const uint32_t estb = fb > pos0 ? entL[fb] : idxb[SEG_CI_ENTRY0];
                 PLS_SYNC();
                 const uint32_t kqb = a + fb, sgb = SEGF(s0 + kqb);      /* (the unit's FIRST segment: the replay walks that one from the entry state; with units, what
                                                                             lies behind it in the unit has no state to start from either) */
@@ -2379,7 +2311,7 @@ PLS_HD void seg_chain_body(const SegJob &j, const SegParams &P, const SegCtlView
                     if (tid == 0) {
                         SEG_DEBUG_COUNT(2, fb);
                         SEG_DEBUG_BREAK(f, c, sgb, estb, cv.y);
-                        idxb[24]++;
+                        idxb[SEG_CI_REPAIRS]++;
                         PLS_ATOMIC_ADD(&j.self->nbreak, 1u);
                         if (j.break_word) PLS_HOST_VISIBLE_ADD(j.break_word, 1u);
                         dnout[(size_t)sgb * 4] = (uint16_t)SEG_INVALID; entry[(size_t)sgb * 4] = estb;
@@ -2397,12 +2329,12 @@ PLS_HD void seg_chain_body(const SegJob &j, const SegParams &P, const SegCtlView
             /* -- repair: position fb has no id (its entry state is not in the segment's entry set) -- or position fb - 1 has an id but no exit
              *    state (its lane left what the tables cover).  That segment is walked step by step from its entry state. -- */
             if (fb > pos0 && entL[fb] == SEG_NOSTATE) fb--;
-            const uint32_t est = fb > pos0 ? entL[fb] : idxb[26];
-            const bool have_tables = idxb[31] != 0u;
+            const uint32_t est = fb > pos0 ? entL[fb] : idxb[SEG_CI_ENTRY0];
+            const bool have_tables = idxb[SEG_CI_TABLES] != 0u;
             PLS_SYNC();
             const uint32_t kq = a + fb, sgq = s0 + kq;                  /* the position and the segment walked */
             const uint32_t xq = sgq * SEG_L;
-            SegPix *pxr = (SegPix *)(uint32_t *)(twr + SEG_TBL_WORDS);  /* [SEG_L + 1] */
+            SegPix *pxr = (SegPix *)LDS::pxr(smem, nseg);                 /* [SEG_L + 1] */
             const SegGeo G_ = seg_geo((int)cv.s);
             PLS_THREADS(tid, CT) {
                 if (!have_tables) {
@@ -2411,7 +2343,7 @@ PLS_HD void seg_chain_body(const SegJob &j, const SegParams &P, const SegCtlView
                     if (tid >= 256 && tid < 768) lut[tid - 256] = P.lut_a[tid - 256];
                 }
                 if (tid >= 768 && tid < 768 + SEG_L) pxr[tid - 768] = seg_pix_load(row, nab, e0g, bpp, seg_umin(xq + (uint32_t)(tid - 768), W - 1u), c);
-                if (tid == 0) { SEG_DEBUG_COUNT(2, fb); SEG_DEBUG_REPAIR(f, c, sgq, est, idxb[28]); idxb[31] = 1u; idxb[24]++; idxb[25] = 0xFFFFFFFFu; dnout[(size_t)sgq * 4] = (uint16_t)SEG_INVALID; entry[(size_t)sgq * 4] = est; }
+                if (tid == 0) { SEG_DEBUG_COUNT(2, fb); SEG_DEBUG_REPAIR(f, c, sgq, est, idxb[SEG_CI_START_ID]); idxb[SEG_CI_TABLES] = 1u; idxb[SEG_CI_REPAIRS]++; idxb[SEG_CI_NOID] = 0xFFFFFFFFu; dnout[(size_t)sgq * 4] = (uint16_t)SEG_INVALID; entry[(size_t)sgq * 4] = est; }
             }
             PLS_SYNC();
             if (kq >= ns) { done = true; break; }                      /* the row's last segment: the replay walks it from its entry state, nothing follows */
@@ -2428,7 +2360,7 @@ PLS_HD void seg_chain_body(const SegJob &j, const SegParams &P, const SegCtlView
                     }
                     if (nid >= SEG_NSP || nid >= dcnt[(size_t)(sgq + 1u) * 4]) nid = SEG_INVALID;
                     entry[(size_t)(sgq + 1u) * 4] = nps;
-                    idxb[26] = nps; idxb[28] = nid;
+                    idxb[SEG_CI_ENTRY0] = nps; idxb[SEG_CI_START_ID] = nid;
                 }
             }
             PLS_SYNC();
@@ -2441,7 +2373,7 @@ PLS_HD void seg_chain_body(const SegJob &j, const SegParams &P, const SegCtlView
     }
     PLS_THREADS(tid, CT) {
         if (tid == 0) {
-            if (idxb[24]) PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_WALKED], idxb[24]);       /* segments walked step by step (reported with the image's result) */
+            if (idxb[SEG_CI_REPAIRS]) PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_WALKED], idxb[SEG_CI_REPAIRS]);       /* segments walked step by step (reported with the image's result) */
             if (prof) {
                 for (int q = 0; q < 3; q++) { PLS_ATOMIC_MAX(&j.result[PLR_SEG_CHAIN_MAX + q], (int32_t)tacc[q]); PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_CHAIN_SUM + q], (uint32_t)tacc[q]); }
                 PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_CHAIN_RUNS], 1u);
@@ -2474,8 +2406,8 @@ PLS_HD void seg_extremes_body(const SegJob &j, const SegParams &P, const SegCtlV
     if (cv.finished || !j.rowmm) return;
     const uint32_t W = j.W, bpp = j.bpp, y = cv.y;
     const uint32_t *row = seg_row_orig(j, y), *e0g = seg_e0(j, y);
-    uint32_t *mm = (uint32_t *)smem;                            /* [0] max, [1] min, biased (unsigned compare) */
-    PLS_THREADS(tid, CT) { if (tid == 0) { mm[0] = 0x80000000u ^ (uint32_t)(-(1 << 30)); mm[1] = 0x80000000u ^ (uint32_t)(1 << 30); } }
+    uint32_t *mm = SegLdsExtremes::mm(smem);                    /* SEG_MM_*: biased (unsigned compare) */
+    PLS_THREADS(tid, CT) { if (tid == 0) { mm[SEG_MM_MAX] = 0x80000000u ^ (uint32_t)(-(1 << 30)); mm[SEG_MM_MIN] = 0x80000000u ^ (uint32_t)(1 << 30); } }
     PLS_SYNC();
     PLS_THREADS(tid, CT) {
         int vmax = -(1 << 30), vmin = 1 << 30;
@@ -2496,10 +2428,10 @@ PLS_HD void seg_extremes_body(const SegJob &j, const SegParams &P, const SegCtlV
             }
         }
         vmax = pls_wave_max_i(vmax); vmin = pls_wave_min_i(vmin);
-        if (PLS_WAVE_LEADER(tid)) { PLS_ATOMIC_MAX_U(&mm[0], 0x80000000u ^ (uint32_t)vmax); PLS_ATOMIC_MIN(&mm[1], 0x80000000u ^ (uint32_t)vmin); }
+        if (PLS_WAVE_LEADER(tid)) { PLS_ATOMIC_MAX_U(&mm[SEG_MM_MAX], 0x80000000u ^ (uint32_t)vmax); PLS_ATOMIC_MIN(&mm[SEG_MM_MIN], 0x80000000u ^ (uint32_t)vmin); }
     }
     PLS_SYNC();
-    PLS_THREADS(tid, CT) { if (tid == 0) { SEG_AS_GLB int32_t *rmm = seg_rowmm(j, y); rmm[0] = (int)(mm[0] ^ 0x80000000u); rmm[1] = (int)(mm[1] ^ 0x80000000u); } }
+    PLS_THREADS(tid, CT) { if (tid == 0) { SEG_AS_GLB int32_t *rmm = seg_rowmm(j, y); rmm[0] = (int)(mm[SEG_MM_MAX] ^ 0x80000000u); rmm[1] = (int)(mm[SEG_MM_MIN] ^ 0x80000000u); } }
 }
 
 template <int RNT>
@@ -2514,16 +2446,12 @@ PLS_HD void seg_replay_body(const SegJob &j, const SegParams &P, const SegCtlVie
     const uint32_t first = sx / SEG_L;
     const uint32_t seg0 = (uint32_t)grp * SEG_GRP, x0g = seg0 * SEG_L;
     const bool walk = !lazy && sx < W && seg0 + SEG_GRP > first;   /* (else: the whole group is validated already -- its share of the row's sums is still wanted) */
-    uint32_t *Hf = (uint32_t *)smem, *rank = Hf + 256, *lut = Hf + 512, *tw = Hf + 1024;
-    SegPix *px = (SegPix *)(tw + SEG_TBL_WORDS);              /* [SEG_GRP][SEG_L][4] */
-    uint32_t *cnt = (uint32_t *)(px + SEG_GRP * SEG_L * 4);   /* [SEG_GRP][64]: four bins a word (seg_cnt_add) */
-    uint32_t *lane = cnt + SEG_GRP * 64;                      /* [SEG_GRP * SEG_PARTS * 4][2]: start state, first | end pixel << 16 (or ~0: idle) */
-    uint32_t *cwl = lane + SEG_GRP * SEG_PARTS * 4 * 2;       /* [SEG_REPLAY_THREADS][4] the group's candidate words */
-    uint32_t *oaL = cwl + SEG_REPLAY_THREADS * 4;             /* [SEG_REPLAY_THREADS + 1] the ORIGINAL row above, from the pixel in front of the group; [+1] the original pixel in front of the group, [+2] its new bytes */
+    typedef SegLdsReplay LDS;
+    uint32_t *Hf = LDS::Hf(smem), *rank = LDS::rank(smem), *lut = LDS::lut(smem), *tw = LDS::tw(smem);
+    SegPix *px = LDS::px(smem);
+    uint32_t *cnt = LDS::cnt(smem), *lane = LDS::lane(smem), *cwl = LDS::cwl(smem), *oaL = LDS::oaL(smem);
     /* (behind the walk, in the tables' place) */
-    uint32_t *rm = tw;                                         /* [768] none's bound: largest H0 within reach of a centre value (centre + 256) */
-    uint32_t *red = rm + 768;                                  /* [16] reductions: derr lo/hi, hs[5], -, -, -, lb lo/hi, reach, -, max, min */
-    uint32_t *h0s = red + 16;                                  /* [256] the committed histogram */
+    uint32_t *rm = LDS::rm(smem), *red = LDS::red(smem), *h0s = LDS::h0s(smem);
     const uint32_t y = cv.y;
     const uint32_t *row = seg_row_orig(j, y), *nab = y ? j.img + (size_t)(y - 1u) * W : nullptr, *e0g = seg_e0(j, y);
     const uint32_t *oab = y ? seg_row_orig(j, y - 1u) : nullptr; /* the ORIGINAL row above */
@@ -2616,7 +2544,7 @@ PLS_HD void seg_replay_body(const SegJob &j, const SegParams &P, const SegCtlVie
         PLS_SYNC();
     }
     SegAcc &A = j.acc[par];
-    PLS_THREADS(tid, RNT) { if (tid < 16) red[tid] = tid == 14 ? (0x80000000u ^ (uint32_t)(-(1 << 30))) : (tid == 15 ? (0x80000000u ^ (uint32_t)(1 << 30)) : 0u); }   /* ([14], [15] biased: unsigned max / min) */
+    PLS_THREADS(tid, RNT) { if (tid < 16) red[tid] = tid == SEG_RR_MAX ? (0x80000000u ^ (uint32_t)(-(1 << 30))) : (tid == SEG_RR_MIN ? (0x80000000u ^ (uint32_t)(1 << 30)) : 0u); }   /* (SEG_RR_MAX, SEG_RR_MIN biased: unsigned max / min) */
     PLS_SYNC();
     {
         /* -- the first half of the workgroup: every thread its pixel: the words out (what the walkers have just written), the pixel's share of the
@@ -2675,8 +2603,8 @@ PLS_HD void seg_replay_body(const SegJob &j, const SegParams &P, const SegCtlVie
             derr = (uint64_t)pls_wave_sum_u32((uint32_t)derr);
             if (adaptive) for (int g = 0; g < SEG_NFILT; g++) hs[g] = pls_wave_sum_u32(hs[g]);
             if (PLS_WAVE_LEADER(tid)) {
-                PLS_ATOMIC_ADD64((uint64_t *)&red[0], derr);
-                if (adaptive) for (int g = 0; g < SEG_NFILT; g++) PLS_ATOMIC_ADD(&red[2 + g], hs[g]);
+                PLS_ATOMIC_ADD64((uint64_t *)&red[SEG_RR_DERR], derr);
+                if (adaptive) for (int g = 0; g < SEG_NFILT; g++) PLS_ATOMIC_ADD(&red[SEG_RR_HS + g], hs[g]);
             }
         }
     }
@@ -2688,11 +2616,11 @@ PLS_HD void seg_replay_body(const SegJob &j, const SegParams &P, const SegCtlVie
         const int32_t *rmm = seg_rowmm(j, y);
         PLS_THREADS(tid, RNT) {
             /* the row's extremes of orig + incoming error (seg_extremes_body, the launch before) */
-            if (tid == 0) red[12] = (uint32_t)seg_none_reach(j, P, (int)cv.s, rmm[0], rmm[1]);
+            if (tid == 0) red[SEG_RR_REACH] = (uint32_t)seg_none_reach(j, P, (int)cv.s, rmm[0], rmm[1]);
             if (tid >= 64 && tid < 64 + 256) h0s[tid - 64] = j.H0[par * 256 + (tid - 64)];
         }
         PLS_SYNC();
-        R = (int)red[12];
+        R = (int)red[SEG_RR_REACH];
         if (R >= 0) {
             PLS_THREADS(tid, RNT) {
                 for (int i = tid; i < 768; i += RNT) {
@@ -2727,7 +2655,7 @@ PLS_HD void seg_replay_body(const SegJob &j, const SegParams &P, const SegCtlVie
                     }
                 }
                 lb = pls_wave_sum_u64(lb);
-                if (PLS_WAVE_LEADER(tid) && lb) PLS_ATOMIC_ADD64((uint64_t *)&red[10], lb);
+                if (PLS_WAVE_LEADER(tid) && lb) PLS_ATOMIC_ADD64((uint64_t *)&red[SEG_RR_LB], lb);
             }
         }
     }
@@ -2735,10 +2663,10 @@ PLS_HD void seg_replay_body(const SegJob &j, const SegParams &P, const SegCtlVie
     PLS_THREADS(tid, RNT) {
         if (tid == 0) {
             if (!lazy) {
-                PLS_ATOMIC_ADD64(&A.derr[f], *(uint64_t *)&red[0]);
-                if (adaptive) for (int g = 0; g < SEG_NFILT; g++) PLS_ATOMIC_ADD(&A.hs[f][g], red[2 + g]);
+                PLS_ATOMIC_ADD64(&A.derr[f], *(uint64_t *)&red[SEG_RR_DERR]);
+                if (adaptive) for (int g = 0; g < SEG_NFILT; g++) PLS_ATOMIC_ADD(&A.hs[f][g], red[SEG_RR_HS + g]);
             }
-            if (f == 0 && R >= 0) { PLS_ATOMIC_ADD64(&A.none_lb, *(uint64_t *)&red[10]); PLS_ATOMIC_ADD(&A.lb_valid, 1u); }
+            if (f == 0 && R >= 0) { PLS_ATOMIC_ADD64(&A.none_lb, *(uint64_t *)&red[SEG_RR_LB]); PLS_ATOMIC_ADD(&A.lb_valid, 1u); }
         }
     }
 }
@@ -2759,10 +2687,6 @@ struct SegVal {
     const uint32_t *btop;         /* [2][SEG_NBAND][4]: per band of either sign: largest upper count bound, its bin, second largest */
     const uint32_t *hiG, *loG;    /* [256] frequency of a bin: upper bound (through the group's end), lower bound (at the group's start) */
 };
-#define SEG_BINB_STRIDE (SEG_L * 4 + 4)
-#define SEG_PC_SEG (SEG_L + 1)                   /* words per segment and slot (one pad word: bank spread) */
-#define SEG_PC_STRIDE_V(V) ((V) * SEG_PC_SEG + 8)
-#define SEG_NBAND 20
 PLS_HD uint32_t seg_pc_get(const uint32_t *pcw, uint32_t pc_stride, uint32_t slot, int d)
 {
     const uint32_t w = pcw[(size_t)slot * pc_stride + (d / (SEG_L * 4)) * SEG_PC_SEG + ((d % (SEG_L * 4)) >> 2)];
@@ -2835,7 +2759,7 @@ PLS_HD int seg_validate_one(const SegVal &V, int d, int mode)
         const uint32_t hu = V.H0[ub] + cs[ub] + n;
         if (u_wins_ties ? hu >= hv_exact : hu > hv_exact) return 0;
     }
-    if (result == 2) PLS_ATOMIC_ADD(&V.wbits[8], 1u);
+    if (result == 2) PLS_ATOMIC_ADD(&V.wbits[SEG_WB_PENDING], 1u);
     return result;
 }
 
@@ -2879,25 +2803,14 @@ PLS_HD void seg_post_body(const SegJob &j, const SegParams &P, const SegCtlView 
     constexpr int NPX = VGRP * SEG_L;                       /* pixels of a group */
     constexpr int NW = SEG_WATCH_OF(VGRP);                  /* slots of the watched bins */
     constexpr int PCS = SEG_PC_STRIDE_V(VGRP);              /* words per slot of the watched bins' prefix counts */
-    uint32_t *H0 = (uint32_t *)smem, *rank = H0 + 256;
-    uint32_t *cum = H0 + 768;                                  /* [VGRP + 1][256]: bumps in front of each segment of the group (staging: row sl + 1 = the bumps OF segment sl) */
-    uint32_t *cw = cum + (VGRP + 1) * 256;                 /* [(NPX + 2)][4] candidate words, from pixel xg0 - 2 */
-    uint32_t *red = cw + (NPX + 2) * 4;                        /* reductions: derr lo/hi, cost, hs[5], fail, lb lo/hi */
-    uint32_t *lut = red + 64;                                  /* [512] split table */
-    uint32_t *ro = lut + 512;                                  /* [NPX + 1] original row, from pixel xg0 - 1 */
-    uint32_t *na = ro + NPX + 2;                               /* [NPX + 1] optimised row above */
-    uint32_t *e0 = na + NPX + 2;                               /* [NPX][2] incoming error */
-    uint32_t *wbits = e0 + 2 * NPX;                            /* [8] bitmap of watched bins, [8] pending decisions / slots in use, [9..] bin of each slot */
-    uint8_t *slot_of = (uint8_t *)(wbits + 32);                /* [256] slot of a watched bin or 255 */
-    uint8_t *pend = slot_of + 256;                             /* [NPX * 4] decision waits for pass 3 */
-    uint8_t *binb = pend + NPX * 4;                            /* [VGRP][SEG_BINB_STRIDE] bin of every decision */
-    uint32_t *pcw = (uint32_t *)(binb + VGRP * SEG_BINB_STRIDE);   /* [NW][PCS] prefix counts of the watched bins */
-    uint32_t *cumx = pcw;                                      /* [VGRP][256] (staging only, before pcw is written: barriers lie between) the bumps of the replay group's segments in front of this half */
+    typedef SegLdsPost<VGRP> LDS;
+    uint32_t *H0 = LDS::H0(smem), *rank = LDS::rank(smem), *cum = LDS::cum(smem), *cw = LDS::cw(smem), *red = LDS::red(smem), *lut = LDS::lut(smem);
+    uint32_t *ro = LDS::ro(smem), *na = LDS::na(smem), *e0 = LDS::e0(smem), *wbits = LDS::wbits(smem);
+    uint8_t *slot_of = LDS::slot_of(smem), *pend = LDS::pend(smem), *binb = LDS::binb(smem);
+    uint32_t *pcw = LDS::pcw(smem), *btop = LDS::btop(smem), *hiG = LDS::hiG(smem), *loG = LDS::loG(smem);
+    uint32_t *cumx = LDS::cumx(smem);                          /* (staging only: in pcw's place) */
     constexpr int NFR = SEG_GRP - VGRP;                     /* segments of the replay group that can lie in front of this validation group */
-    static_assert(NW * PCS >= NFR * 256, "the staged counts of the segments in front fit where the prefix counts go later");
     static_assert(VGRP + NFR == SEG_THREADS / 64 && (NFR == 0 || NFR == VGRP), "the staging burst's sixteen rows of lanes: this group's segments, then the ones in front");
-    uint32_t *btop = pcw + NW * PCS;          /* [2][SEG_NBAND][4] */
-    uint32_t *hiG = btop + 2 * SEG_NBAND * 4, *loG = hiG + 256;
     const uint32_t y = cv.y;
     const uint32_t *row = seg_row_orig(j, y), *nab = y ? j.img + (size_t)(y - 1u) * W : nullptr, *e0g = seg_e0(j, y);
     const SegGeo G = seg_geo((int)cv.s);
@@ -2961,7 +2874,7 @@ PLS_HD void seg_post_body(const SegJob &j, const SegParams &P, const SegCtlView 
             }
         }
         if (tid < 256) { H0[tid] = vh0; rank[tid] = vrank; hiG[tid] = vbefore; }      /* (hiG: parked until the prefix pass has read it; the bounds are written behind that) */
-        if (tid < 16) red[tid] = tid == 8 ? SEG_NOFAIL : (tid == 9 ? vgl : 0u);
+        if (tid < 16) red[tid] = tid == SEG_PR_FAIL ? SEG_NOFAIL : (tid == SEG_PR_LEFT ? vgl : 0u);
         if (tid >= 256 && tid < 768) lut[tid - 256] = vlut;
         PLS_UNROLL
         for (int q = 0; q < NCW; q++) { const int i = tid + q * SEG_THREADS; if (i < (NPX + 2) * 4) cw[i] = vcw[q]; }
@@ -3000,7 +2913,7 @@ PLS_HD void seg_post_body(const SegJob &j, const SegParams &P, const SegCtlView 
     V.sx = sx; V.xg0 = xg0; V.W = W; V.wbits = wbits; V.slot_of = slot_of; V.pcw = pcw; V.pc_stride = PCS; V.binb = binb; V.btop = btop; V.hiG = hiG; V.loG = loG;
     PLS_THREADS(tid, SEG_THREADS) {
         if (tid < 8) wbits[tid] = 0u;
-        if (tid == 8) wbits[8] = 0u;                                   /* number of pending decisions */
+        if (tid == SEG_WB_PENDING) wbits[SEG_WB_PENDING] = 0u;                                   /* number of pending decisions */
         if (tid >= 64 && tid < 128) ((uint32_t *)slot_of)[tid - 64] = 0xffffffffu;
         if (tid >= 256 && tid < 512) { const int b = tid - 256; hiG[b] = H0[b] + cum[VGRP * 256 + b]; loG[b] = H0[b] + cum[b]; }
     }
@@ -3025,26 +2938,26 @@ PLS_HD void seg_post_body(const SegJob &j, const SegParams &P, const SegCtlView 
         for (int d = tid; d < NPX * 4; d += SEG_THREADS) {
             const int r = seg_validate_one(V, d, 0);
             pend[d] = (uint8_t)(r == 2);
-            if (r == 0) PLS_ATOMIC_MIN(&red[8], (xg0 + (uint32_t)(d >> 2)) * 4u + (uint32_t)(d & 3));
+            if (r == 0) PLS_ATOMIC_MIN(&red[SEG_PR_FAIL], (xg0 + (uint32_t)(d >> 2)) * 4u + (uint32_t)(d & 3));
         }
     }
     PLS_SYNC();
     if (prof) tk[2] = PLS_CLOCK();
-    if (wbits[8]) {
+    if (wbits[SEG_WB_PENDING]) {
         PLS_THREADS(tid, SEG_THREADS) {
             if (tid == 0) {
                 int ns = 0;
-                red[13] = wbits[8];
-                for (int b = 0; b < 256 && ns < NW; b++) if ((wbits[b >> 5] >> (b & 31)) & 1u) { slot_of[b] = (uint8_t)ns; wbits[9 + ns] = (uint32_t)b; ns++; }
-                wbits[8] = (uint32_t)ns;
+                red[SEG_PR_PENDING] = wbits[SEG_WB_PENDING];
+                for (int b = 0; b < 256 && ns < NW; b++) if ((wbits[b >> 5] >> (b & 31)) & 1u) { slot_of[b] = (uint8_t)ns; wbits[SEG_WB_BIN + ns] = (uint32_t)b; ns++; }
+                wbits[SEG_WB_PENDING] = (uint32_t)ns;
             }
         }
         PLS_SYNC();
         PLS_THREADS(tid, SEG_THREADS) {
             const int sl = tid / NW, slot = tid % NW;
-            if (sl < VGRP && slot < (int)wbits[8]) {
+            if (sl < VGRP && slot < (int)wbits[SEG_WB_PENDING]) {
                 /* bumps of the slot's bin in front of every decision of segment sl, four decisions per word in and out */
-                const uint32_t b = wbits[9 + slot];
+                const uint32_t b = wbits[SEG_WB_BIN + slot];
                 const uint32_t *src = (const uint32_t *)(binb + sl * SEG_BINB_STRIDE);
                 uint32_t *dst = pcw + (size_t)slot * PCS + sl * SEG_PC_SEG;
                 const int e0seg = seg_max(0, ((int)sx - (int)xg0 - sl * SEG_L) * 4);          /* decisions of the segment in front of the epoch do not count */
@@ -3064,7 +2977,7 @@ PLS_HD void seg_post_body(const SegJob &j, const SegParams &P, const SegCtlView 
         PLS_THREADS(tid, SEG_THREADS) {
             for (int d = tid; d < NPX * 4; d += SEG_THREADS) {
                 if (!pend[d]) continue;
-                if (seg_validate_one(V, d, 1) == 0) PLS_ATOMIC_MIN(&red[8], (xg0 + (uint32_t)(d >> 2)) * 4u + (uint32_t)(d & 3));
+                if (seg_validate_one(V, d, 1) == 0) PLS_ATOMIC_MIN(&red[SEG_PR_FAIL], (xg0 + (uint32_t)(d >> 2)) * 4u + (uint32_t)(d & 3));
             }
         }
     }
@@ -3073,19 +2986,19 @@ PLS_HD void seg_post_body(const SegJob &j, const SegParams &P, const SegCtlView 
     /* the left bytes the row sums took for the pixel in front of this replay group (seg_row_sums) against what was written there */
     PLS_THREADS(tid, SEG_THREADS) {
         if (tid < 4 && (uint32_t)tid < bpp && seg0 == segp && xg0 > sx && xg0 > 0u) {
-            if (seg_cand_byte(cw[1 * 4 + tid]) != (int)((red[9] >> (8 * tid)) & 255u)) PLS_ATOMIC_MIN(&red[8], xg0 * 4u + (uint32_t)tid);
+            if (seg_cand_byte(cw[1 * 4 + tid]) != (int)((red[SEG_PR_LEFT] >> (8 * tid)) & 255u)) PLS_ATOMIC_MIN(&red[SEG_PR_FAIL], xg0 * 4u + (uint32_t)tid);
         }
     }
     PLS_SYNC();
     PLS_THREADS(tid, SEG_THREADS) {
         if (tid == 0) {
             SegAcc &A = j.acc[par];
-            if (red[8] != SEG_NOFAIL) { PLS_ATOMIC_MIN(&A.fail[f], red[8]); PLS_ATOMIC_OR(&A.failmask, 1u << f); PLS_ATOMIC_OR(&j.self->vfail[par], 1u << f); }
+            if (red[SEG_PR_FAIL] != SEG_NOFAIL) { PLS_ATOMIC_MIN(&A.fail[f], red[SEG_PR_FAIL]); PLS_ATOMIC_OR(&A.failmask, 1u << f); PLS_ATOMIC_OR(&j.self->vfail[par], 1u << f); }
             if (prof) {
                 tk[4] = PLS_CLOCK(); tk[5] = tk[4];
                 for (int q = 0; q < PLR_SEG_VAL_PHASES; q++) { PLS_ATOMIC_MAX(&j.result[PLR_SEG_VAL_MAX + q], (int32_t)(tk[q + 1] - tk[q])); PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_VAL_SUM + q], (uint32_t)(tk[q + 1] - tk[q])); }
                 PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_VAL_RUNS], 1u);
-                PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_VAL_PENDING], red[13]);
+                PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_VAL_PENDING], red[SEG_PR_PENDING]);
             }
         }
     }
@@ -3098,11 +3011,11 @@ struct SegDecision {
     uint64_t cost[SEG_NFILT];
     uint32_t ignore, pad_;          /* bit f: whether candidate f's row of that attempt is valid does not matter to this decision */
 };
-static_assert(sizeof(SegDecision) / 4 <= 20, "seg_decide_wg shares it through 20 words");
+static_assert(sizeof(SegDecision) / 4 <= SEG_DEC_WORDS, "seg_decide_wg shares it through SEG_DEC_WORDS words");
 
 /* what the attempt that just finished (control block `cur`, sums `A`) means -- in two steps, so that five lanes can look at a
  * candidate each before one lane draws the conclusion.  Step 1, candidate f: its row cost, or why it has none yet. */
-static_assert(offsetof(SegDecision, cost) == 24, "seg_ctl_body reads cost[f] out of the shared copy by word index");
+static_assert(offsetof(SegDecision, cost) == SEG_DEC_COST_WORD * 4, "seg_ctl_body reads cost[f] out of the shared copy by word index");
 struct SegCandDec { uint64_t cost; uint32_t state; uint32_t pad_; };      /* state 0: cost is final (or ~0: no acceptable row), 1: lazy (none, not run yet), 2: failed validation */
 /* optimistic: the validation of the attempt is still out (it runs next to this decision): every row is taken for valid */
 template <class CT, class AT>
@@ -3256,11 +3169,10 @@ PLS_HD void seg_entropy_costs(seg_lds_u32 spec, seg_lds_u32 ecost, int nt)
     PLS_SYNC();
 }
 
-/* the whole workgroup: lanes 0..4 step 1, lane 0 step 2; the result in shared memory (dshare: 16 words, cdw: 20 words in front of it) */
 /* the control block, the sums and the decision in shared memory, with the address space in the type (ds_* instead of FLAT accesses) */
 typedef SEG_AS_LDS const SegCtl seg_lds_ctl_t;
 typedef SEG_AS_LDS const SegAcc seg_lds_acc_t;
-/* the whole workgroup: lanes 0..4 step 1, lane 0 step 2; the result in shared memory (dshare: 16 words, cdw: 20 words behind it) */
+/* the whole workgroup: lanes 0..4 step 1, lane 0 step 2; the result in shared memory (pl_seg_lds.h: dshare = the region `decision`, SEG_DEC_WORDS words; cdw = `verdict`, four words a candidate) */
 PLS_HD SegDecision seg_decide_wg(const SegJob &j, const SegParams &P, int attempt, seg_lds_ctl_t &cur, seg_lds_acc_t &A, seg_lds_u32 ecost, seg_lds_u32 cdw, seg_lds_u32 dshare, int nt, bool optimistic)
 {
     PLS_THREADS(tid, nt) {
@@ -3294,13 +3206,12 @@ PLS_HD SegDecision seg_decide_wg(const SegJob &j, const SegParams &P, int attemp
  * Tie classes are band local: cls[sgn][b] = offset inside its band (of that sign) of the FIRST bin with the same (H, rank) as bin b,
  * so two bins of one band have equal classes iff their keys are equal -- all the tie test of seg_step_fast needs (the original
  * symbol and the leader it may replace always lie in the same band). */
-PLS_HD void seg_build_tables(SEG_AS_GLB uint32_t *out, seg_lds_u32 H, seg_lds_u32 rank, seg_lds_u32 scratch, seg_lds_u32 stage, int s, int q, int nt, int part, int nparts, int32_t *profslots = nullptr)
+PLS_HD void seg_build_tables(SEG_AS_GLB uint32_t *out, seg_lds_u32 H, seg_lds_u32 rank, SEG_AS_LDS uint64_t *K, seg_lds_u32 stage, int s, int q, int nt, int part, int nparts, int32_t *profslots = nullptr)
 {
     unsigned long long tb[4] = { 0, 0, 0, 0 };
     if (profslots) tb[0] = PLS_CLOCK();
     seg_lds_u8 cls = (seg_lds_u8)(stage + 4 * SEG_TN);        /* [2][256] */
-    /* [256] (H << 32 | rank) of a bin: one 64-bit read and one compare per bin (scratch: 512 words) */
-    SEG_AS_LDS uint64_t *K = (SEG_AS_LDS uint64_t *)scratch;
+    /* K: [256] (H << 32 | rank) of a bin: one 64-bit read and one compare per bin (512 words: pl_seg_lds.h, the overlay K of seg_ctl_body) */
     PLS_THREADS(tid, nt) { for (int b = tid; b < 256; b += nt) K[b] = ((uint64_t)H[b] << 32) | rank[b]; }
     PLS_SYNC();
     if (profslots) tb[1] = PLS_CLOCK();
@@ -3380,12 +3291,10 @@ PLS_HD void seg_ctl_commit(const SegJob &j, const SegParams &P, int par, int cw,
 {
     const int k1 = seg_k_prev(par), k2 = seg_k_prev2(par);
     const uint32_t W = j.W, H = j.H, bpp = j.bpp;
-    seg_lds_u32 lutb = (seg_lds_u32)smem + 8;                  /* [512] next-rows terms of the split */
-    seg_lds_u32 ctlc = lutb + 512, accc = ctlc + (sizeof(SegCtl) + 7) / 8 * 2, dshare = accc + (sizeof(SegAcc) + 7) / 8 * 2;
-    seg_lds_u32 ecost = dshare + 40;                           /* [8] entropy cost of every candidate row; [48]: failmask of the attempt two before */
-    seg_lds_u32 cw5 = dshare + 56;                             /* [SEG_NFILT][(SEG_COMMIT_W + 4)][4] every candidate's words of this workgroup's pixels, two more on either side; the winner's become their terms */
-    seg_lds_u32 ext = cw5 + SEG_NFILT * (SEG_COMMIT_W + 4) * 4;/* [2][SEG_COMMIT_W][2]: err1 of either row parity (which row is committed is in the control block these loads ride along with) */
-    seg_lds_u32 spec = ext + SEG_COMMIT_W * 4;                 /* [SEG_NFILT + 1][256] the bumps of every candidate's row, the committed histogram (for the row costs: seg_entropy_costs) */
+    typedef SegLdsCommit LDS;
+    seg_lds_u32 lutb = LDS::lutb(smem), ctlc = LDS::ctlc(smem), accc = LDS::accc(smem);
+    seg_lds_u32 decision = LDS::decision(smem), verdict = LDS::verdict(smem), ecost = LDS::ecost(smem), failmask = LDS::failmask(smem);
+    seg_lds_u32 cw5 = LDS::cw5(smem), ext = LDS::ext(smem), spec = LDS::spec(smem);
     const uint32_t xw0 = (uint32_t)cw * SEG_COMMIT_W;
     const bool prof = (P.engine_flags & 1) != 0;
     unsigned long long tc0 = 0;
@@ -3425,7 +3334,7 @@ PLS_HD void seg_ctl_commit(const SegJob &j, const SegParams &P, int par, int cw,
                 }
                 ext[tid * 2 + 0] = e1v[0]; ext[tid * 2 + 1] = e1v[1]; ext[(SEG_COMMIT_W + tid) * 2 + 0] = e1v[2]; ext[(SEG_COMMIT_W + tid) * 2 + 1] = e1v[3];
                 lutb[tid] = lb0; lutb[tid + SEG_COMMIT_W] = lb1;
-                if (tid == 0) dshare[48] = fmw;
+                if (tid == 0) failmask[0] = fmw;
                 if (tid < 8) ecost[tid] = 0u;
                 if (tid < (int)(sizeof(SegCtl) / 4)) ctlc[tid] = cword;
                 if (tid >= 128 && tid < 128 + (int)(sizeof(SegAcc) / 4)) accc[tid - 128] = aword;
@@ -3439,7 +3348,7 @@ PLS_HD void seg_ctl_commit(const SegJob &j, const SegParams &P, int par, int cw,
         }
     }
     PLS_SYNC();
-    const bool redo = ((seg_lds_ctl_t *)ctlc)->magic == SEG_MAGIC && (dshare[48] & ~((seg_lds_ctl_t *)ctlc)->ignore) != 0u;
+    const bool redo = ((seg_lds_ctl_t *)ctlc)->magic == SEG_MAGIC && (failmask[0] & ~((seg_lds_ctl_t *)ctlc)->ignore) != 0u;
     if (redo) seg_ctl_reload(j, k2, ctlc, accc, spec, SEG_THREADS);
     unsigned long long tk[4] = { 0, 0, 0, 0 };
     if (prof) tk[0] = PLS_CLOCK();
@@ -3462,7 +3371,7 @@ PLS_HD void seg_ctl_commit(const SegJob &j, const SegParams &P, int par, int cw,
         return;
     }
     seg_entropy_costs(spec, ecost, SEG_THREADS);
-    const SegDecision D = seg_decide_wg(j, P, attempt, cur, A, ecost, dshare + 20, dshare, SEG_THREADS, !redo);
+    const SegDecision D = seg_decide_wg(j, P, attempt, cur, A, ecost, verdict, decision, SEG_THREADS, !redo);
     if (D.kind != SEG_K_COMMIT) return;
     if (prof) tk[1] = PLS_CLOCK();
     const int winner = D.winner;
@@ -3544,18 +3453,20 @@ PLS_HD void seg_ctl_body(const SegJob &j, const SegParams &P, int par, int bx, u
     const int k1 = seg_k_prev(par), k2 = seg_k_prev2(par);
     SegCtl &nxt = j.ctl[par];
     const uint32_t W = j.W, H = j.H, bpp = j.bpp, nseg = j.nseg, ngrp = j.ngrp;
-    seg_lds_u32 Hn = (seg_lds_u32)smem, rank = Hn + 256, scratch = Hn + 512, basen = Hn + 768;   /* 4 x 256 words */
-    seg_lds_u32 stage = Hn + 1024;                               /* SEG_TBL_WORDS: a candidate's tables before they go out; the commit workgroups keep the split table here */
+    typedef SegLdsCtl LDS;
+    seg_lds_u32 Hn = LDS::Hn(smem), rank = LDS::rank(smem), basen = LDS::basen(smem);   /* (and scratch between them: 4 x 256 words) */
+    SEG_AS_LDS uint64_t *K = LDS::K(smem);                       /* seg_build_tables' keys: in the place of scratch AND basen, while the tables are built */
+    seg_lds_u32 stage = LDS::stage(smem);                        /* SEG_TBL_WORDS (with the classes behind it): a candidate's tables before they go out */
     const bool prof = (P.engine_flags & 1) != 0;
     unsigned long long tc0 = 0;
     if (prof) tc0 = PLS_CLOCK();
     /* What the coming attempt's histogram may need is requested before the decision is known (it depends on which candidate won):
      * per candidate w, base[w] + every group's bumps of w's row, and the committed histogram; groups in front of w's epoch are masked
      * out afterwards.  spec[w][b] in the table staging area, which is free until the tables are built. */
-    seg_lds_u32 spec = stage;                                  /* [SEG_NFILT + 1][256] */
+    seg_lds_u32 spec = LDS::spec(smem);                        /* [SEG_NFILT + 1][256] */
     /* the finished attempt's control block and sums, copied into shared memory by the same burst of loads: everything below reads the copies */
-    seg_lds_u32 ctlc = stage + (SEG_NFILT + 1) * 256, accc = ctlc + (sizeof(SegCtl) + 7) / 8 * 2;
-    seg_lds_u32 dshare = accc + (sizeof(SegAcc) + 7) / 8 * 2;  /* [20] the decision, [20] the candidates' verdicts, [8] entropy costs, [4] which attempt is followed */
+    seg_lds_u32 ctlc = LDS::ctlc(smem), accc = LDS::accc(smem);
+    seg_lds_u32 decision = LDS::decision(smem), verdict = LDS::verdict(smem), ecost = LDS::ecost(smem), failmask = LDS::failmask(smem);
     int prev = k1;
     {
         const SegCtl &curg = j.ctl[k1];
@@ -3572,13 +3483,13 @@ PLS_HD void seg_ctl_body(const SegJob &j, const SegParams &P, int par, int bx, u
             if (tid < (int)(sizeof(SegCtl) / 4)) ctlc[tid] = cword;
             if (tid >= 128 && tid < 128 + (int)(sizeof(SegAcc) / 4)) accc[tid - 128] = aword;
             if (bx < SEG_CTL_IMG && tid >= 256 && tid < 512) rank[tid - 256] = rword;
-            if (tid == 512) dshare[48] = fmw;
-            if (tid >= 520 && tid < 528) dshare[40 + tid - 520] = 0u;     /* (the entropy costs) */
+            if (tid == 512) failmask[0] = fmw;
+            if (tid >= 520 && tid < 528) decision[(ecost - decision) + tid - 520] = 0u;     /* (the entropy costs: ecost[tid - 520], indexed from the decision as before the regions had names -- from ecost itself the compiler pairs the loads behind it differently) */
             seg_spec_store<NSP>(j, tid, SEG_THREADS, sr, spec);
         }
     }
     PLS_SYNC();
-    const bool redo = ((seg_lds_ctl_t *)ctlc)->magic == SEG_MAGIC && (dshare[48] & ~((seg_lds_ctl_t *)ctlc)->ignore) != 0u;
+    const bool redo = ((seg_lds_ctl_t *)ctlc)->magic == SEG_MAGIC && (failmask[0] & ~((seg_lds_ctl_t *)ctlc)->ignore) != 0u;
     if (redo) { prev = k2; seg_ctl_reload(j, k2, ctlc, accc, spec, SEG_THREADS); }
     unsigned long long tq1 = 0, tq2 = 0;
     if (prof) tq1 = PLS_CLOCK();
@@ -3587,9 +3498,8 @@ PLS_HD void seg_ctl_body(const SegJob &j, const SegParams &P, int par, int bx, u
     /* one lane decides, the workgroup reads the result (16 waves working it out side by side only take each other's issue slots) */
     /* the number of this attempt is kept on the device (the launcher passes the copy index only) */
     const int attempt = cur.magic != SEG_MAGIC ? 0 : (int)cur.attempts + (redo ? 2 : 1);
-    seg_lds_u32 ecost = dshare + 40;                            /* [8] entropy cost of every candidate row */
     seg_entropy_costs(spec, ecost, SEG_THREADS);
-    const SegDecision D = seg_decide_wg(j, P, attempt, cur, A, ecost, dshare + 20, dshare, SEG_THREADS, !redo);
+    const SegDecision D = seg_decide_wg(j, P, attempt, cur, A, ecost, verdict, decision, SEG_THREADS, !redo);
     if (prof) tq2 = PLS_CLOCK();
     const uint32_t y = attempt ? cur.y : 0u;
     int s_next = attempt ? (int)cur.s : P.strength;
@@ -3678,7 +3588,7 @@ PLS_HD void seg_ctl_body(const SegJob &j, const SegParams &P, int par, int bx, u
         const int sn = s_next < 0 ? 0 : s_next;
         unsigned long long tc1 = 0;
         if (prof) tc1 = PLS_CLOCK();
-        seg_build_tables(j.tables + (size_t)f * SEG_TBL_WORDS, Hn, rank, scratch, stage, sn, sn + 1, SEG_THREADS, tpart, TPARTS, prof ? &j.result[PLR_SEG_TABLE_SUM] : nullptr);
+        seg_build_tables(j.tables + (size_t)f * SEG_TBL_WORDS, Hn, rank, K, stage, sn, sn + 1, SEG_THREADS, tpart, TPARTS, prof ? &j.result[PLR_SEG_TABLE_SUM] : nullptr);
         PLS_THREADS(tid, SEG_THREADS) {
             if (tpart == 0) {
                 for (int b = tid; b < 256; b += SEG_THREADS) j.base[((size_t)par * SEG_NFILT + f) * 256 + b] = 0u;
@@ -3704,7 +3614,7 @@ PLS_HD void seg_ctl_body(const SegJob &j, const SegParams &P, int par, int bx, u
             }
         }
         PLS_SYNC();
-        if (D.start_none) seg_build_tables(j.tables + (size_t)f * SEG_TBL_WORDS, Hn, rank, scratch, stage, (int)cur.s, (int)cur.s + 1, SEG_THREADS, tpart, TPARTS);
+        if (D.start_none) seg_build_tables(j.tables + (size_t)f * SEG_TBL_WORDS, Hn, rank, K, stage, (int)cur.s, (int)cur.s + 1, SEG_THREADS, tpart, TPARTS);
         return;
     }
     if (tpart) return;                                        /* (an epoch inside the row is set up by one workgroup) */
@@ -3716,7 +3626,7 @@ PLS_HD void seg_ctl_body(const SegJob &j, const SegParams &P, int par, int bx, u
                 nxt.active[f] = 0; nxt.start_x[f] = cur.start_x[f]; nxt.restarts[f] = cur.restarts[f];
                 j.self->v[par].active[f] = 0u; j.self->v[par].start_x[f] = cur.start_x[f];
                 for (int c = 0; c < 4; c++) nxt.state[f][c] = cur.state[f][c];
-                nxt.cost[f] = (uint64_t)dshare[6 + 2 * f] | ((uint64_t)dshare[7 + 2 * f] << 32);     /* D.cost[f], from shared memory: indexing the copy in registers with f would send it to the stack */
+                nxt.cost[f] = (uint64_t)decision[SEG_DEC_COST_WORD + 2 * f] | ((uint64_t)decision[SEG_DEC_COST_WORD + 1 + 2 * f] << 32);     /* D.cost[f], from shared memory: indexing the copy in registers with f would send it to the stack */
             }
         }
         return;
@@ -3742,7 +3652,7 @@ PLS_HD void seg_ctl_body(const SegJob &j, const SegParams &P, int par, int bx, u
                 uint32_t *cd = j.cand + (size_t)f * W * 4;
                 for (uint32_t x = (uint32_t)seg_max((int)(sgp * SEG_L), (int)sx); x < xp; x++) for (uint32_t c = 0; c < bpp; c++) basen[seg_cand_bin(cd[(size_t)x * 4 + c])]++;
                 const uint32_t xend = serial ? W : xp + 1;
-                SegState *st = (SegState *)(uint32_t *)scratch;       /* [4], in shared memory: indexed by the channel, in registers it would go to the stack */
+                SegState *st = (SegState *)LDS::walk_state(smem); /* [4], in shared memory: indexed by the channel, in registers it would go to the stack */
                 for (uint32_t c = 0; c < bpp; c++) {
                     int rem1, thr1, rem2, thr2;
                     seg_rem_thr(P.lut_a, P.bleed, xp >= 1 ? seg_cand_diff(cd[(size_t)(xp - 1) * 4 + c]) : 0, rem1, thr1);
@@ -3771,7 +3681,7 @@ PLS_HD void seg_ctl_body(const SegJob &j, const SegParams &P, int par, int bx, u
             }
         }
         PLS_SYNC();
-        seg_build_tables(j.tables + (size_t)f * SEG_TBL_WORDS, Hn, rank, scratch, stage, G.s, G.q, SEG_THREADS, 0, 1);
+        seg_build_tables(j.tables + (size_t)f * SEG_TBL_WORDS, Hn, rank, K, stage, G.s, G.q, SEG_THREADS, 0, 1);
     }
 }
 

@@ -64,7 +64,7 @@ inline int seg_attempt_launches(const SegShape &s, SegLaunch out[SEG_MAX_LAUNCHE
         /* (the validation workgroups can be left out at COMPILE time only -- SEG_EXPERIMENT_NO_VAL_CODE, a timing experiment whose results are unvalidated;
          *  the shipped library has no run-time switch that changes what it computes) */
         const unsigned nctl = SEG_NFILT * s.tparts + 1 + s.max_ncommit, nval = SEG_EXPERIMENT_NO_VAL_CODE ? 0u : SEG_NFILT * s.max_ngrp * (SEG_GRP / SEG_VGRP_OF(s.tparts));
-        put(batch_ctl ? SEG_KERNEL_CTL_BATCH : SEG_KERNEL_CTL, nctl + nval, SEG_THREADS, batch_ctl ? SEG_SM_CTLVAL_V(SEG_VGRP_OF(SEG_TPARTS_BATCH)) : SEG_SM_CTLVAL_V(SEG_VGRP_OF(SEG_TPARTS)), nctl, s.max_ngrp);
+        put(batch_ctl ? SEG_KERNEL_CTL_BATCH : SEG_KERNEL_CTL, nctl + nval, SEG_THREADS, batch_ctl ? seg_lds_ctl_bytes<SEG_TPARTS_BATCH>() : seg_lds_ctl_bytes<SEG_TPARTS>(), nctl, s.max_ngrp);
     }
     const unsigned nt = s.enum_nt, halves = 4 / (nt / SEG_NSP), small_segs = nt / (4 * SEG_NSS);
     if ((s.unit == 1 && s.seeds && !s.seeded) || (units && !s.seeded)) {
@@ -73,21 +73,21 @@ inline int seg_attempt_launches(const SegShape &s, SegLaunch out[SEG_MAX_LAUNCHE
         const unsigned u = units ? SEG_UNIT : 1, pairs = ((s.max_nseg + u - 1) / u) * 4;
         const unsigned nc_seeds = SEG_UNC_SEEDS_OF(u), nc_min = s.seeds && nc_seeds < SEG_UNC ? nc_seeds : SEG_UNC, nc_small = SEG_UNC_SMALL_OF(u);
         const unsigned perb = (pairs + nc_min - 1) / nc_min, pers = (pairs + nc_small - 1) / nc_small;
-        put(units ? SEG_KERNEL_ENUM_UNIT : SEG_KERNEL_ENUM_UNIT1, (s.small_ok ? 3 * perb + 2 * pers : SEG_NFILT * perb) + SEG_NFILT, SEG_UNT, (size_t)SEG_SM_ENUM_UNIT, perb, pers, s.seeds ? 1 : 0);
+        put(units ? SEG_KERNEL_ENUM_UNIT : SEG_KERNEL_ENUM_UNIT1, (s.small_ok ? 3 * perb + 2 * pers : SEG_NFILT * perb) + SEG_NFILT, SEG_UNT, seg_lds_unit_bytes(), perb, pers, s.seeds ? 1 : 0);
     } else if (s.seeded) {
-        put(nt512 ? SEG_KERNEL_ENUM_SEEDED_512 : SEG_KERNEL_ENUM_SEEDED_1024, SEG_NFILT * s.max_nseg * halves + SEG_NFILT, nt512 ? 512 : 1024, nt512 ? (size_t)SEG_SM_ENUM_SEEDED(512) : (size_t)SEG_SM_ENUM_SEEDED(1024), s.max_nseg);
+        put(nt512 ? SEG_KERNEL_ENUM_SEEDED_512 : SEG_KERNEL_ENUM_SEEDED_1024, SEG_NFILT * s.max_nseg * halves + SEG_NFILT, nt512 ? 512 : 1024, seg_lds_seeded_bytes(nt), s.max_nseg);
     } else {
         const unsigned blocks = (s.small_ok ? 3 * s.max_nseg * halves + 2 * ((s.max_nseg + small_segs - 1) / small_segs) : SEG_NFILT * s.max_nseg * halves) + SEG_NFILT;
-        put(nt512 ? SEG_KERNEL_ENUM_512 : SEG_KERNEL_ENUM_1024, blocks, nt512 ? 512 : 1024, (size_t)SEG_SM_ENUM_NT(nt), s.max_nseg);
+        put(nt512 ? SEG_KERNEL_ENUM_512 : SEG_KERNEL_ENUM_1024, blocks, nt512 ? 512 : 1024, seg_lds_enum_bytes(nt), s.max_nseg);
     }
     if (s.seeded && s.max_nseg > 1) {
         const unsigned nblk = (s.max_nseg - 1 + SEG_GS - 1) / SEG_GS;
         put(SEG_KERNEL_GATHER_SEEDED, SEG_NFILT * 4 * nblk, SEG_GT, 0, nblk);
     }
-    if (s.seeded) put(SEG_KERNEL_CHAIN_SEEDED, SEG_NFILT * 4 + 1, SEG_CHAIN_THREADS, SEG_SM_CHAIN(s.max_nseg));
-    else if (units) put(SEG_KERNEL_CHAIN_UNIT, SEG_NFILT * 4 + 1, SEG_CHAIN_THREADS_UNIT, SEG_SM_CHAIN_X((s.max_nseg + s.unit - 1) / s.unit));
-    else put(SEG_KERNEL_CHAIN, SEG_NFILT * 4 + 1, SEG_CHAIN_THREADS, SEG_SM_CHAIN_X(s.max_nseg));
-    put(units ? SEG_KERNEL_REPLAY_BATCH : SEG_KERNEL_REPLAY, SEG_NFILT * s.max_ngrp, units ? SEG_REPLAY_NT_BATCH : SEG_REPLAY_NT, SEG_SM_REPLAY, s.max_ngrp);
+    if (s.seeded) put(SEG_KERNEL_CHAIN_SEEDED, SEG_NFILT * 4 + 1, SEG_CHAIN_THREADS, seg_lds_chain_bytes<true>(s.max_nseg));
+    else if (units) put(SEG_KERNEL_CHAIN_UNIT, SEG_NFILT * 4 + 1, SEG_CHAIN_THREADS_UNIT, seg_lds_chain_bytes<false>((s.max_nseg + s.unit - 1) / s.unit));
+    else put(SEG_KERNEL_CHAIN, SEG_NFILT * 4 + 1, SEG_CHAIN_THREADS, seg_lds_chain_bytes<false>(s.max_nseg));
+    put(units ? SEG_KERNEL_REPLAY_BATCH : SEG_KERNEL_REPLAY, SEG_NFILT * s.max_ngrp, units ? SEG_REPLAY_NT_BATCH : SEG_REPLAY_NT, seg_lds_replay_bytes(), s.max_ngrp);
     return n;
 }
 

@@ -368,6 +368,35 @@ def seg_launch_host_lib():
     return _seg_launch
 
 
+_seg_lds = None
+
+
+def seg_lds_host_lib():
+    """tests/c/seg_lds_host.cpp (the shared-memory layouts of the segment engine's kernel bodies, pngloss_amd/csrc/pl_seg_lds.h, behind a C ABI) built into a
+    shared object (cached per process)."""
+    global _seg_lds
+    if _seg_lds is None:
+        import subprocess
+        import tempfile
+        so = os.path.join(tempfile.mkdtemp(prefix="seg_lds_host_"), "libseg_lds_host.so")
+        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Werror", "-o", so, os.path.join(ROOT, "tests", "c", "seg_lds_host.cpp")], check=True)
+        lib = C.CDLL(so)
+        lib.seg_lds_host_layouts.restype = C.c_int
+        lib.seg_lds_host_layout.argtypes = [C.c_int, C.c_int64, C.c_char_p, C.c_void_p]
+        lib.seg_lds_host_layout.restype = C.c_int
+        lib.seg_lds_host_region.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_char_p, C.c_char_p, C.c_void_p]
+        lib.seg_lds_host_region.restype = C.c_int
+        lib.seg_lds_host_kernels.restype = C.c_int
+        lib.seg_lds_host_kernel_name.argtypes = [C.c_int]
+        lib.seg_lds_host_kernel_name.restype = C.c_char_p
+        lib.seg_lds_host_launch_bytes.argtypes = [C.c_int, C.c_int64]
+        lib.seg_lds_host_launch_bytes.restype = C.c_int64
+        lib.seg_lds_host_constants.argtypes = [C.c_void_p]
+        lib.seg_lds_host_constants.restype = None
+        _seg_lds = lib
+    return _seg_lds
+
+
 def run_seg_host(img, s=19, b=2, filters=True):
     """The segment-parallel engine's kernel bodies on the CPU: returns rc, out, filters, stats
     (attempts, restarts, retried rows, serial rows, unique symbols, bpp, chain states, status)."""
