@@ -332,7 +332,7 @@ static void run_chain_spec(const engine *e, uint32_t y, int f, unsigned s, long 
 
 /* ------------------------------------------------------------------ "band leader" variant of the chain (variant 2)
  *
- * The formulation of the round-2 HIP row engine (pl_engine.hip, chain_lead), proven here on the CPU first.
+ * The formulation of the round-2 HIP row engine (pl_engine.hip: pl_wg_lead.h, chain_lead), proven here on the CPU first.
  * Observation: without the clamp the candidate set of a channel is one of a FIXED partition of v-space into bands
  * [tq, tq+s] (filt >= 0) and [-tq-s, -tq] (filt < 0) (optimize_state.c:186-193), and the choice inside a band is the
  * lexicographic arg-max of (H[v], O_f[v], v==osym, -v) (:212-244).  Keep, per tracked band, its LEADER

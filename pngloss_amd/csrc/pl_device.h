@@ -94,7 +94,6 @@ __device__ __forceinline__ int pl_predict_rt(int f, int above, int diag, int lef
 
 __device__ __forceinline__ int pl_sext8(int v) { return __builtin_amdgcn_sbfe(v, 0, 8); }
 __device__ __forceinline__ int pl_sext16(int v) { return __builtin_amdgcn_sbfe(v, 0, 16); }
-__device__ __forceinline__ int pl_med3(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 /* Exact truncating division of a small signed integer (|n| < 2^17) by a positive constant d <= 32767 using the
  * float reciprocal rd = nextafterf(1.0f/d, +inf): trunc(n * rd) == trunc(n / d).  Proof sketch and exhaustive
@@ -146,7 +145,8 @@ struct PlEngineParams {
     float rbleed;   /* nextafterf(1/bleed, +inf)        */
     float r29;      /* 2*nextafterf(1/9, +inf)          */
     int engine_mode;   /* low 4 bits, test hook: 0 = band-leader chains where their preconditions hold, round-1 chains where those are
-                          measurably slow (default), 1 = round-1 chains only, 2 = band-leader chains wherever possible;
+                          measurably slow (default), 1 = round-1 chains only, 2 = band-leader chains wherever possible, 3 = "mix": the two kinds
+                          take turns every four rows, whatever the clocks say;
                           bits 8..: debugging aid, 1 + the candidate that wins every row */
     int force_careful; /* test hook: always run the chain variant with explicit int16 wrap handling (normally only
                           rows whose incoming |error| exceeds 8000 use it) */

@@ -619,6 +619,46 @@ def test_round1_chains_still_match_the_oracle():
     assert r.returncode == 0 and "legacy ok" in r.stdout, r.stderr[-1500:]
 
 
+_commit_capacity_refs = {}
+
+
+def _commit_capacity_case(width, kind, filters):
+    """image and the oracle's answer, worked out once per case and shared by the engines"""
+    key = (width, kind, filters)
+    if key not in _commit_capacity_refs:
+        h = 4
+        if kind == "rgba noise":
+            img = np.random.default_rng(width).integers(0, 256, (h, width, 4), dtype=np.uint8)
+        else:
+            x = np.arange(width, dtype=np.int64)[None, :] + 37 * np.arange(h, dtype=np.int64)[:, None]
+            img = np.zeros((h, width, 4), np.uint8)
+            img[..., 1] = (x * 255 // (width + 37 * h)).astype(np.uint8)
+            img[..., 3] = (255 - x * 200 // (width + 37 * h)).astype(np.uint8)
+            img = U.as_pixel_class(img, "graya")
+        out, filt = U.run_port(img, 19, 2, filters=filters)
+        for a in (img, out) + ((filt,) if filters else ()):
+            a.setflags(write=False)
+        _commit_capacity_refs[key] = (img, out, filt)
+    return _commit_capacity_refs[key]
+
+
+@pytest.mark.parametrize("over", [0, 1])
+@pytest.mark.parametrize("engine", ["wg", "lead", "legacy"])
+def test_workgroup_engine_rows_at_the_commit_capacity(monkeypatch, engine, over):
+    """The commit pass of the workgroup engine keeps a row's next-rows terms in LDS where the row fits the union the chains leave free, 16 bytes a pixel, and
+    takes the pass without LDS for wider rows: the widest row of the first kind and the narrowest of the second (the capacity read from the layout,
+    pngloss_amd/csrc/pl_wg_lds.h, not written down here), both kinds of chains, four and two bytes a pixel, with and without row filters."""
+    cap = U.wg_lds_layout()["commit_px"]
+    assert cap * 16 <= U.wg_lds_layout()["union_bytes"] < (cap + 1) * 16
+    monkeypatch.setenv("PNGLOSS_HIP_ENGINE", engine)
+    for kind in ("rgba noise", "gray+alpha gradient"):
+        for filters in (True, False):
+            img, want, want_f = _commit_capacity_case(cap + over, kind, filters)
+            out, filt = P.optimize_with_rows(img, 19, 2, want_filters=filters)
+            assert np.array_equal(out, want), (engine, cap + over, kind, filters)
+            assert (filt is None and want_f is None) if not filters else np.array_equal(filt, want_f), (engine, cap + over, kind, filters)
+
+
 def test_band_leader_chains_on_hostile_inputs(engine_choice):
     """Inputs chosen against the band-leader chains: noise (every band in use, ties everywhere), values around 128 (filter
     none's positive and negative bands compete for the same bins), saturated and fully transparent regions (static and

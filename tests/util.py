@@ -397,6 +397,51 @@ def seg_lds_host_lib():
     return _seg_lds
 
 
+_wg_lds = None
+WG_LDS_HOST_BUILD = ["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Werror"]
+
+
+def wg_lds_host_lib():
+    """tests/c/wg_lds_host.cpp (the shared memory of the workgroup engine, pngloss_amd/csrc/pl_wg_lds.h, behind a C ABI) built into a shared object (cached per
+    process)."""
+    global _wg_lds
+    if _wg_lds is None:
+        import subprocess
+        import tempfile
+        so = os.path.join(tempfile.mkdtemp(prefix="wg_lds_host_"), "libwg_lds_host.so")
+        subprocess.run(WG_LDS_HOST_BUILD + ["-o", so, os.path.join(ROOT, "tests", "c", "wg_lds_host.cpp")], check=True)
+        lib = C.CDLL(so)
+        lib.wg_lds_host_place.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
+        lib.wg_lds_host_place.restype = C.c_int
+        lib.wg_lds_host_entry.argtypes = [C.c_int, C.c_char_p, C.c_void_p]
+        lib.wg_lds_host_entry.restype = C.c_int
+        lib.wg_lds_host_constants.argtypes = [C.c_void_p]
+        lib.wg_lds_host_constants.restype = None
+        lib.wg_lds_host_chain_slot.argtypes = [C.c_int, C.c_int]
+        lib.wg_lds_host_chain_slot.restype = C.c_int
+        lib.wg_lds_host_named.argtypes = [C.c_void_p]
+        lib.wg_lds_host_named.restype = None
+        _wg_lds = lib
+    return _wg_lds
+
+
+def wg_lds_layout(region=-1, grow_bytes=0, align=0):
+    """The workgroup engine's LDS as pl_wg_lds.h places it (region >= 0: a copy of the table with that region grown / its alignment replaced): a dict of
+    sound, union_off, union_bytes, launch_bytes, commit_px and entries -- one dict per slot of every region, in carve order: name, view, region, slot, offset,
+    bytes, align."""
+    lib = wg_lds_host_lib()
+    head = np.zeros(6, np.int64)
+    n = lib.wg_lds_host_place(region, grow_bytes, align, head.ctypes.data)
+    assert n > 0
+    entries = []
+    for i in range(n):
+        name, v = C.create_string_buffer(64), np.zeros(6, np.int64)
+        assert lib.wg_lds_host_entry(i, name, v.ctypes.data) == 0
+        entries.append(dict(name=name.value.decode(), view=int(v[0]), region=int(v[1]), slot=int(v[2]), offset=int(v[3]), bytes=int(v[4]), align=int(v[5])))
+    return dict(sound=bool(head[0]), union_off=int(head[1]), union_bytes=int(head[2]), launch_bytes=int(head[3]), regions=int(head[4]), commit_px=int(head[5]),
+                entries=entries)
+
+
 def run_seg_host(img, s=19, b=2, filters=True):
     """The segment-parallel engine's kernel bodies on the CPU: returns rc, out, filters, stats
     (attempts, restarts, retried rows, serial rows, unique symbols, bpp, chain states, status)."""

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Developer tool (build container): the product library with pl_lead_asm.h regenerated under other generator settings and/or extra defines for pl_engine.hip:
+# Developer tool (build container): the product library with pl_lead_asm.h regenerated under other generator settings and/or extra defines for pl_engine.hip and its parts (pl_wg_*.h):
 #   tools/build_wg_variant.sh NAME "PL_LEAD_BURST=2 ..." "-DPL_LEAD_BURST0_CLEAN=2 ..."   -> tools/ablate_build/libpngloss_hip_NAME.so
 # (a copy of the sources with the regenerated header, built by the product's Makefile there; the copy lies two directories below one that holds include/,
 #  like the sources themselves)

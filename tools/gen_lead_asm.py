@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Generates pngloss_amd/csrc/pl_lead_asm.h: the hand-scheduled gfx950 inner loops of the band-leader chains
-(pl_engine.hip, lead_fast_run).  One asm statement = a 4x unrolled loop over pixels; all rotating values (table
+(pl_wg_lead.h, lead_fast_run).  One asm statement = a 4x unrolled loop over pixels; all rotating values (table
 entries, records, addresses) live in fixed VGPRs v200.. so that the rotation costs no moves.
 
 Per pixel step k (pixel i+k), with E[j] = table entry pairs, Q[j] = record quads, A[j] = looked-up addresses:
