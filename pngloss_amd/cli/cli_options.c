@@ -54,7 +54,7 @@ const char cli_usage_text[] =
     "Output names end in \"-loss.png\" or your --ext; with \"-\" the image goes stdin -> stdout.\n"
     "Existing outputs are skipped unless --force is given.\n";
 
-enum { OPT_EXT = 256, OPT_NO_FORCE, OPT_SKIP_LARGER, OPT_STRIP, OPT_GPU_DEFLATE, OPT_GPU_READ, OPT_DISTORTION, OPT_TARGET_PSNR, OPT_MAX_ERROR, OPT_SSIM, OPT_TARGET_SSIM, OPT_TARGET_SIZE, OPT_VISIBLE, OPT_INDEXED };
+enum { OPT_EXT = 256, OPT_NO_FORCE, OPT_SKIP_LARGER, OPT_STRIP, OPT_GPU_DEFLATE, OPT_GPU_READ, OPT_DISTORTION, OPT_TARGET_PSNR, OPT_MAX_ERROR, OPT_SSIM, OPT_TARGET_SSIM, OPT_TARGET_SIZE, OPT_VISIBLE, OPT_INDEXED, OPT_COLORS };
 
 static bool parse_number(const char *text, unsigned long *out)
 {
@@ -116,6 +116,7 @@ pngloss_error cli_options_parse(int argc, char **argv, struct cli_options *o, FI
         { "target-size", required_argument, NULL, OPT_TARGET_SIZE },
         { "visible", no_argument, NULL, OPT_VISIBLE },
         { "indexed", no_argument, NULL, OPT_INDEXED },
+        { "colors", required_argument, NULL, OPT_COLORS },
         { NULL, 0, NULL, 0 },
     };
     memset(o, 0, sizeof *o);
@@ -153,6 +154,10 @@ pngloss_error cli_options_parse(int argc, char **argv, struct cli_options *o, FI
             break;
         case OPT_VISIBLE: o->visible = true; break;
         case OPT_INDEXED: o->indexed = true; break;
+        case OPT_COLORS:
+            if (!parse_number(optarg, &o->colors)) return refuse(err, "--colors requires a numeric argument\n");
+            o->have_colors = true;
+            break;
         case 'h': o->help = true; break;
         case 'V': o->version = true; break;
         case 'o':
@@ -162,6 +167,7 @@ pngloss_error cli_options_parse(int argc, char **argv, struct cli_options *o, FI
             break;
         case 's':
             if (!parse_number(optarg, &o->strength)) return refuse(err, "-s, --strength requires a numeric argument\n");
+            o->have_strength = true;
             break;
         case 'b':
             if (!parse_number(optarg, &o->bleed)) return refuse(err, "-b, --bleed requires a numeric argument\n");
@@ -183,6 +189,11 @@ pngloss_error cli_options_parse(int argc, char **argv, struct cli_options *o, FI
     o->search = quality && size ? CLI_SEARCH_BOTH : quality ? CLI_SEARCH_QUALITY : size ? CLI_SEARCH_SIZE : CLI_SEARCH_NONE;
     /* --indexed chooses between two streams of the device deflate; --target-size budgets the file the device deflate writes: zlib-9's size is not
      * what the device measures */
+    /* --colors makes the palette that --indexed writes, and is the lossy step itself: the row optimiser runs at strength 0, where it changes no pixel */
+    if (o->have_colors) {
+        o->indexed = true;
+        if (!o->have_strength) o->strength = 0;
+    }
     if (o->indexed || size) o->gpu_deflate = true;
     return SUCCESS;
 }
@@ -199,6 +210,10 @@ pngloss_error cli_options_check(const struct cli_options *o, FILE *err)
     if (o->visible && !(o->distortion || o->ssim || quality)) return refuse(err, "--visible needs one of --distortion, --ssim, --target-psnr, --max-error or --target-ssim.\n");
     if (o->visible && size) return refuse(err, "--visible cannot be combined with --target-size.\n");
     if (size && o->size_value < 1) return refuse(err, "Must specify a size target of at least 1 byte or 1 percent.\n");
+    if (o->have_colors && (o->colors < 2 || o->colors > 256)) return refuse(err, "Must specify a number of colours in the range 2-256.\n");
+    if (o->have_colors && o->strength != 0) return refuse(err, "--colors cannot be combined with a strength above 0: the palette is the lossy step.\n");
+    if (o->have_colors && (o->search != CLI_SEARCH_NONE || o->ssim || o->visible))
+        return refuse(err, "--colors cannot be combined with --target-size, --target-psnr, --target-ssim, --max-error, --ssim or --visible.\n");
     if (o->indexed && o->search != CLI_SEARCH_NONE) return refuse(err, "--indexed cannot be combined with --target-size, --target-psnr, --target-ssim or --max-error.\n");
     if (o->bleed < 1 || o->bleed > 32767) return refuse(err, "Must specify a bleed divider in the range 1-32767.\n");
     if (o->extension && o->output_path) return refuse(err, "--ext and --output options can't be used at the same time\n");

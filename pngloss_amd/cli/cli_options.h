@@ -34,6 +34,9 @@ struct cli_options {
     bool ssim;                 /* --ssim: one more line per written file: mean and worst-window SSIM against the input's pixels (measured on the device) */
     bool visible;              /* --visible: --distortion, --ssim and the --target searches measure over visible pixels (the library's option "measure") */
     bool indexed;              /* --indexed: a result of at most 256 colours is written as a palette file where that file is smaller (the library's option "indexed") */
+    bool have_colors;          /* --colors N: every image is quantised to at most N colours first (pngloss_hip_multi_quantize_batch_host), then written at */
+    unsigned long colors;      /* strength 0 with --indexed: the palette is the lossy step.  Not in the usage text (DESIGN.md 9.1b says why) */
+    bool have_strength;        /* -s was given */
     enum cli_search search;
     double target_psnr;        /* 0: no PSNR condition */
     bool have_max_error;
@@ -49,7 +52,7 @@ struct cli_options {
 extern const char cli_usage_text[];
 
 /* argv into *o (defaults: strength 19, bleed 2).  A malformed argument writes its message to err -- getopt_long writes its own to stderr -- and
- * returns INVALID_ARGUMENT.  Ends by deriving `search` and the implied gpu_deflate. */
+ * returns INVALID_ARGUMENT.  Ends by deriving `search`, the implied gpu_deflate and what --colors implies (--indexed, and strength 0 without -s). */
 pngloss_error cli_options_parse(int argc, char **argv, struct cli_options *o, FILE *err);
 
 /* Every rule between the arguments, in the order in which a user meets their messages: the first one broken writes its message to err and gives

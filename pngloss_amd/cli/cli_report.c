@@ -49,6 +49,14 @@ void cli_report_indexed(char *line, size_t cap, const pngloss_hip_palette *p)
              (unsigned long long)p->truecolor_bytes);
 }
 
+void cli_report_quant(char *line, size_t cap, const pngloss_hip_quant_report *q)
+{
+    char in[32];
+    if (q->colors_in > 256) snprintf(in, sizeof in, "more than 256");
+    else snprintf(in, sizeof in, "%u", q->colors_in);
+    snprintf(line, cap, "  colors: %s in the input, %u palette entries%s\n", in, q->entries, q->exact ? ", exact (no pixel changed)" : "");
+}
+
 void cli_report_budget_missed(char *line, size_t cap, const char *name, size_t budget, size_t written, unsigned strength)
 {
     snprintf(line, cap, "  warning: %s: budget of %zu bytes not reached, wrote %zu bytes at strength %u\n", name, budget, written, strength);

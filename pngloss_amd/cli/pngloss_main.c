@@ -30,6 +30,7 @@
 
 #include "../../include/pngloss_hip.h"
 #include "../../include/pngloss_hip_indexed.h"
+#include "../../include/pngloss_hip_quant.h"
 #include "cli_options.h"
 #include "cli_outcome.h"
 #include "cli_report.h"
@@ -72,6 +73,8 @@ struct job {
     bool have_ssim;
     pngloss_hip_palette palette;         /* --indexed: what the library decided for this file (color_type 3: the PLTE / tRNS payloads of the written file) */
     bool have_palette;
+    pngloss_hip_quant_report quant;      /* --colors: what the quantiser did to this file (have_quant: it ran) */
+    bool have_quant;
     png_stream_source src;    /* --gpu-read: inflated scanlines waiting for the device (src.scanlines != NULL) */
 };
 
@@ -282,6 +285,10 @@ static void encode_job(struct job *j, const struct cli_options *o)
         say(j, "%s", line);
     }
     if (o->verbose) say(j, "  compression complete\n  used %u unique symbols\n", j->gpu.unique_symbols);
+    if (o->verbose && j->have_quant) {
+        cli_report_quant(line, sizeof line, &j->quant);
+        say(j, "%s", line);
+    }
     if (o->verbose && j->color_type == 3) {
         cli_report_indexed(line, sizeof line, &j->palette);
         say(j, "%s", line);
@@ -515,7 +522,8 @@ static pngloss_hip_multi *open_contexts(const struct cli_options *o)
         ctx = pngloss_hip_multi_create(list);
     }
     if (!ctx) return NULL;
-    if (o->distortion && pngloss_hip_multi_set_option(ctx, "distortion", "on") != PNGLOSS_SUCCESS)
+    /* (with --colors the record is the quantiser's: strength 0 changes no pixel behind it) */
+    if (o->distortion && !o->have_colors && pngloss_hip_multi_set_option(ctx, "distortion", "on") != PNGLOSS_SUCCESS)
         fputs("  warning: the library refused the option \"distortion\"; no distortion lines\n", stderr);
     if (o->ssim && pngloss_hip_multi_set_option(ctx, "ssim", "on") != PNGLOSS_SUCCESS)
         fputs("  warning: the library refused the option \"ssim\"; no ssim lines\n", stderr);
@@ -540,6 +548,23 @@ static void compute_budgets(struct window_batch *b, struct job *jobs, const stru
         const png_stream_image si = stream_image_of(&j->out, j->in.chunks);
         b->budget[k] = cli_stream_budget(png_stream_largest_stream(&si, j->size_budget, PNG_STREAM_GPU_IDAT_SLICE));
     }
+}
+
+/* --colors: every image of the batch to at most N colours, where it lies (it is the encoder's private copy of the decoded input).  An error fails
+ * every file of the batch, which then has nothing left to optimise */
+static void quantise_batch(pngloss_hip_multi *ctx, struct window_batch *b, struct job *jobs, const struct cli_options *o)
+{
+    const pngloss_hip_quant_params params = { (uint32_t)o->colors, PNGLOSS_HIP_QUANT_DEFAULT_ROUNDS };
+    pngloss_hip_quant_report *reports = calloc(b->m ? b->m : 1, sizeof *reports);
+    int rc = !ctx ? PNGLOSS_HIP_ERROR : !reports ? PNGLOSS_OUT_OF_MEMORY_ERROR : pngloss_hip_multi_quantize_batch_host(ctx, b->imgs, b->m, &params, reports);
+    for (size_t k = 0; k < b->m; k++) {
+        struct job *j = &jobs[b->who[k]];
+        if (rc == PNGLOSS_SUCCESS) { j->quant = reports[k]; j->have_quant = true; continue; }
+        say(j, "  error: GPU colour quantisation failed (%d)\n", rc);
+        j->status = (pngloss_error)rc;
+    }
+    if (rc != PNGLOSS_SUCCESS) b->m = 0;
+    free(reports);
 }
 
 /* The one call into the library.  In a search the library finds a strength per file, -s bounds it, and the records come back in the reports */
@@ -584,7 +609,8 @@ static void take_answer(struct job *j, const struct window_batch *b, size_t k, c
         j->ssim = b->sm[k];
         break;
     default:     /* the plain call keeps the records in the context */
-        last_distortion = o->distortion && ctx && pngloss_hip_multi_last_distortion(ctx, k, &j->distortion) == PNGLOSS_SUCCESS;
+        if (j->have_quant) { j->distortion = j->quant.distortion; last_distortion = o->distortion; }
+        else last_distortion = o->distortion && ctx && pngloss_hip_multi_last_distortion(ctx, k, &j->distortion) == PNGLOSS_SUCCESS;
         last_ssim = o->ssim && ctx && pngloss_hip_multi_last_ssim(ctx, k, &j->ssim) == PNGLOSS_SUCCESS;
         last_palette = o->indexed && ctx && pngloss_hip_multi_last_palette(ctx, k, &j->palette) == PNGLOSS_SUCCESS;
         break;
@@ -616,7 +642,8 @@ static void run_window(struct job *jobs, size_t n, const struct cli_options *o, 
         if (!*ctx) *ctx = open_contexts(o);
         if (timing) fprintf(stderr, "  [timing] GPU contexts ready after %.3f s\n", now_s() - tc0);
         if (o->search == CLI_SEARCH_SIZE) compute_budgets(&b, jobs, o);
-        const int rc = optimise_batch(*ctx, &b, o);
+        if (o->have_colors) quantise_batch(*ctx, &b, jobs, o);
+        const int rc = b.m ? optimise_batch(*ctx, &b, o) : PNGLOSS_SUCCESS;
         for (size_t k = 0; k < b.m; k++) take_answer(&jobs[b.who[k]], &b, k, o, *ctx, rc);
     }
     window_batch_free(&b);

@@ -554,7 +554,7 @@ void pngloss_hip_destroy(pngloss_hip_ctx *ctx)
     seg_engine_release(ctx);
     for (auto &e : ctx->ev)
         if (e) (void)hipEventDestroy(e);
-    for (GrowBuf *b : { &ctx->d_ws, &ctx->d_arena, &ctx->h_pinned, &ctx->d_frames, &ctx->d_keep, &ctx->d_ssim, &ctx->d_target, &ctx->d_index }) b->release();
+    for (GrowBuf *b : { &ctx->d_ws, &ctx->d_arena, &ctx->h_pinned, &ctx->d_frames, &ctx->d_keep, &ctx->d_ssim, &ctx->d_target, &ctx->d_index, &ctx->d_quant }) b->release();
     if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
     if (ctx->h_progress) (void)hipHostFree(ctx->h_progress);
     for (pngloss_hip_ctx *p : ctx->peers) if (p) pngloss_hip_destroy(p);

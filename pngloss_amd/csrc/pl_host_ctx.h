@@ -11,6 +11,7 @@
  *   pl_host_search.hip   the two strength searches (target_search, size_search), their host form and their entry points
  *   pl_host_measure.hip  the job tables of the two measuring kernels, the stand-alone comparisons
  *   pl_host_read.hip     the PNG read side
+ *   pl_host_quant.hip    the colour quantiser: its workspace, the median cut between its two synchronisations, its host form
  * What the host side DECIDES is in plain headers that the CPU suite pins (pl_plan.h, pl_seg_pace.h, pl_layout.h, pl_deal.h, pl_search.h, pl_result.h);
  * these files carry it out.
  *
@@ -20,6 +21,7 @@
  *   - forget_last_batch (pl_host.hip) clears every block's record of the last batch; enqueue begins with it, the searches end with it.
  *   - pl_host.hip joins the launch thread (seg_worker) and synchronises the engine's streams where a batch ends: enqueue, finish, destroy.
  *   - a buffer is grown by whoever lays it out: d_ws by enqueue and by the read side, d_keep by enqueue and by the comparisons.
+ *   - the quantiser's host form makes sure of copy_stream (ensure_copy_stream), as the searches do.
  *   - batch_host (pl_host_window.hip) folds the peers' times into engine_ms and total_ms of the context it was called on.
  *   - engine_calib (pl_host.hip) pins opt_engine on the temporary context it measures with.
  * Every file may READ every member.  What ONE call asks of a batch is never a member: it is a BatchCall, an argument of enqueue.
@@ -29,6 +31,7 @@
 
 #include "../../include/pngloss_hip.h"
 #include "../../include/pngloss_hip_indexed.h"
+#include "../../include/pngloss_hip_quant.h"
 #include "pl_device.h"
 #include "pl_deflate.h"
 #include "pl_pngread.h"
@@ -36,6 +39,7 @@
 #include "pl_distort.h"
 #include "pl_ssim.h"
 #include "pl_index.h"
+#include "pl_quant.h"
 #include "pl_target.h"
 #include "pl_size.h"
 #include "pl_target_dev.h"
@@ -168,6 +172,9 @@ struct pngloss_hip_ctx {
 
     /* ---- pl_host_read.hip: device frames of pngloss_hip_png_decode_batch_device: decoded RGBA8 that stays on the device for the optimiser ---- */
     GrowBuf d_frames;
+
+    /* ---- pl_host_quant.hip: the quantiser's workspace (pl_layout.h: pl_quant_layout), regrown on demand like the others ---- */
+    GrowBuf d_quant;
 };
 
 /* all the GPUs of the node (pl_host_window.hip): one context per device */

@@ -1,6 +1,6 @@
 /*
  * pl_layout.h -- every carve-up of a buffer the host shim makes, as pure functions from sizes to offsets: the batch workspace of enqueue(), the
- * arena of a host window (batch_host_one), the keep arena of the distortion measurement, the tables of the SSIM measurement, the index workspace of the option "indexed", the read side's workspace and frame arena
+ * arena of a host window (batch_host_one), the keep arena of the distortion measurement, the tables of the SSIM measurement, the index workspace of the option "indexed", the quantiser's workspace, the read side's workspace and frame arena
  * (png_decode_body), and the size a buffer is regrown to.
  * Internal.
  *
@@ -15,6 +15,7 @@
 #include "pl_plan.h"
 #include "pl_pngread_core.h"
 #include "pl_index_core.h"
+#include "pl_quant_core.h"
 
 #include <cstdint>
 #include <cstring>
@@ -245,6 +246,59 @@ inline PlIndexLayout pl_index_layout(const std::vector<uint32_t> &width, const s
         m.pitch = px ? (uint32_t)pl_align_up(width[i], 16) : 0;
         m.ids = take(px ? height[i] : 0);
         m.rows = take((size_t)m.pitch * (px ? height[i] : 0));
+    }
+    return l;
+}
+
+/* ================================================================================================ the quantiser's workspace (pngloss_hip_quantize_batch) */
+
+/* The tables in front: the PlIndexJob, PlQuantJob and PlDistortJob tables; then what one memset zeroes (`zeroed` bytes from `counts`): the colour
+ * counters, the palette records (PliRecord), the distortion records and the accumulators (PLQ_MAX_COLORS * PLQ_CELLS 64-bit cells per image); the
+ * colour tables of pl_index_count (`tables_bytes` from `tables`: one memset to 0xFF); the histograms (`hists_bytes` from `hists`: one memset to 0,
+ * 256 KiB per image) and the palettes (PLQ_MAX_COLORS words per image).  Behind them per image with pixels its quantised pixels (`out`, beside the
+ * input: the distortion record is taken between the two before the copy back in place) and -- with `inputs`, the host form -- the input itself.
+ * Every image gets its `out`, exact or not: which ones are is known only after the first synchronisation, and a buffer that cannot be had has to
+ * fail the call before anything is enqueued. */
+struct PlQuantImage { size_t table, hist, pal, acc, out, in; };
+struct PlQuantLayout {
+    size_t index_jobs = 0, quant_jobs = 0, distort_jobs = 0;
+    size_t counts = 0, records = 0, distort_records = 0, accs = 0, zeroed = 0;
+    size_t tables = 0, tables_bytes = 0, hists = 0, hists_bytes = 0, pals = 0, total = 0;
+    std::vector<PlQuantImage> im;
+};
+constexpr size_t PLL_QUANT_ACC = sizeof(uint64_t) * PLQ_MAX_COLORS * PLQ_CELLS, PLL_QUANT_HIST = sizeof(uint32_t) * PLQ_BINS, PLL_QUANT_PAL = sizeof(uint32_t) * PLQ_MAX_COLORS;
+
+/* index_job_bytes, quant_job_bytes, distort_job_bytes, record_bytes, distort_record_bytes: sizeof(PlIndexJob), sizeof(PlQuantJob), sizeof(PlDistortJob),
+ * sizeof(PliRecord), sizeof(PlDistortRecord) */
+inline PlQuantLayout pl_quant_layout(const std::vector<uint32_t> &width, const std::vector<uint32_t> &height, bool inputs, size_t index_job_bytes,
+                                     size_t quant_job_bytes, size_t distort_job_bytes, size_t record_bytes, size_t distort_record_bytes)
+{
+    PlQuantLayout l;
+    const size_t n = width.size(), n1 = n ? n : 1;
+    auto take = [&](size_t bytes) { size_t at = l.total; l.total = pl_align_up(l.total + bytes, PLL_ALIGN); return at; };
+    l.im.resize(n);
+    l.index_jobs = take(index_job_bytes * n1);
+    l.quant_jobs = take(quant_job_bytes * n1);
+    l.distort_jobs = take(distort_job_bytes * n1);
+    l.counts = take(sizeof(uint32_t) * n1);
+    l.records = take(record_bytes * n1);
+    l.distort_records = take(distort_record_bytes * n1);
+    l.accs = take(PLL_QUANT_ACC * n1);
+    l.zeroed = l.total - l.counts;
+    l.tables_bytes = sizeof(uint64_t) * PLI_SLOTS * n1;
+    l.tables = take(l.tables_bytes);
+    l.hists_bytes = PLL_QUANT_HIST * n1;
+    l.hists = take(l.hists_bytes);
+    l.pals = take(PLL_QUANT_PAL * n1);
+    for (size_t i = 0; i < n; i++) {
+        PlQuantImage &m = l.im[i];
+        const size_t bytes = (size_t)width[i] * height[i] * 4;
+        m.table = l.tables + sizeof(uint64_t) * PLI_SLOTS * i;
+        m.hist = l.hists + PLL_QUANT_HIST * i;
+        m.pal = l.pals + PLL_QUANT_PAL * i;
+        m.acc = l.accs + PLL_QUANT_ACC * i;
+        m.out = take(bytes);
+        m.in = take(inputs ? bytes : 0);
     }
     return l;
 }

@@ -117,6 +117,25 @@ class Palette(C.Structure):
                     indexed_bytes=self.indexed_bytes, colors=self.colors)
 
 
+class QuantParams(C.Structure):
+    """pngloss_hip_quant_params: max_colors (N, 2..256) and rounds (R, 0..64) of the colour quantiser.  include/pngloss_hip_quant.h states the rule."""
+    _fields_ = [("max_colors", C.c_uint32), ("rounds", C.c_uint32)]
+
+    def __init__(self, max_colors=256, rounds=8):
+        super().__init__(max_colors, rounds)
+
+
+class QuantReport(C.Structure):
+    """pngloss_hip_quant_report: what the quantiser did to one image.  colors_in: 257 = more than 256; palette[:entries]: the colours of the image as
+    it is now, ascending by word; exact: it had at most max_colors colours and was not changed; distortion: now against the input, all pixels."""
+    _fields_ = [("status", C.c_int32), ("colors_in", C.c_uint32), ("entries", C.c_uint32), ("exact", C.c_uint32), ("palette", C.c_uint32 * 256),
+                ("distortion", Distortion)]
+
+    def as_dict(self):
+        return dict(status=self.status, colors_in=self.colors_in, entries=self.entries, exact=self.exact, palette=list(self.palette)[: self.entries],
+                    distortion=self.distortion.as_dict())
+
+
 class ImagePair(C.Structure):
     _fields_ = [("d_a", C.c_void_p), ("d_b", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32)]
 
@@ -184,6 +203,14 @@ INDEXED_STRUCTS = {"pngloss_hip_palette": Palette}
 INDEXED_PROTOTYPES = {
     "pngloss_hip_last_palette": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(Palette)]),
     "pngloss_hip_multi_last_palette": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(Palette)]),
+}
+
+
+#: ... and for include/pngloss_hip_quant.h, the extension header of the colour quantiser (tests/test_quant_host.py holds them against that header)
+QUANT_STRUCTS = {"pngloss_hip_quant_params": QuantParams, "pngloss_hip_quant_report": QuantReport}
+QUANT_PROTOTYPES = {
+    "pngloss_hip_quantize_batch": (C.c_int, [C.c_void_p, C.POINTER(ImageDesc), C.c_size_t, C.POINTER(QuantParams), C.POINTER(QuantReport), C.c_void_p]),
+    "pngloss_hip_multi_quantize_batch_host": (C.c_int, [C.c_void_p, C.POINTER(HostImage), C.c_size_t, C.POINTER(QuantParams), C.POINTER(QuantReport)]),
 }
 
 
@@ -350,7 +377,7 @@ def hip_lib():
                 except ImportError:
                     pass
             lib = _load(os.environ.get("PNGLOSS_HIP_LIBNAME", "libpngloss_hip.so"))
-            for name, (ret, args) in {**PROTOTYPES, **INDEXED_PROTOTYPES}.items():
+            for name, (ret, args) in {**PROTOTYPES, **INDEXED_PROTOTYPES, **QUANT_PROTOTYPES}.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = ret, args
             _hip = lib
@@ -724,6 +751,16 @@ class HipContext:
         _check(self._lib.pngloss_hip_last_palette(self._ctx, index, C.byref(r)), "last_palette")
         return r
 
+    def quantize(self, images, max_colors=256, rounds=8, stream=0):
+        """pngloss_hip_quantize_batch: images as for run() (device-resident RGBA8), quantised in place to at most max_colors colours each.
+        Synchronous.  Returns (images, reports): the tuples handed in, whose pixels are the quantised ones now, and one report dict per image
+        (QuantReport.as_dict)."""
+        n = len(images)
+        rep = _array(QuantReport, n)
+        params = QuantParams(max_colors, rounds)
+        _check(self._lib.pngloss_hip_quantize_batch(self._ctx, _image_descs(images), n, C.byref(params), rep, stream or None), "quantize_batch")
+        return list(images), [r.as_dict() for r in rep[:n]]
+
     def compare(self, pairs, stream=0):
         """pngloss_hip_compare_batch: pairs = sequence of (d_a_ptr, d_b_ptr, width, height), device-resident RGBA8; returns one Distortion per pair
         (b against a).  Synchronous."""
@@ -826,6 +863,16 @@ class HipMulti:
         r = Palette()
         _check(self._lib.pngloss_hip_multi_last_palette(self._m, index, C.byref(r)), "multi_last_palette")
         return r
+
+    def quantize_host(self, arrays, max_colors=256, rounds=8):
+        """pngloss_hip_multi_quantize_batch_host on a list of (H, W, 4) uint8 arrays.  Returns (outs, reports): the quantised copies and one report
+        dict per image (QuantReport.as_dict)."""
+        outs, _, imgs = _host_images(arrays, want_filters=False)
+        n = len(outs)
+        rep = _array(QuantReport, n)
+        params = QuantParams(max_colors, rounds)
+        _check(self._lib.pngloss_hip_multi_quantize_batch_host(self._m, imgs, n, C.byref(params), rep), "multi_quantize_batch_host")
+        return outs, [r.as_dict() for r in rep[:n]]
 
     def run_host(self, arrays, strength=19, bleed=2, want_filters=True):
         outs, filts, imgs = _host_images(arrays, want_filters)
