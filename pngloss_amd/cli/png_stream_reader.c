@@ -84,6 +84,7 @@ bool png_stream_read(const char *path, png_stream_source *out)
             o += 12 + (size_t)n;
         }
         if (bad || !seen_iend || !seen_idat) break;
+        if (o != (size_t)len) break;                                                            /* bytes behind IEND: libpng's to judge, like anything else unusual */
         /* the formats PNG allows */
         const int ct = out->color_type, d = out->bit_depth;
         if (!pr_valid(ct, d) || (ct == 3 && !out->palette_entries)) break;
@@ -98,8 +99,9 @@ bool png_stream_read(const char *path, png_stream_source *out)
         z.next_out = out->scanlines; z.avail_out = (uInt)want;
         const int zr = inflate(&z, Z_FINISH);
         const size_t got = want - z.avail_out;
+        const bool rest = z.avail_in != 0;                                                      /* bytes behind the stream's trailer: libpng warns and reads on -- its file */
         inflateEnd(&z);
-        if (zr != Z_STREAM_END || got != want || idat_len > 0xffffffffu || want > 0xffffffffu) break;
+        if (zr != Z_STREAM_END || got != want || rest || idat_len > 0xffffffffu || want > 0xffffffffu) break;
         out->scanline_bytes = want;
         out->file_size = (size_t)len;
         ok = true;

@@ -22,7 +22,7 @@ typedef struct {
 } png_stream_source;
 
 /* Reads the file and inflates its image data.  true: `out` is filled (free out->scanlines).  false: the file is not one this
- * path takes -- an interlace method other than none and Adam7, chunks beyond IHDR PLTE tRNS gAMA sRGB IDAT IEND (their handling is libpng's), damaged -- and the
+ * path takes -- an interlace method other than none and Adam7, chunks beyond IHDR PLTE tRNS gAMA sRGB IDAT IEND (their handling is libpng's), bytes behind IEND or behind the image data's zlib trailer, damaged -- and the
  * caller reads it with libpng instead (which also produces the error messages for damaged files). */
 bool png_stream_read(const char *path, png_stream_source *out);
 

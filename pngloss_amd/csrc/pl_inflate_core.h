@@ -356,7 +356,7 @@ PLI_HD void pli_inflate(const PliStream &st, PliShared &S)
                             for (int l = 0; l < 8; l++) cnt[l] = 0;
                             for (int i = 0; i < 19; i++) cnt[cl[i]]++;
                             cnt[0] = 0;
-                            for (int l = 1; l < 8; l++) { left = (left << 1) - (int)cnt[l]; tot += cnt[l]; }
+                            for (int l = 1; l < 8 && left >= 0; l++) { left = (left << 1) - (int)cnt[l]; tot += cnt[l]; }      /* (over-subscribed: left stays negative, no further shift of it) */
                             if (left < 0 || (left > 0 && tot != 1)) S.tok[3] = PLI_E_CODES;
                             else {
                                 uint32_t code = 0;
@@ -691,9 +691,20 @@ PLI_HD void pli_inflate(const PliStream &st, PliShared &S)
         if (pos != expect) err = PLI_E_SIZE;
         else {
             if (pos > flushed) flush(pos - flushed);
-            /* Adler-32 trailer: big endian, behind the last block at the next byte boundary */
+            /* Adler-32 trailer: big endian, behind the last block at the next byte boundary.  A trailer that does not lie wholly inside the stage (a final stored block ends
+             * wherever the stage does): lane 0 hands its position back as the block-header path does, the wave stages once more -- fewer than four bytes are kept, so whatever
+             * the stream still has of the trailer fits -- and the trailer is read from there */
             PLI_LANE0(lane) {
                 pli_drop(B, B.n & 7);
+                S.tok[0] = 0;
+                if ((uint32_t)(B.n >> 3) + (B.iend - B.ip) < 4u && zpos < zbytes) {
+                    B.ip -= (uint32_t)(B.n >> 3); B.buf = 0; B.n = 0;
+                    S.tok[6] = B.ip; S.tok[7] = B.iend; S.tok[0] = PLI_T_INPUT;
+                }
+            }
+            PLI_SYNC();
+            if (S.tok[0] == PLI_T_INPUT) stage();
+            PLI_LANE0(lane) {
                 uint32_t want = 0; bool have = true;
                 for (int i = 0; i < 4; i++) {
                     pli_refill(B, S);
@@ -703,12 +714,7 @@ PLI_HD void pli_inflate(const PliStream &st, PliShared &S)
                 S.tok[3] = (have && want == ((s2 << 16) | s1)) ? 0u : (uint32_t)(have ? PLI_E_ADLER : PLI_E_INPUT);
             }
             PLI_SYNC();
-            err = (int)S.tok[3];
-            /* (a trailer that lies beyond the stage: stage once more and look again) */
-            if (err == PLI_E_INPUT && zpos < zbytes) {
-                PLI_LANE0(lane) { B.ip = B.iend; S.tok[6] = B.ip; S.tok[7] = B.iend; }
-                err = PLI_E_ADLER;       /* (kept simple: such a stream goes to the host reader) */
-            }
+            err = (int)S.tok[3];                     /* (PLI_E_INPUT: the stream ends inside its trailer; PLI_E_ADLER: the sum is wrong) */
         }
     }
     PLI_LANE0(lane) { *st.status = err; }
