@@ -36,7 +36,15 @@ __global__ void seg_k_resolve(const PlJob *jobs, SegJob *sj, unsigned n)
 }
 
 /* The kernels of an attempt: each loads its image's record and hands its place in the grid to its dispatch function (pl_seg_launch.h), which knows what that
- * workgroup does.  (seg_k_ctl: SEG_EXPERIMENT_NO_VAL_CODE, a timing experiment, leaves the validation's code out of it and lifts its occupancy bound.) */
+ * workgroup does.  (seg_k_ctl: SEG_EXPERIMENT_NO_VAL_CODE, a timing experiment, leaves the validation's code out of it and lifts its occupancy bound.)
+ *
+ * THE HEAD of each: the kernels' own arguments arrive in scalar registers at wave launch (the Makefile builds this file with kernel-argument preloading: no
+ * load of the kernel-argument segment in front of the record's -- 0.2-0.4 us a kernel, profiles/seg_heads.txt), so no kernel here may use a hidden argument:
+ * gridDim.x is the launcher's grid_x, passed by value where a dispatch function reads it.  The replay alone also requests its view and the record fields that its
+ * dispatch and its first data request need in ONE burst of scalar loads in front of its first branch (pl_seg_launch.h: seg_view_of, seg_head_pin); what the body
+ * reads late it reads from lines that this burst has brought into the scalar cache. */
+#define SEG_GX_UNUSED 0u                  /* for the dispatch functions that ignore their gx */
+
 #if SEG_EXPERIMENT_NO_VAL_CODE
 #define SEG_CTL_BOUNDS __launch_bounds__(SEG_THREADS)
 #else
@@ -47,15 +55,15 @@ __global__ SEG_CTL_BOUNDS void seg_k_ctl(const SegJob *__restrict__ sj, const Se
 {
     extern __shared__ __align__(16) unsigned char seg_smem[];
     const SegJob j = sj[blockIdx.y];
-    seg_dispatch_ctl<TPARTS>(j, sj + blockIdx.y, *P, k, nctl, max_ngrp, blockIdx.x, gridDim.x, seg_smem);
+    seg_dispatch_ctl<TPARTS>(j, sj + blockIdx.y, *P, k, nctl, max_ngrp, blockIdx.x, SEG_GX_UNUSED, seg_smem);
 }
 
 template <int NT>
-__global__ __launch_bounds__(NT) void seg_k_enum(const SegJob *__restrict__ sj, const SegParams *__restrict__ P, int par, unsigned max_nseg)
+__global__ __launch_bounds__(NT) void seg_k_enum(const SegJob *__restrict__ sj, const SegParams *__restrict__ P, int par, unsigned max_nseg, unsigned grid_x)
 {
     extern __shared__ __align__(16) unsigned char seg_smem[];
     const SegJob j = sj[blockIdx.y];
-    seg_dispatch_enum<NT>(j, sj + blockIdx.y, *P, par, max_nseg, blockIdx.x, gridDim.x, seg_smem);
+    seg_dispatch_enum<NT>(j, sj + blockIdx.y, *P, par, max_nseg, blockIdx.x, grid_x, seg_smem);
 }
 
 template <int NT>
@@ -63,7 +71,7 @@ __global__ __launch_bounds__(NT) void seg_k_enum_seeded(const SegJob *__restrict
 {
     extern __shared__ __align__(16) unsigned char seg_smem[];
     const SegJob j = sj[blockIdx.y];
-    seg_dispatch_enum_seeded<NT>(j, sj + blockIdx.y, *P, par, max_nseg, blockIdx.x, gridDim.x, seg_smem);
+    seg_dispatch_enum_seeded<NT>(j, sj + blockIdx.y, *P, par, max_nseg, blockIdx.x, SEG_GX_UNUSED, seg_smem);
 }
 
 /* (the second bound asks for 8 waves per SIMD: the body's 100 SGPRs held it at 7 -- three workgroups of 8 waves per CU where LDS and threads allow four; with 78 + spills to
@@ -73,7 +81,7 @@ __global__ __launch_bounds__(SEG_UNT, 8) void seg_k_enum_unit(const SegJob *__re
 {
     extern __shared__ __align__(16) unsigned char seg_smem[];
     const SegJob j = sj[blockIdx.y];
-    seg_dispatch_enum_unit<UNIT>(j, sj + blockIdx.y, *P, par, perb, pers, seeds, blockIdx.x, gridDim.x, seg_smem);
+    seg_dispatch_enum_unit<UNIT>(j, sj + blockIdx.y, *P, par, perb, pers, seeds, blockIdx.x, SEG_GX_UNUSED, seg_smem);
 }
 
 template <bool SEEDED, int CT, bool UNITS>
@@ -81,7 +89,7 @@ __global__ __launch_bounds__(CT) void seg_k_chain(const SegJob *__restrict__ sj,
 {
     extern __shared__ __align__(16) unsigned char seg_smem[];
     const SegJob j = sj[blockIdx.y];
-    seg_dispatch_chain<SEEDED, CT, UNITS>(j, sj + blockIdx.y, *P, par, blockIdx.x, gridDim.x, seg_smem);
+    seg_dispatch_chain<SEEDED, CT, UNITS>(j, sj + blockIdx.y, *P, par, blockIdx.x, SEG_GX_UNUSED, seg_smem);
 }
 
 template <int RNT>
@@ -89,7 +97,10 @@ __global__ __launch_bounds__(RNT) void seg_k_replay(const SegJob *__restrict__ s
 {
     extern __shared__ __align__(16) unsigned char seg_smem[];
     const SegJob j = sj[blockIdx.y];
-    seg_dispatch_replay<RNT>(j, sj + blockIdx.y, *P, par, max_ngrp, blockIdx.x, gridDim.x, seg_smem);
+#if defined(__HIP_DEVICE_COMPILE__)
+    seg_head_pin(seg_view_words(sj + blockIdx.y, par), j.img, j.W, j.bpp, j.rowcopy, j.ctl, j.base, j.H0, j.acc, j.tables, j.rck, j.dnout, j.nseg, j.ngrp);
+#endif
+    seg_dispatch_replay<RNT>(j, sj + blockIdx.y, *P, par, max_ngrp, blockIdx.x, SEG_GX_UNUSED, seg_smem);
 }
 
 /* The ORDER of the kernels in the code object, pinned: the one-image kernels first, in the order round 4's library had them, the kernels of batches behind
@@ -101,8 +112,8 @@ template __global__ void seg_k_chain<false, SEG_CHAIN_THREADS, false>(const SegJ
 template __global__ void seg_k_chain<true, SEG_CHAIN_THREADS, false>(const SegJob *__restrict__, const SegParams *__restrict__, int);
 template __global__ void seg_k_enum_seeded<512>(const SegJob *__restrict__, const SegParams *__restrict__, int, unsigned);
 template __global__ void seg_k_enum_seeded<1024>(const SegJob *__restrict__, const SegParams *__restrict__, int, unsigned);
-template __global__ void seg_k_enum<512>(const SegJob *__restrict__, const SegParams *__restrict__, int, unsigned);
-template __global__ void seg_k_enum<1024>(const SegJob *__restrict__, const SegParams *__restrict__, int, unsigned);
+template __global__ void seg_k_enum<512>(const SegJob *__restrict__, const SegParams *__restrict__, int, unsigned, unsigned);
+template __global__ void seg_k_enum<1024>(const SegJob *__restrict__, const SegParams *__restrict__, int, unsigned, unsigned);
 template __global__ void seg_k_ctl<SEG_TPARTS_BATCH>(const SegJob *__restrict__, const SegParams *__restrict__, int, unsigned, unsigned);
 template __global__ void seg_k_enum_unit<SEG_UNIT>(const SegJob *__restrict__, const SegParams *__restrict__, int, unsigned, unsigned, int);
 template __global__ void seg_k_chain<false, SEG_CHAIN_THREADS_UNIT, true>(const SegJob *__restrict__, const SegParams *__restrict__, int);
@@ -115,7 +126,7 @@ template __global__ void seg_k_enum_unit<1>(const SegJob *__restrict__, const Se
 __global__ __launch_bounds__(SEG_GT) void seg_k_gather_seeded(const SegJob *__restrict__ sj, const SegParams *__restrict__ P, int par, unsigned nblk)
 {
     const SegJob j = sj[blockIdx.y];
-    seg_dispatch_gather(j, sj + blockIdx.y, *P, par, nblk, blockIdx.x, gridDim.x, nullptr);
+    seg_dispatch_gather(j, sj + blockIdx.y, *P, par, nblk, blockIdx.x, SEG_GX_UNUSED, nullptr);
 }
 
 /* the kernels of the engine whose dynamic LDS can exceed 64 KB: opted in per device (pl_lds_optin) */
@@ -157,8 +168,8 @@ hipError_t pl_seg_launch_attempt(const PlSegBatch &b, int attempt, hipStream_t s
         switch (L.kernel) {
         case SEG_KERNEL_CTL: SEG_LAUNCH(seg_k_ctl<SEG_TPARTS>, L.a, L.b); break;
         case SEG_KERNEL_CTL_BATCH: SEG_LAUNCH(seg_k_ctl<SEG_TPARTS_BATCH>, L.a, L.b); break;
-        case SEG_KERNEL_ENUM_512: SEG_LAUNCH(seg_k_enum<512>, L.a); break;
-        case SEG_KERNEL_ENUM_1024: SEG_LAUNCH(seg_k_enum<1024>, L.a); break;
+        case SEG_KERNEL_ENUM_512: SEG_LAUNCH(seg_k_enum<512>, L.a, L.grid_x); break;
+        case SEG_KERNEL_ENUM_1024: SEG_LAUNCH(seg_k_enum<1024>, L.a, L.grid_x); break;
         case SEG_KERNEL_ENUM_SEEDED_512: SEG_LAUNCH(seg_k_enum_seeded<512>, L.a); break;
         case SEG_KERNEL_ENUM_SEEDED_1024: SEG_LAUNCH(seg_k_enum_seeded<1024>, L.a); break;
         case SEG_KERNEL_ENUM_UNIT: SEG_LAUNCH(seg_k_enum_unit<SEG_UNIT>, L.a, L.b, L.seeds); break;

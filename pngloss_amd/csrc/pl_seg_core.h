@@ -311,9 +311,10 @@ static_assert(sizeof(SegCtl) / 4 <= 128 && sizeof(SegAcc) / 4 <= 128, "the contr
 /* What the workgroups of an attempt branch on, kept INSIDE the job record (three deep, like the control blocks): the record is the first thing
  * every workgroup loads, so these fields arrive with it -- one round trip to device memory less at the head of every kernel than reading them
  * from the control block behind the record's pointer.  Written by the control workgroups (and the fail masks by the validation) next to the
- * control block's own fields.  The kernels build a workgroup's SegCtlView from the record IN MEMORY (pl_seg.hip:seg_view_of: scalar loads whose
- * addresses need nothing but the kernel's arguments, in flight together with the record itself) and hand it to the body; the CPU harness calls
- * seg_ctl_view. */
+ * control block's own fields.  The kernels build a workgroup's SegCtlView from the record IN MEMORY (pl_seg_launch.h:seg_view_of: scalar loads whose
+ * addresses need nothing but the kernel's arguments) and hand it to the body; the CPU harness calls seg_ctl_view.  In the compiled code these loads are in
+ * flight together with the record's own only in the replay, whose kernel sees to it; everywhere else they follow the record's in one or two round trips of
+ * their own (0.06-0.1 us each), which is cheaper there than keeping the words in registers (seg_view_of, profiles/seg_heads.txt). */
 struct SegViewRec { uint32_t finished, y, s, ignore, magic, pad_; uint32_t active[SEG_NFILT], start_x[SEG_NFILT]; };
 struct SegJob {
     SEG_AS_GLB uint32_t *img;            /* slots image (pl_device.h) */

@@ -4,7 +4,7 @@
  * returns, the call of the kernel body in pl_seg_core.h).  Internal.
  *
  * Plain C++17 plus the PLS_* macros of pl_seg_core.h, no HIP API.  pl_seg.hip carries it out -- its __global__ functions call the dispatch functions with
- * blockIdx.x / gridDim.x, its launcher loops over seg_attempt_launches() --, pl_plan.h fills the SegShape of every launch group, and the CPU harness
+ * blockIdx.x and the launch's grid_x, its launcher loops over seg_attempt_launches() --, pl_plan.h fills the SegShape of every launch group, and the CPU harness
  * (tests/c/seg_host.cpp) runs the same launches block by block, so that the CPU suite covers the grids and the decode of the shipped library, not a copy of them
  * (tests/test_seg_launch_host.py pins every number and checks that every piece of work is visited exactly once).
  */
@@ -44,7 +44,7 @@ enum SegKernel {
 };
 
 /* one launch of an attempt: grid (grid_x, images of the group), `threads` a workgroup, `lds_bytes` of dynamic LDS, and the kernel's scalar arguments behind `par`:
- * control a = nctl, b = max_ngrp; enumeration a = max_nseg -- in units / from seeds a = perb, b = pers, seeds; gather a = nblk; chain none; replay a = max_ngrp */
+ * control a = nctl, b = max_ngrp; enumeration a = max_nseg (and grid_x, which its dispatch reads: no kernel reads gridDim) -- in units / from seeds a = perb, b = pers, seeds; gather a = nblk; chain none; replay a = max_ngrp */
 struct SegLaunch {
     SegKernel kernel;
     unsigned grid_x, threads;
@@ -93,14 +93,50 @@ inline int seg_attempt_launches(const SegShape &s, SegLaunch out[SEG_MAX_LAUNCHE
 
 /* ---- what workgroup bx of a grid of gx does: j = the image's record, already loaded; rec = where it lives (the view is read from there) ---------------------- */
 
-/* a workgroup's view of attempt k (SegCtlView).  On the device straight from the record in device memory: every address follows from the kernel's arguments, so
- * these scalar loads travel with the loads of the record itself -- no second round trip before the workgroup knows whether it has work */
+/* a workgroup's view of attempt k (SegCtlView).  On the device straight from the record in device memory.  Every address follows from the kernel's arguments,
+ * but these scalar loads do NOT travel with the loads of the record itself: the compiler requests a scalar load where its value is first needed and moves it
+ * behind every branch it can (the `||` below is such a branch), so a kernel waits for the record's fields, for the view, and for `ignore` and the fail mask, one
+ * round trip after another (profiles/seg_heads.txt).  Such a trip costs 0.06-0.1 us behind a kernel boundary (profiles/ubench_headtrips.txt), less than what
+ * holding the words in scalar registers costs the enumeration, the chain and the control kernel (profiles/seg_heads.txt: measured, kernel by kernel), so they
+ * keep this form.  WHOLE (the replay, where it does pay): all of v[k] and the fail mask, no load conditional -- its kernel pins them in front of its first
+ * branch (pl_seg.hip: seg_k_replay), one burst with the record's fields and one wait before the first request for data. */
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef const __attribute__((address_space(4))) SegJob *seg_const_job;
+struct SegViewWords { uint32_t finished, y, s, ignore, magic, active[SEG_NFILT], start_x[SEG_NFILT], fail; };
+__device__ __forceinline__ SegViewWords seg_view_words(const SegJob *rec, int k)
+{
+    seg_const_job c = (seg_const_job)(uintptr_t)rec;
+    SegViewWords w;
+    w.finished = c->v[k].finished; w.y = c->v[k].y; w.s = c->v[k].s; w.ignore = c->v[k].ignore; w.magic = c->v[k].magic;
+    for (int f = 0; f < SEG_NFILT; f++) { w.active[f] = c->v[k].active[f]; w.start_x[f] = c->v[k].start_x[f]; }
+    w.fail = c->vfail[seg_k_prev(k)];
+    return w;
+}
+/* seg_head_pin(x, ..) wants its arguments in scalar registers at the place where it stands and emits nothing: in front of a kernel's first branch it keeps
+ * their loads there, unconditional (all arguments are evaluated -- requested -- before the first of them is pinned) */
+template <typename T> __device__ __forceinline__ void seg_head_pin1(T x) { asm volatile("" :: "s"(x)); }
+template <typename... T> __device__ __forceinline__ void seg_head_pin(T... x) { (seg_head_pin1(x), ...); }
+template <> __device__ __forceinline__ void seg_head_pin1(SegViewWords w)
+{
+    seg_head_pin(w.finished, w.y, w.s, w.ignore, w.magic, w.fail);
+    for (int f = 0; f < SEG_NFILT; f++) seg_head_pin(w.active[f], w.start_x[f]);
+}
+#endif
+template <bool WHOLE = false>
 PLS_HD SegCtlView seg_view_of(const SegJob *rec, int k, int f)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
-    typedef const __attribute__((address_space(4))) SegJob *seg_const_job;
-    seg_const_job c = (seg_const_job)(uintptr_t)rec;
     SegCtlView v;
+    if (WHOLE) {
+        static_assert(SEG_NFILT == 5, "the selects below");
+        const SegViewWords w = seg_view_words(rec, k);
+        v.y = w.y; v.s = w.s;
+        v.active = f == 0 ? w.active[0] : f == 1 ? w.active[1] : f == 2 ? w.active[2] : f == 3 ? w.active[3] : w.active[4];
+        v.start_x = f == 0 ? w.start_x[0] : f == 1 ? w.start_x[1] : f == 2 ? w.start_x[2] : f == 3 ? w.start_x[3] : w.start_x[4];
+        v.finished = (unsigned)(w.finished != 0u) | (unsigned)(w.magic != SEG_MAGIC) | (unsigned)((w.fail & ~w.ignore) != 0u);
+        return v;
+    }
+    seg_const_job c = (seg_const_job)(uintptr_t)rec;
     const uint32_t fin = c->v[k].finished, magic = c->v[k].magic, ign = c->v[k].ignore, fm = c->vfail[seg_k_prev(k)];
     v.y = c->v[k].y; v.s = c->v[k].s; v.active = c->v[k].active[f]; v.start_x = c->v[k].start_x[f];
     v.finished = (fin != 0u || magic != SEG_MAGIC || (fm & ~ign) != 0u) ? 1u : 0u;
@@ -235,7 +271,7 @@ PLS_HD void seg_dispatch_replay(const SegJob &j, const SegJob *rec, const SegPar
     (void)gx;
     const unsigned f = bx / max_ngrp, grp = bx % max_ngrp;
     if (grp >= j.ngrp) return;
-    SEG_BODY(seg_replay_body)<RNT>(j, P, seg_view_of(rec, par, (int)f), par, (int)f, (int)grp, smem);
+    SEG_BODY(seg_replay_body)<RNT>(j, P, seg_view_of<true>(rec, par, (int)f), par, (int)f, (int)grp, smem);
 }
 
 #if !defined(__HIPCC__)
