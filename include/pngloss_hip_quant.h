@@ -51,8 +51,8 @@ typedef struct {
  * it enqueues goes to `stream`.  Its workspace (per image about 300 KiB of tables and width * height * 4 bytes for the result, which lies beside
  * the input until its distortion record is taken) is allocated before anything is enqueued: if it cannot be had the call returns
  * PNGLOSS_OUT_OF_MEMORY_ERROR and nothing has run.  PNGLOSS_INVALID_ARGUMENT, before any device work: ctx, params or (with n > 0) images or reports
- * NULL, max_colors outside 2 .. 256, rounds above 64, an image with pixels and no d_rgba or with more than 2^34 pixels, a batch in flight on the
- * context.  The "last batch" of the context (pngloss_hip_last_*) is not touched. */
+ * NULL, max_colors outside 2 .. 256, rounds above 64, an image with pixels and no d_rgba or with 2^32 pixels or more (a histogram bin is a 32-bit count
+ * and may take every pixel), a batch in flight on the context.  The "last batch" of the context (pngloss_hip_last_*) is not touched. */
 int pngloss_hip_quantize_batch(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n, const pngloss_hip_quant_params *params,
                                pngloss_hip_quant_report *reports, void *stream);
 

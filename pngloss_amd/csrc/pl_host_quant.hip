@@ -19,7 +19,7 @@ template <class Image> int check_quant_sizes(const Image *images, size_t n, cons
     for (size_t i = 0; i < n; i++) {
         const uint64_t px = (uint64_t)images[i].width * images[i].height;
         if (px && !pixels_of[i]) return PNGLOSS_INVALID_ARGUMENT;
-        if (px > PLQ_MAX_PIXELS) return PNGLOSS_INVALID_ARGUMENT;
+        if (!plq_pixels_ok(px)) return PNGLOSS_INVALID_ARGUMENT;
     }
     return PNGLOSS_SUCCESS;
 }

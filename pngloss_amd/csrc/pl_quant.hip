@@ -112,7 +112,7 @@ dim3 quant_grid(size_t m, uint64_t max_pixels)
 template <class Kernel>
 hipError_t launch_over_pixels(Kernel kernel, const PlQuantJob *d_jobs, size_t n, uint64_t max_pixels, hipStream_t stream)
 {
-    if (max_pixels > PLQ_MAX_PIXELS) return hipErrorInvalidValue;
+    if (!plq_pixels_ok(max_pixels)) return hipErrorInvalidValue;
     for (size_t first = 0; first < n; first += kMaxImages) {
         const size_t m = n - first < kMaxImages ? n - first : kMaxImages;
         hipLaunchKernelGGL(kernel, quant_grid(m, max_pixels), dim3(kThreads), 0, stream, d_jobs + first);

@@ -51,7 +51,12 @@ static_assert(4u * 255u * 255u < PLQ_BIAS && ((uint64_t)(2u * 4u * 255u * 255u +
 constexpr uint64_t PLQ_WG_PIXELS = (uint64_t)1 << 24;
 static_assert(255ull * PLQ_WG_PIXELS < ((uint64_t)1 << 32), "a workgroup's 32-bit cells hold the channel sums of all its pixels");
 constexpr uint32_t PLQ_MAX_BLOCKS = 1024;           /* workgroups per image of the assign pass at most */
-constexpr uint64_t PLQ_MAX_PIXELS = PLQ_WG_PIXELS * PLQ_MAX_BLOCKS;      /* a larger image is refused (PNGLOSS_INVALID_ARGUMENT) */
+/* A larger image is refused (PNGLOSS_INVALID_ARGUMENT).  A histogram bin is a 32-bit count and one bin may take every pixel of an image: the pixel
+ * count has to fit it.  (The grid alone would allow PLQ_WG_PIXELS * PLQ_MAX_BLOCKS = 2^34.) */
+constexpr uint64_t PLQ_MAX_PIXELS = ((uint64_t)1 << 32) - 1;
+static_assert(PLQ_MAX_PIXELS <= UINT32_MAX, "a histogram bin's 32-bit count holds every pixel of an image");
+static_assert(PLQ_MAX_PIXELS <= PLQ_WG_PIXELS * PLQ_MAX_BLOCKS, "the largest grid takes the largest image with no workgroup past PLQ_WG_PIXELS");
+PLQ_HD bool plq_pixels_ok(uint64_t pixels) { return pixels <= PLQ_MAX_PIXELS; }
 
 #if defined(__HIP_DEVICE_COMPILE__)
 #define PLQ_ADD32(p, v) atomicAdd((p), (v))

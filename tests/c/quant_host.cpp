@@ -8,6 +8,7 @@
  *                     u32 non-empty bins, u32 sum of the histogram; width * height u32 words: the image as it is now
  *        quant_host cut hist.bin max_colors       (65 536 u32 counts) prints the median cut's palette, one hex word per line
  *        quant_host grid pixels want ...          prints "pixels want blocks wg_pixels" per pair
+ *        quant_host pixels width height ...      prints "width height pixels ok" per pair (plq_pixels_ok), then "limit PLQ_MAX_PIXELS"
  *        quant_host layout inputs w h [w h ...]   prints "name offset bytes" per region of pl_quant_layout, then "total 0 bytes" */
 #include <algorithm>
 #include <cstdint>
@@ -150,6 +151,15 @@ int main(int argc, char **argv)
             printf("%llu %u %u %llu\n", (unsigned long long)pixels, want, blocks, (unsigned long long)plq_wg_pixels(pixels, 256 * PLQ_QUAD, blocks));
         }
         printf("limits %llu %u %llu\n", (unsigned long long)PLQ_WG_PIXELS, PLQ_MAX_BLOCKS, (unsigned long long)PLQ_MAX_PIXELS);
+        return 0;
+    }
+    if (argc >= 2 && !strcmp(argv[1], "pixels")) {
+        for (int a = 2; a + 1 < argc; a += 2) {
+            const uint32_t w = (uint32_t)strtoul(argv[a], nullptr, 10), h = (uint32_t)strtoul(argv[a + 1], nullptr, 10);
+            const uint64_t px = (uint64_t)w * h;                    /* (the product as the argument check takes it) */
+            printf("%u %u %llu %d\n", w, h, (unsigned long long)px, plq_pixels_ok(px) ? 1 : 0);
+        }
+        printf("limit %llu\n", (unsigned long long)PLQ_MAX_PIXELS);
         return 0;
     }
     if (argc >= 3 && !strcmp(argv[1], "layout")) {

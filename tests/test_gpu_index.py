@@ -1,7 +1,8 @@
 """GPU tests of the option "indexed" (include/pngloss_hip.h, "Indexed-colour streams"): pngloss_hip_optimize_batch_host_zlib with the option on against
 the numpy restatement of tests/util_index.py applied to the pixels the same call returned, against the call with the option off, and against the CPU
 run of the device's deflate encoder (tests/util.py:deflate_host) on the restated index rows.  Then the suite images the feature was proposed on,
-the command line switch, and the multi-context form."""
+the command line switch, and the multi-context form.  The shapes of X.device_shapes() take the loops of pl_index_rows and pl_index_count past their
+first trip; for them the decision and both streams are also worked out on the CPU alone."""
 import io
 import os
 import subprocess
@@ -100,6 +101,94 @@ def test_single_image_calls_equal_the_batch(ctx, runs):
         i = NAMES.index(name)
         one = _call(ctx, [SHAPES[name]], 0, True)
         assert one[2][0] == runs[0][1][2][i] and one[4][0] == runs[0][1][4][i], name
+
+
+# ---- the loops past one trip (X.device_shapes): rows past the 512 workgroups of an image, pixels past the 1024 of one pass, chunks past the
+# workgroups of the count kernel ----
+
+TRIPS = ["3x1100_five_colours", "4099x3_five_colours", "1030x520_256_colours"]
+LAST_PIXEL = ["257th_in_the_last_pixel", "257th_in_the_first_pixel", "256th_in_the_last_pixel"]
+
+
+@pytest.fixture(scope="module")
+def device():
+    shapes = X.device_shapes()
+    assert list(shapes) == TRIPS + LAST_PIXEL
+    return shapes
+
+
+@pytest.fixture(scope="module")
+def on_the_cpu(device):
+    """name -> (kept, indexed stream or None, truecolour stream): the decision and both streams of the unchanged pixels from the restatements
+    and the CPU run of the encoder alone -- nothing of it comes from the library"""
+    out = {}
+    for name, img in device.items():
+        pixels, flags = U.run_port(img, 0, 2)
+        assert np.array_equal(pixels, img)                                  # strength 0 changes no pixel
+        _, ids, rows = U.png_scanlines_reference(img, flags)
+        truecolor = U.deflate_host(np.concatenate([ids[:, None], rows], axis=1).tobytes())[0]
+        want = X.restate(img)
+        indexed = U.deflate_host(want["scanlines"])[0] if want["eligible"] else None
+        kept = X.keep_indexed(want["eligible"], len(indexed or b""), len(truecolor), want.get("entries", 0), want.get("trns_entries", 0))
+        print(name, "colours", want["colors"], "I", len(indexed or b""), "T", len(truecolor), "kept", kept)
+        out[name] = (kept, indexed, truecolor)
+    return out
+
+
+@pytest.fixture(scope="module")
+def alone(ctx, device):
+    """name -> (off, on): every device shape in a call of its own, at strength 0"""
+    return {name: (_call(ctx, [img], 0, False), _call(ctx, [img], 0, True)) for name, img in device.items()}
+
+
+@pytest.mark.parametrize("name", TRIPS)
+def test_rows_and_pixels_past_one_trip(device, on_the_cpu, alone, name):
+    img = device[name]
+    h, w = img.shape[:2]
+    if name == "3x1100_five_colours":           # rows 512..1023 a second trip of their workgroup, rows 1024..1099 a ragged third
+        assert h > 2 * X.ROW_BLOCKS and h % X.ROW_BLOCKS and w < 4
+    if name == "4099x3_five_colours":           # four passes of 1024 pixels and a tail of three
+        assert w == 4 * X.ROW_PASS + 3 and w % 4 == 3 and h < X.ROW_BLOCKS
+    if name == "1030x520_256_colours":          # both loops at once, and a full table
+        assert h > X.ROW_BLOCKS and w > X.ROW_PASS and X.restate(img)["colors"] == 256
+    cpu_kept, indexed, truecolor = on_the_cpu[name]
+    assert cpu_kept, name                       # the indexed stream is the one that comes back: its bytes are compared, not only its length
+    off, on = alone[name]
+    assert _check(off, on, 0, name)
+    assert on[2][0] == (3, indexed, on[2][0][2]) and off[2][0][1] == truecolor, name
+    assert np.array_equal(on[0][0], img), name
+
+
+@pytest.mark.parametrize("name", LAST_PIXEL)
+def test_the_deciding_colour_in_one_pixel(device, on_the_cpu, alone, name):
+    """59 chunks over the workgroups of pl_index_count: the 257th colour, or the 256th, only in the last pixel of the last chunk (or the first
+    of the first) -- where the early exit, which re-reads the counter before each chunk and each insertion, decides eligibility"""
+    img = device[name]
+    assert img.shape[:2] == (200, 300) and -(-300 * 200 // 1024) == 59
+    cpu_kept, indexed, truecolor = on_the_cpu[name]
+    off, on = alone[name]
+    kept = _check(off, on, 0, name)
+    pal = on[4][0]
+    assert kept == cpu_kept and off[2][0][1] == truecolor and np.array_equal(on[0][0], img), name
+    if name.startswith("257th"):
+        assert X.restate(img)["colors"] == 257 and not kept
+        assert pal["colors"] == 257 and pal["indexed_bytes"] == 0 and on[2][0] == off[2][0], name
+    else:
+        assert X.restate(img)["colors"] == 256 and kept
+        assert pal["colors"] == 256 and pal["entries"] == 256 and len(pal["plte"]) == 3 * 256 and on[2][0][:2] == (3, indexed), name
+
+
+def test_the_device_shapes_in_one_batch_equal_each_alone(ctx, device, alone):
+    names = list(device) + ["1x1", "empty"]
+    images = [device[n] for n in device] + [SHAPES["1x1"], np.zeros((0, 0, 4), np.uint8)]
+    off, on = _call(ctx, images, 0, False), _call(ctx, images, 0, True)
+    for i, (name, img) in enumerate(zip(names, images)):
+        _check(off, on, i, f"{name} in the batch")
+        one_off, one_on = alone[name] if name in alone else (_call(ctx, [img], 0, False), _call(ctx, [img], 0, True))
+        for batch, one in ((off, one_off), (on, one_on)):
+            assert np.array_equal(batch[0][i], one[0][0]) and np.array_equal(batch[1][i], one[1][0]) and batch[2][i] == one[2][0] and batch[3][i] == one[3][0], name
+        assert on[4][i] == one_on[4][0], name
+    assert [z[0] for z in on[2]][:6] == [3, 3, 3] + [off[2][3][0], off[2][4][0], 3] and on[2][-1][1] == b""
 
 
 def test_accessor_rules(ctx):

@@ -1,6 +1,6 @@
 """CPU tests of the colour quantiser (no GPU): the kernels' logic and the host's median cut (pngloss_amd/csrc/pl_quant_core.h) run on the CPU under
 the sanitizers -- with one thread, and with a team of host threads that accumulate concurrently -- against the restatement of tests/util_quant.py;
-the median cut's tie rules on hand-made histograms; the 2^24-pixel bound of a workgroup as arithmetic; the workspace layout; the binding tables
+the median cut's tie rules on hand-made histograms; the 2^24-pixel bound of a workgroup and the 2^32 - 1 pixels of an image as arithmetic; the workspace layout; the binding tables
 against the compiler's view of include/pngloss_hip_quant.h; the argument checks that need no device; the switch --colors; and the restatement's
 quality against Pillow's quantiser."""
 import ctypes as C
@@ -117,16 +117,40 @@ def test_a_workgroup_never_takes_more_than_2_to_the_24_pixels(exe):
     """arithmetic, not a run: the grid the launch picks (plq_blocks) against the restated rule, and the pixels of its busiest workgroup against
     the bound that keeps 255 * pixels inside a 32-bit cell"""
     assert 255 * Q.WG_PIXELS < 1 << 32 <= 256 * Q.WG_PIXELS + (1 << 24)
-    sizes = [1, 3, 1023, 1024, 1025, 8481, 1 << 20, 4096 * 4096, (1 << 24) - 1, 1 << 24, (1 << 24) + 1, 3 << 24, (1 << 30) + 5, 1 << 32, (511 << 24) + 1, (512 << 24) + 1,
-             (1 << 34) - 1, 1 << 34]
+    sizes = [1, 3, 1023, 1024, 1025, 8481, 1 << 20, 4096 * 4096, (1 << 24) - 1, 1 << 24, (1 << 24) + 1, 3 << 24, (1 << 30) + 5, Q.MAX_PIXELS, 1 << 32, (511 << 24) + 1,
+             (512 << 24) + 1, (1 << 34) - 1, 1 << 34]
     args = [str(v) for p in sizes for want in (1, 8, 2048) for v in (p, want)]
     lines = subprocess.run([exe, "grid"] + args, capture_output=True, text=True, check=True).stdout.splitlines()
-    assert lines[-1].split() == ["limits", str(Q.WG_PIXELS), str(Q.MAX_BLOCKS), str(Q.WG_PIXELS * Q.MAX_BLOCKS)]
+    assert lines[-1].split() == ["limits", str(Q.WG_PIXELS), str(Q.MAX_BLOCKS), str(Q.MAX_PIXELS)]
+    assert Q.MAX_PIXELS <= Q.WG_PIXELS * Q.MAX_BLOCKS               # (the grid rule holds for every size below: past the largest image that is taken)
     assert len(lines) == 3 * len(sizes) + 1
     for line in lines[:-1]:
         pixels, want, blocks, busiest = (int(x) for x in line.split())
         assert blocks == Q.blocks(pixels, want) and busiest == Q.wg_pixels(pixels, blocks), line
         assert 1 <= blocks <= Q.MAX_BLOCKS and busiest <= Q.WG_PIXELS and blocks * busiest >= pixels, line
+
+
+def test_an_images_pixel_count_fits_a_histogram_bin(exe):
+    """the size predicate of the argument checks (plq_pixels_ok) at its boundary: a bin of the histogram is a 32-bit count and one bin may take every
+    pixel, so 2^32 - 1 pixels are the most.  Arithmetic on the CPU only: a device test of the refusal would hand an unfixed library 16 GiB to read"""
+    assert Q.MAX_PIXELS == 0xFFFFFFFF and 65535 * 65537 == Q.MAX_PIXELS and 3 * 5 * 17 * 257 * 65537 == Q.MAX_PIXELS
+    sizes = [(0, 0), (1, 1), (70, 46), (65535, 65537), (65537, 65535), (1, 0xFFFFFFFF), (0xFFFFFFFF, 1), (255, 16843009), (65536, 65535), (65536, 65536),
+             (2, 1 << 31), (1 << 31, 2), (65537, 65536), (1 << 17, 1 << 17), (0xFFFFFFFF, 0xFFFFFFFF)]
+    lines = subprocess.run([exe, "pixels"] + [str(v) for s in sizes for v in s], capture_output=True, text=True, check=True).stdout.splitlines()
+    assert lines[-1].split() == ["limit", str(Q.MAX_PIXELS)] and len(lines) == len(sizes) + 1
+    for (w, h), line in zip(sizes, lines):
+        assert [int(x) for x in line.split()] == [w, h, w * h, int(w * h <= Q.MAX_PIXELS)], line
+    verdict = {s: int(line.split()[3]) for s, line in zip(sizes, lines)}
+    assert verdict[(65535, 65537)] == 1 and verdict[(1, 0xFFFFFFFF)] == 1                       # 2^32 - 1 pixels are taken
+    assert verdict[(65536, 65536)] == 0 and verdict[(2, 1 << 31)] == 0                          # 2^32 are refused
+    assert verdict[(0xFFFFFFFF, 0xFFFFFFFF)] == 0 and verdict[(1 << 17, 1 << 17)] == 0          # (the old bound's 2^34 too)
+    # both entry points and the launches ask the predicate, and the constant is stated once
+    host = open(os.path.join(CSRC, "pl_host_quant.hip")).read()
+    assert "if (!plq_pixels_ok(px)) return PNGLOSS_INVALID_ARGUMENT;" in host and host.count("check_quant_sizes(images, n, pixels_of.data())") == 2
+    for name in ("pl_host_quant.hip", "pl_quant.hip", "pl_quant.h"):
+        assert "PLQ_MAX_PIXELS" not in open(os.path.join(CSRC, name)).read(), name
+    core = open(os.path.join(CSRC, "pl_quant_core.h")).read()
+    assert len(re.findall(r"constexpr uint64_t PLQ_MAX_PIXELS\b", core)) == 1 and "static_assert(PLQ_MAX_PIXELS <= UINT32_MAX" in core
 
 
 @pytest.mark.parametrize("inputs", [0, 1])

@@ -100,6 +100,47 @@ def shapes():
     return out
 
 
+def last_pixel_images():
+    """name -> 300x200 image (59 chunks of 1024 pixels): the colour that decides eligibility lies in one pixel only.  Two images have 256 opaque
+    colours everywhere and a 257th in pixel (199, 299) or in pixel (0, 0); the third has 255 everywhere and its 256th only in the last pixel"""
+    rng = np.random.default_rng(57)
+    c = rng.choice(1 << 24, 257, replace=False).astype(np.uint32) | np.uint32(0xFF000000)
+    w, h = 300, 200
+    out = {}
+    body = rng.choice(c[:256], w * h)
+    for name, at in (("257th_in_the_last_pixel", w * h - 1), ("257th_in_the_first_pixel", 0)):
+        words_ = body.copy()
+        words_[at] = c[256]
+        out[name] = from_words(words_, w, h)
+        assert len(np.unique(words_)) == 257 and int((words_ == c[256]).sum()) == 1
+    words_ = rng.choice(c[:255], w * h)
+    words_[-1] = c[255]
+    out["256th_in_the_last_pixel"] = from_words(words_, w, h)
+    assert len(np.unique(words_)) == 256 and int((words_ == c[255]).sum()) == 1
+    return out
+
+
+def device_shapes():
+    """name -> (H, W, 4) uint8 image: shapes for the GPU tests only, at which the loops of pl_index_rows and pl_index_count take a second trip.
+    Deterministic."""
+    rng = np.random.default_rng(29)
+    opaque = lambda n: (rng.choice(1 << 24, n, replace=False).astype(np.uint32) | np.uint32(0xFF000000))
+    five = np.concatenate([opaque(4), np.array([0x40102030], np.uint32)])
+    out = {}
+    out["3x1100_five_colours"] = from_words(rng.choice(five, 3 * 1100), 3, 1100)          # rows 512..1023 a second trip, 1024..1099 a ragged third
+    out["4099x3_five_colours"] = from_words(rng.choice(five, 4099 * 3), 4099, 3)          # four passes of 1024 pixels and a tail of three
+    out["1030x520_256_colours"] = from_words(rng.choice(opaque(256), 1030 * 520), 1030, 520)
+    out.update(last_pixel_images())
+    for name in ("3x1100_five_colours", "4099x3_five_colours"):
+        assert restate(out[name])["colors"] == 5
+    assert restate(out["1030x520_256_colours"])["colors"] == 256
+    return out
+
+
+ROW_BLOCKS = 512               # pl_launch_index_rows: min(height, 512) workgroups an image, each striding over the rows
+ROW_PASS = 1024                # ... of 256 lanes with four pixels each, striding over a row
+
+
 # ---- tests/c/index_host.cpp: the core's bodies on the CPU, under the sanitizers ----
 
 def build_index_host(tmp_path):

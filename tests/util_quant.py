@@ -14,6 +14,7 @@ MAX_COLORS = 256
 BINS = 65536
 WG_PIXELS = 1 << 24            # what one workgroup of the assign pass may take: 255 * 2^24 < 2^32
 MAX_BLOCKS = 1024
+MAX_PIXELS = (1 << 32) - 1     # the largest image that is taken: a histogram bin is a 32-bit count and one bin may take every pixel
 CHUNK = 1024                   # pixels a workgroup takes per step: 256 lanes of 4
 
 
@@ -46,7 +47,7 @@ def _box(bins, hist):
 def median_cut(hist, max_colors, trace=None):
     """the initial palette of a 65 536-bin histogram (a sequence of ints): a list of 1 .. max_colors words, in the order of the box list.
     trace: a list that gets one (box index, channel, cut) per split."""
-    bins = [b for b in range(BINS) if hist[b]]
+    bins = [int(b) for b in np.nonzero(np.asarray(hist[:BINS]))[0]]          # ascending
     if not bins:
         return []
     boxes = [_box(bins, hist)]
@@ -168,6 +169,54 @@ def shapes():
     out["rose_256_no_rounds"] = (rose, 256, 0)
     out["noise_257x33"] = (P.synth_rgba(257, 33, 1, 0), 256, 2)
     out["checker_64x48"] = (P.synth_rgba(64, 48, 5, 0), 4, 8)
+    return out
+
+
+def want_blocks(images):
+    """the workgroups an image the launches of pl_quant.hip would like over `images` working images (quant_grid), restated"""
+    return max(8, -(-2048 // images))
+
+
+def busiest_wg_pixels(pixels, images):
+    """the pixels the busiest workgroup takes of the largest image (`pixels`) of a launch over `images` working images"""
+    return wg_pixels(pixels, blocks(pixels, want_blocks(images)))
+
+
+def device_shapes():
+    """name -> (image or list of images, max_colors, rounds): shapes for the GPU tests only -- multi-megapixel images do not belong in the CPU
+    harness runs of shapes() --, at which a workgroup takes more than one chunk, a channel sum passes 2^32, the cut ends with one entry.
+    Deterministic."""
+    from tests.util_index import last_pixel_images
+    rng = np.random.default_rng(43)
+    distinct = lambda n: np.unique(rng.integers(0, 1 << 32, n + 64, dtype=np.uint64).astype(np.uint32))[:n]
+    out = {}
+    # 2113 chunks against the 2048 workgroups a single image gets
+    pool = rng.permutation(distinct(3000))
+    out["two_chunks_single"] = (from_words(rng.choice(pool, 2100 * 1030), 2100, 1030), 256, 2)
+    # 256 working images: 8 workgroups each, sized by the 10 chunks of the large image in the middle
+    batch = []
+    for _ in range(255):
+        three = distinct(3)
+        batch.append(from_words(rng.permutation(three[[0, 1, 2, int(rng.integers(0, 3))]]), 2, 2))
+    batch.insert(127, from_words(rng.choice(distinct(300), 100 * 100), 100, 100))
+    out["two_chunks_in_a_batch"] = (batch, 2, 3)
+    # one entry takes every bright pixel: its red sum is past 2^32; and the two extreme words, |c|^2 = 0 and p.c = 4 * 255^2
+    three = np.array([0x00000000, 0xFFFFFFFF, 0xFFFEFDFC], np.uint32)
+    out["sums_past_32_bits"] = (from_words(rng.choice(three, 4608 * 4096, p=[0.05, 0.475, 0.475]), 4608, 4096), 2, 2)
+    # more than 256 colours in ONE histogram bin: the cut cannot split it
+    nibbles = rng.choice(1 << 16, 299, replace=False).astype(np.uint32)
+    in_one_bin = np.uint32(0x80808080) + ((nibbles & 15) | ((nibbles >> 4) & 15) << 8 | ((nibbles >> 8) & 15) << 16 | ((nibbles >> 12) & 15) << 24)
+    image = from_words(rng.permutation(np.concatenate([in_one_bin, rng.choice(in_one_bin, 40 * 40 - 299)])), 40, 40)
+    out["one_bin_299_colours"] = (image, 256, 8)
+    out["one_bin_299_colours_to_2"] = (image, 2, 8)
+    rose = U.load_npz("suite_inputs.npz")["rose"]
+    for n in (3, 5, 7, 255):                                            # entry counts around the search loop's unroll of four
+        out[f"rose_{n}"] = (rose, n, 2)
+    for name, img in last_pixel_images().items():
+        out[name] = (img, 256, 2)
+    out["3x1100_300_colours"] = (from_words(rng.choice(distinct(300) | np.uint32(0xFF000000), 3 * 1100), 3, 1100), 5, 2)
+    assert len(np.unique(words(out["two_chunks_single"][0]))) == 3000 and all(len(np.unique(words(a))) == 3 for a in batch if a.shape[0] == 2)
+    assert len(np.unique(words(image))) == 299 and len(np.unique(bin_of(words(image)))) == 1
     return out
 
 
