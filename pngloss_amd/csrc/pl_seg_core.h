@@ -140,6 +140,9 @@ typedef SEG_AS_LDS uint16_t *seg_lds_u16;
 #ifndef SEG_DEBUG_STATE
 #define SEG_DEBUG_STATE(f, k, sl, i, ps)   /* (the CPU harness can count the distinct states of a pair at every segment's end: how fast a unit's states keep merging) */
 #endif
+#ifndef SEG_DEBUG_SMALL
+#define SEG_DEBUG_SMALL(tables, walked, out)   /* (the CPU harness counts the lanes of none / up that walked their tables, and those that ran the step loop and where that left them) */
+#endif
 #ifndef SEG_DEBUG_COUNT
 #define SEG_DEBUG_COUNT(slot, v)   /* (the CPU harness counts a few things the tests pin) */
 #endif
@@ -1345,17 +1348,66 @@ PLS_HD void seg_enum_seeded_body(const SegJob &j, const SegParams &P, const SegC
     }
 }
 
-/* ---- ENUMERATE, none / up (state = (cn, th), SEG_NSS lanes per channel): task (f, SEG_SMALL_SEGS segments from seg0) -------- */
-template <int NT>
+/* ---- ENUMERATE, none / up (state = (cn, th), SEG_NSS lanes per channel): task (f, SEG_SMALL_SEGS segments from seg0) --------
+ * Their prediction ignores the left pixel, and a step reads th only to add it to what it leaves: against the frozen tables, what one pixel does to a state is
+ * cn' = rem_p(cn) + th, th' = thr_p(cn), with rem_p, thr_p (and the byte the step leaves) functions of cn alone that are known without the pixels in front.  The TABLE
+ * PATH (round 10; whenever the tables fit the layout: seg_small_tables_fit) therefore does not run 32 dependent steps per lane: every thread takes ONE pixel record of the
+ * workgroup and steps it from every cn in -cmax .. cmax -- 2 cmax + 1 steps with nothing between them --, leaving rem and thr in shared memory; then one lane per
+ * (segment, channel, entry index) follows its 32 transitions, a lookup and two additions each, and leaves the records the loop leaves.  A lane whose cn leaves
+ * -cmax .. cmax in mid-segment (a clamped or degenerate band: a diff beyond the strength) or whose step leaves the decision tables runs the loop from its entry state. */
+/* the step loop of one lane, from entry index i: checkpoints, exit index, exit state */
+PLS_HD uint32_t seg_small_lane_loop(const SegJob &j, const SegParams &P, int f, bool trx, const SegPix *pxl, int i, size_t slot, const uint32_t *tw, const uint32_t *lut, const SegGeo &G)
+{
+    SegState st;
+    uint32_t out = SEG_INVALID;
+    if (seg_small_decode(P, i, st)) {
+        int bad = 0;
+        for (int part = 0; part < SEG_PARTS; part++) {
+            if (part) j.rck[slot * (SEG_PARTS - 1) + (part - 1)] = bad ? 0xFFFFFFFFu : seg_state_pack(st);
+            bad |= seg_run_fast_f<SEG_PL>(f, trx, pxl + part * SEG_PL * 4, 4, st, SEG_LDS_CU32(tw), G, SEG_LDS_CU32(lut));
+        }
+        if (!bad) out = seg_small_encode(P, st);
+    } else {
+        for (int part = 1; part < SEG_PARTS; part++) j.rck[slot * (SEG_PARTS - 1) + (part - 1)] = 0xFFFFFFFFu;
+    }
+    j.rout[slot] = (uint16_t)out;
+    j.rst[slot] = out == SEG_INVALID ? 0xFFFFFFFFu : seg_state_pack(st);
+    return out;
+}
+#define SEG_SMALL_NONE 0x80FFu    /* a step-table entry: the step is void (it left the decision tables, or rem / thr the entry's bytes): rem = 127 sends any lane beyond cmax */
+/* one pixel record (thread q of the workgroup) from every cn: ct[k][q] = rem + 128 | (thr + 128) << 8 of the step from cn = k - cmax, th = 0; bk[k][qb] = the byte it leaves (a part's last pixel only) */
+template <int F, bool TRX, int NT>
+PLS_HD void seg_small_eval(int cmax, const SegPix &rec, int q, int qb, const SegStepMem &M, const SegGeo &G, SEG_AS_LDS uint16_t *ct, SEG_AS_LDS uint8_t *bk)
+{
+#if defined(__HIPCC__)
+    _Pragma("unroll 3")
+#endif
+    for (int k = 0; k <= 2 * cmax; k++) {
+        SegState st;
+        st.left = 0; st.cn = k - cmax; st.th = 0;
+        int bad = 0;
+        seg_step_fast<F, TRX>(rec, st, bad, M, G);
+        const bool ok = !seg_bad(bad) && st.cn >= -64 && st.cn <= 64 && st.th >= -64 && st.th <= 64;
+        ct[k * NT + q] = (uint16_t)(ok ? (uint32_t)(st.cn + 128) | (uint32_t)(st.th + 128) << 8 : SEG_SMALL_NONE);
+        if (qb >= 0) bk[k * (NT / SEG_PL) + qb] = (uint8_t)st.left;
+    }
+}
+template <int NT, bool TABLES = true>
 PLS_HD void seg_enum_small_body(const SegJob &j, const SegParams &P, const SegCtlView &cv, int par, int f, int seg0, unsigned char *smem)
 {
     if (cv.finished || cv.active != 1) return;
     const uint32_t W = j.W, bpp = j.bpp;
     constexpr int NSEGS = NT / (4 * SEG_NSS);                 /* segments of this workgroup */
+    static_assert(NSEGS * SEG_L * 4 == NT, "the table path: one pixel record per thread");
     if ((uint32_t)(seg0 + NSEGS) * SEG_L <= cv.start_x) return;
     typedef SegLdsSmall<NT> LDS;
     uint32_t *tw = LDS::tw(smem), *lut = LDS::lut(smem);
     SegPix *px = LDS::px(smem);                                /* [NSEGS][SEG_L][4] */
+    const int ns = P.ns_small, cmax = P.cmax, tmax = P.tmax;
+    const bool tab = TABLES && seg_small_tables_fit<NT>(ns, cmax, tmax);   /* one choice for the launch */
+    SEG_AS_LDS uint32_t *sts = LDS::sts(smem);
+    SEG_AS_LDS uint16_t *ct = LDS::ct(smem);
+    SEG_AS_LDS uint8_t *kl = LDS::kl(smem), *bk = LDS::bk(smem);
     const uint32_t y = cv.y;
     const uint32_t *row = seg_row_orig(j, y), *nab = y ? j.img + (size_t)(y - 1u) * W : nullptr, *e0g = seg_e0(j, y);
     const SegGeo G = seg_geo((int)cv.s);
@@ -1364,12 +1416,17 @@ PLS_HD void seg_enum_small_body(const SegJob &j, const SegParams &P, const SegCt
     PLS_SYNC();
     PLS_THREADS(tid, NT) {
         constexpr int NTW = (SEG_TBL_WORDS + NT - 1) / NT;
-        uint32_t vt[NTW], vl = 0;
+        static_assert(SEG_SMALL_KL <= NT && SEG_NSS <= NT, "one entry of the set's tables per thread");
+        uint32_t vt[NTW], vl = 0, vs = 0;
+        uint16_t vk = (uint16_t)SEG_INVALID;
         SegPixRaw vp = seg_pix_raw_zero();
+        const int kn = tab ? (2 * cmax + 1) * (2 * tmax + 1) : 0;
         PLS_UNROLL
         for (int q = 0; q < NTW; q++) { const int i = tid + q * NT; vt[q] = i < SEG_TBL_WORDS ? j.tables[(size_t)f * SEG_TBL_WORDS + i] : 0u; }
         if (tid < 512) vl = P.lut_a[tid];
         if (tid < NSEGS * SEG_L) vp = seg_pix_fetch(row, nab, e0g, (uint32_t)seg0 * SEG_L + (uint32_t)tid, W);
+        if (tid < kn) vk = P.keylut_small[tid];
+        if (tab && tid < SEG_NSS) vs = P.st_small[tid];
         PLS_UNROLL
         for (int q = 0; q < NTW; q++) { const int i = tid + q * NT; if (i < SEG_TBL_WORDS) tw[i] = vt[q]; }
         if (tid < 512) lut[tid] = vl;
@@ -1377,31 +1434,66 @@ PLS_HD void seg_enum_small_body(const SegJob &j, const SegParams &P, const SegCt
             seg_pix_split4(px + tid * 4, vp, bpp, (uint32_t)seg0 * SEG_L + (uint32_t)tid, W);
             if ((bpp & 1u) == 0u && (px[tid * 4 + (bpp - 1u)].w >> 24)) PLS_ATOMIC_OR(trflag, 1u);
         }
+        if (tid < kn) kl[tid] = (uint8_t)(vk == (uint16_t)SEG_INVALID ? 255u : vk);
+        if (tab && tid < SEG_NSS) sts[tid] = vs;
     }
     PLS_SYNC();
     const bool trx = *trflag != 0u;
+    if (tab) {
+        /* evaluate: thread q = pixel record q of the workgroup, px[q] = (segment q / (SEG_L * 4), pixel (q / 4) % SEG_L, channel q % 4) */
+        PLS_THREADS(tid, NT) {
+            const int sl = tid / (SEG_L * 4), pl = (tid >> 2) & (SEG_L - 1), c = tid & 3;
+            const uint32_t seg = (uint32_t)seg0 + (uint32_t)sl, x0 = seg * SEG_L;
+            if (seg < j.nseg && x0 < W && (x0 > cv.start_x || cv.start_x == 0) && (uint32_t)c < bpp) {
+                const SegPix rec = px[tid];
+                const SegStepMem M = seg_step_mem(SEG_LDS_CU32(tw), SEG_LDS_CU32(lut));
+                const int qb = (pl % SEG_PL) == SEG_PL - 1 ? (sl * SEG_PARTS + pl / SEG_PL) * 4 + c : -1;
+                if (f == 2) { if (trx) seg_small_eval<2, true, NT>(cmax, rec, tid, qb, M, G, ct, bk); else seg_small_eval<2, false, NT>(cmax, rec, tid, qb, M, G, ct, bk); }
+                else { if (trx) seg_small_eval<0, true, NT>(cmax, rec, tid, qb, M, G, ct, bk); else seg_small_eval<0, false, NT>(cmax, rec, tid, qb, M, G, ct, bk); }
+            }
+        }
+        PLS_SYNC();
+    }
     PLS_THREADS(tid, NT) {
         const int sl = tid / (4 * SEG_NSS), c = (tid / SEG_NSS) & 3, i = tid % SEG_NSS;
         const uint32_t seg = (uint32_t)seg0 + (uint32_t)sl, x0 = seg * SEG_L;
-        if (seg < j.nseg && x0 < W && (x0 > cv.start_x || cv.start_x == 0) && (uint32_t)c < bpp && i < P.ns_small) {
-            SegState st;
-            uint32_t out = SEG_INVALID;
+        if (seg < j.nseg && x0 < W && (x0 > cv.start_x || cv.start_x == 0) && (uint32_t)c < bpp && i < ns) {
             const size_t slot = (((size_t)f * j.nseg + seg) * 4 + c) * SEG_NSP + i;
-            if (seg_small_decode(P, i, st)) {
-                int bad = 0;
+            bool walked = false;
+            if (tab) {
+                /* walk: ci = cn + cmax indexes the step tables, tb = th + cmax - 128 is what a step adds to the entry's rem + 128 */
+                SEG_AS_LDS const uint16_t *ctl = ct + sl * (SEG_L * 4) + c;
+                SEG_AS_LDS const uint8_t *bkl = bk + sl * SEG_PARTS * 4 + c;
+                const uint32_t w0 = sts[i], top = 2u * (uint32_t)cmax;
+                uint32_t ci = (w0 & 255u) - 128u + (uint32_t)cmax, tb = ((w0 >> 8) & 255u) - 256u + (uint32_t)cmax, over = 0, ck[SEG_PARTS];
+                PLS_UNROLL
                 for (int part = 0; part < SEG_PARTS; part++) {
-                    if (part) j.rck[slot * (SEG_PARTS - 1) + (part - 1)] = bad ? 0xFFFFFFFFu : seg_state_pack(st);
-                    bad |= seg_run_fast_f<SEG_PL>(f, trx, px + (sl * SEG_L + part * SEG_PL) * 4 + c, 4, st, SEG_LDS_CU32(tw), G, SEG_LDS_CU32(lut));
+                    uint32_t from = ci;
+                    PLS_UNROLL
+                    for (int q = 0; q < SEG_PL; q++) {
+                        from = ci;
+                        const uint32_t e = ctl[from * NT + (uint32_t)(part * SEG_PL + q) * 4];
+                        const uint32_t nc = (e & 255u) + tb;                 /* cn' + cmax = rem + th + cmax (wraps far beyond `top` when negative) */
+                        tb = (e >> 8) - 256u + (uint32_t)cmax;
+                        over |= nc > top ? 1u : 0u; ci = seg_umin(nc, top);
+                    }
+                    ck[part] = (uint32_t)bkl[from * (NT / SEG_PL) + (uint32_t)part * 4] | ((ci - (uint32_t)cmax + 32768u) & 0xffffu) << 8 | ((tb - (uint32_t)cmax + 256u) & 255u) << 24;
                 }
-                if (!bad) out = seg_small_encode(P, st);
-            } else {
-                for (int part = 1; part < SEG_PARTS; part++) j.rck[slot * (SEG_PARTS - 1) + (part - 1)] = 0xFFFFFFFFu;
+                if (!over) {
+                    walked = true;
+                    const uint32_t ti = tb - (uint32_t)cmax + 128u + (uint32_t)tmax;      /* th + tmax */
+                    const uint32_t out = ti <= 2u * (uint32_t)tmax && kl[ci * (2u * (uint32_t)tmax + 1u) + ti] != 255u ? (uint32_t)kl[ci * (2u * (uint32_t)tmax + 1u) + ti] : (uint32_t)SEG_INVALID;
+                    PLS_UNROLL
+                    for (int part = 1; part < SEG_PARTS; part++) j.rck[slot * (SEG_PARTS - 1) + (part - 1)] = ck[part - 1];
+                    j.rout[slot] = (uint16_t)out;
+                    j.rst[slot] = out == SEG_INVALID ? 0xFFFFFFFFu : ck[SEG_PARTS - 1];
+                }
             }
+            if (!walked) { const uint32_t out = seg_small_lane_loop(j, P, f, trx, px + (sl * SEG_L) * 4 + c, i, slot, tw, lut, G); (void)out; SEG_DEBUG_SMALL(tab, false, out); }
+            else SEG_DEBUG_SMALL(tab, true, 0u);
             /* no dedupe for the handful of (cn, th) states: the dense id of an entry index is the index itself */
             j.maps[(((size_t)f * j.nseg + seg) * 4 + c) * (size_t)P.nsp + i] = (uint16_t)i;
-            j.rout[(((size_t)f * j.nseg + seg) * 4 + c) * SEG_NSP + i] = (uint16_t)out;
-            j.rst[(((size_t)f * j.nseg + seg) * 4 + c) * SEG_NSP + i] = out == SEG_INVALID ? 0xFFFFFFFFu : seg_state_pack(st);
-            if (i == 0) j.dcnt[((size_t)f * j.nseg + seg) * 4 + c] = (uint32_t)P.ns_small;
+            if (i == 0) j.dcnt[((size_t)f * j.nseg + seg) * 4 + c] = (uint32_t)ns;
         }
     }
 }

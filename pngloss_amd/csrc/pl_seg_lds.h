@@ -188,13 +188,30 @@ SEG_LDS_LAYOUT(SegLdsEnum, SEG_LDS_ENUM, SEG_LDS_ALIGN_NONE, (template <int NT>)
     R(keys, uint32_t, , NT)                           /* [NT] */
 SEG_LDS_LAYOUT(SegLdsSeeded, SEG_LDS_SEEDED, SEG_LDS_ALIGN_NONE, (template <int NT>), (<NT>))
 
-/* seg_enum_small_body<NT>: NT / (4 * SEG_NSS) segments a workgroup */
+/* seg_enum_small_body<NT>: NT / (4 * SEG_NSS) segments a workgroup.  Behind what the step loop needs: the state set, its index table, and the STEP TABLES of the
+ * workgroup's pixel records -- as many bytes as lie between them and the end of seg_enum_body's layout, so that the launch's bytes (seg_lds_enum_bytes_v) stay what they are.
+ * A value of cn costs 2 * NT bytes (what a step from it leaves at every pixel record) and NT / SEG_PL more (the byte it leaves behind a part's last pixel):
+ * SEG_SMALL_NCN values of cn fit (seg_small_tables_fit). */
+#define SEG_SMALL_KL 256          /* most entries of SegParams::keylut_small the table path takes */
+#define SEG_SMALL_ROOM(NT) (SegLdsEnum<NT>::Table::end() - (uint32_t)(SEG_TBL_WORDS * 4 + 512 * 4 + (NT) / (4 * SEG_NSS) * SEG_L * 4 * sizeof(SegPix) + 4 + SEG_NSS * 4 + SEG_SMALL_KL))
+#define SEG_SMALL_NCN(NT) (SEG_SMALL_ROOM(NT) / (2u * (NT) + (NT) / SEG_PL))
 #define SEG_LDS_SMALL(R, O, B, V) \
     R(tw, uint32_t, , SEG_TBL_WORDS) \
     R(lut, uint32_t, , 512) \
     R(px, SegPix, , NT / (4 * SEG_NSS) * SEG_L * 4)   /* [NSEGS][SEG_L][4] */ \
-    R(trflag, uint32_t, , 1)                          /* some pixel is fully transparent */
+    R(trflag, uint32_t, , 1)                          /* some pixel is fully transparent */ \
+    R(sts, uint32_t, SEG_AS_LDS, SEG_NSS)             /* (table path) SegParams::st_small */ \
+    R(ct, uint16_t, SEG_AS_LDS, SEG_SMALL_NCN(NT) * NT)   /* (table path) [2 cmax + 1][NT]: the step of pixel record q from cn (and th = 0): rem + 128 | (thr + 128) << 8, or SEG_SMALL_NONE */ \
+    R(kl, uint8_t, SEG_AS_LDS, SEG_SMALL_KL)          /* (table path) SegParams::keylut_small, a byte an entry (255: none) */ \
+    R(bk, uint8_t, SEG_AS_LDS, SEG_SMALL_ROOM(NT) - 2u * SEG_SMALL_NCN(NT) * NT)   /* (table path) [2 cmax + 1][NT / SEG_PL]: the byte that step leaves, for a part's last pixel */
 SEG_LDS_LAYOUT(SegLdsSmall, SEG_LDS_SMALL, SEG_LDS_ALIGN_NONE, (template <int NT>), (<NT>))
+static_assert(SegLdsSmall<512>::Table::end() == SegLdsEnum<512>::Table::end() && SegLdsSmall<1024>::Table::end() == SegLdsEnum<1024>::Table::end(), "the tables of none / up fill what seg_enum_body's layout leaves them, no more");
+static_assert(SEG_SMALL_ROOM(512) - 2u * SEG_SMALL_NCN(512) * 512 >= SEG_SMALL_NCN(512) * (512 / SEG_PL) && SEG_SMALL_ROOM(1024) - 2u * SEG_SMALL_NCN(1024) * 1024 >= SEG_SMALL_NCN(1024) * (1024 / SEG_PL), "bk holds a byte per value of cn and part");
+/* the table path of seg_enum_small_body: the step tables of a set with |cn| <= cmax, |th| <= tmax fit (and the sentinel of a void step cannot be taken for a value) */
+template <int NT> constexpr bool seg_small_tables_fit(int ns, int cmax, int tmax)
+{
+    return ns > 0 && ns <= SEG_NSS && cmax >= 0 && tmax >= 0 && cmax <= 30 && tmax <= 30 && (uint32_t)(2 * cmax + 1) <= SEG_SMALL_NCN(NT) && (2 * cmax + 1) * (2 * tmax + 1) <= SEG_SMALL_KL;
+}
 
 /* seg_enum_unit_body<LANES, UNIT, NC, SEEDS>: tables, split table, the pool, the first records of every pair, bookkeeping -- and ONE place (work) that holds the
  * first phase's scratch (hash tables, per-turn lists, keys: 10 KB; from seeds: the run-in's records and a turn's staged entry maps behind it) and then, for the
