@@ -15,6 +15,7 @@ from .lib import (  # noqa: F401
     Ssim,
     Palette,
     QuantParams,
+    QuantParams2,
     QuantReport,
     Target,
     Target2,
@@ -37,6 +38,6 @@ from .lib import (  # noqa: F401
 from .synth import SURVEY_FNV_BASIS, fnv1a64, synth_rgba  # noqa: F401
 
 __all__ = [
-    "PNG_FILTER_FLAGS", "HipContext", "HipMulti", "Distortion", "Ssim", "Palette", "QuantParams", "QuantReport", "ssim_mean", "Target", "Target2", "TargetReport", "SizeTarget", "SizeReport", "PSNR_MASK_OF_BPP", "psnr_db", "multi_split", "source_digest", "build", "hip_lib", "synth_lib", "optimize_with_rows", "optimize_with_stride",
+    "PNG_FILTER_FLAGS", "HipContext", "HipMulti", "Distortion", "Ssim", "Palette", "QuantParams", "QuantParams2", "QuantReport", "ssim_mean", "Target", "Target2", "TargetReport", "SizeTarget", "SizeReport", "PSNR_MASK_OF_BPP", "psnr_db", "multi_split", "source_digest", "build", "hip_lib", "synth_lib", "optimize_with_rows", "optimize_with_stride",
     "optimize_for_average_filter", "optimize_image", "synth_rgba", "fnv1a64", "SURVEY_FNV_BASIS",
 ]

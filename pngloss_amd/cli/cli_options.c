@@ -54,7 +54,7 @@ const char cli_usage_text[] =
     "Output names end in \"-loss.png\" or your --ext; with \"-\" the image goes stdin -> stdout.\n"
     "Existing outputs are skipped unless --force is given.\n";
 
-enum { OPT_EXT = 256, OPT_NO_FORCE, OPT_SKIP_LARGER, OPT_STRIP, OPT_GPU_DEFLATE, OPT_GPU_READ, OPT_DISTORTION, OPT_TARGET_PSNR, OPT_MAX_ERROR, OPT_SSIM, OPT_TARGET_SSIM, OPT_TARGET_SIZE, OPT_VISIBLE, OPT_INDEXED, OPT_COLORS };
+enum { OPT_EXT = 256, OPT_NO_FORCE, OPT_SKIP_LARGER, OPT_STRIP, OPT_GPU_DEFLATE, OPT_GPU_READ, OPT_DISTORTION, OPT_TARGET_PSNR, OPT_MAX_ERROR, OPT_SSIM, OPT_TARGET_SSIM, OPT_TARGET_SIZE, OPT_VISIBLE, OPT_INDEXED, OPT_COLORS, OPT_DITHER };
 
 static bool parse_number(const char *text, unsigned long *out)
 {
@@ -117,6 +117,7 @@ pngloss_error cli_options_parse(int argc, char **argv, struct cli_options *o, FI
         { "visible", no_argument, NULL, OPT_VISIBLE },
         { "indexed", no_argument, NULL, OPT_INDEXED },
         { "colors", required_argument, NULL, OPT_COLORS },
+        { "dither", no_argument, NULL, OPT_DITHER },
         { NULL, 0, NULL, 0 },
     };
     memset(o, 0, sizeof *o);
@@ -158,6 +159,7 @@ pngloss_error cli_options_parse(int argc, char **argv, struct cli_options *o, FI
             if (!parse_number(optarg, &o->colors)) return refuse(err, "--colors requires a numeric argument\n");
             o->have_colors = true;
             break;
+        case OPT_DITHER: o->dither = true; break;
         case 'h': o->help = true; break;
         case 'V': o->version = true; break;
         case 'o':
@@ -210,6 +212,7 @@ pngloss_error cli_options_check(const struct cli_options *o, FILE *err)
     if (o->visible && !(o->distortion || o->ssim || quality)) return refuse(err, "--visible needs one of --distortion, --ssim, --target-psnr, --max-error or --target-ssim.\n");
     if (o->visible && size) return refuse(err, "--visible cannot be combined with --target-size.\n");
     if (size && o->size_value < 1) return refuse(err, "Must specify a size target of at least 1 byte or 1 percent.\n");
+    if (o->dither && !o->have_colors) return refuse(err, "--dither requires --colors.\n");
     if (o->have_colors && (o->colors < 2 || o->colors > 256)) return refuse(err, "Must specify a number of colours in the range 2-256.\n");
     if (o->have_colors && o->strength != 0) return refuse(err, "--colors cannot be combined with a strength above 0: the palette is the lossy step.\n");
     if (o->have_colors && (o->search != CLI_SEARCH_NONE || o->ssim || o->visible))

@@ -36,6 +36,7 @@ struct cli_options {
     bool indexed;              /* --indexed: a result of at most 256 colours is written as a palette file where that file is smaller (the library's option "indexed") */
     bool have_colors;          /* --colors N: every image is quantised to at most N colours first (pngloss_hip_multi_quantize_batch_host), then written at */
     unsigned long colors;      /* strength 0 with --indexed: the palette is the lossy step.  Not in the usage text (DESIGN.md 9.1b says why) */
+    bool dither;               /* --dither: --colors remaps with Floyd-Steinberg error diffusion (pngloss_hip_multi_quantize_batch_host2).  Not in the usage text either */
     bool have_strength;        /* -s was given */
     enum cli_search search;
     double target_psnr;        /* 0: no PSNR condition */

@@ -10,6 +10,7 @@
 #include "../../include/pngloss_hip.h"
 #include "../../include/pngloss_hip_indexed.h"
 #include "../../include/pngloss_hip_quant.h"
+#include "../../include/pngloss_hip_dither.h"
 #include "cli_options.h"
 
 #ifdef __cplusplus
@@ -31,6 +32,8 @@ void cli_report_strength(char *line, size_t cap, unsigned strength, unsigned pro
 void cli_report_indexed(char *line, size_t cap, const pngloss_hip_palette *p);
 /* -v with --colors: the input's colours, the palette entries of what is written, and whether the image was left as it was */
 void cli_report_quant(char *line, size_t cap, const pngloss_hip_quant_report *q);
+/* ... with --dither, the line behind it: empty for a file that was exact, which is never dithered */
+void cli_report_dither(char *line, size_t cap, const pngloss_hip_quant_report *q);
 void cli_report_budget_missed(char *line, size_t cap, const char *name, size_t budget, size_t written, unsigned strength);
 
 #ifdef __cplusplus

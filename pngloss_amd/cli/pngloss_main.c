@@ -31,6 +31,7 @@
 #include "../../include/pngloss_hip.h"
 #include "../../include/pngloss_hip_indexed.h"
 #include "../../include/pngloss_hip_quant.h"
+#include "../../include/pngloss_hip_dither.h"
 #include "cli_options.h"
 #include "cli_outcome.h"
 #include "cli_report.h"
@@ -288,6 +289,10 @@ static void encode_job(struct job *j, const struct cli_options *o)
     if (o->verbose && j->have_quant) {
         cli_report_quant(line, sizeof line, &j->quant);
         say(j, "%s", line);
+        if (o->dither) {
+            cli_report_dither(line, sizeof line, &j->quant);
+            say(j, "%s", line);
+        }
     }
     if (o->verbose && j->color_type == 3) {
         cli_report_indexed(line, sizeof line, &j->palette);
@@ -555,8 +560,11 @@ static void compute_budgets(struct window_batch *b, struct job *jobs, const stru
 static void quantise_batch(pngloss_hip_multi *ctx, struct window_batch *b, struct job *jobs, const struct cli_options *o)
 {
     const pngloss_hip_quant_params params = { (uint32_t)o->colors, PNGLOSS_HIP_QUANT_DEFAULT_ROUNDS };
+    const pngloss_hip_quant_params2 dithered = { params.max_colors, params.rounds, PNGLOSS_HIP_DITHER_FLOYD_STEINBERG, 0 };
     pngloss_hip_quant_report *reports = calloc(b->m ? b->m : 1, sizeof *reports);
-    int rc = !ctx ? PNGLOSS_HIP_ERROR : !reports ? PNGLOSS_OUT_OF_MEMORY_ERROR : pngloss_hip_multi_quantize_batch_host(ctx, b->imgs, b->m, &params, reports);
+    int rc = !ctx ? PNGLOSS_HIP_ERROR : !reports ? PNGLOSS_OUT_OF_MEMORY_ERROR
+           : o->dither ? pngloss_hip_multi_quantize_batch_host2(ctx, b->imgs, b->m, &dithered, reports)
+                       : pngloss_hip_multi_quantize_batch_host(ctx, b->imgs, b->m, &params, reports);
     for (size_t k = 0; k < b->m; k++) {
         struct job *j = &jobs[b->who[k]];
         if (rc == PNGLOSS_SUCCESS) { j->quant = reports[k]; j->have_quant = true; continue; }

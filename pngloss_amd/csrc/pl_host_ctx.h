@@ -11,7 +11,7 @@
  *   pl_host_search.hip   the two strength searches (target_search, size_search), their host form and their entry points
  *   pl_host_measure.hip  the job tables of the two measuring kernels, the stand-alone comparisons
  *   pl_host_read.hip     the PNG read side
- *   pl_host_quant.hip    the colour quantiser: its workspace, the median cut between its two synchronisations, its host form
+ *   pl_host_quant.hip    the colour quantiser: its workspace, the median cut between its two synchronisations, its host form -- with and without the dither pass (pl_dither.hip)
  * What the host side DECIDES is in plain headers that the CPU suite pins (pl_plan.h, pl_seg_pace.h, pl_layout.h, pl_deal.h, pl_search.h, pl_result.h);
  * these files carry it out.
  *
@@ -32,6 +32,7 @@
 #include "../../include/pngloss_hip.h"
 #include "../../include/pngloss_hip_indexed.h"
 #include "../../include/pngloss_hip_quant.h"
+#include "../../include/pngloss_hip_dither.h"
 #include "pl_device.h"
 #include "pl_deflate.h"
 #include "pl_pngread.h"
@@ -40,6 +41,7 @@
 #include "pl_ssim.h"
 #include "pl_index.h"
 #include "pl_quant.h"
+#include "pl_dither.h"
 #include "pl_target.h"
 #include "pl_size.h"
 #include "pl_target_dev.h"

@@ -1,17 +1,26 @@
 /*
- * pl_host_quant.hip -- the host side of the colour quantiser (include/pngloss_hip_quant.h; pl_host_ctx.h has the map of the host files): the argument
- * checks, the workspace (pl_layout.h: pl_quant_layout), the median cut between the two synchronisations (pl_quant_core.h), the launches of pl_quant.hip
- * and of the kernels it borrows -- pl_index_count / pl_index_palette for the colours before and after, pl_distort for the record --, and the host
+ * pl_host_quant.hip -- the host side of the colour quantiser (include/pngloss_hip_quant.h, pngloss_hip_dither.h; pl_host_ctx.h has the map of the
+ * host files): the argument checks, the workspace (pl_layout.h: pl_quant_layout, pl_dither_layout), the median cut between the two synchronisations
+ * (pl_quant_core.h), the launches of pl_quant.hip, of pl_dither.hip in place of the remap pass when the call dithers, and of the kernels it borrows -- pl_index_count / pl_index_palette for the colours before and after, pl_distort for the record --, and the host
  * form over the contexts of a node (deal_over_contexts).
  */
 #include "pl_host_ctx.h"
 
 namespace {
 
-int check_quant_params(const pngloss_hip_quant_params *params)
+int check_quant_params(const pngloss_hip_quant_params2 *params)
 {
     if (!params || params->max_colors < PLQ_MIN_COLORS || params->max_colors > PLQ_MAX_COLORS || params->rounds > PLQ_MAX_ROUNDS) return PNGLOSS_INVALID_ARGUMENT;
+    if (params->dither > PNGLOSS_HIP_DITHER_FLOYD_STEINBERG || params->reserved) return PNGLOSS_INVALID_ARGUMENT;
     return PNGLOSS_SUCCESS;
+}
+
+/* the old record as the new one: no dithering */
+const pngloss_hip_quant_params2 *widen(const pngloss_hip_quant_params *params, pngloss_hip_quant_params2 &wide)
+{
+    if (!params) return nullptr;
+    wide = pngloss_hip_quant_params2{ params->max_colors, params->rounds, PNGLOSS_HIP_DITHER_NONE, 0 };
+    return &wide;
 }
 
 template <class Image> int check_quant_sizes(const Image *images, size_t n, const void *const *pixels_of)
@@ -29,11 +38,28 @@ PlQuantLayout quant_layout_of(const std::vector<uint32_t> &width, const std::vec
     return pl_quant_layout(width, height, inputs, sizeof(PlIndexJob), sizeof(PlQuantJob), sizeof(PlDistortJob), sizeof(PliRecord), sizeof(PlDistortRecord));
 }
 
-/* The images img[0 .. n) (device, width[i] * height[i] words each) quantised in place, in the workspace ctx->d_quant, which the caller has grown to
- * lay.total.  Waits for `stream` twice: behind the colour counts and the histograms, and at the end. */
-int quantize_on(pngloss_hip_ctx *ctx, const PlQuantLayout &lay, const std::vector<uint32_t *> &img, const std::vector<uint32_t> &width,
-                const std::vector<uint32_t> &height, const pngloss_hip_quant_params &params, pngloss_hip_quant_report *reports, hipStream_t stream)
+/* the whole workspace of a call: the quantiser's, and behind it -- when the call dithers -- the dither pass's job table and error lines */
+struct QuantWorkspace {
+    PlQuantLayout lay;
+    PlDitherLayout dither;
+    bool dithers = false;
+    size_t total() const { return dithers ? dither.total : lay.total; }
+};
+QuantWorkspace quant_workspace_of(const std::vector<uint32_t> &width, const std::vector<uint32_t> &height, bool inputs, const pngloss_hip_quant_params2 &params)
 {
+    QuantWorkspace ws;
+    ws.lay = quant_layout_of(width, height, inputs);
+    ws.dithers = params.dither == PNGLOSS_HIP_DITHER_FLOYD_STEINBERG;
+    if (ws.dithers) ws.dither = pl_dither_layout(width, ws.lay.total, sizeof(PlDitherJob));
+    return ws;
+}
+
+/* The images img[0 .. n) (device, width[i] * height[i] words each) quantised in place, in the workspace ctx->d_quant, which the caller has grown to
+ * ws.total().  Waits for `stream` twice: behind the colour counts and the histograms, and at the end. */
+int quantize_on(pngloss_hip_ctx *ctx, const QuantWorkspace &ws, const std::vector<uint32_t *> &img, const std::vector<uint32_t> &width,
+                const std::vector<uint32_t> &height, const pngloss_hip_quant_params2 &params, pngloss_hip_quant_report *reports, hipStream_t stream)
+{
+    const PlQuantLayout &lay = ws.lay;
     const size_t n = img.size();
     char *const base = ctx->d_quant.p;
     uint32_t *const d_counts = reinterpret_cast<uint32_t *>(base + lay.counts);
@@ -76,6 +102,7 @@ int quantize_on(pngloss_hip_ctx *ctx, const PlQuantLayout &lay, const std::vecto
 
     /* exact images leave here; the others get their initial palette */
     std::vector<PlQuantJob> work;
+    std::vector<PlDitherJob> dither;
     std::vector<PlDistortJob> djobs(live.size());
     std::vector<uint32_t> pals(n * (size_t)PLQ_MAX_COLORS, 0);
     uint64_t work_pixels = 0;
@@ -93,6 +120,8 @@ int quantize_on(pngloss_hip_ctx *ctx, const PlQuantLayout &lay, const std::vecto
         std::copy(first.begin(), first.end(), pals.begin() + (long)(i * (size_t)PLQ_MAX_COLORS));
         qjobs[k].entries = (uint32_t)first.size();
         work.push_back(qjobs[k]);
+        if (ws.dithers)
+            dither.push_back(PlDitherJob{ img[i], qjobs[k].out, qjobs[k].pal, reinterpret_cast<PlfErr *>(base + ws.dither.line[i]), width[i], height[i], qjobs[k].entries, 0 });
         work_pixels = std::max(work_pixels, qjobs[k].pixels);
     }
     if (!work.empty()) {
@@ -102,7 +131,12 @@ int quantize_on(pngloss_hip_ctx *ctx, const PlQuantLayout &lay, const std::vecto
             PL_CHECK(pl_launch_quant_assign(d_qjobs, work.size(), work_pixels, stream));
             PL_CHECK(pl_launch_quant_update(d_qjobs, work.size(), stream));
         }
-        PL_CHECK(pl_launch_quant_remap(d_qjobs, work.size(), work_pixels, stream));
+        if (ws.dithers) {
+            PL_CHECK(hipMemcpyAsync(base + ws.dither.jobs, dither.data(), sizeof(PlDitherJob) * dither.size(), hipMemcpyHostToDevice, stream));
+            PL_CHECK(pl_launch_dither(reinterpret_cast<const PlDitherJob *>(base + ws.dither.jobs), dither.size(), stream));
+        } else {
+            PL_CHECK(pl_launch_quant_remap(d_qjobs, work.size(), work_pixels, stream));
+        }
     }
     /* the record of (input, output) while both exist, then the output over the input */
     PL_CHECK(hipMemcpyAsync(base + lay.distort_jobs, djobs.data(), sizeof(PlDistortJob) * djobs.size(), hipMemcpyHostToDevice, stream));
@@ -134,14 +168,15 @@ int quantize_on(pngloss_hip_ctx *ctx, const PlQuantLayout &lay, const std::vecto
 }
 
 /* the share of one context in the host form: its images up into the workspace, quantised there, the changed ones back */
-int quantize_host_share(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images, size_t n, const pngloss_hip_quant_params &params, pngloss_hip_quant_report *reports)
+int quantize_host_share(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images, size_t n, const pngloss_hip_quant_params2 &params, pngloss_hip_quant_report *reports)
 {
     if (batch_in_flight_refused(ctx)) return PNGLOSS_INVALID_ARGUMENT;
     PL_CHECK(hipSetDevice(ctx->device));
     std::vector<uint32_t> width, height;
     batch_dims(images, n, width, height);
-    const PlQuantLayout lay = quant_layout_of(width, height, true);
-    int rc = ctx->d_quant.grow(lay.total, 8);
+    const QuantWorkspace ws = quant_workspace_of(width, height, true, params);
+    const PlQuantLayout &lay = ws.lay;
+    int rc = ctx->d_quant.grow(ws.total(), 8);
     if (rc == PNGLOSS_SUCCESS) rc = ensure_copy_stream(ctx);
     if (rc) return rc;
     hipStream_t stream = ctx->copy_stream;
@@ -151,7 +186,7 @@ int quantize_host_share(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *imag
         img[i] = reinterpret_cast<uint32_t *>(ctx->d_quant.p + lay.im[i].in);
         if (bytes) PL_CHECK(hipMemcpyAsync(img[i], images[i].rgba, bytes, hipMemcpyHostToDevice, stream));
     }
-    rc = quantize_on(ctx, lay, img, width, height, params, reports, stream);
+    rc = quantize_on(ctx, ws, img, width, height, params, reports, stream);
     if (rc) return rc;
     for (size_t i = 0; i < n; i++) {
         const size_t bytes = (size_t)width[i] * height[i] * 4;
@@ -161,12 +196,9 @@ int quantize_host_share(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *imag
     return PNGLOSS_SUCCESS;
 }
 
-} // namespace
-
-extern "C" {
-
-int pngloss_hip_quantize_batch(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n, const pngloss_hip_quant_params *params,
-                               pngloss_hip_quant_report *reports, void *stream_)
+/* both forms of pngloss_hip_quantize_batch */
+int quantize_batch(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n, const pngloss_hip_quant_params2 *params,
+                   pngloss_hip_quant_report *reports, void *stream_)
 {
     if (!ctx || (n && (!images || !reports)) || check_quant_params(params)) return PNGLOSS_INVALID_ARGUMENT;
     std::vector<const void *> pixels_of(n);
@@ -177,16 +209,17 @@ int pngloss_hip_quantize_batch(pngloss_hip_ctx *ctx, const pngloss_hip_image_des
     PL_CHECK(hipSetDevice(ctx->device));
     std::vector<uint32_t> width, height;
     batch_dims(images, n, width, height);
-    const PlQuantLayout lay = quant_layout_of(width, height, false);
-    const int rc = ctx->d_quant.grow(lay.total, 8);
+    const QuantWorkspace ws = quant_workspace_of(width, height, false, *params);
+    const int rc = ctx->d_quant.grow(ws.total(), 8);
     if (rc) return rc;
     std::vector<uint32_t *> img(n);
     for (size_t i = 0; i < n; i++) img[i] = static_cast<uint32_t *>(images[i].d_rgba);
-    return quantize_on(ctx, lay, img, width, height, *params, reports, static_cast<hipStream_t>(stream_));
+    return quantize_on(ctx, ws, img, width, height, *params, reports, static_cast<hipStream_t>(stream_));
 }
 
-int pngloss_hip_multi_quantize_batch_host(pngloss_hip_multi *m, const pngloss_hip_host_image *images, size_t n, const pngloss_hip_quant_params *params,
-                                          pngloss_hip_quant_report *reports)
+/* both forms of pngloss_hip_multi_quantize_batch_host */
+int multi_quantize_batch_host(pngloss_hip_multi *m, const pngloss_hip_host_image *images, size_t n, const pngloss_hip_quant_params2 *params,
+                              pngloss_hip_quant_report *reports)
 {
     if (!m || m->ctx.empty() || (n && (!images || !reports)) || check_quant_params(params)) return PNGLOSS_INVALID_ARGUMENT;
     std::vector<const void *> pixels_of(n);
@@ -200,6 +233,36 @@ int pngloss_hip_multi_quantize_batch_host(pngloss_hip_multi *m, const pngloss_hi
         for (size_t k = 0; k < mine.n(); k++) reports[mine.who[k]] = own[k];
         return rc;
     });
+}
+
+} // namespace
+
+extern "C" {
+
+int pngloss_hip_quantize_batch(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n, const pngloss_hip_quant_params *params,
+                               pngloss_hip_quant_report *reports, void *stream)
+{
+    pngloss_hip_quant_params2 wide;
+    return quantize_batch(ctx, images, n, widen(params, wide), reports, stream);
+}
+
+int pngloss_hip_multi_quantize_batch_host(pngloss_hip_multi *m, const pngloss_hip_host_image *images, size_t n, const pngloss_hip_quant_params *params,
+                                          pngloss_hip_quant_report *reports)
+{
+    pngloss_hip_quant_params2 wide;
+    return multi_quantize_batch_host(m, images, n, widen(params, wide), reports);
+}
+
+int pngloss_hip_quantize_batch2(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n, const pngloss_hip_quant_params2 *params,
+                                pngloss_hip_quant_report *reports, void *stream)
+{
+    return quantize_batch(ctx, images, n, params, reports, stream);
+}
+
+int pngloss_hip_multi_quantize_batch_host2(pngloss_hip_multi *m, const pngloss_hip_host_image *images, size_t n, const pngloss_hip_quant_params2 *params,
+                                           pngloss_hip_quant_report *reports)
+{
+    return multi_quantize_batch_host(m, images, n, params, reports);
 }
 
 } /* extern "C" */

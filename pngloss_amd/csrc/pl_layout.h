@@ -1,6 +1,6 @@
 /*
  * pl_layout.h -- every carve-up of a buffer the host shim makes, as pure functions from sizes to offsets: the batch workspace of enqueue(), the
- * arena of a host window (batch_host_one), the keep arena of the distortion measurement, the tables of the SSIM measurement, the index workspace of the option "indexed", the quantiser's workspace, the read side's workspace and frame arena
+ * arena of a host window (batch_host_one), the keep arena of the distortion measurement, the tables of the SSIM measurement, the index workspace of the option "indexed", the quantiser's workspace and the job table and error lines of its dither pass, the read side's workspace and frame arena
  * (png_decode_body), and the size a buffer is regrown to.
  * Internal.
  *
@@ -16,6 +16,7 @@
 #include "pl_pngread_core.h"
 #include "pl_index_core.h"
 #include "pl_quant_core.h"
+#include "pl_dither_core.h"
 
 #include <cstdint>
 #include <cstring>
@@ -300,6 +301,31 @@ inline PlQuantLayout pl_quant_layout(const std::vector<uint32_t> &width, const s
         m.out = take(bytes);
         m.in = take(inputs ? bytes : 0);
     }
+    return l;
+}
+
+/* ================================================================================================ the dither pass of the quantiser (pngloss_hip_quantize_batch2) */
+
+/* Behind the quantiser's workspace, from `base` (pl_quant_layout's total) on: the PlDitherJob table, then per image its error line -- one PlfErr per
+ * column, what the last row of a band of pl_dither leaves for the band below.  `lines_bytes` from `lines` holds them all.  Every image gets its
+ * line, working image or not, for the reason every image gets its `out`. */
+struct PlDitherLayout {
+    size_t jobs = 0, lines = 0, lines_bytes = 0, total = 0;
+    std::vector<size_t> line;
+};
+
+/* job_bytes: sizeof(PlDitherJob) */
+inline PlDitherLayout pl_dither_layout(const std::vector<uint32_t> &width, size_t base, size_t job_bytes)
+{
+    PlDitherLayout l;
+    const size_t n = width.size(), n1 = n ? n : 1;
+    l.total = pl_align_up(base, PLL_ALIGN);
+    auto take = [&](size_t bytes) { size_t at = l.total; l.total = pl_align_up(l.total + bytes, PLL_ALIGN); return at; };
+    l.jobs = take(job_bytes * n1);
+    l.lines = l.total;
+    l.line.resize(n);
+    for (size_t i = 0; i < n; i++) l.line[i] = take(PLF_ERR_BYTES * width[i]);
+    l.lines_bytes = l.total - l.lines;
     return l;
 }
 

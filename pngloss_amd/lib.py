@@ -125,6 +125,15 @@ class QuantParams(C.Structure):
         super().__init__(max_colors, rounds)
 
 
+class QuantParams2(C.Structure):
+    """pngloss_hip_quant_params2: QuantParams with dither (DITHER_NONE = 0, DITHER_FLOYD_STEINBERG = 1) and reserved (0).
+    include/pngloss_hip_dither.h states the rule."""
+    _fields_ = [("max_colors", C.c_uint32), ("rounds", C.c_uint32), ("dither", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def __init__(self, max_colors=256, rounds=8, dither=0, reserved=0):
+        super().__init__(max_colors, rounds, dither, reserved)
+
+
 class QuantReport(C.Structure):
     """pngloss_hip_quant_report: what the quantiser did to one image.  colors_in: 257 = more than 256; palette[:entries]: the colours of the image as
     it is now, ascending by word; exact: it had at most max_colors colours and was not changed; distortion: now against the input, all pixels."""
@@ -211,6 +220,14 @@ QUANT_STRUCTS = {"pngloss_hip_quant_params": QuantParams, "pngloss_hip_quant_rep
 QUANT_PROTOTYPES = {
     "pngloss_hip_quantize_batch": (C.c_int, [C.c_void_p, C.POINTER(ImageDesc), C.c_size_t, C.POINTER(QuantParams), C.POINTER(QuantReport), C.c_void_p]),
     "pngloss_hip_multi_quantize_batch_host": (C.c_int, [C.c_void_p, C.POINTER(HostImage), C.c_size_t, C.POINTER(QuantParams), C.POINTER(QuantReport)]),
+}
+
+#: ... and for include/pngloss_hip_dither.h, the dithering extension of the quantiser (tests/test_dither_host.py holds them against that header)
+DITHER_NONE, DITHER_FLOYD_STEINBERG = 0, 1
+DITHER_STRUCTS = {"pngloss_hip_quant_params2": QuantParams2}
+DITHER_PROTOTYPES = {
+    "pngloss_hip_quantize_batch2": (C.c_int, [C.c_void_p, C.POINTER(ImageDesc), C.c_size_t, C.POINTER(QuantParams2), C.POINTER(QuantReport), C.c_void_p]),
+    "pngloss_hip_multi_quantize_batch_host2": (C.c_int, [C.c_void_p, C.POINTER(HostImage), C.c_size_t, C.POINTER(QuantParams2), C.POINTER(QuantReport)]),
 }
 
 
@@ -377,7 +394,7 @@ def hip_lib():
                 except ImportError:
                     pass
             lib = _load(os.environ.get("PNGLOSS_HIP_LIBNAME", "libpngloss_hip.so"))
-            for name, (ret, args) in {**PROTOTYPES, **INDEXED_PROTOTYPES, **QUANT_PROTOTYPES}.items():
+            for name, (ret, args) in {**PROTOTYPES, **INDEXED_PROTOTYPES, **QUANT_PROTOTYPES, **DITHER_PROTOTYPES}.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = ret, args
             _hip = lib
@@ -751,14 +768,19 @@ class HipContext:
         _check(self._lib.pngloss_hip_last_palette(self._ctx, index, C.byref(r)), "last_palette")
         return r
 
-    def quantize(self, images, max_colors=256, rounds=8, stream=0):
+    def quantize(self, images, max_colors=256, rounds=8, stream=0, dither=None):
         """pngloss_hip_quantize_batch: images as for run() (device-resident RGBA8), quantised in place to at most max_colors colours each.
         Synchronous.  Returns (images, reports): the tuples handed in, whose pixels are the quantised ones now, and one report dict per image
-        (QuantReport.as_dict)."""
+        (QuantReport.as_dict).  dither: None calls that entry point; DITHER_NONE or DITHER_FLOYD_STEINBERG calls pngloss_hip_quantize_batch2
+        (include/pngloss_hip_dither.h)."""
         n = len(images)
         rep = _array(QuantReport, n)
-        params = QuantParams(max_colors, rounds)
-        _check(self._lib.pngloss_hip_quantize_batch(self._ctx, _image_descs(images), n, C.byref(params), rep, stream or None), "quantize_batch")
+        if dither is None:
+            params = QuantParams(max_colors, rounds)
+            _check(self._lib.pngloss_hip_quantize_batch(self._ctx, _image_descs(images), n, C.byref(params), rep, stream or None), "quantize_batch")
+        else:
+            params = QuantParams2(max_colors, rounds, dither)
+            _check(self._lib.pngloss_hip_quantize_batch2(self._ctx, _image_descs(images), n, C.byref(params), rep, stream or None), "quantize_batch2")
         return list(images), [r.as_dict() for r in rep[:n]]
 
     def compare(self, pairs, stream=0):
@@ -864,14 +886,19 @@ class HipMulti:
         _check(self._lib.pngloss_hip_multi_last_palette(self._m, index, C.byref(r)), "multi_last_palette")
         return r
 
-    def quantize_host(self, arrays, max_colors=256, rounds=8):
+    def quantize_host(self, arrays, max_colors=256, rounds=8, dither=None):
         """pngloss_hip_multi_quantize_batch_host on a list of (H, W, 4) uint8 arrays.  Returns (outs, reports): the quantised copies and one report
-        dict per image (QuantReport.as_dict)."""
+        dict per image (QuantReport.as_dict).  dither: None calls that entry point; DITHER_NONE or DITHER_FLOYD_STEINBERG calls
+        pngloss_hip_multi_quantize_batch_host2 (include/pngloss_hip_dither.h)."""
         outs, _, imgs = _host_images(arrays, want_filters=False)
         n = len(outs)
         rep = _array(QuantReport, n)
-        params = QuantParams(max_colors, rounds)
-        _check(self._lib.pngloss_hip_multi_quantize_batch_host(self._m, imgs, n, C.byref(params), rep), "multi_quantize_batch_host")
+        if dither is None:
+            params = QuantParams(max_colors, rounds)
+            _check(self._lib.pngloss_hip_multi_quantize_batch_host(self._m, imgs, n, C.byref(params), rep), "multi_quantize_batch_host")
+        else:
+            params = QuantParams2(max_colors, rounds, dither)
+            _check(self._lib.pngloss_hip_multi_quantize_batch_host2(self._m, imgs, n, C.byref(params), rep), "multi_quantize_batch_host2")
         return outs, [r.as_dict() for r in rep[:n]]
 
     def run_host(self, arrays, strength=19, bleed=2, want_filters=True):
