@@ -12,7 +12,7 @@
 
 namespace {
 
-constexpr int kThreads = 256, kWaves = kThreads / 64;
+constexpr int kThreads = PLD_THREADS, kWaves = kThreads / 64;
 
 __global__ __launch_bounds__(kThreads) void pl_keep(const PlDistortJob *__restrict__ jobs)
 {
@@ -78,16 +78,11 @@ __global__ __launch_bounds__(kThreads) void pl_distort(const PlDistortJob *__res
 __global__ __launch_bounds__(kThreads) void pl_distort_visible(const PlDistortJob *__restrict__ jobs) { distort_body<true>(jobs); }
 
 /* as pl_prepost.hip:batch_grid: enough workgroups to fill 256 CUs several times over, but never more than the batch needs; a launch takes at most
- * 65535 images (gridDim.y) */
-constexpr size_t kMaxImages = 65535;
+ * PLD_MAX_IMAGES images (gridDim.y).  pl_distort_core.h:pld_grid_blocks has the rule. */
+constexpr size_t kMaxImages = PLD_MAX_IMAGES;
 dim3 distort_grid(size_t n, uint64_t max_pixels)
 {
-    size_t blocks = (size_t)((max_pixels + (uint64_t)kThreads * 16 - 1) / ((uint64_t)kThreads * 16));
-    size_t cap = (2048 + n - 1) / n;
-    if (cap < 8) cap = 8;
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    return dim3((unsigned)blocks, (unsigned)n, 1);
+    return dim3((unsigned)pld_grid_blocks(n, max_pixels), (unsigned)n, 1);
 }
 
 } // namespace

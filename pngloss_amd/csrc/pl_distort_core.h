@@ -136,6 +136,23 @@ PLD_HD PldSum pld_thread(const uint32_t *a, const uint32_t *b, size_t n, size_t 
     return s;
 }
 
+/* ---- the launch shape of pl_keep and pl_distort (pl_distort.hip), stated here so that a CPU test can pin it: PLD_THREADS lanes per workgroup, a
+ * launch of at most PLD_MAX_IMAGES images (gridDim.y; a larger batch is launched in slices), and per image enough workgroups to give a lane 16 pixels
+ * of the largest image, but only as many as fill 256 CUs several times over across the batch: min(needed, max(8, ceil(2048 / n))), at least 1.
+ * A batch of 256 or more images so gets 8 workgroups -- 2048 lanes -- per image, however large its images are. ---- */
+constexpr uint32_t PLD_THREADS = 256;
+constexpr size_t PLD_MAX_IMAGES = 65535;
+
+inline size_t pld_grid_blocks(size_t n, uint64_t max_pixels)
+{
+    size_t blocks = (size_t)((max_pixels + (uint64_t)PLD_THREADS * 16 - 1) / ((uint64_t)PLD_THREADS * 16));
+    size_t cap = (2048 + n - 1) / n;
+    if (cap < 8) cap = 8;
+    if (blocks > cap) blocks = cap;
+    if (blocks < 1) blocks = 1;
+    return blocks;
+}
+
 /* the sums of all threads of an image, and its pixel count (visible mode: s.visible), as its record */
 PLD_HD void pld_record(PlDistortRecord &r, const PldSum &s, uint64_t pixels)
 {

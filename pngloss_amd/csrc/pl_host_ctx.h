@@ -198,6 +198,7 @@ static_assert(sizeof(pngloss_hip_distortion) == sizeof(PlDistortRecord) && offse
 static_assert(sizeof(pngloss_hip_ssim) == sizeof(PlSsimRecord) && offsetof(pngloss_hip_ssim, windows) == offsetof(PlSsimRecord, windows) &&
               offsetof(pngloss_hip_ssim, sum_q16) == offsetof(PlSsimRecord, sum_q16) && offsetof(pngloss_hip_ssim, min_q16) == offsetof(PlSsimRecord, min_q16) &&
               offsetof(pngloss_hip_ssim, reserved) == offsetof(PlSsimRecord, reserved), "pngloss_hip_ssim and PlSsimRecord");
+static_assert(PLD_MAX_IMAGES == PLS_MAX_IMAGES && PLD_MAX_IMAGES == 65535, "the measuring launches slice a batch at the same place: gridDim.y holds 65535 images");
 
 struct EmitTarget { void *d_ids; void *d_rows; uint32_t pitch; };
 

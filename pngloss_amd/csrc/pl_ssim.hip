@@ -66,16 +66,11 @@ __global__ __launch_bounds__(kThreads) void pl_ssim(const PlSsimJob *__restrict_
 __global__ __launch_bounds__(kThreads) void pl_ssim_visible(const PlSsimJob *__restrict__ jobs) { ssim_body<true>(jobs); }
 
 /* enough workgroups to fill 256 CUs several times over, but never more than the batch needs (pl_distort.hip:distort_grid); a launch takes at most
- * 65535 images (gridDim.y) */
-constexpr size_t kMaxImages = 65535;
+ * PLS_MAX_IMAGES images (gridDim.y).  pl_ssim_core.h:pls_grid_blocks has the rule. */
+constexpr size_t kMaxImages = PLS_MAX_IMAGES;
 dim3 ssim_grid(size_t n, uint64_t max_tiles)
 {
-    size_t blocks = (size_t)max_tiles;
-    size_t cap = (2048 + n - 1) / n;
-    if (cap < 8) cap = 8;
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    return dim3((unsigned)blocks, (unsigned)n, 1);
+    return dim3((unsigned)pls_grid_blocks(n, max_tiles), (unsigned)n, 1);
 }
 
 } // namespace

@@ -89,6 +89,22 @@ PLS_HD PlsGeom pls_geom(uint32_t width, uint32_t height)
     return g;
 }
 
+/* ---- the launch shape of pl_ssim (pl_ssim.hip), stated here so that a CPU test can pin it: a launch takes at most PLS_MAX_IMAGES images (gridDim.y; a
+ * larger batch is launched in slices), and an image gets a workgroup per tile of the batch's largest image, but only as many as fill 256 CUs several
+ * times over across the batch (pl_distort_core.h:pld_grid_blocks has the same cap): min(max_tiles, max(8, ceil(2048 / n))), at least 1.  Workgroup b
+ * takes tiles b, b + blocks, ... of its image. ---- */
+constexpr size_t PLS_MAX_IMAGES = 65535;
+
+inline size_t pls_grid_blocks(size_t n, uint64_t max_tiles)
+{
+    size_t blocks = (size_t)max_tiles;
+    size_t cap = (2048 + n - 1) / n;
+    if (cap < 8) cap = 8;
+    if (blocks > cap) blocks = cap;
+    if (blocks < 1) blocks = 1;
+    return blocks;
+}
+
 /* rows of four pixels go through 16-byte loads when every cell row of both images starts on a 16-byte boundary: both bases do and the pitch is
  * a multiple of four pixels.  Otherwise word by word. */
 PLS_HD bool pls_vector_rows(const void *a, const void *b, uint32_t width)

@@ -7,6 +7,9 @@
  * CASES: uint64 count, then per case uint64 { pixels, a_offset, b_offset, nthreads } and pixels words of a, pixels words of b.  Each image gets a heap
  * block of its own that starts a_offset / b_offset bytes behind a 16-byte boundary and ends with its last pixel, so a load past an image is a report.
  * Prints per case one line: pixels changed_pixels sq_err[0..3] max_abs[0..3].
+ *
+ *   distort_host grid N MAX_PIXELS [N MAX_PIXELS ...]
+ * The launch shape of pl_distort.hip: prints PLD_MAX_IMAGES and PLD_THREADS on one line, then per (N, MAX_PIXELS) pld_grid_blocks(N, MAX_PIXELS); N >= 1.
  */
 #include "../../pngloss_amd/csrc/pl_distort_core.h"
 
@@ -23,8 +26,21 @@ static uint32_t *block(FILE *f, uint64_t pixels, uint64_t offset, void **base)
     return p;
 }
 
+static int grid(int argc, char **argv)
+{
+    if (argc % 2) return 2;
+    std::printf("%zu %u\n", PLD_MAX_IMAGES, PLD_THREADS);
+    for (int k = 2; k < argc; k += 2) {
+        const uint64_t n = std::strtoull(argv[k], nullptr, 10), max_pixels = std::strtoull(argv[k + 1], nullptr, 10);
+        if (!n) return 2;
+        std::printf("%zu\n", pld_grid_blocks((size_t)n, max_pixels));
+    }
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc >= 2 && std::strcmp(argv[1], "grid") == 0) return grid(argc, argv);
     FILE *f = argc == 2 ? std::fopen(argv[1], "rb") : nullptr;
     uint64_t count = 0;
     if (!f || std::fread(&count, 8, 1, f) != 1) return 2;

@@ -1,5 +1,5 @@
 """CPU tests of the distortion report (no GPU compute): pngloss_hip_psnr_db on hand-made records, the kernel's arithmetic
-(pngloss_amd/csrc/pl_distort_core.h) run on the CPU under the sanitizers against numpy, and the command line switch where no device is needed.
+(pngloss_amd/csrc/pl_distort_core.h) run on the CPU under the sanitizers against numpy, the launch shape (pld_grid_blocks) against its restatement, and the command line switch where no device is needed.
 Expected values come from numpy / Python arithmetic (tests/util_distort.py), never from the code under test."""
 import math
 import os
@@ -76,6 +76,23 @@ def test_core_arithmetic_equals_numpy_under_asan_and_ubsan(tmp_path):
     for (a, b, oa, ob, nt), g in zip(cases, got):
         assert g == D.np_distortion(a, b), (a.shape, oa, ob, nt)
     assert got[len(D.MIXED_SHAPES) * 3 + 4]["sq_err"] == [2048 * 2048 * 255 * 255] * 4 == [272734617600] * 4
+
+
+def test_grid_rule_equals_its_restatement_at_the_pinned_points(tmp_path):
+    """pld_grid_blocks, PLD_MAX_IMAGES and PLD_THREADS of pl_distort_core.h -- what pl_distort.hip launches pl_keep and pl_distort with -- against
+    D.grid_blocks, whose values at the pinned points are written out in D.GRID_POINTS"""
+    exe = D.build_distort_host(tmp_path)
+    assert D.GRID_N == [1, 5, 59, 255, 256, 257, 300, 65535] and sorted(D.GRID_POINTS) == [0, 1, 4096, 4097, 33587200]
+    points = [(n, m) for m in sorted(D.GRID_POINTS) for n in D.GRID_N]
+    points += [(n, m) for n in (2, 7, 8, 228, 229, 260, 2048, 2049, 65540) for m in (4095, 8192, 8193, 32768, 32769, 527857, 4096 * 2048, 4096 * 2048 + 1, 1 << 40)]
+    max_images, threads, got = D.run_distort_grid(exe, points)
+    assert (max_images, threads) == (D.MAX_IMAGES, D.THREADS) == (65535, 256)
+    assert got == [D.grid_blocks(n, m) for n, m in points]
+    assert got[: 5 * 8] == [b for m in sorted(D.GRID_POINTS) for b in D.GRID_POINTS[m]]
+    # what the GPU tests rely on: in a batch of 256 or more an image has 2048 lanes, and 8192 x 4100 pixels are then 4100 quads a lane -- 16 pixels past
+    # the first flush; alone it has 2048 workgroups and a lane never flushes
+    assert D.lane_pixels(260, 8192 * 4100, 8192 * 4100) == 16400 == D.FLUSH_PIXELS + 16 and D.lane_pixels(260, 8192 * 4100, 8192 * 4100, vector=False) == 16400
+    assert D.lane_pixels(1, 8192 * 4100, 8192 * 4100) == 68 < D.FLUSH_PIXELS      # 524 288 lanes, 17 quads at the most
 
 
 @needs_cli

@@ -1,4 +1,5 @@
-"""GPU tests of the distortion report: pngloss_hip_compare_batch on shapes the optimiser cannot produce, the option "distortion" on every optimise
+"""GPU tests of the distortion report: pngloss_hip_compare_batch on shapes the optimiser cannot produce, in a call of 260 pairs (8 workgroups per
+image: long lane loops, a lane that flushes its 32-bit sums) and in one of 65 540 (a second launch), the option "distortion" on every optimise
 entry point (outputs unchanged, records equal to numpy on original and output), the multi-device wrapper and the command line switch.
 
 Every expected record comes from numpy on the two pixel arrays (tests/util_distort.py:np_distortion), the optimised pixels from the CPU oracle
@@ -137,6 +138,118 @@ def test_compare_large_frames_sums_beyond_32_bits_and_a_single_last_pixel():
     assert full == dict(pixels=n, changed_pixels=n, sq_err=[n * 255 * 255] * 4, max_abs=[255] * 4) and n * 255 * 255 == 272734617600 > 1 << 32
     assert one == dict(pixels=n, changed_pixels=1, sq_err=[0, 0, 0, 1], max_abs=[0, 0, 0, 1])
     assert same == dict(pixels=n, changed_pixels=0, sq_err=[0] * 4, max_abs=[0] * 4)
+
+
+#: the pair that makes a lane of pl_distort empty its 32-bit sums: 8192 x 4100 = 2048 lanes x 4100 quads.  With 256 or more pairs in a call an image has
+#: 8 workgroups = 2048 lanes (D.grid_blocks) -- the fewest the rule gives -- and a lane flushes after D.FLUSH_PIXELS = 16 384 pixels, so this is the
+#: smallest shape that reaches pld_flush inside the loops on a device: every lane flushes once, at its 4096th quad, and carries 4 quads to the end.
+FLUSH_W, FLUSH_H, FLUSH_BLOCK_H = 8192, 4100, 100
+#: pixel index -> the channel that gets the error, and the error: the very first pixel, lane 7's first quad after its flush, the very last pixel
+FLUSH_MARKS = {0: (0, 255), 4 * (2048 * 4096 + 7): (2, 253), FLUSH_W * FLUSH_H - 1: (1, 254)}
+
+
+@functools.lru_cache(maxsize=None)
+def _flush_block():
+    """a random 8192 x 100 pair (3.3 MB each), about half of its pixels changed, by at most 100 per channel"""
+    rng = np.random.default_rng(17)
+    a = rng.integers(0, 256, (FLUSH_BLOCK_H, FLUSH_W, 4), dtype=np.uint8)
+    b = np.clip(a.astype(np.int64) + rng.integers(-100, 101, a.shape) * (rng.random(a.shape[:2]) < 0.5)[..., None], 0, 255).astype(np.uint8)
+    a.setflags(write=False); b.setflags(write=False)
+    return a, b
+
+
+def _flush_expected():
+    """the record of the block repeated 41 times with the three marked pixels: 41 x numpy's record of the block, corrected for the three"""
+    a, b = _flush_block()
+    blk = D.np_distortion(a, b)
+    reps = FLUSH_H // FLUSH_BLOCK_H
+    assert reps * FLUSH_BLOCK_H == FLUSH_H and reps == 41 and max(blk["max_abs"]) <= 100 and 0 < blk["changed_pixels"] < blk["pixels"]
+    rec = dict(pixels=reps * blk["pixels"], changed_pixels=reps * blk["changed_pixels"], sq_err=[reps * s for s in blk["sq_err"]], max_abs=list(blk["max_abs"]))
+    fa, fb = a.reshape(-1, 4).astype(np.int64), b.reshape(-1, 4).astype(np.int64)
+    for p, (c, err) in FLUSH_MARKS.items():
+        was = fb[p % len(fa)] - fa[p % len(fa)]               # what the pixel under the mark added
+        rec["changed_pixels"] += 1 - int(was.any())
+        for k in range(4):
+            rec["sq_err"][k] += (err * err if k == c else 0) - int(was[k]) ** 2
+        rec["max_abs"][c] = err
+    return rec
+
+
+def _flush_build(view_a, view_b):
+    """the pair into two device byte views of 8192 * 4100 * 4 bytes: the block 41 times, then the marks (a = 0, b = the error in one channel)"""
+    import torch
+    a, b = _flush_block()
+    for view, blk in ((view_a, a), (view_b, b)):
+        view.view(FLUSH_H // FLUSH_BLOCK_H, -1).copy_(torch.from_numpy(np.array(blk).reshape(1, -1)).cuda())
+    for p, (c, err) in FLUSH_MARKS.items():
+        view_a[4 * p: 4 * p + 4] = 0
+        view_b[4 * p: 4 * p + 4] = 0
+        view_b[4 * p + c] = err
+    torch.cuda.synchronize()
+
+
+def test_compare_260_pairs_small_grid_long_lane_loops_and_the_flush():
+    """With 256 or more pairs in a call an image gets 8 workgroups, whatever its size: the grid-stride loops of pl_distort run long, as they do in
+    production.  The flush pair (above), a 1021 x 517 noise pair -- some 64 quads per lane and a tail of one word -- from aligned bases and from
+    bases 4 bytes off (every pixel through the word loop), and the mixed shapes over and over.  Then the same with the flush pair 4 bytes off
+    alignment: 16 400 words per lane, the flush falls in the word loop.  Alone the flush pair has 2048 workgroups, no lane flushes: the same record."""
+    import torch
+    n, px = 260, FLUSH_W * FLUSH_H
+    rng = np.random.default_rng(19)
+    noise = tuple(rng.integers(0, 256, (517, 1021, 4), dtype=np.uint8) for _ in range(2))
+    mixed = D.mixed_pairs()
+    # the preconditions, from the restated grid rule alone
+    assert n <= D.MAX_IMAGES and D.grid_blocks(n, px) == 8 and px == 33587200 == 8 * D.THREADS * 4 * 4100
+    assert D.lane_pixels(n, px, px) == D.lane_pixels(n, px, px, vector=False) == 16400 > D.FLUSH_PIXELS > 16400 // 2      # one flush in the loop, 16 pixels after it
+    assert D.lane_pixels(n, px, 1021 * 517) == 4 * 65 and 1021 * 517 % 4 == 1 and D.lane_pixels(n, px, 1021 * 517, vector=False) == 258
+    assert D.lane_pixels(1, px, px) == 68 < D.FLUSH_PIXELS and D.grid_blocks(1, px) == 2048
+    want_flush, want_noise, want_mixed = _flush_expected(), D.np_distortion(*noise), [D.np_distortion(a, b) for a, b in mixed]
+    assert want_flush["max_abs"][:3] == [255, 254, 253] and want_flush["pixels"] == px and min(want_flush["sq_err"]) > 1 << 32
+    big = [torch.empty(px * 4 + 16, dtype=torch.uint8, device="cuda") for _ in range(2)]
+    off4 = [torch.zeros(noise[0].size + 16, dtype=torch.uint8, device="cuda") for _ in range(2)]
+    for t, x in zip(off4, noise):
+        t[4: 4 + x.size].copy_(torch.from_numpy(x.reshape(-1)))
+    dev_noise = [_dev(x) for x in noise]
+    dev_mixed = [(_dev(a), _dev(b)) for a, b in mixed]
+    assert all(t.data_ptr() % 16 == 0 for t in big + off4 + dev_noise)
+    order = [k % len(mixed) for k in range(n - 3)]
+    rest = [(dev_noise[0].data_ptr(), dev_noise[1].data_ptr(), 1021, 517), (off4[0].data_ptr() + 4, off4[1].data_ptr() + 4, 1021, 517)]
+    rest += [(dev_mixed[k][0].data_ptr() if mixed[k][0].size else 0, dev_mixed[k][1].data_ptr() if mixed[k][0].size else 0) + mixed[k][0].shape[1::-1] for k in order]
+    ctx = P.HipContext()
+    try:
+        for off in (0, 4):
+            _flush_build(big[0][off: off + px * 4], big[1][off: off + px * 4])
+            flush = (big[0].data_ptr() + off, big[1].data_ptr() + off, FLUSH_W, FLUSH_H)
+            got = [r.as_dict() for r in ctx.compare([flush] + rest)]
+            alone = ctx.compare([flush])[0].as_dict()
+            print(off, got[0], alone)
+            assert got[0] == want_flush, off
+            assert alone == want_flush, off
+            assert got[1] == want_noise and got[2] == want_noise, off
+            for i, k in enumerate(order):
+                assert got[3 + i] == want_mixed[k], (off, 3 + i, mixed[k][0].shape)
+    finally:
+        ctx.close()
+
+
+def test_compare_more_pairs_than_one_launch_takes():
+    """65 540 pairs: a launch takes 65 535 (D.MAX_IMAGES), so the last five are a second launch, which must start at its own jobs"""
+    from tests import util_visible as V
+    pool = V.split_pool()
+    n = V.SPLIT_N
+    assert n > D.MAX_IMAGES == 65535 and n - D.MAX_IMAGES < len(pool) == 7
+    want = D.dicts_array([D.np_distortion(a, b) for _, a, b in pool])
+    assert len({w.tobytes() for w in want}) == 7 and want["pixels"].tolist() == [1, 3, 64, 144, 117, 128, 0]
+    dev = [(_dev(a), _dev(b)) for _, a, b in pool]
+    desc = [(da.data_ptr() if a.size else 0, db.data_ptr() if a.size else 0, a.shape[1], a.shape[0]) for (da, db), (_, a, _) in zip(dev, pool)]
+    ctx = P.HipContext()
+    try:
+        got = D.records_array(ctx.compare([desc[i % 7] for i in range(n)]))
+    finally:
+        ctx.close()
+    bad = D.differing(got, want[np.arange(n) % 7])
+    assert not bad.size, "%d records differ, the first at %s; around the end of the first launch: %s" % (
+        bad.size, bad[:8].tolist(), {i: (got[i].tolist(), want[i % 7].tolist()) for i in range(65534, 65540)})
 
 
 def test_compare_identical_pair_and_a_batch_in_flight():

@@ -1,4 +1,5 @@
-"""GPU tests of the SSIM measurement: pngloss_hip_compare_batch_ssim on every shape and content of tests/util_ssim.py, the option "ssim" on every
+"""GPU tests of the SSIM measurement: pngloss_hip_compare_batch_ssim on every shape and content of tests/util_ssim.py, in a call of 260 pairs
+(8 workgroups per image: tile after tile over one LDS table, sums past 32 bits) and in one of 65 540 (a second launch), the option "ssim" on every
 optimise entry point (outputs unchanged, records equal to the definition on original and oracle output), pngloss_hip_optimize_batch_target2
 against the committed table of the CPU oracle (tests/golden/ssim_target_table.json), the multi-device wrapper and the two command line switches.
 
@@ -17,6 +18,7 @@ from tests import util as U
 from tests import util_distort as D
 from tests import util_ssim as S
 from tests import util_target as T
+from tests import util_visible as V
 
 pytestmark = pytest.mark.gpu
 
@@ -80,6 +82,66 @@ def test_compare_bases_off_16_byte_alignment():
                 assert ctx.compare_ssim([(va.data_ptr(), vb.data_ptr(), a.shape[1], a.shape[0])])[0].as_dict() == S.expected(name), (name, oa, ob)
     finally:
         ctx.close()
+
+
+def _pair_descs(cases):
+    """(name, a, b) cases on the device: (the tensors, to be kept, and one (d_a, d_b, width, height) per case)"""
+    dev = [(_dev(a), _dev(b)) for _, a, b in cases]
+    return dev, [(da.data_ptr() if a.size else 0, db.data_ptr() if a.size else 0, a.shape[1], a.shape[0]) for (da, db), (_, a, _) in zip(dev, cases)]
+
+
+def test_compare_260_pairs_workgroups_past_their_first_tile_and_sums_beyond_32_bits():
+    """With 256 or more pairs in a call an image gets 8 workgroups, whatever its size (S.grid_blocks): a workgroup then takes tile after tile over
+    one LDS table, as it does in production.  Five big pairs in front -- S.trip_pairs() says what each is for --, 255 small ones behind them, most
+    of whose 8 workgroups have no tile at all; then the five alone, one workgroup per tile.  The two uniform pairs sum q past -2^32 and 2^32."""
+    big, want_big = S.trip_pairs(), S.trip_expected()
+    fill, want_fill = S.fill_pairs(), S.fill_expected()
+    n = 260
+    order = [k % len(fill) for k in range(n - len(big))]
+    shapes = S.TRIP_SHAPES + [fill[k][1].shape[1::-1] for k in order]
+    # the preconditions, from the restated grid rule alone
+    assert S.grid_blocks(n, max(S.tiles_of(*s) for s in shapes)) == 8 and n <= S.MAX_IMAGES
+    assert S.trips(n, shapes, 300, 77) == [2, 1, 1, 1, 1, 1, 1, 1]                        # the full tile 0, then the corner tile 8
+    assert S.trips(n, shapes, 1036, 1028) == [36] * 8 and S.trips(n, shapes, 1032, 1032) == [38] + [37] * 7
+    assert S.trips(n, shapes, 517, 261) == [4] * 8 and S.trips(n, shapes, 643, 131) == [3, 3, 3, 3, 2, 2, 2, 2]
+    assert S.trips(n, shapes, 12, 12) == [1, 0, 0, 0, 0, 0, 0, 0] and S.trips(n, shapes, 7, 64) == [0] * 8
+    assert max(max(S.trips(len(big), S.TRIP_SHAPES, *s)) for s in S.TRIP_SHAPES) == 1   # alone: a workgroup per tile
+    assert want_big[1]["sum_q16"] == [66048 * -65300] * 4 and 66048 * -65300 == -4312934400 < -(1 << 32) and want_big[1]["min_q16"] == [-65300] * 4
+    assert want_big[2]["sum_q16"] == [66049 * 65536] * 4 and 66049 * 65536 > 1 << 32 and want_big[2]["min_q16"] == [65536] * 4
+    keep_big, desc_big = _pair_descs(big)
+    keep_fill, desc_fill = _pair_descs(fill)
+    ctx = P.HipContext()
+    try:
+        got = ctx.compare_ssim(desc_big + [desc_fill[k] for k in order])
+        alone = ctx.compare_ssim(desc_big)
+    finally:
+        ctx.close()
+    for k, (name, _, _) in enumerate(big):
+        print(name, got[k].as_dict())
+        assert got[k].as_dict() == want_big[k], name
+        assert alone[k].as_dict() == want_big[k], name
+    assert got[2].mean(0xF) == 1.0
+    for i, k in enumerate(order):
+        assert got[len(big) + i].as_dict() == want_fill[k], (len(big) + i, fill[k][0])
+    assert want_fill[order[2]] == want_fill[order[4]] == NO_WINDOWS                      # 7x64 and 0x0: every workgroup added nothing
+
+
+def test_compare_more_pairs_than_one_launch_takes():
+    """65 540 pairs: a launch takes 65 535 (S.MAX_IMAGES), so the last five are a second launch, which must start at its own jobs"""
+    pool = V.split_pool()
+    n = V.SPLIT_N
+    assert n > S.MAX_IMAGES == 65535 and n - S.MAX_IMAGES < len(pool) == 7
+    want = D.dicts_array([S.py_ssim(a, b) for _, a, b in pool], S.RECORD_DTYPE)
+    assert len({w.tobytes() for w in want}) == 5                                            # (1x1, 3x1 and 0x0 have no window)
+    keep, desc = _pair_descs(pool)
+    ctx = P.HipContext()
+    try:
+        got = D.records_array(ctx.compare_ssim([desc[i % 7] for i in range(n)]), S.RECORD_DTYPE)
+    finally:
+        ctx.close()
+    bad = D.differing(got, want[np.arange(n) % 7])
+    assert not bad.size, "%d records differ, the first at %s; around the end of the first launch: %s" % (
+        bad.size, bad[:8].tolist(), {i: (got[i].tolist(), want[i % 7].tolist()) for i in range(65534, 65540)})
 
 
 def test_compare_refuses_a_batch_in_flight():

@@ -1,6 +1,7 @@
-"""GPU tests of the visible measuring mode: pngloss_hip_compare_batch_visible on the pairs of tests/util_visible.py, the option "measure" behind a
-batch (pixels and filter IDs unchanged, the records those of the definition), the target search accepting on visible records, the multi-device
-wrapper and the tool's --visible.
+"""GPU tests of the visible measuring mode: pngloss_hip_compare_batch_visible on the pairs of tests/util_visible.py, in a call of 260 pairs and in one
+of 65 540 (the kernels' loops past their first trip, a second launch), the option "measure" behind a batch -- of three images and of 258 -- (pixels
+and filter IDs unchanged, the records those of the definition), the target search accepting on visible records, the multi-device wrapper and the
+tool's --visible.
 
 Every expected record comes from the definitions restated in numpy and Python integers (tests/util_visible.py), the optimised pixels from the CPU
 oracle (U.run_port); equality is exact."""
@@ -107,6 +108,70 @@ def test_compare_visible_bases_off_16_byte_alignment():
         ctx.close()
 
 
+def _pair_descs(cases):
+    """(name, a, b) cases on the device: (the tensors, to be kept, and one (d_a, d_b, width, height) per case)"""
+    dev = [(_dev(a), _dev(b)) for _, a, b in cases]
+    return dev, [(da.data_ptr() if a.size else 0, db.data_ptr() if a.size else 0, a.shape[1], a.shape[0]) for (da, db), (_, a, _) in zip(dev, cases)]
+
+
+def test_compare_visible_260_pairs_workgroups_past_their_first_tile():
+    """The visible kernels with 8 workgroups per image (tests/test_gpu_ssim.py has the all-pixel twin and says why 260 pairs): pl_ssim_visible takes
+    tile after tile over one LDS table, pl_distort_visible several quads per lane.  The noise pairs have holes and a band of invisible windows at the
+    right edge; one 300 x 77 pair is invisible altogether -- every workgroup visits its tiles and must count nothing."""
+    big, want_big = V.trip_pairs(), V.trip_expected()
+    fill = S.fill_pairs()
+    want_fill = [(V.np_distortion(a, b), V.py_ssim(a, b)) for _, a, b in fill]
+    n = 260
+    order = [k % len(fill) for k in range(n - len(big))]
+    shapes = [a.shape[1::-1] for _, a, _ in big] + [fill[k][1].shape[1::-1] for k in order]
+    assert shapes[:6] == S.TRIP_SHAPES + [(300, 77)]
+    # the preconditions, from the restated grid rules alone
+    assert S.grid_blocks(n, max(S.tiles_of(*s) for s in shapes)) == 8 and D.grid_blocks(n, max(w * h for w, h in shapes)) == 8
+    assert S.trips(n, shapes, 300, 77) == [2, 1, 1, 1, 1, 1, 1, 1] and S.trips(n, shapes, 1036, 1028) == [36] * 8 and S.trips(n, shapes, 1032, 1032) == [38] + [37] * 7
+    assert S.trips(n, shapes, 517, 261) == [4] * 8 and S.trips(n, shapes, 643, 131) == [3, 3, 3, 3, 2, 2, 2, 2]
+    assert D.lane_pixels(n, 1036 * 1028, 1036 * 1028) == 4 * 131 and D.lane_pixels(n, 1036 * 1028, 517 * 261) == 4 * 17
+    keep_big, desc_big = _pair_descs(big)
+    keep_fill, desc_fill = _pair_descs(fill)
+    ctx = P.HipContext()
+    try:
+        dist, ssim = ctx.compare_visible(desc_big + [desc_fill[k] for k in order])
+        dist_alone, ssim_alone = ctx.compare_visible(desc_big)
+    finally:
+        ctx.close()
+    for k, (name, a, b) in enumerate(big):
+        print(name, dist[k].as_dict(), ssim[k].as_dict())
+        assert (dist[k].as_dict(), ssim[k].as_dict()) == want_big[k], name
+        assert (dist_alone[k].as_dict(), ssim_alone[k].as_dict()) == want_big[k], name
+    assert want_big[5] == (NOTHING, V.NO_WINDOWS) and want_big[1][1]["sum_q16"][0] < -(1 << 32) and want_big[2][1]["sum_q16"][0] > 1 << 32
+    for name, k in (("300x77_noise", 0), ("517x261_near", 3), ("643x131_near", 4)):
+        a, b = big[k][1:]
+        assert 0 < want_big[k][1]["windows"] < S.py_ssim(a, b)["windows"] and 0 < want_big[k][0]["pixels"] < a.shape[0] * a.shape[1], name
+    for i, k in enumerate(order):
+        assert (dist[len(big) + i].as_dict(), ssim[len(big) + i].as_dict()) == want_fill[k], (len(big) + i, fill[k][0])
+
+
+def test_compare_visible_more_pairs_than_one_launch_takes():
+    """65 540 pairs: a launch takes 65 535 (D.MAX_IMAGES, S.MAX_IMAGES), so the last five are a second launch of each kernel, which must start at its
+    own jobs"""
+    pool = V.split_pool()
+    n = V.SPLIT_N
+    assert n > D.MAX_IMAGES == S.MAX_IMAGES == 65535 and n - D.MAX_IMAGES < len(pool) == 7
+    want_d = D.dicts_array([V.np_distortion(a, b) for _, a, b in pool])
+    want_s = D.dicts_array([V.py_ssim(a, b) for _, a, b in pool], S.RECORD_DTYPE)
+    assert len({w.tobytes() for w in want_d}) == 7 and want_d["pixels"].tolist()[:5] == [1, 3, 64, 144, 117] and want_d["pixels"][5] < 128
+    keep, desc = _pair_descs(pool)
+    ctx = P.HipContext()
+    try:
+        dist, ssim = ctx.compare_visible([desc[i % 7] for i in range(n)])
+        got_d, got_s = D.records_array(dist), D.records_array(ssim, S.RECORD_DTYPE)
+    finally:
+        ctx.close()
+    for what, got, want in (("distortion", got_d, want_d), ("ssim", got_s, want_s)):
+        bad = D.differing(got, want[np.arange(n) % 7])
+        assert not bad.size, "%s: %d records differ, the first at %s; around the end of the first launch: %s" % (
+            what, bad.size, bad[:8].tolist(), {i: (got[i].tolist(), want[i % 7].tolist()) for i in range(65534, 65540)})
+
+
 def test_compare_visible_refuses_a_batch_in_flight_and_bad_arguments():
     import torch
     img = P.synth_rgba(160, 48, 0, 1)
@@ -177,6 +242,56 @@ def test_option_changes_the_records_and_nothing_else():
         assert recs_vis[i] == recs_host[i] == (V.np_distortion(img, vis[0][i]), V.py_ssim(img, vis[0][i])) == (vrec, vsrec), V.BATCH_SHAPES[i]
         assert vrec["pixels"] < rec["pixels"] and vsrec["windows"] < srec["windows"] and vrec != rec
         assert D.py_psnr_db(vrec, 0xF) < D.py_psnr_db(rec, 0xF)
+
+
+def _transparent_corner(img):
+    """a copy with its top right third made transparent white, as the transparent areas of real files are; read-only"""
+    img = np.array(img)
+    img[: (img.shape[0] * 2) // 3, (img.shape[1] * 2) // 3:] = (255, 255, 255, 0)
+    img.setflags(write=False)
+    return img
+
+
+def test_options_behind_a_batch_of_258_images():
+    """enqueue's own launches of pl_keep, pl_distort and pl_ssim with 8 workgroups per image at the most (256 or more images: D.grid_blocks,
+    S.grid_blocks): 301 x 77 -- an odd pitch, 9 SSIM tiles on 8 workgroups, several quads per lane of pl_keep and pl_distort and a tail of one word --,
+    1024 x 7 without a window, and four small images over and over.  All-pixel records, then visible ones; the pixels those of the CPU oracle and
+    of the same batch with the options off."""
+    distinct = [_transparent_corner(P.synth_rgba(301, 77, 0, 2)), _transparent_corner(P.synth_rgba(1024, 7, 0, 3))] + list(V.batch_images()) + [P.synth_rgba(48, 16, 5, 1)]
+    ref = []
+    for img in distinct:
+        out, filt = U.run_port(img, 19, T.BLEED)
+        ref.append((out, filt, D.np_distortion(img, out), S.py_ssim(img, out), V.np_distortion(img, out), V.py_ssim(img, out)))
+    n = 258
+    which = [0, 1] + [2 + k % 4 for k in range(n - 2)]
+    imgs = [distinct[k] for k in which]
+    shapes = [a.shape[1::-1] for a in imgs]
+    # the preconditions, from the restated grid rules alone
+    assert S.grid_blocks(n, max(S.tiles_of(*s) for s in shapes)) == 8 and S.trips(n, shapes, 301, 77) == [2, 1, 1, 1, 1, 1, 1, 1] and S.tiles_of(1024, 7) == 0
+    assert D.grid_blocks(n, max(w * h for w, h in shapes)) == 6 and D.lane_pixels(n, 301 * 77, 301 * 77) == 16 and 301 * 77 % 4 == 1
+    assert ref[0][2] != ref[0][4] and ref[0][3] != ref[0][5] and ref[0][2]["changed_pixels"] > 0          # the two modes differ on it
+    ctx = P.HipContext()
+    try:
+        dev, flt, desc = _device_batch(imgs)
+        res_off = ctx.run(desc, 19, T.BLEED)
+        off = _back(dev, flt, imgs)
+        ctx.set_option("distortion", "on")
+        ctx.set_option("ssim", "on")
+        runs = {}
+        for mode in ("all", "visible"):
+            ctx.set_option("measure", mode)
+            dev, flt, desc = _device_batch(imgs)
+            res = ctx.run(desc, 19, T.BLEED)
+            runs[mode] = (_back(dev, flt, imgs), res, [(ctx.distortion(i).as_dict(), ctx.ssim(i).as_dict()) for i in range(n)])
+    finally:
+        ctx.close()
+    for i, k in enumerate(which):
+        out, filt, rec, srec, vrec, vsrec = ref[k]
+        assert res_off[i]["status"] == 0 and np.array_equal(off[0][i], out) and np.array_equal(off[1][i], filt), (i, shapes[i])
+        for mode, want in (("all", (rec, srec)), ("visible", (vrec, vsrec))):
+            (outs, filts), res, recs = runs[mode]
+            assert res[i]["status"] == 0 and np.array_equal(outs[i], out) and np.array_equal(filts[i], filt), (mode, i, shapes[i])
+            assert recs[i] == want, (mode, i, shapes[i])
 
 
 # ------------------------------------------------------------------------------------------------ the search

@@ -1,6 +1,7 @@
 """CPU tests of the SSIM measurement (no GPU compute): the arithmetic of pngloss_amd/csrc/pl_ssim_core.h -- the two thread loops the kernel pl_ssim
 runs per tile -- on the CPU under the sanitizers (tests/c/ssim_host.cpp) against the definition restated in Python integers and against the
-textbook float formula (tests/util_ssim.py); pngloss_hip_ssim_mean on hand-made records; the check of a pngloss_hip_target2, the acceptance rule
+textbook float formula (tests/util_ssim.py), tile by tile and as the kernel's workgroups take them, over a table that is never cleared; the launch
+shape (pls_grid_blocks) against its restatement; pngloss_hip_ssim_mean on hand-made records; the check of a pngloss_hip_target2, the acceptance rule
 with the SSIM condition and the arena layout (tests/c/target2_host.cpp); the exported symbols and the command line switches where no device is
 needed."""
 import ctypes as C
@@ -17,6 +18,7 @@ from pngloss_amd import lib as L
 from tests import util as U
 from tests import util_ssim as S
 from tests import util_target as T
+from tests import util_visible as V
 
 CLI = os.path.join(U.ROOT, "pngloss_amd", "cli")
 have_png = os.path.exists("/opt/conda/include/png.h") or os.path.exists("/usr/include/png.h")
@@ -86,6 +88,65 @@ def test_misaligned_bases_thread_counts_and_odd_pitches(harness):
     got = S.run_ssim_host(exe, d, cases)
     for name, rec in zip(names, got):
         assert rec == S.expected(name), name
+
+
+def test_grid_rule_equals_its_restatement_at_the_pinned_points(harness):
+    """pls_grid_blocks and PLS_MAX_IMAGES of pl_ssim_core.h -- what pl_ssim.hip launches with -- against S.grid_blocks, whose values at the pinned points
+    are written out in S.GRID_POINTS"""
+    exe, _ = harness
+    assert S.GRID_N == [1, 5, 59, 255, 256, 257, 300, 65535] and sorted(S.GRID_POINTS) == [0, 1, 8, 9, 288, 4096]
+    points = [(n, t) for t in sorted(S.GRID_POINTS) for n in S.GRID_N]
+    points += [(n, t) for n in (2, 7, 8, 228, 229, 260, 2048, 2049, 65540) for t in (2, 7, 10, 20, 32, 297, 2047, 2048, 2049, 1 << 40)]
+    max_images, got = S.run_ssim_grid(exe, points)
+    assert max_images == S.MAX_IMAGES == 65535
+    assert got == [S.grid_blocks(n, t) for n, t in points]
+    assert got[: 6 * 8] == [b for t in sorted(S.GRID_POINTS) for b in S.GRID_POINTS[t]]
+    # what the GPU tests rely on: 260 pairs put 8 workgroups on every image, 5 pairs one on (nearly) every tile
+    assert S.grid_blocks(260, 297) == 8 and S.grid_blocks(5, 297) == 297 and S.grid_blocks(65535, 1) == S.grid_blocks(5, 1) == 1
+
+
+#: (name of the pair, workgroups): 300x77, where tile 8 -- the 10 x 2-window corner -- follows the full tile 0 in workgroup 0; 5 x 4 tiles partial in
+#: both directions, 3 and 2 trips; 32 full tiles on an odd width, 4 trips each; 2 x 2 tiles, all in one workgroup
+WORKGROUP_CASES = [("300x77_noise", 8), ("643x131_near", 8), ("517x261_near", 8), ("136x40", 1)]
+
+
+def test_a_workgroups_tiles_over_one_table_that_is_never_cleared(harness):
+    """what LDS sees on the device: the table is poisoned once per workgroup, then the workgroup's tiles run over it one after the other, each leaving
+    its cells behind for the next -- in both instantiations; the records are the definition's and those of the tile-by-tile run"""
+    exe, d = harness
+    plain = {n: (a, b) for n, a, b in S.trip_pairs()}
+    plain["136x40"] = V.ssim_pairs()["136x40"]
+    visible = {n: (a, b) for n, a, b in V.trip_pairs()}
+    visible["136x40"] = V.ssim_pairs()["136x40"]
+    cases, wants = [], []
+    for name, blocks in WORKGROUP_CASES:
+        for vis, pairs, ssim in ((0, plain, S.py_ssim), (1, visible, V.py_ssim)):
+            a, b = pairs[name]
+            per = S.trips(1, [(a.shape[1], a.shape[0])], a.shape[1], a.shape[0])
+            assert len(per) == S.tiles_of(a.shape[1], a.shape[0]) > blocks           # (alone in a call every tile has a workgroup: the older tests)
+            cases += [(a, b, 0, 0, 256, blocks, vis), (a, b, 0, 0, 256, 0, vis)]
+            wants.append((name, vis, ssim(a, b)))
+    assert [S.tiles_of(*plain[n][0].shape[1::-1]) for n, _ in WORKGROUP_CASES] == [9, 20, 32, 4]
+    got = S.run_ssim_host(exe, d, cases)
+    for k, (name, vis, want) in enumerate(wants):
+        assert got[2 * k] == want and got[2 * k + 1] == want, (name, vis)
+        assert want["windows"] > 0
+    # the visible pairs drop windows, so the two instantiations were told apart
+    assert all(wants[2 * k][2] != wants[2 * k + 1][2] for k in range(len(WORKGROUP_CASES)))
+
+
+def test_closed_forms_of_the_two_uniform_pairs_equal_the_definition():
+    """the GPU tests expect 66 048 x (-65300) and 66 049 x 65536 -- past -2^32 and 2^32 -- of the checkerboard and the equal pair: here the definition
+    says so on the whole images"""
+    got = {n: (a, b, S.py_ssim(a, b)) for n, a, b in S.trip_pairs() if n in ("1036x1028_checkerboard_inverse", "1032x1032_equal")}
+    want = dict(zip([n for n, _, _ in S.trip_pairs()], S.trip_expected()))
+    a, b, rec = got["1036x1028_checkerboard_inverse"]
+    assert rec == want["1036x1028_checkerboard_inverse"] == S.uniform_record(a, b)
+    assert rec == dict(windows=258 * 256, sum_q16=[66048 * -65300] * 4, min_q16=[-65300] * 4, reserved=0) and 66048 * -65300 == -4312934400 < -(1 << 32)
+    a, b, rec = got["1032x1032_equal"]
+    assert rec == want["1032x1032_equal"] == S.uniform_record(a, b)
+    assert rec == dict(windows=257 * 257, sum_q16=[66049 * 65536] * 4, min_q16=[65536] * 4, reserved=0) and 66049 * 65536 > 1 << 32
+    assert P.ssim_mean(rec, 0xF) == 1.0
 
 
 def test_ssim_mean_on_hand_made_records_needs_no_device():

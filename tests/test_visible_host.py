@@ -51,6 +51,16 @@ def test_pm_for_every_channel_value_and_alpha(harness):
     assert np.array_equal(V.run_pm(exe).astype(np.int64), words)
 
 
+def test_closed_forms_of_the_two_uniform_pairs_equal_the_visible_definition():
+    """V.trip_expected() takes the SSIM records of the 66 048- and 66 049-window pairs from their 8x8 corner: the definition on the whole pairs agrees"""
+    want = dict(zip([n for n, _, _ in V.trip_pairs()], V.trip_expected()))
+    for name, a, b in V.trip_pairs():
+        if name in ("1036x1028_checkerboard_inverse", "1032x1032_equal"):
+            assert V.py_ssim(a, b) == want[name][1], name
+            assert abs(want[name][1]["sum_q16"][0]) > 1 << 32 and want[name][1]["windows"] == S.geometry(a.shape[1], a.shape[0])[0] * S.geometry(a.shape[1], a.shape[0])[1]
+    assert want["300x77_invisible"] == (dict(pixels=0, changed_pixels=0, sq_err=[0] * 4, max_abs=[0] * 4), V.NO_WINDOWS)
+
+
 def test_distortion_loop_equals_numpy_under_asan_and_ubsan(harness):
     """the visible thread loop on the CPU: the mixed shapes, misaligned bases, a lane that must flush its 32-bit sums, nothing visible, pixels visible
     in one image only, and an opaque pair, whose visible record is the all-pixel one"""

@@ -90,6 +90,75 @@ def run_distort_host(exe, tmp_path, cases):
     return recs
 
 
+# ---- the launch shape of pl_keep and pl_distort (pl_distort_core.h: pld_grid_blocks, PLD_MAX_IMAGES, PLD_THREADS, PLD_FLUSH_PIXELS), restated ----
+
+#: a launch takes at most this many images; lanes per workgroup; a lane empties its 32-bit sums once it has taken this many pixels
+MAX_IMAGES, THREADS, FLUSH_PIXELS = 65535, 256, 16384
+
+
+def grid_blocks(n, max_pixels):
+    """workgroups per image of a launch of n images whose largest has max_pixels pixels: min(ceil(max_pixels / 4096), max(8, ceil(2048 / n))), at
+    least 1"""
+    assert n >= 1
+    return max(1, min(-(-max_pixels // (THREADS * 16)), max(8, -(-2048 // n))))
+
+
+#: the rule at the points the CPU test pins, written out: {max_pixels: blocks for n = GRID_N}
+GRID_N = [1, 5, 59, 255, 256, 257, 300, 65535]
+GRID_POINTS = {
+    0: [1, 1, 1, 1, 1, 1, 1, 1],
+    1: [1, 1, 1, 1, 1, 1, 1, 1],
+    4096: [1, 1, 1, 1, 1, 1, 1, 1],
+    4097: [2, 2, 2, 2, 2, 2, 2, 2],
+    33587200: [2048, 410, 35, 9, 8, 8, 8, 8],
+}
+
+
+def lane_pixels(n, max_pixels, pixels, vector=True):
+    """the most pixels one lane takes of an image of `pixels` in a launch of n images whose largest has max_pixels: quads (16-byte path) or words at a
+    stride of every lane of the image's workgroups"""
+    lanes = grid_blocks(n, max_pixels) * THREADS
+    return 4 * -(-(pixels // 4) // lanes) if vector else -(-pixels // lanes)
+
+
+def run_distort_grid(exe, points):
+    """points: (n, max_pixels) each.  Returns (PLD_MAX_IMAGES, PLD_THREADS, [pld_grid_blocks(n, max_pixels)]) from the C code"""
+    r = subprocess.run([exe, "grid"] + [str(v) for p in points for v in p], capture_output=True, text=True, timeout=300,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr and "LeakSanitizer" not in r.stderr, r.stderr[-2000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == len(points) + 1
+    return int(lines[0].split()[0]), int(lines[0].split()[1]), [int(x) for x in lines[1:]]
+
+
+# ---- many records at once: the ctypes array a compare call filled, seen through numpy ----
+
+#: PlDistortRecord / pngloss_hip_distortion as a numpy record
+RECORD_DTYPE = np.dtype([("pixels", "<u8"), ("changed_pixels", "<u8"), ("sq_err", "<u8", (4,)), ("max_abs", "<u4", (4,))])
+
+
+def records_array(recs, dtype=RECORD_DTYPE):
+    """the list of structures a compare call returned (items of ONE ctypes array) as a numpy array of records over the same memory"""
+    assert dtype.itemsize == 64 == C.sizeof(type(recs[0]))
+    return np.frombuffer(recs[0]._b_base_, dtype=dtype, count=len(recs))
+
+
+def dicts_array(dicts, dtype=RECORD_DTYPE):
+    """record dicts (np_distortion, py_ssim) as a numpy array of records"""
+    out = np.zeros(len(dicts), dtype)
+    for k, d in enumerate(dicts):
+        for name in dtype.names:
+            out[name][k] = d[name]
+    return out
+
+
+def differing(got, want):
+    """indices at which two record arrays differ in any byte"""
+    g, w = (np.ascontiguousarray(x).view(np.uint8).reshape(len(x), -1) for x in (got, want))
+    return np.flatnonzero((g != w).any(axis=1))
+
+
 _keep = None
 
 

@@ -155,6 +155,107 @@ def expected(name):
     raise KeyError(name)
 
 
+# ---- the pairs that take a workgroup of pl_ssim past its first tile, and sum_q16 past 32 bits ----
+
+#: (width, height) of the five big pairs; with 256 or more pairs in a call an image gets 8 workgroups (grid_blocks), which then take
+#: 9 tiles (a full one, then the partial corner in workgroup 0); 288 tiles = 36 each; 297 = 37 and a remainder; 32 full tiles = 4 each; 20 = 3 or 2 each
+TRIP_SHAPES = [(300, 77), (1036, 1028), (1032, 1032), (517, 261), (643, 131)]
+#: the shapes of the small pairs that fill such a call: one window, four, none, two, no pixels
+FILL_SHAPES = [(8, 8), (12, 12), (7, 64), (13, 9), (0, 0)]
+
+
+def near_pair(w, h, seed):
+    """noise and the same noise +- 12"""
+    rng = np.random.default_rng(seed)
+    a = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
+    return a, np.clip(a.astype(np.int64) + rng.integers(-12, 13, a.shape), 0, 255).astype(np.uint8)
+
+
+@functools.lru_cache(maxsize=None)
+def trip_pairs():
+    """[(name, a, b)] of TRIP_SHAPES, read-only: noise against noise; a checkerboard against its inverse (every window the same 8x8 pair); equal
+    images; noise against noise +- 12 on an odd width (word-by-word loads) whose 128 x 64 windows fill 32 tiles to the brim; the same on 159 x 31
+    windows, 5 x 4 tiles partial in both directions"""
+    out = [("300x77_noise",) + contents(300, 77)["noise"], ("1036x1028_checkerboard_inverse",) + contents(1036, 1028)["checkerboard_inverse"],
+           ("1032x1032_equal",) + contents(1032, 1032)["equal"], ("517x261_near",) + near_pair(517, 261, 41), ("643x131_near",) + near_pair(643, 131, 43)]
+    assert [(a.shape[1], a.shape[0]) for _, a, _ in out] == TRIP_SHAPES
+    for _, a, b in out:
+        a.setflags(write=False); b.setflags(write=False)
+    return out
+
+
+def uniform_record(a, b, ssim=None):
+    """the record of a pair whose windows are all the 8x8 pair at its top left corner -- a pattern of period 4 or less both ways, or equal images --:
+    the corner's q, times the window count.  (tests/test_ssim_host.py checks it against py_ssim on the whole pair.)"""
+    nx, ny = geometry(a.shape[1], a.shape[0])
+    one = (ssim or py_ssim)(a[:8, :8], b[:8, :8])
+    assert one["windows"] == 1 and one["sum_q16"] == one["min_q16"]
+    return dict(windows=nx * ny, sum_q16=[nx * ny * q for q in one["sum_q16"]], min_q16=one["min_q16"], reserved=0)
+
+
+@functools.lru_cache(maxsize=None)
+def trip_expected():
+    """the records of trip_pairs(): py_ssim, but for the two uniform pairs of 66 048 and 66 049 windows, which have a closed form"""
+    return [uniform_record(a, b) if name in ("1036x1028_checkerboard_inverse", "1032x1032_equal") else py_ssim(a, b) for name, a, b in trip_pairs()]
+
+
+@functools.lru_cache(maxsize=None)
+def fill_pairs():
+    """[(name, a, b)]: every content of every shape of FILL_SHAPES, shape by shape in turn"""
+    by = {s: list(contents(*s).items()) for s in FILL_SHAPES}
+    return [("%dx%d_%s" % (s + (by[s][k][0],)),) + by[s][k][1] for k in range(5) for s in FILL_SHAPES]
+
+
+@functools.lru_cache(maxsize=None)
+def fill_expected():
+    return [py_ssim(a, b) for _, a, b in fill_pairs()]
+
+
+#: PlSsimRecord / pngloss_hip_ssim as a numpy record (D.records_array, D.dicts_array)
+RECORD_DTYPE = np.dtype([("windows", "<u8"), ("sum_q16", "<i8", (4,)), ("min_q16", "<i4", (4,)), ("reserved", "<u8")])
+
+
+# ---- the launch shape of pl_ssim (pl_ssim_core.h: pls_grid_blocks, PLS_MAX_IMAGES), restated ----
+
+#: a launch takes at most this many images; a larger batch is launched in slices
+MAX_IMAGES = 65535
+
+
+def grid_blocks(n, max_tiles):
+    """workgroups per image of a launch of n images whose largest has max_tiles tiles: min(max_tiles, max(8, ceil(2048 / n))), at least 1"""
+    assert n >= 1
+    return max(1, min(max_tiles, max(8, -(-2048 // n))))
+
+
+#: the rule at the points the CPU test pins, written out: {max_tiles: blocks for n = GRID_N}
+GRID_N = [1, 5, 59, 255, 256, 257, 300, 65535]
+GRID_POINTS = {
+    0: [1, 1, 1, 1, 1, 1, 1, 1],
+    1: [1, 1, 1, 1, 1, 1, 1, 1],
+    8: [8, 8, 8, 8, 8, 8, 8, 8],
+    9: [9, 9, 9, 9, 8, 8, 8, 8],
+    288: [288, 288, 35, 9, 8, 8, 8, 8],
+    4096: [2048, 410, 35, 9, 8, 8, 8, 8],
+}
+
+
+def tiles_of(w, h):
+    nx, ny = geometry(w, h)
+    return -(-nx // 32) * -(-ny // 8)
+
+
+def trips(n, shapes, w, h):
+    """how many tiles each workgroup of a w x h image takes in a launch of n images whose sizes are `shapes` ((w, h) each): one count per workgroup"""
+    blocks = grid_blocks(n, max(tiles_of(*s) for s in shapes))
+    return [len(range(b, tiles_of(w, h), blocks)) for b in range(blocks)]
+
+
+def run_ssim_grid(exe, points):
+    """points: (n, max_tiles) each.  Returns (PLS_MAX_IMAGES, [pls_grid_blocks(n, max_tiles)]) from the C code"""
+    lines = _run(exe, ["grid"] + [str(v) for p in points for v in p], len(points) + 1)
+    return int(lines[0]), [int(x) for x in lines[1:]]
+
+
 # ---- the search with the SSIM condition (pngloss_hip_optimize_batch_target2) ----
 
 def py_accept2(min_psnr_db, max_abs_error, min_ssim, rec, srec, status, bpp):
@@ -223,12 +324,15 @@ def _run(exe, args, n):
 
 
 def run_ssim_host(exe, tmp_path, cases):
-    """cases: (a, b, a_offset, b_offset, nthreads) with a, b (H, W, 4) uint8.  Returns one record dict per case; fails on any sanitizer report."""
+    """cases: (a, b, a_offset, b_offset, nthreads[, blocks[, visible]]) with a, b (H, W, 4) uint8; blocks = B > 0 runs the tiles as B workgroups
+    of the kernel would, each over one table that is never cleared between its tiles, visible = 1 the visible instantiation
+    (tests/c/ssim_host.cpp).  Returns one record dict per case; fails on any sanitizer report."""
     path = str(tmp_path / "cases.bin")
     with open(path, "wb") as fh:
         fh.write(np.array([len(cases)], np.uint64).tobytes())
-        for a, b, oa, ob, nt in cases:
-            fh.write(np.array([a.shape[1], a.shape[0], oa, ob, nt], np.uint64).tobytes())
+        for a, b, oa, ob, nt, *more in cases:
+            blocks, visible = (list(more) + [0, 0])[:2]
+            fh.write(np.array([a.shape[1], a.shape[0], oa, ob, nt, blocks, visible], np.uint64).tobytes())
             fh.write(np.ascontiguousarray(a).tobytes())
             fh.write(np.ascontiguousarray(b).tobytes())
     recs = []

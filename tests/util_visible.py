@@ -161,6 +161,55 @@ def edge_pairs():
     return out
 
 
+@functools.lru_cache(maxsize=None)
+def trip_pairs():
+    """[(name, a, b)], read-only: the pairs of S.trip_pairs() that take a workgroup of pl_ssim past its first tile -- the noise pairs with holes and a
+    band of invisible windows at the right edge -- and a 300 x 77 pair invisible in both images (tiles to visit, no window to count)"""
+    rng = np.random.default_rng(47)
+    out = []
+    for name, a, b in S.trip_pairs():
+        if name.split("_")[1] in ("noise", "near"):
+            a, b = a.copy(), b.copy()
+            _holes(rng, a, b)
+            a[:, a.shape[1] - 20:, 3] = 0; b[:, b.shape[1] - 20:, 3] = 0
+        out.append((name, a, b))
+    a, b = (x.copy() for x in S.contents(300, 77, seed=6)["noise"])
+    a[..., 3] = 0; b[..., 3] = 0
+    out.append(("300x77_invisible", a, b))
+    for _, a, b in out:
+        a.setflags(write=False); b.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def trip_expected():
+    """(distortion record, SSIM record) of trip_pairs() in visible mode; the two uniform pairs by S.uniform_record's closed form (every window of
+    theirs holds a visible pixel; tests/test_visible_host.py checks it against py_ssim on the whole pair)"""
+    return [(np_distortion(a, b), S.uniform_record(a, b, py_ssim) if name in ("1036x1028_checkerboard_inverse", "1032x1032_equal") else py_ssim(a, b))
+            for name, a, b in trip_pairs()]
+
+
+#: pairs of a call that a single launch cannot take (D.MAX_IMAGES = 65535 images a launch): pair i is split_pool()[i % 7]
+SPLIT_N = 65540
+
+
+@functools.lru_cache(maxsize=None)
+def split_pool():
+    """[(name, a, b)], read-only: seven small pairs of seven different distortion records -- 1x1, 3x1, 8x8 (one window), 12x12 (four),
+    13x9 (two), 16x8 with holes, and one without pixels"""
+    rng = np.random.default_rng(53)
+    out = []
+    for w, h in ((1, 1), (3, 1), (8, 8), (12, 12), (13, 9), (16, 8), (0, 0)):
+        a, b = _pair(rng, w, h)
+        if a.size:
+            a[..., 3] |= 1                                  # visible: the all-pixel and the visible pixel counts agree but for the holes
+        if (w, h) == (16, 8):
+            _holes(rng, a, b)
+        a.setflags(write=False); b.setflags(write=False)
+        out.append(("%dx%d" % (w, h), a, b))
+    return out
+
+
 # ---- the images of the batch and search tests, and the CPU oracle on them ----
 
 BATCH_SHAPES = [(64, 48), (96, 64), (40, 8)]
