@@ -219,6 +219,14 @@ double pngloss_hip_last_total_ms(const pngloss_hip_ctx *ctx);
 /* Final 256-bin symbol histogram of image `index` of the last finished batch (host buffer of 256 uint32). */
 int pngloss_hip_last_histogram(pngloss_hip_ctx *ctx, size_t index, uint32_t *hist256);
 
+/* The tables the row engines break ties with (optimize_state.c:228-231), of image `index` of the last finished batch, as the device holds them:
+ * freq[f * 256 + s] is the reference's original_frequency[f][s] (f = none, sub, up, average, paeth) over the image in its byte-per-pixel class,
+ * rank[f * 256 + s] the number of s' with freq[f][s'] < freq[f][s].  Host buffers of 5 * 256 uint32 each; either may be NULL, not both.  Refused
+ * (PNGLOSS_INVALID_ARGUMENT) where pngloss_hip_last_histogram is: while a batch is pending, for an index out of range, after a target or size
+ * search; the index follows the chunks of a host window in the same way.  The row-statistics engine (strength 0) keeps no ranks: asking for `rank`
+ * of an image it took is refused as well.  For tests and diagnosis: two copies from the device, nothing on the path of a batch. */
+int pngloss_hip_last_original_tables(pngloss_hip_ctx *ctx, size_t index, uint32_t *freq, uint32_t *rank);   /* [5][256] each; either may be NULL, not both */
+
 /* ---- How lossy a run was, measured on the device (no reference equivalent: the reference tool reports file sizes only).  The optimiser works in
  * place, so the original is gone before a caller could compare -- and on the fast paths (device-resident batches, frames handed over by
  * pngloss_hip_png_decode_batch_device[_z], PNGLOSS_HIP_Z_STREAM_ONLY) original and result never exist side by side on the host.  With the option

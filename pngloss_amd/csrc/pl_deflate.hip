@@ -339,7 +339,9 @@ size_t pl_deflate_bound(uint32_t width, uint32_t height)
 }
 
 namespace {
-/* the images in groups of at most PL_DEFLATE_MAX_STREAM bytes of scanlines: written (into `written`, indexed like imgs) or measured (into `measured`) */
+constexpr uint64_t DFL_MAX_GROUP_BLOCKS = 65535;        /* gridDim.y */
+static_assert(PL_DEFLATE_MAX_STREAM / PL_DEFLATE_BLOCK_BYTES <= DFL_MAX_GROUP_BLOCKS, "one image's deflate blocks must fit one launch");
+/* the images in groups of at most PL_DEFLATE_MAX_STREAM bytes of scanlines and DFL_MAX_GROUP_BLOCKS deflate blocks: written (into `written`, indexed like imgs) or measured (into `measured`) */
 hipError_t deflate_in_groups(const pl_deflate_image *imgs, size_t n, pl_deflate_image *written, PlSizeRecord *measured, hipStream_t stream)
 {
     dfl_params prm = { PL_DEFLATE_MAX_CHAIN, DFL_KEY_BYTES, PL_DEFLATE_BLOCK_BYTES };
@@ -349,13 +351,17 @@ hipError_t deflate_in_groups(const pl_deflate_image *imgs, size_t n, pl_deflate_
     if (const char *e = std::getenv("PNGLOSS_HIP_DEFLATE_GROUP_BYTES")) group_bytes = std::min<uint64_t>(PL_DEFLATE_MAX_STREAM, std::max(1ll, std::atoll(e)));
     size_t i = 0;
     while (i < n) {
-        uint64_t bytes = 0;
+        uint64_t bytes = 0, blocks = 0;
         size_t j = i;
         while (j < n) {
             const uint64_t len = ((uint64_t)imgs[j].rowbytes + 1u) * imgs[j].height;
             if (len > PL_DEFLATE_MAX_STREAM) return hipErrorInvalidValue;   /* one image beyond 32-bit positions */
-            if (j > i && bytes + len > group_bytes) break;
+            /* dfl_pack, dfl_near and dfl_keys have the group's deflate blocks in gridDim.y: a group ends before it holds more than DFL_MAX_GROUP_BLOCKS
+             * (one image never has that many: PL_DEFLATE_MAX_STREAM / PL_DEFLATE_BLOCK_BYTES blocks at the most) */
+            const uint64_t nb = (len + prm.block_bytes - 1) / prm.block_bytes;
+            if (j > i && (bytes + len > group_bytes || blocks + nb > DFL_MAX_GROUP_BLOCKS)) break;
             bytes += len;
+            blocks += nb;
             ++j;
         }
         const hipError_t rc = deflate_group(imgs + i, j - i, prm, stream, written ? written + i : nullptr, measured ? measured + i : nullptr);

@@ -13,6 +13,7 @@
  * Both are pure streaming kernels: HBM-bound, ~4 B/px read + <=4 B/px written (the previous row comes from L2).
  */
 #include "pl_device.h"
+#include "pl_prepost_core.h"
 
 namespace {
 
@@ -153,7 +154,10 @@ hipError_t pl_launch_emit(const PlJob *d_jobs, const PlJob *h_jobs, size_t n, hi
     if (!any) return hipSuccess;
     size_t blocks = (max_px + (size_t)kThreads * 16 - 1) / ((size_t)kThreads * 16);
     if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(pl_emit_classify, dim3((unsigned)blocks, (unsigned)n), dim3(kThreads), 0, stream, d_jobs);
-    hipLaunchKernelGGL(pl_emit_rows, dim3(max_h, (unsigned)n), dim3(kThreads), 0, stream, d_jobs);
+    /* blockIdx.y = image: a launch takes PLP_MAX_IMAGES of them and starts at its own jobs */
+    for (size_t first = 0; first < n; first += PLP_MAX_IMAGES)
+        hipLaunchKernelGGL(pl_emit_classify, dim3((unsigned)blocks, (unsigned)plp_slice(n, first)), dim3(kThreads), 0, stream, d_jobs + first);
+    for (size_t first = 0; first < n; first += PLP_MAX_IMAGES)
+        hipLaunchKernelGGL(pl_emit_rows, dim3(max_h, (unsigned)plp_slice(n, first)), dim3(kThreads), 0, stream, d_jobs + first);
     return hipGetLastError();
 }

@@ -595,6 +595,17 @@ int pngloss_hip_last_histogram(pngloss_hip_ctx *ctx, size_t index, uint32_t *his
     return PNGLOSS_SUCCESS;
 }
 
+int pngloss_hip_last_original_tables(pngloss_hip_ctx *ctx, size_t index, uint32_t *freq, uint32_t *rank)
+{
+    ctx = chunk_of(ctx, index);
+    if (!ctx || (!freq && !rank) || index >= ctx->n_last || ctx->pending) return PNGLOSS_INVALID_ARGUMENT;
+    if (rank && ctx->engine[index] == PLR_ENGINE_ROWS) return PNGLOSS_INVALID_ARGUMENT;      /* (pl_rank is not run for that engine) */
+    PL_CHECK(hipSetDevice(ctx->device));
+    if (freq) PL_CHECK(hipMemcpy(freq, ctx->h_jobs[index].orig_hist, sizeof(uint32_t) * PL_NFILT * PL_NSYM, hipMemcpyDeviceToHost));
+    if (rank) PL_CHECK(hipMemcpy(rank, ctx->h_jobs[index].orig_rank, sizeof(uint32_t) * PL_NFILT * PL_NSYM, hipMemcpyDeviceToHost));
+    return PNGLOSS_SUCCESS;
+}
+
 int pngloss_hip_last_distortion(pngloss_hip_ctx *ctx, size_t index, pngloss_hip_distortion *out) { return last_record(ctx, index, out, &pngloss_hip_ctx::distortion); }
 int pngloss_hip_last_ssim(pngloss_hip_ctx *ctx, size_t index, pngloss_hip_ssim *out) { return last_record(ctx, index, out, &pngloss_hip_ctx::ssim); }
 int pngloss_hip_last_palette(pngloss_hip_ctx *ctx, size_t index, pngloss_hip_palette *out) { return last_record(ctx, index, out, &pngloss_hip_ctx::palette); }

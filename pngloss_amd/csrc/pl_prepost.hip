@@ -13,11 +13,12 @@
  * read back from PlJob::flags by every later kernel, so the host never synchronises inside the pipeline.
  */
 #include "pl_device.h"
+#include "pl_prepost_core.h"
 #include <cstdlib>
 
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = PLP_THREADS;
 
 __global__ __launch_bounds__(kThreads) void pl_init(const PlJob *jobs)
 {
@@ -124,61 +125,24 @@ __global__ __launch_bounds__(kThreads) void pl_unpack(const PlJob *jobs)
  * images put most residuals into a handful of bins, a wave's lanes would serialise on one word otherwise); a thread takes four
  * neighbouring pixels (one 16-byte load per row, left / diagonal neighbours from registers); sub, up and average residuals of the
  * four channel bytes are taken in one 32-bit word (byte-wise arithmetic without carries across bytes). */
-__device__ __forceinline__ uint32_t pl_sub4(uint32_t a, uint32_t b)      /* per byte (a - b) mod 256 */
-{
-    return ((a | 0x80808080u) - (b & 0x7f7f7f7fu)) ^ (~(a ^ b) & 0x80808080u);
-}
-__device__ __forceinline__ uint32_t pl_avg4(uint32_t a, uint32_t b)      /* per byte floor((a + b) / 2) */
-{
-    return (a & b) + (((a ^ b) & 0xfefefefeu) >> 1);
-}
 template <int REP, int NCH>
 __device__ __forceinline__ void pl_hist_count(uint32_t *mine, uint32_t here, uint32_t left, uint32_t above, uint32_t diag)
 {
-    const uint32_t r1 = pl_sub4(here, left), r2 = pl_sub4(here, above), r3 = pl_sub4(here, pl_avg4(above, left));
+    const PlpResidual r = plp_residual(here, left, above);
 #pragma unroll
     for (int c = 0; c < NCH; c++) {
-        const int hv = (here >> (8 * c)) & 255, lv = (left >> (8 * c)) & 255;
-        const int av = (above >> (8 * c)) & 255, dv = (diag >> (8 * c)) & 255;
-        atomicAdd(&mine[(0 * PL_NSYM + (uint32_t)hv) * REP], 1u);
-        atomicAdd(&mine[(1 * PL_NSYM + ((r1 >> (8 * c)) & 255u)) * REP], 1u);
-        atomicAdd(&mine[(2 * PL_NSYM + ((r2 >> (8 * c)) & 255u)) * REP], 1u);
-        atomicAdd(&mine[(3 * PL_NSYM + ((r3 >> (8 * c)) & 255u)) * REP], 1u);
-        atomicAdd(&mine[(4 * PL_NSYM + (uint32_t)((hv - pl_paeth(av, dv, lv)) & 255)) * REP], 1u);
+        uint32_t bin[PL_NFILT];
+        plp_bins(bin, c, here, left, above, diag, r);
+#pragma unroll
+        for (int f = 0; f < PL_NFILT; f++) atomicAdd(&mine[((uint32_t)f * PL_NSYM + bin[f]) * REP], 1u);
     }
 }
+/* (pl_prepost_core.h has the loop: the quad loader or the pixel loader, at the stride of the image's workgroups) */
 template <int REP, int NT, int NCH>
 __device__ __forceinline__ void pl_hist_loop(uint32_t *mine, const uint32_t *__restrict__ img, uint32_t W, size_t n)
 {
-    if (!(W & 3u) && !(reinterpret_cast<uintptr_t>(img) & 15u) && n < 0xffffffffull) {
-        /* four pixels per thread and step; a row is a whole number of such quads, so a quad never straddles two rows */
-        const uint4 *__restrict__ img4 = reinterpret_cast<const uint4 *>(img);
-        const uint32_t W4 = W >> 2, nq = (uint32_t)(n >> 2);
-        for (uint32_t q = blockIdx.x * NT + threadIdx.x; q < nq; q += gridDim.x * NT) {
-            const uint32_t qx = q % W4;
-            const bool has_up = q >= W4;
-            const uint4 hq = img4[q];
-            uint4 aq = make_uint4(0u, 0u, 0u, 0u);
-            uint32_t left = 0u, diag = 0u;
-            if (has_up) aq = img4[q - W4];
-            if (qx) left = img[(size_t)q * 4 - 1];
-            if (has_up && qx) diag = img[(size_t)(q - W4) * 4 - 1];
-            pl_hist_count<REP, NCH>(mine, hq.x, left, aq.x, diag);
-            pl_hist_count<REP, NCH>(mine, hq.y, hq.x, aq.y, aq.x);
-            pl_hist_count<REP, NCH>(mine, hq.z, hq.y, aq.z, aq.y);
-            pl_hist_count<REP, NCH>(mine, hq.w, hq.z, aq.w, aq.z);
-        }
-    } else {
-        for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n; i += (size_t)gridDim.x * NT) {
-            const uint32_t x = (uint32_t)(i % W);
-            const bool has_up = i >= W;
-            const uint32_t here = img[i];
-            const uint32_t left = x ? img[i - 1] : 0u;
-            const uint32_t above = has_up ? img[i - W] : 0u;
-            const uint32_t diag = (has_up && x) ? img[i - W - 1] : 0u;
-            pl_hist_count<REP, NCH>(mine, here, left, above, diag);
-        }
-    }
+    plp_hist_thread(img, W, n, blockIdx.x, threadIdx.x, gridDim.x, NT,
+                    [mine](uint32_t here, uint32_t left, uint32_t above, uint32_t diag) { pl_hist_count<REP, NCH>(mine, here, left, above, diag); });
 }
 template <int REP, int NT>
 __global__ __launch_bounds__(NT) void pl_hist(const PlJob *__restrict__ jobs)
@@ -204,8 +168,7 @@ __global__ __launch_bounds__(NT) void pl_hist(const PlJob *__restrict__ jobs)
     }
 }
 
-/* rank[f][b] = #{ b' : orig_hist[f][b'] < orig_hist[f][b] }  (0..255): a < b  <=>  rank(a) < rank(b), and
- * a == b <=> rank(a) == rank(b), which is all optimize_state.c:228-235 uses the secondary key for. */
+/* rank[f][b] = #{ b' : orig_hist[f][b'] < orig_hist[f][b] }  (0..255; pl_prepost_core.h:plp_rank says why that is enough) */
 __global__ __launch_bounds__(PL_NSYM) void pl_rank(const PlJob *jobs)
 {
     __shared__ uint32_t h[PL_NSYM];
@@ -215,56 +178,49 @@ __global__ __launch_bounds__(PL_NSYM) void pl_rank(const PlJob *jobs)
         __syncthreads();
         h[threadIdx.x] = mine;
         __syncthreads();
-        uint32_t r = 0;
-        for (int k = 0; k < PL_NSYM; k++) r += h[k] < mine;
-        j.orig_rank[f * PL_NSYM + threadIdx.x] = r;
+        j.orig_rank[f * PL_NSYM + threadIdx.x] = plp_rank(h, mine);
     }
 }
 
-inline dim3 batch_grid(const PlJob *h_jobs, size_t n, uint32_t px_per_thread)
+size_t batch_max_px(const PlJob *h_jobs, size_t n)
 {
-    size_t max_px = 1;
-    for (size_t i = 0; i < n; i++) {
-        size_t px = (size_t)h_jobs[i].width * h_jobs[i].height;
-        if (px > max_px) max_px = px;
-    }
-    size_t blocks = (max_px + (size_t)kThreads * px_per_thread - 1) / ((size_t)kThreads * px_per_thread);
-    /* enough workgroups to fill 256 CUs several times over, but never more than needed for the batch */
-    size_t cap = (2048 + n - 1) / n;
-    if (cap < 8) cap = 8;
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    return dim3((unsigned)blocks, (unsigned)n, 1);
-}
-
-
-
-/* pl_hist: 16 replicas (80 KB) and 1024 threads, one workgroup per CU, three rounds of workgroups on a large frame -- measured
- * against 4 / 8 replicas, 256 / 512 threads and 256 ... 2048 workgroups in profiles/r03_hist_variants.txt */
-template <int REP, int NT>
-hipError_t launch_hist_v(const PlJob *d_jobs, const PlJob *h_jobs, size_t n, hipStream_t stream, unsigned wgs_per_image_cap)
-{
-    constexpr size_t lds = (size_t)REP * PL_NFILT * PL_NSYM * sizeof(uint32_t);
-    static std::atomic<unsigned> optin{ 0 };                  /* (per device: pl_lds_optin) */
-    if (lds > 65536) { const hipError_t attr = pl_lds_optin(reinterpret_cast<const void *>(&pl_hist<REP, NT>), lds, optin); if (attr != hipSuccess) return attr; }
     size_t max_px = 1;
     for (size_t i = 0; i < n; i++) {
         const size_t px = (size_t)h_jobs[i].width * h_jobs[i].height;
         if (px > max_px) max_px = px;
     }
-    size_t blocks = (max_px + (size_t)NT * 16 - 1) / ((size_t)NT * 16);
-    size_t cap = (wgs_per_image_cap + n - 1) / n;
-    if (cap < 4) cap = 4;
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL((pl_hist<REP, NT>), dim3((unsigned)blocks, (unsigned)n), dim3(NT), lds, stream, d_jobs);
+    return max_px;
+}
+
+/* one of pl_classify, pl_repack, pl_unpack over the batch: blockIdx.y = image, so a launch takes PLP_MAX_IMAGES of them and starts at its own jobs;
+ * the workgroups per image are pl_prepost_core.h:plp_batch_blocks of the slice */
+void launch_batch(void (*kernel)(const PlJob *), const PlJob *d_jobs, size_t n, size_t max_px, uint32_t px_per_thread, hipStream_t stream)
+{
+    for (size_t first = 0; first < n; first += PLP_MAX_IMAGES) {
+        const size_t m = plp_slice(n, first);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)plp_batch_blocks(m, max_px, px_per_thread), (unsigned)m, 1), dim3(kThreads), 0, stream, d_jobs + first);
+    }
+}
+
+/* pl_hist: 16 replicas (80 KB) and 1024 threads, one workgroup per CU, three rounds of workgroups on a large frame -- measured
+ * against 4 / 8 replicas, 256 / 512 threads and 256 ... 2048 workgroups in profiles/r03_hist_variants.txt */
+template <int REP, int NT>
+hipError_t launch_hist_v(const PlJob *d_jobs, size_t n, size_t max_px, hipStream_t stream, unsigned wgs_per_image_cap)
+{
+    constexpr size_t lds = (size_t)REP * PL_NFILT * PL_NSYM * sizeof(uint32_t);
+    static std::atomic<unsigned> optin{ 0 };                  /* (per device: pl_lds_optin) */
+    if (lds > 65536) { const hipError_t attr = pl_lds_optin(reinterpret_cast<const void *>(&pl_hist<REP, NT>), lds, optin); if (attr != hipSuccess) return attr; }
+    for (size_t first = 0; first < n; first += PLP_MAX_IMAGES) {
+        const size_t m = plp_slice(n, first);
+        hipLaunchKernelGGL((pl_hist<REP, NT>), dim3((unsigned)plp_hist_blocks(m, max_px, NT, wgs_per_image_cap), (unsigned)m), dim3(NT), lds, stream, d_jobs + first);
+    }
     return hipGetLastError();
 }
-hipError_t launch_hist(const PlJob *d_jobs, const PlJob *h_jobs, size_t n, hipStream_t stream)
+hipError_t launch_hist(const PlJob *d_jobs, size_t n, size_t max_px, hipStream_t stream)
 {
     static const int variant = [] { const char *e = getenv("PNGLOSS_HIP_HIST"); return e ? atoi(e) : 0; }();
-    if (variant == 1) return launch_hist_v<8, 256>(d_jobs, h_jobs, n, stream, 2048);      /* round 2's shape, for comparison */
-    return launch_hist_v<16, 1024>(d_jobs, h_jobs, n, stream, 768);
+    if (variant == 1) return launch_hist_v<8, 256>(d_jobs, n, max_px, stream, 2048);      /* round 2's shape, for comparison */
+    return launch_hist_v<16, 1024>(d_jobs, n, max_px, stream, 768);
 }
 
 } // namespace
@@ -274,11 +230,12 @@ hipError_t pl_launch_prepare(const PlJob *d_jobs, const PlJob *h_jobs, size_t n,
     if (!n) return hipSuccess;
     hipError_t e = hipSuccess;
     hipLaunchKernelGGL(pl_init, dim3((unsigned)n), dim3(kThreads), 0, stream, d_jobs);
-    hipLaunchKernelGGL(pl_classify, batch_grid(h_jobs, n, 16), dim3(kThreads), 0, stream, d_jobs);
-    hipLaunchKernelGGL(pl_repack, batch_grid(h_jobs, n, 8), dim3(kThreads), 0, stream, d_jobs);
+    const size_t max_px = batch_max_px(h_jobs, n);
+    launch_batch(pl_classify, d_jobs, n, max_px, 16, stream);
+    launch_batch(pl_repack, d_jobs, n, max_px, 8, stream);
     if (!with_hist) return hipGetLastError();
     {
-        e = launch_hist(d_jobs, h_jobs, n, stream);
+        e = launch_hist(d_jobs, n, max_px, stream);
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(pl_rank, dim3((unsigned)n), dim3(PL_NSYM), 0, stream, d_jobs);
@@ -288,6 +245,6 @@ hipError_t pl_launch_prepare(const PlJob *d_jobs, const PlJob *h_jobs, size_t n,
 hipError_t pl_launch_finish(const PlJob *d_jobs, const PlJob *h_jobs, size_t n, hipStream_t stream)
 {
     if (!n) return hipSuccess;
-    hipLaunchKernelGGL(pl_unpack, batch_grid(h_jobs, n, 8), dim3(kThreads), 0, stream, d_jobs);
+    launch_batch(pl_unpack, d_jobs, n, batch_max_px(h_jobs, n), 8, stream);
     return hipGetLastError();
 }

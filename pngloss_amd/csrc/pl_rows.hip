@@ -24,6 +24,7 @@
  * an 8192 x 8192 frame against this file's ~4 Gpixels/s (profiles/r05_rows_engine.txt).  Results are the reference's bit for bit either way.
  */
 #include "pl_device.h"
+#include "pl_prepost_core.h"
 
 namespace {
 
@@ -182,7 +183,7 @@ __global__ __launch_bounds__(64) void pl_rows_decide(const PlJob *__restrict__ j
 #pragma unroll
     for (int f = 0; f < PL_NFILT; f++) {
 #pragma unroll
-        for (int q = 0; q < 4; q++) j.orig_hist[f * PL_NSYM + lane + 64 * q] = O[f][q];                /* (pl_hist is not run for this engine: pngloss_hip_last_histogram reads this) */
+        for (int q = 0; q < 4; q++) j.orig_hist[f * PL_NSYM + lane + 64 * q] = O[f][q];                /* (pl_hist is not run for this engine: pngloss_hip_last_original_tables reads this) */
     }
     nz = rows_wave_sum(nz);
     if (lane < PLR_WORDS) { j.result[lane] = 0; }
@@ -201,7 +202,9 @@ hipError_t pl_launch_rows(const PlJob *d_jobs, const PlJob *h_jobs, size_t n, hi
     if (!n) return hipSuccess;
     uint32_t max_h = 0;
     for (size_t i = 0; i < n; i++) max_h = h_jobs[i].height > max_h ? h_jobs[i].height : max_h;
-    if (max_h) hipLaunchKernelGGL(pl_rows_stats, dim3(max_h, (unsigned)n), dim3(kStatThreads), 0, stream, d_jobs);
+    /* blockIdx.y = image: a launch takes PLP_MAX_IMAGES of them and starts at its own jobs */
+    for (size_t first = 0; max_h && first < n; first += PLP_MAX_IMAGES)
+        hipLaunchKernelGGL(pl_rows_stats, dim3(max_h, (unsigned)plp_slice(n, first)), dim3(kStatThreads), 0, stream, d_jobs + first);
     hipLaunchKernelGGL(pl_rows_decide, dim3((unsigned)n), dim3(64), 0, stream, d_jobs);
     return hipGetLastError();
 }

@@ -263,6 +263,7 @@ def _prototypes():
         "pngloss_hip_last_engine_ms": (dbl, [vp]),
         "pngloss_hip_last_total_ms": (dbl, [vp]),
         "pngloss_hip_last_histogram": (i, [vp, sz, vp]),
+        "pngloss_hip_last_original_tables": (i, [vp, sz, vp, vp]),
         "pngloss_hip_last_distortion": (i, [vp, sz, ptr(Distortion)]),
         "pngloss_hip_compare_batch": (i, [vp, ptr(ImagePair), sz, ptr(Distortion), vp]),
         "pngloss_hip_psnr_db": (dbl, [ptr(Distortion), u]),
@@ -812,6 +813,18 @@ class HipContext:
         h = np.zeros(256, np.uint32)
         _check(self._lib.pngloss_hip_last_histogram(self._ctx, index, h.ctypes.data_as(C.c_void_p)), "histogram")
         return h
+
+    def original_tables(self, index=0):
+        """pngloss_hip_last_original_tables: (freq, rank) of image `index` of the last finished batch, (5, 256) uint32 each: original_frequency and
+        the 8-bit ranks the row engines break ties with.  rank is None for an image the row-statistics engine took (it keeps none)."""
+        freq, rank = np.zeros((5, 256), np.uint32), np.zeros((5, 256), np.uint32)
+        _check(self._lib.pngloss_hip_last_original_tables(self._ctx, index, freq.ctypes.data_as(C.c_void_p), None), "original_tables")
+        a = (C.c_int32 * 8)()
+        _check(self._lib.pngloss_hip_last_engine_info(self._ctx, index, a), "engine_info")
+        if a[0] == 4:
+            return freq, None
+        _check(self._lib.pngloss_hip_last_original_tables(self._ctx, index, None, rank.ctypes.data_as(C.c_void_p)), "original_tables")
+        return freq, rank
 
 
 def source_digest():

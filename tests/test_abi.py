@@ -137,7 +137,7 @@ def test_the_layout_check_reports_a_dropped_field(tmp_path, name, field, moved):
 
 
 def test_every_function_of_the_header_has_its_prototype(declared):
-    assert len(HEADER_FUNCTIONS) == 48 and set(declared) == set(HEADER_FUNCTIONS) == set(L.PROTOTYPES)
+    assert len(HEADER_FUNCTIONS) == 49 and set(declared) == set(HEADER_FUNCTIONS) == set(L.PROTOTYPES)
     assert L.ABI_SYMBOLS == tuple(L.PROTOTYPES)
     assert declared["optimize_with_rows"] == ["i32", "ptr", "u32", "u32", "ptr", "bool", "u8", "i64"]      # (the C++ side tells the classes apart)
     assert declared["pngloss_hip_psnr_db"] == ["f64", "ptr", "u32"] and declared["pngloss_hip_pinned_free"] == ["void", "ptr"]
