@@ -146,6 +146,16 @@ hipError_t chain_attr()
 
 } // namespace
 
+#if SEG_EXPERIMENT_TAIL_PLACEMENT
+/* MEASUREMENT BUILD only (tools/enum_tail_placement.py): the records of seg_enum_body_k's tail waves, copied to `out`; returns their words, 0 on an error */
+extern "C" __attribute__((visibility("default"))) size_t pngloss_hip_debug_tail_placement(uint32_t *out, size_t words)
+{
+    const size_t n = sizeof(seg_tail_dbg) / sizeof(uint32_t);
+    if (!out || words < n || hipDeviceSynchronize() != hipSuccess) return 0;
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(seg_tail_dbg), sizeof(seg_tail_dbg)) == hipSuccess ? n : 0;
+}
+#endif
+
 hipError_t pl_seg_launch_resolve(const PlJob *d_jobs, SegJob *d_sj, size_t n, hipStream_t stream)
 {
     if (!n) return hipSuccess;

@@ -128,6 +128,20 @@ typedef SEG_AS_LDS uint16_t *seg_lds_u16;
 #define PLS_UNROLL
 #endif
 #define SEG_NFILT 5
+#ifndef SEG_EXPERIMENT_TAIL_PLACEMENT
+#define SEG_EXPERIMENT_TAIL_PLACEMENT 0   /* (1: MEASUREMENT BUILD, never shipped -- seg_enum_body_k records where the wave that walks the steps behind the dedupe sits and when that
+                                             phase begins and ends: one record per workgroup in a buffer of the build's own, written behind the phase; tools/enum_tail_placement.py
+                                             reads them, profiles/r11_enum_tail_placement.txt has what they said.  What the engine computes stays what it is.) */
+#endif
+#if SEG_EXPERIMENT_TAIL_PLACEMENT && defined(__HIPCC__)
+#define SEG_TAILDBG_ROWS 16               /* the launches of this many rows (y mod: a row attempted again overwrites its records), ... */
+#define SEG_TAILDBG_WGS 1024              /* ... the first this many workgroups of a launch, ... */
+#define SEG_TAILDBG_WORDS 12              /* ... words each: HW_ID and XCC_ID of the tail wave, the tail in 100 MHz ticks and in shader cycles, distinct states, the SIMD of every wave (two bits
+                                             each), HW_ID of wave 0, 1 << 31 | f | seg << 8 | chalf << 24, and the 100 MHz clock (low word) at the body's head, the tail's head and its end */
+static __device__ uint32_t seg_tail_dbg[SEG_TAILDBG_ROWS * SEG_TAILDBG_WGS * SEG_TAILDBG_WORDS];
+__device__ __forceinline__ uint32_t pls_hw_id() { uint32_t v; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(v)); return v; }
+__device__ __forceinline__ uint32_t pls_xcc_id() { uint32_t v; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v)); return v; }
+#endif
 #ifndef SEG_DEBUG_ROW
 #define SEG_DEBUG_ROW(kind, failed, winner, start_none)
 #endif
@@ -1007,6 +1021,9 @@ PLS_HD void seg_enum_body_k(const SegJob &j, const SegParams &P, const SegCtlVie
     const bool prof = (P.engine_flags & 1) != 0;
     unsigned long long te[5] = { 0, 0, 0, 0, 0 };
     if (prof) te[0] = PLS_CLOCK();
+#if SEG_EXPERIMENT_TAIL_PLACEMENT && defined(__HIP_DEVICE_COMPILE__)
+    const unsigned long long exp_head = wall_clock64();
+#endif
     PLS_THREADS(tid, NT) {
         if (tid < 8) trflag[tid] = 0u;
         for (int i = tid; i < 4 * SEG_HT; i += NT) ht[i] = 0xffffffffu;
@@ -1028,6 +1045,13 @@ PLS_HD void seg_enum_body_k(const SegJob &j, const SegParams &P, const SegCtlVie
             seg_pix_split4(px + tid * 4, vp, bpp, x0 - 1 + (uint32_t)tid, W);
             if ((bpp & 1u) == 0u && (px[tid * 4 + (bpp - 1u)].w >> 24)) PLS_ATOMIC_OR(&trflag[SEG_TF_TRANSPARENT], 1u);
         }
+#if SEG_EXPERIMENT_TAIL_PLACEMENT && defined(__HIP_DEVICE_COMPILE__)
+        if ((tid & 63) == 0) {
+            const uint32_t hw = pls_hw_id();
+            PLS_ATOMIC_OR(&trflag[SEG_TF_WSIMD], ((hw >> 4) & 3u) << (2 * (tid >> 6)));
+            if (tid == 0) trflag[SEG_TF_HWID0] = hw;
+        }
+#endif
     }
     PLS_SYNC();
     const bool trx = trflag[SEG_TF_TRANSPARENT] != 0u;
@@ -1095,6 +1119,10 @@ PLS_HD void seg_enum_body_k(const SegJob &j, const SegParams &P, const SegCtlVie
          * four SIMDs: waves x steps is the currency, the other waves end here) */
         uint32_t Dc[NCH];
         for (int k = 0; k < NCH; k++) Dc[k] = trflag[SEG_TF_NDISTINCT + k] < SEG_NSP ? trflag[SEG_TF_NDISTINCT + k] : SEG_NSP;
+#if SEG_EXPERIMENT_TAIL_PLACEMENT && defined(__HIP_DEVICE_COMPILE__)
+        unsigned long long tail_w0 = 0, tail_c0 = 0;
+        if (tid == 0) { tail_w0 = wall_clock64(); tail_c0 = clock64(); }
+#endif
         int lc = 0, i = tid;
         uint32_t D = Dc[0];
         PLS_UNROLL
@@ -1117,6 +1145,17 @@ PLS_HD void seg_enum_body_k(const SegJob &j, const SegParams &P, const SegCtlVie
             j.rout[slot] = (uint16_t)out;
             j.rst[slot] = bad ? 0xFFFFFFFFu : seg_state_pack(st);
         }
+#if SEG_EXPERIMENT_TAIL_PLACEMENT && defined(__HIP_DEVICE_COMPILE__)
+        if (tid == 0 && blockIdx.x < SEG_TAILDBG_WGS && blockIdx.y == 0) {        /* (behind the timed phase) */
+            const unsigned long long tail_c1 = clock64(), tail_w1 = wall_clock64();
+            uint32_t *r = seg_tail_dbg + ((size_t)(y % SEG_TAILDBG_ROWS) * SEG_TAILDBG_WGS + blockIdx.x) * SEG_TAILDBG_WORDS;
+            uint32_t nd = 0;
+            for (int k = 0; k < NCH; k++) nd += Dc[k];
+            r[0] = pls_hw_id(); r[1] = pls_xcc_id(); r[2] = (uint32_t)(tail_w1 - tail_w0); r[3] = (uint32_t)(tail_c1 - tail_c0);
+            r[4] = nd; r[5] = trflag[SEG_TF_WSIMD]; r[6] = trflag[SEG_TF_HWID0]; r[7] = 0x80000000u | (uint32_t)f | (uint32_t)seg << 8 | (uint32_t)chalf << 24;
+            r[8] = (uint32_t)exp_head; r[9] = (uint32_t)tail_w0; r[10] = (uint32_t)tail_w1; r[11] = 0u;
+        }
+#endif
         if (prof && tid == 0) {
             te[3] = PLS_CLOCK(); te[4] = te[3];
             for (int q = 0; q < PLR_SEG_ENUM_PHASES; q++) { PLS_ATOMIC_MAX(&j.result[PLR_SEG_ENUM_MAX + q], (int32_t)(te[q + 1] - te[q])); PLS_ATOMIC_ADD((uint32_t *)&j.result[PLR_SEG_ENUM_SUM + q], (uint32_t)(te[q + 1] - te[q])); }

@@ -180,7 +180,12 @@ PLS_HD void seg_dispatch_enum(const SegJob &j, const SegJob *rec, const SegParam
     constexpr unsigned halves = 4 / (NT / SEG_NSP), small_segs = NT / (4 * SEG_NSS);
     if (bx < nbig * max_nseg * halves) {
         const unsigned k = bx / (max_nseg * halves), r = bx % (max_nseg * halves), seg = r / halves, chalf = r % halves;
-        const unsigned f = small_ok ? (k == 0 ? 1u : (k == 1 ? 3u : 4u)) : k;
+        /* The candidates in the order paeth, avg, (up,) sub, (none): the LONGEST first.  The workgroups of a launch are handed out in the order of blockIdx, a CU of the
+         * headline row gets one of each candidate, and a SIMD issues for its oldest waves first: in the phase in which all eight waves of every workgroup step (the
+         * first steps and the dedupe) the workgroup dispatched last waits for the other two -- 3.4 / 4.0 / 5.9 us for the first / second / third of a CU, whichever
+         * candidate it is.  With sub first and paeth last, the launch ended with paeth's workgroups (5.9 + its 5.7 us behind the dedupe); with paeth first it ends
+         * with sub's, 1.1 us earlier (profiles/r11_enum_tail_placement.txt, table c): 14.60 -> 13.73 us a launch. */
+        const unsigned f = small_ok ? (k == 0 ? 4u : (k == 1 ? 3u : 1u)) : 4u - k;
         if (seg >= j.nseg) return;
         SEG_BODY(seg_enum_body)<NT>(j, P, seg_view_of(rec, par, (int)f), par, (int)f, (int)seg, (int)chalf, smem);
     } else if (bx < gx - SEG_NFILT) {

@@ -58,6 +58,8 @@
 /* trflag of seg_enum_body_k / seg_enum_seeded_body, [8] */
 enum { SEG_TF_TRANSPARENT = 0,    /* some pixel of the segment (seeded: of the window) is fully transparent */
        SEG_TF_NDISTINCT = 1,      /* + channel: distinct states (seeded: distinct entry states) of the workgroup's channel */
+       SEG_TF_WSIMD = 6,          /* (seg_enum_body_k, SEG_EXPERIMENT_TAIL_PLACEMENT only) the SIMD of every wave, two bits each */
+       SEG_TF_HWID0 = 7,          /* (seg_enum_body_k, SEG_EXPERIMENT_TAIL_PLACEMENT only) HW_ID of wave 0 */
        SEG_TF_NRUNIN = 3 };       /* + channel (seeded, two stages, a channel pair per workgroup: the slots of the channels it does not have): distinct states after the run-in's first steps */
 /* misc of seg_enum_unit_body, [128] */
 enum { SEG_UM_TRANSPARENT = 0,    /* transparent pixel seen */
