@@ -54,7 +54,7 @@ const char cli_usage_text[] =
     "Output names end in \"-loss.png\" or your --ext; with \"-\" the image goes stdin -> stdout.\n"
     "Existing outputs are skipped unless --force is given.\n";
 
-enum { OPT_EXT = 256, OPT_NO_FORCE, OPT_SKIP_LARGER, OPT_STRIP, OPT_GPU_DEFLATE, OPT_GPU_READ, OPT_DISTORTION, OPT_TARGET_PSNR, OPT_MAX_ERROR, OPT_SSIM, OPT_TARGET_SSIM, OPT_TARGET_SIZE, OPT_VISIBLE, OPT_INDEXED, OPT_COLORS, OPT_DITHER };
+enum { OPT_EXT = 256, OPT_NO_FORCE, OPT_SKIP_LARGER, OPT_STRIP, OPT_GPU_DEFLATE, OPT_GPU_READ, OPT_DISTORTION, OPT_TARGET_PSNR, OPT_MAX_ERROR, OPT_SSIM, OPT_TARGET_SSIM, OPT_TARGET_SIZE, OPT_VISIBLE, OPT_INDEXED, OPT_COLORS, OPT_DITHER, OPT_COLORS_PSNR, OPT_COLORS_MAX_ERROR };
 
 static bool parse_number(const char *text, unsigned long *out)
 {
@@ -118,6 +118,8 @@ pngloss_error cli_options_parse(int argc, char **argv, struct cli_options *o, FI
         { "indexed", no_argument, NULL, OPT_INDEXED },
         { "colors", required_argument, NULL, OPT_COLORS },
         { "dither", no_argument, NULL, OPT_DITHER },
+        { "colors-psnr", required_argument, NULL, OPT_COLORS_PSNR },
+        { "colors-max-error", required_argument, NULL, OPT_COLORS_MAX_ERROR },
         { NULL, 0, NULL, 0 },
     };
     memset(o, 0, sizeof *o);
@@ -160,6 +162,14 @@ pngloss_error cli_options_parse(int argc, char **argv, struct cli_options *o, FI
             o->have_colors = true;
             break;
         case OPT_DITHER: o->dither = true; break;
+        case OPT_COLORS_PSNR:
+            o->have_colors_psnr = true;
+            o->colors_psnr_ok = parse_decibels(optarg, &o->colors_psnr);
+            break;
+        case OPT_COLORS_MAX_ERROR:
+            o->have_colors_max_error = true;
+            o->colors_max_error_ok = parse_number(optarg, &o->colors_max_error);
+            break;
         case 'h': o->help = true; break;
         case 'V': o->version = true; break;
         case 'o':
@@ -228,5 +238,13 @@ pngloss_error cli_options_check(const struct cli_options *o, FILE *err)
         fputs("No input files specified.\n", err);
         return MISSING_ARGUMENT;
     }
+    /* the colour-count search of --colors: behind every older rule, so that what those answer stays what it was */
+    if (o->have_colors_psnr && !o->have_colors) return refuse(err, "--colors-psnr requires --colors.\n");
+    if (o->have_colors_max_error && !o->have_colors) return refuse(err, "--colors-max-error requires --colors.\n");
+    if (o->have_colors_psnr && !o->colors_psnr_ok) return refuse(err, "--colors-psnr requires a numeric argument\n");
+    if (o->have_colors_psnr && !(o->colors_psnr > 0.0)) return refuse(err, "Must specify a colour PSNR target above 0 dB.\n");
+    if (o->have_colors_max_error && !o->colors_max_error_ok) return refuse(err, "--colors-max-error requires a numeric argument\n");
+    if (o->have_colors_max_error && (o->colors_max_error < 1 || o->colors_max_error > 255))
+        return refuse(err, "Must specify a largest colour channel error in the range 1-255.\n");
     return SUCCESS;
 }

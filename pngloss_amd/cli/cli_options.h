@@ -37,6 +37,14 @@ struct cli_options {
     bool have_colors;          /* --colors N: every image is quantised to at most N colours first (pngloss_hip_multi_quantize_batch_host), then written at */
     unsigned long colors;      /* strength 0 with --indexed: the palette is the lossy step.  Not in the usage text (DESIGN.md 9.1b says why) */
     bool dither;               /* --dither: --colors remaps with Floyd-Steinberg error diffusion (pngloss_hip_multi_quantize_batch_host2).  Not in the usage text either */
+    /* --colors-psnr DB, --colors-max-error E: with --colors M, the colour count is searched per file, at most M: the fewest colours -- by the rule of
+     * include/pngloss_hip_quant_target.h -- that keep DB decibels of PSNR over all four channels, a largest channel error of E, or both
+     * (pngloss_hip_multi_quantize_batch_host_target).  Not in the usage text either.  A value that does not parse is remembered (*_ok) and refused by
+     * cli_options_check behind every older rule */
+    bool have_colors_psnr, colors_psnr_ok;
+    double colors_psnr;
+    bool have_colors_max_error, colors_max_error_ok;
+    unsigned long colors_max_error;
     bool have_strength;        /* -s was given */
     enum cli_search search;
     double target_psnr;        /* 0: no PSNR condition */

@@ -57,6 +57,23 @@ void cli_report_quant(char *line, size_t cap, const pngloss_hip_quant_report *q)
     snprintf(line, cap, "  colors: %s in the input, %u palette entries%s\n", in, q->entries, q->exact ? ", exact (no pixel changed)" : "");
 }
 
+void cli_report_chosen_colors(char *line, size_t cap, const pngloss_hip_quant_target_report *r, unsigned max_colors)
+{
+    if (!r->reached) {
+        snprintf(line, cap, "  chosen: %u of at most %u colours, target not reached\n", r->colors, max_colors);
+        return;
+    }
+    char psnr[32];
+    if (!r->probe_distortion.changed_pixels) snprintf(psnr, sizeof psnr, "exact");
+    else snprintf(psnr, sizeof psnr, "%.2f dB", pngloss_hip_psnr_db(&r->probe_distortion, 0xFu));
+    snprintf(line, cap, "  chosen: %u of at most %u colours, %s (%u probes)\n", r->colors, max_colors, psnr, r->probes);
+}
+
+void cli_report_colors_missed(char *line, size_t cap, const char *name, unsigned max_colors)
+{
+    snprintf(line, cap, "  warning: %s: the colour target is not reached with %u colours; written at %u colours\n", name, max_colors, max_colors);
+}
+
 void cli_report_dither(char *line, size_t cap, const pngloss_hip_quant_report *q)
 {
     snprintf(line, cap, "%s", q->exact ? "" : "  dither: Floyd-Steinberg\n");

@@ -11,6 +11,7 @@
 #include "../../include/pngloss_hip_indexed.h"
 #include "../../include/pngloss_hip_quant.h"
 #include "../../include/pngloss_hip_dither.h"
+#include "../../include/pngloss_hip_quant_target.h"
 #include "cli_options.h"
 
 #ifdef __cplusplus
@@ -32,6 +33,11 @@ void cli_report_strength(char *line, size_t cap, unsigned strength, unsigned pro
 void cli_report_indexed(char *line, size_t cap, const pngloss_hip_palette *p);
 /* -v with --colors: the input's colours, the palette entries of what is written, and whether the image was left as it was */
 void cli_report_quant(char *line, size_t cap, const pngloss_hip_quant_report *q);
+/* ... with --colors-psnr / --colors-max-error, the line behind it: the colour count the search chose below --colors M, the PSNR over all four
+ * channels of the probe it ended on and the probes taken -- or that even M colours did not reach the target */
+void cli_report_chosen_colors(char *line, size_t cap, const pngloss_hip_quant_target_report *r, unsigned max_colors);
+/* the warning for a file whose colour target --colors M did not reach: it was written at M colours */
+void cli_report_colors_missed(char *line, size_t cap, const char *name, unsigned max_colors);
 /* ... with --dither, the line behind it: empty for a file that was exact, which is never dithered */
 void cli_report_dither(char *line, size_t cap, const pngloss_hip_quant_report *q);
 void cli_report_budget_missed(char *line, size_t cap, const char *name, size_t budget, size_t written, unsigned strength);

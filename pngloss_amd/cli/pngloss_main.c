@@ -32,6 +32,7 @@
 #include "../../include/pngloss_hip_indexed.h"
 #include "../../include/pngloss_hip_quant.h"
 #include "../../include/pngloss_hip_dither.h"
+#include "../../include/pngloss_hip_quant_target.h"
 #include "cli_options.h"
 #include "cli_outcome.h"
 #include "cli_report.h"
@@ -76,6 +77,8 @@ struct job {
     bool have_palette;
     pngloss_hip_quant_report quant;      /* --colors: what the quantiser did to this file (have_quant: it ran) */
     bool have_quant;
+    pngloss_hip_quant_target_report chosen;   /* --colors-psnr / --colors-max-error: what the colour-count search did (have_chosen: it ran) */
+    bool have_chosen;
     png_stream_source src;    /* --gpu-read: inflated scanlines waiting for the device (src.scanlines != NULL) */
 };
 
@@ -289,6 +292,10 @@ static void encode_job(struct job *j, const struct cli_options *o)
     if (o->verbose && j->have_quant) {
         cli_report_quant(line, sizeof line, &j->quant);
         say(j, "%s", line);
+        if (j->have_chosen) {
+            cli_report_chosen_colors(line, sizeof line, &j->chosen, (unsigned)o->colors);
+            say(j, "%s", line);
+        }
         if (o->dither) {
             cli_report_dither(line, sizeof line, &j->quant);
             say(j, "%s", line);
@@ -302,6 +309,11 @@ static void encode_job(struct job *j, const struct cli_options *o)
     j->out.chunks = j->in.chunks;          /* metadata travels to the output */
     j->in.chunks = NULL;
     pngloss_error rc = encode_to(j, &j->out, j->filters, o);
+    /* a colour target that even --colors M does not reach: the file was written at M colours; one line says so, the exit status stays */
+    if (j->have_chosen && rc == SUCCESS && !j->chosen.reached) {
+        cli_report_colors_missed(line, sizeof line, j->in_name, (unsigned)o->colors);
+        say(j, "%s", line);
+    }
     /* a budget that was not reached (or is smaller than the container alone): the file was written at -s; one line says so, the exit status stays */
     if (o->search == CLI_SEARCH_SIZE && rc == SUCCESS && (!j->size.reached || j->out.file_size > j->size_budget)) {
         cli_report_budget_missed(line, sizeof line, j->in_name, j->size_budget, j->out.file_size, j->size.strength);
@@ -561,18 +573,25 @@ static void quantise_batch(pngloss_hip_multi *ctx, struct window_batch *b, struc
 {
     const pngloss_hip_quant_params params = { (uint32_t)o->colors, PNGLOSS_HIP_QUANT_DEFAULT_ROUNDS };
     const pngloss_hip_quant_params2 dithered = { params.max_colors, params.rounds, PNGLOSS_HIP_DITHER_FLOYD_STEINBERG, 0 };
+    const bool searched = o->have_colors_psnr || o->have_colors_max_error;
+    const pngloss_hip_quant_params2 plain = { params.max_colors, params.rounds, PNGLOSS_HIP_DITHER_NONE, 0 };
+    const pngloss_hip_quant_target target = { o->have_colors_psnr ? o->colors_psnr : 0.0, o->have_colors_max_error ? (uint32_t)o->colors_max_error : 0, 0 };
     pngloss_hip_quant_report *reports = calloc(b->m ? b->m : 1, sizeof *reports);
-    int rc = !ctx ? PNGLOSS_HIP_ERROR : !reports ? PNGLOSS_OUT_OF_MEMORY_ERROR
+    pngloss_hip_quant_target_report *chosen = searched ? calloc(b->m ? b->m : 1, sizeof *chosen) : NULL;
+    int rc = !ctx ? PNGLOSS_HIP_ERROR : !reports || (searched && !chosen) ? PNGLOSS_OUT_OF_MEMORY_ERROR
+           : searched ? pngloss_hip_multi_quantize_batch_host_target(ctx, b->imgs, b->m, o->dither ? &dithered : &plain, &target, chosen)
            : o->dither ? pngloss_hip_multi_quantize_batch_host2(ctx, b->imgs, b->m, &dithered, reports)
                        : pngloss_hip_multi_quantize_batch_host(ctx, b->imgs, b->m, &params, reports);
     for (size_t k = 0; k < b->m; k++) {
         struct job *j = &jobs[b->who[k]];
+        if (rc == PNGLOSS_SUCCESS && searched) { j->chosen = chosen[k]; j->have_chosen = true; reports[k] = chosen[k].quant; }
         if (rc == PNGLOSS_SUCCESS) { j->quant = reports[k]; j->have_quant = true; continue; }
         say(j, "  error: GPU colour quantisation failed (%d)\n", rc);
         j->status = (pngloss_error)rc;
     }
     if (rc != PNGLOSS_SUCCESS) b->m = 0;
     free(reports);
+    free(chosen);
 }
 
 /* The one call into the library.  In a search the library finds a strength per file, -s bounds it, and the records come back in the reports */

@@ -12,6 +12,7 @@
  *   pl_host_measure.hip  the job tables of the two measuring kernels, the stand-alone comparisons
  *   pl_host_read.hip     the PNG read side
  *   pl_host_quant.hip    the colour quantiser: its workspace, the median cut between its two synchronisations, its host form -- with and without the dither pass (pl_dither.hip)
+ *   pl_host_quant_target.hip  the colour count searched per image from a distortion target (pl_colors.h), over the stages of pl_host_quant.hip
  * What the host side DECIDES is in plain headers that the CPU suite pins (pl_plan.h, pl_seg_pace.h, pl_layout.h, pl_deal.h, pl_search.h, pl_result.h);
  * these files carry it out.
  *
@@ -33,6 +34,7 @@
 #include "../../include/pngloss_hip_indexed.h"
 #include "../../include/pngloss_hip_quant.h"
 #include "../../include/pngloss_hip_dither.h"
+#include "../../include/pngloss_hip_quant_target.h"
 #include "pl_device.h"
 #include "pl_deflate.h"
 #include "pl_pngread.h"
@@ -44,6 +46,7 @@
 #include "pl_dither.h"
 #include "pl_target.h"
 #include "pl_size.h"
+#include "pl_colors.h"
 #include "pl_target_dev.h"
 #define SEG_PLAIN_POINTERS   /* host plumbing only: SegJob is filled here, never dereferenced */
 #include "pl_seg.h"
@@ -320,6 +323,42 @@ uint64_t fill_ssim_jobs(PlSsimJob *jobs, PlSsimRecord *records, PlSsimRecord *d_
                         const uint32_t *width, const uint32_t *height, bool visible);
 int upload_ssim_jobs(pngloss_hip_ctx *ctx, size_t n, const void *const *a, const void *const *b, const uint32_t *width, const uint32_t *height,
                      hipStream_t stream, PlSsimLayout &lay, uint64_t &max_tiles, bool visible);
+
+/* ---- pl_host_quant.hip: the checks and the stages of a quantiser call, which pl_host_quant_target.hip runs too ---- */
+int check_quant_params(const pngloss_hip_quant_params2 *params);
+/* every image with pixels has a pointer (pixels_of[i]) and few enough pixels (plq_pixels_ok) */
+int check_quant_pixels(const uint32_t *width, const uint32_t *height, size_t n, const void *const *pixels_of);
+/* the whole workspace of a call: the quantiser's, and behind it -- when the call dithers -- the dither pass's job table and error lines */
+struct QuantWorkspace {
+    PlQuantLayout lay;
+    PlDitherLayout dither;
+    bool dithers = false;
+    size_t total() const { return dithers ? dither.total : lay.total; }
+};
+QuantWorkspace quant_workspace_of(const std::vector<uint32_t> &width, const std::vector<uint32_t> &height, bool inputs, const pngloss_hip_quant_params2 &params);
+/* One call's images in the workspace ctx->d_quant, which the caller has grown to ws.total(): what quant_survey finds out about them and the job
+ * tables the later stages launch over.  Entry k of ijobs / qjobs is image live[k]; hists holds PLQ_BINS counts per entry, on the host. */
+struct QuantBatch {
+    pngloss_hip_ctx *ctx;
+    const QuantWorkspace &ws;
+    const std::vector<uint32_t *> &img;
+    const std::vector<uint32_t> &width, &height;
+    hipStream_t stream;
+    std::vector<size_t> live;                       /* the images with pixels */
+    std::vector<PlIndexJob> ijobs;
+    std::vector<PlQuantJob> qjobs;
+    uint64_t max_pixels = 0;
+    std::vector<uint32_t> counts, hists;
+    char *base() const { return ctx->d_quant.p; }
+    const PlIndexJob *d_ijobs() const { return reinterpret_cast<const PlIndexJob *>(base() + ws.lay.index_jobs); }
+    const PlQuantJob *d_qjobs() const { return reinterpret_cast<const PlQuantJob *>(base() + ws.lay.quant_jobs); }
+};
+int quant_survey(QuantBatch &b, pngloss_hip_quant_report *reports);
+int quant_first_palette(QuantBatch &b, size_t k, uint32_t colors, std::vector<uint32_t> &pals);
+int quant_refine(QuantBatch &b, const std::vector<size_t> &work, const std::vector<uint32_t> &pals, uint32_t rounds, std::vector<PlQuantJob> &jobs, uint64_t &work_pixels);
+int quant_dither(QuantBatch &b, const std::vector<size_t> &work);
+int quant_close(QuantBatch &b, const std::vector<PlQuantJob> &jobs, uint64_t work_pixels, const std::vector<size_t> &pass, const std::vector<uint32_t> &allowed,
+                pngloss_hip_quant_report *reports);
 
 #pragma GCC visibility pop
 

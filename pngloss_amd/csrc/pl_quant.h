@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pl_quant_core.h"
+#include "pl_quant_measure_core.h"
 
 /* One job = one image.  pl_quant_hist reads img / pixels and fills hist; the other kernels run on the images that are not exact only. */
 struct PlQuantJob {
@@ -21,6 +22,9 @@ struct PlQuantJob {
 hipError_t pl_launch_quant_hist(const PlQuantJob *d_jobs, size_t n, uint64_t max_pixels, hipStream_t stream);
 hipError_t pl_launch_quant_assign(const PlQuantJob *d_jobs, size_t n, uint64_t max_pixels, hipStream_t stream);
 hipError_t pl_launch_quant_remap(const PlQuantJob *d_jobs, size_t n, uint64_t max_pixels, hipStream_t stream);
+/* the remap pass without its stores: the distortion record of (img, img remapped to the job's palette) added up in d_records[k] for job k; the
+ * records are zero before the launch, and `pixels` of each is the caller's to write */
+hipError_t pl_launch_quant_measure(const PlQuantJob *d_jobs, PlDistortRecord *d_records, size_t n, uint64_t max_pixels, hipStream_t stream);
 hipError_t pl_launch_quant_update(const PlQuantJob *d_jobs, size_t n, hipStream_t stream);
 
 #endif

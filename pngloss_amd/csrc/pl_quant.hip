@@ -8,6 +8,8 @@
  *                    broadcast), per pixel and entry one v_dot4_u32_u8, one v_lshl_add_u32 and one v_max_u32; counts and channel sums in 32-bit LDS
  *                    cells of the workgroup (5 KiB), flushed with one 64-bit agent-scope atomic per non-zero cell
  *   pl_quant_remap   the same search without the accumulation: every pixel's nearest entry written to the job's `out`
+ *   pl_quant_measure the remap pass in a measure-only mode (pl_quant_measure_core.h): the same search, (pixel, entry word) into the sums of a distortion
+ *                    record, no pixel stored -- a probe of pngloss_hip_quantize_batch_target reads 4 bytes per pixel and writes a record
  *   pl_quant_update  one workgroup per image: the new entries from the accumulators, which it zeroes for the next round
  *
  * The rounds are enqueued back to back on one stream; no kernel waits for another workgroup.  No reference equivalent.
@@ -92,6 +94,55 @@ __device__ __forceinline__ void assign_body(const PlQuantJob *__restrict__ jobs)
 __global__ __launch_bounds__(kThreads) void pl_quant_assign(const PlQuantJob *__restrict__ jobs) { assign_body<false>(jobs); }
 __global__ __launch_bounds__(kThreads) void pl_quant_remap(const PlQuantJob *__restrict__ jobs) { assign_body<true>(jobs); }
 
+/* The record of job k is records[k], zeroed before the launch; `pixels` is the host's to write.  A workgroup takes up to PLQ_WG_PIXELS pixels
+ * (plq_blocks), a lane of it so up to PLQ_WG_PIXELS / kThreads -- more than a lane's 32-bit sums hold, which is why plq_measure_lane flushes them. */
+static_assert(PLQ_WG_PIXELS / kThreads + PLQ_QUAD > PLD_FLUSH_PIXELS, "a lane of pl_quant_measure can pass PLD_FLUSH_PIXELS pixels: its sums are flushed, not merely bounded");
+__global__ __launch_bounds__(kThreads) void pl_quant_measure(const PlQuantJob *__restrict__ jobs, PlDistortRecord *__restrict__ records)
+{
+    constexpr int kWaves = kThreads / 64;
+    __shared__ uint32_t pal2[2 * PLQ_MAX_COLORS];
+    __shared__ uint64_t wsum[kWaves][5];        /* sq[0..3], changed */
+    __shared__ uint32_t wmax[kWaves][4];
+    const PlQuantJob j = jobs[blockIdx.y];
+    PlDistortRecord *const record = records + blockIdx.y;
+    const size_t n = (size_t)j.pixels;
+    if ((size_t)blockIdx.x * kChunk >= n) return;       /* the whole workgroup: the grid is sized by the largest image of the launch */
+    const uint32_t entries = j.entries < PLQ_MAX_COLORS ? j.entries : PLQ_MAX_COLORS;
+    if (threadIdx.x < entries) {
+        const uint32_t word = j.pal[threadIdx.x];
+        pal2[2 * threadIdx.x] = word;
+        pal2[2 * threadIdx.x + 1] = plq_base(word, threadIdx.x);
+    }
+    __syncthreads();
+    PldSum s = plq_measure_lane(pal2, entries, j.img, n, blockIdx.x, gridDim.x, threadIdx.x, kThreads);
+    /* per wave, then per workgroup; then ONE atomic per quantity and workgroup, none for a quantity that is zero: as pl_distort merges them */
+#pragma unroll
+    for (int off = 32; off; off >>= 1) {
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            s.sq[c] += __shfl_down(s.sq[c], off);
+            s.mx[c] = max(s.mx[c], __shfl_down(s.mx[c], off));
+        }
+        s.changed += __shfl_down(s.changed, off);
+    }
+    const uint32_t wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        for (int c = 0; c < 4; c++) { wsum[wave][c] = s.sq[c]; wmax[wave][c] = s.mx[c]; }
+        wsum[wave][4] = s.changed;
+    }
+    __syncthreads();
+    const uint32_t t = threadIdx.x;
+    if (t < 5) {
+        uint64_t v = 0;
+        for (int w = 0; w < kWaves; w++) v += wsum[w][t];
+        if (v) PLQ_ADD64(t < 4 ? &record->sq_err[t] : &record->changed_pixels, v);
+    } else if (t < 9) {
+        uint32_t v = 0;
+        for (int w = 0; w < kWaves; w++) v = max(v, wmax[w][t - 5]);
+        if (v) atomicMax(&record->max_abs[t - 5], v);
+    }
+}
+
 __global__ __launch_bounds__(kThreads) void pl_quant_update(const PlQuantJob *__restrict__ jobs)
 {
     const PlQuantJob j = jobs[blockIdx.x];
@@ -125,6 +176,16 @@ hipError_t launch_over_pixels(Kernel kernel, const PlQuantJob *d_jobs, size_t n,
 hipError_t pl_launch_quant_hist(const PlQuantJob *d_jobs, size_t n, uint64_t max_pixels, hipStream_t stream) { return launch_over_pixels(pl_quant_hist, d_jobs, n, max_pixels, stream); }
 hipError_t pl_launch_quant_assign(const PlQuantJob *d_jobs, size_t n, uint64_t max_pixels, hipStream_t stream) { return launch_over_pixels(pl_quant_assign, d_jobs, n, max_pixels, stream); }
 hipError_t pl_launch_quant_remap(const PlQuantJob *d_jobs, size_t n, uint64_t max_pixels, hipStream_t stream) { return launch_over_pixels(pl_quant_remap, d_jobs, n, max_pixels, stream); }
+
+hipError_t pl_launch_quant_measure(const PlQuantJob *d_jobs, PlDistortRecord *d_records, size_t n, uint64_t max_pixels, hipStream_t stream)
+{
+    if (!plq_pixels_ok(max_pixels)) return hipErrorInvalidValue;
+    for (size_t first = 0; first < n; first += kMaxImages) {
+        const size_t m = n - first < kMaxImages ? n - first : kMaxImages;
+        hipLaunchKernelGGL(pl_quant_measure, quant_grid(m, max_pixels), dim3(kThreads), 0, stream, d_jobs + first, d_records + first);
+    }
+    return hipGetLastError();
+}
 
 hipError_t pl_launch_quant_update(const PlQuantJob *d_jobs, size_t n, hipStream_t stream)
 {

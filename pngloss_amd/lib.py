@@ -145,6 +145,26 @@ class QuantReport(C.Structure):
                     distortion=self.distortion.as_dict())
 
 
+class QuantTarget(C.Structure):
+    """pngloss_hip_quant_target: min_psnr_db (0 = no condition, inf = only exact results pass) and max_abs_error (0 = no condition, 1..255); one
+    of the two has to be set.  include/pngloss_hip_quant_target.h states the rule."""
+    _fields_ = [("min_psnr_db", C.c_double), ("max_abs_error", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def __init__(self, min_psnr_db=0.0, max_abs_error=0, reserved=0):
+        super().__init__(min_psnr_db, max_abs_error, reserved)
+
+
+class QuantTargetReport(C.Structure):
+    """pngloss_hip_quant_target_report: the chosen colour count, whether the target was reached, the probes of the rule (probed[k] and bit k of
+    accepted_mask), the Distortion the probe at `colors` took and the QuantReport of pngloss_hip_quantize_batch2 at `colors`."""
+    _fields_ = [("colors", C.c_uint32), ("reached", C.c_uint32), ("probes", C.c_uint32), ("accepted_mask", C.c_uint32), ("probed", C.c_uint32 * 12),
+                ("probe_distortion", Distortion), ("quant", QuantReport)]
+
+    def as_dict(self):
+        return dict(colors=self.colors, reached=self.reached, probes=self.probes, accepted_mask=self.accepted_mask, probed=list(self.probed)[: self.probes],
+                    probe_distortion=self.probe_distortion.as_dict(), quant=self.quant.as_dict())
+
+
 class ImagePair(C.Structure):
     _fields_ = [("d_a", C.c_void_p), ("d_b", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32)]
 
@@ -228,6 +248,16 @@ DITHER_STRUCTS = {"pngloss_hip_quant_params2": QuantParams2}
 DITHER_PROTOTYPES = {
     "pngloss_hip_quantize_batch2": (C.c_int, [C.c_void_p, C.POINTER(ImageDesc), C.c_size_t, C.POINTER(QuantParams2), C.POINTER(QuantReport), C.c_void_p]),
     "pngloss_hip_multi_quantize_batch_host2": (C.c_int, [C.c_void_p, C.POINTER(HostImage), C.c_size_t, C.POINTER(QuantParams2), C.POINTER(QuantReport)]),
+}
+
+#: ... and for include/pngloss_hip_quant_target.h, the quantiser's colour count from a distortion target (tests/test_quant_target_host.py holds
+#: them against that header)
+QUANT_TARGET_STRUCTS = {"pngloss_hip_quant_target": QuantTarget, "pngloss_hip_quant_target_report": QuantTargetReport}
+QUANT_TARGET_PROTOTYPES = {
+    "pngloss_hip_quantize_batch_target": (C.c_int, [C.c_void_p, C.POINTER(ImageDesc), C.c_size_t, C.POINTER(QuantParams2), C.POINTER(QuantTarget),
+                                                    C.POINTER(QuantTargetReport), C.c_void_p]),
+    "pngloss_hip_multi_quantize_batch_host_target": (C.c_int, [C.c_void_p, C.POINTER(HostImage), C.c_size_t, C.POINTER(QuantParams2), C.POINTER(QuantTarget),
+                                                               C.POINTER(QuantTargetReport)]),
 }
 
 
@@ -395,7 +425,7 @@ def hip_lib():
                 except ImportError:
                     pass
             lib = _load(os.environ.get("PNGLOSS_HIP_LIBNAME", "libpngloss_hip.so"))
-            for name, (ret, args) in {**PROTOTYPES, **INDEXED_PROTOTYPES, **QUANT_PROTOTYPES, **DITHER_PROTOTYPES}.items():
+            for name, (ret, args) in {**PROTOTYPES, **INDEXED_PROTOTYPES, **QUANT_PROTOTYPES, **DITHER_PROTOTYPES, **QUANT_TARGET_PROTOTYPES}.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = ret, args
             _hip = lib
@@ -784,6 +814,17 @@ class HipContext:
             _check(self._lib.pngloss_hip_quantize_batch2(self._ctx, _image_descs(images), n, C.byref(params), rep, stream or None), "quantize_batch2")
         return list(images), [r.as_dict() for r in rep[:n]]
 
+    def quantize_target(self, images, target, max_colors=256, rounds=8, dither=DITHER_NONE, stream=0):
+        """pngloss_hip_quantize_batch_target: images as for quantize(), target a QuantTarget.  Every image is quantised in place to the colour count
+        the rule of include/pngloss_hip_quant_target.h finds for it, at most max_colors.  Synchronous.  Returns (images, reports): one report dict
+        per image (QuantTargetReport.as_dict)."""
+        n = len(images)
+        rep = _array(QuantTargetReport, n)
+        params = QuantParams2(max_colors, rounds, dither)
+        _check(self._lib.pngloss_hip_quantize_batch_target(self._ctx, _image_descs(images), n, C.byref(params), C.byref(target), rep, stream or None),
+               "quantize_batch_target")
+        return list(images), [r.as_dict() for r in rep[:n]]
+
     def compare(self, pairs, stream=0):
         """pngloss_hip_compare_batch: pairs = sequence of (d_a_ptr, d_b_ptr, width, height), device-resident RGBA8; returns one Distortion per pair
         (b against a).  Synchronous."""
@@ -912,6 +953,16 @@ class HipMulti:
         else:
             params = QuantParams2(max_colors, rounds, dither)
             _check(self._lib.pngloss_hip_multi_quantize_batch_host2(self._m, imgs, n, C.byref(params), rep), "multi_quantize_batch_host2")
+        return outs, [r.as_dict() for r in rep[:n]]
+
+    def quantize_host_target(self, arrays, target, max_colors=256, rounds=8, dither=DITHER_NONE):
+        """pngloss_hip_multi_quantize_batch_host_target on a list of (H, W, 4) uint8 arrays, target a QuantTarget.  Returns (outs, reports): the
+        quantised copies and one report dict per image (QuantTargetReport.as_dict)."""
+        outs, _, imgs = _host_images(arrays, want_filters=False)
+        n = len(outs)
+        rep = _array(QuantTargetReport, n)
+        params = QuantParams2(max_colors, rounds, dither)
+        _check(self._lib.pngloss_hip_multi_quantize_batch_host_target(self._m, imgs, n, C.byref(params), C.byref(target), rep), "multi_quantize_batch_host_target")
         return outs, [r.as_dict() for r in rep[:n]]
 
     def run_host(self, arrays, strength=19, bleed=2, want_filters=True):
