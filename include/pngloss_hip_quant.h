@@ -14,7 +14,8 @@ extern "C" {
 /* Colour quantisation (no reference equivalent: the reference tool never reduces the number of colours, and says of itself that it "does not do a
  * good job on paletted images or images with large areas of flat color").  These are CALLS, not an option: the results of every other call depend on
  * no option, as before.  Everything is an integer, so the device's answer is defined bit for bit.  A pixel is its RGBA8 word, channels R, G, B, A
- * in that order; all four channels weigh the same.  Dithering: pngloss_hip_dither.h.
+ * in that order; all four channels weigh the same (the search on alpha-premultiplied
+ * pixels instead, where what transparency hides costs nothing: pngloss_hip_quant_space.h).  Dithering: pngloss_hip_dither.h.
  *   exact        An image with at most max_colors distinct words comes back unchanged: exact = 1, palette = its colours ascending by the word read as a
  *                little-endian uint32 (the palette order of pngloss_hip_indexed.h).  An image without pixels is exact with 0 entries.
  *   histogram    bin(p) = (R>>4) | (G>>4)<<4 | (B>>4)<<8 | (A>>4)<<12: 65 536 bins; a bin's coordinate on a channel is that channel's 4-bit field.

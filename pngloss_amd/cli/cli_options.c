@@ -54,7 +54,7 @@ const char cli_usage_text[] =
     "Output names end in \"-loss.png\" or your --ext; with \"-\" the image goes stdin -> stdout.\n"
     "Existing outputs are skipped unless --force is given.\n";
 
-enum { OPT_EXT = 256, OPT_NO_FORCE, OPT_SKIP_LARGER, OPT_STRIP, OPT_GPU_DEFLATE, OPT_GPU_READ, OPT_DISTORTION, OPT_TARGET_PSNR, OPT_MAX_ERROR, OPT_SSIM, OPT_TARGET_SSIM, OPT_TARGET_SIZE, OPT_VISIBLE, OPT_INDEXED, OPT_COLORS, OPT_DITHER, OPT_COLORS_PSNR, OPT_COLORS_MAX_ERROR };
+enum { OPT_EXT = 256, OPT_NO_FORCE, OPT_SKIP_LARGER, OPT_STRIP, OPT_GPU_DEFLATE, OPT_GPU_READ, OPT_DISTORTION, OPT_TARGET_PSNR, OPT_MAX_ERROR, OPT_SSIM, OPT_TARGET_SSIM, OPT_TARGET_SIZE, OPT_VISIBLE, OPT_INDEXED, OPT_COLORS, OPT_DITHER, OPT_COLORS_PSNR, OPT_COLORS_MAX_ERROR, OPT_COLORS_VISIBLE };
 
 static bool parse_number(const char *text, unsigned long *out)
 {
@@ -120,6 +120,7 @@ pngloss_error cli_options_parse(int argc, char **argv, struct cli_options *o, FI
         { "dither", no_argument, NULL, OPT_DITHER },
         { "colors-psnr", required_argument, NULL, OPT_COLORS_PSNR },
         { "colors-max-error", required_argument, NULL, OPT_COLORS_MAX_ERROR },
+        { "colors-visible", no_argument, NULL, OPT_COLORS_VISIBLE },
         { NULL, 0, NULL, 0 },
     };
     memset(o, 0, sizeof *o);
@@ -170,6 +171,7 @@ pngloss_error cli_options_parse(int argc, char **argv, struct cli_options *o, FI
             o->have_colors_max_error = true;
             o->colors_max_error_ok = parse_number(optarg, &o->colors_max_error);
             break;
+        case OPT_COLORS_VISIBLE: o->colors_visible = true; break;
         case 'h': o->help = true; break;
         case 'V': o->version = true; break;
         case 'o':
@@ -246,5 +248,7 @@ pngloss_error cli_options_check(const struct cli_options *o, FILE *err)
     if (o->have_colors_max_error && !o->colors_max_error_ok) return refuse(err, "--colors-max-error requires a numeric argument\n");
     if (o->have_colors_max_error && (o->colors_max_error < 1 || o->colors_max_error > 255))
         return refuse(err, "Must specify a largest colour channel error in the range 1-255.\n");
+    /* the space of --colors: behind those again */
+    if (o->colors_visible && !o->have_colors) return refuse(err, "--colors-visible requires --colors.\n");
     return SUCCESS;
 }

@@ -45,6 +45,9 @@ struct cli_options {
     double colors_psnr;
     bool have_colors_max_error, colors_max_error_ok;
     unsigned long colors_max_error;
+    /* --colors-visible: --colors searches its palette on alpha-premultiplied pixels (the *3 calls of include/pngloss_hip_quant_space.h at space 1), and
+     * the record behind --distortion and the colour-count search is the visible-mode one.  Not in the usage text either */
+    bool colors_visible;
     bool have_strength;        /* -s was given */
     enum cli_search search;
     double target_psnr;        /* 0: no PSNR condition */

@@ -79,6 +79,11 @@ void cli_report_dither(char *line, size_t cap, const pngloss_hip_quant_report *q
     snprintf(line, cap, "%s", q->exact ? "" : "  dither: Floyd-Steinberg\n");
 }
 
+void cli_report_colors_space(char *line, size_t cap, const pngloss_hip_quant_report *q)
+{
+    snprintf(line, cap, "%s", q->exact ? "" : "  colour space: premultiplied\n");
+}
+
 void cli_report_budget_missed(char *line, size_t cap, const char *name, size_t budget, size_t written, unsigned strength)
 {
     snprintf(line, cap, "  warning: %s: budget of %zu bytes not reached, wrote %zu bytes at strength %u\n", name, budget, written, strength);

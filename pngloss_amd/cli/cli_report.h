@@ -40,6 +40,8 @@ void cli_report_chosen_colors(char *line, size_t cap, const pngloss_hip_quant_ta
 void cli_report_colors_missed(char *line, size_t cap, const char *name, unsigned max_colors);
 /* ... with --dither, the line behind it: empty for a file that was exact, which is never dithered */
 void cli_report_dither(char *line, size_t cap, const pngloss_hip_quant_report *q);
+/* ... with --colors-visible, the line behind those: empty for a file that was exact, which no space touches */
+void cli_report_colors_space(char *line, size_t cap, const pngloss_hip_quant_report *q);
 void cli_report_budget_missed(char *line, size_t cap, const char *name, size_t budget, size_t written, unsigned strength);
 
 #ifdef __cplusplus

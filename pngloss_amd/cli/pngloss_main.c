@@ -33,6 +33,7 @@
 #include "../../include/pngloss_hip_quant.h"
 #include "../../include/pngloss_hip_dither.h"
 #include "../../include/pngloss_hip_quant_target.h"
+#include "../../include/pngloss_hip_quant_space.h"
 #include "cli_options.h"
 #include "cli_outcome.h"
 #include "cli_report.h"
@@ -268,7 +269,8 @@ static pngloss_error encode_to(struct job *j, png24_image *img, unsigned char *f
 static void say_distortion(struct job *j, const struct cli_options *o)
 {
     char line[256];
-    cli_report_distortion(line, sizeof line, &j->distortion, j->gpu.bytes_per_pixel, o->visible);
+    /* (--colors-visible: the record is the quantiser's, which that switch makes the visible-mode one) */
+    cli_report_distortion(line, sizeof line, &j->distortion, j->gpu.bytes_per_pixel, o->visible || o->colors_visible);
     say(j, "%s", line);
 }
 
@@ -292,6 +294,10 @@ static void encode_job(struct job *j, const struct cli_options *o)
     if (o->verbose && j->have_quant) {
         cli_report_quant(line, sizeof line, &j->quant);
         say(j, "%s", line);
+        if (o->colors_visible) {
+            cli_report_colors_space(line, sizeof line, &j->quant);
+            say(j, "%s", line);
+        }
         if (j->have_chosen) {
             cli_report_chosen_colors(line, sizeof line, &j->chosen, (unsigned)o->colors);
             say(j, "%s", line);
@@ -575,10 +581,15 @@ static void quantise_batch(pngloss_hip_multi *ctx, struct window_batch *b, struc
     const pngloss_hip_quant_params2 dithered = { params.max_colors, params.rounds, PNGLOSS_HIP_DITHER_FLOYD_STEINBERG, 0 };
     const bool searched = o->have_colors_psnr || o->have_colors_max_error;
     const pngloss_hip_quant_params2 plain = { params.max_colors, params.rounds, PNGLOSS_HIP_DITHER_NONE, 0 };
+    /* --colors-visible: the same call in the premultiplied space */
+    const pngloss_hip_quant_params3 visible = { params.max_colors, params.rounds, o->dither ? PNGLOSS_HIP_DITHER_FLOYD_STEINBERG : PNGLOSS_HIP_DITHER_NONE,
+                                                PNGLOSS_HIP_QUANT_SPACE_VISIBLE };
     const pngloss_hip_quant_target target = { o->have_colors_psnr ? o->colors_psnr : 0.0, o->have_colors_max_error ? (uint32_t)o->colors_max_error : 0, 0 };
     pngloss_hip_quant_report *reports = calloc(b->m ? b->m : 1, sizeof *reports);
     pngloss_hip_quant_target_report *chosen = searched ? calloc(b->m ? b->m : 1, sizeof *chosen) : NULL;
     int rc = !ctx ? PNGLOSS_HIP_ERROR : !reports || (searched && !chosen) ? PNGLOSS_OUT_OF_MEMORY_ERROR
+           : searched && o->colors_visible ? pngloss_hip_multi_quantize_batch_host_target3(ctx, b->imgs, b->m, &visible, &target, chosen)
+           : o->colors_visible ? pngloss_hip_multi_quantize_batch_host3(ctx, b->imgs, b->m, &visible, reports)
            : searched ? pngloss_hip_multi_quantize_batch_host_target(ctx, b->imgs, b->m, o->dither ? &dithered : &plain, &target, chosen)
            : o->dither ? pngloss_hip_multi_quantize_batch_host2(ctx, b->imgs, b->m, &dithered, reports)
                        : pngloss_hip_multi_quantize_batch_host(ctx, b->imgs, b->m, &params, reports);

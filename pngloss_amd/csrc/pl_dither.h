@@ -15,7 +15,8 @@ struct PlDitherJob {
     uint32_t width, height, entries, reserved;
 };
 
-/* One workgroup per job.  Asynchronous on `stream`; no kernel waits for another workgroup. */
-hipError_t pl_launch_dither(const PlDitherJob *d_jobs, size_t n, hipStream_t stream);
+/* One workgroup per job.  Asynchronous on `stream`; no kernel waits for another workgroup.  visible: the rule of the premultiplied space
+ * (include/pngloss_hip_quant_space.h) -- `pal` holds premultiplied words, `out` gets straight ones */
+hipError_t pl_launch_dither(const PlDitherJob *d_jobs, size_t n, hipStream_t stream, bool visible = false);
 
 #endif

@@ -9,6 +9,10 @@
  *               next wave through a ring in LDS and, in the last wave, to the next band through the image's error line (plain vector stores and
  *               loads, a barrier between write and read).  A lane's pixels are loaded kAhead steps before their turn.
  *
+ *   pl_dither_visible   the rule of the premultiplied space (include/pngloss_hip_quant_space.h): plf_pixel premultiplies the pixel, a pixel
+ *               with alpha 0 takes no error in, and the word stored is the straight one of the nearest entry, from a second LDS table (1 KiB;
+ *               lane e makes entry e's word at the kernel's start)
+ *
  * A single image runs on one CU.  No kernel waits for another workgroup.  No reference equivalent.
  */
 #include "pl_dither.h"
@@ -20,10 +24,24 @@ constexpr uint32_t kAhead = 4;                  /* steps a pixel is loaded befor
 static_assert(PLF_K % kAhead == 0, "the registers of the pixels in flight rotate a whole number of times per epoch");
 static_assert(kThreads <= 1024 && kThreads % 64 == 0, "whole waves, one workgroup");
 
-__global__ __launch_bounds__(kThreads) void pl_dither(const PlDitherJob *__restrict__ jobs)
+/* the premultiplied space keeps the straight word of every entry; pl_dither has no such table */
+template <bool On>
+__device__ __forceinline__ uint32_t *straight_table()
+{
+    if constexpr (On) {
+        __shared__ uint32_t straight[PLQ_MAX_COLORS];
+        return straight;
+    } else {
+        return nullptr;
+    }
+}
+
+template <bool Visible>
+__device__ __forceinline__ void dither_body(const PlDitherJob *__restrict__ jobs)
 {
     __shared__ uint32_t pal2[2 * PLQ_MAX_COLORS];
     __shared__ PlfErr ring[PLF_RING_ENTRIES];
+    uint32_t *const straight = straight_table<Visible>();
     const PlDitherJob j = jobs[blockIdx.x];
     const uint32_t W = j.width, H = j.height;
     const uint32_t entries = j.entries < PLQ_MAX_COLORS ? j.entries : PLQ_MAX_COLORS;
@@ -31,6 +49,7 @@ __global__ __launch_bounds__(kThreads) void pl_dither(const PlDitherJob *__restr
         const uint32_t word = j.pal[e];
         pal2[2 * e] = word;
         pal2[2 * e + 1] = plq_base(word, e);
+        if (Visible) straight[e] = plq_straight(word);
     }
     __syncthreads();
     const uint32_t lane = threadIdx.x & (PLF_LANES - 1);
@@ -79,7 +98,7 @@ __global__ __launch_bounds__(kThreads) void pl_dither(const PlDitherJob *__restr
                         const uint32_t p = q[u];
                         q[u] = pixel_at(x + kAhead);
                         if (has_row && x >= 0 && (uint64_t)x < W) {
-                            dst[x] = plf_pixel(pal2, entries, p, s.last, s.ul, s.up, s.ur, &s.last, nullptr);
+                            dst[x] = plf_pixel<Visible>(pal2, entries, p, s.last, s.ul, s.up, s.ur, &s.last, nullptr, straight);
                             if (lane == PLF_LANES - 1) {
                                 if (to_ring) ring[plf_ring_index(wave + 1, (uint64_t)x)] = s.last;
                                 else if (to_line) j.line[x] = s.last;
@@ -95,14 +114,17 @@ __global__ __launch_bounds__(kThreads) void pl_dither(const PlDitherJob *__restr
     }
 }
 
+__global__ __launch_bounds__(kThreads) void pl_dither(const PlDitherJob *__restrict__ jobs) { dither_body<false>(jobs); }
+__global__ __launch_bounds__(kThreads) void pl_dither_visible(const PlDitherJob *__restrict__ jobs) { dither_body<true>(jobs); }
+
 } // namespace
 
-hipError_t pl_launch_dither(const PlDitherJob *d_jobs, size_t n, hipStream_t stream)
+hipError_t pl_launch_dither(const PlDitherJob *d_jobs, size_t n, hipStream_t stream, bool visible)
 {
     constexpr size_t kMaxImages = (size_t)1 << 30;
     for (size_t first = 0; first < n; first += kMaxImages) {
         const size_t m = n - first < kMaxImages ? n - first : kMaxImages;
-        hipLaunchKernelGGL(pl_dither, dim3((unsigned)m), dim3(kThreads), 0, stream, d_jobs + first);
+        hipLaunchKernelGGL(visible ? pl_dither_visible : pl_dither, dim3((unsigned)m), dim3(kThreads), 0, stream, d_jobs + first);
     }
     return hipGetLastError();
 }

@@ -81,13 +81,20 @@ PLQ_HD int32_t plf_round16(int32_t s) { return (int32_t)((uint32_t)(s + 8 + PLF_
 /* ---- the step of one pixel ---- */
 
 /* p: the pixel; left, ul, up, ur: the errors at (y, x-1), (y-1, x-1), (y-1, x), (y-1, x+1).  Returns the word of the nearest entry, *err the new
- * error.  pal2 as plq_search takes it.  a: when not NULL, the four a_c (the CPU harness reports them) */
-PLQ_HD uint32_t plf_pixel(const uint32_t *pal2, uint32_t entries, uint32_t p, PlfErr left, PlfErr ul, PlfErr up, PlfErr ur, PlfErr *err, int32_t *a)
+ * error.  pal2 as plq_search takes it.  a: when not NULL, the four a_c (the CPU harness reports them).
+ * Visible (include/pngloss_hip_quant_space.h): the rule on the premultiplied pixel pm(p) over premultiplied entries; a pixel with alpha 0 takes no
+ * error in (S_c counts as 0, so v = 0) and passes its own on; the word returned is straight[best], the plq_straight of the nearest entry, and the
+ * error stays in premultiplied units.  The bounds of the rule hold as they are: pm(p)'s channels are 0 .. 255. */
+template <bool Visible = false>
+PLQ_HD uint32_t plf_pixel(const uint32_t *pal2, uint32_t entries, uint32_t p, PlfErr left, PlfErr ul, PlfErr up, PlfErr ur, PlfErr *err, int32_t *a,
+                          const uint32_t *straight = nullptr)
 {
     int32_t v[4];
     uint32_t word = 0;
+    if (Visible) p = pld_pm(p);
+    const bool takes = !Visible || (p >> 24) != 0;
     for (uint32_t c = 0; c < 4; c++) {
-        const int32_t s = 7 * plf_err_channel(left, c) + plf_err_channel(ul, c) + 5 * plf_err_channel(up, c) + 3 * plf_err_channel(ur, c);
+        const int32_t s = takes ? 7 * plf_err_channel(left, c) + plf_err_channel(ul, c) + 5 * plf_err_channel(up, c) + 3 * plf_err_channel(ur, c) : 0;
         const int32_t ac = (int32_t)plq_channel(p, c) + plf_round16(s);
         if (a) a[c] = ac;
         v[c] = ac < 0 ? 0 : ac > 255 ? 255 : ac;
@@ -98,7 +105,7 @@ PLQ_HD uint32_t plf_pixel(const uint32_t *pal2, uint32_t entries, uint32_t p, Pl
     const uint32_t out = pal2[2 * best];
     for (uint32_t c = 0; c < 4; c++) v[c] -= (int32_t)plq_channel(out, c);
     *err = plf_err_pack(v);
-    return out;
+    return Visible ? straight[best] : out;
 }
 
 /* what a lane keeps between its steps */

@@ -13,6 +13,8 @@
  *   pl_host_read.hip     the PNG read side
  *   pl_host_quant.hip    the colour quantiser: its workspace, the median cut between its two synchronisations, its host form -- with and without the dither pass (pl_dither.hip)
  *   pl_host_quant_target.hip  the colour count searched per image from a distortion target (pl_colors.h), over the stages of pl_host_quant.hip
+ *   pl_host_quant_space.hip   the entry points that name the space the palette search runs in (include/pngloss_hip_quant_space.h): they split
+ *                        the parameter record and call what the older entry points of the two files above call
  * What the host side DECIDES is in plain headers that the CPU suite pins (pl_plan.h, pl_seg_pace.h, pl_layout.h, pl_deal.h, pl_search.h, pl_result.h);
  * these files carry it out.
  *
@@ -35,6 +37,7 @@
 #include "../../include/pngloss_hip_quant.h"
 #include "../../include/pngloss_hip_dither.h"
 #include "../../include/pngloss_hip_quant_target.h"
+#include "../../include/pngloss_hip_quant_space.h"
 #include "pl_device.h"
 #include "pl_deflate.h"
 #include "pl_pngread.h"
@@ -333,9 +336,11 @@ struct QuantWorkspace {
     PlQuantLayout lay;
     PlDitherLayout dither;
     bool dithers = false;
+    bool visible = false;       /* the call runs in the premultiplied space (include/pngloss_hip_quant_space.h): no byte of the workspace differs, the kernels do */
     size_t total() const { return dithers ? dither.total : lay.total; }
 };
-QuantWorkspace quant_workspace_of(const std::vector<uint32_t> &width, const std::vector<uint32_t> &height, bool inputs, const pngloss_hip_quant_params2 &params);
+QuantWorkspace quant_workspace_of(const std::vector<uint32_t> &width, const std::vector<uint32_t> &height, bool inputs, const pngloss_hip_quant_params2 &params,
+                                  uint32_t space);
 /* One call's images in the workspace ctx->d_quant, which the caller has grown to ws.total(): what quant_survey finds out about them and the job
  * tables the later stages launch over.  Entry k of ijobs / qjobs is image live[k]; hists holds PLQ_BINS counts per entry, on the host. */
 struct QuantBatch {
@@ -359,6 +364,17 @@ int quant_refine(QuantBatch &b, const std::vector<size_t> &work, const std::vect
 int quant_dither(QuantBatch &b, const std::vector<size_t> &work);
 int quant_close(QuantBatch &b, const std::vector<PlQuantJob> &jobs, uint64_t work_pixels, const std::vector<size_t> &pass, const std::vector<uint32_t> &allowed,
                 pngloss_hip_quant_report *reports);
+/* The calls themselves, behind every entry point of theirs: the older ones hand in PNGLOSS_HIP_QUANT_SPACE_RGBA, those of pl_host_quant_space.hip the
+ * space of their record, which they have checked (0 or 1); every other check is made here, before any device work */
+int quantize_batch(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n, const pngloss_hip_quant_params2 *params, uint32_t space,
+                   pngloss_hip_quant_report *reports, void *stream);
+int multi_quantize_batch_host(pngloss_hip_multi *m, const pngloss_hip_host_image *images, size_t n, const pngloss_hip_quant_params2 *params, uint32_t space,
+                              pngloss_hip_quant_report *reports);
+/* ---- pl_host_quant_target.hip ---- */
+int quantize_batch_target(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n, const pngloss_hip_quant_params2 *params, uint32_t space,
+                          const pngloss_hip_quant_target *target, pngloss_hip_quant_target_report *reports, void *stream);
+int multi_quantize_batch_host_target(pngloss_hip_multi *m, const pngloss_hip_host_image *images, size_t n, const pngloss_hip_quant_params2 *params, uint32_t space,
+                                     const pngloss_hip_quant_target *target, pngloss_hip_quant_target_report *reports);
 
 #pragma GCC visibility pop
 

@@ -2,7 +2,8 @@
  * pl_host_quant.hip -- the host side of the colour quantiser (include/pngloss_hip_quant.h, pngloss_hip_dither.h; pl_host_ctx.h has the map of the
  * host files): the argument checks, the workspace (pl_layout.h: pl_quant_layout, pl_dither_layout), the median cut between the two synchronisations
  * (pl_quant_core.h), the launches of pl_quant.hip, of pl_dither.hip in place of the remap pass when the call dithers, and of the kernels it borrows -- pl_index_count / pl_index_palette for the colours before and after, pl_distort for the record --, and the host
- * form over the contexts of a node (deal_over_contexts).
+ * form over the contexts of a node (deal_over_contexts).  The space of a call (include/pngloss_hip_quant_space.h; its entry points are in
+ * pl_host_quant_space.hip) travels in the workspace record: every stage asks b.ws.visible which twin of a kernel it launches.
  */
 #include "pl_host_ctx.h"
 
@@ -47,10 +48,12 @@ PlQuantLayout quant_layout_of(const std::vector<uint32_t> &width, const std::vec
 
 } // namespace
 
-QuantWorkspace quant_workspace_of(const std::vector<uint32_t> &width, const std::vector<uint32_t> &height, bool inputs, const pngloss_hip_quant_params2 &params)
+QuantWorkspace quant_workspace_of(const std::vector<uint32_t> &width, const std::vector<uint32_t> &height, bool inputs, const pngloss_hip_quant_params2 &params,
+                                  uint32_t space)
 {
     QuantWorkspace ws;
     ws.lay = quant_layout_of(width, height, inputs);
+    ws.visible = space == PNGLOSS_HIP_QUANT_SPACE_VISIBLE;
     ws.dithers = params.dither == PNGLOSS_HIP_DITHER_FLOYD_STEINBERG;
     if (ws.dithers) ws.dither = pl_dither_layout(width, ws.lay.total, sizeof(PlDitherJob));
     return ws;
@@ -90,7 +93,7 @@ int quant_survey(QuantBatch &b, pngloss_hip_quant_report *reports)
     PL_CHECK(hipMemcpyAsync(base + lay.index_jobs, b.ijobs.data(), sizeof(PlIndexJob) * b.ijobs.size(), hipMemcpyHostToDevice, stream));
     PL_CHECK(hipMemcpyAsync(base + lay.quant_jobs, b.qjobs.data(), sizeof(PlQuantJob) * b.qjobs.size(), hipMemcpyHostToDevice, stream));
     PL_CHECK(pl_launch_index_count(b.d_ijobs(), b.ijobs.size(), b.max_pixels, stream));
-    PL_CHECK(pl_launch_quant_hist(b.d_qjobs(), b.qjobs.size(), b.max_pixels, stream));
+    PL_CHECK(pl_launch_quant_hist(b.d_qjobs(), b.qjobs.size(), b.max_pixels, stream, b.ws.visible));
     PL_CHECK(hipMemcpyAsync(b.counts.data(), d_counts, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, stream));
     for (size_t k = 0; k < b.live.size(); k++)
         PL_CHECK(hipMemcpyAsync(b.hists.data() + k * (size_t)PLQ_BINS, b.qjobs[k].hist, PLL_QUANT_HIST, hipMemcpyDeviceToHost, stream));
@@ -130,7 +133,7 @@ int quant_refine(QuantBatch &b, const std::vector<size_t> &work, const std::vect
     PL_CHECK(hipMemcpyAsync(base + b.ws.lay.pals, pals.data(), PLL_QUANT_PAL * b.img.size(), hipMemcpyHostToDevice, b.stream));
     PL_CHECK(hipMemcpyAsync(base + b.ws.lay.quant_jobs, jobs.data(), sizeof(PlQuantJob) * jobs.size(), hipMemcpyHostToDevice, b.stream));
     for (uint32_t round = 0; round < rounds; round++) {
-        PL_CHECK(pl_launch_quant_assign(b.d_qjobs(), jobs.size(), work_pixels, b.stream));
+        PL_CHECK(pl_launch_quant_assign(b.d_qjobs(), jobs.size(), work_pixels, b.stream, b.ws.visible));
         PL_CHECK(pl_launch_quant_update(b.d_qjobs(), jobs.size(), b.stream));
     }
     return PNGLOSS_SUCCESS;
@@ -147,7 +150,7 @@ int quant_dither(QuantBatch &b, const std::vector<size_t> &work)
     }
     if (dither.empty()) return PNGLOSS_SUCCESS;
     PL_CHECK(hipMemcpyAsync(base + b.ws.dither.jobs, dither.data(), sizeof(PlDitherJob) * dither.size(), hipMemcpyHostToDevice, b.stream));
-    PL_CHECK(pl_launch_dither(reinterpret_cast<const PlDitherJob *>(base + b.ws.dither.jobs), dither.size(), b.stream));
+    PL_CHECK(pl_launch_dither(reinterpret_cast<const PlDitherJob *>(base + b.ws.dither.jobs), dither.size(), b.stream, b.ws.visible));
     return PNGLOSS_SUCCESS;
 }
 
@@ -176,12 +179,13 @@ int quant_close(QuantBatch &b, const std::vector<PlQuantJob> &jobs, uint64_t wor
             const int rc = quant_dither(b, pass);
             if (rc) return rc;
         } else {
-            PL_CHECK(pl_launch_quant_remap(b.d_qjobs(), jobs.size(), work_pixels, stream));
+            PL_CHECK(pl_launch_quant_remap(b.d_qjobs(), jobs.size(), work_pixels, stream, b.ws.visible));
         }
     }
-    /* the record of (input, output) while both exist, then the output over the input */
+    /* the record of (input, output) while both exist -- in the premultiplied space the visible-mode one, which counts `pixels` itself into records
+     * that are zero (quant_survey zeroed them, or the search did before its close) --, then the output over the input */
     PL_CHECK(hipMemcpyAsync(base + lay.distort_jobs, djobs.data(), sizeof(PlDistortJob) * djobs.size(), hipMemcpyHostToDevice, stream));
-    PL_CHECK(pl_launch_distort(d_djobs, djobs.size(), b.max_pixels, stream));
+    PL_CHECK(pl_launch_distort(d_djobs, djobs.size(), b.max_pixels, stream, b.ws.visible));
     for (size_t k = 0; k < b.live.size(); k++)
         if (!reports[b.live[k]].exact)
             PL_CHECK(hipMemcpyAsync(const_cast<uint32_t *>(b.qjobs[k].img), b.qjobs[k].out, (size_t)b.qjobs[k].pixels * 4, hipMemcpyDeviceToDevice, stream));
@@ -238,13 +242,14 @@ int quantize_on(pngloss_hip_ctx *ctx, const QuantWorkspace &ws, const std::vecto
 }
 
 /* the share of one context in the host form: its images up into the workspace, quantised there, the changed ones back */
-int quantize_host_share(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images, size_t n, const pngloss_hip_quant_params2 &params, pngloss_hip_quant_report *reports)
+int quantize_host_share(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images, size_t n, const pngloss_hip_quant_params2 &params, uint32_t space,
+                        pngloss_hip_quant_report *reports)
 {
     if (batch_in_flight_refused(ctx)) return PNGLOSS_INVALID_ARGUMENT;
     PL_CHECK(hipSetDevice(ctx->device));
     std::vector<uint32_t> width, height;
     batch_dims(images, n, width, height);
-    const QuantWorkspace ws = quant_workspace_of(width, height, true, params);
+    const QuantWorkspace ws = quant_workspace_of(width, height, true, params, space);
     const PlQuantLayout &lay = ws.lay;
     int rc = ctx->d_quant.grow(ws.total(), 8);
     if (rc == PNGLOSS_SUCCESS) rc = ensure_copy_stream(ctx);
@@ -266,8 +271,10 @@ int quantize_host_share(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *imag
     return PNGLOSS_SUCCESS;
 }
 
-/* both forms of pngloss_hip_quantize_batch */
-int quantize_batch(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n, const pngloss_hip_quant_params2 *params,
+} // namespace
+
+/* every form of pngloss_hip_quantize_batch; space: PNGLOSS_HIP_QUANT_SPACE_*, checked by the caller */
+int quantize_batch(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n, const pngloss_hip_quant_params2 *params, uint32_t space,
                    pngloss_hip_quant_report *reports, void *stream_)
 {
     if (!ctx || (n && (!images || !reports)) || check_quant_params(params)) return PNGLOSS_INVALID_ARGUMENT;
@@ -279,7 +286,7 @@ int quantize_batch(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, s
     PL_CHECK(hipSetDevice(ctx->device));
     std::vector<uint32_t> width, height;
     batch_dims(images, n, width, height);
-    const QuantWorkspace ws = quant_workspace_of(width, height, false, *params);
+    const QuantWorkspace ws = quant_workspace_of(width, height, false, *params, space);
     const int rc = ctx->d_quant.grow(ws.total(), 8);
     if (rc) return rc;
     std::vector<uint32_t *> img(n);
@@ -287,8 +294,8 @@ int quantize_batch(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, s
     return quantize_on(ctx, ws, img, width, height, *params, reports, static_cast<hipStream_t>(stream_));
 }
 
-/* both forms of pngloss_hip_multi_quantize_batch_host */
-int multi_quantize_batch_host(pngloss_hip_multi *m, const pngloss_hip_host_image *images, size_t n, const pngloss_hip_quant_params2 *params,
+/* every form of pngloss_hip_multi_quantize_batch_host */
+int multi_quantize_batch_host(pngloss_hip_multi *m, const pngloss_hip_host_image *images, size_t n, const pngloss_hip_quant_params2 *params, uint32_t space,
                               pngloss_hip_quant_report *reports)
 {
     if (!m || m->ctx.empty() || (n && (!images || !reports)) || check_quant_params(params)) return PNGLOSS_INVALID_ARGUMENT;
@@ -299,13 +306,11 @@ int multi_quantize_batch_host(pngloss_hip_multi *m, const pngloss_hip_host_image
     /* (no last batch to index: the records are in the reports) */
     return deal_over_contexts(m, images, n, nullptr, nullptr, nullptr, false, [&](pngloss_hip_ctx *ctx, HostSubset &mine) {
         std::vector<pngloss_hip_quant_report> own(mine.n());
-        const int rc = quantize_host_share(ctx, mine.images.data(), mine.n(), *params, own.data());
+        const int rc = quantize_host_share(ctx, mine.images.data(), mine.n(), *params, space, own.data());
         for (size_t k = 0; k < mine.n(); k++) reports[mine.who[k]] = own[k];
         return rc;
     });
 }
-
-} // namespace
 
 extern "C" {
 
@@ -313,26 +318,26 @@ int pngloss_hip_quantize_batch(pngloss_hip_ctx *ctx, const pngloss_hip_image_des
                                pngloss_hip_quant_report *reports, void *stream)
 {
     pngloss_hip_quant_params2 wide;
-    return quantize_batch(ctx, images, n, widen(params, wide), reports, stream);
+    return quantize_batch(ctx, images, n, widen(params, wide), PNGLOSS_HIP_QUANT_SPACE_RGBA, reports, stream);
 }
 
 int pngloss_hip_multi_quantize_batch_host(pngloss_hip_multi *m, const pngloss_hip_host_image *images, size_t n, const pngloss_hip_quant_params *params,
                                           pngloss_hip_quant_report *reports)
 {
     pngloss_hip_quant_params2 wide;
-    return multi_quantize_batch_host(m, images, n, widen(params, wide), reports);
+    return multi_quantize_batch_host(m, images, n, widen(params, wide), PNGLOSS_HIP_QUANT_SPACE_RGBA, reports);
 }
 
 int pngloss_hip_quantize_batch2(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n, const pngloss_hip_quant_params2 *params,
                                 pngloss_hip_quant_report *reports, void *stream)
 {
-    return quantize_batch(ctx, images, n, params, reports, stream);
+    return quantize_batch(ctx, images, n, params, PNGLOSS_HIP_QUANT_SPACE_RGBA, reports, stream);
 }
 
 int pngloss_hip_multi_quantize_batch_host2(pngloss_hip_multi *m, const pngloss_hip_host_image *images, size_t n, const pngloss_hip_quant_params2 *params,
                                            pngloss_hip_quant_report *reports)
 {
-    return multi_quantize_batch_host(m, images, n, params, reports);
+    return multi_quantize_batch_host(m, images, n, params, PNGLOSS_HIP_QUANT_SPACE_RGBA, reports);
 }
 
 } /* extern "C" */

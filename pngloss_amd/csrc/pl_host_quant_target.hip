@@ -9,6 +9,9 @@
  *   the close       quant_close over the palettes the search kept: the tail of every quantiser call, so `quant` is by construction that call's report
  * The state of the search is palettes, not images: the host keeps the final palette of the last accepted probe, which is the one the procedure
  * ends on.
+ * In the premultiplied space (include/pngloss_hip_quant_space.h; ws.visible) a probe's record is the visible-mode one: the measuring kernels count
+ * `pixels` themselves, a record without visible pixels is accepted, and an exact probe -- which needs no device work and passes whatever it counts --
+ * takes its `pixels` from the record of the close.
  */
 #include "pl_host_ctx.h"
 
@@ -45,7 +48,7 @@ int quantize_target_on(pngloss_hip_ctx *ctx, const QuantWorkspace &ws, const std
     auto take = [&](size_t i, const PlDistortRecord &rec, uint32_t entries) {
         const uint32_t colors = search[i].next;
         const bool ends_here = search[i].first;     /* a refused first probe is the image's result all the same */
-        const bool accepted = pl_colors_accept(target, rec);
+        const bool accepted = pl_colors_accept(target, rec);       /* (a record with pixels == 0 -- nothing visible in either image -- passes there) */
         if (accepted || ends_here) {
             kept[i] = Kept{ colors, entries, rec };
             std::copy(pal_of(pals, i), pal_of(pals, i) + PLQ_MAX_COLORS, pal_of(kept_pals, i));
@@ -86,16 +89,16 @@ int quantize_target_on(pngloss_hip_ctx *ctx, const QuantWorkspace &ws, const std
                 in_out[round[r].first] = round[r].second;
             }
             PL_CHECK(hipMemcpyAsync(base + lay.distort_jobs, djobs.data(), sizeof(PlDistortJob) * djobs.size(), hipMemcpyHostToDevice, stream));
-            PL_CHECK(pl_launch_distort(reinterpret_cast<const PlDistortJob *>(base + lay.distort_jobs), djobs.size(), work_pixels, stream));
+            PL_CHECK(pl_launch_distort(reinterpret_cast<const PlDistortJob *>(base + lay.distort_jobs), djobs.size(), work_pixels, stream, ws.visible));
         } else {
-            PL_CHECK(pl_launch_quant_measure(b.d_qjobs(), d_distort, jobs.size(), work_pixels, stream));
+            PL_CHECK(pl_launch_quant_measure(b.d_qjobs(), d_distort, jobs.size(), work_pixels, stream, ws.visible));
         }
         std::vector<PlDistortRecord> records(work.size());
         PL_CHECK(hipMemcpyAsync(records.data(), d_distort, sizeof(PlDistortRecord) * records.size(), hipMemcpyDeviceToHost, stream));
         PL_CHECK(hipMemcpyAsync(pals.data(), base + lay.pals, PLL_QUANT_PAL * n, hipMemcpyDeviceToHost, stream));
         PL_CHECK(hipStreamSynchronize(stream));
         for (size_t r = 0; r < work.size(); r++) {
-            records[r].pixels = jobs[r].pixels;
+            if (!ws.visible) records[r].pixels = jobs[r].pixels;
             take(round[r].first, records[r], jobs[r].entries);
         }
     }
@@ -133,6 +136,7 @@ int quantize_target_on(pngloss_hip_ctx *ctx, const QuantWorkspace &ws, const std
         std::copy(search[i].probed, search[i].probed + PLC_MAX_PROBES, rep.probed);
         std::memcpy(&rep.probe_distortion, &kept[i].record, sizeof rep.probe_distortion);
         rep.quant = quant[i];
+        if (ws.visible && quant[i].exact) rep.probe_distortion.pixels = quant[i].distortion.pixels;
         if (!ws.dithers && std::memcmp(&rep.probe_distortion, &rep.quant.distortion, sizeof rep.probe_distortion) != 0) {
             std::fprintf(stderr, "pngloss_hip: quantize target: image %zu: the probe at %u colours measured another record than the result has\n", i, rep.colors);
             return PNGLOSS_HIP_ERROR;
@@ -143,13 +147,13 @@ int quantize_target_on(pngloss_hip_ctx *ctx, const QuantWorkspace &ws, const std
 
 /* the share of one context in the host form: its images up into the workspace, searched there, the changed ones back */
 int quantize_target_host_share(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images, size_t n, const pngloss_hip_quant_params2 &params,
-                               const pngloss_hip_quant_target &target, pngloss_hip_quant_target_report *reports)
+                               uint32_t space, const pngloss_hip_quant_target &target, pngloss_hip_quant_target_report *reports)
 {
     if (batch_in_flight_refused(ctx)) return PNGLOSS_INVALID_ARGUMENT;
     PL_CHECK(hipSetDevice(ctx->device));
     std::vector<uint32_t> width, height;
     batch_dims(images, n, width, height);
-    const QuantWorkspace ws = quant_workspace_of(width, height, true, params);
+    const QuantWorkspace ws = quant_workspace_of(width, height, true, params, space);
     int rc = ctx->d_quant.grow(ws.total(), 8);
     if (rc == PNGLOSS_SUCCESS) rc = ensure_copy_stream(ctx);
     if (rc) return rc;
@@ -185,10 +189,9 @@ int check_target_call(const void *object, const Image *images, size_t n, const p
 
 } // namespace
 
-extern "C" {
-
-int pngloss_hip_quantize_batch_target(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n, const pngloss_hip_quant_params2 *params,
-                                      const pngloss_hip_quant_target *target, pngloss_hip_quant_target_report *reports, void *stream_)
+/* every form of pngloss_hip_quantize_batch_target; space: PNGLOSS_HIP_QUANT_SPACE_*, checked by the caller */
+int quantize_batch_target(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n, const pngloss_hip_quant_params2 *params, uint32_t space,
+                          const pngloss_hip_quant_target *target, pngloss_hip_quant_target_report *reports, void *stream_)
 {
     if (check_target_call(ctx, images, n, params, target, reports, [](const pngloss_hip_image_desc &im) { return (const void *)im.d_rgba; })) return PNGLOSS_INVALID_ARGUMENT;
     if (batch_in_flight_refused(ctx)) return PNGLOSS_INVALID_ARGUMENT;
@@ -196,7 +199,7 @@ int pngloss_hip_quantize_batch_target(pngloss_hip_ctx *ctx, const pngloss_hip_im
     PL_CHECK(hipSetDevice(ctx->device));
     std::vector<uint32_t> width, height;
     batch_dims(images, n, width, height);
-    const QuantWorkspace ws = quant_workspace_of(width, height, false, *params);
+    const QuantWorkspace ws = quant_workspace_of(width, height, false, *params, space);
     const int rc = ctx->d_quant.grow(ws.total(), 8);
     if (rc) return rc;
     std::vector<uint32_t *> img(n);
@@ -204,18 +207,33 @@ int pngloss_hip_quantize_batch_target(pngloss_hip_ctx *ctx, const pngloss_hip_im
     return quantize_target_on(ctx, ws, img, width, height, *params, *target, reports, static_cast<hipStream_t>(stream_));
 }
 
-int pngloss_hip_multi_quantize_batch_host_target(pngloss_hip_multi *m, const pngloss_hip_host_image *images, size_t n, const pngloss_hip_quant_params2 *params,
-                                                 const pngloss_hip_quant_target *target, pngloss_hip_quant_target_report *reports)
+/* every form of pngloss_hip_multi_quantize_batch_host_target */
+int multi_quantize_batch_host_target(pngloss_hip_multi *m, const pngloss_hip_host_image *images, size_t n, const pngloss_hip_quant_params2 *params, uint32_t space,
+                                     const pngloss_hip_quant_target *target, pngloss_hip_quant_target_report *reports)
 {
     if (check_target_call(m, images, n, params, target, reports, [](const pngloss_hip_host_image &im) { return (const void *)im.rgba; })) return PNGLOSS_INVALID_ARGUMENT;
     if (m->ctx.empty()) return PNGLOSS_INVALID_ARGUMENT;
     if (!n) return PNGLOSS_SUCCESS;
     return deal_over_contexts(m, images, n, nullptr, nullptr, nullptr, false, [&](pngloss_hip_ctx *ctx, HostSubset &mine) {
         std::vector<pngloss_hip_quant_target_report> own(mine.n());
-        const int rc = quantize_target_host_share(ctx, mine.images.data(), mine.n(), *params, *target, own.data());
+        const int rc = quantize_target_host_share(ctx, mine.images.data(), mine.n(), *params, space, *target, own.data());
         for (size_t k = 0; k < mine.n(); k++) reports[mine.who[k]] = own[k];
         return rc;
     });
+}
+
+extern "C" {
+
+int pngloss_hip_quantize_batch_target(pngloss_hip_ctx *ctx, const pngloss_hip_image_desc *images, size_t n, const pngloss_hip_quant_params2 *params,
+                                      const pngloss_hip_quant_target *target, pngloss_hip_quant_target_report *reports, void *stream)
+{
+    return quantize_batch_target(ctx, images, n, params, PNGLOSS_HIP_QUANT_SPACE_RGBA, target, reports, stream);
+}
+
+int pngloss_hip_multi_quantize_batch_host_target(pngloss_hip_multi *m, const pngloss_hip_host_image *images, size_t n, const pngloss_hip_quant_params2 *params,
+                                                 const pngloss_hip_quant_target *target, pngloss_hip_quant_target_report *reports)
+{
+    return multi_quantize_batch_host_target(m, images, n, params, PNGLOSS_HIP_QUANT_SPACE_RGBA, target, reports);
 }
 
 } /* extern "C" */

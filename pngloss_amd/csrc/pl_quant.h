@@ -18,13 +18,14 @@ struct PlQuantJob {
     uint32_t entries, reserved;
 };
 
-/* max_pixels: the largest `pixels` of the n jobs (sizes the grids).  All asynchronous on `stream`; no kernel waits for another workgroup. */
-hipError_t pl_launch_quant_hist(const PlQuantJob *d_jobs, size_t n, uint64_t max_pixels, hipStream_t stream);
-hipError_t pl_launch_quant_assign(const PlQuantJob *d_jobs, size_t n, uint64_t max_pixels, hipStream_t stream);
-hipError_t pl_launch_quant_remap(const PlQuantJob *d_jobs, size_t n, uint64_t max_pixels, hipStream_t stream);
+/* max_pixels: the largest `pixels` of the n jobs (sizes the grids).  All asynchronous on `stream`; no kernel waits for another workgroup.
+ * visible: the kernels of the premultiplied space (include/pngloss_hip_quant_space.h) -- `pal` then holds premultiplied words, `out` gets straight ones */
+hipError_t pl_launch_quant_hist(const PlQuantJob *d_jobs, size_t n, uint64_t max_pixels, hipStream_t stream, bool visible = false);
+hipError_t pl_launch_quant_assign(const PlQuantJob *d_jobs, size_t n, uint64_t max_pixels, hipStream_t stream, bool visible = false);
+hipError_t pl_launch_quant_remap(const PlQuantJob *d_jobs, size_t n, uint64_t max_pixels, hipStream_t stream, bool visible = false);
 /* the remap pass without its stores: the distortion record of (img, img remapped to the job's palette) added up in d_records[k] for job k; the
- * records are zero before the launch, and `pixels` of each is the caller's to write */
-hipError_t pl_launch_quant_measure(const PlQuantJob *d_jobs, PlDistortRecord *d_records, size_t n, uint64_t max_pixels, hipStream_t stream);
+ * records are zero before the launch, and `pixels` of each is the caller's to write -- visible: the visible-mode record, `pixels` counted by the kernel */
+hipError_t pl_launch_quant_measure(const PlQuantJob *d_jobs, PlDistortRecord *d_records, size_t n, uint64_t max_pixels, hipStream_t stream, bool visible = false);
 hipError_t pl_launch_quant_update(const PlQuantJob *d_jobs, size_t n, hipStream_t stream);
 
 #endif

@@ -25,14 +25,21 @@
  * its word and its base = ((PLQ_BIAS - |c|^2) << 8) | (255 - index); key = (p.c << 9) + base -- on the device one v_dot4_u32_u8, one v_lshl_add_u32 and
  * one v_max_u32 per pixel and entry.
  *
- * Shared by the HIP kernels (pl_quant.hip) and by tests/c/quant_host.cpp (test infrastructure), which runs the same bodies on the CPU under the
- * sanitizers, with one thread and with a team of threads that accumulate concurrently.
+ * The space (include/pngloss_hip_quant_space.h).  With Visible every step above runs on the alpha-premultiplied words pm(p) (pl_distort_core.h: pld_pm)
+ * instead of p: a pixel is converted once, right behind its load (plq_space_quad), and everything behind that -- bins, keys, sums, the merging of equal
+ * neighbours -- sees premultiplied words.  The palette holds premultiplied words; what the remap stores is plq_straight of the entry.  Without Visible
+ * nothing is converted and the code is what it was.
+ *
+ * Shared by the HIP kernels (pl_quant.hip) and by tests/c/quant_host.cpp and tests/c/quant_space_host.cpp (test infrastructure), which run the same
+ * bodies on the CPU under the sanitizers, with one thread and with a team of threads that accumulate concurrently.
  */
 #ifndef PL_QUANT_CORE_H
 #define PL_QUANT_CORE_H
 
 #include <stddef.h>
 #include <stdint.h>
+
+#include "pl_distort_core.h"
 
 #if defined(__HIPCC__)
 #define PLQ_HD __host__ __device__ __forceinline__
@@ -74,6 +81,31 @@ PLQ_HD uint32_t plq_dot4_plain(uint32_t a, uint32_t b)
     return plq_channel(a, 0) * plq_channel(b, 0) + plq_channel(a, 1) * plq_channel(b, 1) + plq_channel(a, 2) * plq_channel(b, 2) + plq_channel(a, 3) * plq_channel(b, 3);
 }
 
+/* ---- the space ---- */
+
+/* the m <= PLQ_QUAD pixels a lane has just loaded, as the words the search runs on */
+template <bool Visible>
+PLQ_HD void plq_space_quad(uint32_t *w, uint32_t m)
+{
+    if (Visible)
+        for (uint32_t k = 0; k < PLQ_QUAD; k++)
+            if (k < m) w[k] = pld_pm(w[k]);
+}
+
+/* the straight word of a premultiplied palette entry: alpha 0 is the word 0, else each of R, G, B is (c' * 255 + a / 2) / a, at most 255.
+ * pm(plq_straight(e)) == e whenever r', g', b' <= a, which holds for every entry made of premultiplied pixels (tests/test_quant_space_host.py) */
+PLQ_HD uint32_t plq_straight(uint32_t entry)
+{
+    const uint32_t a = entry >> 24;
+    if (!a) return 0u;
+    uint32_t word = entry & 0xFF000000u;
+    for (uint32_t c = 0; c < 3; c++) {
+        const uint32_t v = (plq_channel(entry, c) * 255u + a / 2u) / a;
+        word |= (v > 255u ? 255u : v) << (8 * c);
+    }
+    return word;
+}
+
 /* ---- the histogram ---- */
 
 PLQ_HD uint32_t plq_bin(uint32_t word)
@@ -82,16 +114,26 @@ PLQ_HD uint32_t plq_bin(uint32_t word)
 }
 PLQ_HD uint32_t plq_coord(uint32_t bin, uint32_t c) { return (bin >> (4 * c)) & 15u; }
 
-/* m <= PLQ_QUAD consecutive pixels into the table: a run of pixels of one bin costs one atomic */
-PLQ_HD void plq_hist_quad(uint32_t *hist, const uint32_t *w, uint32_t m)
+/* m <= PLQ_QUAD consecutive pixels into the table: a run of pixels of one bin costs one atomic.  Visible: the bins of the premultiplied words.
+ * There every pixel with an alpha below 16 lands in bin 0, whatever its colour -- the whole transparent surround of a sprite, millions of additions
+ * to one address.  With held0 they go to the caller's own count instead, which it adds to hist[0] once (pl_quant_hist_visible: once per wave). */
+template <bool Visible = false>
+PLQ_HD void plq_hist_quad(uint32_t *hist, const uint32_t *w, uint32_t m, uint32_t *held0 = nullptr)
 {
     uint32_t bin = 0, run = 0;
     for (uint32_t k = 0; k < m; k++) {
-        const uint32_t b = plq_bin(w[k]);
-        if (run && b != bin) { PLQ_ADD32(hist + bin, run); run = 0; }
+        const uint32_t b = plq_bin(Visible ? pld_pm(w[k]) : w[k]);
+        if (run && b != bin) {
+            if (Visible && held0 && !bin) *held0 += run;
+            else PLQ_ADD32(hist + bin, run);
+            run = 0;
+        }
         bin = b; run++;
     }
-    if (run) PLQ_ADD32(hist + bin, run);
+    if (run) {
+        if (Visible && held0 && !bin) *held0 += run;
+        else PLQ_ADD32(hist + bin, run);
+    }
 }
 
 /* ---- the grid of the assign pass: how many workgroups an image gets, and how many pixels the busiest of them takes ---- */

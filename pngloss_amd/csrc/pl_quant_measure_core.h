@@ -30,6 +30,10 @@ PLQ_HD void plq_load_quad(const uint32_t *p, uint32_t m, uint32_t *w)
  * table of `entries` entries.  The lane's 32-bit sums are emptied into the 64-bit ones as pld_thread empties them: a workgroup may take 2^24 pixels
  * (plq_blocks), a lane so 65 536, and a step adds at most four to the PLD_FLUSH_PIXELS a lane holds. */
 static_assert(PLD_FLUSH_PIXELS + PLQ_QUAD - 1 <= PLD_LANE_PIXELS_MAX, "a lane's 32-bit sums would overflow before they are flushed");
+/* Visible (include/pngloss_hip_quant_space.h): the pixels are premultiplied behind the load, the entries are premultiplied words, and the sums are
+ * taken on (pm(p), pal[k]) as they stand -- pm(plq_straight(pal[k])) == pal[k], so this is the visible-mode record of (input, remapped image) without
+ * the straight word ever being made.  s.visible counts the pixels whose alpha or whose entry's alpha is non-zero. */
+template <bool Visible = false>
 PLQ_HD PldSum plq_measure_lane(const uint32_t *pal2, uint32_t entries, const uint32_t *img, size_t n, size_t block, size_t blocks, uint32_t lane, uint32_t lanes)
 {
     PldSum s = {};
@@ -42,12 +46,16 @@ PLQ_HD PldSum plq_measure_lane(const uint32_t *pal2, uint32_t entries, const uin
         const uint32_t m = n - base < PLQ_QUAD ? (uint32_t)(n - base) : PLQ_QUAD;
         uint32_t w[PLQ_QUAD], best[PLQ_QUAD];
         plq_load_quad(img + base, m, w);
+        plq_space_quad<Visible>(w, m);
         plq_search_quad(pal2, entries, w, m, best);
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
         for (uint32_t k = 0; k < PLQ_QUAD; k++)
-            if (k < m) pld_pixel(l, w[k], pal2[2 * best[k]]);
+            if (k < m) {
+                pld_pixel(l, w[k], pal2[2 * best[k]]);
+                if (Visible) l.visible += ((w[k] | pal2[2 * best[k]]) >> 24) ? 1u : 0u;
+            }
         held += m;
         if (held >= PLD_FLUSH_PIXELS) { pld_flush(s, l); held = 0; }
     }

@@ -134,6 +134,15 @@ class QuantParams2(C.Structure):
         super().__init__(max_colors, rounds, dither, reserved)
 
 
+class QuantParams3(C.Structure):
+    """pngloss_hip_quant_params3: QuantParams2 with its last word named: space (QUANT_SPACE_RGBA = 0, QUANT_SPACE_VISIBLE = 1: the palette search
+    runs on alpha-premultiplied pixels).  include/pngloss_hip_quant_space.h states the rule."""
+    _fields_ = [("max_colors", C.c_uint32), ("rounds", C.c_uint32), ("dither", C.c_uint32), ("space", C.c_uint32)]
+
+    def __init__(self, max_colors=256, rounds=8, dither=0, space=0):
+        super().__init__(max_colors, rounds, dither, space)
+
+
 class QuantReport(C.Structure):
     """pngloss_hip_quant_report: what the quantiser did to one image.  colors_in: 257 = more than 256; palette[:entries]: the colours of the image as
     it is now, ascending by word; exact: it had at most max_colors colours and was not changed; distortion: now against the input, all pixels."""
@@ -258,6 +267,19 @@ QUANT_TARGET_PROTOTYPES = {
                                                     C.POINTER(QuantTargetReport), C.c_void_p]),
     "pngloss_hip_multi_quantize_batch_host_target": (C.c_int, [C.c_void_p, C.POINTER(HostImage), C.c_size_t, C.POINTER(QuantParams2), C.POINTER(QuantTarget),
                                                                C.POINTER(QuantTargetReport)]),
+}
+
+#: ... and for include/pngloss_hip_quant_space.h, the quantiser's calls with the space of the palette search (tests/test_quant_space_host.py holds
+#: them against that header)
+QUANT_SPACE_RGBA, QUANT_SPACE_VISIBLE = 0, 1
+QUANT_SPACE_STRUCTS = {"pngloss_hip_quant_params3": QuantParams3}
+QUANT_SPACE_PROTOTYPES = {
+    "pngloss_hip_quantize_batch3": (C.c_int, [C.c_void_p, C.POINTER(ImageDesc), C.c_size_t, C.POINTER(QuantParams3), C.POINTER(QuantReport), C.c_void_p]),
+    "pngloss_hip_multi_quantize_batch_host3": (C.c_int, [C.c_void_p, C.POINTER(HostImage), C.c_size_t, C.POINTER(QuantParams3), C.POINTER(QuantReport)]),
+    "pngloss_hip_quantize_batch_target3": (C.c_int, [C.c_void_p, C.POINTER(ImageDesc), C.c_size_t, C.POINTER(QuantParams3), C.POINTER(QuantTarget),
+                                                     C.POINTER(QuantTargetReport), C.c_void_p]),
+    "pngloss_hip_multi_quantize_batch_host_target3": (C.c_int, [C.c_void_p, C.POINTER(HostImage), C.c_size_t, C.POINTER(QuantParams3), C.POINTER(QuantTarget),
+                                                                C.POINTER(QuantTargetReport)]),
 }
 
 
@@ -425,7 +447,8 @@ def hip_lib():
                 except ImportError:
                     pass
             lib = _load(os.environ.get("PNGLOSS_HIP_LIBNAME", "libpngloss_hip.so"))
-            for name, (ret, args) in {**PROTOTYPES, **INDEXED_PROTOTYPES, **QUANT_PROTOTYPES, **DITHER_PROTOTYPES, **QUANT_TARGET_PROTOTYPES}.items():
+            for name, (ret, args) in {**PROTOTYPES, **INDEXED_PROTOTYPES, **QUANT_PROTOTYPES, **DITHER_PROTOTYPES, **QUANT_TARGET_PROTOTYPES,
+                                       **QUANT_SPACE_PROTOTYPES}.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = ret, args
             _hip = lib
@@ -799,14 +822,18 @@ class HipContext:
         _check(self._lib.pngloss_hip_last_palette(self._ctx, index, C.byref(r)), "last_palette")
         return r
 
-    def quantize(self, images, max_colors=256, rounds=8, stream=0, dither=None):
+    def quantize(self, images, max_colors=256, rounds=8, stream=0, dither=None, space=None):
         """pngloss_hip_quantize_batch: images as for run() (device-resident RGBA8), quantised in place to at most max_colors colours each.
         Synchronous.  Returns (images, reports): the tuples handed in, whose pixels are the quantised ones now, and one report dict per image
         (QuantReport.as_dict).  dither: None calls that entry point; DITHER_NONE or DITHER_FLOYD_STEINBERG calls pngloss_hip_quantize_batch2
-        (include/pngloss_hip_dither.h)."""
+        (include/pngloss_hip_dither.h).  space: None calls what it called without; QUANT_SPACE_RGBA or QUANT_SPACE_VISIBLE calls
+        pngloss_hip_quantize_batch3 (include/pngloss_hip_quant_space.h), with dither None as DITHER_NONE."""
         n = len(images)
         rep = _array(QuantReport, n)
-        if dither is None:
+        if space is not None:
+            params = QuantParams3(max_colors, rounds, dither or DITHER_NONE, space)
+            _check(self._lib.pngloss_hip_quantize_batch3(self._ctx, _image_descs(images), n, C.byref(params), rep, stream or None), "quantize_batch3")
+        elif dither is None:
             params = QuantParams(max_colors, rounds)
             _check(self._lib.pngloss_hip_quantize_batch(self._ctx, _image_descs(images), n, C.byref(params), rep, stream or None), "quantize_batch")
         else:
@@ -814,15 +841,21 @@ class HipContext:
             _check(self._lib.pngloss_hip_quantize_batch2(self._ctx, _image_descs(images), n, C.byref(params), rep, stream or None), "quantize_batch2")
         return list(images), [r.as_dict() for r in rep[:n]]
 
-    def quantize_target(self, images, target, max_colors=256, rounds=8, dither=DITHER_NONE, stream=0):
+    def quantize_target(self, images, target, max_colors=256, rounds=8, dither=DITHER_NONE, stream=0, space=None):
         """pngloss_hip_quantize_batch_target: images as for quantize(), target a QuantTarget.  Every image is quantised in place to the colour count
         the rule of include/pngloss_hip_quant_target.h finds for it, at most max_colors.  Synchronous.  Returns (images, reports): one report dict
-        per image (QuantTargetReport.as_dict)."""
+        per image (QuantTargetReport.as_dict).  space: None calls that entry point; QUANT_SPACE_RGBA or QUANT_SPACE_VISIBLE calls
+        pngloss_hip_quantize_batch_target3 (include/pngloss_hip_quant_space.h)."""
         n = len(images)
         rep = _array(QuantTargetReport, n)
-        params = QuantParams2(max_colors, rounds, dither)
-        _check(self._lib.pngloss_hip_quantize_batch_target(self._ctx, _image_descs(images), n, C.byref(params), C.byref(target), rep, stream or None),
-               "quantize_batch_target")
+        if space is not None:
+            params = QuantParams3(max_colors, rounds, dither, space)
+            _check(self._lib.pngloss_hip_quantize_batch_target3(self._ctx, _image_descs(images), n, C.byref(params), C.byref(target), rep, stream or None),
+                   "quantize_batch_target3")
+        else:
+            params = QuantParams2(max_colors, rounds, dither)
+            _check(self._lib.pngloss_hip_quantize_batch_target(self._ctx, _image_descs(images), n, C.byref(params), C.byref(target), rep, stream or None),
+                   "quantize_batch_target")
         return list(images), [r.as_dict() for r in rep[:n]]
 
     def compare(self, pairs, stream=0):
@@ -940,14 +973,18 @@ class HipMulti:
         _check(self._lib.pngloss_hip_multi_last_palette(self._m, index, C.byref(r)), "multi_last_palette")
         return r
 
-    def quantize_host(self, arrays, max_colors=256, rounds=8, dither=None):
+    def quantize_host(self, arrays, max_colors=256, rounds=8, dither=None, space=None):
         """pngloss_hip_multi_quantize_batch_host on a list of (H, W, 4) uint8 arrays.  Returns (outs, reports): the quantised copies and one report
         dict per image (QuantReport.as_dict).  dither: None calls that entry point; DITHER_NONE or DITHER_FLOYD_STEINBERG calls
-        pngloss_hip_multi_quantize_batch_host2 (include/pngloss_hip_dither.h)."""
+        pngloss_hip_multi_quantize_batch_host2 (include/pngloss_hip_dither.h).  space: None calls what it called without; QUANT_SPACE_RGBA or
+        QUANT_SPACE_VISIBLE calls pngloss_hip_multi_quantize_batch_host3 (include/pngloss_hip_quant_space.h), with dither None as DITHER_NONE."""
         outs, _, imgs = _host_images(arrays, want_filters=False)
         n = len(outs)
         rep = _array(QuantReport, n)
-        if dither is None:
+        if space is not None:
+            params = QuantParams3(max_colors, rounds, dither or DITHER_NONE, space)
+            _check(self._lib.pngloss_hip_multi_quantize_batch_host3(self._m, imgs, n, C.byref(params), rep), "multi_quantize_batch_host3")
+        elif dither is None:
             params = QuantParams(max_colors, rounds)
             _check(self._lib.pngloss_hip_multi_quantize_batch_host(self._m, imgs, n, C.byref(params), rep), "multi_quantize_batch_host")
         else:
@@ -955,14 +992,19 @@ class HipMulti:
             _check(self._lib.pngloss_hip_multi_quantize_batch_host2(self._m, imgs, n, C.byref(params), rep), "multi_quantize_batch_host2")
         return outs, [r.as_dict() for r in rep[:n]]
 
-    def quantize_host_target(self, arrays, target, max_colors=256, rounds=8, dither=DITHER_NONE):
+    def quantize_host_target(self, arrays, target, max_colors=256, rounds=8, dither=DITHER_NONE, space=None):
         """pngloss_hip_multi_quantize_batch_host_target on a list of (H, W, 4) uint8 arrays, target a QuantTarget.  Returns (outs, reports): the
-        quantised copies and one report dict per image (QuantTargetReport.as_dict)."""
+        quantised copies and one report dict per image (QuantTargetReport.as_dict).  space: None calls that entry point; QUANT_SPACE_RGBA or
+        QUANT_SPACE_VISIBLE calls pngloss_hip_multi_quantize_batch_host_target3 (include/pngloss_hip_quant_space.h)."""
         outs, _, imgs = _host_images(arrays, want_filters=False)
         n = len(outs)
         rep = _array(QuantTargetReport, n)
-        params = QuantParams2(max_colors, rounds, dither)
-        _check(self._lib.pngloss_hip_multi_quantize_batch_host_target(self._m, imgs, n, C.byref(params), C.byref(target), rep), "multi_quantize_batch_host_target")
+        if space is not None:
+            params = QuantParams3(max_colors, rounds, dither, space)
+            _check(self._lib.pngloss_hip_multi_quantize_batch_host_target3(self._m, imgs, n, C.byref(params), C.byref(target), rep), "multi_quantize_batch_host_target3")
+        else:
+            params = QuantParams2(max_colors, rounds, dither)
+            _check(self._lib.pngloss_hip_multi_quantize_batch_host_target(self._m, imgs, n, C.byref(params), C.byref(target), rep), "multi_quantize_batch_host_target")
         return outs, [r.as_dict() for r in rep[:n]]
 
     def run_host(self, arrays, strength=19, bleed=2, want_filters=True):
