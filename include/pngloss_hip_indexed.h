@@ -21,7 +21,7 @@ extern "C" {
  *                  come first; trns_entries is the number of entries with alpha != 255, and a tRNS chunk holds exactly the alphas of those first
  *                  entries (none when trns_entries is 0)
  *   indexed scanlines  colour type 3, bit depth 8: per row the filter type byte 0 ("none", what libpng uses for palette images) and `width` index
- *                  bytes.  Bit depths 1, 2 and 4 are not written, however few colours there are.
+ *                  bytes.  Bit depths 1, 2 and 4 are written only where the option "index_depth" asks for them (pngloss_hip_index_depth.h).
  *   decision       T = size of the truecolour stream, I = size of the indexed one, both complete zlib streams as pngloss_hip_zstream.size counts them,
  *                  both written by the device deflate; overhead = 12 + 3 * entries + (trns_entries ? 12 + trns_entries : 0), the PLTE and tRNS
  *                  chunks.  Indexed is kept iff the image is eligible and I + overhead < T; a tie goes to truecolour.

@@ -54,7 +54,7 @@ const char cli_usage_text[] =
     "Output names end in \"-loss.png\" or your --ext; with \"-\" the image goes stdin -> stdout.\n"
     "Existing outputs are skipped unless --force is given.\n";
 
-enum { OPT_EXT = 256, OPT_NO_FORCE, OPT_SKIP_LARGER, OPT_STRIP, OPT_GPU_DEFLATE, OPT_GPU_READ, OPT_DISTORTION, OPT_TARGET_PSNR, OPT_MAX_ERROR, OPT_SSIM, OPT_TARGET_SSIM, OPT_TARGET_SIZE, OPT_VISIBLE, OPT_INDEXED, OPT_COLORS, OPT_DITHER, OPT_COLORS_PSNR, OPT_COLORS_MAX_ERROR, OPT_COLORS_VISIBLE };
+enum { OPT_EXT = 256, OPT_NO_FORCE, OPT_SKIP_LARGER, OPT_STRIP, OPT_GPU_DEFLATE, OPT_GPU_READ, OPT_DISTORTION, OPT_TARGET_PSNR, OPT_MAX_ERROR, OPT_SSIM, OPT_TARGET_SSIM, OPT_TARGET_SIZE, OPT_VISIBLE, OPT_INDEXED, OPT_COLORS, OPT_DITHER, OPT_COLORS_PSNR, OPT_COLORS_MAX_ERROR, OPT_COLORS_VISIBLE, OPT_INDEX_DEPTH };
 
 static bool parse_number(const char *text, unsigned long *out)
 {
@@ -121,6 +121,7 @@ pngloss_error cli_options_parse(int argc, char **argv, struct cli_options *o, FI
         { "colors-psnr", required_argument, NULL, OPT_COLORS_PSNR },
         { "colors-max-error", required_argument, NULL, OPT_COLORS_MAX_ERROR },
         { "colors-visible", no_argument, NULL, OPT_COLORS_VISIBLE },
+        { "index-depth", required_argument, NULL, OPT_INDEX_DEPTH },
         { NULL, 0, NULL, 0 },
     };
     memset(o, 0, sizeof *o);
@@ -172,6 +173,11 @@ pngloss_error cli_options_parse(int argc, char **argv, struct cli_options *o, FI
             o->colors_max_error_ok = parse_number(optarg, &o->colors_max_error);
             break;
         case OPT_COLORS_VISIBLE: o->colors_visible = true; break;
+        case OPT_INDEX_DEPTH:
+            o->have_index_depth = true;
+            o->index_depth = optarg;
+            o->index_depth_ok = strcmp(optarg, "auto") == 0 || strcmp(optarg, "min") == 0 || strcmp(optarg, "8") == 0;
+            break;
         case 'h': o->help = true; break;
         case 'V': o->version = true; break;
         case 'o':
@@ -250,5 +256,8 @@ pngloss_error cli_options_check(const struct cli_options *o, FILE *err)
         return refuse(err, "Must specify a largest colour channel error in the range 1-255.\n");
     /* the space of --colors: behind those again */
     if (o->colors_visible && !o->have_colors) return refuse(err, "--colors-visible requires --colors.\n");
+    /* the bit depth of the palette files: behind those again (--colors implies --indexed) */
+    if (o->have_index_depth && !o->indexed) return refuse(err, "--index-depth requires --indexed or --colors.\n");
+    if (o->have_index_depth && !o->index_depth_ok) return refuse(err, "--index-depth requires auto, min or 8\n");
     return SUCCESS;
 }

@@ -48,6 +48,11 @@ struct cli_options {
     /* --colors-visible: --colors searches its palette on alpha-premultiplied pixels (the *3 calls of include/pngloss_hip_quant_space.h at space 1), and
      * the record behind --distortion and the colour-count search is the visible-mode one.  Not in the usage text either */
     bool colors_visible;
+    /* --index-depth auto|min|8: with --indexed or --colors, the bit depth of a palette file of at most 16 colours (the library's option
+     * "index_depth": 8 bits as without the switch, the smallest file of 8 bits and the packed depth, or the packed depth alone).  Not in the usage
+     * text either.  A value that is none of the three is remembered (index_depth_ok) and refused by cli_options_check behind every older rule */
+    bool have_index_depth, index_depth_ok;
+    const char *index_depth;
     bool have_strength;        /* -s was given */
     enum cli_search search;
     double target_psnr;        /* 0: no PSNR condition */

@@ -49,6 +49,17 @@ void cli_report_indexed(char *line, size_t cap, const pngloss_hip_palette *p)
              (unsigned long long)p->truecolor_bytes);
 }
 
+void cli_report_index_depth(char *line, size_t cap, const pngloss_hip_index_depth *r)
+{
+    if (r->bit_depth < 1 || r->bit_depth >= 8) { if (cap) line[0] = 0; return; }
+    if (r->indexed8_bytes)
+        snprintf(line, cap, "  index depth: %u bits, %llu bytes of packed image data against %llu bytes at 8 bits\n", r->bit_depth,
+                 (unsigned long long)r->packed_bytes, (unsigned long long)r->indexed8_bytes);
+    else
+        snprintf(line, cap, "  index depth: %u bits, %llu bytes of packed image data (the 8-bit stream was not written)\n", r->bit_depth,
+                 (unsigned long long)r->packed_bytes);
+}
+
 void cli_report_quant(char *line, size_t cap, const pngloss_hip_quant_report *q)
 {
     char in[32];

@@ -9,6 +9,7 @@
 
 #include "../../include/pngloss_hip.h"
 #include "../../include/pngloss_hip_indexed.h"
+#include "../../include/pngloss_hip_index_depth.h"
 #include "../../include/pngloss_hip_quant.h"
 #include "../../include/pngloss_hip_dither.h"
 #include "../../include/pngloss_hip_quant_target.h"
@@ -31,6 +32,9 @@ void cli_report_ssim(char *line, size_t cap, const pngloss_hip_ssim *r, enum cli
 /* -v: what a search chose; what --indexed decided; and the warning of a --target-size budget that -s did not reach */
 void cli_report_strength(char *line, size_t cap, unsigned strength, unsigned probes);
 void cli_report_indexed(char *line, size_t cap, const pngloss_hip_palette *p);
+/* ... with --index-depth, the line behind it for a file kept below 8 bits: the depth, the packed stream's size and the 8-bit stream's (which
+ * --index-depth min does not write); empty for any other file */
+void cli_report_index_depth(char *line, size_t cap, const pngloss_hip_index_depth *r);
 /* -v with --colors: the input's colours, the palette entries of what is written, and whether the image was left as it was */
 void cli_report_quant(char *line, size_t cap, const pngloss_hip_quant_report *q);
 /* ... with --colors-psnr / --colors-max-error, the line behind it: the colour count the search chose below --colors M, the PSNR over all four

@@ -137,7 +137,10 @@ pngloss_error png_stream_write(FILE *out, const png_stream_image *im, size_t *by
     const bool indexed = im->color_type == 3;
     if (indexed && (!im->palette || im->palette_entries < 1 || im->palette_entries > 256 || im->trns_entries > im->palette_entries || (im->trns_entries && !im->trns)))
         return INVALID_ARGUMENT;
-    const size_t rowbytes = (size_t)im->width * channels;
+    const unsigned index_bits = im->index_bits ? im->index_bits : 8;
+    if (index_bits != 1 && index_bits != 2 && index_bits != 4 && index_bits != 8) return INVALID_ARGUMENT;
+    if (indexed && im->palette_entries > (1u << index_bits)) return INVALID_ARGUMENT;
+    const size_t rowbytes = indexed ? ((size_t)im->width * index_bits + 7) / 8 : (size_t)im->width * channels;
     const size_t data_size = (rowbytes + 1) * im->height;
     sink s = { out, 0, SUCCESS };
     size_t meta = 0;
@@ -146,7 +149,7 @@ pngloss_error png_stream_write(FILE *out, const png_stream_image *im, size_t *by
     unsigned char ihdr[13];
     be32(ihdr, im->width);
     be32(ihdr + 4, im->height);
-    ihdr[8] = 8; ihdr[9] = (unsigned char)im->color_type; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;
+    ihdr[8] = indexed ? (unsigned char)index_bits : 8; ihdr[9] = (unsigned char)im->color_type; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;
     put_chunk(&s, "IHDR", ihdr, 13);
     if (im->tag_gamma) {
         unsigned char g[4];

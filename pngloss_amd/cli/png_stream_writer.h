@@ -15,7 +15,7 @@ extern "C" {
 
 typedef struct {
     uint32_t width, height;
-    int color_type;                    /* 0 gray, 4 gray+alpha, 2 RGB, 6 RGBA, 3 indexed (`palette`); always 8 bits per sample or index */
+    int color_type;                    /* 0 gray, 4 gray+alpha, 2 RGB, 6 RGBA, 3 indexed (`palette`); 8 bits per sample, and per index unless index_bits says less */
     const unsigned char *filter_ids;   /* [height] PNG filter type 0..4 of every scanline                       */
     const unsigned char *rows;         /* filtered scanline bytes, width*channels per row ...                   */
     size_t pitch;                      /* ... `pitch` bytes apart                                               */
@@ -31,6 +31,9 @@ typedef struct {
     unsigned palette_entries;
     const unsigned char *trns;         /* the alphas of the first trns_entries palette entries: the tRNS payload;      */
     unsigned trns_entries;             /* 0: no tRNS chunk is written                                                  */
+    /* colour type 3 only (the library's option "index_depth"): the bit depth of the indices, IHDR byte 8.  Below 8 the rows are packed scanlines,
+     * ceil(width * index_bits / 8) bytes each with the leftmost pixel in the high bits, and the palette has at most 1 << index_bits entries */
+    unsigned index_bits;               /* 0 or 8: 8; else 1, 2 or 4 */
 } png_stream_image;
 
 pngloss_error png_stream_write(FILE *out, const png_stream_image *image, size_t *bytes_written, size_t *metadata_bytes);

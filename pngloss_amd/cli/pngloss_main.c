@@ -30,6 +30,7 @@
 
 #include "../../include/pngloss_hip.h"
 #include "../../include/pngloss_hip_indexed.h"
+#include "../../include/pngloss_hip_index_depth.h"
 #include "../../include/pngloss_hip_quant.h"
 #include "../../include/pngloss_hip_dither.h"
 #include "../../include/pngloss_hip_quant_target.h"
@@ -76,6 +77,8 @@ struct job {
     bool have_ssim;
     pngloss_hip_palette palette;         /* --indexed: what the library decided for this file (color_type 3: the PLTE / tRNS payloads of the written file) */
     bool have_palette;
+    pngloss_hip_index_depth depth;       /* --index-depth: the bit depth of the stream the library kept (have_depth: the library had a record) */
+    bool have_depth;
     pngloss_hip_quant_report quant;      /* --colors: what the quantiser did to this file (have_quant: it ran) */
     bool have_quant;
     pngloss_hip_quant_target_report chosen;   /* --colors-psnr / --colors-max-error: what the colour-count search did (have_chosen: it ran) */
@@ -249,6 +252,7 @@ static pngloss_error encode_to(struct job *j, png24_image *img, unsigned char *f
         if (j->color_type == 3) {
             si.palette = &j->palette.rgb[0][0]; si.palette_entries = j->palette.entries;
             si.trns = j->palette.alpha; si.trns_entries = j->palette.trns_entries;
+            if (j->have_depth) si.index_bits = j->depth.bit_depth;
         }
         rc = png_stream_write(f, &si, &img->file_size, &img->metadata_size);
     } else {
@@ -310,6 +314,10 @@ static void encode_job(struct job *j, const struct cli_options *o)
     if (o->verbose && j->color_type == 3) {
         cli_report_indexed(line, sizeof line, &j->palette);
         say(j, "%s", line);
+        if (j->have_depth) {
+            cli_report_index_depth(line, sizeof line, &j->depth);
+            say(j, "%s", line);
+        }
     }
     if (o->skip_if_larger) j->out.maximum_file_size = j->in.file_size - 1;
     j->out.chunks = j->in.chunks;          /* metadata travels to the output */
@@ -552,6 +560,9 @@ static pngloss_hip_multi *open_contexts(const struct cli_options *o)
         fputs("  warning: the library refused the option \"ssim\"; no ssim lines\n", stderr);
     if (o->indexed && pngloss_hip_multi_set_option(ctx, "indexed", "on") != PNGLOSS_SUCCESS)
         fputs("  warning: the library refused the option \"indexed\"; every file is written as truecolour\n", stderr);
+    /* (a library that refuses it stays at 8 bits, and its record says so) */
+    if (o->have_index_depth && pngloss_hip_multi_set_option(ctx, "index_depth", o->index_depth) != PNGLOSS_SUCCESS)
+        fputs("  warning: the library refused the option \"index_depth\"; palette files are written at 8 bits\n", stderr);
     /* --visible: what those two and the searches measure.  A library that refuses it would measure something else than the lines say */
     if (o->visible && pngloss_hip_multi_set_option(ctx, "measure", "visible") != PNGLOSS_SUCCESS) {
         fputs("  error: the library refused the option \"measure\"\n", stderr);
@@ -651,11 +662,16 @@ static void take_answer(struct job *j, const struct window_batch *b, size_t k, c
         else last_distortion = o->distortion && ctx && pngloss_hip_multi_last_distortion(ctx, k, &j->distortion) == PNGLOSS_SUCCESS;
         last_ssim = o->ssim && ctx && pngloss_hip_multi_last_ssim(ctx, k, &j->ssim) == PNGLOSS_SUCCESS;
         last_palette = o->indexed && ctx && pngloss_hip_multi_last_palette(ctx, k, &j->palette) == PNGLOSS_SUCCESS;
+        j->have_depth = o->have_index_depth && last_palette && pngloss_hip_multi_last_index_depth(ctx, k, &j->depth) == PNGLOSS_SUCCESS;
         break;
     }
     j->have_distortion = cli_have_distortion(o->search, o->distortion, rc, last_distortion);
     j->have_ssim = cli_have_ssim(o->search, o->ssim, o->have_target_ssim, rc, last_ssim);
     j->have_palette = cli_have_palette(o->search, o->indexed, last_palette);
+    if (o->have_index_depth && j->have_palette && !j->have_depth && j->color_type == 3 && rc == PNGLOSS_SUCCESS) {
+        say(j, "  error: the library returned an indexed stream without its bit depth\n");
+        j->status = (pngloss_error)PNGLOSS_HIP_ERROR;
+    }
     if (cli_indexed_without_palette(j->color_type, j->have_palette, rc)) {
         say(j, "  error: the library returned an indexed stream without its palette\n");
         j->status = (pngloss_error)PNGLOSS_HIP_ERROR;

@@ -37,7 +37,7 @@ static PlHooks from_env()
 
 void forget_last_batch(pngloss_hip_ctx *c)
 {
-    c->n_last = 0; c->h_jobs.clear(); c->distortion.clear(); c->d_records = nullptr; c->ssim.clear(); c->d_ssim_records = nullptr; c->palette.clear(); c->split_last = false;
+    c->n_last = 0; c->h_jobs.clear(); c->distortion.clear(); c->d_records = nullptr; c->ssim.clear(); c->d_ssim_records = nullptr; c->palette.clear(); c->index_depth.clear(); c->split_last = false;
 }
 
 namespace {
@@ -612,6 +612,8 @@ int pngloss_hip_last_palette(pngloss_hip_ctx *ctx, size_t index, pngloss_hip_pal
 int pngloss_hip_multi_last_distortion(pngloss_hip_multi *m, size_t index, pngloss_hip_distortion *out) { return multi_last_record(m, index, out, &pngloss_hip_ctx::distortion); }
 int pngloss_hip_multi_last_ssim(pngloss_hip_multi *m, size_t index, pngloss_hip_ssim *out) { return multi_last_record(m, index, out, &pngloss_hip_ctx::ssim); }
 int pngloss_hip_multi_last_palette(pngloss_hip_multi *m, size_t index, pngloss_hip_palette *out) { return multi_last_record(m, index, out, &pngloss_hip_ctx::palette); }
+int pngloss_hip_last_index_depth(pngloss_hip_ctx *ctx, size_t index, pngloss_hip_index_depth *out) { return last_record(ctx, index, out, &pngloss_hip_ctx::index_depth); }
+int pngloss_hip_multi_last_index_depth(pngloss_hip_multi *m, size_t index, pngloss_hip_index_depth *out) { return multi_last_record(m, index, out, &pngloss_hip_ctx::index_depth); }
 
 int pngloss_hip_last_engine_info(pngloss_hip_ctx *ctx, size_t index, int32_t info[PLR_INFO_WORDS])
 {
@@ -656,6 +658,13 @@ int pngloss_hip_set_option(pngloss_hip_ctx *ctx, const char *name, const char *v
     if (std::strcmp(name, "distortion") == 0) return on_off(ctx->opt_distortion);      /* measure every batch from here on (pl_distort.hip) */
     if (std::strcmp(name, "ssim") == 0) return on_off(ctx->opt_ssim);                  /* measure the structural similarity of every batch from here on (pl_ssim.hip) */
     if (std::strcmp(name, "indexed") == 0) return on_off(ctx->opt_indexed);            /* the calls that return zlib streams also try colour type 3 from here on (pl_index.hip, window_index) */
+    if (std::strcmp(name, "index_depth") == 0) {
+        /* ... and with it on, at which bit depths: "8" (default) | "auto" | "min" (include/pngloss_hip_index_depth.h) */
+        if (std::strcmp(value, "8") == 0) { ctx->opt_index_depth = PLI_DEPTH_8; return PNGLOSS_SUCCESS; }
+        if (std::strcmp(value, "auto") == 0) { ctx->opt_index_depth = PLI_DEPTH_AUTO; return PNGLOSS_SUCCESS; }
+        if (std::strcmp(value, "min") == 0) { ctx->opt_index_depth = PLI_DEPTH_MIN; return PNGLOSS_SUCCESS; }
+        return PNGLOSS_INVALID_ARGUMENT;
+    }
     return PNGLOSS_INVALID_ARGUMENT;
 }
 

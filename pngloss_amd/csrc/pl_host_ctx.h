@@ -34,6 +34,7 @@
 
 #include "../../include/pngloss_hip.h"
 #include "../../include/pngloss_hip_indexed.h"
+#include "../../include/pngloss_hip_index_depth.h"
 #include "../../include/pngloss_hip_quant.h"
 #include "../../include/pngloss_hip_dither.h"
 #include "../../include/pngloss_hip_quant_target.h"
@@ -119,6 +120,7 @@ struct pngloss_hip_ctx {
      * (pl_distort_core.h, pl_ssim_core.h).  The pipeline never sees it. */
     bool opt_visible = false;        /* pngloss_hip_set_option("measure", "all" | "visible") */
     bool opt_indexed = false;        /* pngloss_hip_set_option("indexed", "on" | "off") */
+    uint32_t opt_index_depth = PLI_DEPTH_8;   /* pngloss_hip_set_option("index_depth", "8" | "auto" | "min"): read where opt_indexed is (pl_index_core.h: PliDepthMode) */
     /* one device arena, regrown on demand, carved per batch */
     GrowBuf d_ws;
     std::vector<PlJob> h_jobs;
@@ -164,6 +166,7 @@ struct pngloss_hip_ctx {
      * demand like the others; used by the deflate stage of a host window (window_index) */
     GrowBuf d_index;
     std::vector<pngloss_hip_palette> palette;        /* per image of the last finished host window that returned zlib streams with the option on; else empty */
+    std::vector<pngloss_hip_index_depth> index_depth;   /* ... and beside it which bit depth was kept, from which sizes (option "index_depth"; the packed rows lie behind the index workspace in d_index) */
 
     /* ---- pl_host_measure.hip: the tables of the two measuring kernels ---- */
     /* options "distortion" and "ssim": the keep arena (pl_layout.h: job table, records, the originals pl_keep copies -- one arena, one pl_keep launch for
@@ -213,9 +216,10 @@ struct EmitTarget { void *d_ids; void *d_rows; uint32_t pitch; };
 struct Measure {
     bool distortion = false, ssim = false, visible = false;
     bool indexed = false;       /* option "indexed": not a measurement, but it travels the same way -- the deflate stage of a host window (window_index) reads it, nothing else does */
+    uint32_t index_depth = PLI_DEPTH_8;   /* option "index_depth": beside it, read where it is on */
 };
 /* ... as the caller's options ask for it: what the plain entry points hand on (no context: nothing; the call fails where it always did) */
-inline Measure measure_of_options(const pngloss_hip_ctx *c) { return c ? Measure{ c->opt_distortion, c->opt_ssim, c->opt_visible, c->opt_indexed } : Measure{}; }
+inline Measure measure_of_options(const pngloss_hip_ctx *c) { return c ? Measure{ c->opt_distortion, c->opt_ssim, c->opt_visible, c->opt_indexed, c->opt_index_depth } : Measure{}; }
 
 /* What one call asks of a batch (enqueue): written down by its entry point, read by enqueue and run_seg_engine, kept nowhere */
 struct BatchCall {

@@ -70,6 +70,8 @@ struct HostWindow {
     std::vector<EmitTarget> emits;
     bool indexed = false;           /* option "indexed" on a window that returns zlib streams: the deflate stage also tries colour type 3 (window_index) */
     PlIndexLayout ilay;             /* ... in the index workspace, laid out and grown before anything is enqueued */
+    uint32_t index_depth = PLI_DEPTH_8;     /* option "index_depth" beside it: at "auto" and "min" the packed rows lie behind the index workspace */
+    PlPackLayout play;
     /* this image's pixels (and filter flags) come back to the caller */
     bool comes_back(size_t i) const
     {
@@ -148,13 +150,17 @@ int window_scanlines(const HostWindow &w)
 /* Option "indexed", behind the truecolour streams of the images `who` (zs[i].size = T is in place): count every image's colours; for the eligible
  * ones build the palette and the index rows and deflate those into a buffer of the window's own -- BOTH candidates are written, and the indexed one
  * replaces the truecolour stream in the caller's buffer where I + overhead < T (pl_index_core.h).  An image that is not eligible costs the count
- * kernel and nothing else, and its stream is the one the call above wrote.  Leaves the palette records of the window in ctx->palette. */
+ * kernel and nothing else, and its stream is the one the call above wrote.  Leaves the palette records of the window in ctx->palette.
+ * Option "index_depth" at "auto" adds a third candidate for an image of at most 16 colours -- its index rows packed at min_depth by pl_index_pack,
+ * deflated in one more call -- and at "min" puts it in the place of the 8-bit one; which stream is kept is pl_index_core.h's pli_keep_depth, and
+ * ctx->index_depth says it.  At "8" nothing here launches or writes anything it did not without that option. */
 int window_index(const HostWindow &w, const std::vector<size_t> &who)
 {
     pngloss_hip_ctx *ctx = w.ctx;
     pngloss_hip_zstream *zs = w.zs;
     hipStream_t stream = ctx->copy_stream;
     ctx->palette.assign(w.n, pngloss_hip_palette{});
+    ctx->index_depth.assign(w.n, pngloss_hip_index_depth{});
     if (who.empty()) return PNGLOSS_SUCCESS;
     char *const base = ctx->d_index.p;
     uint32_t *const d_counts = reinterpret_cast<uint32_t *>(base + w.ilay.counts);
@@ -193,26 +199,65 @@ int window_index(const HostWindow &w, const std::vector<size_t> &who)
     PL_CHECK(hipMemcpyAsync(base + w.ilay.jobs, elig.data(), sizeof(PlIndexJob) * elig.size(), hipMemcpyHostToDevice, stream));   /* (the count kernel has read its table: synchronised above) */
     PL_CHECK(pl_launch_index_palette(reinterpret_cast<const PlIndexJob *>(base + w.ilay.jobs), elig.size(), stream));
     PL_CHECK(pl_launch_index_rows(reinterpret_cast<const PlIndexJob *>(base + w.ilay.jobs), elig.size(), max_height, stream));
+    /* option "index_depth" at "auto" or "min": the index rows of the images with min_depth < 8 once more, packed at that depth -- one launch, whatever
+     * the depths (the counter is the number of entries: held against the record below) */
+    constexpr size_t none = ~(size_t)0;
+    std::vector<PlPackJob> packs;
+    std::vector<size_t> pack_of(elig.size(), none);
+    uint32_t pack_height = 0;
+    for (size_t k = 0; k < elig.size(); k++) {
+        const size_t i = elig_who[k];
+        if (!pli_wants_packed(w.index_depth, counts[i])) continue;
+        const PlPackImage &m = w.play.im[i];
+        pack_of[k] = packs.size();
+        packs.push_back(PlPackJob{ elig[k].rows, reinterpret_cast<uint8_t *>(base + m.ids), reinterpret_cast<uint8_t *>(base + m.rows), w.images[i].width, w.images[i].height,
+                                   elig[k].pitch, m.pitch, pli_min_depth(counts[i]), 0 });
+        pack_height = std::max(pack_height, w.images[i].height);
+    }
+    if (!packs.empty()) {
+        PL_CHECK(hipMemcpyAsync(base + w.play.jobs, packs.data(), sizeof(PlPackJob) * packs.size(), hipMemcpyHostToDevice, stream));
+        PL_CHECK(pl_launch_index_pack(reinterpret_cast<const PlPackJob *>(base + w.play.jobs), packs.size(), pack_height, stream));
+    }
     for (size_t k = 0; k < elig.size(); k++) PL_CHECK(hipMemcpyAsync(&records[k], elig[k].record, sizeof(PliRecord), hipMemcpyDeviceToHost, stream));
     PL_CHECK(hipStreamSynchronize(stream));
-    std::vector<pl_deflate_image> dz(elig.size());
-    std::vector<std::vector<unsigned char>> out(elig.size());
+    /* the candidates: the 8-bit rows of every eligible image (under "min": of those with min_depth 8), then the packed rows, a deflate call each */
+    std::vector<pl_deflate_image> dz, dzp(packs.size());
+    std::vector<size_t> dz_of(elig.size(), none);
+    std::vector<std::vector<unsigned char>> out(elig.size()), outp(packs.size());
     for (size_t k = 0; k < elig.size(); k++) {
         const size_t i = elig_who[k];
         if (records[k].entries != counts[i]) {
             std::fprintf(stderr, "pngloss_hip: indexed: image %zu has %u colours in its table, its counter says %u\n", i, records[k].entries, counts[i]);
             return PNGLOSS_HIP_ERROR;
         }
-        out[k].resize(pl_deflate_bound((w.images[i].width + 3) / 4, w.images[i].height));      /* (the bound is stated for 4-byte pixels: width index bytes are at most that many) */
-        dz[k] = deflate_image_of(elig[k].ids, elig[k].rows, elig[k].pitch, w.images[i].width, w.images[i].height, out[k].data(), out[k].size());
+        const size_t bound = pl_deflate_bound((w.images[i].width + 3) / 4, w.images[i].height);      /* (the bound is stated for 4-byte pixels: width index bytes are at most that many) */
+        if (pli_wants_indexed8(w.index_depth, counts[i])) {
+            out[k].resize(bound);
+            dz_of[k] = dz.size();
+            dz.push_back(deflate_image_of(elig[k].ids, elig[k].rows, elig[k].pitch, w.images[i].width, w.images[i].height, out[k].data(), out[k].size()));
+        }
+        if (pack_of[k] != none) {
+            const PlPackJob &pj = packs[pack_of[k]];
+            outp[pack_of[k]].resize(bound);
+            dzp[pack_of[k]] = deflate_image_of(pj.ids, pj.rows, pj.pitch, pli_packed_rowbytes(pj.width, pj.depth), pj.height, outp[pack_of[k]].data(), bound);
+        }
     }
-    const int rc = deflate_rc(pl_deflate_images(dz.data(), dz.size(), nullptr));
+    int rc = dz.empty() ? PNGLOSS_SUCCESS : deflate_rc(pl_deflate_images(dz.data(), dz.size(), nullptr));
+    if (rc == PNGLOSS_SUCCESS && !dzp.empty()) rc = deflate_rc(pl_deflate_images(dzp.data(), dzp.size(), nullptr));
     if (rc) return rc;
     for (size_t k = 0; k < elig.size(); k++) {
         const size_t i = elig_who[k];
         pngloss_hip_palette &p = ctx->palette[i];
-        p.indexed_bytes = dz[k].out_size;
-        if (!pli_keep_indexed(counts[i], p.indexed_bytes, p.truecolor_bytes, records[k].trns_entries) || dz[k].out_size > zs[i].capacity) continue;
+        pngloss_hip_index_depth &r = ctx->index_depth[i];
+        const pl_deflate_image *d8 = dz_of[k] != none ? &dz[dz_of[k]] : nullptr, *dp = pack_of[k] != none ? &dzp[pack_of[k]] : nullptr;
+        r.min_depth = pli_min_depth(counts[i]);
+        r.indexed8_bytes = d8 ? d8->out_size : 0;
+        r.packed_bytes = dp ? dp->out_size : 0;
+        p.indexed_bytes = pli_indexed_candidate(w.index_depth, counts[i], r.indexed8_bytes, r.packed_bytes);
+        const uint32_t depth = pli_keep_depth(w.index_depth, counts[i], r.indexed8_bytes, r.packed_bytes, p.truecolor_bytes, records[k].trns_entries);     /* (at "8": 8 iff pli_keep_indexed) */
+        const pl_deflate_image *kept = depth == 8 ? d8 : dp;
+        if (!depth || kept->out_size > zs[i].capacity) continue;
+        r.bit_depth = depth;
         p.entries = records[k].entries;
         p.trns_entries = records[k].trns_entries;
         for (uint32_t e = 0; e < p.entries; e++) {
@@ -220,8 +265,8 @@ int window_index(const HostWindow &w, const std::vector<size_t> &who)
             p.rgb[e][0] = (uint8_t)word; p.rgb[e][1] = (uint8_t)(word >> 8); p.rgb[e][2] = (uint8_t)(word >> 16);
             p.alpha[e] = (uint8_t)(word >> 24);
         }
-        std::memcpy(zs[i].data, out[k].data(), dz[k].out_size);
-        zstream_take(zs[i], dz[k]);
+        std::memcpy(zs[i].data, kept->out, kept->out_size);
+        zstream_take(zs[i], *kept);
         zs[i].color_type = 3;
     }
     return PNGLOSS_SUCCESS;
@@ -285,7 +330,9 @@ int batch_host_one(pngloss_hip_ctx *ctx, const pngloss_hip_host_image *images, s
         batch_dims(images, n, width, height);
         w.indexed = true;
         w.ilay = pl_index_layout(width, height, sizeof(PlIndexJob), sizeof(PliRecord));
-        rc = ctx->d_index.grow(w.ilay.total, 8);
+        w.index_depth = measure.index_depth;
+        if (w.index_depth != PLI_DEPTH_8) w.play = pl_index_pack_layout(width, height, w.ilay.total, sizeof(PlPackJob));
+        rc = ctx->d_index.grow(w.index_depth != PLI_DEPTH_8 ? w.play.total : w.ilay.total, 8);
     }
     if (rc == PNGLOSS_SUCCESS) rc = ensure_copy_stream(ctx);
     if (rc) return rc;

@@ -24,4 +24,18 @@ hipError_t pl_launch_index_count(const PlIndexJob *d_jobs, size_t n, uint64_t ma
 hipError_t pl_launch_index_palette(const PlIndexJob *d_jobs, size_t n, hipStream_t stream);
 hipError_t pl_launch_index_rows(const PlIndexJob *d_jobs, size_t n, uint32_t max_height, hipStream_t stream);
 
+/* Option "index_depth": one job = one eligible image with min_depth < 8, behind pl_index_rows.  pl_index_pack reads the 8-bit index rows and
+ * writes the rows packed at `depth`; the jobs of one launch may differ in depth. */
+struct PlPackJob {
+    const uint8_t *rows8;       /* device: PlIndexJob::rows, 16-byte aligned, `pitch8` bytes apart (a multiple of 16, >= width) */
+    uint8_t *ids;               /* device: height filter type bytes of the packed rows, pl_index_pack writes 0 into each */
+    uint8_t *rows;              /* device: height packed rows, `pitch` bytes apart; pitch is a multiple of 4 and >= 4 * pli_packed_dwords(width, depth) */
+    uint32_t width, height, pitch8, pitch;
+    uint32_t depth, reserved;   /* 1, 2 or 4 */
+};
+
+static_assert(sizeof(PlIndexJob) == 72 && sizeof(PlPackJob) == 48, "the job records as tests/c/index_depth_host.cpp lays them out (it cannot include this header: no HIP runtime there)");
+
+hipError_t pl_launch_index_pack(const PlPackJob *d_jobs, size_t n, uint32_t max_height, hipStream_t stream);
+
 #endif

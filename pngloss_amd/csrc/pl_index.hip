@@ -9,6 +9,9 @@
  *   pl_index_palette  one workgroup per eligible image: gathers the table's <= 256 words, rank-sorts them, writes the palette record and each
  *                     colour's index beside it in its slot
  *   pl_index_rows     eligible images: the table in LDS (8 KB), four lookups per lane packed into one dword store; one zero filter byte per row
+ *   pl_index_pack     option "index_depth" at "auto" or "min" only, eligible images of at most 16 colours: the 8-bit index rows packed at bit depth
+ *                     1, 2 or 4 (the job says which: one launch for a batch that mixes them), a lane one dword of a packed row from 16-byte
+ *                     loads; no table, no LDS; one zero filter byte per row
  *
  * No kernel waits on another workgroup: the only cross-workgroup traffic is the compare-and-swap on a slot and the relaxed counter.
  * No reference equivalent.
@@ -90,6 +93,27 @@ __global__ __launch_bounds__(kThreads) void pl_index_rows(const PlIndexJob *__re
     }
 }
 
+/* the rows of one job packed at depth D: a workgroup strides over the rows, a lane over the dwords of a packed row (256 lanes make 8192 / 4096 /
+ * 2048 pixels a trip at depth 1 / 2 / 4) */
+template <uint32_t D> __device__ __forceinline__ void pack_rows(const PlPackJob &j)
+{
+    const uint32_t dwords = pli_packed_dwords(j.width, D);                   /* dwords * 4 <= pitch: the tail's dword stays inside the row */
+    for (uint32_t y = blockIdx.x; y < j.height; y += gridDim.x) {
+        if (threadIdx.x == 0) j.ids[y] = 0;
+        const uint8_t *row8 = j.rows8 + (size_t)y * j.pitch8;
+        uint32_t *dst = reinterpret_cast<uint32_t *>(j.rows + (size_t)y * j.pitch);
+        for (uint32_t q = threadIdx.x; q < dwords; q += kThreads) dst[q] = pli_pack_lane<D>(row8, j.width, q);
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void pl_index_pack(const PlPackJob *__restrict__ jobs)
+{
+    const PlPackJob j = jobs[blockIdx.y];
+    if (j.depth == 1) pack_rows<1>(j);                /* (uniform for the workgroup: the job is blockIdx.y's) */
+    else if (j.depth == 2) pack_rows<2>(j);
+    else if (j.depth == 4) pack_rows<4>(j);
+}
+
 constexpr size_t kMaxImages = 65535;                /* gridDim.y */
 
 } // namespace
@@ -122,6 +146,17 @@ hipError_t pl_launch_index_rows(const PlIndexJob *d_jobs, size_t n, uint32_t max
         uint32_t blocks = max_height < 512 ? max_height : 512;
         if (blocks < 1) blocks = 1;
         hipLaunchKernelGGL(pl_index_rows, dim3(blocks, (unsigned)m), dim3(kThreads), 0, stream, d_jobs + first);
+    }
+    return hipGetLastError();
+}
+
+hipError_t pl_launch_index_pack(const PlPackJob *d_jobs, size_t n, uint32_t max_height, hipStream_t stream)
+{
+    for (size_t first = 0; first < n; first += kMaxImages) {
+        const size_t m = n - first < kMaxImages ? n - first : kMaxImages;
+        uint32_t blocks = max_height < 512 ? max_height : 512;
+        if (blocks < 1) blocks = 1;
+        hipLaunchKernelGGL(pl_index_pack, dim3(blocks, (unsigned)m), dim3(kThreads), 0, stream, d_jobs + first);
     }
     return hipGetLastError();
 }

@@ -8,7 +8,7 @@
  *   eligible       the image has pixels and 1 <= colours <= 256
  *   palette order  ascending by the word as a uint32: alpha most significant, then B, G, R -- entries that are not opaque come first, so the
  *                  tRNS chunk holds exactly the alphas of the first trns_entries entries
- *   index rows     colour type 3 at bit depth 8: per row a filter type byte 0 and `width` index bytes (depths 1 / 2 / 4 are not written)
+ *   index rows     colour type 3 at bit depth 8: per row a filter type byte 0 and `width` index bytes (depths 1 / 2 / 4: "the packed rows" below)
  *   decision       indexed is kept iff eligible and I + overhead < T (I, T: the complete zlib streams of the two encodings), a tie goes to truecolour;
  *                  overhead = 12 + 3 * entries + (trns_entries ? 12 + trns_entries : 0): the PLTE and tRNS chunks
  *
@@ -177,6 +177,105 @@ inline uint64_t pli_overhead(uint32_t entries, uint32_t trns_entries) { return 1
 inline bool pli_keep_indexed(uint32_t colors, uint64_t indexed_bytes, uint64_t truecolor_bytes, uint32_t trns_entries)
 {
     return colors >= 1 && colors <= PLI_MAX_COLORS && indexed_bytes + pli_overhead(colors, trns_entries) < truecolor_bytes;
+}
+
+/* ---- the packed rows: bit depths 1, 2 and 4 (option "index_depth", include/pngloss_hip_index_depth.h; restated with numpy in
+ * tests/util_index_depth.py) ----
+ *   min_depth(entries)  1 for 1..2 entries, 2 for 3..4, 4 for 5..16, 8 for 17..256 (0 for anything else: no palette)
+ *   packed scanline at depth d in {1, 2, 4}: the filter type byte 0, then ceil(width * d / 8) bytes; pixel x lies in byte x * d / 8 at the shift
+ *                       8 - d * (x % (8 / d) + 1) -- the leftmost pixel in the high bits, as PNG requires; the unused low bits of a row's last byte are 0
+ *   the palette, its order, tRNS and the overhead are the ones above, unchanged
+ * The packed rows are made from the 8-bit index rows pl_index_rows has written, not from the pixels: one thread makes one dword of a packed row, in
+ * memory order (first byte low), from 32 / 16 / 8 index bytes at depth 1 / 2 / 4.  Of an 8-bit row only the bytes up to its last dword are written,
+ * and only `width` of them are indices: everything behind `width` is masked here, never trusted. */
+
+PLI_HD uint32_t pli_min_depth(uint32_t entries)
+{
+    return entries < 1 || entries > PLI_MAX_COLORS ? 0u : entries <= 2 ? 1u : entries <= 4 ? 2u : entries <= 16 ? 4u : 8u;
+}
+
+/* four index bytes (pixel 0 in the low byte) as 4 * D bits of a packed row.  D = 1: a nibble, pixel 0 its high bit; D = 2: a byte, pixel 0 its
+ * high two bits -- the multiplications move every masked field to a place of its own, so nothing carries; D = 4: two bytes, the first one low */
+template <uint32_t D> PLI_HD uint32_t pli_pack_word(uint32_t w)
+{
+    static_assert(D == 1 || D == 2 || D == 4, "the packed depths");
+    if (D == 1) return ((w & 0x01010101u) * 0x80402010u) >> 28;
+    if (D == 2) return ((w & 0x03030303u) * 0x40100401u) >> 24;
+    const uint32_t t = w & 0x0F0F0F0Fu, u = (t << 4) | (t >> 8);
+    return (u & 0xFFu) | ((u >> 8) & 0xFF00u);
+}
+
+/* one dword of a packed row from the 32 / D index bytes in src[0 .. 8 / D): the first `valid` of them are pixels of the row, the others are masked */
+template <uint32_t D> PLI_HD uint32_t pli_pack_dword(const uint32_t *src, uint32_t valid)
+{
+    uint32_t out = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (uint32_t k = 0; k < 8 / D; k++) {
+        const uint32_t m = valid > 4 * k ? valid - 4 * k : 0u;
+        const uint32_t keep = m >= 4 ? ~0u : (1u << (8 * m)) - 1u;
+        out |= pli_pack_word<D>(src[k] & keep) << (D == 1 ? 8 * (k >> 1) + 4 * (1 - (k & 1)) : 4 * D * k);
+    }
+    return out;
+}
+
+/* dword q of the packed row of the 8-bit row `row8` (16-byte aligned, its pitch a multiple of 16 and >= width; q * 32 / D < width).  The index bytes
+ * come in 16-byte loads (8 at depth 4).  At depth 1 a thread has two of them, and the second may start behind the row's pitch -- the pitch is a
+ * multiple of 16, not of 32 --, so a load that starts at or behind `width` is left out: one that starts in front of it ends inside the pitch. */
+template <uint32_t D> PLI_HD uint32_t pli_pack_lane(const uint8_t *row8, uint32_t width, uint32_t q)
+{
+    constexpr uint32_t per = 32 / D, words = 8 / D, step = words < 4 ? words : 4;      /* dwords a load brings */
+    const uint32_t x = q * per, valid = width - x < per ? width - x : per;
+    uint32_t src[words];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (uint32_t g = 0; g < words; g += step) {
+        if (x + 4 * g < width) __builtin_memcpy(src + g, __builtin_assume_aligned(row8 + x + 4 * g, 4 * step), 4 * step);
+        else for (uint32_t k = 0; k < step; k++) src[g + k] = 0u;
+    }
+    return pli_pack_dword<D>(src, valid);
+}
+
+/* ... with the depth as a value */
+PLI_HD uint32_t pli_pack_lane_at(uint32_t depth, const uint8_t *row8, uint32_t width, uint32_t q)
+{
+    return depth == 1 ? pli_pack_lane<1>(row8, width, q) : depth == 2 ? pli_pack_lane<2>(row8, width, q) : pli_pack_lane<4>(row8, width, q);
+}
+
+/* dwords of a packed row that hold pixels, and its bytes as the deflate reads them */
+PLI_HD uint32_t pli_packed_dwords(uint32_t width, uint32_t depth) { return (uint32_t)(((uint64_t)width * depth + 31) / 32); }
+PLI_HD uint32_t pli_packed_rowbytes(uint32_t width, uint32_t depth) { return (uint32_t)(((uint64_t)width * depth + 7) / 8); }
+
+/* ---- which stream is kept under the option "index_depth" (host arithmetic; pli_keep_indexed above is the rule of "8") ----
+ *   candidates  T: the truecolour stream; I8: the 8-bit index rows; Ip: the rows packed at min_depth, for an eligible image with min_depth < 8
+ *   "8"         T against I8
+ *   "auto"      the smallest of T, I8 + overhead, Ip + overhead; a tie goes to the earlier one in that order
+ *   "min"       T against the indexed stream at min_depth alone (for 17..256 colours that is I8) */
+enum PliDepthMode : uint32_t { PLI_DEPTH_8 = 0, PLI_DEPTH_AUTO = 1, PLI_DEPTH_MIN = 2 };
+
+/* which indexed candidates an image of `colors` colours (257: more than 256) gets */
+inline bool pli_wants_packed(uint32_t mode, uint32_t colors) { return mode != PLI_DEPTH_8 && pli_min_depth(colors) >= 1 && pli_min_depth(colors) < 8; }
+inline bool pli_wants_indexed8(uint32_t mode, uint32_t colors) { return pli_min_depth(colors) >= 1 && (mode != PLI_DEPTH_MIN || pli_min_depth(colors) == 8); }
+
+/* the bit depth of the stream that is kept; 0: truecolour.  The size of a candidate the image did not get is not read. */
+inline uint32_t pli_keep_depth(uint32_t mode, uint32_t colors, uint64_t indexed8_bytes, uint64_t packed_bytes, uint64_t truecolor_bytes, uint32_t trns_entries)
+{
+    uint64_t best = truecolor_bytes;
+    uint32_t depth = 0;
+    const uint64_t overhead = pli_overhead(colors, trns_entries);
+    if (pli_wants_indexed8(mode, colors) && indexed8_bytes + overhead < best) { best = indexed8_bytes + overhead; depth = 8; }
+    if (pli_wants_packed(mode, colors) && packed_bytes + overhead < best) depth = pli_min_depth(colors);
+    return depth;
+}
+
+/* the indexed candidate that was compared with T (pngloss_hip_palette.indexed_bytes): the smaller one where there are two; 0 when not eligible */
+inline uint64_t pli_indexed_candidate(uint32_t mode, uint32_t colors, uint64_t indexed8_bytes, uint64_t packed_bytes)
+{
+    if (!pli_wants_packed(mode, colors)) return pli_wants_indexed8(mode, colors) ? indexed8_bytes : 0u;
+    if (!pli_wants_indexed8(mode, colors)) return packed_bytes;
+    return packed_bytes < indexed8_bytes ? packed_bytes : indexed8_bytes;
 }
 
 #endif

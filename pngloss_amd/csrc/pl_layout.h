@@ -1,6 +1,6 @@
 /*
  * pl_layout.h -- every carve-up of a buffer the host shim makes, as pure functions from sizes to offsets: the batch workspace of enqueue(), the
- * arena of a host window (batch_host_one), the keep arena of the distortion measurement, the tables of the SSIM measurement, the index workspace of the option "indexed", the quantiser's workspace and the job table and error lines of its dither pass, the read side's workspace and frame arena
+ * arena of a host window (batch_host_one), the keep arena of the distortion measurement, the tables of the SSIM measurement, the index workspace of the option "indexed" and the packed rows of "index_depth" behind it, the quantiser's workspace and the job table and error lines of its dither pass, the read side's workspace and frame arena
  * (png_decode_body), and the size a buffer is regrown to.
  * Internal.
  *
@@ -245,6 +245,37 @@ inline PlIndexLayout pl_index_layout(const std::vector<uint32_t> &width, const s
         const bool px = width[i] && height[i];
         m.table = l.tables + sizeof(uint64_t) * PLI_SLOTS * i;
         m.pitch = px ? (uint32_t)pl_align_up(width[i], 16) : 0;
+        m.ids = take(px ? height[i] : 0);
+        m.rows = take((size_t)m.pitch * (px ? height[i] : 0));
+    }
+    return l;
+}
+
+/* ================================================================================================ the packed index rows (option "index_depth": window_index) */
+
+/* Behind the index workspace, from `base` (pl_index_layout's total) on: the PlPackJob table, then per image with pixels the filter type bytes and
+ * the rows of its packed scanlines.  The depth of an image is known only after the batch has run, so the pitch is the one the widest packed depth
+ * needs -- ceil(width * 4 / 8) bytes, a multiple of 16 as the other scanline pitches -- and the rows of a shallower depth lie the same distance
+ * apart.  Every image gets its rows, for the reason every image gets its index rows. */
+struct PlPackImage { size_t ids, rows; uint32_t pitch; };
+struct PlPackLayout {
+    size_t jobs = 0, total = 0;
+    std::vector<PlPackImage> im;
+};
+
+/* job_bytes: sizeof(PlPackJob) */
+inline PlPackLayout pl_index_pack_layout(const std::vector<uint32_t> &width, const std::vector<uint32_t> &height, size_t base, size_t job_bytes)
+{
+    PlPackLayout l;
+    const size_t n = width.size(), n1 = n ? n : 1;
+    l.total = pl_align_up(base, PLL_ALIGN);
+    auto take = [&](size_t bytes) { size_t at = l.total; l.total = pl_align_up(l.total + bytes, PLL_ALIGN); return at; };
+    l.im.resize(n);
+    l.jobs = take(job_bytes * n1);
+    for (size_t i = 0; i < n; i++) {
+        PlPackImage &m = l.im[i];
+        const bool px = width[i] && height[i];
+        m.pitch = px ? (uint32_t)pl_align_up(((size_t)width[i] + 1) / 2, 16) : 0;
         m.ids = take(px ? height[i] : 0);
         m.rows = take((size_t)m.pitch * (px ? height[i] : 0));
     }

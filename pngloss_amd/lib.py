@@ -117,6 +117,15 @@ class Palette(C.Structure):
                     indexed_bytes=self.indexed_bytes, colors=self.colors)
 
 
+class IndexDepth(C.Structure):
+    """pngloss_hip_index_depth: which bit depth the option "index_depth" kept for one image (0: truecolour) and from which sizes.  min_depth: 1, 2,
+    4 or 8 for an eligible image, else 0; indexed8_bytes / packed_bytes: 0 where that candidate was not written."""
+    _fields_ = [("bit_depth", C.c_uint32), ("min_depth", C.c_uint32), ("indexed8_bytes", C.c_uint64), ("packed_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return dict(bit_depth=self.bit_depth, min_depth=self.min_depth, indexed8_bytes=self.indexed8_bytes, packed_bytes=self.packed_bytes)
+
+
 class QuantParams(C.Structure):
     """pngloss_hip_quant_params: max_colors (N, 2..256) and rounds (R, 0..64) of the colour quantiser.  include/pngloss_hip_quant.h states the rule."""
     _fields_ = [("max_colors", C.c_uint32), ("rounds", C.c_uint32)]
@@ -280,6 +289,14 @@ QUANT_SPACE_PROTOTYPES = {
                                                      C.POINTER(QuantTargetReport), C.c_void_p]),
     "pngloss_hip_multi_quantize_batch_host_target3": (C.c_int, [C.c_void_p, C.POINTER(HostImage), C.c_size_t, C.POINTER(QuantParams3), C.POINTER(QuantTarget),
                                                                 C.POINTER(QuantTargetReport)]),
+}
+
+#: ... and for include/pngloss_hip_index_depth.h, the bit depths of the indexed-colour write side (tests/test_index_depth_host.py holds them against
+#: that header)
+INDEX_DEPTH_STRUCTS = {"pngloss_hip_index_depth": IndexDepth}
+INDEX_DEPTH_PROTOTYPES = {
+    "pngloss_hip_last_index_depth": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(IndexDepth)]),
+    "pngloss_hip_multi_last_index_depth": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(IndexDepth)]),
 }
 
 
@@ -448,7 +465,7 @@ def hip_lib():
                     pass
             lib = _load(os.environ.get("PNGLOSS_HIP_LIBNAME", "libpngloss_hip.so"))
             for name, (ret, args) in {**PROTOTYPES, **INDEXED_PROTOTYPES, **QUANT_PROTOTYPES, **DITHER_PROTOTYPES, **QUANT_TARGET_PROTOTYPES,
-                                       **QUANT_SPACE_PROTOTYPES}.items():
+                                       **QUANT_SPACE_PROTOTYPES, **INDEX_DEPTH_PROTOTYPES}.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = ret, args
             _hip = lib
@@ -822,6 +839,12 @@ class HipContext:
         _check(self._lib.pngloss_hip_last_palette(self._ctx, index, C.byref(r)), "last_palette")
         return r
 
+    def index_depth(self, index=0):
+        """pngloss_hip_last_index_depth: the IndexDepth of image `index` of the last finished run_host_zlib; the rules of palette()."""
+        r = IndexDepth()
+        _check(self._lib.pngloss_hip_last_index_depth(self._ctx, index, C.byref(r)), "last_index_depth")
+        return r
+
     def quantize(self, images, max_colors=256, rounds=8, stream=0, dither=None, space=None):
         """pngloss_hip_quantize_batch: images as for run() (device-resident RGBA8), quantised in place to at most max_colors colours each.
         Synchronous.  Returns (images, reports): the tuples handed in, whose pixels are the quantised ones now, and one report dict per image
@@ -971,6 +994,12 @@ class HipMulti:
         """pngloss_hip_multi_last_palette: the Palette of arrays[index] of the last run_host_zlib, whichever context it went to"""
         r = Palette()
         _check(self._lib.pngloss_hip_multi_last_palette(self._m, index, C.byref(r)), "multi_last_palette")
+        return r
+
+    def index_depth(self, index=0):
+        """pngloss_hip_multi_last_index_depth: the IndexDepth of arrays[index] of the last run_host_zlib, whichever context it went to"""
+        r = IndexDepth()
+        _check(self._lib.pngloss_hip_multi_last_index_depth(self._m, index, C.byref(r)), "multi_last_index_depth")
         return r
 
     def quantize_host(self, arrays, max_colors=256, rounds=8, dither=None, space=None):
